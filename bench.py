@@ -7,7 +7,13 @@ inputs resident in HBM.  Multi-GPU: one process per GPU (torchrun), the global b
 detail_tts_amd.sharding with no data-path collective, one RCCL broadcast of the packed weight blob at start-up (weak scaling).
 Prints ONE JSON line on rank 0.
 
+A plain run sets up, warms up, times --steps steps and prints the headline line (`value`, `ms_per_step`, ...).  --full adds what the
+headline does not need: the per-stage timings, launch profiling and board power over the timed region, the pipelined == blocking
+check, the rooflines, the extra workloads (un-pipelined, exact fp32, batch 1, ragged, long-form) and the CPU baseline.
+--dump-outputs DIR writes the last timed step's waveforms and lengths as DIR/<name>.npy (float32 / float64).
+
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
 """
 import argparse
 import hashlib
@@ -208,6 +214,14 @@ def launch_ranks(n):
     return subprocess.call(cmd, env=env)
 
 
+def dump_outputs(out_dir, wav, lens, suffix=""):
+    """--dump-outputs: what a caller of the timed path receives from its last step - the waveforms [B, 1, samples] (float32) and the
+    valid length of each in samples (float64) - as <out_dir>/wav<suffix>.npy and <out_dir>/lengths<suffix>.npy (8 x 9.98 s: 7.7 MB)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"wav{suffix}.npy"), wav.float().cpu().numpy())
+    np.save(os.path.join(out_dir, f"lengths{suffix}.npy"), np.asarray(lens, np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -215,10 +229,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=8, help="utterances per GPU")
     ap.add_argument("--codes", type=int, default=N_CODES, help="codes per utterance (234 = the BASELINE config; smaller only for dry runs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--full", action="store_true", help="also the per-stage / per-kernel / power figures, the checks, the extra "
+                    "workloads and the CPU baseline (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--probe-out", help="write <path>.rank<k>.json: hashes of the bound weights and of a shared probe utterance")
     args = ap.parse_args()
     n_codes = args.codes
+    full = args.full
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))         # `python bench.py --gpus N`: become N ranks (one per GPU) under torch.distributed.run
@@ -334,19 +352,21 @@ def main():
     torch.cuda.synchronize()
     if multi:
         dist.barrier()
-    model.stage_ms = {}
-    step(99, pipelined=False)                # one untimed, un-pipelined pass with per-stage hipEvents (adds a sync, so not part of the timed region)
-    stage_ms = {k: round(v, 2) for k, v in model.stage_ms.items()}
-    model.stage_ms = None
-    # per-launch hipEvents on the launch streams, live over the timed region: every launch of every PROF_EVERY-th sampling step of each
-    # batch (all streams, so the union of the intervals keeps its meaning) - bracketing all 50 steps costs 2 % of the step
+    stage_ms = {}
     PROF_EVERY = int(os.environ.get("DTTS_BENCH_PROF_EVERY", "5"))
-    model.rt.profile_sampling(PROF_EVERY)
-    model.rt.profile_enable(os.environ.get("DTTS_BENCH_NO_PROF") != "1")
+    if full:
+        model.stage_ms = {}
+        step(99, pipelined=False)                # one untimed, un-pipelined pass with per-stage hipEvents (adds a sync, so not part of the timed region)
+        stage_ms = {k: round(v, 2) for k, v in model.stage_ms.items()}
+        model.stage_ms = None
+        # per-launch hipEvents on the launch streams, live over the timed region: every launch of every PROF_EVERY-th sampling step of each
+        # batch (all streams, so the union of the intervals keeps its meaning) - bracketing all 50 steps costs 2 % of the step
+        model.rt.profile_sampling(PROF_EVERY)
+        model.rt.profile_enable(os.environ.get("DTTS_BENCH_NO_PROF") != "1")
     torch.cuda.synchronize()
     if multi:
         dist.barrier()
-    power = PowerSampler(local).start()
+    power = PowerSampler(local).start() if full else None
     t0 = time.perf_counter()
     outs = run_steps(100, args.steps)
     wavs, lens = [o[0] for o in outs], outs[-1][1]
@@ -354,18 +374,22 @@ def main():
     if multi:
         dist.barrier()
     dt = time.perf_counter() - t0
-    power = power.stop()
+    power = power.stop() if power else None
     if power:       # the step's ENERGY: at the board's power limit a kernel costs the step its joules, not its stand-alone duration
         power["energy_J_per_step"] = round(power["mean_W"] * dt / args.steps, 1)
         power["J_per_audio_s"] = round(power["mean_W"] * dt / (args.steps * B * n_codes * 1024 / 24000.0), 3)
-    prof = model.rt.profile_report()
-    model.rt.profile_enable(False)
-    model.rt.profile_sampling(1)
-    assert all(l == n_codes * 1024 for l in lens) and all(bool(torch.isfinite(w).all()) for w in wavs)
+    prof = []
+    if full:
+        prof = model.rt.profile_report()
+        model.rt.profile_enable(False)
+        model.rt.profile_sampling(1)
+        assert all(l == n_codes * 1024 for l in lens) and all(bool(torch.isfinite(w).all()) for w in wavs)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, wavs[-1], lens, "" if rank == 0 else f"_rank{rank}")
     # the last pipelined waveform of the timed region against ONE blocking infer() of the same request (untimed): three requests' stages
     # shared the chip while it was made (tests/test_gpu_hazard.py holds eight requests to this bit for bit under the signal weights)
     pipelined_equals_blocking = None
-    if pipeline and os.environ.get("DTTS_BENCH_NO_EXTRA") != "1":
+    if full and pipeline and os.environ.get("DTTS_BENCH_NO_EXTRA") != "1":
         ref_wav = model.infer(text, tl, refer, rl, batch=True, seed=1234 + 100 + args.steps - 1, sample_ids=sample_ids,
                               max_generate_length=n_codes + 1, suppress_eos=True)
         pipelined_equals_blocking = bool(torch.equal(ref_wav, wavs[-1]))
@@ -373,7 +397,7 @@ def main():
     del wavs
     # stage C alone under the all-kernel profiler (untimed): TFLOP/s and algorithmic GB/s of the vocoder stage
     voc = None
-    if rank == 0 and os.environ.get("DTTS_BENCH_NO_PROF") != "1":
+    if full and rank == 0 and os.environ.get("DTTS_BENCH_NO_PROF") != "1":
         mel = torch.from_numpy((np.random.RandomState(5).randn(B, 128, 4 * n_codes) * 2 - 5).astype(np.float32)).to(dev)
         model.rt.vocoder(mel, 1, sample_ids)
         model.rt.profile_enable(2)
@@ -394,7 +418,7 @@ def main():
                        "stage against the fp32 MFMA peak"}
     # ---- extra measurements of the SAME run (untimed region, rank 0, N = 1 only): what the headline number is NOT --------------------
     extra = {}
-    if world == 1 and os.environ.get("DTTS_BENCH_NO_EXTRA") != "1":
+    if full and world == 1 and os.environ.get("DTTS_BENCH_NO_EXTRA") != "1":
         def timed(fn, n):
             torch.cuda.synchronize()
             t = time.perf_counter()
@@ -588,19 +612,22 @@ def main():
                                   "batch i + 1 (SynthesizerTrn.infer_stream)") if pipeline else
                                  ("stage C of batch i on a second HIP stream under the GPT decode of batch i + 1" if overlap else "none")},
         "rank_ms_per_step": rank_ms, "weight_broadcast": bcast,
-        "stage_ms": stage_ms,
-        "pipelined_equals_blocking": pipelined_equals_blocking,
-        "power": power,
-        **extra,
-        "roofline": roof,
-        "roofline_attention": roof_att,
-        "roofline_decode": roof_dec,
-        "roofline_vocoder": voc,
-        "kernels": sorted([{"name": p["name"], "launches": p["launches"], "ms": round(p["total_ms"], 2),
-                            "busy_ms": round(p["union_ms"], 2),
-                            "tflops": round(p["flops"] / max(p["union_ms"], 1e-9) / 1e9, 2)} for p in prof], key=lambda k: -k["ms"])[:8],
     }
-    if not args.no_cpu_baseline and world == 1:          # the CPU baseline is a 1-GPU line item (rank 0 at N = 1 only)
+    if full:
+        out.update({
+            "stage_ms": stage_ms,
+            "pipelined_equals_blocking": pipelined_equals_blocking,
+            "power": power,
+            **extra,
+            "roofline": roof,
+            "roofline_attention": roof_att,
+            "roofline_decode": roof_dec,
+            "roofline_vocoder": voc,
+            "kernels": sorted([{"name": p["name"], "launches": p["launches"], "ms": round(p["total_ms"], 2),
+                                "busy_ms": round(p["union_ms"], 2),
+                                "tflops": round(p["flops"] / max(p["union_ms"], 1e-9) / 1e9, 2)} for p in prof], key=lambda k: -k["ms"])[:8],
+        })
+    if full and not args.no_cpu_baseline and world == 1:          # the CPU baseline is a 1-GPU line item (rank 0 at N = 1 only)
         out["cpu_baseline"] = cpu_baseline(W)
     print(json.dumps(out))
     if multi:

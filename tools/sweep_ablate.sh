@@ -8,19 +8,20 @@
 #   exit        DTTS_GPT_TOKEN_ABLATE=4: the launch alone (128 workgroups x 160 KB LDS acquired and released at once)
 #   chain       DTTS_GPT_TOKEN_KERNEL=0: the 53-launch chain
 REPS="${1:-2}"
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}
+mkdir -p $OUT
 for rep in $(seq 1 $REPS); do
   for cfg in base no_weights no_wait neither exit chain; do
     case $cfg in
       base) E="DTTS_X=0";; no_weights) E="DTTS_GPT_TOKEN_ABLATE=1";; no_wait) E="DTTS_GPT_TOKEN_ABLATE=2";; neither) E="DTTS_GPT_TOKEN_ABLATE=3";;
       exit) E="DTTS_GPT_TOKEN_ABLATE=4";; chain) E="DTTS_GPT_TOKEN_KERNEL=0";;
     esac
-    env $E DTTS_BENCH_NO_EXTRA=1 python bench.py --steps ${STEPS:-8} --warmup ${WARMUP:-3} --no-cpu-baseline > gpurun_out/abl_${cfg}_$rep.json 2> gpurun_out/abl_${cfg}_$rep.err
+    env $E DTTS_BENCH_NO_EXTRA=1 python bench.py --full --steps ${STEPS:-8} --warmup ${WARMUP:-3} --no-cpu-baseline > $OUT/abl_${cfg}_$rep.json 2> $OUT/abl_${cfg}_$rep.err
     python - "$cfg" "$rep" <<PY
 import json, sys
 c, r = sys.argv[1:]
 try:
-    d = json.loads(open(f"gpurun_out/abl_{c}_{r}.json").read().strip().splitlines()[-1])
+    d = json.loads(open(f"$OUT/abl_{c}_{r}.json").read().strip().splitlines()[-1])
     p = d.get("power") or {}
     print(f"{c:11s} rep={r}: {d['ms_per_step']:7.2f} ms/step, stage-A alone {d['stage_ms'].get('gpt_decode')} ms, diff_sample alone {d['stage_ms'].get('diff_sample')} ms, "
           f"{p.get('mean_W')} W, {p.get('mean_sclk_MHz')} MHz, {p.get('energy_J_per_step')} J/step")
