@@ -76,6 +76,14 @@ SIGNATURES = {
     "dtts_diff_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dtts_diff_sample": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_ulonglong, c_int_p, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "dtts_diff_schedule": (C.c_int, [C.c_void_p, c_int_p, C.c_int, c_int_p, C.c_void_p]),
+    "dtts_diff_schedule_coefs": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_float_p, C.c_int, c_int_p]),
+    "dtts_diff_sample_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_ulonglong,
+                                      c_int_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "dtts_diff_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int,
+                                 C.c_ulonglong, c_int_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dtts_diff_forward_t": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_void_p]),
     "dtts_vocoder": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_ulonglong, c_int_p, C.c_float, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "dtts_vocoder_stream": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_ulonglong, c_int_p, C.c_float, C.c_void_p,

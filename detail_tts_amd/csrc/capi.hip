@@ -295,6 +295,43 @@ int dtts_diff_sample(dtts_handle* h, const float* code_emb, const int* lens, int
     DTTS_API_END(h)
 }
 
+int dtts_diff_schedule(dtts_handle* h, const int* timesteps, int n, int* id_out, void* stream) {
+    DTTS_API_BEGIN
+    DTTS_REQUIRE(id_out, "id_out");
+    *id_out = h->m->diff_schedule(timesteps, n, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_diff_schedule_coefs(dtts_handle* h, int id, int* tmap, float* coefs, int cap, int* n_out) {
+    DTTS_API_BEGIN
+    const int n = h->m->diff_schedule_info(id, tmap, coefs, cap);
+    if (n_out) *n_out = n;
+    DTTS_API_END(h)
+}
+
+int dtts_diff_sample_ex(dtts_handle* h, int id, int sampler, float eta, const float* code_emb, const int* lens, int B, int T,
+                        unsigned long long seed, const int* sample_ids, int n_steps, const float* x_init, const float* step_noise,
+                        float* mel_out, int denorm, void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_sample_ex(id, sampler, eta, code_emb, lens, B, T, seed, sample_ids, n_steps, x_init, step_noise, mel_out, denorm,
+                         (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_diff_step(dtts_handle* h, int id, int sampler, float eta, float* x, const float* code_emb, const int* lens, int B, int T,
+                   int step, unsigned long long seed, const int* sample_ids, const float* noise, float* x0_out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_step(id, sampler, eta, x, code_emb, lens, B, T, step, seed, sample_ids, noise, x0_out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_diff_forward_t(dtts_handle* h, const float* x, const float* code_emb, const int* lens, int B, int T, int timestep,
+                        int cond_free, float* out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_forward_t(x, code_emb, lens, B, T, timestep, cond_free, out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
 int dtts_vocoder(dtts_handle* h, const float* mel, const int* lens, int B, int T, unsigned long long seed, const int* sample_ids,
                  float noise_scale, const float* noise_override, float* wav, float* trace_z, void* stream) {
     DTTS_API_BEGIN

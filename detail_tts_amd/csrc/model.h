@@ -1,6 +1,7 @@
 // Host-side runtime of libdetail_hip.so: weight binding, workspace, stage orchestration.
 // Everything here enqueues work on the caller's HIP stream; no hidden synchronisation except
-// workspace growth (hipMalloc) which only happens when a call needs more memory than any before it.
+// workspace growth (hipMalloc) which only happens when a call needs more memory than any before it, and the schedule cache
+// (diff_schedule: hipMalloc of a new schedule's tables; an eviction waits for the last launch that read the evicted tables).
 #pragma once
 #include <map>
 #include <memory>
@@ -132,6 +133,23 @@ private:
 };
 Arena* arena_override();     // the calling thread's stand-in (nullptr: none)
 
+// A sampling schedule: SpacedDiffusion(use_timesteps = tmap, linear betas over cfg.diff_trained_steps) (vqvae/utils/diffusion.py:1172-1220).
+// The coefficient tables are computed in float64 on the host and cast to fp32; ss_table holds every ResBlock's AdaGN scale / shift
+// at every step of the schedule: emb_layers(time_embed(sinusoid(tmap[i]))) (vqvae/diff_model.py:294, 108).
+struct Schedule {
+    int id = 0;                           // 0: the default (cfg.diff_steps) schedule built at bind
+    std::vector<int> tmap;                // model timesteps of the spaced steps, ascending (timestep_map)
+    std::vector<DiffStepCoefs> p;         // ancestral sampler (p_sample)
+    std::vector<float> ac, ac_prev;       // fp32 alphas_cumprod / alphas_cumprod_prev (DDIM: the eta-dependent terms are per call)
+    float cfk_k = 0.f;
+    const float* ss_table = nullptr;      // [n_resblocks][2C][n]
+    int n = 0;
+    void* mem = nullptr;                  // owned device memory (cached schedules; the default one lives in the bind-time arena)
+    hipEvent_t used = nullptr;            // recorded after every call that read ss_table: an eviction waits for it
+    ~Schedule();
+    DdimStepCoefs ddim(int i, float eta) const;
+};
+
 class Model {
 public:
     Model(const dtts_config& cfg, int device);
@@ -148,6 +166,20 @@ public:
                       float* out, hipStream_t s);
     void diff_sample(const float* code_emb, const int* lens_host, int B, int T, unsigned long long seed, const int* sample_ids_host,
                      int n_steps, const float* x_init, const float* step_noise, float* mel_out, int denorm, hipStream_t s);
+    // any schedule (id from diff_schedule) and sampler (0 = ancestral p_sample, 1 = DDIM with `eta`); diff_sample == diff_sample_ex(0, 0, 0)
+    void diff_sample_ex(int sched_id, int sampler, float eta, const float* code_emb, const int* lens_host, int B, int T,
+                        unsigned long long seed, const int* sample_ids_host, int n_steps, const float* x_init, const float* step_noise,
+                        float* mel_out, int denorm, hipStream_t s);
+    // one sampler step of schedule `sched_id` on x in place (unit entry of the sampler parity tests)
+    void diff_step(int sched_id, int sampler, float eta, float* x, const float* code_emb, const int* lens_host, int B, int T, int step,
+                   unsigned long long seed, const int* sample_ids_host, const float* noise, float* x0_out, hipStream_t s);
+    // DiffusionTts.forward at any model timestep in [0, diff_trained_steps): default-schedule timesteps take their step of that schedule
+    void diff_forward_t(const float* x, const float* code_emb, const int* lens_host, int B, int T, int timestep, int cond_free,
+                        float* out, hipStream_t s);
+    // the schedule of these model timesteps (any order, duplicates ignored): built on s on first use, then cached; returns its id
+    int diff_schedule(const int* timesteps, int n, hipStream_t s);
+    // host copy of a schedule: tmap[n]; coefs: per step {sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, min_log, max_log, cfk, ac, ac_prev}
+    int diff_schedule_info(int sched_id, int* tmap, float* coefs, int cap);
     // one p_sample at `step` on x in place (unit entry of the sampler parity tests)
     void diff_p_sample(float* x, const float* code_emb, const int* lens_host, int B, int T, int step, unsigned long long seed,
                        const int* sample_ids_host, const float* noise, float* x0_out, hipStream_t s);
@@ -279,7 +311,7 @@ private:
     };
     void attention_block(const AttnBlockW& w, const float* x, float* y, float* qkv, float* att, float* ab, const int* lens, int B,
                          int T, int Ta, hipStream_t s, void* xs = nullptr, GnFuse* f = nullptr, const GnNext* next = nullptr);
-    void res_block_fwd(const ResBlockW& w, const float* x, float* h1, float* y, float* ab, const int* lens, int B, int T, int Ta,
+    void res_block_fwd(const Schedule& sc, const ResBlockW& w, const float* x, float* h1, float* y, float* ab, const int* lens, int B, int T, int Ta,
                        int step, hipStream_t s, void* xs = nullptr, const int* step_idx = nullptr, GnFuse* f = nullptr,
                        const GnNext* next = nullptr);
     // fused-GroupNorm plumbing: per launch stream an exchange buffer (zeroed when (re)allocated; only ever holds tags of earlier
@@ -299,12 +331,12 @@ private:
     bool use_x3() const;
     // cbuf0: [B + Nu, C, T] = B conditional code embeddings followed by Nu unconditional inputs (one per distinct length)
     // integ (optional): [B + Nu, C, T] outputs of the conditioning_timestep_integrator for this step (precompute_integrator)
-    void diff_forward_pair(const float* x, const float* cbuf0, const int* lens2, const int* lens_i, const int* umap, int B, int Nu,
+    void diff_forward_pair(const Schedule& sc, const float* x, const float* cbuf0, const int* lens2, const int* lens_i, const int* umap, int B, int Nu,
                            int T, int step, float* out2, hipStream_t s, const float* integ = nullptr);
     // The integrator sees (code embedding | unconditioned embedding, timestep) only - never x_t - so its output for every sampling
     // step is known before the loop starts: steps are evaluated J at a time as one batch of J*(B+Nu) samples, each at its own step.
     // ready != null: only the first chunk runs on s, the later ones on si_; (first step, event) per later chunk is appended to *ready
-    void precompute_integrator(const float* cbuf0, const int* lens_i_host, int B, int Nu, int T, const std::vector<int>& steps,
+    void precompute_integrator(const Schedule& sc, const float* cbuf0, const int* lens_i_host, int B, int Nu, int T, const std::vector<int>& steps,
                                float* integ_all, hipStream_t s, std::vector<std::pair<int, hipEvent_t>>* ready = nullptr);
     struct PairPlan { const int *lens2, *lens_i, *umap; int Nu; std::vector<int> ulen; };
     PairPlan plan_pair(const int* lens_host, int B, int T, hipStream_t s);
@@ -318,10 +350,17 @@ private:
     std::vector<AttnBlockW> latcond_, ctx_;
     PackedConv inp_block_, integ1_, integ2_, out_conv_, latcond0_, ctx0_, ctx1_, te0_, te2_;
     const float *out_gn_g_ = nullptr, *out_gn_b_ = nullptr, *code_gn_g_ = nullptr, *code_gn_b_ = nullptr, *uncond_ = nullptr;
-    float* ss_table_ = nullptr;      // [n_resblocks][2C][NS]
-    int n_steps_ = 0;
-    std::vector<int> timestep_map_;
-    std::vector<DiffStepCoefs> step_coefs_;
+    int n_resblocks_ = 0;
+    Schedule sched0_;                // the default schedule (cfg.diff_steps), tables in persist_
+    // cached schedules, most recently used first; at most MAX_SCHEDULES (an N = 200 schedule is ~20 MB at 1024 channels)
+    static constexpr size_t MAX_SCHEDULES = 8;
+    std::vector<std::unique_ptr<Schedule>> sched_cache_;
+    int sched_next_id_ = 1;
+    std::mutex sched_mu_;
+    Schedule& schedule(int id);
+    void diff_forward_s(Schedule& sc, const float* x, const float* code_emb, const int* lens_host, int B, int T, int step, int cond_free,
+                        float* out, hipStream_t s);
+    void build_ss_table(const std::vector<int>& tmap, float* ss_table, float* scratch, int* ts_dev, hipStream_t s);
 
     // vocoder
     MelStyleW ref_enc_, gpt_cond_;

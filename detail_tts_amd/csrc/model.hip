@@ -331,7 +331,23 @@ void Model::run_conv(const PackedConv& pc, ConvParams p, hipStream_t s) const {
 }
 
 // ---- diffusion schedule (float64 on the host, cast to fp32 on use: vqvae/utils/diffusion.py:179-228, 1181-1195, 1315)
-static void make_schedule(int trained, int steps, float cfk_k, std::vector<int>& tmap, std::vector<DiffStepCoefs>& coefs) {
+// space_timesteps(trained, [steps])  (vqvae/utils/diffusion.py:1223-1272)
+static std::vector<int> space_steps(int trained, int steps) {
+    std::vector<char> use(trained, 0);
+    const double frac = steps <= 1 ? 1.0 : (double)(trained - 1) / (double)(steps - 1);
+    double cur = 0.0;
+    for (int i = 0; i < steps; ++i) {
+        use[(int)std::nearbyint(cur)] = 1;   // Python round(): half to even == nearbyint in the default mode
+        cur += frac;
+    }
+    std::vector<int> tmap;
+    for (int i = 0; i < trained; ++i)
+        if (use[i]) tmap.push_back(i);
+    return tmap;
+}
+
+// the spaced schedule of the model timesteps `tmap` (ascending, distinct, in [0, trained))
+static void make_schedule(int trained, const std::vector<int>& tmap, float cfk_k, Schedule& sc) {
     std::vector<double> betas(trained), ac(trained);
     const double scale = 1000.0 / trained, b0 = scale * 0.0001, b1 = scale * 0.02;
     double prod = 1.0;
@@ -340,23 +356,12 @@ static void make_schedule(int trained, int steps, float cfk_k, std::vector<int>&
         prod *= (1.0 - betas[i]);
         ac[i] = prod;
     }
-    // space_timesteps(trained, [steps])  (vqvae/utils/diffusion.py:1223-1272)
-    std::vector<char> use(trained, 0);
-    const double frac = steps <= 1 ? 1.0 : (double)(trained - 1) / (double)(steps - 1);
-    double cur = 0.0;
-    for (int i = 0; i < steps; ++i) {
-        use[(int)std::nearbyint(cur)] = 1;   // Python round(): half to even == nearbyint in the default mode
-        cur += frac;
-    }
-    tmap.clear();
     std::vector<double> nb;
     double last = 1.0;
-    for (int i = 0; i < trained; ++i)
-        if (use[i]) {
-            nb.push_back(1.0 - ac[i] / last);
-            last = ac[i];
-            tmap.push_back(i);
-        }
+    for (int t : tmap) {
+        nb.push_back(1.0 - ac[t] / last);
+        last = ac[t];
+    }
     const int n = (int)nb.size();
     std::vector<double> acp(n), acp_prev(n), post_var(n);
     prod = 1.0;
@@ -366,23 +371,148 @@ static void make_schedule(int trained, int steps, float cfk_k, std::vector<int>&
         acp[i] = prod;
     }
     for (int i = 0; i < n; ++i) post_var[i] = nb[i] * (1.0 - acp_prev[i]) / (1.0 - acp[i]);
-    coefs.resize(n);
+    sc.tmap = tmap;
+    sc.n = n;
+    sc.cfk_k = cfk_k;
+    sc.p.resize(n);
+    sc.ac.resize(n);
+    sc.ac_prev.resize(n);
     for (int i = 0; i < n; ++i) {
         DiffStepCoefs k;
         k.sqrt_recip_ac = (float)std::sqrt(1.0 / acp[i]);
         k.sqrt_recipm1_ac = (float)std::sqrt(1.0 / acp[i] - 1.0);
         k.coef1 = (float)(nb[i] * std::sqrt(acp_prev[i]) / (1.0 - acp[i]));
         k.coef2 = (float)((1.0 - acp_prev[i]) * std::sqrt(1.0 - nb[i]) / (1.0 - acp[i]));
-        k.min_log = (float)std::log(i == 0 ? post_var[1] : post_var[i]);
+        // posterior_log_variance_clipped; a 1-step schedule has no post_var[1] (the reference cannot build one) and never uses it
+        k.min_log = (float)std::log(i == 0 ? post_var[n > 1 ? 1 : 0] : post_var[i]);
         k.max_log = (float)std::log(nb[i]);
         k.cfk = (float)(cfk_k * (1.0 - (double)i / (double)n));
         k.nonzero = i != 0;
-        coefs[i] = k;
+        sc.p[i] = k;
+        sc.ac[i] = (float)acp[i];
+        sc.ac_prev[i] = (float)acp_prev[i];
     }
+}
+
+// ddim_sample's scalars (vqvae/utils/diffusion.py:773-777) in fp32, as the reference evaluates them on fp32 tensors
+DdimStepCoefs Schedule::ddim(int i, float eta) const {
+    DdimStepCoefs k;
+    k.sqrt_recip_ac = p[i].sqrt_recip_ac;
+    k.sqrt_recipm1_ac = p[i].sqrt_recipm1_ac;
+    k.cfk = p[i].cfk;
+    const float a = ac[i], ap = ac_prev[i];
+    k.sigma = eta * std::sqrt((1.f - ap) / (1.f - a)) * std::sqrt(1.f - a / ap);
+    k.sqrt_ac_prev = std::sqrt(ap);
+    k.dir = std::sqrt(1.f - ap - k.sigma * k.sigma);
+    k.nonzero = i != 0;
+    return k;
+}
+
+Schedule::~Schedule() {
+    if (used) (void)hipEventSynchronize(used);
+    if (mem) (void)hipFree(mem);
+    if (used) (void)hipEventDestroy(used);
+}
+
+// AdaGN tables of the schedule: t_emb = time_embed(sinusoid(ts)) for every sampling step, then every ResBlock's
+// emb_layers (SiLU -> Linear) -> ss_table[rb][2C][NS]   (vqvae/diff_model.py:294, 108).  scratch: 3 C NS floats
+void Model::build_ss_table(const std::vector<int>& tmap, float* ss_table, float* scratch, int* ts_dev, hipStream_t s) {
+    const int C = cfg.diff_channels, NS = (int)tmap.size();
+    float* sinus = scratch;
+    float* t1 = scratch + (size_t)C * NS;
+    float* temb = scratch + (size_t)2 * C * NS;
+    DTTS_CHECK_HIP(hipMemcpyAsync(ts_dev, tmap.data(), sizeof(int) * NS, hipMemcpyHostToDevice, s));
+    launch_timestep_sinusoid(ts_dev, NS, C, sinus, s);
+    ConvParams p;
+    p.B = 1;
+    p.Tin = NS;
+    p.Nout = NS;
+    p.x_cs = NS;
+    p.y_cs = NS;
+    p.x = sinus;
+    p.y = t1;
+    p.epi_act = ACT_SILU;
+    run_conv(te0_, p, s);
+    p.x = t1;
+    p.y = temb;
+    p.epi_act = ACT_NONE;
+    run_conv(te2_, p, s);
+    auto emb_of = [&](const ResBlockW& rb) {
+        ConvParams q;
+        q.B = 1;
+        q.Tin = NS;
+        q.Nout = NS;
+        q.x_cs = NS;
+        q.y_cs = NS;
+        q.x = temb;
+        q.pro_act = ACT_SILU;
+        q.y = ss_table + (size_t)rb.index * 2 * C * NS;
+        run_conv(rb.emb, q, s);
+    };
+    for (auto& l : integ_) emb_of(l.rb);
+    for (auto& l : layers_) emb_of(l.rb);
+    for (auto& r : tail_) emb_of(r);
+}
+
+Schedule& Model::schedule(int id) {
+    if (id == 0) return sched0_;
+    std::lock_guard<std::mutex> lk(sched_mu_);
+    for (auto& e : sched_cache_)
+        if (e->id == id) return *e;
+    throw Error(-1, "diffusion schedule " + std::to_string(id) + " is not cached (evicted or never built): call dtts_diff_schedule again");
+}
+
+int Model::diff_schedule(const int* timesteps, int n, hipStream_t s) {
+    DTTS_REQUIRE(bound_ && sched0_.n > 0, "diffusion weights not bound");
+    DTTS_REQUIRE(timesteps && n >= 1, "diff_schedule: empty timestep list");
+    const int trained = cfg.diff_trained_steps;
+    std::vector<int> tmap(timesteps, timesteps + n);
+    for (int t : tmap) DTTS_REQUIRE(t >= 0 && t < trained, "diff_schedule: timestep out of [0, diff_trained_steps)");
+    std::sort(tmap.begin(), tmap.end());
+    tmap.erase(std::unique(tmap.begin(), tmap.end()), tmap.end());
+    if (tmap == sched0_.tmap) return 0;
+    std::lock_guard<std::mutex> lk(sched_mu_);
+    for (size_t k = 0; k < sched_cache_.size(); ++k)
+        if (sched_cache_[k]->tmap == tmap) {
+            std::rotate(sched_cache_.begin(), sched_cache_.begin() + k, sched_cache_.begin() + k + 1);   // most recently used first
+            return sched_cache_[0]->id;
+        }
+    // evict the least recently used; its destructor waits for the last launch that read its table
+    while (sched_cache_.size() >= MAX_SCHEDULES) sched_cache_.pop_back();
+    auto sc = std::make_unique<Schedule>();
+    make_schedule(trained, tmap, cfg.cond_free_k, *sc);
+    const int C = cfg.diff_channels, NS = sc->n;
+    const size_t fl = (size_t)n_resblocks_ * 2 * C * NS;
+    DTTS_CHECK_HIP(hipMalloc(&sc->mem, sizeof(float) * (fl + 3 * (size_t)C * NS) + sizeof(int) * NS));
+    float* base = static_cast<float*>(sc->mem);
+    sc->ss_table = base;
+    build_ss_table(sc->tmap, base, base + fl, reinterpret_cast<int*>(base + fl + 3 * (size_t)C * NS), s);
+    DTTS_CHECK_HIP(hipEventCreateWithFlags(&sc->used, hipEventDisableTiming));
+    DTTS_CHECK_HIP(hipEventRecord(sc->used, s));
+    sc->id = sched_next_id_++;
+    sched_cache_.insert(sched_cache_.begin(), std::move(sc));
+    return sched_cache_[0]->id;
+}
+
+int Model::diff_schedule_info(int sched_id, int* tmap, float* coefs, int cap) {
+    const Schedule& sc = schedule(sched_id);
+    for (int i = 0; i < sc.n && i < cap; ++i) {
+        if (tmap) tmap[i] = sc.tmap[i];
+        if (coefs) {
+            const DiffStepCoefs& k = sc.p[i];
+            const float v[9] = {k.sqrt_recip_ac, k.sqrt_recipm1_ac, k.coef1, k.coef2, k.min_log, k.max_log, k.cfk, sc.ac[i], sc.ac_prev[i]};
+            std::memcpy(coefs + (size_t)9 * i, v, sizeof(v));
+        }
+    }
+    return sc.n;
 }
 
 void Model::build_diffusion(hipStream_t s) {
     const int C = cfg.diff_channels, H = cfg.diff_heads, NL = cfg.diff_layers;
+    {
+        std::lock_guard<std::mutex> lk(sched_mu_);
+        sched_cache_.clear();                       // (re)bind: cached AdaGN tables were made of the previous weights
+    }
     const std::string d = "diffusion.";
     integ_.clear();
     layers_.clear();
@@ -416,49 +546,18 @@ void Model::build_diffusion(hipStream_t s) {
     te0_ = conv(d + "time_embed.0", C, C, 1);
     te2_ = conv(d + "time_embed.2", C, C, 1);
 
-    make_schedule(cfg.diff_trained_steps, cfg.diff_steps, cfg.cond_free_k, timestep_map_, step_coefs_);
-    n_steps_ = (int)timestep_map_.size();
+    make_schedule(cfg.diff_trained_steps, space_steps(cfg.diff_trained_steps, cfg.diff_steps), cfg.cond_free_k, sched0_);
+    sched0_.id = 0;
+    n_resblocks_ = rbi;
 
-    // ---- timestep tables on the device: t_emb = time_embed(sinusoid(ts)) for every sampling step, then
-    // every ResBlock's emb_layers (SiLU -> Linear) -> ss_table[rb][2C][NS]   (vqvae/diff_model.py:294, 108)
-    const int NS = n_steps_, NRB = rbi;
+    // ---- timestep tables on the device (build_ss_table) in the bind-time arena
+    const int NS = sched0_.n, NRB = rbi;
     persist_.ensure(sizeof(float) * ((size_t)NRB * 2 * C * NS + 3 * (size_t)C * NS) + sizeof(int) * NS + 4096);
-    ss_table_ = persist_.f32((size_t)NRB * 2 * C * NS);
-    float* sinus = persist_.f32((size_t)C * NS);
-    float* t1 = persist_.f32((size_t)C * NS);
-    float* temb = persist_.f32((size_t)C * NS);
+    float* ss_table = persist_.f32((size_t)NRB * 2 * C * NS);
+    float* scratch = persist_.f32(3 * (size_t)C * NS);
     int* ts_dev = persist_.i32(NS);
-    DTTS_CHECK_HIP(hipMemcpyAsync(ts_dev, timestep_map_.data(), sizeof(int) * NS, hipMemcpyHostToDevice, s));
-    launch_timestep_sinusoid(ts_dev, NS, C, sinus, s);
-    ConvParams p;
-    p.B = 1;
-    p.Tin = NS;
-    p.Nout = NS;
-    p.x_cs = NS;
-    p.y_cs = NS;
-    p.x = sinus;
-    p.y = t1;
-    p.epi_act = ACT_SILU;
-    run_conv(te0_, p, s);
-    p.x = t1;
-    p.y = temb;
-    p.epi_act = ACT_NONE;
-    run_conv(te2_, p, s);
-    auto emb_of = [&](const ResBlockW& rb) {
-        ConvParams q;
-        q.B = 1;
-        q.Tin = NS;
-        q.Nout = NS;
-        q.x_cs = NS;
-        q.y_cs = NS;
-        q.x = temb;
-        q.pro_act = ACT_SILU;
-        q.y = ss_table_ + (size_t)rb.index * 2 * C * NS;
-        run_conv(rb.emb, q, s);
-    };
-    for (auto& l : integ_) emb_of(l.rb);
-    for (auto& l : layers_) emb_of(l.rb);
-    for (auto& r : tail_) emb_of(r);
+    sched0_.ss_table = ss_table;
+    build_ss_table(sched0_.tmap, ss_table, scratch, ts_dev, s);
 
     // ---- split-precision (3 x bf16) copies of the trunk's conv weights (conv_x3.h)
     std::vector<PackedConv*> hot = {&inp_block_, &integ1_, &integ2_, &out_conv_};
@@ -649,7 +748,7 @@ void Model::attention_block(const AttnBlockW& w, const float* x, float* y, float
 }
 
 // diffusion ResBlock (vqvae/diff_model.py:106-119): y = x + conv3(SiLU(AdaGN(conv1(SiLU(GN(x))))))
-void Model::res_block_fwd(const ResBlockW& w, const float* x, float* h1, float* y, float* ab, const int* lens, int B, int T,
+void Model::res_block_fwd(const Schedule& sc, const ResBlockW& w, const float* x, float* h1, float* y, float* ab, const int* lens, int B, int T,
                           int Ta, int step, hipStream_t s, void* xs, const int* step_idx, GnFuse* f, const GnNext* next) {
     const int C = cfg.diff_channels;
     const long long bs = (long long)C * Ta;
@@ -680,7 +779,7 @@ void Model::res_block_fwd(const ResBlockW& w, const float* x, float* h1, float* 
         p.x3 = xs;
         p.x3_tp = x3_tp(T);
     }
-    const float* ada = ss_table_ + (size_t)w.index * 2 * C * n_steps_ + (step_idx ? 0 : step);   // step_idx: per-sample steps
+    const float* ada = sc.ss_table + (size_t)w.index * 2 * C * sc.n + (step_idx ? 0 : step);   // step_idx: per-sample steps
     if (f) {                                            // AdaGN + SiLU + split of h1 in the 1x1 conv's epilogue; h1 itself is never stored (:106-119)
         GnNext n2;
         n2.gamma = w.gn2_g;
@@ -690,13 +789,13 @@ void Model::res_block_fwd(const ResBlockW& w, const float* x, float* h1, float* 
         p1.y = nullptr;
         gn_fill(p1, f->slot, conv_x3_gn_xch_bytes(B, C, T), n2, f->xs_alt, groups, s);
         p1.gn_ada = ada;
-        p1.gn_ada_stride = n_steps_;
+        p1.gn_ada_stride = sc.n;
         p1.gn_ada_idx = step_idx;
         run_conv(w.c1, p1, s);
     } else {
         run_conv(w.c1, p, s);
-        if (x3) launch_gn_split_planes(h1, bs, Ta, lens, T, B, C, groups, w.gn2_g, w.gn2_b, 1e-5f, ada, n_steps_, 0, ACT_SILU, xs, s, step_idx);
-        else launch_gn_coeffs(h1, bs, Ta, lens, T, B, C, groups, w.gn2_g, w.gn2_b, 1e-5f, ada, n_steps_, 0, ab, s, step_idx);
+        if (x3) launch_gn_split_planes(h1, bs, Ta, lens, T, B, C, groups, w.gn2_g, w.gn2_b, 1e-5f, ada, sc.n, 0, ACT_SILU, xs, s, step_idx);
+        else launch_gn_coeffs(h1, bs, Ta, lens, T, B, C, groups, w.gn2_g, w.gn2_b, 1e-5f, ada, sc.n, 0, ab, s, step_idx);
     }
     ConvParams q = p;
     q.x = h1;
@@ -748,7 +847,7 @@ Model::PairPlan Model::plan_pair(const int* lens_host, int B, int T, hipStream_t
 // One batched (cond | uncond) DiffusionTts.forward.  The two halves are independent until the sampler update, so they run on
 // two HIP streams (fork after the shared x-path, join before returning): the per-launch prologue/epilogue of one half's
 // kernels overlaps the matrix work of the other's (measured +6..9 % on the conv GEMMs).  DTTS_TWO_STREAMS=0 disables it.
-void Model::diff_forward_pair(const float* x, const float* cbuf0, const int* lens2, const int* lens_i, const int* umap, int B, int Nu,
+void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* cbuf0, const int* lens2, const int* lens_i, const int* umap, int B, int Nu,
                               int T, int step, float* out2, hipStream_t s, const float* integ) {
     const int C = cfg.diff_channels, Ta = T, OC = cfg.diff_out_channels;
     const long long bs = (long long)C * Ta;
@@ -814,7 +913,7 @@ void Model::diff_forward_pair(const float* x, const float* cbuf0, const int* len
         void* xs = x3 ? ws().raw(x3_bytes(Bi, C, T)) : nullptr;
         const float* in = cbuf0;
         for (int l = 0; l < 3; ++l) {
-            res_block_fwd(integ_[l].rb, in, tA, tB, ab, lens_i, Bi, T, Ta, step, s, xs);
+            res_block_fwd(sc, integ_[l].rb, in, tA, tB, ab, lens_i, Bi, T, Ta, step, s, xs);
             attention_block(integ_[l].at, tB, bufI, qkv, tA, ab, lens_i, Bi, T, Ta, s, xs);
             in = bufI;
         }
@@ -889,12 +988,12 @@ void Model::diff_forward_pair(const float* x, const float* cbuf0, const int* len
         for (size_t li = 0; li < layers_.size(); ++li) {   // output back into `cur` (x is dead after the residual add)
             const auto& l = layers_[li];
             const GnNext na = norm_of(l.at.gn_g, l.at.gn_b, ACT_NONE), nn = first_norm(li + 1, 0);
-            res_block_fwd(l.rb, cur, t1, t2, ab, lens, n, T, Ta, step, st, xs, nullptr, f, &na);
+            res_block_fwd(sc, l.rb, cur, t1, t2, ab, lens, n, T, Ta, step, st, xs, nullptr, f, &na);
             attention_block(l.at, t2, cur, qkv, t1, ab, lens, n, T, Ta, st, xs, f, &nn);
         }
         for (size_t ti = 0; ti < tail_.size(); ++ti) {
             const GnNext nn = first_norm(layers_.size(), ti + 1);
-            res_block_fwd(tail_[ti], cur, t1, t2, ab, lens, n, T, Ta, step, st, xs, nullptr, f, &nn);
+            res_block_fwd(sc, tail_[ti], cur, t1, t2, ab, lens, n, T, Ta, step, st, xs, nullptr, f, &nn);
             std::swap(cur, t2);
         }
         // out: GN, SiLU, conv k3 (:312)
@@ -930,7 +1029,7 @@ static int integ_chunk(int Bi) {     // steps per batched evaluation (~36 sample
     return std::max(1, target / Bi);
 }
 
-void Model::precompute_integrator(const float* cbuf0, const int* lens_i_host, int B, int Nu, int T, const std::vector<int>& steps,
+void Model::precompute_integrator(const Schedule& sc, const float* cbuf0, const int* lens_i_host, int B, int Nu, int T, const std::vector<int>& steps,
                                   float* integ_all, hipStream_t s, std::vector<std::pair<int, hipEvent_t>>* ready) {
     const int C = cfg.diff_channels, Bi = B + Nu, J = integ_chunk(Bi), NS = (int)steps.size();
     const size_t ct = (size_t)C * T, mark = ws().mark();
@@ -1013,7 +1112,7 @@ void Model::precompute_integrator(const float* cbuf0, const int* lens_i_host, in
         register_cols(dl, lv.data(), nb, T, L.st);
         float* outp = integ_all + (size_t)k0 * Bi * ct;
         auto dlayer = [&](const DiffLayerW& l, const float* in, float* o) {
-            res_block_fwd(l.rb, in, L.bufB, L.bufC, L.ab, dl, nb, T, T, 0, L.st, L.xs, ds);
+            res_block_fwd(sc, l.rb, in, L.bufB, L.bufC, L.ab, dl, nb, T, T, 0, L.st, L.xs, ds);
             attention_block(l.at, L.bufC, o, L.qkv, L.bufB, L.ab, dl, nb, T, T, L.st, L.xs);
         };
         dlayer(integ_[0], vin, L.bufA);
@@ -1047,7 +1146,12 @@ void Model::diff_forward(const float* x, const float* code_emb, const int* lens_
                          float* out, hipStream_t s) {
     gn_check();
     DTTS_REQUIRE(bound_, "weights not bound");
-    DTTS_REQUIRE(step >= 0 && step < n_steps_, "step out of range");
+    DTTS_REQUIRE(step >= 0 && step < sched0_.n, "step out of range");
+    diff_forward_s(sched0_, x, code_emb, lens_host, B, T, step, cond_free, out, s);
+}
+
+void Model::diff_forward_s(Schedule& sc, const float* x, const float* code_emb, const int* lens_host, int B, int T, int step, int cond_free,
+                           float* out, hipStream_t s) {
     const int C = cfg.diff_channels, OC = cfg.diff_out_channels;
     ws().ensure(pair_ws_bytes(B, C, T) + sizeof(float) * ((size_t)2 * B * C * T + (size_t)2 * B * OC * T) + 4096);
     const PairPlan pl = plan_pair(lens_host, B, T, s);
@@ -1059,18 +1163,42 @@ void Model::diff_forward(const float* x, const float* code_emb, const int* lens_
     else
         launch_broadcast_channels(uncond_, B, C, T, cbuf0, (long long)C * T, T, s);
     launch_broadcast_channels(uncond_, pl.Nu, C, T, cbuf0 + half, (long long)C * T, T, s);
-    diff_forward_pair(x, cbuf0, pl.lens2, pl.lens_i, pl.umap, B, pl.Nu, T, step, out2, s);
+    diff_forward_pair(sc, x, cbuf0, pl.lens2, pl.lens_i, pl.umap, B, pl.Nu, T, step, out2, s);
     const float* src = out2 + (cond_free ? (size_t)B * OC * T : 0);
     DTTS_CHECK_HIP(hipMemcpyAsync(out, src, sizeof(float) * (size_t)B * OC * T, hipMemcpyDeviceToDevice, s));
+}
+
+void Model::diff_forward_t(const float* x, const float* code_emb, const int* lens_host, int B, int T, int timestep, int cond_free,
+                           float* out, hipStream_t s) {
+    gn_check();
+    DTTS_REQUIRE(bound_, "weights not bound");
+    DTTS_REQUIRE(timestep >= 0 && timestep < cfg.diff_trained_steps, "timestep out of [0, diff_trained_steps)");
+    const auto it = std::lower_bound(sched0_.tmap.begin(), sched0_.tmap.end(), timestep);
+    if (it != sched0_.tmap.end() && *it == timestep) {               // a default-schedule timestep: its step of that table
+        diff_forward_s(sched0_, x, code_emb, lens_host, B, T, (int)(it - sched0_.tmap.begin()), cond_free, out, s);
+        return;
+    }
+    Schedule& sc = schedule(diff_schedule(&timestep, 1, s));          // a one-step schedule: only its AdaGN table is used
+    diff_forward_s(sc, x, code_emb, lens_host, B, T, 0, cond_free, out, s);
+    DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
 }
 
 void Model::diff_sample(const float* code_emb, const int* lens_host, int B, int T, unsigned long long seed,
                         const int* sample_ids_host, int n_steps, const float* x_init, const float* step_noise, float* mel_out,
                         int denorm, hipStream_t s) {
+    diff_sample_ex(0, 0, 0.f, code_emb, lens_host, B, T, seed, sample_ids_host, n_steps, x_init, step_noise, mel_out, denorm, s);
+}
+
+void Model::diff_sample_ex(int sched_id, int sampler, float eta, const float* code_emb, const int* lens_host, int B, int T,
+                           unsigned long long seed, const int* sample_ids_host, int n_steps, const float* x_init, const float* step_noise,
+                           float* mel_out, int denorm, hipStream_t s) {
     gn_check();
     DTTS_REQUIRE(bound_, "weights not bound");
+    DTTS_REQUIRE(sampler == 0 || sampler == 1, "sampler: 0 (p) or 1 (ddim)");
+    DTTS_REQUIRE(eta >= 0.f, "eta must be >= 0");
+    Schedule& sc = schedule(sched_id);
     const int C = cfg.diff_channels, OC = cfg.diff_out_channels, MC = cfg.mel_channels;
-    if (n_steps <= 0 || n_steps > n_steps_) n_steps = n_steps_;
+    if (n_steps <= 0 || n_steps > sc.n) n_steps = sc.n;
     const size_t per_call = pair_ws_bytes(B, C, T);
     // the integrator outputs of all steps are evaluated up front (opt-out: DTTS_INTEG_PRECOMPUTE=0); Nu <= B distinct lengths
     static const bool env_pre_on = []() { const char* v = getenv("DTTS_INTEG_PRECOMPUTE"); return !(v && v[0] == '0'); }();
@@ -1123,35 +1251,49 @@ void Model::diff_sample(const float* code_emb, const int* lens_host, int B, int 
     std::vector<std::pair<int, hipEvent_t>> ready;
     if (env_pre) {
         std::vector<int> steps(n_steps), li(Bi);
-        for (int k = 0; k < n_steps; ++k) steps[k] = n_steps_ - 1 - k;
+        for (int k = 0; k < n_steps; ++k) steps[k] = sc.n - 1 - k;
         for (int b = 0; b < B; ++b) li[b] = lens_host ? lens_host[b] : T;
         for (int u = 0; u < pl.Nu; ++u) li[B + u] = pl.ulen[u];
         integ_all = ws().f32((size_t)n_steps * Bi * C * T);
-        precompute_integrator(cbuf0, li.data(), B, pl.Nu, T, steps, integ_all, s, pipe ? &ready : nullptr);
+        precompute_integrator(sc, cbuf0, li.data(), B, pl.Nu, T, steps, integ_all, s, pipe ? &ready : nullptr);
     }
     const size_t mark = ws().mark();
     size_t next_ready = 0;
     for (int k = 0; k < n_steps; ++k) {
-        const int i = n_steps_ - 1 - k;
+        const int i = sc.n - 1 - k;
         Profiler::gate() = (k % Profiler::get().step_every) == 0;
         ws().rewind(mark);                              // the forward's scratch is re-carved every step
         if (next_ready < ready.size() && ready[next_ready].first == k)
             DTTS_CHECK_HIP(hipStreamWaitEvent(s, ready[next_ready++].second, 0));
-        diff_forward_pair(x, cbuf0, lens2, pl.lens_i, pl.umap, B, pl.Nu, T, i, out2, s,
+        diff_forward_pair(sc, x, cbuf0, lens2, pl.lens_i, pl.umap, B, pl.Nu, T, i, out2, s,
                           integ_all ? integ_all + (size_t)k * Bi * C * T : nullptr);
         const bool last = (k == n_steps - 1);
-        launch_diff_update(x, xbs, T, out2, (long long)OC * T, T, lens2, T, B, MC, step_coefs_[i], seed, sids, i,
-                           step_noise ? step_noise + (size_t)k * B * MC * T : nullptr, (denorm && last) ? 1 : 0, s);
+        const float* nz = step_noise ? step_noise + (size_t)k * B * MC * T : nullptr;
+        if (sampler == 1)
+            launch_ddim_update(x, xbs, T, out2, (long long)OC * T, T, lens2, T, B, MC, sc.ddim(i, eta), seed, sids, i, nz,
+                               (denorm && last) ? 1 : 0, s);
+        else
+            launch_diff_update(x, xbs, T, out2, (long long)OC * T, T, lens2, T, B, MC, sc.p[i], seed, sids, i, nz, (denorm && last) ? 1 : 0, s);
     }
     Profiler::gate() = true;
+    if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
 }
 
 // GaussianDiffusion.p_sample (vqvae/utils/diffusion.py:445-485) at one sampling step, x in place
 void Model::diff_p_sample(float* x, const float* code_emb, const int* lens_host, int B, int T, int step, unsigned long long seed,
                           const int* sample_ids_host, const float* noise, float* x0_out, hipStream_t s) {
+    diff_step(0, 0, 0.f, x, code_emb, lens_host, B, T, step, seed, sample_ids_host, noise, x0_out, s);
+}
+
+// one p_sample (vqvae/utils/diffusion.py:445-485) or ddim_sample (:744-783) of schedule `sched_id` at spaced step `step`, x in place
+void Model::diff_step(int sched_id, int sampler, float eta, float* x, const float* code_emb, const int* lens_host, int B, int T, int step,
+                      unsigned long long seed, const int* sample_ids_host, const float* noise, float* x0_out, hipStream_t s) {
     gn_check();
     DTTS_REQUIRE(bound_, "weights not bound");
-    DTTS_REQUIRE(step >= 0 && step < n_steps_, "step out of range");
+    DTTS_REQUIRE(sampler == 0 || sampler == 1, "sampler: 0 (p) or 1 (ddim)");
+    DTTS_REQUIRE(eta >= 0.f, "eta must be >= 0");
+    Schedule& sc = schedule(sched_id);
+    DTTS_REQUIRE(step >= 0 && step < sc.n, "step out of range");
     DTTS_REQUIRE(sample_ids_host, "sample_ids");
     const int C = cfg.diff_channels, OC = cfg.diff_out_channels, MC = cfg.mel_channels;
     ws().ensure(pair_ws_bytes(B, C, T) + sizeof(float) * ((size_t)2 * B * C * T + (size_t)2 * B * OC * T) + 8192);
@@ -1162,9 +1304,14 @@ void Model::diff_p_sample(float* x, const float* code_emb, const int* lens_host,
     const size_t half = (size_t)B * C * T;
     DTTS_CHECK_HIP(hipMemcpyAsync(cbuf0, code_emb, sizeof(float) * half, hipMemcpyDeviceToDevice, s));
     launch_broadcast_channels(uncond_, pl.Nu, C, T, cbuf0 + half, (long long)C * T, T, s);
-    diff_forward_pair(x, cbuf0, pl.lens2, pl.lens_i, pl.umap, B, pl.Nu, T, step, out2, s);
-    launch_diff_update(x, (long long)MC * T, T, out2, (long long)OC * T, T, pl.lens2, T, B, MC, step_coefs_[step], seed, sids, step, noise, 0, s,
-                       x0_out);
+    diff_forward_pair(sc, x, cbuf0, pl.lens2, pl.lens_i, pl.umap, B, pl.Nu, T, step, out2, s);
+    if (sampler == 1)
+        launch_ddim_update(x, (long long)MC * T, T, out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.ddim(step, eta), seed, sids, step, noise,
+                           0, s, x0_out);
+    else
+        launch_diff_update(x, (long long)MC * T, T, out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.p[step], seed, sids, step, noise, 0, s,
+                           x0_out);
+    if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
 }
 
 void Model::diff_conditioning(const float* refer, const int* lens_host, int B, int Tmax, float* cond_out, hipStream_t s) {
@@ -1296,7 +1443,7 @@ void Model::op_attention_block(const char* prefix, const float* x, const int* le
 void Model::op_resblock(const char* prefix, const float* x, const int* lens_host, int B, int T, int step, float* y,
                         hipStream_t s) {
     DTTS_REQUIRE(bound_, "weights not bound");
-    DTTS_REQUIRE(step >= 0 && step < n_steps_, "step out of range");
+    DTTS_REQUIRE(step >= 0 && step < sched0_.n, "step out of range");
     const int C = cfg.diff_channels;
     const ResBlockW* found = nullptr;
     const std::string pf(prefix);
@@ -1315,7 +1462,7 @@ void Model::op_resblock(const char* prefix, const float* x, const int* lens_host
     float* h1 = ws().f32(act);
     float* ab = ws().f32((size_t)2 * B * C);
     void* xs = use_x3() ? ws().raw(x3_bytes(B, C, T)) : nullptr;
-    res_block_fwd(*found, x, h1, y, ab, dl, B, T, T, step, s, xs);
+    res_block_fwd(sched0_, *found, x, h1, y, ab, dl, B, T, T, step, s, xs);
 }
 
 // Generic conv entry for parity tests.  In phases mode (ConvTranspose1d) Cout is the real channel count per phase,

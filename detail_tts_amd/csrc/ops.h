@@ -48,6 +48,20 @@ void launch_diff_update(float* x, long long x_bs, int x_cs, const float* model_o
                         int T, int B, int C, DiffStepCoefs k, unsigned long long seed, const int* sample_ids, int step,
                         const float* noise_override, int final_denorm, hipStream_t s, float* x0_out = nullptr);   // x0_out: pred_xstart [B,C,T]
 
+struct DdimStepCoefs {   // one DDIM step (vqvae/utils/diffusion.py:744-783): fp32 as the reference's _extract_into_tensor hands them out
+    float sqrt_recip_ac, sqrt_recipm1_ac, cfk;
+    float sqrt_ac_prev;  // sqrt(alpha_bar_prev)
+    float dir;           // sqrt(1 - alpha_bar_prev - sigma^2)
+    float sigma;         // eta * sqrt((1 - alpha_bar_prev) / (1 - alpha_bar)) * sqrt(1 - alpha_bar / alpha_bar_prev)
+    int nonzero;         // spaced step index != 0
+};
+// One DDIM update on the same [2B, 2C, T] (cond | uncond) forward output as launch_diff_update: CFG combine, x0 clamp, eps re-derived
+// from x0 (:402-405), x <- x0 sqrt(ab_prev) + dir eps' + [i != 0] sigma z.  Philox noise (STAGE_DIFF_STEP, `step`, the per-sample
+// element order of launch_diff_update) is drawn only when sigma > 0 and i != 0; `noise_override` replaces it.
+void launch_ddim_update(float* x, long long x_bs, int x_cs, const float* model_out, long long m_bs, int m_cs, const int* lens,
+                        int T, int B, int C, DdimStepCoefs k, unsigned long long seed, const int* sample_ids, int step,
+                        const float* noise_override, int final_denorm, hipStream_t s, float* x0_out = nullptr);
+
 // y = a*x + b*z (generic elementwise with optional exp on second operand) used by the flow prior:
 // z_p = m + noise * exp(logs) * noise_scale  (vqvae/model_24k.py:860)
 void launch_flow_prior(const float* stats, long long s_bs, int s_cs, const int* lens, int T, int B, int C, float noise_scale,

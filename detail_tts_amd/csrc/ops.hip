@@ -366,6 +366,53 @@ void launch_diff_update(float* x, long long x_bs, int x_cs, const float* model_o
     DTTS_CHECK_HIP(hipGetLastError());
 }
 
+// DDIM update (vqvae/utils/diffusion.py:744-783 on p_mean_variance :284-386).  Same element walk and noise keys as diff_update_kernel.
+__global__ void ddim_update_kernel(float* x, long long x_bs, int x_cs, const float* mo, long long m_bs, int m_cs, const int* lens,
+                                   int T, int B, int C, DdimStepCoefs k, unsigned long long seed, const int* sample_ids, int step,
+                                   const float* noise_override, int final_denorm, float* x0_out) {
+    const int b = blockIdx.y;
+    const int len = lens ? lens[b] : T;
+    const unsigned sample = (unsigned)sample_ids[b];
+    float* xb = x + (long long)b * x_bs;
+    const float* mc = mo + (long long)b * m_bs;
+    const float* mu = mo + (long long)(B + b) * m_bs;
+    const int n = C * len;
+    const int nblk = (n + 3) / 4;
+    const bool noisy = k.nonzero && k.sigma > 0.f;
+    for (int blk = blockIdx.x * blockDim.x + threadIdx.x; blk < nblk; blk += gridDim.x * blockDim.x) {
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (noisy && !noise_override) philox_normal4(seed, sample, STAGE_DIFF_STEP, step, (unsigned)blk, z);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = blk * 4 + i;
+            if (e >= n) break;
+            const int c = e / len, t = e - c * len;
+            const float xv = xb[(long long)c * x_cs + t];
+            const float eps_c = mc[(long long)c * m_cs + t];
+            const float eps_u = mu[(long long)c * m_cs + t];
+            const float eps = (1.f + k.cfk) * eps_c - k.cfk * eps_u;
+            const float sx = k.sqrt_recip_ac * xv;
+            float x0 = sx - k.sqrt_recipm1_ac * eps;
+            x0 = fminf(fmaxf(x0, -1.f), 1.f);
+            if (x0_out) x0_out[(long long)b * C * T + (long long)c * T + t] = x0;
+            const float eps2 = (sx - x0) / k.sqrt_recipm1_ac;          // _predict_eps_from_xstart: a division, as the reference
+            float v = x0 * k.sqrt_ac_prev + k.dir * eps2;
+            if (noisy) v += k.sigma * (noise_override ? noise_override[(long long)b * C * T + (long long)c * T + t] : z[i]);
+            if (final_denorm) v = ((v + 1.f) * 0.5f) * (2.7f - (-11.512925465f)) + (-11.512925465f);
+            xb[(long long)c * x_cs + t] = v;
+        }
+    }
+}
+
+void launch_ddim_update(float* x, long long x_bs, int x_cs, const float* model_out, long long m_bs, int m_cs, const int* lens,
+                        int T, int B, int C, DdimStepCoefs k, unsigned long long seed, const int* sample_ids, int step,
+                        const float* noise_override, int final_denorm, hipStream_t s, float* x0_out) {
+    const int nblk = (C * T + 3) / 4;
+    hipLaunchKernelGGL(ddim_update_kernel, dim3(cdiv(nblk, 256) > 64 ? 64 : cdiv(nblk, 256), B), dim3(256), 0, s, x, x_bs, x_cs,
+                       model_out, m_bs, m_cs, lens, T, B, C, k, seed, sample_ids, step, noise_override, final_denorm, x0_out);
+    DTTS_CHECK_HIP(hipGetLastError());
+}
+
 // ---------------------------------------------------------------------------------------------
 __global__ void flow_prior_kernel(const float* stats, long long s_bs, int s_cs, const int* lens, int T, int C, float noise_scale,
                                   unsigned long long seed, const int* sample_ids, const float* noise_override, int flip,

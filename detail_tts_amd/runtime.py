@@ -303,6 +303,58 @@ class Runtime:
                                            _ptr(x_init), _ptr(step_noise), _ptr(out), 1 if denorm else 0, self._stream()))
         return out
 
+    def diff_schedule(self, timesteps):
+        """id of the sampling schedule of these model timesteps (built on the current stream on first use, then cached on the
+        handle; 0 = the default 50-step schedule).  Call it outside any stream capture."""
+        ts = np.ascontiguousarray(np.asarray(sorted(set(int(t) for t in timesteps)), np.int32))
+        sid = C.c_int(0)
+        self._rc(self.lib.dtts_diff_schedule(self.h, ts.ctypes.data_as(_lib.c_int_p), len(ts), C.byref(sid), self._stream()))
+        return sid.value
+
+    def diff_schedule_coefs(self, sched):
+        """host copy of a schedule: (timestep_map [n], fp32 coefs [n, 9]: sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2,
+        posterior_log_variance_clipped, log(betas), cfk, alphas_cumprod, alphas_cumprod_prev)"""
+        n = C.c_int(0)
+        self._rc(self.lib.dtts_diff_schedule_coefs(self.h, int(sched), None, None, 0, C.byref(n)))
+        tmap = np.zeros(n.value, np.int32)
+        coefs = np.zeros((n.value, 9), np.float32)
+        self._rc(self.lib.dtts_diff_schedule_coefs(self.h, int(sched), tmap.ctypes.data_as(_lib.c_int_p),
+                                                   coefs.ctypes.data_as(_lib.c_float_p), n.value, C.byref(n)))
+        return tmap, coefs
+
+    def diff_sample_ex(self, code_emb, seed, sample_ids, sched=0, sampler=0, eta=0.0, lens=None, n_steps=0, x_init=None, step_noise=None,
+                       denorm=True):
+        """diff_sample on schedule `sched` (diff_schedule) with sampler 0 = p (ancestral) / 1 = ddim"""
+        _check(code_emb, "code_emb"); _check(x_init, "x_init"); _check(step_noise, "step_noise")
+        B, _, T = code_emb.shape
+        out = torch.zeros((B, self.cfg["diffusion"]["in_channels"], T), device=self.device, dtype=torch.float32)
+        li, si = _ints(lens), _ints(sample_ids)
+        self._rc(self.lib.dtts_diff_sample_ex(self.h, int(sched), int(sampler), float(eta), _ptr(code_emb), li[0] if li else None, B, T,
+                                              int(seed), si[0], int(n_steps), _ptr(x_init), _ptr(step_noise), _ptr(out),
+                                              1 if denorm else 0, self._stream()))
+        return out
+
+    def diff_step(self, x, code_emb, step, seed, sample_ids, sched=0, sampler=0, eta=0.0, lens=None, noise=None, return_x0=False):
+        """one sampler step (p_sample / ddim_sample) of schedule `sched` at spaced step `step` (n - 1 = first): the new x (and pred_xstart)"""
+        _check(x, "x"); _check(code_emb, "code_emb"); _check(noise, "noise")
+        B, _, T = x.shape
+        xo = x.clone()
+        x0 = torch.zeros_like(x) if return_x0 else None
+        li, si = _ints(lens), _ints(sample_ids)
+        self._rc(self.lib.dtts_diff_step(self.h, int(sched), int(sampler), float(eta), _ptr(xo), _ptr(code_emb), li[0] if li else None, B, T,
+                                         int(step), int(seed), si[0], _ptr(noise), _ptr(x0), self._stream()))
+        return (xo, x0) if return_x0 else xo
+
+    def diff_forward_t(self, x, timestep, code_emb=None, cond_free=False, lens=None):
+        """DiffusionTts.forward at MODEL timestep `timestep` in [0, 4000)"""
+        _check(x, "x"); _check(code_emb, "code_emb")
+        B, _, T = x.shape
+        out = torch.zeros((B, self.cfg["diffusion"]["out_channels"], T), device=self.device, dtype=torch.float32)
+        li = _ints(lens)
+        self._rc(self.lib.dtts_diff_forward_t(self.h, _ptr(x), _ptr(code_emb), li[0] if li else None, B, T, int(timestep),
+                                              1 if cond_free else 0, _ptr(out), self._stream()))
+        return out
+
     # ------------------------------------------------------------------ stage C
     def vocoder(self, mel, seed, sample_ids, lens=None, noise_scale=0.667, noise_override=None, return_z=False, stream_chunk=0):
         """infer_flowvae; stream_chunk > 0: the generator runs in windows of that many frames (+ 16-frame halo), dtts_vocoder_stream"""

@@ -18,7 +18,7 @@ from ..config import COND_FREE_K, INFER_DIFFUSION_STEPS, MAX_GENERATE_LENGTH, ME
 from ..gpt.model import UnifiedVoice
 from ..runtime import Runtime
 from .diff_model import DiffusionTts
-from .utils.diffusion import SpacedDiffusion, get_named_beta_schedule, space_timesteps
+from .utils.diffusion import SAMPLERS, SpacedDiffusion, get_named_beta_schedule, space_timesteps
 
 
 def normalize_torch_mel(mel):
@@ -50,6 +50,26 @@ def do_spectrogram_diffusion(diffusion_model, diffuser, latents, conditioning_la
                                  model_kwargs={"precomputed_aligned_embeddings": emb}, progress=verbose, seed=seed,
                                  sample_ids=sample_ids, lens=lens)
     return mel[:, :, :out_len]
+
+
+def sampling_args(diffusion_steps=None, sampler="p", eta=0.0):
+    """Host-side check of infer()'s sampling arguments, before any launch -> (model timesteps, sampler id, eta).
+    diffusion_steps: None = 50 (the reference's infer_diffuser), else 1 .. 4000 steps of space_timesteps(4000, [N]);
+    sampler: "p" (ancestral, the reference's p_sample_loop) or "ddim" (ddim_sample_loop with `eta` >= 0)."""
+    n = INFER_DIFFUSION_STEPS if diffusion_steps is None else diffusion_steps
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= TRAINED_DIFFUSION_STEPS:
+        raise ValueError(f"diffusion_steps must be an integer in [1, {TRAINED_DIFFUSION_STEPS}], not {diffusion_steps!r}")
+    if sampler == "dpm++2m":
+        raise NotImplementedError("sampler 'dpm++2m' is not implemented on the device: use 'p' or 'ddim'")
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler must be 'p' or 'ddim', not {sampler!r}")
+    try:
+        eta = float(eta)
+    except (TypeError, ValueError):
+        raise ValueError(f"eta must be a number >= 0, not {eta!r}") from None
+    if not eta >= 0.0 or eta == float("inf"):
+        raise ValueError(f"eta must be a finite number >= 0, not {eta!r}")
+    return sorted(space_timesteps(TRAINED_DIFFUSION_STEPS, [int(n)])), SAMPLERS[sampler], eta
 
 
 class Generator:
@@ -104,7 +124,7 @@ class SynthesizerTrn:
         self.dec = Generator(self.rt)
         self.infer_diffuser = SpacedDiffusion(space_timesteps(TRAINED_DIFFUSION_STEPS, [INFER_DIFFUSION_STEPS]),
                                               betas=get_named_beta_schedule("linear", TRAINED_DIFFUSION_STEPS),
-                                              conditioning_free=True, conditioning_free_k=COND_FREE_K)
+                                              conditioning_free=True, conditioning_free_k=COND_FREE_K, sampler="dpm++2m")
         self.rt.timestep_map = list(self.infer_diffuser.timestep_map)
         self.stage_ms = None          # set to {} to collect per-stage hipEvent timings of the next infer() call
         self._voc_stream = None       # second stream of infer(stream_vocoder=True)
@@ -126,8 +146,11 @@ class SynthesizerTrn:
     # ------------------------------------------------------------------------------------------------------------
     def infer(self, text, text_length, refer, refer_lengths, noise_scale=NOISE_SCALE, *, batch=False, seed=None, sample_ids=None,
               forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False, return_lengths=False,
-              stream_vocoder=False, vocoder_chunk=256, wait=True, check_range=True):
+              stream_vocoder=False, vocoder_chunk=256, wait=True, check_range=True, diffusion_steps=None, sampler="p", eta=0.0):
         """vqvae/model_24k.py:774-810.  Returns wav [B,1,1024*n_max] (B=1 unless batch=True).
+
+        diffusion_steps / sampler / eta: stage B's schedule (None = the reference's 50 steps) and sampler ("p" = the reference's
+        ancestral p_sample_loop, "ddim" = ddim_sample_loop with `eta`); see sampling_args.  Fewer steps cost proportionally less.
 
         stream_vocoder: stage C runs on a second HIP stream, its generator window by window (`vocoder_chunk` mel frames + halo,
         dtts_vocoder_stream; 0 = one shot).  With wait=False the call returns while stage C is still running - `self.vocoder_done` is the event
@@ -137,6 +160,7 @@ class SynthesizerTrn:
         check_range (with wait=True): the call waits for its own waveform and raises if stage C's split-precision planes saturated on
         THIS request (dtts_vocoder_check; the reference computes those convs in fp32).  With wait=False (or check_range=False) the call
         stays asynchronous: wait on `self.vocoder_done`, then call `self.check_vocoder()` before reading the waveform."""
+        sched_ts, sampler_id, eta = sampling_args(diffusion_steps, sampler, eta)
         text = torch.as_tensor(text)
         refer = torch.as_tensor(refer)
         tl = torch.as_tensor(text_length).reshape(-1).tolist()
@@ -189,7 +213,8 @@ class SynthesizerTrn:
         code_emb = self.rt.diff_timestep_independent(lat, cond, n)
         mark("diff_cond")
         lens_t = [4 * v for v in n]
-        mel = self.rt.diff_sample(code_emb, seed, sample_ids, lens=lens_t, denorm=True)
+        sched = self.rt.diff_schedule(sched_ts)
+        mel = self.rt.diff_sample_ex(code_emb, seed, sample_ids, sched=sched, sampler=sampler_id, eta=eta, lens=lens_t, denorm=True)
         mark("diff_sample")
         # ---- stage C (:805-809)
         if stream_vocoder:
@@ -228,7 +253,7 @@ class SynthesizerTrn:
 
     # ------------------------------------------------------------------------------------------------------------
     def infer_stream(self, requests, noise_scale=NOISE_SCALE, *, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False,
-                     vocoder_chunk=0, pair_stage_a=False, on_saturation="rerun_fp32"):
+                     vocoder_chunk=0, pair_stage_a=False, on_saturation="rerun_fp32", diffusion_steps=None, sampler="p", eta=0.0):
         """Batch server: `infer(..., batch=True)` over a sequence of request batches, software-pipelined over three HIP streams.
 
         requests: iterable of dicts with keys text [B,Lt], text_length [B], refer [B,128,Tr], refer_lengths [B] and optionally seed,
@@ -247,10 +272,14 @@ class SynthesizerTrn:
         on_saturation: what happens to a request whose stage C saturated its split-precision planes (dtts_vocoder_check).  "rerun_fp32"
         (default): THAT request's stage C is run again on the exact fp32 kernels (option voc_x3 = 0, which cannot saturate) and its
         waveform is handed out as usual - the requests behind it, whose stages are already enqueued, are not lost (ADVICE r05);
-        "raise": the error leaves the generator (and ends the stream)."""
+        "raise": the error leaves the generator (and ends the stream).
+
+        diffusion_steps / sampler / eta: as in infer(), one schedule for every request of the stream."""
         assert on_saturation in ("rerun_fp32", "raise")
+        sched_ts, sampler_id, eta = sampling_args(diffusion_steps, sampler, eta)
         dev = self.device
         cur = torch.cuda.current_stream(dev)
+        sched = self.rt.diff_schedule(sched_ts)      # built here, once: no table allocation inside the pipelined loop
         if self._gpt_stream is None:
             lo, hi = torch.cuda.Stream.priority_range() if hasattr(torch.cuda.Stream, "priority_range") else (0, -1)
             self._gpt_stream = torch.cuda.Stream(dev, priority=lo if os.environ.get("DTTS_STAGE_A_PRIORITY") == "low" else hi)
@@ -370,7 +399,7 @@ class SynthesizerTrn:
             cond = self.rt.diff_conditioning(refer, st["rl"])
             code_emb = self.rt.diff_timestep_independent(lat, cond, n)
             lens_t = [4 * v for v in n]
-            mel = self.rt.diff_sample(code_emb, st["seed"], st["sids"], lens=lens_t, denorm=True)
+            mel = self.rt.diff_sample_ex(code_emb, st["seed"], st["sids"], sched=sched, sampler=sampler_id, eta=eta, lens=lens_t, denorm=True)
             ready = torch.cuda.Event()
             ready.record(cur)
             if tr:

@@ -1,13 +1,23 @@
 """Sampler object mirroring the subset of the reference's SpacedDiffusion that inference uses
-(vqvae/utils/diffusion.py:1181-1220 + GaussianDiffusion.p_sample_loop :654-742).  The arithmetic lives in
-libdetail_hip.so (dtts_diff_sample); this class carries the schedule constants and the call surface."""
+(vqvae/utils/diffusion.py:179-228 + 1172-1272; p_sample_loop :654-742, ddim_sample_loop :819-899, sample_loop :640-652).  The
+arithmetic lives in libdetail_hip.so (dtts_diff_sample_ex); this class carries the schedule constants and the call surface."""
 from __future__ import annotations
 
 import numpy as np
 
+SAMPLERS = {"p": 0, "ddim": 1}
+
 
 def space_timesteps(num_timesteps, section_counts):
-    """vqvae/utils/diffusion.py:1223-1272 (list-of-ints form)."""
+    """vqvae/utils/diffusion.py:1223-1272: an int, a list of ints, or the string forms "25", "10,15" and "ddim25"."""
+    if isinstance(section_counts, str):
+        if section_counts.startswith("ddim"):
+            desired_count = int(section_counts[len("ddim"):])
+            for i in range(1, num_timesteps):
+                if len(range(0, num_timesteps, i)) == desired_count:
+                    return set(range(0, num_timesteps, i))
+            raise ValueError(f"cannot create exactly {num_timesteps} steps with an integer stride")
+        section_counts = [int(x) for x in section_counts.split(",")]
     if isinstance(section_counts, int):
         section_counts = [section_counts]
     size_per, extra = num_timesteps // len(section_counts), num_timesteps % len(section_counts)
@@ -33,8 +43,12 @@ def get_named_beta_schedule(name, n):
 
 
 class SpacedDiffusion:
-    def __init__(self, use_timesteps, betas, conditioning_free=True, conditioning_free_k=2.0, **_ignored):
+    def __init__(self, use_timesteps, betas, conditioning_free=True, conditioning_free_k=2.0, rescale_timesteps=False, sampler="ddim",
+                 model_mean_type="epsilon", model_var_type="learned_range", loss_type="mse", ramp_conditioning_free=True):
+        if model_mean_type != "epsilon" or model_var_type != "learned_range" or not ramp_conditioning_free:
+            raise NotImplementedError("the device sampler implements the inference model's epsilon / learned_range / ramped-guidance form")
         self.use_timesteps = set(use_timesteps)
+        self.original_num_steps = len(betas)
         ac = np.cumprod(1.0 - np.asarray(betas, np.float64))
         last, nb, self.timestep_map = 1.0, [], []
         for i, a in enumerate(ac):
@@ -42,17 +56,69 @@ class SpacedDiffusion:
                 nb.append(1 - a / last)
                 last = a
                 self.timestep_map.append(i)
-        self.betas = np.array(nb)
-        self.num_timesteps = len(nb)
-        self.original_num_steps = len(betas)
+        self.sampler = sampler
+        self.rescale_timesteps = rescale_timesteps
         self.conditioning_free = conditioning_free
         self.conditioning_free_k = conditioning_free_k
+        # GaussianDiffusion.__init__ on the spaced betas (vqvae/utils/diffusion.py:201-228), float64
+        betas = np.array(nb, dtype=np.float64)
+        self.betas = betas
+        self.num_timesteps = int(betas.shape[0])
+        alphas = 1.0 - betas
+        self.alphas_cumprod = np.cumprod(alphas, axis=0)
+        self.alphas_cumprod_prev = np.append(1.0, self.alphas_cumprod[:-1])
+        self.alphas_cumprod_next = np.append(self.alphas_cumprod[1:], 0.0)
+        self.sqrt_alphas_cumprod = np.sqrt(self.alphas_cumprod)
+        self.sqrt_one_minus_alphas_cumprod = np.sqrt(1.0 - self.alphas_cumprod)
+        self.log_one_minus_alphas_cumprod = np.log(1.0 - self.alphas_cumprod)
+        self.sqrt_recip_alphas_cumprod = np.sqrt(1.0 / self.alphas_cumprod)
+        self.sqrt_recipm1_alphas_cumprod = np.sqrt(1.0 / self.alphas_cumprod - 1)
+        self.posterior_variance = betas * (1.0 - self.alphas_cumprod_prev) / (1.0 - self.alphas_cumprod)
+        # a 1-step schedule has no posterior_variance[1] (the reference raises here); its only step adds no noise
+        pv = self.posterior_variance
+        with np.errstate(divide="ignore"):
+            self.posterior_log_variance_clipped = np.log(np.append(pv[1 if len(pv) > 1 else 0], pv[1:]))
+        self.posterior_mean_coef1 = betas * np.sqrt(self.alphas_cumprod_prev) / (1.0 - self.alphas_cumprod)
+        self.posterior_mean_coef2 = (1.0 - self.alphas_cumprod_prev) * np.sqrt(alphas) / (1.0 - self.alphas_cumprod)
 
-    def p_sample_loop(self, model, shape, noise=None, model_kwargs=None, progress=False, seed=0, sample_ids=None, lens=None, **_):
-        """model: a detail_tts_amd DiffusionTts; returns x_0 (normalised mel) [B,128,T]."""
+    # ---------------------------------------------------------------------------------------------------- sampling loops
+    def _check(self, sampler):
+        if sampler == "dpm++2m":
+            raise NotImplementedError("sampler 'dpm++2m' (the reference's k-diffusion DPM-Solver path, vqvae/utils/diffusion.py:487-581) "
+                                      "is not implemented on the device: use 'p' or 'ddim'")
+        if sampler not in SAMPLERS:
+            raise ValueError(f"sampler must be 'p' or 'ddim', not {sampler!r}")
+        if not self.conditioning_free:
+            raise NotImplementedError("conditioning_free=False sampling (one unguided forward per step) is not implemented on the device")
+        if self.rescale_timesteps:
+            raise NotImplementedError("rescale_timesteps=True (float timesteps) is not implemented on the device")
+
+    def _loop(self, sampler, model, shape, noise, model_kwargs, seed, sample_ids, lens, eta, denorm=False):
+        self._check(sampler)
+        if eta < 0:
+            raise ValueError("eta must be >= 0")
         emb = (model_kwargs or {}).get("precomputed_aligned_embeddings")
         if emb is None:
             raise ValueError("precomputed_aligned_embeddings is required (as in do_spectrogram_diffusion)")
         B = shape[0]
         sample_ids = list(range(B)) if sample_ids is None else sample_ids
-        return model.rt.diff_sample(emb, seed, sample_ids, lens=lens, x_init=noise, denorm=False)
+        rt = model.rt
+        sched = rt.diff_schedule(self.timestep_map)
+        return rt.diff_sample_ex(emb, seed, sample_ids, sched=sched, sampler=SAMPLERS[sampler], eta=eta, lens=lens, x_init=noise,
+                                 denorm=denorm)
+
+    def p_sample_loop(self, model, shape, noise=None, model_kwargs=None, progress=False, seed=0, sample_ids=None, lens=None, **_):
+        """model: a detail_tts_amd DiffusionTts; returns x_0 (normalised mel) [B,128,T] of THIS diffuser's schedule."""
+        return self._loop("p", model, shape, noise, model_kwargs, seed, sample_ids, lens, 0.0)
+
+    def ddim_sample_loop(self, model, shape, noise=None, model_kwargs=None, progress=False, eta=0.0, seed=0, sample_ids=None, lens=None,
+                         **_):
+        """vqvae/utils/diffusion.py:819-851 (ddim_sample :744-783 per step, Philox noise when eta > 0)"""
+        return self._loop("ddim", model, shape, noise, model_kwargs, seed, sample_ids, lens, float(eta))
+
+    def sample_loop(self, *args, **kwargs):
+        """vqvae/utils/diffusion.py:640-652: dispatch on self.sampler"""
+        self._check(self.sampler)
+        if self.sampler == "ddim":
+            return self.ddim_sample_loop(*args, **kwargs)
+        return self.p_sample_loop(*args, **kwargs)

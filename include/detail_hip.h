@@ -18,7 +18,7 @@
  * [B, C, T] (channel-major, time contiguous) buffers owned by the caller; `lens`/`sample_ids`
  * arrays are HOST int32 arrays of B entries; all launches are asynchronous on `stream`
  * (a hipStream_t passed as void*), with no hidden synchronisation except when the internal
- * workspace has to grow.
+ * workspace has to grow, or when dtts_diff_schedule builds a new schedule (allocation) or evicts one (waits for its last reader).
  *
  * Threads: one handle per device.  A handle may be driven by TWO host threads at once under this split: one thread issues only the
  * decode-session calls (dtts_gpt_prefill / _decode_step / _decode / _steps / _all_finished / _finish: stage A, own scratch and state),
@@ -194,6 +194,35 @@ int dtts_diff_sample(dtts_handle* h, const float* code_emb, const int* lens, int
  * x [B,128,T] is updated IN PLACE; x0_out (may be NULL) receives pred_xstart.  Unit entry of the sampler parity tests. */
 int dtts_diff_p_sample(dtts_handle* h, float* x, const float* code_emb, const int* lens, int B, int T, int step,
                        unsigned long long seed, const int* sample_ids, const float* noise, float* x0_out, void* stream);
+
+/* A sampling schedule: SpacedDiffusion(use_timesteps = timesteps[0..n), linear betas over diff_trained_steps)
+ * (vqvae/utils/diffusion.py:1172-1220, 179-228; any space_timesteps set, "ddimN" striding included: :1223-1272).
+ * Timesteps in [0, diff_trained_steps), any order, duplicates ignored.  The coefficient tables (float64 -> fp32) and the AdaGN table
+ * of every step (vqvae/diff_model.py:294, 108) are built on `stream` on first use and cached on the handle (least recently used
+ * evicted, after the launches that read it); *id_out = 0 for the default diff_steps schedule.  Not inside a stream capture. */
+int dtts_diff_schedule(dtts_handle* h, const int* timesteps, int n, int* id_out, void* stream);
+
+/* Host copy of schedule `id`: *n_out steps; tmap [cap] (may be NULL) receives timestep_map; coefs [cap][9] (may be NULL) per step
+ * {sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, posterior_mean_coef1, posterior_mean_coef2, posterior_log_variance_clipped,
+ * log(betas), guidance cfk, alphas_cumprod, alphas_cumprod_prev} as fp32 (vqvae/utils/diffusion.py:204-228, 349-355). */
+int dtts_diff_schedule_coefs(dtts_handle* h, int id, int* tmap, float* coefs, int cap, int* n_out);
+
+/* dtts_diff_sample on schedule `id` with sampler 0 = p_sample_loop (vqvae/utils/diffusion.py:654-742, 445-485) or
+ * 1 = ddim_sample_loop (:654-742 over ddim_sample :744-783) with `eta` >= 0.  Other arguments as dtts_diff_sample;
+ * step_noise [n_steps][B,128,T] replaces the Philox noise of the steps that draw it.  (id, sampler, eta) = (0, 0, 0) is dtts_diff_sample. */
+int dtts_diff_sample_ex(dtts_handle* h, int id, int sampler, float eta, const float* code_emb, const int* lens, int B, int T,
+                        unsigned long long seed, const int* sample_ids, int n_steps, const float* x_init, const float* step_noise,
+                        float* mel_out, int denorm, void* stream);
+
+/* One p_sample (vqvae/utils/diffusion.py:445-485) or ddim_sample (:744-783) of schedule `id` at spaced step `step` (n - 1 = first):
+ * x [B,128,T] IN PLACE; noise [B,128,T] (may be NULL: Philox spec); x0_out (may be NULL) receives pred_xstart. */
+int dtts_diff_step(dtts_handle* h, int id, int sampler, float eta, float* x, const float* code_emb, const int* lens, int B, int T,
+                   int step, unsigned long long seed, const int* sample_ids, const float* noise, float* x0_out, void* stream);
+
+/* DiffusionTts.forward (vqvae/diff_model.py:262-322) at MODEL timestep `timestep` in [0, diff_trained_steps), as the reference's
+ * model accepts any t.  Arguments as dtts_diff_forward. */
+int dtts_diff_forward_t(dtts_handle* h, const float* x, const float* code_emb, const int* lens, int B, int T, int timestep,
+                        int cond_free, float* out, void* stream);
 
 /* ---- stage C: flow-VAE front + HiFiGAN generator -------------------------------------------------- */
 
