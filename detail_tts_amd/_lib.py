@@ -84,6 +84,12 @@ SIGNATURES = {
                                  C.c_ulonglong, c_int_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dtts_diff_forward_t": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                       C.c_void_p]),
+    "dtts_dpm_schedule_table": (C.c_int, [C.c_int, c_float_p, c_float_p, c_float_p, C.c_int, c_int_p]),
+    "dtts_diff_schedule_dpm": (C.c_int, [C.c_void_p, C.c_int, c_int_p, C.c_void_p]),
+    "dtts_diff_step_dpm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_void_p]),
+    "dtts_diff_forward_tf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p,
+                                       C.c_void_p]),
     "dtts_vocoder": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_ulonglong, c_int_p, C.c_float, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "dtts_vocoder_stream": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_ulonglong, c_int_p, C.c_float, C.c_void_p,

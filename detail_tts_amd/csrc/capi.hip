@@ -332,6 +332,46 @@ int dtts_diff_forward_t(dtts_handle* h, const float* x, const float* code_emb, c
     DTTS_API_END(h)
 }
 
+int dtts_dpm_schedule_table(int n, float* times, float* model_times, float* coefs, int cap, int* n_out) {
+    DTTS_API_BEGIN
+    DTTS_REQUIRE(n >= 2, "n must be >= 2");
+    std::vector<float> t, mt, lam;
+    std::vector<dtts::DpmStepCoefs> st;
+    dtts::dpm_schedule_table(n, 0.f, t, mt, st, &lam);              // the guidance scale is not part of the table
+    if (n_out) *n_out = n;
+    DTTS_REQUIRE(!(times || model_times || coefs) || cap >= n, "cap < n");
+    if (times) std::memcpy(times, t.data(), sizeof(float) * (n + 1));
+    if (model_times) std::memcpy(model_times, mt.data(), sizeof(float) * n);
+    if (coefs)
+        for (int k = 0; k < n; ++k) {
+            const dtts::DpmStepCoefs& c = st[k];
+            const float v[7] = {c.alpha_s, c.sigma_s, lam[k], c.ratio, c.c1, c.inv_r0, (float)c.order};
+            std::memcpy(coefs + (size_t)7 * k, v, sizeof(v));
+        }
+    DTTS_API_END(nullptr)
+}
+
+int dtts_diff_schedule_dpm(dtts_handle* h, int n, int* id_out, void* stream) {
+    DTTS_API_BEGIN
+    DTTS_REQUIRE(id_out, "id_out");
+    *id_out = h->m->diff_schedule_dpm(n, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_diff_step_dpm(dtts_handle* h, int id, float* x, float* x0_hist, const float* code_emb, const int* lens, int B, int T, int step,
+                       float* x0_out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_step_dpm(id, x, x0_hist, code_emb, lens, B, T, step, x0_out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_diff_forward_tf(dtts_handle* h, const float* x, const float* code_emb, const int* lens, int B, int T, float timestep,
+                         int cond_free, float* out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_forward_tf(x, code_emb, lens, B, T, timestep, cond_free, out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
 int dtts_vocoder(dtts_handle* h, const float* mel, const int* lens, int B, int T, unsigned long long seed, const int* sample_ids,
                  float noise_scale, const float* noise_override, float* wav, float* trace_z, void* stream) {
     DTTS_API_BEGIN

@@ -136,11 +136,17 @@ Arena* arena_override();     // the calling thread's stand-in (nullptr: none)
 // A sampling schedule: SpacedDiffusion(use_timesteps = tmap, linear betas over cfg.diff_trained_steps) (vqvae/utils/diffusion.py:1172-1220).
 // The coefficient tables are computed in float64 on the host and cast to fp32; ss_table holds every ResBlock's AdaGN scale / shift
 // at every step of the schedule: emb_layers(time_embed(sinusoid(tmap[i]))) (vqvae/diff_model.py:294, 108).
+// Float-time schedules (kind != 0) carry fp32 model times instead of tmap: DPM-Solver++(2M) of n steps (kind 1: k_diffusion_sample_loop,
+// vqvae/utils/diffusion.py:487-581), or fractional forward times alone (kind 2: diff_forward_tf).  Column i of every table is step
+// n - 1 - i of the loop (n - 1 = first), as for the integer schedules, so the samplers' loop and the trunk read them the same way.
 struct Schedule {
     int id = 0;                           // 0: the default (cfg.diff_steps) schedule built at bind
-    std::vector<int> tmap;                // model timesteps of the spaced steps, ascending (timestep_map)
+    int kind = 0;                         // 0: integer timesteps (tmap); 1: DPM-Solver++(2M); 2: fractional model times (forward only)
+    std::vector<int> tmap;                // kind 0: model timesteps of the spaced steps, ascending (timestep_map)
+    std::vector<float> ftimes;            // kinds 1, 2: fp32 model time of column i, ascending (kind 1: t_{n-1-i} * 1000)
     std::vector<DiffStepCoefs> p;         // ancestral sampler (p_sample)
     std::vector<float> ac, ac_prev;       // fp32 alphas_cumprod / alphas_cumprod_prev (DDIM: the eta-dependent terms are per call)
+    std::vector<DpmStepCoefs> dpm;        // kind 1: the update of column i
     float cfk_k = 0.f;
     const float* ss_table = nullptr;      // [n_resblocks][2C][n]
     int n = 0;
@@ -148,7 +154,15 @@ struct Schedule {
     hipEvent_t used = nullptr;            // recorded after every call that read ss_table: an eviction waits for it
     ~Schedule();
     DdimStepCoefs ddim(int i, float eta) const;
+    bool same_key(const Schedule& o) const { return kind == o.kind && tmap == o.tmap && ftimes == o.ftimes; }
 };
+
+// DPM-Solver++(2M) of n >= 2 steps as the reference's DPM_Solver.sample runs it (vqvae/utils/dpm_solver.py:1159-1201: time_uniform,
+// multistep, order 2, lower_order_final) on NoiseScheduleVP("linear", 0.025, 5.0) (:108-154), in fp32 in the reference's order of
+// operations.  times [n + 1]: torch.linspace(1, 1e-3, n + 1) in fp32; model_times [n]: t_k * 1000; steps [n]: the update t_k -> t_{k+1}
+// in the solver's order (k = 0 first); lambda_s [n] (optional): lambda(t_k).
+void dpm_schedule_table(int n, float cfk, std::vector<float>& times, std::vector<float>& model_times, std::vector<DpmStepCoefs>& steps,
+                        std::vector<float>* lambda_s = nullptr);
 
 class Model {
 public:
@@ -180,6 +194,15 @@ public:
     int diff_schedule(const int* timesteps, int n, hipStream_t s);
     // host copy of a schedule: tmap[n]; coefs: per step {sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, min_log, max_log, cfk, ac, ac_prev}
     int diff_schedule_info(int sched_id, int* tmap, float* coefs, int cap);
+    // the DPM-Solver++(2M) schedule of n steps (dpm_schedule_table + its AdaGN table at the fractional model times): as diff_schedule
+    int diff_schedule_dpm(int n, hipStream_t s);
+    // one DPM-Solver++(2M) step of DPM schedule `sched_id` at step index `step` (n - 1 = first): x in place; x0_hist [B,128,T] holds the
+    // previous step's x0 (read by a second-order step) and receives this step's; x0_out (optional) receives it too
+    void diff_step_dpm(int sched_id, float* x, float* x0_hist, const float* code_emb, const int* lens_host, int B, int T, int step,
+                       float* x0_out, hipStream_t s);
+    // DiffusionTts.forward at a fp32 model time in [0, diff_trained_steps): integer values take diff_forward_t's route bit for bit
+    void diff_forward_tf(const float* x, const float* code_emb, const int* lens_host, int B, int T, float timestep, int cond_free,
+                         float* out, hipStream_t s);
     // one p_sample at `step` on x in place (unit entry of the sampler parity tests)
     void diff_p_sample(float* x, const float* code_emb, const int* lens_host, int B, int T, int step, unsigned long long seed,
                        const int* sample_ids_host, const float* noise, float* x0_out, hipStream_t s);
@@ -360,7 +383,9 @@ private:
     Schedule& schedule(int id);
     void diff_forward_s(Schedule& sc, const float* x, const float* code_emb, const int* lens_host, int B, int T, int step, int cond_free,
                         float* out, hipStream_t s);
-    void build_ss_table(const std::vector<int>& tmap, float* ss_table, float* scratch, int* ts_dev, hipStream_t s);
+    void build_ss_table(const Schedule& sc, float* ss_table, float* scratch, void* ts_dev, hipStream_t s);
+    // the cached schedule with key's (kind, tmap, ftimes), else `key` itself (host tables filled) with its AdaGN table built on s; its id
+    int cache_schedule(std::unique_ptr<Schedule> key, hipStream_t s);
 
     // vocoder
     MelStyleW ref_enc_, gpt_cond_;

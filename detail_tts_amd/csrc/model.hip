@@ -414,15 +414,74 @@ Schedule::~Schedule() {
     if (used) (void)hipEventDestroy(used);
 }
 
+// ---- DPM-Solver++(2M) (vqvae/utils/diffusion.py:487-581 -> vqvae/utils/dpm_solver.py), fp32 scalars in the reference's order
+// NoiseScheduleVP("linear", continuous_beta_0 = 0.1 / 4, continuous_beta_1 = 20 / 4) (:108-154): the Python float constants meet fp32
+// 0-d tensors, so each is rounded to fp32 and every operation is rounded on its own
+static float dpm_log_alpha(float t) {               // marginal_log_mean_coeff: -0.25 t^2 (b1 - b0) - 0.5 t b0
+#pragma clang fp contract(off)
+    const float a = (-0.25f * (t * t)) * (float)(20.0 / 4 - 0.1 / 4);
+    const float b = (0.5f * t) * (float)(0.1 / 4);
+    return a - b;
+}
+static float dpm_sigma(float t) { return std::sqrt(1.f - std::exp(2.f * dpm_log_alpha(t))); }       // marginal_std
+static float dpm_lambda(float t) {                                                                 // marginal_lambda
+#pragma clang fp contract(off)
+    const float la = dpm_log_alpha(t);
+    return la - 0.5f * std::log(1.f - std::exp(2.f * la));
+}
+
+void dpm_schedule_table(int n, float cfk, std::vector<float>& times, std::vector<float>& model_times, std::vector<DpmStepCoefs>& steps,
+                        std::vector<float>* lambda_s) {
+#pragma clang fp contract(off)
+    DTTS_REQUIRE(n >= 2, "DPM-Solver++(2M) needs at least 2 steps (the reference asserts steps >= order)");
+    // torch.linspace(t_T = 1, t_0 = 1 / total_N, n + 1) in fp32 (:474, 1159-1173) as torch's CPU kernel fills it: the first half
+    // start + step * i, the second half end - step * (n - i), each a fused multiply-add
+    const float start = 1.f, end = (float)(1.0 / 1000), step = (end - start) / (float)n;
+    const int cnt = n + 1, half = cnt / 2;
+    times.resize(cnt);
+    for (int i = 0; i < cnt; ++i)
+        times[i] = i < half ? std::fma(step, (float)i, start) : std::fma(-step, (float)(cnt - 1 - i), end);
+    model_times.resize(n);
+    steps.resize(n);
+    if (lambda_s) lambda_s->resize(n);
+    for (int k = 0; k < n; ++k) {
+        const float s = times[k], t = times[k + 1];
+        model_times[k] = s * 1000.f;                                    // t_continuous * 1000 (vqvae/utils/diffusion.py:534)
+        DpmStepCoefs c;
+        c.cfk = cfk;
+        c.alpha_s = std::exp(dpm_log_alpha(s));
+        c.sigma_s = dpm_sigma(s);
+        const float lam_s = dpm_lambda(s), lam_t = dpm_lambda(t);
+        const float h = lam_t - lam_s;
+        c.ratio = dpm_sigma(t) / c.sigma_s;
+        c.c1 = std::exp(dpm_log_alpha(t)) * std::expm1(-h);
+        c.c2 = 0.5f * c.c1;
+        // the first step is first order; so is the last one below 10 steps (lower_order_final, :1195-1201)
+        c.order = (k == 0 || (n < 10 && k == n - 1)) ? 1 : 2;
+        c.inv_r0 = 0.f;
+        if (c.order == 2) {
+            const float h_0 = lam_s - dpm_lambda(times[k - 1]);
+            c.inv_r0 = 1.f / (h_0 / h);
+        }
+        steps[k] = c;
+        if (lambda_s) (*lambda_s)[k] = lam_s;
+    }
+}
+
 // AdaGN tables of the schedule: t_emb = time_embed(sinusoid(ts)) for every sampling step, then every ResBlock's
-// emb_layers (SiLU -> Linear) -> ss_table[rb][2C][NS]   (vqvae/diff_model.py:294, 108).  scratch: 3 C NS floats
-void Model::build_ss_table(const std::vector<int>& tmap, float* ss_table, float* scratch, int* ts_dev, hipStream_t s) {
-    const int C = cfg.diff_channels, NS = (int)tmap.size();
+// emb_layers (SiLU -> Linear) -> ss_table[rb][2C][NS]   (vqvae/diff_model.py:294, 108).  scratch: 3 C NS floats; ts_dev: NS words
+void Model::build_ss_table(const Schedule& sc, float* ss_table, float* scratch, void* ts_dev, hipStream_t s) {
+    const int C = cfg.diff_channels, NS = sc.n;
     float* sinus = scratch;
     float* t1 = scratch + (size_t)C * NS;
     float* temb = scratch + (size_t)2 * C * NS;
-    DTTS_CHECK_HIP(hipMemcpyAsync(ts_dev, tmap.data(), sizeof(int) * NS, hipMemcpyHostToDevice, s));
-    launch_timestep_sinusoid(ts_dev, NS, C, sinus, s);
+    if (sc.kind == 0) {
+        DTTS_CHECK_HIP(hipMemcpyAsync(ts_dev, sc.tmap.data(), sizeof(int) * NS, hipMemcpyHostToDevice, s));
+        launch_timestep_sinusoid(static_cast<const int*>(ts_dev), NS, C, sinus, s);
+    } else {                                                   // fractional model times (timestep_embedding, vqvae/diff_model.py:20-38)
+        DTTS_CHECK_HIP(hipMemcpyAsync(ts_dev, sc.ftimes.data(), sizeof(float) * NS, hipMemcpyHostToDevice, s));
+        launch_timestep_sinusoid(static_cast<const float*>(ts_dev), NS, C, sinus, s);
+    }
     ConvParams p;
     p.B = 1;
     p.Tin = NS;
@@ -462,6 +521,28 @@ Schedule& Model::schedule(int id) {
     throw Error(-1, "diffusion schedule " + std::to_string(id) + " is not cached (evicted or never built): call dtts_diff_schedule again");
 }
 
+int Model::cache_schedule(std::unique_ptr<Schedule> sc, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(sched_mu_);
+    for (size_t k = 0; k < sched_cache_.size(); ++k)
+        if (sched_cache_[k]->same_key(*sc)) {
+            std::rotate(sched_cache_.begin(), sched_cache_.begin() + k, sched_cache_.begin() + k + 1);   // most recently used first
+            return sched_cache_[0]->id;
+        }
+    // evict the least recently used; its destructor waits for the last launch that read its table
+    while (sched_cache_.size() >= MAX_SCHEDULES) sched_cache_.pop_back();
+    const int C = cfg.diff_channels, NS = sc->n;
+    const size_t fl = (size_t)n_resblocks_ * 2 * C * NS;
+    DTTS_CHECK_HIP(hipMalloc(&sc->mem, sizeof(float) * (fl + 3 * (size_t)C * NS) + sizeof(int) * NS));
+    float* base = static_cast<float*>(sc->mem);
+    sc->ss_table = base;
+    build_ss_table(*sc, base, base + fl, base + fl + 3 * (size_t)C * NS, s);
+    DTTS_CHECK_HIP(hipEventCreateWithFlags(&sc->used, hipEventDisableTiming));
+    DTTS_CHECK_HIP(hipEventRecord(sc->used, s));
+    sc->id = sched_next_id_++;
+    sched_cache_.insert(sched_cache_.begin(), std::move(sc));
+    return sched_cache_[0]->id;
+}
+
 int Model::diff_schedule(const int* timesteps, int n, hipStream_t s) {
     DTTS_REQUIRE(bound_ && sched0_.n > 0, "diffusion weights not bound");
     DTTS_REQUIRE(timesteps && n >= 1, "diff_schedule: empty timestep list");
@@ -471,31 +552,33 @@ int Model::diff_schedule(const int* timesteps, int n, hipStream_t s) {
     std::sort(tmap.begin(), tmap.end());
     tmap.erase(std::unique(tmap.begin(), tmap.end()), tmap.end());
     if (tmap == sched0_.tmap) return 0;
-    std::lock_guard<std::mutex> lk(sched_mu_);
-    for (size_t k = 0; k < sched_cache_.size(); ++k)
-        if (sched_cache_[k]->tmap == tmap) {
-            std::rotate(sched_cache_.begin(), sched_cache_.begin() + k, sched_cache_.begin() + k + 1);   // most recently used first
-            return sched_cache_[0]->id;
-        }
-    // evict the least recently used; its destructor waits for the last launch that read its table
-    while (sched_cache_.size() >= MAX_SCHEDULES) sched_cache_.pop_back();
     auto sc = std::make_unique<Schedule>();
     make_schedule(trained, tmap, cfg.cond_free_k, *sc);
-    const int C = cfg.diff_channels, NS = sc->n;
-    const size_t fl = (size_t)n_resblocks_ * 2 * C * NS;
-    DTTS_CHECK_HIP(hipMalloc(&sc->mem, sizeof(float) * (fl + 3 * (size_t)C * NS) + sizeof(int) * NS));
-    float* base = static_cast<float*>(sc->mem);
-    sc->ss_table = base;
-    build_ss_table(sc->tmap, base, base + fl, reinterpret_cast<int*>(base + fl + 3 * (size_t)C * NS), s);
-    DTTS_CHECK_HIP(hipEventCreateWithFlags(&sc->used, hipEventDisableTiming));
-    DTTS_CHECK_HIP(hipEventRecord(sc->used, s));
-    sc->id = sched_next_id_++;
-    sched_cache_.insert(sched_cache_.begin(), std::move(sc));
-    return sched_cache_[0]->id;
+    return cache_schedule(std::move(sc), s);
+}
+
+int Model::diff_schedule_dpm(int n, hipStream_t s) {
+    DTTS_REQUIRE(bound_ && sched0_.n > 0, "diffusion weights not bound");
+    DTTS_REQUIRE(n >= 2 && n <= cfg.diff_trained_steps, "diff_schedule_dpm: n out of [2, diff_trained_steps]");
+    auto sc = std::make_unique<Schedule>();
+    std::vector<float> times, mt;
+    std::vector<DpmStepCoefs> steps;
+    dpm_schedule_table(n, cfg.cond_free_k, times, mt, steps);
+    sc->kind = 1;
+    sc->n = n;
+    sc->cfk_k = cfg.cond_free_k;
+    sc->ftimes.resize(n);
+    sc->dpm.resize(n);
+    for (int i = 0; i < n; ++i) {                   // column i = solver step n - 1 - i
+        sc->ftimes[i] = mt[n - 1 - i];
+        sc->dpm[i] = steps[n - 1 - i];
+    }
+    return cache_schedule(std::move(sc), s);
 }
 
 int Model::diff_schedule_info(int sched_id, int* tmap, float* coefs, int cap) {
     const Schedule& sc = schedule(sched_id);
+    DTTS_REQUIRE(sc.kind == 0, "diff_schedule_coefs: not an integer-timestep schedule (DPM tables: dtts_dpm_schedule_table)");
     for (int i = 0; i < sc.n && i < cap; ++i) {
         if (tmap) tmap[i] = sc.tmap[i];
         if (coefs) {
@@ -557,7 +640,7 @@ void Model::build_diffusion(hipStream_t s) {
     float* scratch = persist_.f32(3 * (size_t)C * NS);
     int* ts_dev = persist_.i32(NS);
     sched0_.ss_table = ss_table;
-    build_ss_table(sched0_.tmap, ss_table, scratch, ts_dev, s);
+    build_ss_table(sched0_, ss_table, scratch, ts_dev, s);
 
     // ---- split-precision (3 x bf16) copies of the trunk's conv weights (conv_x3.h)
     std::vector<PackedConv*> hot = {&inp_block_, &integ1_, &integ2_, &out_conv_};
@@ -1183,6 +1266,25 @@ void Model::diff_forward_t(const float* x, const float* code_emb, const int* len
     DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
 }
 
+void Model::diff_forward_tf(const float* x, const float* code_emb, const int* lens_host, int B, int T, float timestep, int cond_free,
+                            float* out, hipStream_t s) {
+    gn_check();
+    DTTS_REQUIRE(bound_, "weights not bound");
+    DTTS_REQUIRE(std::isfinite(timestep) && timestep >= 0.f && timestep < (float)cfg.diff_trained_steps,
+                 "timestep out of [0, diff_trained_steps)");
+    if (timestep == std::floor(timestep)) {                           // an integer time: diff_forward_t's route, bit for bit
+        diff_forward_t(x, code_emb, lens_host, B, T, (int)timestep, cond_free, out, s);
+        return;
+    }
+    auto key = std::make_unique<Schedule>();                          // a one-column fractional schedule: only its AdaGN table is used
+    key->kind = 2;
+    key->n = 1;
+    key->ftimes = {timestep};
+    Schedule& sc = schedule(cache_schedule(std::move(key), s));
+    diff_forward_s(sc, x, code_emb, lens_host, B, T, 0, cond_free, out, s);
+    DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
+}
+
 void Model::diff_sample(const float* code_emb, const int* lens_host, int B, int T, unsigned long long seed,
                         const int* sample_ids_host, int n_steps, const float* x_init, const float* step_noise, float* mel_out,
                         int denorm, hipStream_t s) {
@@ -1194,9 +1296,13 @@ void Model::diff_sample_ex(int sched_id, int sampler, float eta, const float* co
                            float* mel_out, int denorm, hipStream_t s) {
     gn_check();
     DTTS_REQUIRE(bound_, "weights not bound");
-    DTTS_REQUIRE(sampler == 0 || sampler == 1, "sampler: 0 (p) or 1 (ddim)");
+    DTTS_REQUIRE(sampler == 0 || sampler == 1 || sampler == 2, "sampler: 0 (p), 1 (ddim) or 2 (dpmsolver++)");
     DTTS_REQUIRE(eta >= 0.f, "eta must be >= 0");
     Schedule& sc = schedule(sched_id);
+    const bool dpm = sampler == 2;
+    DTTS_REQUIRE(dpm == (sc.kind == 1), dpm ? "sampler 2 (dpmsolver++) runs on a DPM schedule (dtts_diff_schedule_dpm)"
+                                            : "samplers 0 / 1 run on an integer-timestep schedule (dtts_diff_schedule)");
+    DTTS_REQUIRE(!dpm || (eta == 0.f && !step_noise), "dpmsolver++ draws no noise: eta must be 0 and step_noise NULL");
     const int C = cfg.diff_channels, OC = cfg.diff_out_channels, MC = cfg.mel_channels;
     if (n_steps <= 0 || n_steps > sc.n) n_steps = sc.n;
     const size_t per_call = pair_ws_bytes(B, C, T);
@@ -1208,12 +1314,14 @@ void Model::diff_sample_ex(int sched_id, int sampler, float eta, const float* co
     const size_t integ_table = sizeof(float) * (size_t)n_steps * 2 * B * C * T;
     const bool env_pre = env_pre_on && (double)integ_table <= max_gb * 1073741824.0;
     const size_t integ_bytes = env_pre ? integ_table + integ_ws_bytes(integ_chunk(B + 1) * 2 * B, C, T) : 0;
-    ws().ensure(per_call + integ_bytes + sizeof(float) * ((size_t)2 * B * C * T + (size_t)2 * B * OC * T) + 8192);
+    const size_t hist_floats = dpm ? (size_t)B * MC * T : 0;          // DPM-Solver++(2M): the previous step's x0
+    ws().ensure(per_call + integ_bytes + sizeof(float) * ((size_t)2 * B * C * T + (size_t)2 * B * OC * T + hist_floats) + 8192);
     const PairPlan pl = plan_pair(lens_host, B, T, s);
     const int* lens2 = pl.lens2;
     const int* sids = upload_ints(sample_ids_host, B, s);
     float* cbuf0 = ws().f32((size_t)2 * B * C * T);
     float* out2 = ws().f32((size_t)2 * B * OC * T);
+    float* x0_hist = dpm ? ws().f32(hist_floats) : nullptr;
     const size_t half = (size_t)B * C * T;
     DTTS_CHECK_HIP(hipMemcpyAsync(cbuf0, code_emb, sizeof(float) * half, hipMemcpyDeviceToDevice, s));
     launch_broadcast_channels(uncond_, pl.Nu, C, T, cbuf0 + half, (long long)C * T, T, s);
@@ -1269,7 +1377,9 @@ void Model::diff_sample_ex(int sched_id, int sampler, float eta, const float* co
                           integ_all ? integ_all + (size_t)k * Bi * C * T : nullptr);
         const bool last = (k == n_steps - 1);
         const float* nz = step_noise ? step_noise + (size_t)k * B * MC * T : nullptr;
-        if (sampler == 1)
+        if (dpm)
+            launch_dpm_update(x, xbs, T, out2, (long long)OC * T, T, lens2, T, B, MC, sc.dpm[i], x0_hist, (denorm && last) ? 1 : 0, s);
+        else if (sampler == 1)
             launch_ddim_update(x, xbs, T, out2, (long long)OC * T, T, lens2, T, B, MC, sc.ddim(i, eta), seed, sids, i, nz,
                                (denorm && last) ? 1 : 0, s);
         else
@@ -1293,6 +1403,7 @@ void Model::diff_step(int sched_id, int sampler, float eta, float* x, const floa
     DTTS_REQUIRE(sampler == 0 || sampler == 1, "sampler: 0 (p) or 1 (ddim)");
     DTTS_REQUIRE(eta >= 0.f, "eta must be >= 0");
     Schedule& sc = schedule(sched_id);
+    DTTS_REQUIRE(sc.kind == 0, "diff_step runs on an integer-timestep schedule (DPM-Solver++: diff_step_dpm)");
     DTTS_REQUIRE(step >= 0 && step < sc.n, "step out of range");
     DTTS_REQUIRE(sample_ids_host, "sample_ids");
     const int C = cfg.diff_channels, OC = cfg.diff_out_channels, MC = cfg.mel_channels;
@@ -1312,6 +1423,28 @@ void Model::diff_step(int sched_id, int sampler, float eta, float* x, const floa
         launch_diff_update(x, (long long)MC * T, T, out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.p[step], seed, sids, step, noise, 0, s,
                            x0_out);
     if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
+}
+
+// one DPM-Solver++(2M) step (vqvae/utils/dpm_solver.py:1176-1208 per step) of DPM schedule `sched_id` at step index `step`, x in place
+void Model::diff_step_dpm(int sched_id, float* x, float* x0_hist, const float* code_emb, const int* lens_host, int B, int T, int step,
+                          float* x0_out, hipStream_t s) {
+    gn_check();
+    DTTS_REQUIRE(bound_, "weights not bound");
+    Schedule& sc = schedule(sched_id);
+    DTTS_REQUIRE(sc.kind == 1, "diff_step_dpm runs on a DPM schedule (dtts_diff_schedule_dpm)");
+    DTTS_REQUIRE(step >= 0 && step < sc.n, "step out of range");
+    DTTS_REQUIRE(x && x0_hist && code_emb, "x, x0_hist, code_emb");
+    const int C = cfg.diff_channels, OC = cfg.diff_out_channels, MC = cfg.mel_channels;
+    ws().ensure(pair_ws_bytes(B, C, T) + sizeof(float) * ((size_t)2 * B * C * T + (size_t)2 * B * OC * T) + 8192);
+    const PairPlan pl = plan_pair(lens_host, B, T, s);
+    float* cbuf0 = ws().f32((size_t)2 * B * C * T);
+    float* out2 = ws().f32((size_t)2 * B * OC * T);
+    const size_t half = (size_t)B * C * T;
+    DTTS_CHECK_HIP(hipMemcpyAsync(cbuf0, code_emb, sizeof(float) * half, hipMemcpyDeviceToDevice, s));
+    launch_broadcast_channels(uncond_, pl.Nu, C, T, cbuf0 + half, (long long)C * T, T, s);
+    diff_forward_pair(sc, x, cbuf0, pl.lens2, pl.lens_i, pl.umap, B, pl.Nu, T, step, out2, s);
+    launch_dpm_update(x, (long long)MC * T, T, out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.dpm[step], x0_hist, 0, s, x0_out);
+    DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
 }
 
 void Model::diff_conditioning(const float* refer, const int* lens_host, int B, int Tmax, float* cond_out, hipStream_t s) {

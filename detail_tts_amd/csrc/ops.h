@@ -32,6 +32,8 @@ void launch_broadcast_channels(const float* v, int B, int C, int T, float* y, lo
 
 // sinusoidal timestep embedding table, vqvae/diff_model.py:20-38: out[c, i] for timestep ts[i]; cos half first. out is [dim, n]
 void launch_timestep_sinusoid(const int* ts, int n, int dim, float* out, hipStream_t s);
+// the same at fp32 (fractional) timesteps: `timesteps[:, None].float() * freqs[None]` as the reference
+void launch_timestep_sinusoid(const float* ts, int n, int dim, float* out, hipStream_t s);
 
 // Philox normal fill (spec: oracle/philox.py / philox.h): out[b, 0..n) for (seed, sample_ids[b], stage, step), scaled
 void launch_philox_normal(float* out, long long bs, int n, int B, unsigned long long seed, const int* sample_ids, int stage,
@@ -61,6 +63,21 @@ struct DdimStepCoefs {   // one DDIM step (vqvae/utils/diffusion.py:744-783): fp
 void launch_ddim_update(float* x, long long x_bs, int x_cs, const float* model_out, long long m_bs, int m_cs, const int* lens,
                         int T, int B, int C, DdimStepCoefs k, unsigned long long seed, const int* sample_ids, int step,
                         const float* noise_override, int final_denorm, hipStream_t s, float* x0_out = nullptr);
+
+struct DpmStepCoefs {    // one DPM-Solver++(2M) step s -> t (vqvae/utils/dpm_solver.py:547-580, 796-831), fp32 as the reference computes them
+    float cfk;           // constant guidance scale: eps = eps_u + cfk (eps_c - eps_u)   (:322-330)
+    float alpha_s, sigma_s;   // data prediction x0 = (x - sigma_s eps) / alpha_s, no clamp   (:433-442)
+    float ratio;         // sigma_t / sigma_s
+    float c1;            // alpha_t * expm1(-h)
+    float c2;            // 0.5 * alpha_t * expm1(-h)   (second order)
+    float inv_r0;        // 1 / r0 = h / h_0             (second order)
+    int order;           // 1 or 2
+};
+// One DPM-Solver++(2M) update on the same [2B, 2C, T] (cond | uncond) forward output as launch_diff_update: guidance, x0 (no clamp),
+// x <- ratio x - c1 x0 [- c2 inv_r0 (x0 - x0_prev)].  x0_hist [B,C,T] holds the previous step's x0 (read when order == 2) and receives
+// this step's.  No noise is drawn.  `final_denorm` de-normalises the result; x0_out (optional) receives x0 as well.
+void launch_dpm_update(float* x, long long x_bs, int x_cs, const float* model_out, long long m_bs, int m_cs, const int* lens,
+                       int T, int B, int C, DpmStepCoefs k, float* x0_hist, int final_denorm, hipStream_t s, float* x0_out = nullptr);
 
 // y = a*x + b*z (generic elementwise with optional exp on second operand) used by the flow prior:
 // z_p = m + noise * exp(logs) * noise_scale  (vqvae/model_24k.py:860)

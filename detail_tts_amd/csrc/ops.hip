@@ -275,7 +275,8 @@ void launch_broadcast_channels(const float* v, int B, int C, int T, float* y, lo
     DTTS_CHECK_HIP(hipGetLastError());
 }
 
-__global__ void timestep_sinusoid_kernel(const int* ts, int n, int dim, float* out) {
+template <typename TS>   // int: the integer schedules' timesteps; float: fractional model times (DPM-Solver)
+__global__ void timestep_sinusoid_kernel(const TS* ts, int n, int dim, float* out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;   // over half*n
     const int half = dim / 2;
     if (i >= half * n) return;
@@ -287,7 +288,12 @@ __global__ void timestep_sinusoid_kernel(const int* ts, int n, int dim, float* o
 }
 
 void launch_timestep_sinusoid(const int* ts, int n, int dim, float* out, hipStream_t s) {
-    hipLaunchKernelGGL(timestep_sinusoid_kernel, dim3(cdiv(dim / 2 * n, 256)), dim3(256), 0, s, ts, n, dim, out);
+    hipLaunchKernelGGL(timestep_sinusoid_kernel<int>, dim3(cdiv(dim / 2 * n, 256)), dim3(256), 0, s, ts, n, dim, out);
+    DTTS_CHECK_HIP(hipGetLastError());
+}
+
+void launch_timestep_sinusoid(const float* ts, int n, int dim, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(timestep_sinusoid_kernel<float>, dim3(cdiv(dim / 2 * n, 256)), dim3(256), 0, s, ts, n, dim, out);
     DTTS_CHECK_HIP(hipGetLastError());
 }
 
@@ -410,6 +416,51 @@ void launch_ddim_update(float* x, long long x_bs, int x_cs, const float* model_o
     const int nblk = (C * T + 3) / 4;
     hipLaunchKernelGGL(ddim_update_kernel, dim3(cdiv(nblk, 256) > 64 ? 64 : cdiv(nblk, 256), B), dim3(256), 0, s, x, x_bs, x_cs,
                        model_out, m_bs, m_cs, lens, T, B, C, k, seed, sample_ids, step, noise_override, final_denorm, x0_out);
+    DTTS_CHECK_HIP(hipGetLastError());
+}
+
+// DPM-Solver++(2M) update (vqvae/utils/dpm_solver.py:433-442 data prediction, :547-580 first order, :796-831 second order, guidance
+// :322-330).  Same element walk and ragged lens as diff_update_kernel; no noise.  Every product and difference is rounded on its own
+// (no contraction), in the reference's order: its fp32 tensors are evaluated one operation at a time.
+__global__ void dpm_update_kernel(float* x, long long x_bs, int x_cs, const float* mo, long long m_bs, int m_cs, const int* lens,
+                                  int T, int B, int C, DpmStepCoefs k, float* x0_hist, int final_denorm, float* x0_out) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.y;
+    const int len = lens ? lens[b] : T;
+    float* xb = x + (long long)b * x_bs;
+    float* hb = x0_hist + (long long)b * C * T;
+    const float* mc = mo + (long long)b * m_bs;
+    const float* mu = mo + (long long)(B + b) * m_bs;
+    const int n = C * len;
+    const int nblk = (n + 3) / 4;
+    const bool second = k.order == 2;
+    for (int blk = blockIdx.x * blockDim.x + threadIdx.x; blk < nblk; blk += gridDim.x * blockDim.x) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = blk * 4 + i;
+            if (e >= n) break;
+            const int c = e / len, t = e - c * len;
+            const float xv = xb[(long long)c * x_cs + t];
+            const float eps_c = mc[(long long)c * m_cs + t];
+            const float eps_u = mu[(long long)c * m_cs + t];
+            const float eps = eps_u + k.cfk * (eps_c - eps_u);
+            const float x0 = (xv - k.sigma_s * eps) / k.alpha_s;          // a division, as the reference
+            const long long h = (long long)c * T + t;
+            float v = k.ratio * xv - k.c1 * x0;
+            if (second) v = v - k.c2 * (k.inv_r0 * (x0 - hb[h]));
+            hb[h] = x0;
+            if (x0_out) x0_out[(long long)b * C * T + h] = x0;
+            if (final_denorm) v = ((v + 1.f) * 0.5f) * (2.7f - (-11.512925465f)) + (-11.512925465f);
+            xb[(long long)c * x_cs + t] = v;
+        }
+    }
+}
+
+void launch_dpm_update(float* x, long long x_bs, int x_cs, const float* model_out, long long m_bs, int m_cs, const int* lens,
+                       int T, int B, int C, DpmStepCoefs k, float* x0_hist, int final_denorm, hipStream_t s, float* x0_out) {
+    const int nblk = (C * T + 3) / 4;
+    hipLaunchKernelGGL(dpm_update_kernel, dim3(cdiv(nblk, 256) > 64 ? 64 : cdiv(nblk, 256), B), dim3(256), 0, s, x, x_bs, x_cs,
+                       model_out, m_bs, m_cs, lens, T, B, C, k, x0_hist, final_denorm, x0_out);
     DTTS_CHECK_HIP(hipGetLastError());
 }
 

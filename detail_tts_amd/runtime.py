@@ -324,7 +324,8 @@ class Runtime:
 
     def diff_sample_ex(self, code_emb, seed, sample_ids, sched=0, sampler=0, eta=0.0, lens=None, n_steps=0, x_init=None, step_noise=None,
                        denorm=True):
-        """diff_sample on schedule `sched` (diff_schedule) with sampler 0 = p (ancestral) / 1 = ddim"""
+        """diff_sample on schedule `sched` (diff_schedule) with sampler 0 = p (ancestral) / 1 = ddim, or on a DPM schedule
+        (diff_schedule_dpm) with sampler 2 = dpmsolver++ (eta 0, no step_noise)"""
         _check(code_emb, "code_emb"); _check(x_init, "x_init"); _check(step_noise, "step_noise")
         B, _, T = code_emb.shape
         out = torch.zeros((B, self.cfg["diffusion"]["in_channels"], T), device=self.device, dtype=torch.float32)
@@ -353,6 +354,55 @@ class Runtime:
         li = _ints(lens)
         self._rc(self.lib.dtts_diff_forward_t(self.h, _ptr(x), _ptr(code_emb), li[0] if li else None, B, T, int(timestep),
                                               1 if cond_free else 0, _ptr(out), self._stream()))
+        return out
+
+    def diff_schedule_dpm(self, n):
+        """id of the DPM-Solver++(2M) schedule of n >= 2 steps (dtts_diff_schedule_dpm: built on the current stream on first use, then
+        cached on the handle with the integer schedules).  Call it outside any stream capture."""
+        sid = C.c_int(0)
+        self._rc(self.lib.dtts_diff_schedule_dpm(self.h, int(n), C.byref(sid), self._stream()))
+        return sid.value
+
+    def sampler_schedule(self, key, sampler):
+        """the schedule id of sampling_args' (schedule key, sampler id): DPM-Solver++ (2) keys on its step count, the others on their
+        model timesteps"""
+        return self.diff_schedule_dpm(key) if sampler == 2 else self.diff_schedule(key)
+
+    @staticmethod
+    def dpm_schedule_table(n):
+        """host-only (no GPU): DPM-Solver++(2M)'s fp32 tables of n steps (dtts_dpm_schedule_table) -> (times [n+1], model times [n],
+        coefs [n, 7]: alpha_s, sigma_s, lambda_s, sigma_t / sigma_s, alpha_t * expm1(-h), 1 / r0, order) in the solver's step order"""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 2:
+            raise ValueError(f"DPM-Solver++(2M) needs an integer n >= 2, not {n!r}")
+        lib = _lib.load()
+        times, mt, coefs = np.zeros(n + 1, np.float32), np.zeros(n, np.float32), np.zeros((n, 7), np.float32)
+        nout = C.c_int(0)
+        rc = lib.dtts_dpm_schedule_table(int(n), times.ctypes.data_as(_lib.c_float_p), mt.ctypes.data_as(_lib.c_float_p),
+                                         coefs.ctypes.data_as(_lib.c_float_p), int(n), C.byref(nout))
+        if rc != 0:
+            raise DttsError(f"libdetail_hip error {rc} in dtts_dpm_schedule_table({n})")
+        return times, mt, coefs
+
+    def diff_step_dpm(self, x, x0_hist, code_emb, step, sched, lens=None, return_x0=False):
+        """one DPM-Solver++(2M) step of DPM schedule `sched` at step index `step` (n - 1 = first): (new x, new x0 history[, x0]);
+        x0_hist holds the previous step's x0 (read by a second-order step; any values at the first step)"""
+        _check(x, "x"); _check(x0_hist, "x0_hist"); _check(code_emb, "code_emb")
+        B, _, T = x.shape
+        xo, ho = x.clone(), x0_hist.clone()
+        x0 = torch.zeros_like(x) if return_x0 else None
+        li = _ints(lens)
+        self._rc(self.lib.dtts_diff_step_dpm(self.h, int(sched), _ptr(xo), _ptr(ho), _ptr(code_emb), li[0] if li else None, B, T, int(step),
+                                             _ptr(x0), self._stream()))
+        return (xo, ho, x0) if return_x0 else (xo, ho)
+
+    def diff_forward_tf(self, x, timestep, code_emb=None, cond_free=False, lens=None):
+        """DiffusionTts.forward at a fp32 MODEL time in [0, 4000), fractional or not (integer values: diff_forward_t bit for bit)"""
+        _check(x, "x"); _check(code_emb, "code_emb")
+        B, _, T = x.shape
+        out = torch.zeros((B, self.cfg["diffusion"]["out_channels"], T), device=self.device, dtype=torch.float32)
+        li = _ints(lens)
+        self._rc(self.lib.dtts_diff_forward_tf(self.h, _ptr(x), _ptr(code_emb), li[0] if li else None, B, T, float(timestep),
+                                               1 if cond_free else 0, _ptr(out), self._stream()))
         return out
 
     # ------------------------------------------------------------------ stage C

@@ -30,17 +30,20 @@ class DiffusionTts:
 
     def forward(self, x, timesteps, aligned_conditioning=None, conditioning_latent=None, precomputed_aligned_embeddings=None,
                 conditioning_free=False, return_code_pred=False, lengths=None):
-        """vqvae/diff_model.py:262-322.  `timesteps` are model-side integer timesteps in [0, 4000), as _WrappedModel passes them
-        (vqvae/utils/diffusion.py:1282-1287); those of the default 50-step schedule use its bind-time tables."""
+        """vqvae/diff_model.py:262-322.  `timesteps` are model-side timesteps in [0, 4000): integers as _WrappedModel passes them
+        (vqvae/utils/diffusion.py:1282-1287; those of the default 50-step schedule use its bind-time tables), or fractional fp32 times
+        as k_diffusion_sample_loop passes them (t * 1000, :534-535; timestep_embedding takes `timesteps.float()`, :20-38)."""
         if precomputed_aligned_embeddings is None and not conditioning_free:
             precomputed_aligned_embeddings = self.timestep_independent(aligned_conditioning, conditioning_latent, x.shape[-1])
-        ts = set(int(t) for t in torch.as_tensor(timesteps).reshape(-1).tolist())
+        ts = set(torch.as_tensor(timesteps).reshape(-1).float().tolist())
         if len(ts) != 1:
             raise ValueError("all batch rows must share one timestep (as in p_sample_loop)")
         t = ts.pop()
         if not 0 <= t < 4000:
             raise ValueError(f"timestep {t} is outside the trained range [0, 4000)")
-        return self.rt.diff_forward_t(x.float().contiguous(), t, None if conditioning_free else precomputed_aligned_embeddings,
-                                      cond_free=conditioning_free, lens=lengths)
+        emb = None if conditioning_free else precomputed_aligned_embeddings
+        if t == int(t):
+            return self.rt.diff_forward_t(x.float().contiguous(), int(t), emb, cond_free=conditioning_free, lens=lengths)
+        return self.rt.diff_forward_tf(x.float().contiguous(), t, emb, cond_free=conditioning_free, lens=lengths)
 
     __call__ = forward

@@ -53,22 +53,31 @@ def do_spectrogram_diffusion(diffusion_model, diffuser, latents, conditioning_la
 
 
 def sampling_args(diffusion_steps=None, sampler="p", eta=0.0):
-    """Host-side check of infer()'s sampling arguments, before any launch -> (model timesteps, sampler id, eta).
-    diffusion_steps: None = 50 (the reference's infer_diffuser), else 1 .. 4000 steps of space_timesteps(4000, [N]);
-    sampler: "p" (ancestral, the reference's p_sample_loop) or "ddim" (ddim_sample_loop with `eta` >= 0)."""
+    """Host-side check of infer()'s sampling arguments, before any launch -> (schedule key, sampler id, eta).
+    diffusion_steps: None = 50 (the reference's infer_diffuser), else 1 .. 4000 steps of space_timesteps(4000, [N]) (2 .. 4000 for
+    "dpmsolver++", which needs steps >= its order 2); sampler: "p" (ancestral, the reference's p_sample_loop), "ddim" (ddim_sample_loop
+    with `eta` >= 0) or "dpmsolver++" (k_diffusion_sample_loop's DPM-Solver++(2M), eta must be 0).  The schedule key is the sorted model
+    timesteps for "p" / "ddim" and the step count N for "dpmsolver++" (Runtime.sampler_schedule)."""
     n = INFER_DIFFUSION_STEPS if diffusion_steps is None else diffusion_steps
     if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= TRAINED_DIFFUSION_STEPS:
         raise ValueError(f"diffusion_steps must be an integer in [1, {TRAINED_DIFFUSION_STEPS}], not {diffusion_steps!r}")
     if sampler == "dpm++2m":
-        raise NotImplementedError("sampler 'dpm++2m' is not implemented on the device: use 'p' or 'ddim'")
+        raise NotImplementedError("sampler 'dpm++2m' is not implemented on the device (in k-diffusion it names Karras-sigma "
+                                  "sample_dpmpp_2m): the reference's own DPM-Solver++(2M) path is sampler='dpmsolver++'")
     if sampler not in SAMPLERS:
-        raise ValueError(f"sampler must be 'p' or 'ddim', not {sampler!r}")
+        raise ValueError(f"sampler must be 'p', 'ddim' or 'dpmsolver++', not {sampler!r}")
     try:
         eta = float(eta)
     except (TypeError, ValueError):
         raise ValueError(f"eta must be a number >= 0, not {eta!r}") from None
     if not eta >= 0.0 or eta == float("inf"):
         raise ValueError(f"eta must be a finite number >= 0, not {eta!r}")
+    if sampler == "dpmsolver++":
+        if int(n) < 2:
+            raise ValueError(f"dpmsolver++ needs diffusion_steps >= 2 (its order), not {diffusion_steps!r}")
+        if eta != 0.0:
+            raise ValueError(f"dpmsolver++ draws no noise: eta must be 0, not {eta!r}")
+        return int(n), SAMPLERS[sampler], 0.0
     return sorted(space_timesteps(TRAINED_DIFFUSION_STEPS, [int(n)])), SAMPLERS[sampler], eta
 
 
@@ -150,7 +159,8 @@ class SynthesizerTrn:
         """vqvae/model_24k.py:774-810.  Returns wav [B,1,1024*n_max] (B=1 unless batch=True).
 
         diffusion_steps / sampler / eta: stage B's schedule (None = the reference's 50 steps) and sampler ("p" = the reference's
-        ancestral p_sample_loop, "ddim" = ddim_sample_loop with `eta`); see sampling_args.  Fewer steps cost proportionally less.
+        ancestral p_sample_loop, "ddim" = ddim_sample_loop with `eta`, "dpmsolver++" = the DPM-Solver++(2M) the reference's own
+        infer_diffuser configures, k_diffusion_sample_loop); see sampling_args.  Fewer steps cost proportionally less.
 
         stream_vocoder: stage C runs on a second HIP stream, its generator window by window (`vocoder_chunk` mel frames + halo,
         dtts_vocoder_stream; 0 = one shot).  With wait=False the call returns while stage C is still running - `self.vocoder_done` is the event
@@ -213,7 +223,7 @@ class SynthesizerTrn:
         code_emb = self.rt.diff_timestep_independent(lat, cond, n)
         mark("diff_cond")
         lens_t = [4 * v for v in n]
-        sched = self.rt.diff_schedule(sched_ts)
+        sched = self.rt.sampler_schedule(sched_ts, sampler_id)
         mel = self.rt.diff_sample_ex(code_emb, seed, sample_ids, sched=sched, sampler=sampler_id, eta=eta, lens=lens_t, denorm=True)
         mark("diff_sample")
         # ---- stage C (:805-809)
@@ -279,7 +289,7 @@ class SynthesizerTrn:
         sched_ts, sampler_id, eta = sampling_args(diffusion_steps, sampler, eta)
         dev = self.device
         cur = torch.cuda.current_stream(dev)
-        sched = self.rt.diff_schedule(sched_ts)      # built here, once: no table allocation inside the pipelined loop
+        sched = self.rt.sampler_schedule(sched_ts, sampler_id)      # built here, once: no table allocation inside the pipelined loop
         if self._gpt_stream is None:
             lo, hi = torch.cuda.Stream.priority_range() if hasattr(torch.cuda.Stream, "priority_range") else (0, -1)
             self._gpt_stream = torch.cuda.Stream(dev, priority=lo if os.environ.get("DTTS_STAGE_A_PRIORITY") == "low" else hi)

@@ -1,11 +1,12 @@
 """Sampler object mirroring the subset of the reference's SpacedDiffusion that inference uses
-(vqvae/utils/diffusion.py:179-228 + 1172-1272; p_sample_loop :654-742, ddim_sample_loop :819-899, sample_loop :640-652).  The
-arithmetic lives in libdetail_hip.so (dtts_diff_sample_ex); this class carries the schedule constants and the call surface."""
+(vqvae/utils/diffusion.py:179-228 + 1172-1272; p_sample_loop :654-742, ddim_sample_loop :819-899, k_diffusion_sample_loop :487-581,
+sample_loop :640-652).  The arithmetic lives in libdetail_hip.so (dtts_diff_sample_ex); this class carries the schedule constants and
+the call surface."""
 from __future__ import annotations
 
 import numpy as np
 
-SAMPLERS = {"p": 0, "ddim": 1}
+SAMPLERS = {"p": 0, "ddim": 1, "dpmsolver++": 2}
 
 
 def space_timesteps(num_timesteps, section_counts):
@@ -84,26 +85,35 @@ class SpacedDiffusion:
     # ---------------------------------------------------------------------------------------------------- sampling loops
     def _check(self, sampler):
         if sampler == "dpm++2m":
-            raise NotImplementedError("sampler 'dpm++2m' (the reference's k-diffusion DPM-Solver path, vqvae/utils/diffusion.py:487-581) "
-                                      "is not implemented on the device: use 'p' or 'ddim'")
+            raise NotImplementedError("sampler 'dpm++2m' is not implemented on the device (in k-diffusion the key names Karras-sigma "
+                                      "sample_dpmpp_2m): the reference's own DPM-Solver++(2M) path (vqvae/utils/diffusion.py:487-581) "
+                                      "is sampler='dpmsolver++'")
         if sampler not in SAMPLERS:
-            raise ValueError(f"sampler must be 'p' or 'ddim', not {sampler!r}")
+            raise ValueError(f"sampler must be 'p', 'ddim' or 'dpmsolver++', not {sampler!r}")
         if not self.conditioning_free:
             raise NotImplementedError("conditioning_free=False sampling (one unguided forward per step) is not implemented on the device")
-        if self.rescale_timesteps:
+        if self.rescale_timesteps and sampler != "dpmsolver++":
             raise NotImplementedError("rescale_timesteps=True (float timesteps) is not implemented on the device")
 
     def _loop(self, sampler, model, shape, noise, model_kwargs, seed, sample_ids, lens, eta, denorm=False):
         self._check(sampler)
         if eta < 0:
             raise ValueError("eta must be >= 0")
+        if sampler == "dpmsolver++":
+            if self.num_timesteps < 2:
+                raise ValueError("dpmsolver++ needs >= 2 steps (the reference asserts steps >= order)")
+            if self.conditioning_free_k != 2.0:
+                raise NotImplementedError("the device's DPM-Solver++ guidance scale is the model's cond_free_k = 2.0")
         emb = (model_kwargs or {}).get("precomputed_aligned_embeddings")
         if emb is None:
             raise ValueError("precomputed_aligned_embeddings is required (as in do_spectrogram_diffusion)")
         B = shape[0]
         sample_ids = list(range(B)) if sample_ids is None else sample_ids
         rt = model.rt
-        sched = rt.diff_schedule(self.timestep_map)
+        if sampler == "dpmsolver++":
+            sched = rt.diff_schedule_dpm(self.num_timesteps)
+        else:
+            sched = rt.diff_schedule(self.timestep_map)
         return rt.diff_sample_ex(emb, seed, sample_ids, sched=sched, sampler=SAMPLERS[sampler], eta=eta, lens=lens, x_init=noise,
                                  denorm=denorm)
 
@@ -116,9 +126,24 @@ class SpacedDiffusion:
         """vqvae/utils/diffusion.py:819-851 (ddim_sample :744-783 per step, Philox noise when eta > 0)"""
         return self._loop("ddim", model, shape, noise, model_kwargs, seed, sample_ids, lens, float(eta))
 
+    def k_diffusion_sample_loop(self, k_sampler, pbar, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                                device=None, model_kwargs=None, progress=False, seed=0, sample_ids=None, lens=None, **_):
+        """vqvae/utils/diffusion.py:487-581: DPM-Solver++(2M) over num_timesteps steps (vqvae/utils/dpm_solver.py, time_uniform,
+        multistep, order 2) with constant guidance cond_free_k; as in the reference, `k_sampler` is ignored.  x_T = `noise` (None: the
+        Philox STAGE_DIFF_INIT draw); no noise after it, no clamp.  `pbar` (may be None) is advanced by the num_timesteps model
+        evaluations once the loop is enqueued."""
+        if not isinstance(model_kwargs, dict):
+            raise ValueError("model_kwargs must be a dict (the reference asserts it)")
+        x = self._loop("dpmsolver++", model, shape, noise, model_kwargs, seed, sample_ids, lens, 0.0)
+        if pbar is not None:
+            pbar.update(self.num_timesteps)
+        return x
+
     def sample_loop(self, *args, **kwargs):
-        """vqvae/utils/diffusion.py:640-652: dispatch on self.sampler"""
+        """vqvae/utils/diffusion.py:640-652: dispatch on self.sampler ("dpmsolver++": k_diffusion_sample_loop)"""
         self._check(self.sampler)
+        if self.sampler == "dpmsolver++":
+            return self.k_diffusion_sample_loop(None, None, *args, **kwargs)
         if self.sampler == "ddim":
             return self.ddim_sample_loop(*args, **kwargs)
         return self.p_sample_loop(*args, **kwargs)

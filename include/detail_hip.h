@@ -209,7 +209,9 @@ int dtts_diff_schedule_coefs(dtts_handle* h, int id, int* tmap, float* coefs, in
 
 /* dtts_diff_sample on schedule `id` with sampler 0 = p_sample_loop (vqvae/utils/diffusion.py:654-742, 445-485) or
  * 1 = ddim_sample_loop (:654-742 over ddim_sample :744-783) with `eta` >= 0.  Other arguments as dtts_diff_sample;
- * step_noise [n_steps][B,128,T] replaces the Philox noise of the steps that draw it.  (id, sampler, eta) = (0, 0, 0) is dtts_diff_sample. */
+ * step_noise [n_steps][B,128,T] replaces the Philox noise of the steps that draw it.  (id, sampler, eta) = (0, 0, 0) is dtts_diff_sample.
+ * Sampler 2 = k_diffusion_sample_loop's DPM-Solver++(2M) (vqvae/utils/diffusion.py:487-581) on a schedule of dtts_diff_schedule_dpm:
+ * x_T (Philox or x_init), then one guided forward and one update per step, no further noise; eta must be 0 and step_noise NULL. */
 int dtts_diff_sample_ex(dtts_handle* h, int id, int sampler, float eta, const float* code_emb, const int* lens, int B, int T,
                         unsigned long long seed, const int* sample_ids, int n_steps, const float* x_init, const float* step_noise,
                         float* mel_out, int denorm, void* stream);
@@ -223,6 +225,33 @@ int dtts_diff_step(dtts_handle* h, int id, int sampler, float eta, float* x, con
  * model accepts any t.  Arguments as dtts_diff_forward. */
 int dtts_diff_forward_t(dtts_handle* h, const float* x, const float* code_emb, const int* lens, int B, int T, int timestep,
                         int cond_free, float* out, void* stream);
+
+/* DPM-Solver++(2M) of n >= 2 steps as k_diffusion_sample_loop runs it (vqvae/utils/diffusion.py:487-581: DPM_Solver.sample with
+ * dpmsolver++, order 2, multistep, time_uniform, lower_order_final; vqvae/utils/dpm_solver.py:1159-1201) on
+ * NoiseScheduleVP("linear", 0.025, 5.0) (:108-154), fp32 in the reference's order of operations.  HOST ONLY: no handle, no GPU.
+ * *n_out = n; with cap >= n: times [n + 1] = torch.linspace(1, 1e-3, n + 1) in fp32, model_times [n] = t_k * 1000 (the model's
+ * fractional timestep, :534-535), coefs [n][7] per step k (t_k -> t_{k+1}, the solver's order) {alpha(t_k), sigma(t_k), lambda(t_k),
+ * sigma(t_{k+1}) / sigma(t_k), alpha(t_{k+1}) * expm1(-h), 1 / r0 (0 for a first-order step), order} (:547-580, 796-831).
+ * Any of the three may be NULL. */
+int dtts_dpm_schedule_table(int n, float* times, float* model_times, float* coefs, int cap, int* n_out);
+
+/* The DPM-Solver++(2M) schedule of n steps (2 <= n <= diff_trained_steps): dtts_dpm_schedule_table's step scalars and the AdaGN table
+ * at its fractional model times (timestep_embedding, vqvae/diff_model.py:20-38), built and cached as dtts_diff_schedule (same cache,
+ * never shared with an integer schedule); step index i is solver step n - 1 - i.  Not inside a stream capture. */
+int dtts_diff_schedule_dpm(dtts_handle* h, int n, int* id_out, void* stream);
+
+/* One DPM-Solver++(2M) step (vqvae/utils/dpm_solver.py:1176-1208: model evaluation, guidance :322-330, x0 :433-442, first- or
+ * second-order update :547-580 / :796-831) of DPM schedule `id` at step index `step` (n - 1 = first): x [B,128,T] IN PLACE;
+ * x0_hist [B,128,T] holds the previous step's x0 (read by a second-order step) and receives this step's; x0_out (may be NULL)
+ * receives it too. */
+int dtts_diff_step_dpm(dtts_handle* h, int id, float* x, float* x0_hist, const float* code_emb, const int* lens, int B, int T, int step,
+                       float* x0_out, void* stream);
+
+/* dtts_diff_forward_t at a fp32 MODEL time in [0, diff_trained_steps), fractional as k_diffusion_sample_loop passes it
+ * (vqvae/utils/diffusion.py:534-535; timestep_embedding takes fractional timesteps, vqvae/diff_model.py:20-38).  An integer value
+ * is dtts_diff_forward_t bit for bit. */
+int dtts_diff_forward_tf(dtts_handle* h, const float* x, const float* code_emb, const int* lens, int B, int T, float timestep,
+                         int cond_free, float* out, void* stream);
 
 /* ---- stage C: flow-VAE front + HiFiGAN generator -------------------------------------------------- */
 

@@ -20,7 +20,7 @@ sys.path.insert(0, ROOT)
 
 from bench import L_TEXT, N_CODES, T_REF, PowerSampler  # noqa: E402
 
-CONFIGS = [("p", 50), ("ddim", 50), ("ddim", 25), ("ddim", 20), ("p", 25)]
+CONFIGS = [("p", 50), ("ddim", 50), ("ddim", 25), ("ddim", 20), ("p", 25), ("dpmsolver++", 50), ("dpmsolver++", 20), ("dpmsolver++", 10)]
 
 
 def main():
