@@ -28,6 +28,9 @@ struct AttnParams {
     int x3_tp = 0;
     // x3 only: q / k / v come as AttnPlanes images (qkv is ignored) written by the qkv conv
     const void* planes = nullptr;
+    // attention_x3b only: 1 = QK^T and PV as ONE fp16 product each (plane 0 of the Q / K / V images and of P) instead of three - the
+    // trunk's fp16 mode (option "trunk_fp16"); any other kernel refuses it
+    int p1 = 0;
     // attention_x3b only (set by its launcher): the keys of a (sample, head, query block) split over `ksplit` workgroups, whose waves
     // leave their unnormalised (O, l, m) in kpart; the last wave to arrive (kcount) merges them in split order
     int ksplit = 1;

@@ -72,9 +72,13 @@ __device__ __forceinline__ void split_pair_mix(float x, float y, unsigned& w0, u
     asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(w1) : "v"(w0), "v"(y));
 }
 
+// (P1 - the trunk's fp16 mode, AttnParams::p1: the product of the two plane-0 fragments alone; plane 1 of Q, K, V and P is then never
+// loaded, staged or computed)
 #define DTTS_X3B_MFMA(acc, A, Bq)                                                        \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[1], Bq[0], acc, 0, 0, 0);             \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[0], Bq[1], acc, 0, 0, 0);             \
+    if (!P1) {                                                                           \
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[1], Bq[0], acc, 0, 0, 0);         \
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[0], Bq[1], acc, 0, 0, 0);         \
+    }                                                                                    \
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[0], Bq[0], acc, 0, 0, 0);
 
 struct WaveState {
@@ -99,11 +103,12 @@ struct WaveState {
 //   kb_addr: this lane's byte address of K chunk (plane 0, c8 = hh, key q) of the stage that holds block b + 1's tile (+ its half)
 //   v_addr0 / v_addr1: byte address of V chunk (plane 0, j 0, hh, channel vch0 / vch1) of block b - 1; lanes q >= 16 pass the ones area
 //   GENERAL: the block class of b is NEAR or FAR_MASK (bias from the extended table / tail mask); else FAR (one bias, no mask)
-template <int PAR /* b & 1 */, bool DO_QK, bool DO_PV, bool DO_SM, bool GENERAL, int ABL>
+template <int PAR /* b & 1 */, bool DO_QK, bool DO_PV, bool DO_SM, bool GENERAL, int ABL, bool P1>
 __device__ __forceinline__ void attn_step(WaveState& st, const unsigned char* smem, unsigned kb_addr, unsigned v_addr0, unsigned v_addr1, bool near,
                                           const float* ext_lane, int lim, float bfar) {
     f16v& sq = st.s[PAR ^ 1];
     f16v& ss = st.s[PAR];
+    constexpr int NPLR = P1 ? 1 : NPL;                       // operand planes this instantiation reads
     if (DO_PV) {
         // The accumulators are pinned to v[200:231] HERE (physical-register constraints), so that the 32 multiplies can name their
         // registers: with one tied operand per element the allocator scattered the two tuples over single registers and re-assembled
@@ -157,13 +162,13 @@ __device__ __forceinline__ void attn_step(WaveState& st, const unsigned char* sm
 #pragma unroll
         for (int s = 0; s < 3; ++s)
 #pragma unroll
-            for (int pl = 0; pl < NPL; ++pl) ka[s][pl] = as_hf(*reinterpret_cast<const uint4*>(smem + kb_addr + pl * (KCH * 16) + s * (2 * KT * 16)));
+            for (int pl = 0; pl < NPLR; ++pl) ka[s][pl] = as_hf(*reinterpret_cast<const uint4*>(smem + kb_addr + pl * (KCH * 16) + s * (2 * KT * 16)));
     }
     if (DO_PV && !(ABL & 32)) {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int pl = 0; pl < NPL; ++pl) {
+            for (int pl = 0; pl < NPLR; ++pl) {
                 va[j][0][pl] = as_hf(*reinterpret_cast<const uint4*>(smem + v_addr0 + pl * VHALF + j * (2 * D * 16)));
                 va[j][1][pl] = as_hf(*reinterpret_cast<const uint4*>(smem + v_addr1 + pl * VHALF + j * (2 * D * 16)));
             }
@@ -255,6 +260,16 @@ __device__ __forceinline__ void attn_step(WaveState& st, const unsigned char* sm
 #pragma unroll
             for (int k = 0; k < 8; ++k)
                 pv[k] = __builtin_amdgcn_exp2f(GENERAL ? e[8 * j + k] - m_sub : fmaf(ss[8 * j + k], SU, c0));      // 1024 P: the scale is free in the exponent
+            if (P1) {                                        // fp16(1024 P) alone: one v_cvt_pk_f16_f32 per pair
+                typedef float f2 __attribute__((ext_vector_type(2)));
+                uint4 w0;
+                w0.x = __builtin_bit_cast(unsigned, __builtin_convertvector((f2){pv[0], pv[1]}, hf2));
+                w0.y = __builtin_bit_cast(unsigned, __builtin_convertvector((f2){pv[2], pv[3]}, hf2));
+                w0.z = __builtin_bit_cast(unsigned, __builtin_convertvector((f2){pv[4], pv[5]}, hf2));
+                w0.w = __builtin_bit_cast(unsigned, __builtin_convertvector((f2){pv[6], pv[7]}, hf2));
+                st.pf[j][0] = as_hf(w0);
+                continue;
+            }
             uint4 w0, w1;
             split_pair_mix(pv[0], pv[1], w0.x, w1.x);
             split_pair_mix(pv[2], pv[3], w0.y, w1.y);
@@ -265,7 +280,17 @@ __device__ __forceinline__ void attn_step(WaveState& st, const unsigned char* sm
         }
     }
     if (DO_SM && (ABL & 4)) st.need = 0;
-    if (DO_QK && DO_PV && DO_SM && !GENERAL && !(ABL & 28)) {
+    if (P1 && DO_QK && DO_PV && DO_SM && !GENERAL && !(ABL & 28)) {
+        // the hot instantiation of the one-product mode: 7 MFMAs (3 QK^T + 4 PV) against ~56 vector / transcendental instructions (the
+        // 72 of the three-product step less the 16 v_fma_mix of the P residual plane) = one MFMA, then eight
+        constexpr int M_MFMA = 0x8, M_VALU = 0x2 | 0x400;
+#pragma unroll
+        for (int g = 0; g < 7; ++g) {
+            __builtin_amdgcn_sched_group_barrier(M_MFMA, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(M_VALU, 8, 0);
+        }
+    }
+    if (!P1 && DO_QK && DO_PV && DO_SM && !GENERAL && !(ABL & 28)) {
         // the hot instantiation: one MFMA, then three or four vector / transcendental instructions (21 MFMAs : ~72)
         constexpr int M_MFMA = 0x8, M_VALU = 0x2 | 0x400;
 #define DTTS_X3B_SGB2                                          \
@@ -285,7 +310,7 @@ __device__ __forceinline__ void mfma_result_fence(f16v& a, f16v& b) {
     asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" : "+v"(a), "+v"(b));
 }
 
-template <int MINB, int ABL, bool KSPLIT = false>
+template <int MINB, int ABL, bool KSPLIT = false, bool ONEP = false>
 __global__ __launch_bounds__(256, MINB) void flash_attn_x3b_kernel(const AttnParams p) {
     constexpr float LOG2E = 1.4426950408889634f;
     constexpr int NW = 4, QPB = NW * QPW;
@@ -339,6 +364,20 @@ __global__ __launch_bounds__(256, MINB) void flash_attn_x3b_kernel(const AttnPar
     const unsigned char* lane_img = kvimg + lane16 + (size_t)jt0 * AttnPlanes::TILE_BYTES;
     auto dma_group = [&](int j1) __attribute__((always_inline)) {
         const int kt = j1 < ntiles ? j1 : ntiles - 1, vt = j1 < 1 ? 0 : j1 - 1;
+        if (ONEP) {
+            // plane 0 only: 12 pieces, three per wave - waves 0, 1 the two halves of K plane 0 (6 KiB, contiguous at the head of the tile
+            // image), waves 2, 3 plane 0 of V blocks 2 j1 - 2, 2 j1 - 1 (3 KiB each) -> the same stage / ring-slot addresses as below
+            const bool isk = wave < 2;
+            const int u = wave - 2;
+            const unsigned char* src = isk ? lane_img + (size_t)kt * AttnPlanes::TILE_BYTES + wave * 3072
+                                           : lane_img + (size_t)vt * AttnPlanes::TILE_BYTES + KBYTES + u * VHALF;
+            const unsigned dst = isk ? LDS_K + (j1 & 1) * KBYTES + wave * 3072 : LDS_V + ((2 * j1 - 2 + u) & 3) * VSLOT;
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i * 1024),
+                                                 (__attribute__((address_space(3))) void*)(smem + dst + i * 1024), 16, 0, 0);
+            return;
+        }
         const unsigned char* ksrc = lane_img + (size_t)kt * AttnPlanes::TILE_BYTES + wave * 1024;
         const unsigned kdst = LDS_K + (j1 & 1) * KBYTES + wave * 1024;
 #pragma unroll
@@ -360,7 +399,7 @@ __global__ __launch_bounds__(256, MINB) void flash_attn_x3b_kernel(const AttnPar
 #pragma unroll
         for (int s = 0; s < 3; ++s)
 #pragma unroll
-            for (int pl = 0; pl < NPL; ++pl)
+            for (int pl = 0; pl < (ONEP ? 1 : NPL); ++pl)
                 st.qf[s][pl] = as_hf(*reinterpret_cast<const uint4*>(himg + ((size_t)(pl * (D / 8) + 2 * s + hh) * Tq + tc) * 16));
     }
 #pragma unroll
@@ -398,7 +437,7 @@ __global__ __launch_bounds__(256, MINB) void flash_attn_x3b_kernel(const AttnPar
         const int lim = len - s0b - 4 * hh;                                  // key of register r is valid iff roff(r) < lim
         const float bfar = far_hi ? bias_hi : bias_lo;
         const float* ext_lane = ext_s + (s0b + 4 * hh - t + EXT_HALF);       // near blocks only: in range there
-        attn_step<PAR, DQ, DP, DS, GEN, ABL>(st, smem, kb_addr, va0, va1, !(far_hi || far_lo), ext_lane, lim, bfar);
+        attn_step<PAR, DQ, DP, DS, GEN, ABL, ONEP>(st, smem, kb_addr, va0, va1, !(far_hi || far_lo), ext_lane, lim, bfar);
     };
     using T1 = std::integral_constant<bool, true>;
     using T0 = std::integral_constant<bool, false>;
@@ -583,9 +622,14 @@ void launch_flash_attention_x3b(const AttnParams& p, hipStream_t stream) {
         AttnParams q = p;
         q.ksplit = S;
         x3_split_workspace(stream, (size_t)base * S, &q.kpart, &q.kcount);
-        auto kern = flash_attn_x3b_kernel<2, 0, true>;
+        auto kern = p.p1 ? flash_attn_x3b_kernel<2, 0, true, true> : flash_attn_x3b_kernel<2, 0, true>;
         lds_optin(reinterpret_cast<const void*>(kern), LDS_BYTES);
         hipLaunchKernelGGL(kern, grid, dim3(NW * 64), LDS_BYTES, stream, q);
+        DTTS_CHECK_HIP(hipGetLastError());
+        return;
+    }
+    if (p.p1) {          // one-product mode: the measurement builds and DTTS_ATTN_OCC do not apply
+        go(flash_attn_x3b_kernel<2, 0, false, true>);
         DTTS_CHECK_HIP(hipGetLastError());
         return;
     }

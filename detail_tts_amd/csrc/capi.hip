@@ -107,6 +107,13 @@ int dtts_set_option(dtts_handle* h, const char* key, int value) {
     DTTS_API_END(h)
 }
 
+int dtts_get_option(dtts_handle* h, const char* key, int* value) {
+    DTTS_API_BEGIN
+    if (!value) throw dtts::Error(-2, "dtts_get_option: value is null");
+    *value = h->m->get_option(key);
+    DTTS_API_END(h)
+}
+
 long long dtts_vocoder_ticket(dtts_handle* h) { return h && h->m ? h->m->vocoder_ticket() : 0; }
 int dtts_vocoder_check_active(dtts_handle* h) { return h && h->m && h->m->vocoder_check_active() ? 1 : 0; }
 

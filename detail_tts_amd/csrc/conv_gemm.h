@@ -87,6 +87,7 @@ struct ConvParams {
     int* next_sat = nullptr;       // raised when a scaled value leaves fp16's range (as launch_split_planes_ex)
     int ksplit = 1;
     int ksplit_max = 0;            // conv_x3: caller's cap on the split (0: the launcher's rule)
+    int p1 = 0;                    // conv_x3: 1 = one fp16 product (plane 0 of both operands, 32 channels per K-step) instead of three (conv_x3.h)
     int epi_vec = 0;               // conv_x3: y / res rows are 16-byte aligned -> LDS-staged epilogue with 16-byte stores (set by the launcher)
     float* kpart = nullptr;
     int* kcount = nullptr;

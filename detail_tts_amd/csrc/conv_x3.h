@@ -39,6 +39,8 @@ void launch_gn_split_planes(const float* x, long long x_bs, int x_cs, const int*
                             void* out, hipStream_t s, const int* ada_idx = nullptr);
 // uses p.w3 / p.x3 / p.x3_tp (+ the epilogue fields of ConvParams); stride 1, dilation 1, pad <= X3_HALO, no phases; gate (tanh * sigmoid on packed row pairs) + badd only
 // as a 1x1 conv without residual (EPI 4: the WaveNet in_layers over launch_split_planes_taps planes)
+// p.p1 (the trunk's fp16 mode, option "trunk_fp16"): ONE product h0 h0' on plane 0 of the same images, 32 channels per K-step, instead of
+// three (Cin a multiple of 32, no gate); plane 1 is neither fetched nor multiplied (conv_x3.hip)
 void launch_conv_x3(const ConvParams& p, hipStream_t s);
 
 // Split scratch of a launch stream (conv_x3's split-K slabs; the trunk attention's key-split partials use the same slot: launches on one

@@ -269,9 +269,18 @@ __global__ __launch_bounds__(1024) void gn_split_planes_reg_kernel(const float* 
 // ONCE, every tap reads it through a shifted (16-byte aligned) ds_read_b128; only the W tile changes per tap.
 // Every wave issues the SAME number of LDS-DMA instructions per step (5 for k = 1; 3, + 1 halo at the last tap, for k = 3), so the
 // counted wait is one immediate for all waves; VMEM loads complete in order.
-template <int EPI, bool KW3, int NSTG>
+//
+// P1 (the trunk's fp16 mode, option "trunk_fp16"): ONE product h0 h0' instead of three.  A K-step then covers 32 channels of PLANE 0
+// of the same operand images: its four "kinds" are the block's four 8-channel chunks instead of (plane, k-half), so the LDS layout, the
+// 5 pieces per step, the 10 fragment reads and every counted wait keep their form - a kind only maps to another chunk in HBM
+// (chunk_of) and a block is 4 chunks wide - while the step issues 12 MFMAs (2 x 3 tiles x 2 k-halves) for 32 channels instead of 36.
+// No piece, fragment read or MFMA of plane 1 exists in these instantiations; a tile runs half as many steps and barriers.
+template <int EPI, bool KW3, int NSTG, bool P1 = false>
 __global__ __launch_bounds__(256, (NSTG == 2 && EPI != 3) ? 3 : 2) void conv_x3_kernel(ConvParams p) {
     constexpr int KW = KW3 ? 3 : 1, D = NSTG - 1;       // D: prefetch distance in steps (W, X of k = 1) / channel blocks (X of k = 3)
+    constexpr int CB = P1 ? 4 : 2;                      // 8-channel chunks of a K-step's channel block
+    constexpr int NT = P1 ? 2 : 3;                      // MFMA terms of a K-step: (k-half, k-half) pairs / split cross products
+    auto chunk_of = [](int kind) { return P1 ? kind * NPL : (kind & 1) * NPL + (kind >> 1); };      // kind -> (chunk, plane) row of the block in HBM
     constexpr int XOFF = NSTG * WTILE;                  // LDS: W stages | X buffers | bias
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, lhi = lane >> 5;
@@ -305,7 +314,7 @@ __global__ __launch_bounds__(256, (NSTG == 2 && EPI != 3) ? 3 : 2) void conv_x3_
     const int m0 = mt * BM, n0 = nti * BN;
     const int nvalid = p.len_out ? p.len_out[b] : p.Nout;
     if (n0 >= nvalid) return;
-    const int C8 = p.Cin >> 3, call = p.Cin >> 4, Tp = p.x3_tp;
+    const int C8 = p.Cin >> 3, call = p.Cin >> (P1 ? 5 : 4), Tp = p.x3_tp;
     // split z owns channel blocks [cbeg, cend): the loop below indexes them from 0 through the shifted base pointers
     const int cbeg = (int)((long long)call * z / S), c16n = (int)((long long)call * (z + 1) / S) - cbeg, nks = KW * c16n;
     const int bin = p.x_bidx ? p.x_bidx[b] : b;
@@ -313,22 +322,22 @@ __global__ __launch_bounds__(256, (NSTG == 2 && EPI != 3) ? 3 : 2) void conv_x3_
     // `global_load_lds_dwordx4 v_lane16, s[ptr]`: no per-piece VALU address arithmetic, and the pointers advance by constant strides
     // (round 2 recomputed each piece's address from (step, kind, half) - 45 SALU + 12 VALU per K-step against 18 MFMAs).
     const unsigned lane16 = (unsigned)lane * 16u;
-    const unsigned char* wb8 = static_cast<const unsigned char*>(p.w3) + ((long long)m0 + (long long)(2 * cbeg) * NPL * p.CoutP) * 16;
+    const unsigned char* wb8 = static_cast<const unsigned char*>(p.w3) + ((long long)m0 + (long long)(CB * cbeg) * NPL * p.CoutP) * 16;
     const unsigned char* xb8 = static_cast<const unsigned char*>(p.x3) +
-                               ((long long)bin * C8 * NPL * Tp + n0 + (X3_HALO - p.pad) + (long long)(2 * cbeg) * NPL * Tp) * 16;
+                               ((long long)bin * C8 * NPL * Tp + n0 + (X3_HALO - p.pad) + (long long)(CB * cbeg) * NPL * Tp) * 16;
     const long long wtapB = (long long)C8 * NPL * p.CoutP * 16;           // bytes between taps
-    const long long wblkB = (long long)2 * NPL * p.CoutP * 16;            // bytes between 16-channel blocks (W)
-    const long long xblkB = (long long)2 * NPL * Tp * 16;                 //                              (X)
+    const long long wblkB = (long long)CB * NPL * p.CoutP * 16;           // bytes between channel blocks (W)
+    const long long xblkB = (long long)CB * NPL * Tp * 16;                //                              (X)
     auto dma = [&](const unsigned char* g, int lds_off) {
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + lane16),
                                          (__attribute__((address_space(3))) void*)(smem + lds_off), 16, 0, 0);
     };
     // This wave's pieces (1 KiB = 64 rows / columns of one (plane, k-half) "kind").  W: kind = wave, row halves 0 / 1.  X (k = 1): kind = wave,
     // column blocks 0..2.  X (k = 3): the 12 pieces of a channel block are spread over its three taps, piece tap * 4 + wave at tap `tap`.
-    const int wkind = wave, wpl = wkind >> 1, wh = wkind & 1;
-    const unsigned char* wq = wb8 + (long long)(wh * NPL + wpl) * p.CoutP * 16;          // W piece pointer of the step being ISSUED (row half 0)
+    const int wkind = wave;
+    const unsigned char* wq = wb8 + (long long)chunk_of(wkind) * p.CoutP * 16;          // W piece pointer of the step being ISSUED (row half 0)
     const int wlds = wkind * (BM * 16);                                                   // + stage * WTILE (+ 1024 for row half 1)
-    const unsigned char* xq = xb8 + (long long)(wh * NPL + wpl) * Tp * 16;               // k = 1: X pieces of the step being issued (column block 0)
+    const unsigned char* xq = xb8 + (long long)chunk_of(wkind) * Tp * 16;               // k = 1: X pieces of the step being issued (column block 0)
     const int xlds = XOFF + wkind * (BN * 16);
     // k = 3: per-tap (kind, column block) of this wave's X piece
     long long x3o[3];
@@ -336,11 +345,11 @@ __global__ __launch_bounds__(256, (NSTG == 2 && EPI != 3) ? 3 : 2) void conv_x3_
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
         const int j = t * 4 + wave, kind = j / 3, cb = j - kind * 3;
-        x3o[t] = ((long long)((kind & 1) * NPL + (kind >> 1)) * Tp + cb * 64) * 16;
+        x3o[t] = ((long long)chunk_of(kind) * Tp + cb * 64) * 16;
         x3l[t] = XOFF + kind * (BN * 16) + cb * 1024;
     }
     // k = 3 halo: lanes 0..7 fetch (kind = lane >> 1, column 192 + (lane & 1)); expressed against the lane16 offset every piece carries
-    const long long halo_lane = (lane < 2 * NK) ? (((long long)(((lane >> 1) & 1) * NPL + (lane >> 2)) * Tp + BN + (lane & 1)) * 16 - (long long)lane16) : 0;
+    const long long halo_lane = (lane < 2 * NK) ? (((long long)chunk_of(lane >> 1) * Tp + BN + (lane & 1)) * 16 - (long long)lane16) : 0;
     const unsigned char* xblk = xb8;                                                      // k = 3: block pointer of the X tile being issued
     auto issue_w = [&](int i, int stage) { dma(wq + i * 1024, stage * WTILE + wlds + i * 1024); };
     auto issue_x1 = [&](int i, int stage) { dma(xq + i * 1024, stage * XBUF + xlds + i * 1024); };
@@ -450,7 +459,8 @@ __global__ __launch_bounds__(256, (NSTG == 2 && EPI != 3) ? 3 : 2) void conv_x3_
             if (KW3) xblk += xblkB;
         }
     };
-    constexpr int TA[3] = {1, 0, 0}, TB[3] = {0, 1, 0};   // term-major: one cross product over the wave's 6 accumulators per group, smallest terms first
+    // term-major: one cross product over the wave's 6 accumulators per group, smallest terms first (P1: the two k-halves of the 32 channels)
+    constexpr int TA[3] = {P1 ? 0 : 1, P1 ? 1 : 0, 0}, TB[3] = {0, 1, 0};
     {
     hf8 a[2][NPL], bb[3][NPL];
     int ks = 0;
@@ -485,32 +495,39 @@ __global__ __launch_bounds__(256, (NSTG == 2 && EPI != 3) ? 3 : 2) void conv_x3_
                 const int nn = wn0 + j * 32 + l31 + TAPc;
                 return nn < BN ? xb_addr + lhi * (BN * 16) + nn * 16 + pl * (2 * BN * 16) : xb_addr + XMAIN + lhi * 32 + (nn - BN) * 16 + pl * 64;
             };
-            rd(a[0][1], a_addr(0, 1)); rd(bb[0][0], x_addr(0, 0)); rd(bb[1][0], x_addr(1, 0)); rd(bb[2][0], x_addr(2, 0));
-            rd(a[1][1], a_addr(1, 1));
-            rd(a[0][0], a_addr(0, 0)); rd(bb[0][1], x_addr(0, 1)); rd(bb[1][1], x_addr(1, 1)); rd(bb[2][1], x_addr(2, 1));
-            rd(a[1][0], a_addr(1, 0));
+            // (P1: the same ten reads in the order ITS two terms consume them - first k-half A 0 + X 0..2 | A 1 | second k-half A 0 + X 0..2 | A 1 -
+            // so the four counted waits keep their values and guard the registers of that order)
+            constexpr int PA0 = TA[0], PA1 = TA[1];
+            rd(a[0][PA0], a_addr(0, PA0)); rd(bb[0][0], x_addr(0, 0)); rd(bb[1][0], x_addr(1, 0)); rd(bb[2][0], x_addr(2, 0));
+            rd(a[1][PA0], a_addr(1, PA0));
+            rd(a[0][PA1], a_addr(0, PA1)); rd(bb[0][1], x_addr(0, 1)); rd(bb[1][1], x_addr(1, 1)); rd(bb[2][1], x_addr(2, 1));
+            rd(a[1][PA1], a_addr(1, PA1));
         }
+        auto uslot = [&](int slot) {
+            __builtin_amdgcn_sched_barrier(0);
+            if (slot < 2) issue_w(slot, SWI);
+            else if (!KW3) issue_x1(slot - 2, SXI);
+            else if (slot == 2) issue_x3(TAPc, SXI);
+            else if (slot == 3 && TAPc == 2) issue_halo(SXI);
+            __builtin_amdgcn_sched_barrier(0);
+        };
         int slot = 0;
 #pragma unroll
-        for (int t = 0; t < 3; ++t)
+        for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                if (ASM_READS && t == 0 && i == 0) asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(a[0][1]), "+v"(bb[0][0]), "+v"(bb[1][0]), "+v"(bb[2][0]));
-                if (ASM_READS && t == 0 && i == 1) asm volatile("s_waitcnt lgkmcnt(5)" : "+v"(a[1][1]));
-                if (ASM_READS && t == 1 && i == 0) asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(a[0][0]), "+v"(bb[0][1]), "+v"(bb[1][1]), "+v"(bb[2][1]));
-                if (ASM_READS && t == 1 && i == 1) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[1][0]));
+                if (ASM_READS && t == 0 && i == 0) asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(a[0][TA[0]]), "+v"(bb[0][0]), "+v"(bb[1][0]), "+v"(bb[2][0]));
+                if (ASM_READS && t == 0 && i == 1) asm volatile("s_waitcnt lgkmcnt(5)" : "+v"(a[1][TA[0]]));
+                if (ASM_READS && t == 1 && i == 0) asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(a[0][TA[1]]), "+v"(bb[0][1]), "+v"(bb[1][1]), "+v"(bb[2][1]));
+                if (ASM_READS && t == 1 && i == 1) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[1][TA[1]]));
 #pragma unroll
                 for (int j = 0; j < 3; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][TA[t]], bb[j][TB[t]], acc[i][j], 0, 0, 0);
-                if (slot < 5) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (slot < 2) issue_w(slot, SWI);
-                    else if (!KW3) issue_x1(slot - 2, SXI);
-                    else if (slot == 2) issue_x3(TAPc, SXI);
-                    else if (slot == 3 && TAPc == 2) issue_halo(SXI);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                if (slot < 5) uslot(slot);
                 ++slot;
             }
+        // (P1: four MFMA groups for five pieces - the fifth, the last X piece of a k = 1 step, follows the fourth)
+#pragma unroll
+        for (; slot < 5; ++slot) uslot(slot);
         // pointers of the step issued next: W one tap / one channel block further (the tap being ISSUED is (TAPc + D) % KW), X per block
         if (!KW3) {
             wq += wblkB;
@@ -557,7 +574,7 @@ __global__ __launch_bounds__(256, (NSTG == 2 && EPI != 3) ? 3 : 2) void conv_x3_
         const bool wlive = ks + D < nks, xlive = KW3 ? c16 + D < c16n : ks + D < nks;
         int slot = 0;
 #pragma unroll
-        for (int t = 0; t < 3; ++t)
+        for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -565,6 +582,8 @@ __global__ __launch_bounds__(256, (NSTG == 2 && EPI != 3) ? 3 : 2) void conv_x3_
                 if (slot < 5) issue_slot(slot, swi, sxi, wlive, xlive);
                 ++slot;
             }
+#pragma unroll
+        for (; slot < 5; ++slot) issue_slot(slot, swi, sxi, wlive, xlive);      // (P1: four groups, five pieces)
         advance();
     }
     }
@@ -1272,6 +1291,8 @@ void launch_conv_x3(const ConvParams& p_in, hipStream_t s) {
     }
     DTTS_REQUIRE(p.B > 0 && p.Nout > 0 && p.Cout > 0, "empty conv");
     DTTS_REQUIRE(p.Cin % 16 == 0 && p.CoutP % BM == 0, "conv_x3: channel padding");
+    const bool p1 = p.p1 != 0;
+    DTTS_REQUIRE(!p1 || (p.Cin % 32 == 0 && p.gate == GATE_NONE), "conv_x3 one-product mode: input channels a multiple of 32, no gate");
     const bool gated = p.gate == GATE_TANH_SIGMOID;         // WN in_layers as a 1x1 conv over the tap-expanded planes (launch_split_planes_taps)
     DTTS_REQUIRE(p.stride == 1 && p.dil == 1 && p.phases == 1 && (p.gate == GATE_NONE ? !p.badd : gated), "conv_x3: unsupported conv form");
     DTTS_REQUIRE(!gated || (p.KW == 1 && !gn && !p.qkv_planes && !p.res && p.epi_act == ACT_NONE && p.out_scale == 1.f && p.Cout % 2 == 0),
@@ -1316,15 +1337,27 @@ void launch_conv_x3(const ConvParams& p_in, hipStream_t s) {
     const int l4 = 4 * (WTILE + XBUF) + 3 * BM * (int)sizeof(float) + 16;      // the attribute is a maximum: every instantiation gets the 4-stage size
     const dim3 grid((unsigned)nwg);
     const double cols = (double)p.B * p.Nout;
-    const double flops = 2.0 * p.Cout * p.Cin * p.KW * cols;                      // fp32-equivalent; the MFMA pipe executes 3x this in fp16
+    const double flops = 2.0 * p.Cout * p.Cin * p.KW * cols;                      // fp32-equivalent; the MFMA pipe executes 3x this in fp16 (p1: 1x)
     const double bytes = 4.0 * cols * p.Cin + 4.0 * cols * p.Cout * (p.res ? 2.0 : 1.0) + 4.0 * (double)p.Cout * p.Cin * p.KW;
     {
         static const bool by_shape = []() { const char* v = getenv("DTTS_PROF_SHAPES"); return v && v[0] == '1'; }();
-        const char* tag = "conv_x3_kernel<128,192>";
-        if (by_shape) tag = p.KW == 3 ? "conv_x3 k3" : (p.Cout > 1024 ? "conv_x3 k1 M=2304" : (p.res ? "conv_x3 k1 +res" : "conv_x3 k1"));
+        const char* tag = p1 ? "conv_x3_kernel<128,192,fp16>" : "conv_x3_kernel<128,192>";
+        if (by_shape && p1) tag = p.KW == 3 ? "conv_x3 fp16 k3" : (p.Cout > 1024 ? "conv_x3 fp16 k1 M=2304" : (p.res ? "conv_x3 fp16 k1 +res" : "conv_x3 fp16 k1"));
+        else if (by_shape) tag = p.KW == 3 ? "conv_x3 k3" : (p.Cout > 1024 ? "conv_x3 k1 M=2304" : (p.res ? "conv_x3 k1 +res" : "conv_x3 k1"));
         ProfScope ps(tag, flops, bytes, s);
         const bool epi = p.epi_act != ACT_NONE || p.out_scale != 1.f;
+#define DTTS_LAUNCH_X3P1(E, K3)                                                                                        \
+    do {                                                                                                               \
+        if (nstg == 4) { lds_optin(reinterpret_cast<const void*>(conv_x3_kernel<E, K3, 4, true>), l4); hipLaunchKernelGGL((conv_x3_kernel<E, K3, 4, true>), grid, dim3(256), lds, s, p); } \
+        else if (nstg == 3) { lds_optin(reinterpret_cast<const void*>(conv_x3_kernel<E, K3, 3, true>), l4); hipLaunchKernelGGL((conv_x3_kernel<E, K3, 3, true>), grid, dim3(256), lds, s, p); } \
+        else { lds_optin(reinterpret_cast<const void*>(conv_x3_kernel<E, K3, 2, true>), l4); hipLaunchKernelGGL((conv_x3_kernel<E, K3, 2, true>), grid, dim3(256), lds, s, p); } \
+    } while (0)
 #define DTTS_LAUNCH_X3(E, K3)                                                                                          \
+    do {                                                                                                               \
+        if (p1) DTTS_LAUNCH_X3P1(E, K3);                                                                               \
+        else DTTS_LAUNCH_X3N(E, K3);                                                                                   \
+    } while (0)
+#define DTTS_LAUNCH_X3N(E, K3)                                                                                         \
     do {                                                                                                               \
         if (nstg == 4) { lds_optin(reinterpret_cast<const void*>(conv_x3_kernel<E, K3, 4>), l4); hipLaunchKernelGGL((conv_x3_kernel<E, K3, 4>), grid, dim3(256), lds, s, p); } \
         else if (nstg == 3) { lds_optin(reinterpret_cast<const void*>(conv_x3_kernel<E, K3, 3>), l4); hipLaunchKernelGGL((conv_x3_kernel<E, K3, 3>), grid, dim3(256), lds, s, p); } \
@@ -1335,7 +1368,7 @@ void launch_conv_x3(const ConvParams& p_in, hipStream_t s) {
             else DTTS_LAUNCH_X3(3, false);
         } else if (gated) {
             DTTS_REQUIRE(p.epi_vec, "conv_x3 gated epilogue: rows of y must be 16-byte aligned");
-            DTTS_LAUNCH_X3(4, false);
+            DTTS_LAUNCH_X3N(4, false);
         } else if (p.qkv_planes) {
             DTTS_REQUIRE(p.KW == 1 && !epi && !p.res && p.Cout % 144 == 0 && p.qkv_heads * 144 == p.Cout, "qkv planes epilogue: 48-channel heads, 1x1 conv");
             DTTS_LAUNCH_X3(2, false);
@@ -1347,6 +1380,8 @@ void launch_conv_x3(const ConvParams& p_in, hipStream_t s) {
             else DTTS_LAUNCH_X3(0, false);
         }
 #undef DTTS_LAUNCH_X3
+#undef DTTS_LAUNCH_X3N
+#undef DTTS_LAUNCH_X3P1
     }
     DTTS_CHECK_HIP(hipGetLastError());
 }

@@ -259,7 +259,15 @@ public:
 
     void set_option(const std::string& key, int value) {
         if (key == "two_streams") opt_two_streams_ = value != 0;
-        else if (key == "conv_x3") opt_conv_x3_ = value != 0;
+        else if (key == "conv_x3") {
+            DTTS_REQUIRE(value != 0 || !opt_trunk_fp16_, "conv_x3 = 0 (exact fp32 kernels) has no trunk_fp16 mode: set trunk_fp16 = 0 first");
+            opt_conv_x3_ = value != 0;
+        }
+        else if (key == "trunk_fp16") {
+            DTTS_REQUIRE(value == 0 || value == 1, "trunk_fp16: 0 or 1");
+            DTTS_REQUIRE(value == 0 || use_x3(), "trunk_fp16 = 1 needs the split-precision kernels (conv_x3 = 1): the exact fp32 kernels have no one-product mode");
+            opt_trunk_fp16_ = value != 0;     // (a kernel choice made at launch time: the only captured graphs, stage A's decode graphs, hold no trunk launch)
+        }
         else if (key == "gpt_graph") opt_gpt_graph_ = value != 0;
         else if (key == "x3_range_check") opt_range_check_ = value != 0;
         else if (key == "gpt_token_kernel") { opt_gpt_token_ = value != 0; if (value != 0) tok_failed_ = false; gpt_drop_graphs(); }
@@ -279,6 +287,11 @@ public:
         else if (key == "ln_reg") set_ln_channels_reg(value != 0);          // process-wide: the register-resident channel LayerNorm (ops.h)
         else if (key == "integ_pipeline") opt_integ_pipeline_ = value;      // 0 (default) / 1; -1: by batch size (on up to batch 4)
         else throw Error(-1, "unknown option '" + key + "'");
+    }
+    int get_option(const std::string& key) const {      // the options a caller restores after a per-call override
+        if (key == "conv_x3") return use_x3() ? 1 : 0;
+        if (key == "trunk_fp16") return opt_trunk_fp16_ ? 1 : 0;
+        throw Error(-1, "option '" + key + "' cannot be read back");
     }
     std::string last_error;
     dtts_config cfg;
@@ -473,6 +486,9 @@ public:
 private:
     int opt_cfg_streams_ = 0;             // chunks (= streams) the 2B-sample cond | uncond stack of a diffusion forward is cut into; 0 = by batch size
     bool opt_conv_x3_ = true;             // diffusion trunk convs on the 3 x bf16 split-precision path (conv_x3.h)
+    // option "trunk_fp16" (the reference's DiffusionTts.enable_fp16, vqvae/diff_model.py:157, 299-309): layers[1:] of the trunk run
+    // their convs and attention products as ONE fp16 product (ConvParams::p1 / AttnParams::p1) instead of three
+    bool opt_trunk_fp16_ = false;
     Arena w3_;                            // split-precision weight copies
     Arena w3_voc_;                        // ... of the generator's wide ResBlock1 convs
     static constexpr int MAX_CFG_STREAMS = 4;

@@ -312,6 +312,18 @@ static void attach_cols(ConvParams& p) {
         }
 }
 
+// Trunk fp16 mode (option "trunk_fp16"): set around the launches of a layer the mode covers - layers[1:] of DiffusionTts.layers, as the
+// reference's autocast (vqvae/diff_model.py:299-309) - by diff_forward_pair and the unit entries; run_conv and attention_block read it.
+// Per host thread: stage A's thread issues no trunk launch.
+static thread_local bool t_layer_p1 = false;
+namespace {
+struct LayerP1 {
+    bool prev;
+    explicit LayerP1(bool on) : prev(t_layer_p1) { t_layer_p1 = on; }
+    ~LayerP1() { t_layer_p1 = prev; }
+};
+}  // namespace
+
 void Model::run_conv(const PackedConv& pc, ConvParams p, hipStream_t s) const {
     p.w = pc.w;
     if (!p.bias) p.bias = pc.b;
@@ -323,6 +335,7 @@ void Model::run_conv(const PackedConv& pc, ConvParams p, hipStream_t s) const {
     if (p.x3) {
         DTTS_REQUIRE(pc.w3, "conv has no split-precision weights");
         p.w3 = pc.w3;
+        p.p1 = t_layer_p1 ? 1 : 0;
         attach_cols(p);
         launch_conv_x3(p, s);
         return;
@@ -761,6 +774,7 @@ void Model::attention_block(const AttnBlockW& w, const float* x, float* y, float
     p.y_cs = Ta;
     static const bool env_planes = []() { const char* v = getenv("DTTS_ATTN_PLANES"); return !(v && v[0] == '0'); }();
     const bool planes = x3 && attn_x3_enabled() && env_planes && D == AttnPlanes::D;
+    DTTS_REQUIRE(!t_layer_p1 || planes, "trunk_fp16: the attention has its one-product mode only on the qkv conv's operand images (split-precision path, head dim 48)");
     if (x3) {
         p.x3 = xs;
         p.x3_tp = x3_tp(T);
@@ -793,6 +807,7 @@ void Model::attention_block(const AttnBlockW& w, const float* x, float* y, float
     a.bias_tab = w.bias_tab;
     a.x3 = x3 && attn_x3_enabled();
     if (planes) a.planes = qkv;
+    a.p1 = t_layer_p1 ? 1 : 0;
     // the proj conv's input planes come straight from the attention epilogue; xs still holds the zero halo / tail columns that
     // gn_split_planes wrote for the qkv conv (same B, T, lens), and the qkv conv has consumed the rest
     const bool att_planes = a.x3 && D == 48 && w.bias_tab && T + 1 < x3_tp(T);      // (other head dims: fp32 attention, its output is split below)
@@ -939,6 +954,7 @@ void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* c
     int groups = 32;
     while (C % groups) groups /= 2;
     const bool x3 = use_x3();
+    DTTS_REQUIRE(!opt_trunk_fp16_ || x3, "trunk_fp16 = 1 needs the split-precision kernels (conv_x3 = 1)");
 
     // shared x path: inp_block + the x-half of integrating_conv (+ bias) on the B samples (vqvae/diff_model.py:296-298)
     float* xin = ws().f32((size_t)B * C * Ta);
@@ -1070,12 +1086,14 @@ void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* c
         float* t2 = bufC;
         for (size_t li = 0; li < layers_.size(); ++li) {   // output back into `cur` (x is dead after the residual add)
             const auto& l = layers_[li];
+            LayerP1 mode(opt_trunk_fp16_ && li >= 1);       // layers[0] keeps the three-product kernels (:305-307)
             const GnNext na = norm_of(l.at.gn_g, l.at.gn_b, ACT_NONE), nn = first_norm(li + 1, 0);
             res_block_fwd(sc, l.rb, cur, t1, t2, ab, lens, n, T, Ta, step, st, xs, nullptr, f, &na);
             attention_block(l.at, t2, cur, qkv, t1, ab, lens, n, T, Ta, st, xs, f, &nn);
         }
         for (size_t ti = 0; ti < tail_.size(); ++ti) {
             const GnNext nn = first_norm(layers_.size(), ti + 1);
+            LayerP1 mode(opt_trunk_fp16_);
             res_block_fwd(sc, tail_[ti], cur, t1, t2, ab, lens, n, T, Ta, step, st, xs, nullptr, f, &nn);
             std::swap(cur, t2);
         }
@@ -1566,9 +1584,14 @@ void Model::op_attention_block(const char* prefix, const float* x, const int* le
     float* att = ws().f32(act);
     float* ab = ws().f32((size_t)2 * B * C);
     // the trunk's blocks take the split-precision path exactly as inside diff_forward
+    bool p1 = false;                                    // the layer-index rule of the trunk's fp16 mode, as inside diff_forward
     for (auto* grp : {&integ_, &layers_})
-        for (auto& dl2 : *grp)
-            if (dl2.at.qkv.w == w.qkv.w) w = dl2.at;
+        for (size_t i = 0; i < grp->size(); ++i)
+            if ((*grp)[i].at.qkv.w == w.qkv.w) {
+                w = (*grp)[i].at;
+                p1 = opt_trunk_fp16_ && grp == &layers_ && i >= 1;
+            }
+    LayerP1 mode(p1);
     void* xs = (use_x3() && w.qkv.w3) ? ws().raw(x3_bytes(B, C, T)) : nullptr;
     attention_block(w, x, y, qkv, att, ab, dl, B, T, T, s, xs);
 }
@@ -1580,12 +1603,13 @@ void Model::op_resblock(const char* prefix, const float* x, const int* lens_host
     const int C = cfg.diff_channels;
     const ResBlockW* found = nullptr;
     const std::string pf(prefix);
-    auto check = [&](const ResBlockW& r, const std::string& name) {
-        if (name == pf) found = &r;
+    bool p1 = false;                                    // the layer-index rule of the trunk's fp16 mode, as inside diff_forward
+    auto check = [&](const ResBlockW& r, const std::string& name, bool covered) {
+        if (name == pf) { found = &r; p1 = opt_trunk_fp16_ && covered; }
     };
-    for (size_t i = 0; i < integ_.size(); ++i) check(integ_[i].rb, "diffusion.conditioning_timestep_integrator." + std::to_string(i) + ".resblk");
-    for (size_t i = 0; i < layers_.size(); ++i) check(layers_[i].rb, "diffusion.layers." + std::to_string(i) + ".resblk");
-    for (size_t i = 0; i < tail_.size(); ++i) check(tail_[i], "diffusion.layers." + std::to_string(layers_.size() + i));
+    for (size_t i = 0; i < integ_.size(); ++i) check(integ_[i].rb, "diffusion.conditioning_timestep_integrator." + std::to_string(i) + ".resblk", false);
+    for (size_t i = 0; i < layers_.size(); ++i) check(layers_[i].rb, "diffusion.layers." + std::to_string(i) + ".resblk", i >= 1);
+    for (size_t i = 0; i < tail_.size(); ++i) check(tail_[i], "diffusion.layers." + std::to_string(layers_.size() + i), true);
     DTTS_REQUIRE(found, "unknown resblock prefix");
     const size_t act = (size_t)B * C * T;
     ws().ensure(sizeof(float) * (act + (size_t)2 * B * C) + x3_bytes(B, C, T) + 8192);
@@ -1595,6 +1619,7 @@ void Model::op_resblock(const char* prefix, const float* x, const int* lens_host
     float* h1 = ws().f32(act);
     float* ab = ws().f32((size_t)2 * B * C);
     void* xs = use_x3() ? ws().raw(x3_bytes(B, C, T)) : nullptr;
+    LayerP1 mode(p1);
     res_block_fwd(sched0_, *found, x, h1, y, ab, dl, B, T, T, step, s, xs);
 }
 

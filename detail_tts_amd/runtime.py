@@ -103,6 +103,12 @@ class Runtime:
     def set_option(self, key, value):
         self._rc(self.lib.dtts_set_option(self.h, key.encode(), int(value)))
 
+    def get_option(self, key):
+        """"conv_x3" / "trunk_fp16" as the library holds them"""
+        v = C.c_int(0)
+        self._rc(self.lib.dtts_get_option(self.h, key.encode(), C.byref(v)))
+        return int(v.value)
+
     def profile_enable(self, on=True):
         """True / 1: MFMA kernels; 2: also the bandwidth-only helper kernels; False: off"""
         self.lib.dtts_profile_enable(int(on))

@@ -11,6 +11,18 @@ class DiffusionTts:
         self.in_channels = cfg["in_channels"]
         self.out_channels = cfg["out_channels"]
         self.num_heads = cfg["num_heads"]
+        if cfg.get("use_fp16", False):                          # vqvae/diff_model.py:157: the constructor stores use_fp16
+            self.enable_fp16 = True
+
+    @property
+    def enable_fp16(self):
+        """The reference's half-precision switch (vqvae/diff_model.py:157, 299-309: layers[1:] under autocast), settable as on its
+        module.  Here: option "trunk_fp16" - those layers' convs and attention products as one fp16 product, fp32 accumulation."""
+        return bool(self.rt.get_option("trunk_fp16"))
+
+    @enable_fp16.setter
+    def enable_fp16(self, on):
+        self.rt.set_option("trunk_fp16", 1 if on else 0)
 
     def get_conditioning(self, conditioning_input, lengths=None):
         """vqvae/diff_model.py:221-229: mel [B,128,T] -> [B,1536]"""

@@ -6,6 +6,7 @@ would be alone), the noise seed / per-utterance stream ids, and forced codes (pa
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import time
 from concurrent.futures import ThreadPoolExecutor
@@ -81,6 +82,20 @@ def sampling_args(diffusion_steps=None, sampler="p", eta=0.0):
     return sorted(space_timesteps(TRAINED_DIFFUSION_STEPS, [int(n)])), SAMPLERS[sampler], eta
 
 
+TRUNK_PRECISIONS = {"fp32": 0, "fp16": 1}
+
+
+def trunk_precision_arg(trunk_precision):
+    """Host-side check of infer()'s `trunk_precision`, before any launch -> None (what the model's config says) or the value of option
+    "trunk_fp16" for this call: "fp32" = the three-product split-precision trunk, "fp16" = the reference's use_fp16 mode
+    (vqvae/diff_model.py:299-309): layers[1:] of the trunk as single fp16 products with fp32 accumulation."""
+    if trunk_precision is None:
+        return None
+    if trunk_precision not in TRUNK_PRECISIONS:
+        raise ValueError(f"trunk_precision must be 'fp32' or 'fp16' (or None: the model's config), not {trunk_precision!r}")
+    return TRUNK_PRECISIONS[trunk_precision]
+
+
 class Generator:
     """vqvae/model_24k.py:221-296"""
 
@@ -147,6 +162,28 @@ class SynthesizerTrn:
     def eval(self):
         return self
 
+    def _check_trunk_precision(self, trunk_precision):
+        """-> the per-call value of option "trunk_fp16" (None: none); "fp16" without the split-precision kernels is refused here"""
+        prec = trunk_precision_arg(trunk_precision)              # (the value itself: no device, no model state)
+        if prec == 1 and not self.rt.get_option("conv_x3"):
+            raise ValueError("trunk_precision='fp16' needs the split-precision kernels (option conv_x3 = 1): the exact fp32 kernels "
+                             "have no one-product mode")
+        return prec
+
+    @contextlib.contextmanager
+    def _trunk_precision(self, prec):
+        """option "trunk_fp16" = prec around the launches of ONE diffusion; the previous value is back when the block ends, whatever
+        happened inside (the kernel choice is made at launch time, so the enqueued work keeps it)"""
+        if prec is None:
+            yield
+            return
+        prev = self.rt.get_option("trunk_fp16")
+        self.rt.set_option("trunk_fp16", prec)
+        try:
+            yield
+        finally:
+            self.rt.set_option("trunk_fp16", prev)
+
     def to(self, device):
         if torch.device(device) != self.device:
             raise NotImplementedError("re-create the model on the target device (weights are bound to one GPU)")
@@ -155,12 +192,17 @@ class SynthesizerTrn:
     # ------------------------------------------------------------------------------------------------------------
     def infer(self, text, text_length, refer, refer_lengths, noise_scale=NOISE_SCALE, *, batch=False, seed=None, sample_ids=None,
               forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False, return_lengths=False,
-              stream_vocoder=False, vocoder_chunk=256, wait=True, check_range=True, diffusion_steps=None, sampler="p", eta=0.0):
+              stream_vocoder=False, vocoder_chunk=256, wait=True, check_range=True, diffusion_steps=None, sampler="p", eta=0.0,
+              trunk_precision=None):
         """vqvae/model_24k.py:774-810.  Returns wav [B,1,1024*n_max] (B=1 unless batch=True).
 
         diffusion_steps / sampler / eta: stage B's schedule (None = the reference's 50 steps) and sampler ("p" = the reference's
         ancestral p_sample_loop, "ddim" = ddim_sample_loop with `eta`, "dpmsolver++" = the DPM-Solver++(2M) the reference's own
         infer_diffuser configures, k_diffusion_sample_loop); see sampling_args.  Fewer steps cost proportionally less.
+
+        trunk_precision: "fp32" / "fp16" for THIS call's diffusion (None = what the config's diffusion.use_fp16 / diffusion.enable_fp16
+        says): "fp16" is the reference's use_fp16 mode, layers[1:] of the trunk as single fp16 products (trunk_precision_arg); the
+        model's own setting is back when the call returns.
 
         stream_vocoder: stage C runs on a second HIP stream, its generator window by window (`vocoder_chunk` mel frames + halo,
         dtts_vocoder_stream; 0 = one shot).  With wait=False the call returns while stage C is still running - `self.vocoder_done` is the event
@@ -171,6 +213,7 @@ class SynthesizerTrn:
         THIS request (dtts_vocoder_check; the reference computes those convs in fp32).  With wait=False (or check_range=False) the call
         stays asynchronous: wait on `self.vocoder_done`, then call `self.check_vocoder()` before reading the waveform."""
         sched_ts, sampler_id, eta = sampling_args(diffusion_steps, sampler, eta)
+        prec = SynthesizerTrn._check_trunk_precision(self, trunk_precision)
         text = torch.as_tensor(text)
         refer = torch.as_tensor(refer)
         tl = torch.as_tensor(text_length).reshape(-1).tolist()
@@ -224,7 +267,8 @@ class SynthesizerTrn:
         mark("diff_cond")
         lens_t = [4 * v for v in n]
         sched = self.rt.sampler_schedule(sched_ts, sampler_id)
-        mel = self.rt.diff_sample_ex(code_emb, seed, sample_ids, sched=sched, sampler=sampler_id, eta=eta, lens=lens_t, denorm=True)
+        with self._trunk_precision(prec):
+            mel = self.rt.diff_sample_ex(code_emb, seed, sample_ids, sched=sched, sampler=sampler_id, eta=eta, lens=lens_t, denorm=True)
         mark("diff_sample")
         # ---- stage C (:805-809)
         if stream_vocoder:
@@ -263,7 +307,8 @@ class SynthesizerTrn:
 
     # ------------------------------------------------------------------------------------------------------------
     def infer_stream(self, requests, noise_scale=NOISE_SCALE, *, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False,
-                     vocoder_chunk=0, pair_stage_a=False, on_saturation="rerun_fp32", diffusion_steps=None, sampler="p", eta=0.0):
+                     vocoder_chunk=0, pair_stage_a=False, on_saturation="rerun_fp32", diffusion_steps=None, sampler="p", eta=0.0,
+                     trunk_precision=None):
         """Batch server: `infer(..., batch=True)` over a sequence of request batches, software-pipelined over three HIP streams.
 
         requests: iterable of dicts with keys text [B,Lt], text_length [B], refer [B,128,Tr], refer_lengths [B] and optionally seed,
@@ -284,9 +329,11 @@ class SynthesizerTrn:
         waveform is handed out as usual - the requests behind it, whose stages are already enqueued, are not lost (ADVICE r05);
         "raise": the error leaves the generator (and ends the stream).
 
-        diffusion_steps / sampler / eta: as in infer(), one schedule for every request of the stream."""
+        diffusion_steps / sampler / eta / trunk_precision: as in infer(), one schedule and one trunk mode for every request of the stream
+        (the option is set around each request's diffusion launches only, on this thread: nothing leaks into other calls)."""
         assert on_saturation in ("rerun_fp32", "raise")
         sched_ts, sampler_id, eta = sampling_args(diffusion_steps, sampler, eta)
+        prec = SynthesizerTrn._check_trunk_precision(self, trunk_precision)
         dev = self.device
         cur = torch.cuda.current_stream(dev)
         sched = self.rt.sampler_schedule(sched_ts, sampler_id)      # built here, once: no table allocation inside the pipelined loop
@@ -409,7 +456,8 @@ class SynthesizerTrn:
             cond = self.rt.diff_conditioning(refer, st["rl"])
             code_emb = self.rt.diff_timestep_independent(lat, cond, n)
             lens_t = [4 * v for v in n]
-            mel = self.rt.diff_sample_ex(code_emb, st["seed"], st["sids"], sched=sched, sampler=sampler_id, eta=eta, lens=lens_t, denorm=True)
+            with self._trunk_precision(prec):
+                mel = self.rt.diff_sample_ex(code_emb, st["seed"], st["sids"], sched=sched, sampler=sampler_id, eta=eta, lens=lens_t, denorm=True)
             ready = torch.cuda.Event()
             ready.record(cur)
             if tr:

@@ -376,8 +376,18 @@ int dtts_spectrogram(dtts_handle* h, const float* wav, const int* lens, int B, i
  *                 Without it the check is still on, through dtts_vocoder_ticket / dtts_vocoder_check (no synchronisation);
  *   "conv_x3"     (default 1): diffusion-trunk convs and attention, the generator's wide ResBlock1 convs and the flow's WaveNet in_layers on the split-precision path (every fp32 operand as two
  *                 scaled fp16 planes, three fp16 MFMA products per fp32 product, fp32 accumulate: fp32-GEMM-class error);
- *                 0 = the exact fp32-MFMA kernels. */
+ *                 0 = the exact fp32-MFMA kernels;
+ *   "trunk_fp16"  (default 0): the reference's DiffusionTts.enable_fp16 / config "use_fp16" (vqvae/diff_model.py:143-157, 299-309: every
+ *                 trunk layer except the first under autocast).  1 = layers[1:] of the diffusion trunk (9 of the 10 DiffusionLayers, the 3
+ *                 ResBlocks) run their convs and their attention products QK^T, PV as ONE fp16 product with fp32 accumulation - plane 0
+ *                 of the same operand images, 32 channels per K-step - instead of three.  layers[0], inp_block, integrating_conv, the
+ *                 conditioning integrator, the time embedding / AdaGN tables and the out conv keep the three-product kernels; GroupNorm,
+ *                 softmax, residual adds and every activation between kernels stay fp32.  All samplers, any step count.  Refused with
+ *                 conv_x3 = 0 (the exact fp32 kernels have no such mode), and conv_x3 = 0 is refused while it is 1.  A launch-time
+ *                 kernel choice: the captured graphs (stage A's decode graphs) hold no trunk launch, none is dropped. */
 int dtts_set_option(dtts_handle* h, const char* key, int value);
+/* Reads back "conv_x3" (1 only if DTTS_CONV_X3 does not disable it) or "trunk_fp16": what a caller needs to restore after a per-call override. */
+int dtts_get_option(dtts_handle* h, const char* key, int* value);
 
 /* ---- measurement ---------------------------------------------------------------------------------------------- */
 /* Per-launch hipEvent profiling of the MFMA kernels (conv GEMM, flash attention), recorded on the launch stream.
