@@ -68,6 +68,9 @@ SIGNATURES = {
     "dtts_gpt_finish": (C.c_int, [C.c_void_p, c_int_p, c_int_p, C.c_void_p]),
     "dtts_op_sample_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_int_p, C.c_int, C.c_void_p, C.c_int, C.c_float,
                                         C.c_float, C.c_float, c_int_p, C.c_void_p]),
+    "dtts_op_sample_logits_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_int_p, C.c_int, C.c_void_p, C.c_int, C.c_float,
+                                           C.c_float, C.c_float, C.c_float, C.c_int, c_int_p, C.c_void_p]),
+    "dtts_sampler_max_vocab": (C.c_int, []),
     "dtts_diff_p_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_ulonglong, c_int_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "dtts_gpt_latents": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, c_int_p, c_int_p, C.c_int, c_int_p, c_int_p, C.c_int,

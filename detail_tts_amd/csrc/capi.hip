@@ -252,11 +252,21 @@ int dtts_gpt_finish(dtts_handle* h, int* codes_out, int* ncodes_out, void* strea
 
 int dtts_op_sample_logits(dtts_handle* h, const float* logits, int R, int V, const int* history, int hist_len, const float* uniforms,
                           int top_k, float top_p, float temperature, float repetition_penalty, int* tokens_out, void* stream) {
+    return dtts_op_sample_logits_ex(h, logits, R, V, history, hist_len, uniforms, top_k, top_p, temperature, repetition_penalty, 0.f, 0,
+                                    tokens_out, stream);
+}
+
+int dtts_op_sample_logits_ex(dtts_handle* h, const float* logits, int R, int V, const int* history, int hist_len, const float* uniforms,
+                             int top_k, float top_p, float temperature, float repetition_penalty, float typical_mass, int suppress_eos,
+                             int* tokens_out, void* stream) {
     DTTS_API_BEGIN
-    h->m->op_sample_logits(logits, R, V, history, hist_len, uniforms, top_k, top_p, temperature, repetition_penalty, tokens_out,
-                           (hipStream_t)stream);
+    DTTS_REQUIRE(typical_mass >= 0.f && typical_mass <= 1.f, "op_sample_logits: typical_mass outside [0, 1] (0 = off)");      // NaN fails both
+    h->m->op_sample_logits(logits, R, V, history, hist_len, uniforms, top_k, top_p, temperature, repetition_penalty, typical_mass,
+                           suppress_eos, tokens_out, (hipStream_t)stream);
     DTTS_API_END(h)
 }
+
+int dtts_sampler_max_vocab(void) { return dtts::sampler_max_vocab(); }
 
 int dtts_diff_p_sample(dtts_handle* h, float* x, const float* code_emb, const int* lens, int B, int T, int step,
                        unsigned long long seed, const int* sample_ids, const float* noise, float* x0_out, void* stream) {

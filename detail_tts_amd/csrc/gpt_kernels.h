@@ -105,6 +105,7 @@ struct SamplerParams {
     long long* trace = nullptr;   // debug: wall-clock stamps of row 0 (DTTS_SAMPLER_TRACE = n: the n-th launch), normally null
 };
 void launch_sampler(const SamplerParams& p, hipStream_t s);
+int sampler_max_vocab();          // the largest V launch_sampler admits (from the kernel's LDS budget)
 
 // ---- one decode token as ONE persistent kernel (gpt_token.hip): 128 resident workgroups, activations exchanged through memory as
 // {value, tag} words.  Replaces the 5-launches-per-layer chain for sessions of <= 8 rows on the GPT-2 shape of the reference config.

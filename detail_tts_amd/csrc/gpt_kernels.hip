@@ -663,6 +663,15 @@ void launch_gather_last(const float* x, long long bs, int cs, const int* lens, i
 constexpr int SAMP_THREADS = 1024;
 constexpr int SORT_MAX = 16384;
 static_assert(SAMP_THREADS == 4 * 256, "sampler: one thread per bin of the four radix histograms");
+// ONE LDS budget per workgroup, static + dynamic (gfx950 holds 160 KB): the opt-in size and the largest vocabulary both follow from it.
+//   static : red[SAMP_THREADS / 64] + hist4[4 * 256] + sh_u[4] + sh_i[4]   (launch_sampler checks it against the compiled kernel)
+//   dynamic: sv[Vpad] float + skey[SORT_MAX] float + sidx[SORT_MAX] unsigned short
+constexpr int SAMP_LDS_BUDGET = 150 * 1024;
+constexpr int SAMP_LDS_STATIC = (int)sizeof(float) * (SAMP_THREADS / 64) + (int)sizeof(unsigned) * (4 * 256 + 4) + (int)sizeof(int) * 4;
+constexpr int SAMP_LDS_SORT = (int)(sizeof(float) + sizeof(unsigned short)) * SORT_MAX;
+constexpr int SAMP_LDS_DYNAMIC_MAX = SAMP_LDS_BUDGET - SAMP_LDS_STATIC;
+constexpr int SAMP_V_MAX = ((SAMP_LDS_DYNAMIC_MAX - SAMP_LDS_SORT) / (int)sizeof(float)) & ~3;      // Vpad = V rounded up to 4
+static_assert(SAMP_V_MAX >= 8194 && SAMP_V_MAX <= SORT_MAX && SAMP_V_MAX < 65535, "sampler: ids are unsigned short, one sort slot per id");
 
 __device__ __forceinline__ unsigned f2ord(float f) {
     const unsigned u = __float_as_uint(f);
@@ -1095,10 +1104,20 @@ __global__ __launch_bounds__(SAMP_THREADS) void sampler_kernel(const SamplerPara
 #undef SSTAMP
 }
 
+int sampler_max_vocab() { return SAMP_V_MAX; }
+
 void launch_sampler(const SamplerParams& p, hipStream_t s) {
-    DTTS_REQUIRE(p.V <= SORT_MAX && p.V < 65535, "vocabulary too large for the LDS sampler");
-    const size_t lds = sizeof(float) * (size_t)(((p.V + 3) & ~3) + SORT_MAX) + sizeof(unsigned short) * SORT_MAX;
-    lds_optin(reinterpret_cast<const void*>(sampler_kernel), 150 * 1024);
+    DTTS_REQUIRE(p.V >= 1 && p.V <= SAMP_V_MAX, "vocabulary too large for the LDS sampler");
+    const size_t lds = sizeof(float) * (size_t)((p.V + 3) & ~3) + SAMP_LDS_SORT;
+    // the static part of the budget is what the compiler really laid out, checked once
+    static const bool static_ok = []() {
+        hipFuncAttributes a;
+        DTTS_CHECK_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(sampler_kernel)));
+        return a.sharedSizeBytes <= (size_t)SAMP_LDS_STATIC;
+    }();
+    DTTS_REQUIRE(static_ok, "sampler: static LDS exceeds SAMP_LDS_STATIC");
+    DTTS_REQUIRE(lds <= (size_t)SAMP_LDS_DYNAMIC_MAX, "sampler: LDS request over the budget");
+    lds_optin(reinterpret_cast<const void*>(sampler_kernel), SAMP_LDS_DYNAMIC_MAX);
     // DTTS_SAMPLER_TRACE = n: the n-th launch records wall-clock stamps of row 0's phases and prints them (100 MHz clock)
     static const int trace_at = []() { const char* v = getenv("DTTS_SAMPLER_TRACE"); return v ? atoi(v) : 0; }();
     static int launches = 0;

@@ -219,7 +219,8 @@ public:
     void gpt_finish(int* codes_host, int* ncodes_host, hipStream_t s);
     int gpt_steps() const { return gs_.active ? gs_.steps : 0; }
     void op_sample_logits(const float* logits, int R, int V, const int* history_host, int hist_len, const float* uniforms, int top_k,
-                          float top_p, float temperature, float repetition_penalty, int* tokens_host, hipStream_t s);
+                          float top_p, float temperature, float repetition_penalty, float typical_mass, int suppress_eos, int* tokens_host,
+                          hipStream_t s);
     void gpt_latents(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host,
                      int Lt_max, const int* codes_host, const int* ncodes_host, int n_max, int B, float* latents_cm, int lat_stride,
                      hipStream_t s);

@@ -690,8 +690,10 @@ void Model::gpt_generate(const float* refer, const int* refer_lens_host, int Tr,
 
 // unit entry: the device sampler on given logits rows (HF logits processors + inverse-CDF draw), one token per row
 void Model::op_sample_logits(const float* logits, int R, int V, const int* history_host, int hist_len, const float* uniforms, int top_k,
-                             float top_p, float temperature, float repetition_penalty, int* tokens_host, hipStream_t s) {
-    DTTS_REQUIRE(R >= 1 && R <= GEMV_MAXB && V >= 2 && V < 65535, "op_sample_logits: rows 1..16");
+                             float top_p, float temperature, float repetition_penalty, float typical_mass, int suppress_eos,
+                             int* tokens_host, hipStream_t s) {
+    DTTS_REQUIRE(R >= 1 && R <= GEMV_MAXB, "op_sample_logits: rows 1..16");
+    DTTS_REQUIRE(V >= 2 && V <= sampler_max_vocab(), "op_sample_logits: vocabulary outside 2 .. the LDS sampler's maximum");
     ws().ensure((size_t)R * V + sizeof(int) * 4 * R + sizeof(GptCtl) + 16 * 256);
     unsigned char* seen = static_cast<unsigned char*>(ws().raw((size_t)R * V));
     int* finished = ws().i32(R);
@@ -710,6 +712,8 @@ void Model::op_sample_logits(const float* logits, int R, int V, const int* histo
     c.temperature = temperature;
     c.top_p = top_p;
     c.top_k = top_k;
+    c.typical_mass = typical_mass;
+    c.suppress_eos = suppress_eos;
     c.max_steps = 1;
     c.forced_u = uniforms;
     c.u_stride = 1;

@@ -596,15 +596,18 @@ class Runtime:
                                              _ptr(noise), _ptr(x0), self._stream()))
         return (xo, x0) if return_x0 else xo
 
-    def op_sample_logits(self, logits, history, uniforms, top_k=50, top_p=0.8, temperature=0.8, repetition_penalty=2.0):
-        """device sampler on logits rows [R, V] (R <= 16) with the rows' input_ids history [R, n] and one uniform per row -> token ids"""
+    def op_sample_logits(self, logits, history, uniforms, top_k=50, top_p=0.8, temperature=0.8, repetition_penalty=2.0,
+                         typical_mass=None, suppress_eos=False):
+        """device sampler on logits rows [R, V] (R <= 16) with the rows' input_ids history [R, n] and one uniform per row -> token ids.
+        typical_mass in (0, 1): the reference's TypicalLogitsWarper; suppress_eos: id V - 1 is never drawn."""
         _check(logits, "logits"); _check(uniforms, "uniforms")
         R, V = logits.shape
         hist = np.ascontiguousarray(np.asarray(history, np.int32).reshape(R, -1))
         out = np.zeros((R,), np.int32)
-        self._rc(self.lib.dtts_op_sample_logits(self.h, _ptr(logits), R, V, hist.ctypes.data_as(_lib.c_int_p), hist.shape[1], _ptr(uniforms),
-                                                int(top_k or 0), float(top_p if top_p is not None else 1.0), float(temperature),
-                                                float(repetition_penalty), out.ctypes.data_as(_lib.c_int_p), self._stream()))
+        self._rc(self.lib.dtts_op_sample_logits_ex(self.h, _ptr(logits), R, V, hist.ctypes.data_as(_lib.c_int_p), hist.shape[1],
+                                                   _ptr(uniforms), int(top_k or 0), float(top_p if top_p is not None else 1.0),
+                                                   float(temperature), float(repetition_penalty), float(typical_mass or 0.0),
+                                                   int(bool(suppress_eos)), out.ctypes.data_as(_lib.c_int_p), self._stream()))
         return out
 
     def op_philox_normal(self, n, seed, sample_ids, stage, step):

@@ -435,6 +435,15 @@ int dtts_op_conv1d(dtts_handle* h, const char* name, const float* x, const int* 
 int dtts_op_sample_logits(dtts_handle* h, const float* logits, int R, int V, const int* history, int hist_len,
                           const float* uniforms, int top_k, float top_p, float temperature, float repetition_penalty,
                           int* tokens_out, void* stream);
+/* dtts_op_sample_logits plus the two remaining sampler options of dtts_gpt_options: typical_mass in (0, 1) runs the reference's
+ * TypicalLogitsWarper (gpt/modules/typical_sampling.py:11-33) between the repetition penalty and the temperature (0 = off);
+ * suppress_eos != 0 sets the logit of id V - 1 (the stop token's place in a row) to -inf before every processor.
+ * V is limited by the sampler's LDS budget: 2 <= V <= dtts_sampler_max_vocab(), anything else is refused before a launch. */
+int dtts_op_sample_logits_ex(dtts_handle* h, const float* logits, int R, int V, const int* history, int hist_len,
+                             const float* uniforms, int top_k, float top_p, float temperature, float repetition_penalty,
+                             float typical_mass, int suppress_eos, int* tokens_out, void* stream);
+/* The largest vocabulary the device sampler holds in LDS (host-only, no device needed). */
+int dtts_sampler_max_vocab(void);
 /* Philox normal fill: out[b, 0..n) for (seed, sample_ids[b], stage, step) */
 int dtts_op_philox_normal(dtts_handle* h, float* out, int n, int B, unsigned long long seed, const int* sample_ids, int stage,
                           int step, void* stream);
