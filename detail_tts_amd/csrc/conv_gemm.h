@@ -95,5 +95,6 @@ struct ConvParams {
 };
 
 void launch_conv_gemm(const ConvParams& p, hipStream_t stream);
+void set_conv_small_tiles(int n);   // launches of at most n 128 x 128 tiles take the 64 x 64 tile: 0 = never, n < 0 = the default (DTTS_CONV_SMALL_TILES, else 384); process-wide
 
 }  // namespace dtts

@@ -9,6 +9,7 @@
 // read is a conflict-free ds_read_b32 of 32 consecutive floats per lane-half.  Global->LDS goes
 // through registers (double-buffered LDS, one barrier per K-step) because the input path applies
 // the fused prologue (GroupNorm affine + SiLU / leaky-relu, zero padding, per-sample length).
+#include <atomic>
 #include <cstdlib>
 #include "conv_gemm_kernel.h"
 
@@ -19,6 +20,15 @@ static int env_int(const char* name) {
     const char* v = getenv(name);
     return v ? atoi(v) : 0;
 }
+
+// option "conv_small_tiles" / DTTS_CONV_SMALL_TILES (process-wide, like ln_reg): launches of at most n 128 x 128 tiles take the 64 x 64
+// tile, 0 = never; n < 0 goes back to the default (the environment's value, else 384).  Read at launch time.
+static int conv_small_tiles_default() {
+    static const int n = []() { const char* v = getenv("DTTS_CONV_SMALL_TILES"); return v ? atoi(v) : 384; }();
+    return n;
+}
+static std::atomic<int> g_conv_small_tiles{-1};
+void set_conv_small_tiles(int n) { g_conv_small_tiles.store(n < 0 ? -1 : n, std::memory_order_relaxed); }
 
 void launch_conv_gemm(const ConvParams& p_in, hipStream_t stream) {
     static const int ablate = env_int("DTTS_CONV_ABLATE");
@@ -35,7 +45,9 @@ void launch_conv_gemm(const ConvParams& p_in, hipStream_t stream) {
     // is a serial chain of 64-cycle fp32 MFMAs, so the launch takes one tile's time however empty the chip is - 64 x 64 tiles cut that
     // chain to a quarter per K-step on four times the workgroups (same k order per output: identical sums).  DTTS_CONV_SMALL_TILES = n:
     // launches of at most n 128 x 128 tiles take the small tile (0: never).
-    static const int small_tiles = []() { const char* v = getenv("DTTS_CONV_SMALL_TILES"); return v ? atoi(v) : 384; }();
+    // (option "conv_small_tiles": set_conv_small_tiles above)
+    const int small_opt = g_conv_small_tiles.load(std::memory_order_relaxed);
+    const int small_tiles = small_opt >= 0 ? small_opt : conv_small_tiles_default();
     if (small_tiles > 0 && p.CoutP % 64 == 0 && fits(64) && (long long)cdiv(p.CoutP, 128) * cdiv(p.Nout, 128) * p.B <= small_tiles) {
         // ... and a small launch is bound by one memory latency per K-step (two-stage pipeline): 32-channel steps halve their number
         static const int small_bk = []() { const char* v = getenv("DTTS_CONV_SMALL_BK"); return v ? atoi(v) : 32; }();

@@ -286,6 +286,9 @@ public:
         else if (key == "attn_ksplit_cus") set_attn_ksplit_cus(value);
         else if (key == "attn_ksplit") set_attn_ksplit(value);             // process-wide: key split of the trunk attention's small launches (attention.h)
         else if (key == "ln_reg") set_ln_channels_reg(value != 0);          // process-wide: the register-resident channel LayerNorm (ops.h)
+        // process-wide: the small-launch tile rule of the exact fp32 conv (conv_gemm.h).  A kernel choice made at launch time; the only
+        // captured graphs, stage A's decode graphs, hold no conv_gemm launch (the prefill, which does, is never captured): nothing to drop
+        else if (key == "conv_small_tiles") set_conv_small_tiles(value);
         else if (key == "integ_pipeline") opt_integ_pipeline_ = value;      // 0 (default) / 1; -1: by batch size (on up to batch 4)
         else throw Error(-1, "unknown option '" + key + "'");
     }

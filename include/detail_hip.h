@@ -366,6 +366,11 @@ int dtts_spectrogram(dtts_handle* h, const float* wav, const int* lens, int B, i
  *   "ln_reg"      (default 1; process-wide): the channel LayerNorms of <= 1024 channels (GPT prefill / teacher-forced pass,
  *                 MelStyleEncoder, enc_p) hold a thread's channels in registers - one load pass instead of three; the same sums in the
  *                 same order, bit-identical output; env DTTS_LN_REG=0;
+ *   "conv_small_tiles" (default 384; process-wide): exact-fp32 conv launches (csrc/conv_gemm.h) of at most this many 128 x 128 tiles take
+ *                 the 64 x 64 tile (a quarter of the serial MFMA chain per K-step on four times the workgroups); 0 = never, so that the
+ *                 launcher picks among the 128- / 64- / 32-row tiles by shape alone - how tests/test_gpu_conv_tiles.py reaches every
+ *                 tile at a tiny shape; < 0 = back to the default; env DTTS_CONV_SMALL_TILES sets the default.  A launch-time kernel
+ *                 choice: the captured graphs (stage A's decode graphs) hold no conv launch, none is dropped;
  *   "integ_pipeline" (default 0): 1 (-1: up to batch 4) = only the first chunk of the conditioning_timestep_integrator's step outputs is
  *                 evaluated in front of the sampling loop, the later chunks on a stream of their own under the first sampling steps
  *                 (bit-identical; returns 1 ms at batch 1 but can cost a pipelined request 60 ms in a process with many live

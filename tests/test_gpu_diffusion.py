@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 from conftest import tol
+from conv_tile_probe import launches_of
 
 pytestmark = pytest.mark.gpu
 
@@ -36,15 +37,15 @@ def test_philox_normal_matches_spec(rt):
 
 
 @pytest.mark.parametrize("cfg", [
-    dict(cin=128, cout=768, k=3, pad=1, T=48),
-    dict(cin=768, cout=768, k=1, pad=0, T=200),
-    dict(cin=768, cout=256, k=3, pad=1, T=333),
-    dict(cin=200, cout=200, k=11, pad=25, dil=5, T=300),
-    dict(cin=100, cout=100, k=7, pad=9, dil=3, T=257),
-    dict(cin=50, cout=50, k=3, pad=1, T=500),
-    dict(cin=25, cout=25, k=11, pad=5, T=130),
-    dict(cin=12, cout=1, k=7, pad=3, T=1000),
-    dict(cin=128, cout=768, k=3, pad=1, stride=2, T=101),
+    dict(cin=128, cout=768, k=3, pad=1, T=48, tile="64,64,k32"),
+    dict(cin=768, cout=768, k=1, pad=0, T=200, tile="64,64,k32"),
+    dict(cin=768, cout=256, k=3, pad=1, T=333, tile="64,64,k32"),
+    dict(cin=200, cout=200, k=11, pad=25, dil=5, T=300, tile="64,64,k16"),
+    dict(cin=100, cout=100, k=7, pad=9, dil=3, T=257, tile="64,64,k16"),
+    dict(cin=50, cout=50, k=3, pad=1, T=500, tile="64,64,k32"),
+    dict(cin=25, cout=25, k=11, pad=5, T=130, tile="32,128,k16"),
+    dict(cin=12, cout=1, k=7, pad=3, T=1000, tile="32,128,k16"),
+    dict(cin=128, cout=768, k=3, pad=1, stride=2, T=101, tile="64,64,k32"),
 ])
 def test_conv1d_kernel(cfg):
     from detail_tts_amd.packing import pack_conv
@@ -59,7 +60,8 @@ def test_conv1d_kernel(cfg):
     r = Runtime({}, parts=(), extra={"t.wp": wp, "t.bp": bp})
     x = rs.randn(2, cin, T).astype(np.float32)
     lens = [T, max(1, T - 37)]
-    y = host(r.op_conv1d("t", dev(x), cout, k, stride=stride, dil=dil, pad=pad, lens_in=lens))
+    y, ran = launches_of(r, lambda: host(r.op_conv1d("t", dev(x), cout, k, stride=stride, dil=dil, pad=pad, lens_in=lens)))
+    assert ran == {f"conv_gemm_kernel<{cfg['tile']}>": 1}, ran      # the tile the launcher's rule picks today (the others: test_gpu_conv_tiles.py)
     for bi, L in enumerate(lens):
         ref = ops.conv1d(x[bi:bi + 1, :, :L], w, b, stride=stride, padding=pad, dilation=dil)[0]
         assert maxabs(y[bi, :, :ref.shape[1]], ref) < 2e-5, (cfg, bi)
@@ -70,14 +72,16 @@ def test_conv_transpose_as_phases():
     from detail_tts_amd.runtime import Runtime
     from oracle import ops
     rs = np.random.RandomState(1)
-    for (cin, cout, k, s, p, T) in [(400, 200, 16, 8, 4, 48), (200, 100, 8, 4, 2, 100), (100, 50, 2, 2, 0, 333), (25, 12, 2, 2, 0, 64)]:
+    for (cin, cout, k, s, p, T, tile) in [(400, 200, 16, 8, 4, 48, "64,64,k16"), (200, 100, 8, 4, 2, 100, "64,64,k16"), (100, 50, 2, 2, 0, 333, "64,64,k16"),
+                                          (25, 12, 2, 2, 0, 64, "32,128,k16")]:
         w = (rs.randn(cin, cout, k) / np.sqrt(cin)).astype(np.float32)
         b = rs.randn(cout).astype(np.float32)
         weq, pad = convtranspose_as_phases(w, s, p)
         wp, bp = pack_conv(weq, np.tile(b, s))
         r = Runtime({}, parts=(), extra={"t.wp": wp, "t.bp": bp})
         x = rs.randn(2, cin, T).astype(np.float32)
-        y = host(r.op_conv1d("t", dev(x), cout, weq.shape[2], pad=pad, phases=s))
+        y, ran = launches_of(r, lambda: host(r.op_conv1d("t", dev(x), cout, weq.shape[2], pad=pad, phases=s)))
+        assert ran == {f"conv_gemm_kernel<{tile}>": 1}, ran
         ref = ops.conv_transpose1d(x, w, b, stride=s, padding=p)
         assert y.shape == ref.shape
         assert maxabs(y, ref) < 2e-5, (cin, cout, k, s)
@@ -96,7 +100,8 @@ def test_gated_conv_epilogue():
     x = rs.randn(2, hid, T).astype(np.float32)
     a = ops.conv1d(x, w, b, padding=2)
     for gate, ref in ((1, np.tanh(a[:, :hid]) * ops.sigmoid(a[:, hid:])), (2, a[:, :hid] * ops.sigmoid(a[:, hid:]))):
-        y = host(r.op_conv1d("t", dev(x), 2 * hid, 5, pad=2, gate=gate))
+        y, ran = launches_of(r, lambda: host(r.op_conv1d("t", dev(x), 2 * hid, 5, pad=2, gate=gate)))
+        assert ran == {"conv_gemm_kernel<64,64,k16>": 1}, ran
         assert maxabs(y, ref) < 2e-5
 
 
