@@ -99,7 +99,7 @@ def build_variant(name, token_flags):
 
 
 def build_variant_all(name, extra_flags, only=None, drop_flags=()):
-    """Measurement builds (tools/round5_measure.sh): EVERY source (or those in `only`) compiled with `extra_flags` appended, as
+    """Measurement builds (python -m detail_tts_amd.build --variant <name> <flags>): EVERY source (or those in `only`) compiled with `extra_flags` appended, as
     libdetail_hip_<name>.so next to the product library (objects under csrc/build/variant_<name>/).  DTTS_LIB_PATH selects it."""
     build(verbose=False)
     vdir = os.path.join(CSRC, "build", "variant_" + name)

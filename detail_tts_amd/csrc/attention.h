@@ -21,15 +21,18 @@ struct AttnParams {
     const float* band = nullptr;
     int band_w = 0;
     float* ml_out = nullptr;      // optional [B,H,T,2] (running max, denominator) for the rel-value fix-up
-    int x3 = 0;                   // split-precision (3 x bf16) kernel (attention_x3.hip): head dim 48 + T5 bias only
-    // x3 only: write the output as split-precision planes [B][H*D/8][3][x3_tp][8 bf16] (conv_x3.h layout, column t + 1) instead
-    // of fp32 `out`; only columns t < len are written (halo / tail columns keep what the previous writer left: zeros)
+    int layout_pad = 0;           // unused.  Holds the place of the retired `x3` selector: the struct is the kernels' argument, and without
+                                  // these 4 bytes every later member moves by 8 - other scalar-load offsets in every attention kernel.
+                                  // Drop it with the next change that rebuilds those kernels' code anyway.
+    // planes != null only: write the output as split-precision planes [B][H*D/8][2][x3_tp][8 fp16] (conv_x3.h layout, column t + 1)
+    // instead of fp32 `out`; only columns t < len are written (halo / tail columns keep what the previous writer left: zeros)
     void* out_x3 = nullptr;
     int x3_tp = 0;
-    // x3 only: q / k / v come as AttnPlanes images (qkv is ignored) written by the qkv conv
+    // non-null selects the split-precision kernel (attention_x3b.hip: head dim 48 + T5 bias only): q / k / v come as AttnPlanes
+    // images written by the qkv conv (qkv is ignored).  Null: flash_attn_kernel on the fp32 rows.
     const void* planes = nullptr;
-    // attention_x3b only: 1 = QK^T and PV as ONE fp16 product each (plane 0 of the Q / K / V images and of P) instead of three - the
-    // trunk's fp16 mode (option "trunk_fp16"); any other kernel refuses it
+    // planes != null only: 1 = QK^T and PV as ONE fp16 product each (plane 0 of the Q / K / V images and of P) instead of three - the
+    // trunk's fp16 mode (option "trunk_fp16")
     int p1 = 0;
     // attention_x3b only (set by its launcher): the keys of a (sample, head, query block) split over `ksplit` workgroups, whose waves
     // leave their unnormalised (O, l, m) in kpart; the last wave to arrive (kcount) merges them in split order
@@ -55,9 +58,7 @@ struct AttnPlanes {
 };
 
 void launch_flash_attention(const AttnParams& p, hipStream_t stream);
-void launch_flash_attention_x3(const AttnParams& p, hipStream_t stream);   // called by launch_flash_attention when p.x3 (fp32 q, k, v)
-void launch_flash_attention_x3w(const AttnParams& p, hipStream_t stream);  // ... when the operands are AttnPlanes images (round 2-4 kernel: DTTS_ATTN_KERNEL=w)
-void launch_flash_attention_x3b(const AttnParams& p, hipStream_t stream);  // ... the block-skewed kernel (default)
+void launch_flash_attention_x3b(const AttnParams& p, hipStream_t stream);  // called by launch_flash_attention when p.planes
 void set_attn_ksplit(int n);      // key ranges per (sample, head, query block) of attention_x3b launches of <= 2 samples that do not fill the CUs: 1 = off, 2 .. 4 (default: up to 4); process-wide
 void set_attn_ksplit_cus(int n);  // ... split only while workgroups x S <= n (default 256)
 int attn_ksplit();

@@ -258,18 +258,13 @@ void launch_flash_attention(const AttnParams& p, hipStream_t stream) {
     dim3 grid(cdiv(p.T, QPB) * p.H * p.B);
     const char* tag = p.D == 48 ? "flash_attn_kernel<48>" : p.D == 64 ? "flash_attn_kernel<64>" : p.D == 96 ? "flash_attn_kernel<96>" : "flash_attn_kernel<192>";
     const double pairs = (double)p.B * p.H * (double)p.T * p.T * (p.causal ? 0.5 : 1.0);
-    if (p.x3 && p.D == 48 && p.bias_tab && !p.causal && !p.band && !p.ml_out) {
-        static const bool old_kernel = []() { const char* v = getenv("DTTS_ATTN_KERNEL"); return v && v[0] == 'w'; }();
-        DTTS_REQUIRE(!p.p1 || (p.planes && !old_kernel), "one-product attention: only the block-skewed kernel on operand images has it");
-        ProfScope ps3(p.planes ? (old_kernel ? "flash_attn_x3w_kernel" : (p.p1 ? "flash_attn_x3b_kernel<fp16>" : "flash_attn_x3b_kernel")) : "flash_attn_x3_kernel<48>", 4.0 * pairs * p.D,
-                      4.0 * (double)p.B * p.H * p.D * p.T * 4.0, stream);
-        if (p.planes && old_kernel) launch_flash_attention_x3w(p, stream);
-        else if (p.planes) launch_flash_attention_x3b(p, stream);
-        else launch_flash_attention_x3(p, stream);
+    if (p.planes) {          // the split-precision kernel on the qkv conv's operand images (attention_x3b.hip)
+        ProfScope ps3(p.p1 ? "flash_attn_x3b_kernel<fp16>" : "flash_attn_x3b_kernel", 4.0 * pairs * p.D, 4.0 * (double)p.B * p.H * p.D * p.T * 4.0, stream);
+        launch_flash_attention_x3b(p, stream);
         return;
     }
-    DTTS_REQUIRE(!p.p1, "one-product attention needs the split-precision kernel (head dim 48, T5 bias)");
-    DTTS_REQUIRE(!p.out_x3, "split-precision attention output needs the x3 kernel (head dim 48, T5 bias)");
+    DTTS_REQUIRE(!p.p1, "one-product attention needs operand images (split-precision kernel: head dim 48, T5 bias)");
+    DTTS_REQUIRE(!p.out_x3, "split-precision attention output needs operand images (split-precision kernel: head dim 48, T5 bias)");
     ProfScope ps(tag, 4.0 * pairs * p.D, 4.0 * (double)p.B * p.H * p.D * p.T * 4.0, stream);
     auto lds = [](int D) { const int nb = D <= 96 ? 2 : 1; return sizeof(float) * (size_t)(nb * D * KPITCH + nb * KT * (D + 4) + 2 * BIAS_CLIP + 1); };
     switch (p.D) {

@@ -2,15 +2,28 @@
 // (build.py reads the line above: no NaN canonicalisation in front of every v_max3_f32; infinities keep their meaning.)
 // Split-precision flash attention of the diffusion trunk, software-pipelined over 32-key blocks (head dim 48, T5 relative-position bias;
 // operands = the AttnPlanes images the qkv conv wrote; vqvae/utils/diff_util.py:136-215 AttentionBlock / QKVAttentionLegacy,
-// vqvae/utils/xtransformers.py:146-186 RelativePositionBias).
+// vqvae/utils/xtransformers.py:146-186 RelativePositionBias).  The one split-precision attention kernel of the library.
 //
-// Arithmetic, layouts and the lane <-> key mapping are those of attention_x3w.hip (the round 2 - 4 kernel, kept behind
-// DTTS_ATTN_KERNEL=w for A/B runs):
-//   S^T[key 32, query 32] += K^T[key, c 16] Q[c 16, query]      3 channel steps x 3 split products   (v_mfma_f32_32x32x16_f16)
-//   O[c 32, query 32]     += V[c, key 16] P^T[key 16, query]    2 channel tiles x 2 key steps x 3 split products
-// a lane (query q = lane & 31, half hh = lane >> 5) holds the 16 keys (r & 3) + 8 (r >> 2) + 4 hh of its query per 32-key block, and
-// those registers are the B operand of the PV product.  What changed is the SCHEDULE and the vector-instruction count (VERDICT r04
-// item 1: 312 vector instructions against 42 MFMAs per 64-key tile, matrix pipe busy 34 %):
+// Shape.  v_mfma_f32_16x16x32_f16 sustains only half the flops per cycle of v_mfma_f32_32x32x16_f16 on gfx950 (tools/ubench/
+// mfma_peak16.hip: 1.3 vs 2.5 PFLOP/s), so a wave owns 32 queries and BOTH products run on the 32 x 32 instruction:
+//   S^T[key 32, query 32] += K^T[key, c 16] Q[c 16, query]      3 channel steps (D = 48 = 3 x 16: no half-used instruction)
+//   O[c 32, query 32]     += V[c, key 16] P^T[key 16, query]    2 channel tiles (48 of 64 rows used) x 2 key steps per 32-key block
+// Every fp32 operand is two scaled fp16 planes (a = h0 + h1, 22 bits: split3.h, conv_x3.h) and a product is the three significant
+// cross products h1 h0', h0 h1', h0 h0', smallest first, accumulated in fp32: 3 x 3 + 2 x 2 x 3 = 21 MFMAs per 32-key block.
+// The score tile comes out TRANSPOSED, so a lane (query q = lane & 31, half hh = lane >> 5) holds 16 keys of its query per 32-key
+// block - rows (r & 3) + 8 (r >> 2) + 4 hh of the MFMA C layout - and those registers ARE the B operand of the PV product, because
+// the V chunks are stored in the matching key order: k-slot 8 hh + e of key step j  <->  key 16 j + (e & 3) + 8 (e >> 2) + 4 hh
+// (attention.h: AttnPlanes).  256 threads = 4 waves x 32 queries share each 64-key K / V tile (24 KiB image, moved by LDS-DMA).
+//
+// Scales.  Q carries scale * log2(e) * 16 and K carries 16, so the score accumulator holds 256 S (undone by the fma that adds the
+// bias: SU); P = exp2(s - m + 10) (the 1024 is free in the exponent) and V carries 16, so the output accumulator holds 16384 O, and
+// the denominator is accumulated from the same scaled P: O = acc / (16 l').
+// Lazy running maximum (M_SLACK).  A query's maximum m is raised - and the accumulators rescaled - only when a block's maximum
+// exceeds it by more than 2^3; otherwise P = exp2(e - m + 10) <= 8192 stays inside fp16's range and the block costs no rescale.
+// Decided per QUERY: one cross-lane exchange gives both lanes of a query the pair's maximum.
+//
+// Schedule (what round 5 changed against the round 2 - 4 kernel, which ran QK^T -> softmax -> PV phases per 64-key tile: 312 vector
+// instructions against 42 MFMAs, matrix pipe busy 34 %):
 //   * the unit of work is a 32-key BLOCK and a step is pipelined over three of them - QK^T of block b + 1, softmax of block b, PV of
 //     block b - 1 - so none of a step's 21 MFMAs depends on its vector work (attn_step below);
 //   * the accumulators are touched by ONE code path: every join at which they are live on both sides (block-class arms, a C++ rescale
@@ -20,10 +33,13 @@
 //   * the softmax denominator comes out of the PV MFMAs (the 16 unused rows of the second channel tile read a "ones" fragment);
 //   * the numerators are split with v_cvt_pk_f16_f32 + v_fma_mixlo/hi_f16 (3 instructions per pair instead of 4);
 //   * K tiles are double-buffered, V travels in 32-key blocks through a ring of four 6 KiB slots one tile behind K, 24 LDS-DMA pieces
-//     and one barrier per 64 keys as before.
+//     and one barrier per 64 keys.
 // Vector instructions per launch 1.92e7 -> 1.51e7 (rocprofv3 SQ_INSTS_VALU, B = 8, T = 936), 102.6 -> 94.5 us alone
 // (profiles/r05_attn_ablate_pipelined.txt); under the bench the chip runs at its 1400 W power limit (profiles/r05_power_bench.txt:
 // 1340 - 1360 W, 1.97 GHz) and the step time does not move (DESIGN.md par. 4).
+// History: the round 2 - 4 kernel and a variant that split fp32 q / k / v while staging them were retired after the interleaved A/B of
+// profiles/r05_ab_attention.txt; the ablation builds of this kernel (loop ingredients removed one by one) left their results in
+// profiles/r05_attn_ablate_*.txt.
 #include <atomic>
 #include <type_traits>
 
@@ -103,7 +119,7 @@ struct WaveState {
 //   kb_addr: this lane's byte address of K chunk (plane 0, c8 = hh, key q) of the stage that holds block b + 1's tile (+ its half)
 //   v_addr0 / v_addr1: byte address of V chunk (plane 0, j 0, hh, channel vch0 / vch1) of block b - 1; lanes q >= 16 pass the ones area
 //   GENERAL: the block class of b is NEAR or FAR_MASK (bias from the extended table / tail mask); else FAR (one bias, no mask)
-template <int PAR /* b & 1 */, bool DO_QK, bool DO_PV, bool DO_SM, bool GENERAL, int ABL, bool P1>
+template <int PAR /* b & 1 */, bool DO_QK, bool DO_PV, bool DO_SM, bool GENERAL, bool P1>
 __device__ __forceinline__ void attn_step(WaveState& st, const unsigned char* smem, unsigned kb_addr, unsigned v_addr0, unsigned v_addr1, bool near,
                                           const float* ext_lane, int lim, float bfar) {
     f16v& sq = st.s[PAR ^ 1];
@@ -158,13 +174,13 @@ __device__ __forceinline__ void attn_step(WaveState& st, const unsigned char* sm
     }
     // ---- LDS fragments, then the 21 MFMAs: they depend on registers of earlier steps only
     hf8 ka[3][NPL], va[2][2][NPL];                           // K fragments of the 3 channel steps; V fragments [key step][channel tile]
-    if (DO_QK && !(ABL & 32)) {
+    if (DO_QK) {
 #pragma unroll
         for (int s = 0; s < 3; ++s)
 #pragma unroll
             for (int pl = 0; pl < NPLR; ++pl) ka[s][pl] = as_hf(*reinterpret_cast<const uint4*>(smem + kb_addr + pl * (KCH * 16) + s * (2 * KT * 16)));
     }
-    if (DO_PV && !(ABL & 32)) {
+    if (DO_PV) {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -173,24 +189,14 @@ __device__ __forceinline__ void attn_step(WaveState& st, const unsigned char* sm
                 va[j][1][pl] = as_hf(*reinterpret_cast<const uint4*>(smem + v_addr1 + pl * VHALF + j * (2 * D * 16)));
             }
     }
-    if (ABL & 32) {          // measurement build: no fragment reads
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-#pragma unroll
-            for (int pl = 0; pl < NPL; ++pl) ka[s][pl] = st.qf[s][pl];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int pl = 0; pl < NPL; ++pl) va[j][0][pl] = va[j][1][pl] = st.qf[j][pl];
-    }
-    if (DO_QK && !(ABL & 16)) {
+    if (DO_QK) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) sq[r] = 0.f;
         DTTS_X3B_MFMA(sq, ka[0], st.qf[0])
         DTTS_X3B_MFMA(sq, ka[1], st.qf[1])
         DTTS_X3B_MFMA(sq, ka[2], st.qf[2])
     }
-    if (DO_PV && !(ABL & 8)) {
+    if (DO_PV) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             DTTS_X3B_MFMA(st.oacc[0], va[j][0], st.pf[j])
@@ -199,7 +205,7 @@ __device__ __forceinline__ void attn_step(WaveState& st, const unsigned char* sm
     }
     // ---- softmax of block b: exponent arguments e = s + bias (log2 domain) of this lane's 16 keys and their maximum, the lazy running
     // maximum (decided per query: both lanes of a query see the pair's maximum; P = exp2(e - m + 10) <= 8192 otherwise), the P planes
-    if (DO_SM && !(ABL & 4)) {
+    if (DO_SM) {
         f16v e;                                              // GENERAL only
         float mx;
         if (GENERAL) {
@@ -279,8 +285,7 @@ __device__ __forceinline__ void attn_step(WaveState& st, const unsigned char* sm
             st.pf[j][1] = as_hf(w1);
         }
     }
-    if (DO_SM && (ABL & 4)) st.need = 0;
-    if (P1 && DO_QK && DO_PV && DO_SM && !GENERAL && !(ABL & 28)) {
+    if (P1 && DO_QK && DO_PV && DO_SM && !GENERAL) {
         // the hot instantiation of the one-product mode: 7 MFMAs (3 QK^T + 4 PV) against ~56 vector / transcendental instructions (the
         // 72 of the three-product step less the 16 v_fma_mix of the P residual plane) = one MFMA, then eight
         constexpr int M_MFMA = 0x8, M_VALU = 0x2 | 0x400;
@@ -290,7 +295,7 @@ __device__ __forceinline__ void attn_step(WaveState& st, const unsigned char* sm
             __builtin_amdgcn_sched_group_barrier(M_VALU, 8, 0);
         }
     }
-    if (!P1 && DO_QK && DO_PV && DO_SM && !GENERAL && !(ABL & 28)) {
+    if (!P1 && DO_QK && DO_PV && DO_SM && !GENERAL) {
         // the hot instantiation: one MFMA, then three or four vector / transcendental instructions (21 MFMAs : ~72)
         constexpr int M_MFMA = 0x8, M_VALU = 0x2 | 0x400;
 #define DTTS_X3B_SGB2                                          \
@@ -310,7 +315,7 @@ __device__ __forceinline__ void mfma_result_fence(f16v& a, f16v& b) {
     asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" : "+v"(a), "+v"(b));
 }
 
-template <int MINB, int ABL, bool KSPLIT = false, bool ONEP = false>
+template <int MINB, bool KSPLIT = false, bool ONEP = false>
 __global__ __launch_bounds__(256, MINB) void flash_attn_x3b_kernel(const AttnParams p) {
     constexpr float LOG2E = 1.4426950408889634f;
     constexpr int NW = 4, QPB = NW * QPW;
@@ -437,7 +442,7 @@ __global__ __launch_bounds__(256, MINB) void flash_attn_x3b_kernel(const AttnPar
         const int lim = len - s0b - 4 * hh;                                  // key of register r is valid iff roff(r) < lim
         const float bfar = far_hi ? bias_hi : bias_lo;
         const float* ext_lane = ext_s + (s0b + 4 * hh - t + EXT_HALF);       // near blocks only: in range there
-        attn_step<PAR, DQ, DP, DS, GEN, ABL, ONEP>(st, smem, kb_addr, va0, va1, !(far_hi || far_lo), ext_lane, lim, bfar);
+        attn_step<PAR, DQ, DP, DS, GEN, ONEP>(st, smem, kb_addr, va0, va1, !(far_hi || far_lo), ext_lane, lim, bfar);
     };
     using T1 = std::integral_constant<bool, true>;
     using T0 = std::integral_constant<bool, false>;
@@ -450,10 +455,10 @@ __global__ __launch_bounds__(256, MINB) void flash_attn_x3b_kernel(const AttnPar
     if (!empty) {
     dma_group(1);
     if (!wave_active) {
-        for (int j = 1; j <= ((ABL & 2) ? 1 : ntiles); ++j) {
+        for (int j = 1; j <= ntiles; ++j) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-            if (j < ntiles && !(ABL & 1)) dma_group(j + 1);
+            if (j < ntiles) dma_group(j + 1);
         }
         return;
     }
@@ -467,13 +472,11 @@ __global__ __launch_bounds__(256, MINB) void flash_attn_x3b_kernel(const AttnPar
     // around the wave's queries: ~4 iterations), FAR, GENERAL (a masked tail).  Each run is its own loop over ONE code path - choosing
     // the path per iteration is a join that costs a copy of the accumulators every time.
     auto iteration = [&](int j, auto gen) __attribute__((always_inline)) {
-        if (!(ABL & 1)) dma_group(j + 1);          // K(j + 1) into the stage K(j - 1) left, V(j) into the slots V(j - 2) left
+        dma_group(j + 1);          // K(j + 1) into the stage K(j - 1) left, V(j) into the slots V(j - 2) left
         step(2 * j - 1, P1{}, T1{}, T1{}, T1{}, gen);
         step(2 * j, P0{}, T1{}, T1{}, T1{}, gen);
-        if (!(ABL & 2)) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's pieces of group j + 1 have landed (the barrier covers the others')
-            __syncthreads();
-        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // this wave's pieces of group j + 1 have landed (the barrier covers the others')
+        __syncthreads();
     };
     {
         // blocks b with 32 b + 31 - tq0 <= -64 are far below, with 32 b - (tq0 + 31) >= 64 far above; blocks >= bmask reach beyond len
@@ -491,10 +494,6 @@ __global__ __launch_bounds__(256, MINB) void flash_attn_x3b_kernel(const AttnPar
         for (int j = e1; j < e2; ++j) iteration(j, T1{});
         for (int j = e2; j < jM; ++j) iteration(j, T0{});
         for (int j = jM; j < ntiles; ++j) iteration(j, T1{});
-    }
-    if (ABL & 2) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
     }
     // V(ntiles - 1) arrived with the last group: the last softmax with the PV product before it, then the PV product of the last block
     step(nblk - 1, P1{}, T0{}, T1{}, T1{}, T1{});
@@ -574,8 +573,7 @@ void set_attn_ksplit_cus(int n) { g_attn_ksplit_cus.store(n < 1 ? 1 : n, std::me
 static int attn_ksplit_cus() {
     int v = g_attn_ksplit_cus.load(std::memory_order_relaxed);
     if (v < 0) {
-        const char* e = getenv("DTTS_ATTN_KSPLIT_CUS");
-        set_attn_ksplit_cus(e ? atoi(e) : 256);
+        set_attn_ksplit_cus(env_int("DTTS_ATTN_KSPLIT_CUS", 256));
         v = g_attn_ksplit_cus.load(std::memory_order_relaxed);
     }
     return v;
@@ -585,73 +583,46 @@ void set_attn_ksplit(int n) { g_attn_ksplit.store(n < 1 ? 1 : (n > 4 ? 4 : n), s
 int attn_ksplit() {
     int v = g_attn_ksplit.load(std::memory_order_relaxed);
     if (v < 0) {
-        const char* e = getenv("DTTS_ATTN_KSPLIT");
-        set_attn_ksplit(e ? atoi(e) : 4);
+        set_attn_ksplit(env_int("DTTS_ATTN_KSPLIT", 4));
         v = g_attn_ksplit.load(std::memory_order_relaxed);
     }
     return v;
 }
 
-// operands = AttnPlanes images (p.planes)
+// operands = AttnPlanes images (p.planes).  Two workgroups per CU: 218 registers; the 1024 workgroups of the headline launch are two
+// full rounds of 512 (three per CU spilled).
 void launch_flash_attention_x3b(const AttnParams& p, hipStream_t stream) {
     DTTS_REQUIRE(p.D == 48 && p.bias_tab && !p.causal && !p.band && !p.ml_out && p.planes, "attention_x3b covers head dim 48 with the T5 bias on operand images");
     constexpr int NW = 4;
-    // workgroups per CU: 2 (218 registers; 1024 workgroups of the headline launch = two full rounds of 512) or, DTTS_ATTN_OCC=3, 3 (spills)
-    static const int occ = []() { const char* v = getenv("DTTS_ATTN_OCC"); return v ? atoi(v) : 2; }();
     const int base = cdiv(p.T, NW * QPW) * p.H * p.B;
-    static const int abl = []() { const char* v = getenv("DTTS_ATTN_ABLATE"); return v ? atoi(v) : 0; }();
     // Key split (round 6): a launch of <= 2 samples (the batch-1 CFG pair, single-sample unit calls) whose (head, sample, 128-query)
     // workgroups do not even fill the CUs cuts the keys into S ranges, one workgroup each, merged by the last wave to arrive - but only
     // while base x S workgroups still find a CU each: at T = 936 the pair's 256 workgroups already occupy every CU and a split buys
     // nothing (measured: batch-1 diffusion 122.8 ms without, 123.4 / 125.9 / 126.8 ms with S = 2 / 3 / 4, profiles/r06_batch1.txt), so
     // the headline shapes run exactly round 5's launch.  DTTS_ATTN_KSPLIT = the largest S tried (default 4; 1 = off).
     const int ks_env = attn_ksplit();
-    static const int ks_maxb = []() { const char* v = getenv("DTTS_ATTN_KSPLIT_MAXB"); return v ? atoi(v) : 2; }();
+    static const int ks_maxb = env_int("DTTS_ATTN_KSPLIT_MAXB", 2);
     const int ks_cus = attn_ksplit_cus();
     int S = 1;
-    if (!abl && p.B <= ks_maxb && ks_env > 1) {
+    if (p.B <= ks_maxb && ks_env > 1) {
         S = ks_env;
         while (S > 1 && ((long long)base * S > ks_cus || AttnPlanes::nt64(p.T) < 2 * S || (size_t)base * S > X3_MAX_SLABS || (size_t)base * NW > X3_SPLIT_COUNTERS)) --S;
     }
-    const dim3 grid(base * S);
-    auto go = [&](auto kern) {
-        lds_optin(reinterpret_cast<const void*>(kern), LDS_BYTES);
-        hipLaunchKernelGGL(kern, grid, dim3(NW * 64), LDS_BYTES, stream, p);
-    };
+    AttnParams q = p;
     if (S > 1) {
-        AttnParams q = p;
         q.ksplit = S;
         x3_split_workspace(stream, (size_t)base * S, &q.kpart, &q.kcount);
-        auto kern = p.p1 ? flash_attn_x3b_kernel<2, 0, true, true> : flash_attn_x3b_kernel<2, 0, true>;
+    }
+    auto go = [&](auto kern) {
         lds_optin(reinterpret_cast<const void*>(kern), LDS_BYTES);
-        hipLaunchKernelGGL(kern, grid, dim3(NW * 64), LDS_BYTES, stream, q);
-        DTTS_CHECK_HIP(hipGetLastError());
-        return;
-    }
-    if (p.p1) {          // one-product mode: the measurement builds and DTTS_ATTN_OCC do not apply
-        go(flash_attn_x3b_kernel<2, 0, false, true>);
-        DTTS_CHECK_HIP(hipGetLastError());
-        return;
-    }
-    if (abl) {          // measurement builds (garbage results): which ingredient of the loop costs what (DESIGN.md par. 4)
-        switch (abl) {
-            case 1: go(flash_attn_x3b_kernel<2, 1>); break;
-            case 2: go(flash_attn_x3b_kernel<2, 2>); break;
-            case 3: go(flash_attn_x3b_kernel<2, 3>); break;
-            case 4: go(flash_attn_x3b_kernel<2, 4>); break;
-            case 8: go(flash_attn_x3b_kernel<2, 8>); break;
-            case 16: go(flash_attn_x3b_kernel<2, 16>); break;
-            case 24: go(flash_attn_x3b_kernel<2, 24>); break;
-            case 28: go(flash_attn_x3b_kernel<2, 28>); break;
-            case 32: go(flash_attn_x3b_kernel<2, 32>); break;
-            case 35: go(flash_attn_x3b_kernel<2, 35>); break;
-            case 39: go(flash_attn_x3b_kernel<2, 39>); break;
-            default: DTTS_REQUIRE(false, "DTTS_ATTN_ABLATE: 1, 2, 3, 4, 8, 16, 24, 28, 32, 35 or 39");
-        }
-    } else if (occ == 2) {
-        go(flash_attn_x3b_kernel<2, 0>);
+        hipLaunchKernelGGL(kern, dim3(base * S), dim3(NW * 64), LDS_BYTES, stream, q);
+    };
+    if (S > 1) {
+        if (p.p1) go(flash_attn_x3b_kernel<2, true, true>);
+        else go(flash_attn_x3b_kernel<2, true>);
     } else {
-        go(flash_attn_x3b_kernel<3, 0>);
+        if (p.p1) go(flash_attn_x3b_kernel<2, false, true>);          // one-product mode (the trunk's fp16 mode)
+        else go(flash_attn_x3b_kernel<2>);
     }
     DTTS_CHECK_HIP(hipGetLastError());
 }

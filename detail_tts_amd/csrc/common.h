@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <stdexcept>
 #include <string>
 
@@ -37,6 +38,21 @@ bool device_fits(int wgs, int lds_bytes);
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return cdiv(a, b) * b; }
+
+// Environment switches (DTTS_*, DESIGN.md par. 4.10), host only.  One parsing for all of them; a call site caches what it reads in a
+// `static const` (or, where dtts_set_option can override it later, reads lazily inside its getter).
+static inline const char* env_str(const char* name) { return getenv(name); }       // the raw text, for the few switches with a parsing of their own
+static inline long long env_int(const char* name, long long dflt) {
+    const char* v = env_str(name);
+    return v ? atoll(v) : dflt;
+}
+static inline bool env_on(const char* name) {          // on unless the value starts with '0'
+    const char* v = env_str(name);
+    return !(v && v[0] == '0');
+}
+static inline int env_tri(const char* name) {          // -1 = not set (the caller's own rule decides), else env_on
+    return env_str(name) ? (env_on(name) ? 1 : 0) : -1;
+}
 
 // noise streams of the Philox spec (oracle/philox.py)
 enum NoiseStage : int { STAGE_GPT_SAMPLE = 1, STAGE_DIFF_INIT = 2, STAGE_DIFF_STEP = 3, STAGE_FLOW_PRIOR = 4 };

@@ -94,6 +94,9 @@ struct ConvParams {
     int ablate = 0;                // experiments only (DTTS_CONV_ABLATE): 1 skip global loads, 2 skip LDS stores, 4 skip barriers
 };
 
+// Picks the tile BM x BN (output rows x columns) by CoutP and the ragged tail of Nout - 128 x 128, 128 x 64, 64 x 128, 64 x 64 or
+// 32 x 128, all with 16-channel K-steps - except that launches of few tiles take 64 x 64, with 32-channel K-steps where CinP % 32 == 0
+// and the taps span <= 3 columns (conv_gemm.hip).  One translation unit per instantiated shape: conv_tile_*.hip.
 void launch_conv_gemm(const ConvParams& p, hipStream_t stream);
 void set_conv_small_tiles(int n);   // launches of at most n 128 x 128 tiles take the 64 x 64 tile: 0 = never, n < 0 = the default (DTTS_CONV_SMALL_TILES, else 384); process-wide
 

@@ -469,7 +469,7 @@ __global__ __launch_bounds__(256, (NSTG == 2 && EPI != 3) ? 3 : 2) void conv_x3_
     // a K-step carries its 18 MFMAs, 10 fragment reads, 5 pieces and a handful of scalar pointer adds - no stage / tap / liveness
     // bookkeeping (round 3: 3.7 scalar instructions per MFMA, and with one wave per SIMD the wave's own issue slots between two MFMAs
     // are what the K-step runs out of).  The generic loop below finishes the last < PERIOD + D steps (and runs everything when
-    // DTTS_CONV_UNROLL=0: p.ablate bit 9).
+    // p.ablate bit 9 is set: DTTS_CONV_ABLATE=512).
     constexpr int PERIOD = KW * NSTG;
     auto ustep = [&](auto kc) {
         constexpr int k = decltype(kc)::value;                        // step index inside the period
@@ -1184,9 +1184,9 @@ void launch_gn_split_planes(const float* x, long long x_bs, int x_cs, const int*
     const int Tp = x3_tp(T);
     uint4* o = static_cast<uint4*>(out);
     ProfScope ps("gn_split_planes_kernel", 0.0, (double)B * C * T * 8.0, s);      // fp32 in, two fp16 planes out
-    static const int ns = []() { const char* v = getenv("DTTS_GN_SPLIT_NS"); return v ? atoi(v) : 1; }();
-    static const int nt = []() { const char* v = getenv("DTTS_GN_SPLIT_NT"); return v ? atoi(v) : 1024; }();
-    static const bool reg_ok = []() { const char* v = getenv("DTTS_GN_SPLIT_REG"); return !(v && v[0] == '0'); }();
+    static const int ns = env_int("DTTS_GN_SPLIT_NS", 1);
+    static const int nt = env_int("DTTS_GN_SPLIT_NT", 1024);
+    static const bool reg_ok = env_on("DTTS_GN_SPLIT_REG");
     constexpr int NI = 3;
     if (reg_ok && ns == 1 && (C / groups / 8) * Tp <= NI * 1024) {          // the slab fits the workgroup's registers: one HBM read
         if (act == ACT_SILU)
@@ -1262,7 +1262,7 @@ void x3_split_workspace(hipStream_t s, size_t nslabs, float** part, int** count)
 size_t conv_x3_gn_xch_bytes(int B, int Cout, int T) { return (size_t)B * (Cout / 8) * cdiv(T, BN) * 2 * 16; }
 
 static long long split_tiles_max() {
-    static const long long v = []() { const char* e = getenv("DTTS_CONV_KSPLIT_MAXTILE"); return e ? atoll(e) : 128LL; }();
+    static const long long v = env_int("DTTS_CONV_KSPLIT_MAXTILE", 128);
     return v;
 }
 
@@ -1280,7 +1280,7 @@ void launch_conv_x3(const ConvParams& p_in, hipStream_t s) {
     ConvParams p = p_in;
     DTTS_REQUIRE(p.w3 && p.x3 && (p.y || p.qkv_planes || p.gn_out3) && p.x3_tp > 0, "conv_x3: operands");
     const bool gn = p.gn_out3 != nullptr;
-    static const int env_ablate = []() { const char* v = getenv("DTTS_CONV_ABLATE"); return v ? atoi(v) : 0; }();
+    static const int env_ablate = env_int("DTTS_CONV_ABLATE", 0);
     if (env_ablate) p.ablate = env_ablate;
     if (gn) {
         DTTS_REQUIRE(conv_x3_gn_fusable(p.Cout, p.CoutP, p.Cin, p.KW, p.gn_groups, p.B, p.Nout), "conv_x3: this launch cannot carry a fused GroupNorm");
@@ -1303,26 +1303,26 @@ void launch_conv_x3(const ConvParams& p_in, hipStream_t s) {
     // so the loads run further ahead (counted vmcnt): four stages (82 KiB, one workgroup per CU) up to DTTS_CONV_STAGES4_MAXWG = 128
     // workgroups (half the CUs: batch 1), three (61 KiB, two per CU) up to DTTS_CONV_STAGES3_MAXWG = 600, two (41 KiB, three per CU)
     // for launches that fill the chip several times over.  DTTS_CONV_STAGES = 2 / 3 / 4 forces one.
-    static const int force_stg = []() { const char* v = getenv("DTTS_CONV_STAGES"); const int n = v ? atoi(v) : 0; return n >= 2 && n <= 4 ? n : 0; }();
-    static const long long max3 = []() { const char* v = getenv("DTTS_CONV_STAGES3_MAXWG"); return v ? atoll(v) : 600LL; }();
-    static const long long max4 = []() { const char* v = getenv("DTTS_CONV_STAGES4_MAXWG"); return v ? atoll(v) : 128LL; }();
+    static const int force_stg = []() { const int n = env_int("DTTS_CONV_STAGES", 0); return n >= 2 && n <= 4 ? n : 0; }();
+    static const long long max3 = env_int("DTTS_CONV_STAGES3_MAXWG", 600);
+    static const long long max4 = env_int("DTTS_CONV_STAGES4_MAXWG", 128);
     if (gn) p.cols = nullptr;                                            // the fused GroupNorm's id order is per sample
     DTTS_REQUIRE(!p.cols || (p.ncols > 0 && p.ncols <= cdiv(p.Nout, BN) * p.B && cdiv(p.Nout, BN) < 256), "conv_x3: column table");
     const long long ntile = (long long)(p.CoutP / BM) * (p.cols ? p.ncols : cdiv(p.Nout, BN) * p.B);
     // split-K: launches of at most 128 tiles (half the CUs: batch 1) divide the channel blocks among up to 4 workgroups per tile
-    static const int max_split = []() { const char* v = getenv("DTTS_CONV_KSPLIT"); const int n = v ? atoi(v) : 4; return n < 1 ? 1 : (n > 8 ? 8 : n); }();
+    static const int max_split = []() { const int n = env_int("DTTS_CONV_KSPLIT", 4); return n < 1 ? 1 : (n > 8 ? 8 : n); }();
     int S = 1;
     // (k = 3: 144 K-steps per tile; the 48 steps of a 1x1 conv barely pay for the exchange: at most 2 there)
     const long long split_tiles = split_tiles_max();
-    static const long long split_wgs = []() { const char* v = getenv("DTTS_CONV_KSPLIT_WGS"); return v ? atoll(v) : 256LL; }();
+    static const long long split_wgs = env_int("DTTS_CONV_KSPLIT_WGS", 256);
     // (decided on the PADDED tile count: a column table must not change the summation order of a launch)
     const long long ntile_pad = (long long)(p.CoutP / BM) * cdiv(p.Nout, BN) * p.B;
-    static const int max_split_k1 = []() { const char* v = getenv("DTTS_CONV_KSPLIT_K1"); return v ? atoi(v) : 2; }();
+    static const int max_split_k1 = env_int("DTTS_CONV_KSPLIT_K1", 2);
     if (ntile_pad <= split_tiles) S = (int)std::min<long long>(std::min<long long>(p.KW == 3 ? max_split : std::min(max_split, max_split_k1), split_wgs / ntile_pad), (p.Cin >> 4) / 8);
     if (p.ksplit_max > 0) S = std::min(S, p.ksplit_max);
     if (S < 1) S = 1;
     p.ksplit = S;
-    static const bool epi_vec_on = []() { const char* v = getenv("DTTS_X3_EPI_VEC"); return !(v && v[0] == '0'); }();
+    static const bool epi_vec_on = env_on("DTTS_X3_EPI_VEC");
     auto al16 = [](const void* q, long long bs, int cs) { return (reinterpret_cast<unsigned long long>(q) & 15ull) == 0 && (bs & 3) == 0 && (cs & 3) == 0; };
     p.epi_vec = (epi_vec_on && p.y && al16(p.y, p.y_bs, p.y_cs) && (!p.res || al16(p.res, p.res_bs, p.res_cs))) ? 1 : 0;
     if (S > 1) {
@@ -1331,7 +1331,7 @@ void launch_conv_x3(const ConvParams& p_in, hipStream_t s) {
         p.kcount = w.count;
     }
     const long long nwg = ntile * S;
-    static const long long max4k3 = []() { const char* v = getenv("DTTS_CONV_STAGES4_MAXWG_K3"); return v ? atoll(v) : 128LL; }();
+    static const long long max4k3 = env_int("DTTS_CONV_STAGES4_MAXWG_K3", 128);
     const int nstg = force_stg ? force_stg : (nwg <= (p.KW == 3 ? max4k3 : max4) ? 4 : (nwg <= max3 ? 3 : 2));
     const size_t lds = (size_t)nstg * (WTILE + XBUF) + BM * sizeof(float) + 16 + (gn ? 2 * BM * sizeof(float) : 0);
     const int l4 = 4 * (WTILE + XBUF) + 3 * BM * (int)sizeof(float) + 16;      // the attribute is a maximum: every instantiation gets the 4-stage size
@@ -1340,7 +1340,7 @@ void launch_conv_x3(const ConvParams& p_in, hipStream_t s) {
     const double flops = 2.0 * p.Cout * p.Cin * p.KW * cols;                      // fp32-equivalent; the MFMA pipe executes 3x this in fp16 (p1: 1x)
     const double bytes = 4.0 * cols * p.Cin + 4.0 * cols * p.Cout * (p.res ? 2.0 : 1.0) + 4.0 * (double)p.Cout * p.Cin * p.KW;
     {
-        static const bool by_shape = []() { const char* v = getenv("DTTS_PROF_SHAPES"); return v && v[0] == '1'; }();
+        static const bool by_shape = []() { const char* v = env_str("DTTS_PROF_SHAPES"); return v && v[0] == '1'; }();
         const char* tag = p1 ? "conv_x3_kernel<128,192,fp16>" : "conv_x3_kernel<128,192>";
         if (by_shape && p1) tag = p.KW == 3 ? "conv_x3 fp16 k3" : (p.Cout > 1024 ? "conv_x3 fp16 k1 M=2304" : (p.res ? "conv_x3 fp16 k1 +res" : "conv_x3 fp16 k1"));
         else if (by_shape) tag = p.KW == 3 ? "conv_x3 k3" : (p.Cout > 1024 ? "conv_x3 k1 M=2304" : (p.res ? "conv_x3 k1 +res" : "conv_x3 k1"));

@@ -384,12 +384,12 @@ static void gemv_block_launch_v(int pro, const float* W, int K, int CoutP, const
 // >= 192; else narrow 64-column workgroups; and 64 instead of 128 input rows per workgroup when even those are fewer than 128
 // (the 768 x 768 attention projection: 12 column groups x 6 slices).
 static int gemv_rows(int K, int CoutP) {
-    static const int force = []() { const char* v = getenv("DTTS_GEMV_ROWS"); return v ? atoi(v) : 0; }();
+    static const int force = env_int("DTTS_GEMV_ROWS", 0);
     if (force) return force;
     return ((long long)cdiv(CoutP, 64) * (K / 128) < 128 && K % 64 == 0) ? 64 : 128;
 }
 static bool gemv_wide(int K, int CoutP) {
-    static const int force = []() { const char* v = getenv("DTTS_GEMV_VEC"); return v ? atoi(v) : 0; }();
+    static const int force = env_int("DTTS_GEMV_VEC", 0);
     return force ? force == 4 : (long long)cdiv(CoutP, 256) * (K / 128) >= 192;
 }
 
@@ -572,7 +572,7 @@ __global__ __launch_bounds__(256) void decode_attention_qkv_kernel(const float* 
 }
 
 int decode_attention_splits() {
-    static const int n = []() { const char* v = getenv("DTTS_GPT_KSPLIT"); const int k = v ? atoi(v) : 2; return k < 1 ? 1 : (k > 8 ? 8 : k); }();
+    static const int n = []() { const int k = env_int("DTTS_GPT_KSPLIT", 2); return k < 1 ? 1 : (k > 8 ? 8 : k); }();
     return n;
 }
 
@@ -1119,7 +1119,7 @@ void launch_sampler(const SamplerParams& p, hipStream_t s) {
     DTTS_REQUIRE(lds <= (size_t)SAMP_LDS_DYNAMIC_MAX, "sampler: LDS request over the budget");
     lds_optin(reinterpret_cast<const void*>(sampler_kernel), SAMP_LDS_DYNAMIC_MAX);
     // DTTS_SAMPLER_TRACE = n: the n-th launch records wall-clock stamps of row 0's phases and prints them (100 MHz clock)
-    static const int trace_at = []() { const char* v = getenv("DTTS_SAMPLER_TRACE"); return v ? atoi(v) : 0; }();
+    static const int trace_at = env_int("DTTS_SAMPLER_TRACE", 0);
     static int launches = 0;
     static long long* d_trace = nullptr;
     SamplerParams q = p;

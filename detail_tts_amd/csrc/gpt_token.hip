@@ -595,7 +595,7 @@ void launch_gpt_token(const GptTokenParams& p, hipStream_t s) {
     const bool narrow = !r16 && !r1 && !r4 && p.wgs != 0 && p.wgs != TG;              // 8-row sessions on 64 / 32 workgroups (gpt_token_n.hip; the same bits)
     const int lds_request = p.exclusive_cu ? LDS_EXCLUSIVE : (int)(r16 ? sizeof(SmemT<16>) : r1 ? sizeof(SmemT<1>) : r4 ? sizeof(SmemT<4>) : sizeof(SmemT<8>));   // the attribute was raised by gpt_token_prepare (bind time)
     // DTTS_GPT_TOKEN_TRACE = n: the n-th launch records wall-clock stamps of workgroups 0 and 37 at every exchange and prints them
-    static const int trace_at = []() { const char* v = getenv("DTTS_GPT_TOKEN_TRACE"); return v ? atoi(v) : 0; }();
+    static const int trace_at = env_int("DTTS_GPT_TOKEN_TRACE", 0);
     static int launches = 0;
     static long long* d_trace = nullptr;
     GptTokenParams q = p;

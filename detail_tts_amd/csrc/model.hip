@@ -12,7 +12,7 @@ namespace dtts {
 // Side streams of the diffusion trunk.  DTTS_B_CU_RESERVE = n (experiment): the stream's queue is masked off the last n CUs of the
 // 256 (the mask's bits interleave over the 8 XCDs), which stay free for the decode chain of the next request.
 static void make_side_stream(hipStream_t* st) {
-    static const int reserve = []() { const char* v = getenv("DTTS_B_CU_RESERVE"); return v ? atoi(v) : 0; }();
+    static const int reserve = env_int("DTTS_B_CU_RESERVE", 0);
     if (reserve > 0 && reserve < 256) {
         uint32_t mask[8];
         for (int i = 0; i < 8; ++i) mask[i] = 0xffffffffu;
@@ -88,7 +88,7 @@ struct ColTable {
 };
 thread_local std::vector<ColTable> t_col_tables;
 static bool col_tables_on() {
-    static const bool on = []() { const char* v = getenv("DTTS_CONV_COLS"); return !(v && v[0] == '0'); }();
+    static const bool on = env_on("DTTS_CONV_COLS");
     return on;
 }
 
@@ -691,14 +691,9 @@ static size_t qkv_floats(int B, int C, int T) {
     return std::max(rows, planes) + 64;
 }
 
-static bool attn_x3_enabled() {
-    static const bool on = []() { const char* v = getenv("DTTS_ATTN_X3"); return !(v && v[0] == '0'); }();
-    return on;
-}
-
 bool Model::use_x3() const {
-    static const bool env_on = []() { const char* v = getenv("DTTS_CONV_X3"); return !(v && v[0] == '0'); }();
-    return env_on && opt_conv_x3_;
+    static const bool on = env_on("DTTS_CONV_X3");
+    return on && opt_conv_x3_;
 }
 
 // ------------------------------------------------------------------------------ fused GroupNorm plumbing (conv_x3.h)
@@ -772,8 +767,8 @@ void Model::attention_block(const AttnBlockW& w, const float* x, float* y, float
     p.y = qkv;
     p.y_bs = 3 * bs;
     p.y_cs = Ta;
-    static const bool env_planes = []() { const char* v = getenv("DTTS_ATTN_PLANES"); return !(v && v[0] == '0'); }();
-    const bool planes = x3 && attn_x3_enabled() && env_planes && D == AttnPlanes::D;
+    const bool planes = x3 && D == AttnPlanes::D;       // (other head dims: fp32 attention, its output is split below)
+    DTTS_REQUIRE(!planes || w.bias_tab, "split-precision attention (head dim 48) needs the block's relative-position bias table");
     DTTS_REQUIRE(!t_layer_p1 || planes, "trunk_fp16: the attention has its one-product mode only on the qkv conv's operand images (split-precision path, head dim 48)");
     if (x3) {
         p.x3 = xs;
@@ -805,12 +800,11 @@ void Model::attention_block(const AttnBlockW& w, const float* x, float* y, float
     a.D = D;
     a.scale = 1.f / std::sqrt((float)D);
     a.bias_tab = w.bias_tab;
-    a.x3 = x3 && attn_x3_enabled();
     if (planes) a.planes = qkv;
     a.p1 = t_layer_p1 ? 1 : 0;
     // the proj conv's input planes come straight from the attention epilogue; xs still holds the zero halo / tail columns that
     // gn_split_planes wrote for the qkv conv (same B, T, lens), and the qkv conv has consumed the rest
-    const bool att_planes = a.x3 && D == 48 && w.bias_tab && T + 1 < x3_tp(T);      // (other head dims: fp32 attention, its output is split below)
+    const bool att_planes = planes && T + 1 < x3_tp(T);
     DTTS_REQUIRE(!f || att_planes, "fused GroupNorm: the attention must write the proj conv's planes");
     void* xs_att = f ? f->xs_alt : xs;                  // fused: the proj conv reads xs_alt and its epilogue writes xs (the next block's input)
     if (att_planes) {
@@ -949,7 +943,7 @@ void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* c
                               int T, int step, float* out2, hipStream_t s, const float* integ) {
     const int C = cfg.diff_channels, Ta = T, OC = cfg.diff_out_channels;
     const long long bs = (long long)C * Ta;
-    static const bool env_two = []() { const char* v = getenv("DTTS_TWO_STREAMS"); return !(v && v[0] == '0'); }();
+    static const bool env_two = env_on("DTTS_TWO_STREAMS");
     const bool two_streams = env_two && opt_two_streams_;
     int groups = 32;
     while (C % groups) groups /= 2;
@@ -985,7 +979,7 @@ void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* c
     // 2B-sample launch per layer (best per-kernel efficiency: a 768-channel conv is one full wave of workgroups); NS = 2 (default):
     // cond | uncond on two streams - the HBM-bound GroupNorm/split passes and the VALU-bound attention of one chunk run under the
     // matrix work of the other (measured 3.3 % faster end to end than NS = 1 with the fp16-plane kernels); option "cfg_streams".
-    static const int env_ns = []() { const char* v = getenv("DTTS_CFG_STREAMS"); return v ? atoi(v) : 0; }();
+    static const int env_ns = env_int("DTTS_CFG_STREAMS", 0);
     // default (option 0): 2 chunks from batch 5 up, 1 below (<= 8 samples per layer: a single launch sequence is faster, measured at B = 1, 2, 4)
     int NS = env_ns > 0 ? env_ns : (opt_cfg_streams_ > 0 ? opt_cfg_streams_ : (B <= 4 ? 1 : 2));
     if (!two_streams) NS = 1;
@@ -1041,7 +1035,7 @@ void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* c
         void* xs = x3 ? ws().raw(x3_bytes(n, C, T)) : nullptr;
         // fused GroupNorm (conv_x3.h): every GN + activation + split of the stack runs in the epilogue of the conv in front of it
         // (8 -> 5 launches per DiffusionLayer); planes ping-pong between xs and xs2; chunk k uses exchange slot k
-        static const int env_fuse = []() { const char* v = getenv("DTTS_GN_FUSE"); return v ? (v[0] == '0' ? 0 : 1) : -1; }();
+        static const int env_fuse = env_tri("DTTS_GN_FUSE");
         const bool fuse = x3 && (env_fuse >= 0 ? env_fuse != 0 : opt_gn_fuse_) && conv_x3_gn_fusable(C, C, C, 3, groups, n, T) && T + 1 < x3_tp(T);
         GnFuse fz;
         GnFuse* f = nullptr;
@@ -1126,7 +1120,7 @@ static size_t integ_ws_bytes(int Bv, int C, int T) {
 static int integ_chunk(int Bi) {     // steps per batched evaluation (~36 samples per launch; DTTS_INTEG_SAMPLES overrides)
     // (batch 1, 12 / 20 / 36 / 52 / 100 samples per launch: diff_sample 122.8 - 126.2 / 123.1 / 123.5 - 124.2 / 123.4 / 123.6 ms - flat within the
     // run-to-run spread, profiles/r05_integ_pipeline_ab.txt)
-    static const int target = []() { const char* v = getenv("DTTS_INTEG_SAMPLES"); return v ? atoi(v) : 36; }();
+    static const int target = env_int("DTTS_INTEG_SAMPLES", 36);
     return std::max(1, target / Bi);
 }
 
@@ -1136,7 +1130,7 @@ void Model::precompute_integrator(const Schedule& sc, const float* cbuf0, const 
     const size_t ct = (size_t)C * T, mark = ws().mark();
     const int Bv = J * Bi;
     const bool x3 = use_x3();
-    static const bool env_two = []() { const char* v = getenv("DTTS_TWO_STREAMS"); return !(v && v[0] == '0'); }();
+    static const bool env_two = env_on("DTTS_TWO_STREAMS");
     // `ready` (the latency regime: diff_sample asks for it when the sampling loop is one launch sequence that cannot fill the chip):
     // only the FIRST chunk of steps is evaluated on s; the later ones go to the low-priority stream si_ and run UNDER the loop's first
     // steps, which wait for a chunk's event when they reach its first step.  Same launches on the same inputs: same values.  The
@@ -1149,14 +1143,14 @@ void Model::precompute_integrator(const Schedule& sc, const float* cbuf0, const 
             // overlap returns 1 ms of the ~10 the chunks take (batch 1: 124.6 -> 123.7 ms, profiles/r05_integ_pipeline_ab.txt).
             // Confining the chunks to DTTS_INTEG_CUS CUs (the mask's low bits) was measured and is OFF: 32 / 64 / 128 CUs gave 167 / 148 /
             // 139 ms - a masked queue runs these launches far slower than its share of the chip.  Default: a low-priority stream.
-            static const int cus = []() { const char* v = getenv("DTTS_INTEG_CUS"); return v ? atoi(v) : 0; }();
+            static const int cus = env_int("DTTS_INTEG_CUS", 0);
             if (cus > 0 && cus < 256) {
                 uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
                 for (int b = 0; b < cus; ++b) mask[b >> 5] |= 1u << (b & 31);
                 DTTS_CHECK_HIP(hipExtStreamCreateWithCUMask(&si_, 8, mask));
             } else {
                 // DTTS_INTEG_PRIO=low: the lowest stream priority (measured: no different from the normal one)
-                static const bool low = []() { const char* v = getenv("DTTS_INTEG_PRIO"); return v && v[0] == 'l'; }();
+                static const bool low = []() { const char* v = env_str("DTTS_INTEG_PRIO"); return v && v[0] == 'l'; }();
                 int least = 0, greatest = 0;
                 DTTS_CHECK_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
                 DTTS_CHECK_HIP(hipStreamCreateWithPriority(&si_, hipStreamNonBlocking, low ? least : 0));
@@ -1325,10 +1319,10 @@ void Model::diff_sample_ex(int sched_id, int sampler, float eta, const float* co
     if (n_steps <= 0 || n_steps > sc.n) n_steps = sc.n;
     const size_t per_call = pair_ws_bytes(B, C, T);
     // the integrator outputs of all steps are evaluated up front (opt-out: DTTS_INTEG_PRECOMPUTE=0); Nu <= B distinct lengths
-    static const bool env_pre_on = []() { const char* v = getenv("DTTS_INTEG_PRECOMPUTE"); return !(v && v[0] == '0'); }();
+    static const bool env_pre_on = env_on("DTTS_INTEG_PRECOMPUTE");
     // the precomputed integrator outputs of all steps cost n_steps * 2B * C * T floats (3 GB at batch 8 x 10 s, 11 GB at batch 4 x 60 s):
     // beyond DTTS_INTEG_MAX_GB (default 24) the integrator is evaluated inside every step instead (same values, no table)
-    static const double max_gb = []() { const char* v = getenv("DTTS_INTEG_MAX_GB"); return v ? atof(v) : 24.0; }();
+    static const double max_gb = []() { const char* v = env_str("DTTS_INTEG_MAX_GB"); return v ? atof(v) : 24.0; }();
     const size_t integ_table = sizeof(float) * (size_t)n_steps * 2 * B * C * T;
     const bool env_pre = env_pre_on && (double)integ_table <= max_gb * 1073741824.0;
     const size_t integ_bytes = env_pre ? integ_table + integ_ws_bytes(integ_chunk(B + 1) * 2 * B, C, T) : 0;
@@ -1371,7 +1365,7 @@ void Model::diff_sample_ex(int sched_id, int sampler, float eta, const float* co
     // OFF by default: it returns 1 ms of a blocking batch-1 call, but in a process that holds more streams (after batch-8 requests) the
     // extra stream shares a hardware queue with the next request's stage A and a pipelined single-utterance request takes 208 instead
     // of 147 ms (profiles/r05_integ_pipeline_ab.txt)
-    static const int env_pipe = []() { const char* v = getenv("DTTS_INTEG_PIPELINE"); return v ? atoi(v) : -1; }();
+    static const int env_pipe = env_int("DTTS_INTEG_PIPELINE", -1);
     const int pipe_opt = env_pipe >= 0 ? env_pipe : opt_integ_pipeline_;
     const bool pipe = pipe_opt < 0 ? B <= 4 : pipe_opt != 0;
     std::vector<std::pair<int, hipEvent_t>> ready;

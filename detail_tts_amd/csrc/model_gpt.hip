@@ -110,9 +110,9 @@ void Model::build_gpt(hipStream_t s) {
 
 // sessions of <= 8 rows decode a token with ONE persistent kernel (DTTS_GPT_TOKEN_KERNEL=0: the launch-per-GEMV chain)
 bool Model::gpt_use_token_kernel() const {
-    static const bool env_on = []() { const char* v = getenv("DTTS_GPT_TOKEN_KERNEL"); return !(v && v[0] == '0'); }();
-    static const int env_rows = []() { const char* v = getenv("DTTS_GPT_TOKEN_ROWS"); return v ? atoi(v) : GPT_TOKEN_ROWS; }();
-    return env_on && opt_gpt_token_ && tok_ok_ && !tok_failed_ && gs_.B <= std::min(env_rows, GPT_TOKEN_ROWS) && gs_.xch != nullptr;
+    static const bool on = env_on("DTTS_GPT_TOKEN_KERNEL");
+    static const int env_rows = env_int("DTTS_GPT_TOKEN_ROWS", GPT_TOKEN_ROWS);
+    return on && opt_gpt_token_ && tok_ok_ && !tok_failed_ && gs_.B <= std::min(env_rows, GPT_TOKEN_ROWS) && gs_.xch != nullptr;
 }
 
 // HF GPT-2 stack (without ln_f) over x [B, C, L] in place; optionally fills the KV cache.
@@ -400,17 +400,17 @@ void Model::gpt_step_launches(hipStream_t s) {
         p.logits = gs_.logits;
         p.err = gs_.tok_err;
         p.epoch = gs_.tok_epoch;
-        static const int env_excl = []() { const char* v = getenv("DTTS_GPT_TOKEN_EXCLUSIVE_CU"); return v ? (v[0] == '0' ? 0 : 1) : -1; }();
+        static const int env_excl = env_tri("DTTS_GPT_TOKEN_EXCLUSIVE_CU");
         p.exclusive_cu = env_excl >= 0 ? env_excl : (opt_tok_exclusive_ ? 1 : 0);
-        static const int env_prio = []() { const char* v = getenv("DTTS_GPT_TOKEN_PRIO"); return v ? atoi(v) : 1; }();
-        static const int env_nap = []() { const char* v = getenv("DTTS_GPT_TOKEN_NAP"); return v ? atoi(v) : 0; }();
-        static const int env_ablate = []() { const char* v = getenv("DTTS_GPT_TOKEN_ABLATE"); return v ? atoi(v) : 0; }();
+        static const int env_prio = env_int("DTTS_GPT_TOKEN_PRIO", 1);
+        static const int env_nap = env_int("DTTS_GPT_TOKEN_NAP", 0);
+        static const int env_ablate = env_int("DTTS_GPT_TOKEN_ABLATE", 0);
         p.prio = env_prio;
         p.poll_nap = env_nap;
         p.ablate = env_ablate;
-        static const int env_min_rows = []() { const char* v = getenv("DTTS_GPT_TOKEN_MIN_ROWS"); return v ? atoi(v) : 0; }();
+        static const int env_min_rows = env_int("DTTS_GPT_TOKEN_MIN_ROWS", 0);
         p.min_rows = env_min_rows ? env_min_rows : opt_tok_min_rows_;
-        static const int env_wgs = []() { const char* v = getenv("DTTS_GPT_TOKEN_WGS"); return v ? atoi(v) : 0; }();
+        static const int env_wgs = env_int("DTTS_GPT_TOKEN_WGS", 0);
         p.wgs = env_wgs ? env_wgs : gs_.tok_wgs;
         if (opt_tok_fault_ > 0 && --opt_tok_fault_ == 0) {      // test hook: what a timed-out exchange leaves behind (flag up, token dead)
             const int one = 1;
@@ -465,7 +465,7 @@ void Model::gpt_step_launches(hipStream_t s) {
         a.y_out = gs_.x;
         a.stats_out = gs_.st1;
         launch_gemv_block(GP_RESSUM, w.attn.w, C, w.attn.CoutP, a, B, gs_.part, s);
-        static const bool fuse_proj = []() { const char* v = getenv("DTTS_GPT_FUSE_PROJ"); return !(v && v[0] == '0'); }();
+        static const bool fuse_proj = env_on("DTTS_GPT_FUSE_PROJ");
         const bool fp = fuse_proj && w.proj.CoutP == 768 && H == 16;
         if (fp) {                                        // K2 + K3: attention and its output projection, per-head partials in part2
             launch_decode_attention_qkv(gs_.part, sq, w.attn.CoutP, gs_.st1, st_sl, w.attn_c, w.attn_d, cache, gs_.kv_bs, gs_.cap, gs_.ctl, B, H,
@@ -520,7 +520,7 @@ void Model::gpt_drop_graphs() {
 }
 
 static int gpt_graph_chunk() {
-    static const int n = []() { const char* v = getenv("DTTS_GPT_GRAPH_CHUNK"); const int k = v ? atoi(v) : 16; return k < 1 ? 1 : (k > 64 ? 64 : k); }();
+    static const int n = []() { const int k = env_int("DTTS_GPT_GRAPH_CHUNK", 16); return k < 1 ? 1 : (k > 64 ? 64 : k); }();
     return n;
 }
 
@@ -550,7 +550,7 @@ int Model::gpt_decode(int n_steps, hipStream_t s) {
     DTTS_REQUIRE(gs_.active, "dtts_gpt_decode: no session (call dtts_gpt_prefill first)");
     int n = std::min(n_steps, gs_.G - gs_.steps);
     if (n <= 0) return 0;
-    static const int env_graph = []() { const char* v = getenv("DTTS_GPT_GRAPH"); return v ? (v[0] == '0' ? 0 : 1) : -1; }();
+    static const int env_graph = env_tri("DTTS_GPT_GRAPH");
     if (!(env_graph >= 0 ? env_graph != 0 : opt_gpt_graph_)) {
         for (int i = 0; i < n; ++i) gpt_step_launches(s);
         gs_.steps += n;

@@ -242,7 +242,7 @@ void Model::resblock1_fwd(const ResBlock1W& rb, const float* x, float* tmp, floa
     // Round 5: only the block's FIRST conv is fed by a split pass; every conv's epilogue writes lrelu(y) as the next conv's planes
     // (ConvParams::next3) into the other of two plane buffers, convs1 without an fp32 output at all: 6 -> 1 split passes per ResBlock1.
     // Option voc_chain_planes = 0 / DTTS_VOC_CHAIN_PLANES=0: a split pass in front of every conv (round 4) - the same planes, bit for bit.
-    static const bool chain_env = []() { const char* v = getenv("DTTS_VOC_CHAIN_PLANES"); return !(v && v[0] == '0'); }();
+    static const bool chain_env = env_on("DTTS_VOC_CHAIN_PLANES");
     const int Tp = x3d_tp(T), CP = x3 ? rb.c1[0].CinP : 0;
     bool chain = x3 && chain_env && opt_voc_chain_;
     for (int li = 0; li < 3 && chain; ++li) chain = rb.c1[li].CinP == CP && rb.c2[li].CinP == CP && rb.c1[li].Cout == ch && rb.c2[li].Cout == ch;
@@ -298,8 +298,8 @@ void Model::resblock1_fwd(const ResBlock1W& rb, const float* x, float* tmp, floa
 
 // the fused kernel covers stages of at most 32 channels with the (3, 7, 11) kernels (DTTS_VOC_FUSED=0: launch by launch as before)
 bool Model::rb_fused_ok(const GenStageW& st, int ch) const {
-    static const bool env_on = []() { const char* v = getenv("DTTS_VOC_FUSED"); return !(v && v[0] == '0'); }();
-    if (!env_on || ch > 32) return false;
+    static const bool on = env_on("DTTS_VOC_FUSED");
+    if (!on || ch > 32) return false;
     int halo = 0;
     for (int l = 0; l < 3; ++l) halo += 10 * (cfg.resblock_dilations[l] + 1) / 2;
     return st.rb[0].k == 3 && st.rb[1].k == 7 && st.rb[2].k == 11 && halo <= 60 && st.rb[0].c1[0].CoutP == 32;
@@ -350,7 +350,7 @@ static const char* kSatMsg = "vocoder: an activation exceeds the range of the sp
                              "request saturated; rerun with dtts_set_option(\"voc_x3\", 0) / DTTS_VOC_X3=0 (stage C alone) or \"conv_x3\", 0 (everything) on the exact fp32 kernels";
 
 int* Model::x3_sat_flag(hipStream_t s) {
-    static const int env = []() { const char* v = getenv("DTTS_X3_RANGE_CHECK"); return v ? (v[0] == '0' ? 0 : 1) : -1; }();
+    static const int env = env_tri("DTTS_X3_RANGE_CHECK");
     (void)s;
     ++x3_ticket_;
     if (env == 1) opt_range_check_ = true;
@@ -390,8 +390,8 @@ void Model::x3_sat_check(hipStream_t s) {
 }
 
 bool Model::vocoder_x3() const {
-    static const bool env_on = []() { const char* v = getenv("DTTS_VOC_X3"); return !(v && v[0] == '0'); }();
-    return env_on && opt_voc_x3_ && use_x3();
+    static const bool on = env_on("DTTS_VOC_X3");
+    return on && opt_voc_x3_ && use_x3();
 }
 
 // unit entry point: dec.resblocks[stage * 3 + branch] on x [B, ch(stage), T]
@@ -566,7 +566,7 @@ void Model::wn_fwd(const CouplingW& c, float* h, const float* g, int gin, float*
     // Split-precision in_layers (round 5): the k = 5 conv as a 1x1 conv_x3 launch (its 3 / 4-stage small-launch pipeline + split-K) over
     // the 5-tap expansion of h - same w3 image, gate + conditioning rows in the epilogue.  fp32-MFMA form when the rows of the
     // activations are not 16-byte aligned (T % 4) or with conv_x3 = 0 / DTTS_VOC_X3 = 0 / DTTS_VOC_WN_X3 = 0.
-    static const bool env_wn = []() { const char* v = getenv("DTTS_VOC_WN_X3"); return !(v && v[0] == '0'); }();
+    static const bool env_wn = env_on("DTTS_VOC_WN_X3");
     const bool x3 = env_wn && vocoder_x3() && c.in[0].w3 && c.in[0].KW == 5 && T % 4 == 0 && hid % 16 == 0;
     const size_t mark = ws().mark();
     void* xs5 = x3 ? ws().raw(x3_bytes(B, 5 * hid, T)) : nullptr;

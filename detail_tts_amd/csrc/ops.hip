@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void ln_channels_reg_kernel(const float* x, co
     }
 }
 
-static std::atomic<int> g_ln_reg{[]() { const char* v = getenv("DTTS_LN_REG"); return (v && v[0] == '0') ? 0 : 1; }()};
+static std::atomic<int> g_ln_reg{env_on("DTTS_LN_REG") ? 1 : 0};
 void set_ln_channels_reg(bool on) { g_ln_reg.store(on ? 1 : 0, std::memory_order_relaxed); }   // option "ln_reg" (process-wide)
 
 void launch_ln_channels(const float* x, const float* r, long long bs, int cs, const int* lens, int T, int B, int C,

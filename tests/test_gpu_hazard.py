@@ -60,7 +60,7 @@ def test_headline_size_infer_stream_equals_blocking_infer(synth):
 # ---- one stage repeated under another stage's load ------------------------------------------------------------------------------------
 
 def _trunk_load(rt):
-    """stage B at the headline shape: both CFG chunks of conv_x3 / flash_attn_x3w / gn_split_planes at B = 8, T = 936"""
+    """stage B at the headline shape: both CFG chunks of conv_x3 / flash_attn_x3b / gn_split_planes at B = 8, T = 936"""
     r8 = torch.from_numpy((np.random.RandomState(1).randn(8, 128, T_REF) * 2 - 5).astype(np.float32)).cuda()
     ce = rt.diff_timestep_independent(torch.randn(8, 768, N_CODES, device="cuda"), rt.diff_conditioning(r8))
     return lambda: rt.diff_sample(ce, 3, list(range(8)), n_steps=3)

@@ -371,3 +371,21 @@ def test_shipped_library_has_no_packed_fp32_math():
     assert "v_fma_f32" in asm and "v_mfma_f32_32x32x16_f16" in asm
     packed = [l for l in asm.splitlines() if "v_pk_fma_f32" in l or "v_pk_mul_f32" in l or "v_pk_add_f32" in l]
     assert not packed, (len(packed), packed[:5])
+
+
+def test_every_dtts_name_of_the_sources_is_in_design_md():
+    """DESIGN.md par. 4.10 is the one list of the library's switches: every DTTS_* name that the C++ sources or the Python package spell
+    (environment switches, compile-time defines and the macros that share the prefix) appears there by its full name.  Plain text search."""
+    import glob
+    pkg = os.path.join(ROOT, "detail_tts_amd")
+    files = glob.glob(os.path.join(pkg, "csrc", "*.hip")) + glob.glob(os.path.join(pkg, "csrc", "*.h")) + glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True)
+    assert len(files) > 40, len(files)
+    name = re.compile(r"DTTS_[A-Z0-9_]+")
+    used = {}
+    for f in files:
+        for n in name.findall(open(f, encoding="utf-8").read()):
+            used.setdefault(n, os.path.relpath(f, ROOT))
+    assert "DTTS_CONV_X3" in used and "DTTS_LIB_PATH" in used
+    documented = set(name.findall(open(os.path.join(ROOT, "DESIGN.md"), encoding="utf-8").read()))
+    missing = {n: f for n, f in used.items() if n not in documented}
+    assert not missing, missing
