@@ -284,6 +284,13 @@ int dtts_gpt_latents(dtts_handle* h, const float* refer, const int* refer_lens, 
     DTTS_API_END(h)
 }
 
+int dtts_gpt_score(dtts_handle* h, const float* latents_cm, int lat_stride, const int* targets, const int* ntargets, int n_max, int B,
+                   float* logprob_out, float* logits_out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->gpt_score(latents_cm, lat_stride, targets, ntargets, n_max, B, logprob_out, logits_out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
 int dtts_diff_conditioning(dtts_handle* h, const float* refer, const int* lens, int B, int Tmax, float* cond_out, void* stream) {
     DTTS_API_BEGIN
     h->m->diff_conditioning(refer, lens, B, Tmax, cond_out, (hipStream_t)stream);

@@ -157,4 +157,25 @@ void launch_gpt_token(const GptTokenParams& p, hipStream_t s);
 bool gpt_token_n_prepare();          // gpt_token_n.hip: kernel attributes of the 64 / 32-workgroup instantiations
 void launch_gpt_token_n(const GptTokenParams& p, hipStream_t s);      // called by launch_gpt_token when p.wgs < 128
 
+// ---- log-probability of given codes from latents (gpt_score.hip): mel_head GEMM fused with an online log-sum-exp over V and the
+// gather of the target logit; V is split over workgroups (SCORE_CHUNKS chunks of 128 packed rows each) and merged in split order
+constexpr int SCORE_CHUNKS = 5;
+struct ScoreParams {
+    const float* lat;            // latents_cm [B][C][lat_cs]: column k = final_norm(ln_f(h)) at position k
+    long long lat_bs;
+    int lat_cs;
+    const float *w, *bias;       // mel_head as bound: K-major [CinP][CoutP], bias [CoutP]
+    int C, CinP, V, CoutP;
+    const int* targets;          // DEVICE [B][n_max]
+    const int* ntargets;         // DEVICE [B]
+    const int* tiles;            // DEVICE [ntiles][2]: (row b, first column) of every live 128-column tile
+    int B, n_max;
+    float* part;                 // [splits][B][n_max][3] (max, sum, target logit): gpt_score_part_floats
+    float* out;                  // [B][n_max]
+    float* logits_out;           // [B][V][n_max] or null
+};
+int gpt_score_splits(int CoutP);
+size_t gpt_score_part_floats(int B, int n_max, int CoutP);
+void launch_gpt_score(const ScoreParams& p, int ntiles, hipStream_t s);      // ntiles = 0: only the zero fill of the merge pass
+
 }  // namespace dtts

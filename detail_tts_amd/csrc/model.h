@@ -224,6 +224,9 @@ public:
     void gpt_latents(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host,
                      int Lt_max, const int* codes_host, const int* ncodes_host, int n_max, int B, float* latents_cm, int lat_stride,
                      hipStream_t s);
+    // log p(targets[b][k] | latents_cm[b, :, k]) under the unprocessed distribution (gpt_score.hip); targets / ntargets HOST; asynchronous
+    void gpt_score(const float* latents_cm, int lat_stride, const int* targets_host, const int* ntargets_host, int n_max, int B,
+                   float* logprob_out, float* logits_out, hipStream_t s);
     // ---- stage C
     void mel_style(const MelStyleW& w, const float* mel, const int* lens_dev, const int* lens_host, int B, int T, float* g_out,
                    hipStream_t s);
@@ -420,6 +423,7 @@ private:
 
     Arena gpt_persist_;                   // LayerNorm-algebra vectors (bind time)
     Arena gpt_tokw_;                      // weights repacked for the persistent token kernel (bind time)
+    Arena gpt_score_ws_;                  // gpt_score's per-split partials, sized at bind time for 16 rows x gpt_max_mel_pos columns
     std::vector<GptTokenLayer> tok_layers_;   // host copy of the layer table (uploaded at bind time)
     GptTokenParams tokp_;                 // its launch parameters (weight side filled at bind time, session side at prefill)
     bool tok_ok_ = false;                 // the model has the shape the token kernel is written for

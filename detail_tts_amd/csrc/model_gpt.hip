@@ -104,6 +104,8 @@ void Model::build_gpt(hipStream_t s) {
         tokp_.Vs = GPT_TOKEN_VS;
         tokp_.lnf_g = lnf_g_; tokp_.lnf_b = lnf_b_; tokp_.fin_g = fin_g_; tokp_.fin_b = fin_b_;
     }
+    // gpt_score's partials for a full group (16 rows x every mel position): no allocation in its launch path
+    gpt_score_ws_.ensure(sizeof(float) * gpt_score_part_floats(GEMV_MAXB, cfg.gpt_max_mel_pos, mel_head_.CoutP) + 4096);
     gpt_drop_graphs();      // captured graphs hold the old weight pointers
     gs_ = GptSession();
 }
@@ -808,6 +810,55 @@ void Model::gpt_latents(const float* refer, const int* refer_lens_host, int Tr, 
     hipLaunchKernelGGL(copy_columns_kernel, dim3(cdiv(n_max, 128) > 0 ? cdiv(n_max, 128) : 1, C, B), dim3(128), 0, s, emb, bs, L, d_c0,
                        d_nn, C, latents_cm, (long long)C * lat_stride, lat_stride);
     DTTS_CHECK_HIP(hipGetLastError());
+}
+
+// gpt/model.py:408-415 (mel_head on final_norm's output) + log_softmax + gather, on latents the decode / the teacher-forced pass left:
+// column k of latents_cm is the hidden state token k was drawn from, so logprob[b][k] = log p(targets[b][k]) under the UNPROCESSED
+// distribution.  Rows run in groups of 16 (one targets table per group); everything is enqueued on s, nothing is allocated unless a
+// call asks for more columns than the model has mel positions.
+void Model::gpt_score(const float* latents_cm, int lat_stride, const int* targets_host, const int* ntargets_host, int n_max, int B,
+                      float* logprob_out, float* logits_out, hipStream_t s) {
+    DTTS_REQUIRE(bound_ && has_gpt_, "gpt weights not bound");
+    DTTS_REQUIRE(B >= 0 && n_max >= 0, "gpt_score: B, n_max");
+    if (B == 0 || n_max == 0) return;
+    DTTS_REQUIRE(latents_cm && targets_host && ntargets_host && logprob_out, "gpt_score: null argument");
+    DTTS_REQUIRE(n_max <= lat_stride, "gpt_score: n_max exceeds the latents' column stride");
+    DTTS_REQUIRE(n_max <= 4096, "gpt_score: at most 4096 positions per row");
+    const int C = cfg.gpt_dim, V = cfg.gpt_mel_codes;
+    for (int b = 0; b < B; ++b) {
+        DTTS_REQUIRE(ntargets_host[b] >= 0 && ntargets_host[b] <= n_max, "gpt_score: ntargets outside [0, n_max]");
+        for (int k = 0; k < ntargets_host[b]; ++k) {
+            const int t = targets_host[(size_t)b * n_max + k];
+            DTTS_REQUIRE(t >= 0 && t < V, "gpt_score: target outside the mel_head's rows");
+        }
+    }
+    for (int g0 = 0; g0 < B; g0 += GEMV_MAXB) {
+        const int nb = std::min(GEMV_MAXB, B - g0);
+        std::vector<int> tg((size_t)nb * n_max, 0), tiles;
+        for (int b = 0; b < nb; ++b) {
+            const int nt = ntargets_host[g0 + b];
+            std::copy(targets_host + (size_t)(g0 + b) * n_max, targets_host + (size_t)(g0 + b) * n_max + nt, tg.begin() + (size_t)b * n_max);
+            for (int n0 = 0; n0 < nt; n0 += 128) { tiles.push_back(b); tiles.push_back(n0); }
+        }
+        const size_t need = sizeof(float) * gpt_score_part_floats(nb, n_max, mel_head_.CoutP) + 4096;
+        if (need > gpt_score_ws_.capacity()) gpt_score_ws_.ensure(need);
+        gpt_score_ws_.reset();
+        ScoreParams p;
+        p.lat = latents_cm + (size_t)g0 * C * lat_stride;
+        p.lat_bs = (long long)C * lat_stride;
+        p.lat_cs = lat_stride;
+        p.w = mel_head_.w;
+        p.bias = mel_head_.b;
+        p.C = C; p.CinP = mel_head_.CinP; p.V = V; p.CoutP = mel_head_.CoutP;
+        p.targets = upload_ints(tg.data(), (int)tg.size(), s);
+        p.ntargets = upload_ints(ntargets_host + g0, nb, s);
+        p.tiles = upload_ints(tiles.data(), (int)tiles.size(), s);
+        p.B = nb; p.n_max = n_max;
+        p.part = gpt_score_ws_.f32(gpt_score_part_floats(nb, n_max, mel_head_.CoutP));
+        p.out = logprob_out + (size_t)g0 * n_max;
+        p.logits_out = logits_out ? logits_out + (size_t)g0 * V * n_max : nullptr;
+        launch_gpt_score(p, (int)tiles.size() / 2, s);
+    }
 }
 
 }  // namespace dtts

@@ -112,4 +112,16 @@ class UnifiedVoice:
         lat = self.rt.gpt_latents(refer, cl, self._texts(text_inputs, text_lengths), code_list)
         return lat.permute(0, 2, 1).contiguous()
 
+    def mel_logprobs(self, speech_conditioning_latent, cond_lengths, text_inputs, text_lengths, mel_codes_list):
+        """Teacher-forced log-probabilities: for every row the fp32 numpy array log p(c_k | prompt, c_1 .. c_{k-1}), k = 1 .. n, of its
+        codes c_1 .. c_n under the model's unprocessed distribution = log_softmax(mel_logits)[c_k] of the reference's forward
+        (gpt/model.py:408-415, 479) at the positions of the codes.  Rows may differ in length; append the stop token (8193) to a row to
+        score its stop as well.  Runs rt.gpt_latents, then rt.gpt_score on those latents (no [B, V, n] logits are materialised)."""
+        refer = speech_conditioning_latent.float().contiguous()
+        cl = None if cond_lengths is None else torch.as_tensor(cond_lengths).reshape(-1).tolist()
+        codes = [np.asarray(torch.as_tensor(c).cpu().numpy() if not isinstance(c, np.ndarray) else c, np.int32).reshape(-1) for c in mel_codes_list]
+        lat = self.rt.gpt_latents(refer, cl, self._texts(text_inputs, text_lengths), codes)
+        lp = self.rt.gpt_score(lat, codes).cpu().numpy()
+        return [lp[b, : len(c)].copy() for b, c in enumerate(codes)]
+
     __call__ = forward

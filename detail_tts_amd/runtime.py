@@ -273,6 +273,26 @@ class Runtime:
                                            _ptr(lat), nmax, self._stream()))
         return lat
 
+    def gpt_score(self, lat, codes_list, want_logits=False):
+        """log p(codes_list[b][k] | lat[b, :, k]) under the model's unprocessed distribution (dtts_gpt_score): lat cuda [B,768,>= n_max] as
+        gpt_generate / gpt_finish / gpt_latents return it, codes_list one int array per row (any lengths, 0 included) ->
+        logprob cuda fp32 [B, n_max] (0.0 at / beyond a row's length) [, logits cuda [B, V, n_max] with want_logits].  Asynchronous."""
+        _check(lat, "lat")
+        B, _, stride = lat.shape
+        if len(codes_list) != B:
+            raise DttsError(f"gpt_score: {len(codes_list)} code rows for {B} latent rows")
+        nn = np.array([len(c) for c in codes_list], np.int32).reshape(B)
+        nmax = int(nn.max()) if B else 0
+        out = torch.zeros((B, nmax), device=self.device, dtype=torch.float32)
+        logits = torch.zeros((B, self.cfg["gpt"]["number_mel_codes"], nmax), device=self.device, dtype=torch.float32) if want_logits else None
+        codes = np.zeros((B, max(nmax, 1)), np.int32)[:, :nmax]
+        codes = np.ascontiguousarray(codes)
+        for b, c in enumerate(codes_list):
+            codes[b, :len(c)] = np.asarray(c, np.int32)
+        self._rc(self.lib.dtts_gpt_score(self.h, _ptr(lat), int(stride), codes.ctypes.data_as(_lib.c_int_p), nn.ctypes.data_as(_lib.c_int_p),
+                                         nmax, B, _ptr(out), _ptr(logits), self._stream()))
+        return (out, logits) if want_logits else out
+
     # ------------------------------------------------------------------ stage B
     def diff_conditioning(self, refer, lens=None):
         _check(refer, "refer")

@@ -16,6 +16,7 @@ import torch
 
 from ..config import COND_FREE_K, INFER_DIFFUSION_STEPS, MAX_GENERATE_LENGTH, MEL_MIN, NOISE_SCALE, REPETITION_PENALTY, TEMPERATURE, \
     TOP_P, TORCH_MEL_MAX, TRAINED_DIFFUSION_STEPS, load_config
+from ..gpt.candidates import check_choose, check_num_candidates, expand_sample_ids, rank_candidates
 from ..gpt.model import UnifiedVoice
 from ..runtime import Runtime
 from .diff_model import DiffusionTts
@@ -193,8 +194,18 @@ class SynthesizerTrn:
     def infer(self, text, text_length, refer, refer_lengths, noise_scale=NOISE_SCALE, *, batch=False, seed=None, sample_ids=None,
               forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False, return_lengths=False,
               stream_vocoder=False, vocoder_chunk=256, wait=True, check_range=True, diffusion_steps=None, sampler="p", eta=0.0,
-              trunk_precision=None):
+              trunk_precision=None, num_candidates=1, choose=None, return_candidates=False):
         """vqvae/model_24k.py:774-810.  Returns wav [B,1,1024*n_max] (B=1 unless batch=True).
+
+        num_candidates = N in 1 .. 16 (not with forced_codes): stage A samples N code sequences per utterance (rows expanded with
+        repeat_interleave; candidate c of utterance b draws from Philox stream sample_ids[b] + c * 2**20, so candidate 0 IS the N = 1
+        decode), scores each with the model's own log-probability from the decode-time latents (dtts_gpt_score: one fused launch, no second
+        GPT pass) and keeps the best (gpt/candidates.py rank_candidates: mean log-probability, candidates that drew the stop token
+        first, ties to the lowest index), or candidate choose[b].  Stages B and C run on the B winners with the original sample_ids:
+        when candidate 0 wins the waveform is the N = 1 call's bit for bit.  return_candidates: the call also returns
+        dict(codes [B,N,G], ncodes [B,N], scores [B,N], stopped [B,N], chosen [B]) as its last value.  The default (N = 1, no
+        return_candidates) launches no scoring and is unchanged.  Whether best-of-N improves the audio is unmeasured (no trained
+        checkpoint).
 
         diffusion_steps / sampler / eta: stage B's schedule (None = the reference's 50 steps) and sampler ("p" = the reference's
         ancestral p_sample_loop, "ddim" = ddim_sample_loop with `eta`, "dpmsolver++" = the DPM-Solver++(2M) the reference's own
@@ -214,6 +225,7 @@ class SynthesizerTrn:
         stays asynchronous: wait on `self.vocoder_done`, then call `self.check_vocoder()` before reading the waveform."""
         sched_ts, sampler_id, eta = sampling_args(diffusion_steps, sampler, eta)
         prec = SynthesizerTrn._check_trunk_precision(self, trunk_precision)
+        ncand = check_num_candidates(num_candidates, forced_codes)
         text = torch.as_tensor(text)
         refer = torch.as_tensor(refer)
         tl = torch.as_tensor(text_length).reshape(-1).tolist()
@@ -223,13 +235,19 @@ class SynthesizerTrn:
             if forced_codes is not None:
                 forced_codes = forced_codes[:1]
         B = text.shape[0]
+        choose = check_choose(choose, B, ncand)
+        candidates = (ncand > 1 or return_candidates) and forced_codes is None
+        if return_candidates and not candidates:
+            raise ValueError("return_candidates: forced_codes leave no candidates to report")
+        sample_ids = list(range(B)) if sample_ids is None else list(sample_ids)
+        cand_ids = expand_sample_ids(sample_ids, ncand) if candidates else None      # (ValueError on colliding streams: before any launch)
         refer = refer.to(self.device, torch.float32).contiguous()
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        sample_ids = list(range(B)) if sample_ids is None else list(sample_ids)
         texts = [text[b, : int(tl[b])].cpu().numpy().astype(np.int32) for b in range(B)]
         rl = [int(v) for v in rl]
         ev = []
+        cand = None
 
         def mark(name):
             if self.stage_ms is not None:
@@ -239,12 +257,19 @@ class SynthesizerTrn:
 
         mark("start")
         # ---- stage A: codes + latents (:782-799)
-        session = forced_codes is None and B <= 16
+        session = forced_codes is None and B * (ncand if candidates else 1) <= 16
         if forced_codes is None:
             kw = dict(max_generate_length=max_generate_length, top_k=top_k, top_p=TOP_P, temperature=TEMPERATURE,
                       repetition_penalty=REPETITION_PENALTY, suppress_eos=suppress_eos)
+            a_refer, a_rl, a_texts, a_ids = refer, rl, texts, sample_ids
+            if candidates and ncand > 1:                            # HF's num_return_sequences expansion: every row N times
+                a_refer = refer.repeat_interleave(ncand, 0).contiguous()
+                a_rl = [v for v in rl for _ in range(ncand)]
+                a_texts = [t for t in texts for _ in range(ncand)]
+            if candidates:
+                a_ids = cand_ids
             if session:         # one decode session: prefill (+ first token), then 16-token chunks; finish flags polled per chunk
-                self.rt.gpt_prefill(refer, rl, texts, seed, sample_ids, **kw)
+                self.rt.gpt_prefill(a_refer, a_rl, a_texts, seed, a_ids, **kw)
                 mark("gpt_prefill")
                 while self.rt.gpt_steps() < max_generate_length:
                     if not suppress_eos and self.rt.gpt_all_finished():
@@ -252,7 +277,23 @@ class SynthesizerTrn:
                     self.rt.gpt_decode(16)
                 codes, ncodes, lat = self.rt.gpt_finish()
             else:
-                codes, ncodes, lat = self.rt.gpt_generate(refer, rl, texts, seed, sample_ids, **kw)
+                codes, ncodes, lat = self.rt.gpt_generate(a_refer, a_rl, a_texts, seed, a_ids, **kw)
+            if candidates:
+                # the model's own log-probability of every candidate, from the latents its tokens were drawn from (stop token included)
+                nc = [int(c) for c in ncodes]
+                logp = self.rt.gpt_score(lat, [codes[r, : nc[r]] for r in range(B * ncand)]).cpu().numpy()
+                stopped = [bool(codes[r, nc[r] - 1] == self.gpt.stop_mel_token) for r in range(B * ncand)]
+                chosen, scores = [], np.zeros((B, ncand), np.float64)
+                for b in range(B):
+                    r0, r1 = b * ncand, (b + 1) * ncand
+                    best, scores[b] = rank_candidates(logp[r0:r1], nc[r0:r1], stopped[r0:r1])
+                    chosen.append(best if choose is None else choose[b])
+                cand = dict(codes=codes.reshape(B, ncand, -1).copy(), ncodes=np.asarray(nc, np.int32).reshape(B, ncand), scores=scores,
+                            stopped=np.asarray(stopped, bool).reshape(B, ncand), chosen=list(chosen))
+                rows = [b * ncand + c for b, c in enumerate(chosen)]
+                ncodes = ncodes[rows]
+                if ncand > 1:                                       # the winners' latent rows, gathered on the device
+                    lat = lat.index_select(0, torch.as_tensor(rows, device=self.device))
             n = [int(c) - 1 for c in ncodes]                       # codes = codes[:, :-1]  (:795)
             if min(n) < 1:
                 raise ValueError("an utterance produced no mel codes (stop token first)")
@@ -298,8 +339,8 @@ class SynthesizerTrn:
             for (_, a), (nm, b) in zip(ev[:-1], ev[1:]):
                 self.stage_ms[nm] = self.stage_ms.get(nm, 0.0) + a.elapsed_time(b)
         if return_lengths:
-            return wav, [1024 * v for v in n]
-        return wav
+            return (wav, [1024 * v for v in n], cand) if return_candidates else (wav, [1024 * v for v in n])
+        return (wav, cand) if return_candidates else wav
 
     def check_vocoder(self, ticket=None):
         """raise if the stage-C call `ticket` (default: the last one issued) saturated; the caller has waited for its waveform"""

@@ -164,6 +164,19 @@ int dtts_gpt_latents(dtts_handle* h, const float* refer, const int* refer_lens, 
                      int Lt_max, const int* codes, const int* ncodes, int n_max, int B, float* latents_cm, int lat_stride,
                      void* stream);
 
+/* gpt/model.py:408-415 + log_softmax + gather: logprob[b][k] = log p(targets[b][k] | latents_cm[b,:,k]) under the
+ * UNPROCESSED model distribution (temperature 1, no penalty / top-k / top-p).  latents_cm DEVICE [B,768,lat_stride] as
+ * dtts_gpt_generate / dtts_gpt_prefill / dtts_gpt_latents leave it (column k = the hidden state token k is drawn from);
+ * targets HOST [B][n_max] (range-checked before any launch: 0 <= t < 8194), ntargets HOST [B] in [0, n_max], n_max <= lat_stride.
+ * logprob_out DEVICE [B][n_max]: columns at / beyond ntargets[b] receive 0.0.  logits_out DEVICE [B][8194][n_max] or NULL:
+ * the raw mel_head logits from the same accumulators (columns at / beyond ntargets[b] are left untouched); with NULL no
+ * [B,V,n] buffer exists anywhere.  One fused kernel (mel_head GEMM + online log-sum-exp over V + gather, V split over
+ * workgroups) and a merge pass in fixed order: no atomics, two calls give the same bits.  Asynchronous on `stream`; no
+ * allocation in the launch path (the partials' workspace is sized at bind time); B * n_max == 0 is a no-op.  One caller
+ * per handle at a time. */
+int dtts_gpt_score(dtts_handle* h, const float* latents_cm, int lat_stride, const int* targets, const int* ntargets, int n_max,
+                   int B, float* logprob_out, float* logits_out, void* stream);
+
 /* ---- stage B: diffusion mel decoder ---------------------------------------------------------- */
 
 /* DiffusionTts.get_conditioning (vqvae/diff_model.py:221-229): refer [B,128,Tmax] -> cond [B,1536] */
