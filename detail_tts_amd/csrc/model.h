@@ -17,6 +17,8 @@
 #include "attention.h"
 #include "common.h"
 #include "conv_gemm.h"
+#include "conv_x3.h"
+#include "diff_schedule.h"
 #include "gpt_kernels.h"
 #include "ops.h"
 #include "../../include/detail_hip.h"
@@ -31,6 +33,13 @@ struct PackedConv {
 };
 
 static inline int packed_cout(int cout) { return cout > 64 ? round_up(cout, 128) : (cout > 32 ? 64 : 32); }
+
+// GroupNorm groups of a C-channel norm (normalization(), vqvae/utils/diff_util.py): 32, halved until it divides C
+static inline int gn_groups(int C) {
+    int groups = 32;
+    while (C % groups) groups /= 2;
+    return groups;
+}
 
 struct AttnBlockW {
     const float *gn_g = nullptr, *gn_b = nullptr, *bias_tab = nullptr;
@@ -132,37 +141,6 @@ private:
     Arena* prev_;
 };
 Arena* arena_override();     // the calling thread's stand-in (nullptr: none)
-
-// A sampling schedule: SpacedDiffusion(use_timesteps = tmap, linear betas over cfg.diff_trained_steps) (vqvae/utils/diffusion.py:1172-1220).
-// The coefficient tables are computed in float64 on the host and cast to fp32; ss_table holds every ResBlock's AdaGN scale / shift
-// at every step of the schedule: emb_layers(time_embed(sinusoid(tmap[i]))) (vqvae/diff_model.py:294, 108).
-// Float-time schedules (kind != 0) carry fp32 model times instead of tmap: DPM-Solver++(2M) of n steps (kind 1: k_diffusion_sample_loop,
-// vqvae/utils/diffusion.py:487-581), or fractional forward times alone (kind 2: diff_forward_tf).  Column i of every table is step
-// n - 1 - i of the loop (n - 1 = first), as for the integer schedules, so the samplers' loop and the trunk read them the same way.
-struct Schedule {
-    int id = 0;                           // 0: the default (cfg.diff_steps) schedule built at bind
-    int kind = 0;                         // 0: integer timesteps (tmap); 1: DPM-Solver++(2M); 2: fractional model times (forward only)
-    std::vector<int> tmap;                // kind 0: model timesteps of the spaced steps, ascending (timestep_map)
-    std::vector<float> ftimes;            // kinds 1, 2: fp32 model time of column i, ascending (kind 1: t_{n-1-i} * 1000)
-    std::vector<DiffStepCoefs> p;         // ancestral sampler (p_sample)
-    std::vector<float> ac, ac_prev;       // fp32 alphas_cumprod / alphas_cumprod_prev (DDIM: the eta-dependent terms are per call)
-    std::vector<DpmStepCoefs> dpm;        // kind 1: the update of column i
-    float cfk_k = 0.f;
-    const float* ss_table = nullptr;      // [n_resblocks][2C][n]
-    int n = 0;
-    void* mem = nullptr;                  // owned device memory (cached schedules; the default one lives in the bind-time arena)
-    hipEvent_t used = nullptr;            // recorded after every call that read ss_table: an eviction waits for it
-    ~Schedule();
-    DdimStepCoefs ddim(int i, float eta) const;
-    bool same_key(const Schedule& o) const { return kind == o.kind && tmap == o.tmap && ftimes == o.ftimes; }
-};
-
-// DPM-Solver++(2M) of n >= 2 steps as the reference's DPM_Solver.sample runs it (vqvae/utils/dpm_solver.py:1159-1201: time_uniform,
-// multistep, order 2, lower_order_final) on NoiseScheduleVP("linear", 0.025, 5.0) (:108-154), in fp32 in the reference's order of
-// operations.  times [n + 1]: torch.linspace(1, 1e-3, n + 1) in fp32; model_times [n]: t_k * 1000; steps [n]: the update t_k -> t_{k+1}
-// in the solver's order (k = 0 first); lambda_s [n] (optional): lambda(t_k).
-void dpm_schedule_table(int n, float cfk, std::vector<float>& times, std::vector<float>& model_times, std::vector<DpmStepCoefs>& steps,
-                        std::vector<float>* lambda_s = nullptr);
 
 class Model {
 public:
@@ -328,7 +306,14 @@ private:
     void gpt_prefill_layers(float* x, const int* lens, int B, int L, float* kv_cache, long long kv_layer_stride, long long kv_bs,
                             int kv_cs, hipStream_t s);
     MelStyleW mel_style_w(const std::string& prefix, int n_mel, int hidden, int out) const;
+    // the one place a ConvParams is laid out: x [B, cin, Ta] -> y [B, cout, Ta], T live columns, lengths `lens` (device) on both sides
     ConvParams cp(const float* x, int cin, float* y, int cout, int B, int T, int Ta, const int* lens) const;
+    // ... and with an output side of its own (strided convs): x [B, cin, Tin_a] / len_in -> y [B, cout, Nout_a] / len_out
+    ConvParams cp(const float* x, int cin, int Tin, int Tin_a, const int* len_in, float* y, int cout, int Nout, int Nout_a, const int* len_out,
+                  int B) const;
+    // the input's split-precision planes xs (made for T columns) / a residual [., ., cs] added in the epilogue
+    static void with_planes(ConvParams& p, const void* xs, int T) { p.x3 = xs; p.x3_tp = x3_tp(T); }
+    static void with_res(ConvParams& p, const float* res, long long bs, int cs) { p.res = res; p.res_bs = bs; p.res_cs = cs; }
 
     const int* upload_ints(const int* host, int n, hipStream_t s);
     // Ragged batches: build, upload and remember (per host thread, keyed by the device address of the lengths) the table of live
@@ -338,9 +323,8 @@ private:
 
     // building blocks on [B, C, T] buffers (all lens are device pointers)
     void run_conv(const PackedConv& pc, ConvParams p, hipStream_t s) const;
-    // xs: scratch for the split-precision input planes (x3_bytes(B, C, T)); null -> exact fp32 MFMA path
     // GnNext / GnFuse: the GroupNorm + activation + split that FOLLOWS a block runs in the epilogue of the block's last conv
-    // (conv_x3.h "fused GroupNorm").  `f` carries the second planes buffer (producer and consumer planes ping-pong between xs and
+    // (conv_x3.h "fused GroupNorm").  TrunkIo::f carries the second planes buffer (producer and consumer planes ping-pong between xs and
     // f->xs_alt), the exchange buffer of the launch stream and whether xs ALREADY holds the block's normalised input (written by the
     // previous block's last conv).  next == nullptr: the block's output is left un-normalised (fp32 rows only).
     struct GnNext {
@@ -352,10 +336,22 @@ private:
         int slot = 0;                // exchange buffer / tag counter of this launch stream (gn_xch_)
         bool in_ready = false;
     };
-    void attention_block(const AttnBlockW& w, const float* x, float* y, float* qkv, float* att, float* ab, const int* lens, int B,
-                         int T, int Ta, hipStream_t s, void* xs = nullptr, GnFuse* f = nullptr, const GnNext* next = nullptr);
-    void res_block_fwd(const Schedule& sc, const ResBlockW& w, const float* x, float* h1, float* y, float* ab, const int* lens, int B, int T, int Ta,
-                       int step, hipStream_t s, void* xs = nullptr, const int* step_idx = nullptr, GnFuse* f = nullptr,
+    // what every launch of a trunk block shares: the batch, its stream and scratch, and the kernel mode
+    struct TrunkIo {
+        const int* lens;             // device lengths [B]
+        int B, T, Ta;                // samples, live columns, allocated columns of the [B, C, Ta] buffers
+        hipStream_t s;
+        float* ab;                   // GroupNorm coefficients [B, C, 2] of the exact fp32 path
+        void* xs = nullptr;          // scratch for the split-precision input planes (x3_bytes(B, C, T)); null -> exact fp32 MFMA path
+        GnFuse* f = nullptr;
+        bool p1 = false;             // option "trunk_fp16" covers this block: one fp16 product (ConvParams::p1 / AttnParams::p1) instead of three
+        const int* step_idx = nullptr;   // ResBlock: per-sample step (device) of a batch whose samples sit at different sampling steps
+    };
+    // the norm in front of a block's first conv: planes of act(GN(x)) in io.xs (x3), else coefficients in io.ab for the conv's prologue;
+    // nothing when the previous conv's fused epilogue has written the planes already
+    void norm_input(const float* x, int C, const float* gamma, const float* beta, int act, bool x3, const TrunkIo& io);
+    void attention_block(const AttnBlockW& w, const float* x, float* y, float* qkv, float* att, const TrunkIo& io, const GnNext* next = nullptr);
+    void res_block_fwd(const Schedule& sc, const ResBlockW& w, const float* x, float* h1, float* y, int step, const TrunkIo& io,
                        const GnNext* next = nullptr);
     // fused-GroupNorm plumbing: per launch stream an exchange buffer (zeroed when (re)allocated; only ever holds tags of earlier
     // launches) and a tag counter; one host-mapped error flag the kernels raise when a poll gives up
@@ -383,6 +379,13 @@ private:
                                float* integ_all, hipStream_t s, std::vector<std::pair<int, hipEvent_t>>* ready = nullptr);
     struct PairPlan { const int *lens2, *lens_i, *umap; int Nu; std::vector<int> ulen; };
     PairPlan plan_pair(const int* lens_host, int B, int T, hipStream_t s);
+    // what the entry points around one diff_forward_pair share: the workspace sized for the call (+ extra_bytes, + hist_floats), the plan,
+    // the sample ids (optional), cbuf0 = (code_emb, or the unconditioned embedding when null | unconditional inputs), out2 [2B, OC, T]
+    // and the DPM-Solver++ history [hist_floats]
+    struct PairCall { PairPlan pl; const int* sids; float *cbuf0, *out2, *hist; };
+    PairCall begin_pair(const float* code_emb, const int* lens_host, const int* sample_ids_host, int B, int T, hipStream_t s,
+                        size_t extra_bytes = 0, size_t hist_floats = 0);
+    void ensure_fork_events();
 
     std::unordered_map<std::string, std::pair<const float*, size_t>> weights_;
     bool bound_ = false;

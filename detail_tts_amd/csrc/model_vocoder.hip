@@ -221,18 +221,7 @@ static size_t generator_planes_bytes(const dtts_config& cfg, int B, int T) {
 void Model::resblock1_fwd(const ResBlock1W& rb, const float* x, float* tmp, float* out, int ch, const int* lens, int B, int T, hipStream_t s,
                           void* xs) {
     auto cp = [&](const float* in, float* o) {
-        ConvParams p;
-        p.B = B;
-        p.Tin = T;
-        p.Nout = T;
-        p.len_in = lens;
-        p.len_out = lens;
-        p.x = in;
-        p.x_bs = (long long)ch * T;
-        p.x_cs = T;
-        p.y = o;
-        p.y_bs = (long long)ch * T;
-        p.y_cs = T;
+        ConvParams p = this->cp(in, ch, o, ch, B, T, T, lens);
         p.pro_act = ACT_LRELU;
         p.pro_slope = 0.1f;
         return p;
@@ -534,21 +523,7 @@ void Model::op_generator(const float* z, const float* g, const int* lens_host, i
 void Model::wn_fwd(const CouplingW& c, float* h, const float* g, int gin, float* Gc, float* acts, float* h2, float* skip, const int* dl,
                    int B, int T, hipStream_t s) {
     const int hid = cfg.hidden_channels;
-    auto cp = [&](const float* in, float* o) {
-        ConvParams p;
-        p.B = B;
-        p.Tin = T;
-        p.Nout = T;
-        p.len_in = dl;
-        p.len_out = dl;
-        p.x = in;
-        p.x_bs = (long long)hid * T;
-        p.x_cs = T;
-        p.y = o;
-        p.y_bs = (long long)hid * T;
-        p.y_cs = T;
-        return p;
-    };
+    auto cp = [&](const float* in, float* o) { return this->cp(in, hid, o, hid, B, T, T, dl); };
     // G = cond_layer(g): [B, 1536] in packed (gate-interleaved) row order
     ConvParams q;
     q.B = B;
@@ -905,22 +880,14 @@ void Model::vq_encode(const float* mel, const int* lens_host, int B, int T, int*
     const int* d1 = upload_ints(l1.data(), B, s);
     const int* d2 = upload_ints(l2.data(), B, s);
     launch_ln_channels(mel, nullptr, (long long)MC * T, T, d0, T, B, MC, vqe_ln_g_, vqe_ln_b_, 1e-5f, ln, (long long)MC * T, T, s);
-    ConvParams p = cp(ln, MC, h1, 2 * inter, B, T, T, d0);
+    ConvParams p = cp(ln, MC, T, T, d0, h1, 2 * inter, T1, T1, d1, B);
     p.stride = 2;
     p.pad = 1;
-    p.Nout = T1;
-    p.len_out = d1;
-    p.y_bs = (long long)2 * inter * T1;
-    p.y_cs = T1;
     p.epi_act = ACT_SILU;
     run_conv(vqe_c1_, p, s);
-    p = cp(h1, 2 * inter, h2, C, B, T1, T1, d1);
+    p = cp(h1, 2 * inter, T1, T1, d1, h2, C, T2, T2, d2, B);
     p.stride = 2;
     p.pad = 1;
-    p.Nout = T2;
-    p.len_out = d2;
-    p.y_bs = (long long)C * T2;
-    p.y_cs = T2;
     p.epi_act = ACT_SILU;
     run_conv(vqe_c2_, p, s);
     p = cp(h2, C, xv, C, B, T2, T2, d2);

@@ -256,6 +256,38 @@ def test_sampler_varlen_batch_equals_single(rt, weights):
         assert maxabs(xb[b, :, :L], xs[0]) < 1e-4, b
 
 
+def test_sampler_step_over_several_stream_chunks(rt, weights):
+    """Option cfg_streams = 1, 2, 4: the cond | uncond stack of a forward cut into that many chunks, each a launch sequence on its own
+    stream (the default takes more than one only from batch 5 up).  One ancestral step (step 49, device Philox noise) of a ragged batch
+    of 2 - one full row, one shorter than a 64-column tile - through diff_step: every row against the numpy oracle of that row alone,
+    at test_sampler_varlen_batch_equals_single's gate (the tighter of that test's and test_sampler_steps_golden's one-step gate).  The
+    settings are not compared with each other: their launch sizes differ, and the attention's key split of small launches may differ
+    with them."""
+    from oracle import diffusion as D, philox
+    rs = np.random.RandomState(17)
+    lens, i, seed, sids = [64, 40], 49, 99, [11, 12]
+    x = rs.randn(2, 128, 64).astype(np.float32)
+    ce = (rs.randn(2, 768, 64) * 0.5).astype(np.float32)
+    sched = D.make_schedule()
+    ts = [sched["timestep_map"][i]]
+    refs = []
+    for b, L in enumerate(lens):
+        xb, cb = x[b:b + 1, :, :L], ce[b:b + 1, :, :L]
+        noise = philox.normal(seed, sids[b], philox.STAGE_DIFF_STEP, i, 128 * L).reshape(1, 128, L)
+        refs.append(D.p_sample_update(sched, i, xb, D.diffusion_forward(weights, xb, ts, cb),
+                                      D.diffusion_forward(weights, xb, ts, conditioning_free=True), noise)[0][0])
+    try:
+        for ns in (1, 2, 4):
+            rt.set_option("cfg_streams", ns)
+            y = host(rt.diff_step(dev(x), dev(ce), i, seed, sids, lens=lens))
+            for b, L in enumerate(lens):
+                e = maxabs(y[b, :, :L], refs[b])
+                print(f"\n[cfg_streams={ns}, row {b}] max-abs {e:.2e}")
+                assert np.isfinite(y[b, :, :L]).all() and e < 1e-4, (ns, b, e)
+    finally:
+        rt.set_option("cfg_streams", 0)
+
+
 def test_tiny_and_ragged_lengths(rt, weights):
     """T = 4 (one code), and lengths that are not multiples of any tile."""
     from oracle import diffusion as D
