@@ -291,6 +291,14 @@ int dtts_gpt_score(dtts_handle* h, const float* latents_cm, int lat_stride, cons
     DTTS_API_END(h)
 }
 
+int dtts_gpt_forward_losses(dtts_handle* h, const float* refer, const int* refer_lens, int Tr, const int* text_ids, int Lt, const int* mel_codes,
+                            int n, int B, float* losses_out, float* text_logprob, float* mel_logprob, float* mel_logits, void* stream) {
+    DTTS_API_BEGIN
+    h->m->gpt_forward_losses(refer, refer_lens, Tr, text_ids, Lt, mel_codes, n, B, losses_out, text_logprob, mel_logprob, mel_logits,
+                             (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
 int dtts_diff_conditioning(dtts_handle* h, const float* refer, const int* lens, int B, int Tmax, float* cond_out, void* stream) {
     DTTS_API_BEGIN
     h->m->diff_conditioning(refer, lens, B, Tmax, cond_out, (hipStream_t)stream);

@@ -178,4 +178,8 @@ int gpt_score_splits(int CoutP);
 size_t gpt_score_part_floats(int B, int n_max, int CoutP);
 void launch_gpt_score(const ScoreParams& p, int ntiles, hipStream_t s);      // ntiles = 0: only the zero fill of the merge pass
 
+// the two cross-entropy means of UnifiedVoice.forward (gpt/model.py:489-491): out[i] = -mean(lp_i[0 .. n_i)), lp_i DEVICE log-probabilities
+// as launch_gpt_score leaves them; fixed summation order (a function of n_i only), no atomics
+void launch_gpt_loss_means(const float* lp0, int n0, const float* lp1, int n1, float* out, hipStream_t s);
+
 }  // namespace dtts

@@ -658,6 +658,32 @@ void launch_gather_last(const float* x, long long bs, int cs, const int* lens, i
     DTTS_CHECK_HIP(hipGetLastError());
 }
 
+// F.cross_entropy's mean reduction over per-position log-probabilities (gpt/model.py:489-490): block i writes out[i] = -mean(lp_i[0 .. n_i)).
+// Thread t sums elements t, t + 256, ... in index order, then the 256 partials fold in a fixed tree: the order is a function of n_i
+// only (no atomics, two runs give the same bits) and the input is the FLAT [B * positions] array, so it does not see gpt_score's
+// row groups.  fp64 accumulators: the sum is exact to well below one fp32 ulp of the result at any n_i the model admits.
+constexpr int LOSS_THREADS = 256;
+__global__ __launch_bounds__(LOSS_THREADS) void gpt_loss_means_kernel(const float* lp0, int n0, const float* lp1, int n1, float* out) {
+    __shared__ double red[LOSS_THREADS];
+    const float* lp = blockIdx.x == 0 ? lp0 : lp1;
+    const int n = blockIdx.x == 0 ? n0 : n1;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += LOSS_THREADS) acc += (double)lp[i];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = LOSS_THREADS / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = (float)(-red[0] / (double)n);
+}
+
+void launch_gpt_loss_means(const float* lp0, int n0, const float* lp1, int n1, float* out, hipStream_t s) {
+    DTTS_REQUIRE(lp0 && lp1 && out && n0 >= 1 && n1 >= 1, "gpt_loss_means: operands");
+    hipLaunchKernelGGL(gpt_loss_means_kernel, dim3(2), dim3(LOSS_THREADS), 0, s, lp0, n0, lp1, n1, out);
+    DTTS_CHECK_HIP(hipGetLastError());
+}
+
 // ------------------------------------------------------------------------------------------ sampler
 // HF GenerationMixin._sample logits processing + inverse-CDF multinomial of the Philox spec.
 constexpr int SAMP_THREADS = 1024;

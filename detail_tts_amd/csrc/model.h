@@ -205,6 +205,11 @@ public:
     // log p(targets[b][k] | latents_cm[b, :, k]) under the unprocessed distribution (gpt_score.hip); targets / ntargets HOST; asynchronous
     void gpt_score(const float* latents_cm, int lat_stride, const int* targets_host, const int* ntargets_host, int n_max, int B,
                    float* logprob_out, float* logits_out, hipStream_t s);
+    // UnifiedVoice.forward's loss mode (gpt/model.py:429-491) on a RECTANGULAR batch: every row has Lt text ids and n mel codes (HOST).
+    // losses_out DEVICE [2] = (loss_text, loss_mel), the plain means over all B (Lt + 2) / B (n + 2) positions; optional DEVICE outputs:
+    // text_logprob [B][Lt + 2], mel_logprob [B][n + 2] (log-softmax at the targets), mel_logits [B][V][n + 2].  Needs gpt.text_head.
+    void gpt_forward_losses(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, int Lt, const int* codes_host, int n,
+                            int B, float* losses_out, float* text_logprob, float* mel_logprob, float* mel_logits, hipStream_t s);
     // ---- stage C
     void mel_style(const MelStyleW& w, const float* mel, const int* lens_dev, const int* lens_host, int B, int T, float* g_out,
                    hipStream_t s);
@@ -298,6 +303,20 @@ private:
     void build_vocoder(hipStream_t s);
     void build_gpt(hipStream_t s);
     void gpt_head_and_sample(hipStream_t s);
+    // The teacher-forced pass gpt_latents and gpt_forward_losses share: conditioning encoder, [cond | text | start, codes, stop]
+    // embeddings, the GPT-2 stack, ln_f and final_norm.  enc [B, C, L] (in ws(), which was sized with extra_ws_bytes to spare for the
+    // caller) holds final_norm(ln_f(h)) of every column; row b has 1 + tl[b] + ml[b] live columns.
+    struct GptForced {
+        float* enc = nullptr;
+        int L = 0;
+        std::vector<int> tl, ml;         // text positions (ids + 2) and mel positions (codes + 2) of every row
+    };
+    GptForced gpt_teacher_forced(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host,
+                                 int Lt_max, const int* codes_host, const int* ncodes_host, int n_max, int B, size_t extra_ws_bytes,
+                                 hipStream_t s);
+    // one head through gpt_score.hip over columns of lat [B][C][lat_cs] (targets range-checked by the caller), rows in groups of 16
+    void score_head(const PackedConv& head, const float* lat, long long lat_bs, int lat_cs, const int* targets_host, const int* ntargets_host,
+                    int n_max, int B, float* logprob_out, float* logits_out, hipStream_t s);
     void gpt_step_launches(hipStream_t s);
     hipGraphExec_t gpt_capture(int n);
     void gpt_drop_graphs();
@@ -421,6 +440,8 @@ private:
     // gpt
     std::vector<GptLayerW> gpt_layers_;
     PackedConv mel_head_;
+    PackedConv text_head_;                // optional (gpt.text_head.*): only UnifiedVoice.forward's loss mode reads it
+    bool has_text_head_ = false;
     const float *lnf_g_ = nullptr, *lnf_b_ = nullptr, *fin_g_ = nullptr, *fin_b_ = nullptr;
     const float *text_emb_ = nullptr, *mel_emb_ = nullptr, *text_pos_ = nullptr, *mel_pos_ = nullptr;
 

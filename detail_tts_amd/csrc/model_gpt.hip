@@ -41,6 +41,9 @@ void Model::build_gpt(hipStream_t s) {
     fin_g_ = W("gpt.final_norm.weight", C);
     fin_b_ = W("gpt.final_norm.bias", C);
     mel_head_ = conv("gpt.mel_head", C, cfg.gpt_mel_codes, 1);
+    // text_head (gpt/model.py:318): bound only when the checkpoint carries it; nothing on the inference path reads it
+    has_text_head_ = weights_.count("gpt.text_head.wp") != 0;
+    text_head_ = has_text_head_ ? conv("gpt.text_head", C, cfg.gpt_text_tokens, 1) : PackedConv();
     text_emb_ = W("gpt.text_embedding.weight", (size_t)cfg.gpt_text_tokens * C);
     mel_emb_ = W("gpt.mel_embedding.weight", (size_t)cfg.gpt_mel_codes * C);
     text_pos_ = W("gpt.text_pos_embedding.emb.weight", (size_t)cfg.gpt_max_text_pos * C);
@@ -744,18 +747,21 @@ void Model::op_sample_logits(const float* logits, int R, int V, const int* histo
     DTTS_CHECK_HIP(hipStreamSynchronize(s));
 }
 
-// UnifiedVoice.forward(..., return_latent=True) as called at vqvae/model_24k.py:796-799.
-// codes [B][n_max] host, n[b] valid -> latents_cm [B, C, lat_stride] (columns 0..n[b]-1)
-void Model::gpt_latents(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host,
-                        int Lt_max, const int* codes_host, const int* ncodes_host, int n_max, int B, float* latents_cm, int lat_stride,
-                        hipStream_t s) {
+// The teacher-forced pass over [cond | 255, text, 0 | 8192, codes, 8193] (gpt/model.py:463-476, 392-403): see model.h
+Model::GptForced Model::gpt_teacher_forced(const float* refer, const int* refer_lens_host, int Tr, const int* text_host,
+                                           const int* text_lens_host, int Lt_max, const int* codes_host, const int* ncodes_host, int n_max,
+                                           int B, size_t extra_ws_bytes, hipStream_t s) {
     DTTS_REQUIRE(bound_ && has_gpt_, "gpt weights not bound");
     const int C = cfg.gpt_dim;
-    std::vector<int> ids, tl;
+    GptForced f;
+    std::vector<int> ids;
     int tl_max;
-    text_prefix_ids(text_host, text_lens_host, B, Lt_max, cfg.gpt_text_tokens, ids, tl, tl_max);
+    text_prefix_ids(text_host, text_lens_host, B, Lt_max, cfg.gpt_text_tokens, ids, f.tl, tl_max);
     DTTS_REQUIRE(tl_max <= cfg.gpt_max_text_pos, "text too long");
-    std::vector<int> ml(B), lt(B), c0(B), nn(B);
+    const std::vector<int>& tl = f.tl;
+    std::vector<int>& ml = f.ml;
+    ml.resize(B);
+    std::vector<int> lt(B), nn(B);
     int ml_max = 0, L = 0;
     for (int b = 0; b < B; ++b) {
         nn[b] = ncodes_host ? ncodes_host[b] : n_max;
@@ -764,7 +770,6 @@ void Model::gpt_latents(const float* refer, const int* refer_lens_host, int Tr, 
         ml_max = std::max(ml_max, ml[b]);
         lt[b] = 1 + tl[b] + ml[b];
         L = std::max(L, lt[b]);
-        c0[b] = 1 + tl[b];                                  // column of the start_mel input
     }
     DTTS_REQUIRE(ml_max <= cfg.gpt_max_mel_pos, "too many mel codes");
     std::vector<int> mids((size_t)B * ml_max, 8193);
@@ -779,7 +784,7 @@ void Model::gpt_latents(const float* refer, const int* refer_lens_host, int Tr, 
         r[nn[b] + 1] = 8193;
     }
     ws().ensure(sizeof(float) * ((size_t)2 * B * C * L + (size_t)B * C) + prefill_ws(B, C, L) + sizeof(int) * mids.size() +
-               (size_t)sizeof(float) * ((size_t)5 * B * (C / 2) * Tr + (size_t)B * C * Tr) + 65536);
+               (size_t)sizeof(float) * ((size_t)5 * B * (C / 2) * Tr + (size_t)B * C * Tr) + 65536 + extra_ws_bytes);
     float* emb = ws().f32((size_t)B * C * L);
     float* enc = ws().f32((size_t)B * C * L);
     float* cond = ws().f32((size_t)B * C);
@@ -798,24 +803,75 @@ void Model::gpt_latents(const float* refer, const int* refer_lens_host, int Tr, 
     const int* d_tl = upload_ints(tl.data(), B, s);
     const int* d_ml = upload_ints(ml.data(), B, s);
     const int* d_lt = upload_ints(lt.data(), B, s);
-    const int* d_c0 = upload_ints(c0.data(), B, s);
-    const int* d_nn = upload_ints(nn.data(), B, s);
     DTTS_CHECK_HIP(hipMemsetAsync(emb, 0, sizeof(float) * (size_t)B * C * L, s));
     launch_build_prefix(cond, d_ids, tl_max, d_tl, text_emb_, text_pos_, mel_emb_, mel_pos_, d_mids, ml_max, d_ml, B, C, L, emb, s);
     gpt_prefill_layers(emb, d_lt, B, L, nullptr, 0, 0, 0, s);
     const long long bs = (long long)C * L;
     launch_ln_channels(emb, nullptr, bs, L, d_lt, L, B, C, lnf_g_, lnf_b_, 1e-5f, enc, bs, L, s);       // GPT2Model.ln_f
     launch_ln_channels(enc, nullptr, bs, L, d_lt, L, B, C, fin_g_, fin_b_, 1e-5f, emb, bs, L, s);       // final_norm (:403)
+    f.enc = emb;
+    f.L = L;
+    return f;
+}
+
+// UnifiedVoice.forward(..., return_latent=True) as called at vqvae/model_24k.py:796-799.
+// codes [B][n_max] host, n[b] valid -> latents_cm [B, C, lat_stride] (columns 0..n[b]-1)
+void Model::gpt_latents(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host,
+                        int Lt_max, const int* codes_host, const int* ncodes_host, int n_max, int B, float* latents_cm, int lat_stride,
+                        hipStream_t s) {
+    const int C = cfg.gpt_dim;
+    const GptForced f = gpt_teacher_forced(refer, refer_lens_host, Tr, text_host, text_lens_host, Lt_max, codes_host, ncodes_host, n_max, B, 0, s);
+    std::vector<int> c0(B), nn(B);
+    for (int b = 0; b < B; ++b) {
+        c0[b] = 1 + f.tl[b];                                // column of the start_mel input
+        nn[b] = f.ml[b] - 2;
+    }
+    const int* d_c0 = upload_ints(c0.data(), B, s);
+    const int* d_nn = upload_ints(nn.data(), B, s);
     // enc[:, -(n+2):][:, :-2]  (:406, :481)
-    hipLaunchKernelGGL(copy_columns_kernel, dim3(cdiv(n_max, 128) > 0 ? cdiv(n_max, 128) : 1, C, B), dim3(128), 0, s, emb, bs, L, d_c0,
-                       d_nn, C, latents_cm, (long long)C * lat_stride, lat_stride);
+    hipLaunchKernelGGL(copy_columns_kernel, dim3(cdiv(n_max, 128) > 0 ? cdiv(n_max, 128) : 1, C, B), dim3(128), 0, s, f.enc, (long long)C * f.L,
+                       f.L, d_c0, d_nn, C, latents_cm, (long long)C * lat_stride, lat_stride);
     DTTS_CHECK_HIP(hipGetLastError());
+}
+
+// `head` (mel_head / text_head as bound) fused with log-softmax + gather over the columns of lat (gpt_score.hip).  Rows run in groups of
+// 16 (one targets table per group); everything is enqueued on s, nothing is allocated unless a call asks for more partials than the
+// workspace sized at bind time holds.
+void Model::score_head(const PackedConv& head, const float* lat, long long lat_bs, int lat_cs, const int* targets_host, const int* ntargets_host,
+                       int n_max, int B, float* logprob_out, float* logits_out, hipStream_t s) {
+    const int V = head.Cout;
+    for (int g0 = 0; g0 < B; g0 += GEMV_MAXB) {
+        const int nb = std::min(GEMV_MAXB, B - g0);
+        std::vector<int> tg((size_t)nb * n_max, 0), tiles;
+        for (int b = 0; b < nb; ++b) {
+            const int nt = ntargets_host[g0 + b];
+            std::copy(targets_host + (size_t)(g0 + b) * n_max, targets_host + (size_t)(g0 + b) * n_max + nt, tg.begin() + (size_t)b * n_max);
+            for (int n0 = 0; n0 < nt; n0 += 128) { tiles.push_back(b); tiles.push_back(n0); }
+        }
+        const size_t need = sizeof(float) * gpt_score_part_floats(nb, n_max, head.CoutP) + 4096;
+        if (need > gpt_score_ws_.capacity()) gpt_score_ws_.ensure(need);
+        gpt_score_ws_.reset();
+        ScoreParams p;
+        p.lat = lat + (size_t)g0 * lat_bs;
+        p.lat_bs = lat_bs;
+        p.lat_cs = lat_cs;
+        p.w = head.w;
+        p.bias = head.b;
+        p.C = head.Cin; p.CinP = head.CinP; p.V = V; p.CoutP = head.CoutP;
+        p.targets = upload_ints(tg.data(), (int)tg.size(), s);
+        p.ntargets = upload_ints(ntargets_host + g0, nb, s);
+        p.tiles = upload_ints(tiles.data(), (int)tiles.size(), s);
+        p.B = nb; p.n_max = n_max;
+        p.part = gpt_score_ws_.f32(gpt_score_part_floats(nb, n_max, head.CoutP));
+        p.out = logprob_out + (size_t)g0 * n_max;
+        p.logits_out = logits_out ? logits_out + (size_t)g0 * V * n_max : nullptr;
+        launch_gpt_score(p, (int)tiles.size() / 2, s);
+    }
 }
 
 // gpt/model.py:408-415 (mel_head on final_norm's output) + log_softmax + gather, on latents the decode / the teacher-forced pass left:
 // column k of latents_cm is the hidden state token k was drawn from, so logprob[b][k] = log p(targets[b][k]) under the UNPROCESSED
-// distribution.  Rows run in groups of 16 (one targets table per group); everything is enqueued on s, nothing is allocated unless a
-// call asks for more columns than the model has mel positions.
+// distribution.
 void Model::gpt_score(const float* latents_cm, int lat_stride, const int* targets_host, const int* ntargets_host, int n_max, int B,
                       float* logprob_out, float* logits_out, hipStream_t s) {
     DTTS_REQUIRE(bound_ && has_gpt_, "gpt weights not bound");
@@ -832,33 +888,38 @@ void Model::gpt_score(const float* latents_cm, int lat_stride, const int* target
             DTTS_REQUIRE(t >= 0 && t < V, "gpt_score: target outside the mel_head's rows");
         }
     }
-    for (int g0 = 0; g0 < B; g0 += GEMV_MAXB) {
-        const int nb = std::min(GEMV_MAXB, B - g0);
-        std::vector<int> tg((size_t)nb * n_max, 0), tiles;
-        for (int b = 0; b < nb; ++b) {
-            const int nt = ntargets_host[g0 + b];
-            std::copy(targets_host + (size_t)(g0 + b) * n_max, targets_host + (size_t)(g0 + b) * n_max + nt, tg.begin() + (size_t)b * n_max);
-            for (int n0 = 0; n0 < nt; n0 += 128) { tiles.push_back(b); tiles.push_back(n0); }
-        }
-        const size_t need = sizeof(float) * gpt_score_part_floats(nb, n_max, mel_head_.CoutP) + 4096;
-        if (need > gpt_score_ws_.capacity()) gpt_score_ws_.ensure(need);
-        gpt_score_ws_.reset();
-        ScoreParams p;
-        p.lat = latents_cm + (size_t)g0 * C * lat_stride;
-        p.lat_bs = (long long)C * lat_stride;
-        p.lat_cs = lat_stride;
-        p.w = mel_head_.w;
-        p.bias = mel_head_.b;
-        p.C = C; p.CinP = mel_head_.CinP; p.V = V; p.CoutP = mel_head_.CoutP;
-        p.targets = upload_ints(tg.data(), (int)tg.size(), s);
-        p.ntargets = upload_ints(ntargets_host + g0, nb, s);
-        p.tiles = upload_ints(tiles.data(), (int)tiles.size(), s);
-        p.B = nb; p.n_max = n_max;
-        p.part = gpt_score_ws_.f32(gpt_score_part_floats(nb, n_max, mel_head_.CoutP));
-        p.out = logprob_out + (size_t)g0 * n_max;
-        p.logits_out = logits_out ? logits_out + (size_t)g0 * V * n_max : nullptr;
-        launch_gpt_score(p, (int)tiles.size() / 2, s);
+    score_head(mel_head_, latents_cm, (long long)C * lat_stride, lat_stride, targets_host, ntargets_host, n_max, B, logprob_out, logits_out, s);
+}
+
+// UnifiedVoice.forward's loss mode (gpt/model.py:429-491).  The reference has no attention mask and takes both cross-entropies as plain
+// means over every position, so a batch is a rectangle: every row has the full Lt text ids and n mel codes (clip_inputs and
+// set_mel_padding are host preprocessing of the caller, detail_tts_amd/gpt/model.py).  Inputs [cond | 255, text, 0 | 8192, codes, 8193];
+// targets (build_aligned_inputs_and_targets, :372-375) [text, 0, 0] and [codes, 8193, 8193]; text logits from columns 1 .. Lt + 2 of
+// final_norm's output, mel logits from its last n + 2 columns (:402-415) - both heads read the teacher-forced pass's own buffer.
+void Model::gpt_forward_losses(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, int Lt, const int* codes_host, int n,
+                               int B, float* losses_out, float* text_logprob, float* mel_logprob, float* mel_logits, hipStream_t s) {
+    DTTS_REQUIRE(bound_ && has_gpt_, "gpt weights not bound");
+    DTTS_REQUIRE(has_text_head_, "gpt_forward_losses: gpt.text_head.weight is not bound (the checkpoint carries no text_head)");
+    DTTS_REQUIRE(B >= 1 && Lt >= 0 && n >= 0, "gpt_forward_losses: B, Lt, n");
+    DTTS_REQUIRE(refer && losses_out && text_host && codes_host, "gpt_forward_losses: null argument");
+    DTTS_REQUIRE(Lt + 2 <= 4096 && n + 2 <= 4096, "gpt_forward_losses: at most 4096 positions per span (gpt_score's limit)");
+    DTTS_REQUIRE(text_head_.Cout == cfg.gpt_text_tokens && text_head_.Cout > text_head_.CoutP - 128, "gpt_forward_losses: packed text_head shape");
+    const int C = cfg.gpt_dim, nt = Lt + 2, nm = n + 2;
+    const size_t lp_floats = (size_t)B * nt + (size_t)B * nm;
+    // ids and codes are range-checked in here, before any launch
+    const GptForced f = gpt_teacher_forced(refer, refer_lens_host, Tr, text_host, nullptr, Lt, codes_host, nullptr, n, B,
+                                           sizeof(float) * lp_floats + 4 * 256, s);
+    if (!text_logprob) text_logprob = ws().f32((size_t)B * nt);
+    if (!mel_logprob) mel_logprob = ws().f32((size_t)B * nm);
+    std::vector<int> tt((size_t)B * nt, 0), tm((size_t)B * nm, 8193), ntt(B, nt), ntm(B, nm);
+    for (int b = 0; b < B; ++b) {
+        std::copy(text_host + (size_t)b * Lt, text_host + (size_t)(b + 1) * Lt, tt.begin() + (size_t)b * nt);
+        std::copy(codes_host + (size_t)b * n, codes_host + (size_t)(b + 1) * n, tm.begin() + (size_t)b * nm);
     }
+    const long long bs = (long long)C * f.L;
+    score_head(text_head_, f.enc + 1, bs, f.L, tt.data(), ntt.data(), nt, B, text_logprob, nullptr, s);
+    score_head(mel_head_, f.enc + (f.L - nm), bs, f.L, tm.data(), ntm.data(), nm, B, mel_logprob, mel_logits, s);
+    launch_gpt_loss_means(text_logprob, B * nt, mel_logprob, B * nm, losses_out, s);
 }
 
 }  // namespace dtts

@@ -5,6 +5,30 @@ import numpy as np
 import torch
 
 
+def _host_ints(x):
+    return None if x is None else torch.as_tensor(x).detach().cpu().numpy().astype(np.int64)
+
+
+def forward_inputs(text_inputs, text_lengths, mel_codes, wav_lengths, mel_length_compression=1024, stop_mel_token=8193, clip_inputs=False):
+    """Host preprocessing of UnifiedVoice.forward's loss mode, in the reference's order (gpt/model.py:453-462): clip_inputs slices the
+    text to text_lengths.max() columns and the codes to wav_lengths.max() // mel_length_compression; set_mel_padding (:377-390) then
+    rewrites row b's codes from column wav_lengths[b] // mel_length_compression + 1 on with the stop token.  Integer arrays in,
+    (text [B, Lt], codes [B, n]) int32 copies out; the inputs are left alone (the reference pads mel_codes in place)."""
+    text = np.array(text_inputs, np.int64, ndmin=2)
+    codes = np.array(mel_codes, np.int64, ndmin=2)
+    wl = np.asarray(wav_lengths, np.int64).reshape(-1)
+    if text.shape[0] != codes.shape[0] or wl.shape[0] != codes.shape[0]:
+        raise ValueError(f"forward: text {text.shape}, mel_codes {codes.shape} and wav_lengths {wl.shape} disagree on the batch size")
+    if clip_inputs:
+        text = text[:, : int(np.asarray(text_lengths, np.int64).max())]
+        codes = codes[:, : int(wl.max()) // mel_length_compression]
+    for b in range(codes.shape[0]):
+        end = int(wl[b]) // mel_length_compression + 1
+        if end < codes.shape[1]:
+            codes[b, end:] = stop_mel_token
+    return np.ascontiguousarray(text, np.int32), np.ascontiguousarray(codes, np.int32)
+
+
 class UnifiedVoice:
     def __init__(self, rt, cfg):
         self.rt = rt
@@ -94,10 +118,27 @@ class UnifiedVoice:
         return torch.from_numpy(codes[:, :n].astype(np.int64)).to(refer.device)
 
     def forward(self, speech_conditioning_latent, cond_lengths, text_inputs, text_lengths, mel_codes, wav_lengths, types=None,
-                text_first=True, raw_mels=None, return_attentions=False, return_latent=False, clip_inputs=False):
-        """gpt/model.py:429-491, return_latent=True only (the inference use, vqvae/model_24k.py:796-799) -> [B, n, 768]"""
-        if not return_latent or types is not None or raw_mels is not None or not text_first:
-            raise NotImplementedError("only forward(..., return_latent=True) is on the inference path")
+                text_first=True, raw_mels=None, return_attentions=False, return_latent=False, clip_inputs=False, *, return_logits=True):
+        """gpt/model.py:429-491.
+
+        return_latent=True (the inference use, vqvae/model_24k.py:796-799) -> latents [B, n, 768]; rows are ragged there (text_lengths
+        and wav_lengths give every row its own length).
+
+        Otherwise the reference's loss mode -> (loss_text, loss_mel, mel_logits): two 0-d fp32 CUDA tensors and [B, 8194, n + 2]
+        (None with return_logits=False: no logits are materialised).  The batch is the reference's RECTANGLE: its forward has no
+        attention mask and takes both cross-entropies as plain means over all B (Lt + 2) / B (n + 2) positions, so every row counts with
+        the full text_inputs.shape[1] and mel_codes.shape[1]; text_lengths matters only under clip_inputs, wav_lengths only through
+        clip_inputs and set_mel_padding (forward_inputs).  Needs gpt.text_head in the checkpoint (dtts_gpt_forward_losses)."""
+        if types is not None or raw_mels is not None or not text_first or (return_attentions and not return_latent):
+            raise NotImplementedError("UnifiedVoice.forward: types, raw_mels, text_first=False and return_attentions=True are not implemented "
+                                      "on the device")
+        if not return_latent:
+            refer = speech_conditioning_latent.float().contiguous()
+            cl = None if cond_lengths is None else torch.as_tensor(cond_lengths).reshape(-1).tolist()
+            text, codes = forward_inputs(_host_ints(text_inputs), _host_ints(text_lengths), _host_ints(mel_codes), _host_ints(wav_lengths),
+                                         self.mel_length_compression, self.stop_mel_token, clip_inputs)
+            losses, logits = self.rt.gpt_forward_losses(refer, cl, text, codes, want_logits=bool(return_logits))
+            return losses[0], losses[1], logits
         refer = speech_conditioning_latent.float().contiguous()
         cl = None if cond_lengths is None else torch.as_tensor(cond_lengths).reshape(-1).tolist()
         codes = torch.as_tensor(mel_codes).cpu().numpy().astype(np.int32)

@@ -260,6 +260,8 @@ def pack_gpt(pk, P, cfg):
         pk.add(n + ".weight", P[n + ".weight"])
         pk.add(n + ".bias", P[n + ".bias"])
     pk.conv("gpt.mel_head", P["gpt.mel_head.weight"], P["gpt.mel_head.bias"])
+    if "gpt.text_head.weight" in P:         # optional (weights.optional_param_spec): 257 rows zero-padded to CoutP = 384, like mel_head
+        pk.conv("gpt.text_head", P["gpt.text_head.weight"], P["gpt.text_head.bias"])
     for n in ("gpt.text_embedding.weight", "gpt.mel_embedding.weight", "gpt.text_pos_embedding.emb.weight",
               "gpt.mel_pos_embedding.emb.weight"):
         pk.add(n, P[n])

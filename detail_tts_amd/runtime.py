@@ -293,6 +293,27 @@ class Runtime:
                                          nmax, B, _ptr(out), _ptr(logits), self._stream()))
         return (out, logits) if want_logits else out
 
+    def gpt_forward_losses(self, refer, refer_lens, text, codes, want_logits=True, want_logprobs=False):
+        """UnifiedVoice.forward's loss mode on a rectangular batch (dtts_gpt_forward_losses): refer cuda [B,128,Tr], text int [B,Lt] and
+        codes int [B,n] host arrays as they stand after clip_inputs / set_mel_padding -> (losses cuda fp32 [2] = (loss_text, loss_mel),
+        mel_logits cuda [B, V, n+2] or None[, text_logprob cuda [B, Lt+2], mel_logprob cuda [B, n+2] with want_logprobs]).  Asynchronous."""
+        _check(refer, "refer")
+        B, _, Tr = refer.shape
+        text = np.ascontiguousarray(np.asarray(text, np.int32))
+        codes = np.ascontiguousarray(np.asarray(codes, np.int32))
+        if text.ndim != 2 or codes.ndim != 2 or text.shape[0] != B or codes.shape[0] != B:
+            raise DttsError(f"gpt_forward_losses: text {text.shape} / codes {codes.shape} are not [B, Lt] / [B, n] with B = {B}")
+        Lt, n = text.shape[1], codes.shape[1]
+        rl = _ints(refer_lens if refer_lens is not None else [Tr] * B)
+        losses = torch.zeros((2,), device=self.device, dtype=torch.float32)
+        logits = torch.zeros((B, self.cfg["gpt"]["number_mel_codes"], n + 2), device=self.device, dtype=torch.float32) if want_logits else None
+        tlp = torch.zeros((B, Lt + 2), device=self.device, dtype=torch.float32) if want_logprobs else None
+        mlp = torch.zeros((B, n + 2), device=self.device, dtype=torch.float32) if want_logprobs else None
+        self._rc(self.lib.dtts_gpt_forward_losses(self.h, _ptr(refer), rl[0], Tr, text.ctypes.data_as(_lib.c_int_p), Lt,
+                                                  codes.ctypes.data_as(_lib.c_int_p), n, B, _ptr(losses), _ptr(tlp), _ptr(mlp), _ptr(logits),
+                                                  self._stream()))
+        return (losses, logits, tlp, mlp) if want_logprobs else (losses, logits)
+
     # ------------------------------------------------------------------ stage B
     def diff_conditioning(self, refer, lens=None):
         _check(refer, "refer")

@@ -147,6 +147,8 @@ class SynthesizerTrn:
         self.gpt = UnifiedVoice(self.rt, self.cfg["gpt"])
         self.diffusion = DiffusionTts(self.rt, self.cfg["diffusion"])
         self.dec = Generator(self.rt)
+        self.text_loss_weight = self.cfg["train"]["text_weight"]      # vqvae/model_24k.py:603-604
+        self.mel_loss_weight = self.cfg["train"]["mel_weight"]
         self.infer_diffuser = SpacedDiffusion(space_timesteps(TRAINED_DIFFUSION_STEPS, [INFER_DIFFUSION_STEPS]),
                                               betas=get_named_beta_schedule("linear", TRAINED_DIFFUSION_STEPS),
                                               conditioning_free=True, conditioning_free_k=COND_FREE_K, sampler="dpm++2m")
@@ -664,6 +666,17 @@ class SynthesizerTrn:
         lens = None if y_lengths is None else [int(v) for v in torch.as_tensor(y_lengths).reshape(-1).tolist()]
         codes, xvq = self.rt.vq_encode(y, lens)
         return codes.long(), xvq
+
+    def forward_gpt(self, y, y_lengths, data):
+        """vqvae/model_24k.py:697-704, the GPT stage's validation loss: codes of data['raw_mel'] (encode), then UnifiedVoice.forward's
+        loss mode on (data['mel'], data['spec_length'], data['text'], data['text_length'], codes, data['raw_wav_length']) ->
+        loss_text * train.text_weight + loss_mel * train.mel_weight, a 0-d fp32 CUDA tensor.  No mel logits are materialised.
+        Needs gpt.text_head in the checkpoint.  y / y_lengths are unused, as in the reference."""
+        code, _ = self.encode(data["raw_mel"], data["raw_spec_length"])
+        mel = torch.as_tensor(data["mel"]).to(self.device, torch.float32).contiguous()
+        loss_text, loss_mel, _ = self.gpt(mel, data["spec_length"], data["text"], data["text_length"], code, data["raw_wav_length"],
+                                          return_logits=False)
+        return loss_text * self.text_loss_weight + loss_mel * self.mel_loss_weight
 
     def infer_vqvae(self, y, noise_scale=NOISE_SCALE, *, seed=0, sample_ids=None):
         """vqvae/model_24k.py:864-876: mel -> codes -> quantised latent + vq_ref_enc -> vq_dec -> (recon, wav); first row only"""

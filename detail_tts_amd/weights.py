@@ -6,9 +6,11 @@ constructors: vqvae/model_24k.py:515-650, gpt/model.py:265-331,
 vqvae/diff_model.py:133-209, vqvae/modules/modules.py:152-229/240-313/421-455/
 642-695, vqvae/modules/attentions.py:73-94/161-195/317-336).  A real checkpoint
 (`ckpt['G']`, prepare/load_infer.py:21-26) is accepted as-is: unneeded keys
-(`enc_q.*`, `quantizer.*`, `vq_*`, `gpt.text_head.*`, the `gpt.inference_model.*`
-aliases ...) are ignored, and old-style weight-norm pairs
-(`weight_g`/`weight_v`) are folded to a plain `weight`.
+(`enc_q.*`, `quantizer.*`, `vq_*`, the `gpt.inference_model.*` aliases ...) are
+ignored, and old-style weight-norm pairs (`weight_g`/`weight_v`) are folded to a
+plain `weight`.  `gpt.text_head.*` is OPTIONAL (`optional_param_spec`): no
+inference entry reads it, `UnifiedVoice.forward`'s loss mode does, so it is kept
+when the checkpoint carries it and never asked for.
 
 Nothing here touches the GPU; it is host-side numpy.
 """
@@ -251,12 +253,27 @@ def inference_param_spec(cfg=None) -> "OrderedDict[str, tuple]":
     return spec
 
 
+def optional_param_spec(cfg=None) -> "OrderedDict[str, tuple]":
+    """name -> (shape, kind) of the tensors that are bound WHEN PRESENT and never required: gpt.text_head (gpt/model.py:318,
+    nn.Linear(model_dim, number_text_tokens * types + 1)), read only by UnifiedVoice.forward's loss mode (gpt/model.py:479-491)."""
+    cfg = load_config(cfg)
+    g = cfg["gpt"]
+    rows = g["number_text_tokens"] * g.get("types", 1) + 1
+    spec: "OrderedDict[str, tuple]" = OrderedDict()
+    spec["gpt.text_head.weight"] = ((rows, g["model_dim"]), K_W)
+    spec["gpt.text_head.bias"] = ((rows,), K_B)
+    return spec
+
+
 def _rng_for(seed: int, name: str) -> np.random.Generator:
     return np.random.Generator(np.random.Philox(key=[int(seed) & 0xFFFFFFFFFFFFFFFF, zlib.crc32(name.encode())]))
 
 
-def synthetic_state_dict(seed: int = 0, cfg=None, only_prefixes=None, variant=None) -> "OrderedDict[str, np.ndarray]":
+def synthetic_state_dict(seed: int = 0, cfg=None, only_prefixes=None, variant=None, optional=False) -> "OrderedDict[str, np.ndarray]":
     """Deterministic random-init weights in *state-dict form* (fp32 numpy).
+
+    ``optional=True`` appends the tensors of ``optional_param_spec`` (gpt.text_head); every tensor has its own stream, so the others
+    keep their values.
 
     ``variant="signal"``: the same draws, rescaled so that the vocoder's output DEPENDS ON ITS INPUT.  With the plain fan-in
     init every generator conv attenuates its input by ~0.58 (uniform +-1/sqrt(fan_in) has std 1/sqrt(3 fan_in)) while every bias
@@ -273,6 +290,8 @@ def synthetic_state_dict(seed: int = 0, cfg=None, only_prefixes=None, variant=No
     gate is exercised.  Scales are fan-in based so activations stay O(1).
     """
     spec = inference_param_spec(cfg)
+    if optional:
+        spec.update(optional_param_spec(cfg))
     out: "OrderedDict[str, np.ndarray]" = OrderedDict()
     for name, (shape, kind) in spec.items():
         if only_prefixes is not None and not name.startswith(tuple(only_prefixes)):
@@ -388,7 +407,8 @@ def folded_param_names(cfg=None):
 
 
 def select_inference_params(state: dict, cfg=None) -> "OrderedDict[str, np.ndarray]":
-    """Fold + keep exactly the tensors the hot path needs; raise on missing/mis-shaped."""
+    """Fold + keep exactly the tensors the hot path needs; raise on missing/mis-shaped.  The tensors of optional_param_spec
+    (gpt.text_head) pass through when the checkpoint has them all (mis-shaped ones raise); their absence is never an error."""
     folded = fold_weight_norm({k: v for k, v in state.items() if not k.startswith("gpt.inference_model.")})
     spec = inference_param_spec(cfg)
     out: "OrderedDict[str, np.ndarray]" = OrderedDict()
@@ -404,4 +424,11 @@ def select_inference_params(state: dict, cfg=None) -> "OrderedDict[str, np.ndarr
         if tuple(a.shape) != tuple(shape):
             raise ValueError(f"'{k}': expected shape {tuple(shape)}, got {tuple(a.shape)}")
         out[k] = a
+    opt = optional_param_spec(cfg)
+    if all(k in folded for k in opt):
+        for k, (shape, kind) in opt.items():
+            a = np.ascontiguousarray(_np(folded[k]), dtype=np.float32)
+            if tuple(a.shape) != tuple(shape):
+                raise ValueError(f"'{k}': expected shape {tuple(shape)}, got {tuple(a.shape)}")
+            out[k] = a
     return out

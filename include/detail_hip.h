@@ -7,7 +7,7 @@
  *   vqvae/model_24k.py:848    SynthesizerTrn.infer_flowvae
  *   vqvae/model_24k.py:479    do_spectrogram_diffusion
  *   gpt/model.py:514          UnifiedVoice.inference_speech_tortoise
- *   gpt/model.py:429          UnifiedVoice.forward(return_latent=True)
+ *   gpt/model.py:429          UnifiedVoice.forward (return_latent=True, and the loss mode: loss_text, loss_mel, mel_logits)
  *   vqvae/diff_model.py:221/231/262  DiffusionTts.get_conditioning / timestep_independent / forward
  *   vqvae/model_24k.py:269    Generator.forward
  * which detail_tts_amd/ mirrors.  This header is what that Python layer binds (ctypes); each entry point
@@ -176,6 +176,24 @@ int dtts_gpt_latents(dtts_handle* h, const float* refer, const int* refer_lens, 
  * per handle at a time. */
 int dtts_gpt_score(dtts_handle* h, const float* latents_cm, int lat_stride, const int* targets, const int* ntargets, int n_max,
                    int B, float* logprob_out, float* logits_out, void* stream);
+
+/* UnifiedVoice.forward in loss mode (gpt/model.py:429-491; the GPT stage's validation loss, vqvae/model_24k.py:697-704):
+ * (loss_text, loss_mel, mel_logits) of a RECTANGULAR teacher-forced batch.  The reference's forward has no attention mask and
+ * takes both cross-entropies as plain means over every position (no ignore_index), so every row has the full Lt text ids and
+ * n mel codes; clip_inputs and set_mel_padding are host preprocessing the caller applies first (UnifiedVoice.forward in
+ * detail_tts_amd/gpt/model.py does).  refer DEVICE [B,128,Tr], refer_lens HOST [B] or NULL; text_ids HOST [B][Lt] and
+ * mel_codes HOST [B][n], range-checked before any launch.  GPT input [cond | 255, text, 0 | 8192, codes, 8193]; targets
+ * [text, 0, 0] and [codes, 8193, 8193] (build_aligned_inputs_and_targets, :372-375).
+ * Outputs (DEVICE): losses_out [2] = (loss_text, loss_mel), -mean of the log-probabilities over all B (Lt + 2) and all
+ * B (n + 2) positions; text_logprob [B][Lt + 2], mel_logprob [B][n + 2] (log_softmax of the head's logits at the targets)
+ * and mel_logits [B][8194][n + 2], each optional (NULL: not written; without mel_logits no [B,V,n] buffer exists anywhere).
+ * One teacher-forced pass (shared with dtts_gpt_latents), the fused head kernel of dtts_gpt_score once per head (text_head,
+ * V = 257; mel_head, V = 8194) and a fixed-order reduction: no atomics, two calls give the same bits, and a row's values do
+ * not depend on the rest of the batch.  Asynchronous on `stream` like dtts_gpt_latents.  Needs gpt.text_head.weight / .bias
+ * in the bound blob (optional tensors: the inference path never reads them) and fails naming gpt.text_head.weight otherwise. */
+int dtts_gpt_forward_losses(dtts_handle* h, const float* refer, const int* refer_lens, int Tr, const int* text_ids, int Lt,
+                            const int* mel_codes, int n, int B, float* losses_out, float* text_logprob, float* mel_logprob,
+                            float* mel_logits, void* stream);
 
 /* ---- stage B: diffusion mel decoder ---------------------------------------------------------- */
 
