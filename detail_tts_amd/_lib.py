@@ -97,6 +97,16 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p]),
     "dtts_diff_forward_tf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p,
                                        C.c_void_p]),
+    "dtts_diff_forward_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, c_int_p, C.c_void_p,
+                                         C.c_void_p]),
+    "dtts_diff_schedule_qtable": (C.c_int, [C.c_void_p, C.c_int, c_float_p, C.c_int, c_int_p]),
+    "dtts_diff_q_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, c_int_p, C.c_void_p, C.c_ulonglong, c_int_p, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dtts_diff_loss_terms": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dtts_diff_training_losses": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, c_int_p, C.c_void_p, C.c_ulonglong, c_int_p, C.c_void_p, c_int_p,
+                                            C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dtts_l1_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dtts_vocoder": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_ulonglong, c_int_p, C.c_float, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "dtts_vocoder_stream": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_ulonglong, c_int_p, C.c_float, C.c_void_p,

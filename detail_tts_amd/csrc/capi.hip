@@ -404,6 +404,48 @@ int dtts_diff_forward_tf(dtts_handle* h, const float* x, const float* code_emb, 
     DTTS_API_END(h)
 }
 
+int dtts_diff_forward_rows(dtts_handle* h, int id, const float* x, const float* code_emb, const int* lens, int B, int T, const int* steps,
+                           float* out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_forward_rows(id, x, code_emb, lens, B, T, steps, out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_diff_schedule_qtable(dtts_handle* h, int id, float* table, int cap, int* n_out) {
+    DTTS_API_BEGIN
+    const int n = h->m->diff_schedule_qtable(id, table, cap);
+    if (n_out) *n_out = n;
+    DTTS_API_END(h)
+}
+
+int dtts_diff_q_sample(dtts_handle* h, int id, const float* mel, int normalize, const int* t, const float* noise, unsigned long long seed,
+                       const int* sample_ids, int B, int T, float* x_start_out, float* x_t_out, float* noise_out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_q_sample(id, mel, normalize, t, noise, seed, sample_ids, B, T, x_start_out, x_t_out, noise_out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_diff_loss_terms(dtts_handle* h, int id, const float* model_out, const float* x_start, const float* x_t, const float* noise,
+                         const int* t, int B, int T, float* terms_out, float* pred_xstart, void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_loss_terms(id, model_out, x_start, x_t, noise, t, B, T, terms_out, pred_xstart, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_diff_training_losses(dtts_handle* h, int id, const float* x_start, const int* t, const float* noise, unsigned long long seed,
+                              const int* sample_ids, const float* code_emb, const int* lens, int B, int T, float* terms_out,
+                              float* pred_xstart, void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_training_losses(id, x_start, t, noise, seed, sample_ids, code_emb, lens, B, T, terms_out, pred_xstart, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_l1_mean(dtts_handle* h, const float* a, const float* b, int B, int C, int T, float* out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->l1_mean(a, b, B, C, T, out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
 int dtts_vocoder(dtts_handle* h, const float* mel, const int* lens, int B, int T, unsigned long long seed, const int* sample_ids,
                  float noise_scale, const float* noise_override, float* wav, float* trace_z, void* stream) {
     DTTS_API_BEGIN

@@ -52,6 +52,8 @@ void make_schedule(int trained, const std::vector<int>& tmap, float cfk_k, Sched
     sc.p.resize(n);
     sc.ac.resize(n);
     sc.ac_prev.resize(n);
+    sc.sqrt_ac.resize(n);
+    sc.sqrt_1m_ac.resize(n);
     for (int i = 0; i < n; ++i) {
         DiffStepCoefs k;
         k.sqrt_recip_ac = (float)std::sqrt(1.0 / acp[i]);
@@ -66,6 +68,8 @@ void make_schedule(int trained, const std::vector<int>& tmap, float cfk_k, Sched
         sc.p[i] = k;
         sc.ac[i] = (float)acp[i];
         sc.ac_prev[i] = (float)acp_prev[i];
+        sc.sqrt_ac[i] = (float)std::sqrt(acp[i]);
+        sc.sqrt_1m_ac[i] = (float)std::sqrt(1.0 - acp[i]);
     }
 }
 

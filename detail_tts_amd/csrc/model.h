@@ -18,6 +18,7 @@
 #include "common.h"
 #include "conv_gemm.h"
 #include "conv_x3.h"
+#include "diff_loss.h"
 #include "diff_schedule.h"
 #include "gpt_kernels.h"
 #include "ops.h"
@@ -181,6 +182,23 @@ public:
     // DiffusionTts.forward at a fp32 model time in [0, diff_trained_steps): integer values take diff_forward_t's route bit for bit
     void diff_forward_tf(const float* x, const float* code_emb, const int* lens_host, int B, int T, float timestep, int cond_free,
                          float* out, hipStream_t s);
+    // DiffusionTts.forward, conditional branch only, with every batch row at its own column of integer-timestep schedule `sched_id`:
+    // row b is evaluated at column step_of_row[b] (HOST, B) in the conditioning_timestep_integrator and in every ResBlock of the stack
+    // and tail.  A B-sample stack on the caller's stream (no unconditional rows), three-product trunk, GroupNorm as its own pass.
+    void diff_forward_rows(int sched_id, const float* x, const float* code_emb, const int* lens_host, int B, int T, const int* step_of_row,
+                           float* out, hipStream_t s);
+    // ---- evaluation losses (diff_loss.h; GaussianDiffusion.training_losses, vqvae/utils/diffusion.py:930-1012).  t_host [B]: columns of
+    // the integer-timestep schedule `sched_id`.  The losses are means over the whole [128, T] rectangle of every row (mean_flat).
+    void diff_q_sample(int sched_id, const float* mel, int normalize, const int* t_host, const float* noise, unsigned long long seed,
+                       const int* sample_ids_host, int B, int T, float* x_start_out, float* x_t_out, float* noise_out, hipStream_t s);
+    void diff_loss_terms(int sched_id, const float* model_out, const float* x_start, const float* x_t, const float* noise, const int* t_host,
+                         int B, int T, float* terms_out, float* pred_xstart, hipStream_t s);
+    void diff_training_losses(int sched_id, const float* x_start, const int* t_host, const float* noise, unsigned long long seed,
+                              const int* sample_ids_host, const float* code_emb, const int* lens_host, int B, int T, float* terms_out,
+                              float* pred_xstart, hipStream_t s);
+    void l1_mean(const float* a, const float* b, int B, int C, int T, float* out, hipStream_t s);
+    // host copy of a schedule's forward-process tables: out[i] = {sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod} of column i
+    int diff_schedule_qtable(int sched_id, float* out, int cap);
     // one p_sample at `step` on x in place (unit entry of the sampler parity tests)
     void diff_p_sample(float* x, const float* code_emb, const int* lens_host, int B, int T, int step, unsigned long long seed,
                        const int* sample_ids_host, const float* noise, float* x0_out, hipStream_t s);
@@ -405,6 +423,13 @@ private:
     PairCall begin_pair(const float* code_emb, const int* lens_host, const int* sample_ids_host, int B, int T, hipStream_t s,
                         size_t extra_bytes = 0, size_t hist_floats = 0);
     void ensure_fork_events();
+    // the per-row driver behind diff_forward_rows / diff_training_losses: carves rows_ws_bytes(B, C, T) of ws(), which the caller has sized
+    void diff_forward_rows_s(const Schedule& sc, const float* x, const float* code_emb, const int* lens_host, int B, int T, const int* step_of_row,
+                             float* out, hipStream_t s);
+    static size_t rows_ws_bytes(int B, int C, int T);
+    // the integer-timestep schedule `sched_id` with t_host [B] checked against its columns; the rows' coefficients on the device
+    const Schedule& loss_schedule(int sched_id, const int* t_host, int B, const char* who);
+    const DiffLossCoefs* upload_loss_coefs(const Schedule& sc, const int* t_host, int B, hipStream_t s);
 
     std::unordered_map<std::string, std::pair<const float*, size_t>> weights_;
     bool bound_ = false;

@@ -590,6 +590,106 @@ void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* c
     }
 }
 
+size_t Model::rows_ws_bytes(int B, int C, int T) {
+    const size_t act = (size_t)B * C * T;
+    // x path (2 act) + integrator output (act) + one block's scratch (3 act + qkv + coefficients); planes: x path, code path, blocks
+    return sizeof(float) * (6 * act + qkv_floats(B, C, T) + (size_t)2 * B * C) + 3 * x3_bytes(B, C, T) + 32 * 256;
+}
+
+// DiffusionTts.forward (vqvae/diff_model.py:262-322), conditional branch only, every row at its own column of sc: the launch sequence of
+// one chunk of diff_forward_pair on the B conditional samples, on s alone, with TrunkIo::step_idx set in the integrator, the stack and
+// the tail.  GroupNorm runs as its own pass (the fused epilogue route has never carried a per-row index and is not taken here).
+void Model::diff_forward_rows_s(const Schedule& sc, const float* x, const float* code_emb, const int* lens_host, int B, int T,
+                                const int* step_of_row, float* out, hipStream_t s) {
+    const int C = cfg.diff_channels, Ta = T, OC = cfg.diff_out_channels;
+    const long long bs = (long long)C * Ta;
+    const size_t act = (size_t)B * C * Ta;
+    const bool x3 = use_x3();
+    std::vector<int> l(B);
+    for (int b = 0; b < B; ++b) l[b] = lens_host ? lens_host[b] : T;
+    const int* lens = upload_ints(l.data(), B, s);
+    const int* steps = upload_ints(step_of_row, B, s);
+    register_cols(lens, l.data(), B, T, s);
+    float* xin = ws().f32(act);
+    float* xpath = ws().f32(act);
+    float* bufI = ws().f32(act);
+    float* bufA = ws().f32(act);
+    float* bufB = ws().f32(act);
+    float* bufC = ws().f32(act);
+    float* qkv = ws().f32(qkv_floats(B, C, T));
+    TrunkIo io{lens, B, T, Ta, s, ws().f32((size_t)B * C * 2)};
+    void* xs0 = x3 ? ws().raw(x3_bytes(B, C, T)) : nullptr;
+    void* xs_code = x3 ? ws().raw(x3_bytes(B, C, T)) : nullptr;
+    io.xs = x3 ? ws().raw(x3_bytes(B, C, T)) : nullptr;
+    io.step_idx = steps;
+    // x path: inp_block + the x-half of integrating_conv (+ bias)  (:296-298)
+    {
+        ConvParams p = cp(x, cfg.mel_channels, T, T, lens, xin, C, T, Ta, lens, B);
+        p.pad = 1;
+        ConvParams q = cp(xin, C, xpath, C, B, T, Ta, lens);
+        if (x3) {
+            launch_split_planes(x, p.x_bs, T, nullptr, ACT_NONE, lens, T, B, cfg.mel_channels, xs0, s);
+            with_planes(p, xs0, T);
+            run_conv(inp_block_, p, s);
+            launch_split_planes(xin, bs, Ta, nullptr, ACT_NONE, lens, T, B, C, xs0, s);
+            with_planes(q, xs0, T);
+            run_conv(integ1_, q, s);
+        } else {
+            run_conv(inp_block_, p, s);
+            run_conv(integ1_, q, s);
+        }
+    }
+    // conditioning_timestep_integrator (:295) on the B code embeddings
+    const float* in = code_emb;
+    for (int li = 0; li < 3; ++li) {
+        res_block_fwd(sc, integ_[li].rb, in, bufA, bufB, 0, io);
+        attention_block(integ_[li].at, bufB, bufI, qkv, bufA, io);
+        in = bufI;
+    }
+    // integrating_conv, code half, accumulated onto the x-path term
+    ConvParams r = cp(bufI, C, bufB, C, B, T, Ta, lens);
+    with_res(r, xpath, bs, Ta);
+    if (x3) {
+        launch_split_planes(bufI, bs, Ta, nullptr, ACT_NONE, lens, T, B, C, xs_code, s);
+        with_planes(r, xs_code, T);
+    }
+    run_conv(integ2_, r, s);
+    // main stack and tail (:299-309), three products throughout
+    float* cur = bufB;
+    float* t1 = bufA;
+    float* t2 = bufC;
+    for (const auto& lyr : layers_) {
+        res_block_fwd(sc, lyr.rb, cur, t1, t2, 0, io);
+        attention_block(lyr.at, t2, cur, qkv, t1, io);
+    }
+    for (const auto& rb : tail_) {
+        res_block_fwd(sc, rb, cur, t1, t2, 0, io);
+        std::swap(cur, t2);
+    }
+    // out: GN, SiLU, conv k3 (:312)
+    norm_input(cur, C, out_gn_g_, out_gn_b_, ACT_SILU, x3, io);
+    ConvParams o = cp(cur, C, T, Ta, lens, out, OC, T, T, lens, B);
+    o.pro_ab = io.ab;
+    o.pro_act = ACT_SILU;
+    o.pad = 1;
+    if (x3) with_planes(o, io.xs, T);
+    run_conv(out_conv_, o, s);
+    if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
+}
+
+void Model::diff_forward_rows(int sched_id, const float* x, const float* code_emb, const int* lens_host, int B, int T, const int* step_of_row,
+                              float* out, hipStream_t s) {
+    gn_check();
+    DTTS_REQUIRE(bound_, "weights not bound");
+    DTTS_REQUIRE(x && code_emb && step_of_row && out && B >= 1 && T >= 1, "diff_forward_rows: x, code_emb, steps, out");
+    DTTS_REQUIRE(!opt_trunk_fp16_, "diff_forward_rows runs the three-product trunk only: set trunk_fp16 = 0 for this call");
+    const Schedule& sc = schedule(sched_id);
+    DTTS_REQUIRE(sc.kind == 0, "diff_forward_rows runs on an integer-timestep schedule (dtts_diff_schedule)");
+    for (int b = 0; b < B; ++b) DTTS_REQUIRE(step_of_row[b] >= 0 && step_of_row[b] < sc.n, "diff_forward_rows: a row's column is outside the schedule");
+    ws().ensure(rows_ws_bytes(B, cfg.diff_channels, T) + 8192);
+    diff_forward_rows_s(sc, x, code_emb, lens_host, B, T, step_of_row, out, s);
+}
+
 static size_t integ_ws_bytes(int Bv, int C, int T) {
     const size_t act = (size_t)Bv * C * T;
     return sizeof(float) * (act + 2 * (3 * act + qkv_floats(Bv, C, T) + (size_t)2 * Bv * C)) + 2 * x3_bytes(Bv, C, T) + 32 * 256;

@@ -452,6 +452,90 @@ class Runtime:
                                                1 if cond_free else 0, _ptr(out), self._stream()))
         return out
 
+    def diff_forward_rows(self, x, steps, code_emb, sched=0, lens=None):
+        """DiffusionTts.forward, conditional branch only, row b at column steps[b] of integer-timestep schedule `sched`
+        (dtts_diff_forward_rows) -> [B, 256, T]"""
+        _check(x, "x"); _check(code_emb, "code_emb")
+        if code_emb is None:
+            raise DttsError("diff_forward_rows: code_emb is required (only the conditional branch is evaluated)")
+        B, _, T = x.shape
+        st = _ints(steps)
+        if len(st[1]) != B:
+            raise DttsError(f"diff_forward_rows: {len(st[1])} steps for {B} rows")
+        out = torch.zeros((B, self.cfg["diffusion"]["out_channels"], T), device=self.device, dtype=torch.float32)
+        li = _ints(lens)
+        self._rc(self.lib.dtts_diff_forward_rows(self.h, int(sched), _ptr(x), _ptr(code_emb), li[0] if li else None, B, T, st[0], _ptr(out),
+                                                 self._stream()))
+        return out
+
+    def diff_schedule_qtable(self, sched):
+        """host copy of a schedule's forward-process tables: fp32 [n, 2] = (sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod)"""
+        n = C.c_int(0)
+        self._rc(self.lib.dtts_diff_schedule_qtable(self.h, int(sched), None, 0, C.byref(n)))
+        tab = np.zeros((n.value, 2), np.float32)
+        self._rc(self.lib.dtts_diff_schedule_qtable(self.h, int(sched), tab.ctypes.data_as(_lib.c_float_p), n.value, C.byref(n)))
+        return tab
+
+    def _loss_t(self, t, B, who):
+        ti = _ints(t)
+        if len(ti[1]) != B:
+            raise DttsError(f"{who}: {len(ti[1])} timesteps for {B} rows")
+        return ti
+
+    def diff_q_sample(self, sched, mel, t, noise=None, seed=0, sample_ids=None, normalize=False):
+        """GaussianDiffusion.q_sample on schedule `sched` (dtts_diff_q_sample): mel [B,128,T] (raw log-mel with normalize=True, else
+        x_start), t [B] columns of the schedule -> (x_start, x_t, noise); noise None: drawn on Philox stage 5 from (seed, sample_ids)"""
+        _check(mel, "mel"); _check(noise, "noise")
+        B, _, T = mel.shape
+        ti = self._loss_t(t, B, "diff_q_sample")
+        si = _ints(list(range(B)) if sample_ids is None else sample_ids)
+        x_start = torch.empty_like(mel) if normalize else mel
+        x_t = torch.empty_like(mel)
+        drawn = torch.empty_like(mel) if noise is None else None
+        self._rc(self.lib.dtts_diff_q_sample(self.h, int(sched), _ptr(mel), 1 if normalize else 0, ti[0], _ptr(noise), int(seed), si[0], B, T,
+                                             _ptr(x_start) if normalize else None, _ptr(x_t), _ptr(drawn), self._stream()))
+        return x_start, x_t, (noise if noise is not None else drawn)
+
+    def diff_loss_terms(self, sched, model_out, x_start, x_t, noise, t, want_pred=False):
+        """the loss arithmetic of training_losses on a given model output (dtts_diff_loss_terms) -> terms cuda fp32 [B, 3] =
+        (mse, vb, loss) per row [, pred_xstart [B,128,T] with want_pred]"""
+        for a, nm in ((model_out, "model_out"), (x_start, "x_start"), (x_t, "x_t"), (noise, "noise")):
+            _check(a, nm)
+        B, _, T = x_start.shape
+        if tuple(model_out.shape) != (B, 2 * x_start.shape[1], T) or x_t.shape != x_start.shape or noise.shape != x_start.shape:
+            raise DttsError("diff_loss_terms: model_out [B,256,T] and x_start / x_t / noise [B,128,T]")
+        ti = self._loss_t(t, B, "diff_loss_terms")
+        terms = torch.zeros((B, 3), device=self.device, dtype=torch.float32)
+        pred = torch.empty_like(x_start) if want_pred else None
+        self._rc(self.lib.dtts_diff_loss_terms(self.h, int(sched), _ptr(model_out), _ptr(x_start), _ptr(x_t), _ptr(noise), ti[0], B, T,
+                                               _ptr(terms), _ptr(pred), self._stream()))
+        return (terms, pred) if want_pred else terms
+
+    def diff_training_losses(self, sched, x_start, t, code_emb, noise=None, seed=0, sample_ids=None, lens=None, want_pred=True):
+        """training_losses composed on the device (dtts_diff_training_losses): q_sample -> the per-row trunk forward -> the loss terms
+        -> (terms cuda fp32 [B, 3] = (mse, vb, loss), pred_xstart [B,128,T] or None)"""
+        _check(x_start, "x_start"); _check(code_emb, "code_emb"); _check(noise, "noise")
+        B, _, T = x_start.shape
+        if code_emb is None or tuple(code_emb.shape[::2]) != (B, T):
+            raise DttsError("diff_training_losses: code_emb [B,768,T] is required")
+        ti = self._loss_t(t, B, "diff_training_losses")
+        si = _ints(list(range(B)) if sample_ids is None else sample_ids)
+        li = _ints(lens)
+        terms = torch.zeros((B, 3), device=self.device, dtype=torch.float32)
+        pred = torch.empty_like(x_start) if want_pred else None
+        self._rc(self.lib.dtts_diff_training_losses(self.h, int(sched), _ptr(x_start), ti[0], _ptr(noise), int(seed), si[0], _ptr(code_emb),
+                                                    li[0] if li else None, B, T, _ptr(terms), _ptr(pred), self._stream()))
+        return terms, pred
+
+    def l1_mean(self, a, b):
+        """mean |a - b| over two [B, C, T] tensors (dtts_l1_mean: fixed-order reduction) -> 0-d fp32 cuda"""
+        _check(a, "a"); _check(b, "b")
+        if a.shape != b.shape or a.dim() != 3:
+            raise DttsError("l1_mean: two [B, C, T] tensors of one shape")
+        out = torch.zeros((1,), device=self.device, dtype=torch.float32)
+        self._rc(self.lib.dtts_l1_mean(self.h, _ptr(a), _ptr(b), a.shape[0], a.shape[1], a.shape[2], _ptr(out), self._stream()))
+        return out[0]
+
     # ------------------------------------------------------------------ stage C
     def vocoder(self, mel, seed, sample_ids, lens=None, noise_scale=0.667, noise_override=None, return_z=False, stream_chunk=0):
         """infer_flowvae; stream_chunk > 0: the generator runs in windows of that many frames (+ 16-frame halo), dtts_vocoder_stream"""

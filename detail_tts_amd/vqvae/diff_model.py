@@ -44,16 +44,28 @@ class DiffusionTts:
                 conditioning_free=False, return_code_pred=False, lengths=None):
         """vqvae/diff_model.py:262-322.  `timesteps` are model-side timesteps in [0, 4000): integers as _WrappedModel passes them
         (vqvae/utils/diffusion.py:1282-1287; those of the default 50-step schedule use its bind-time tables), or fractional fp32 times
-        as k_diffusion_sample_loop passes them (t * 1000, :534-535; timestep_embedding takes `timesteps.float()`, :20-38)."""
+        as k_diffusion_sample_loop passes them (t * 1000, :534-535; timestep_embedding takes `timesteps.float()`, :20-38).  Integer
+        timesteps may differ between rows (conditional branch only, not with the fp16 trunk mode); fractional ones may not."""
         if precomputed_aligned_embeddings is None and not conditioning_free:
             precomputed_aligned_embeddings = self.timestep_independent(aligned_conditioning, conditioning_latent, x.shape[-1])
-        ts = set(torch.as_tensor(timesteps).reshape(-1).float().tolist())
-        if len(ts) != 1:
-            raise ValueError("all batch rows must share one timestep (as in p_sample_loop)")
-        t = ts.pop()
-        if not 0 <= t < 4000:
-            raise ValueError(f"timestep {t} is outside the trained range [0, 4000)")
+        tl = torch.as_tensor(timesteps).reshape(-1).float().tolist()
+        for t in tl:
+            if not 0 <= t < 4000:
+                raise ValueError(f"timestep {t} is outside the trained range [0, 4000)")
         emb = None if conditioning_free else precomputed_aligned_embeddings
+        if len(set(tl)) != 1:
+            # rows at different timesteps (training_losses draws one t per row): the conditional branch alone, every row at its own
+            # column of a one-off schedule of the distinct values (dtts_diff_forward_rows)
+            if any(t != int(t) for t in tl):
+                raise ValueError("batch rows at different FRACTIONAL timesteps are not implemented (integer timesteps may differ)")
+            if conditioning_free:
+                raise ValueError("conditioning_free=True needs all batch rows at one timestep (as in p_sample_loop)")
+            if len(tl) != x.shape[0]:
+                raise ValueError(f"{len(tl)} timesteps for {x.shape[0]} batch rows")
+            distinct = sorted(set(int(t) for t in tl))
+            cols = [distinct.index(int(t)) for t in tl]
+            return self.rt.diff_forward_rows(x.float().contiguous(), cols, emb, sched=self.rt.diff_schedule(distinct), lens=lengths)
+        t = tl[0]
         if t == int(t):
             return self.rt.diff_forward_t(x.float().contiguous(), int(t), emb, cond_free=conditioning_free, lens=lengths)
         return self.rt.diff_forward_tf(x.float().contiguous(), t, emb, cond_free=conditioning_free, lens=lengths)

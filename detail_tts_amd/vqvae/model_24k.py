@@ -20,7 +20,7 @@ from ..gpt.candidates import check_choose, check_num_candidates, expand_sample_i
 from ..gpt.model import UnifiedVoice
 from ..runtime import Runtime
 from .diff_model import DiffusionTts
-from .utils.diffusion import SAMPLERS, SpacedDiffusion, get_named_beta_schedule, space_timesteps
+from .utils.diffusion import SAMPLERS, SpacedDiffusion, check_timesteps, get_named_beta_schedule, space_timesteps
 
 
 def normalize_torch_mel(mel):
@@ -84,6 +84,15 @@ def sampling_args(diffusion_steps=None, sampler="p", eta=0.0):
 
 
 TRUNK_PRECISIONS = {"fp32": 0, "fp16": 1}
+
+TRAIN_DIFFUSION_STEPS = 200         # vqvae/model_24k.py:560-561 (desired_diffusion_steps)
+FORWARD_TARGETS = {"vqvae": "forward_vq", "gpt": "forward_gpt", "diff": "forward_diff"}      # cfg['train']['target'] -> stage loss (:740-751)
+
+
+def draw_timesteps(seed, batch, steps=TRAIN_DIFFUSION_STEPS):
+    """forward_diff's `t` when the caller gives none: `batch` integers in [0, steps) from numpy's RandomState(seed) on the host.  They
+    cannot equal torch.randint's draw (vqvae/model_24k.py:673): a caller who wants the reference's numbers passes its t and noise."""
+    return [int(v) for v in np.random.RandomState(int(seed) % (1 << 32)).randint(0, steps, size=int(batch))]
 
 
 def trunk_precision_arg(trunk_precision):
@@ -153,6 +162,13 @@ class SynthesizerTrn:
                                               betas=get_named_beta_schedule("linear", TRAINED_DIFFUSION_STEPS),
                                               conditioning_free=True, conditioning_free_k=COND_FREE_K, sampler="dpm++2m")
         self.rt.timestep_map = list(self.infer_diffuser.timestep_map)
+        # vqvae/model_24k.py:560-580: the training / validation diffuser, 200 of the 4000 steps, no guidance (its sampling loops stay refused)
+        self.desired_diffusion_steps = TRAIN_DIFFUSION_STEPS
+        self.diffuser = SpacedDiffusion(space_timesteps(TRAINED_DIFFUSION_STEPS, [TRAIN_DIFFUSION_STEPS]),
+                                        betas=get_named_beta_schedule("linear", TRAINED_DIFFUSION_STEPS),
+                                        conditioning_free=False, conditioning_free_k=COND_FREE_K)
+        self.diffuser.rt = self.infer_diffuser.rt = self.rt
+        self.target = self.cfg["train"].get("target")                 # :631
         self.stage_ms = None          # set to {} to collect per-stage hipEvent timings of the next infer() call
         self._voc_stream = None       # second stream of infer(stream_vocoder=True)
         self._gpt_stream = None       # high-priority stage-A stream of infer_stream()
@@ -677,6 +693,64 @@ class SynthesizerTrn:
         loss_text, loss_mel, _ = self.gpt(mel, data["spec_length"], data["text"], data["text_length"], code, data["raw_wav_length"],
                                           return_logits=False)
         return loss_text * self.text_loss_weight + loss_mel * self.mel_loss_weight
+
+    def forward_diff(self, y, y_lengths, data, *, t=None, noise=None, seed=0):
+        """vqvae/model_24k.py:667-696, the diffusion stage's validation loss -> a 0-d fp32 CUDA tensor.  eval() semantics, no gradients
+        (unconditioned_percentage and layer_drop are training branches).  x_start = normalize_torch_mel(data['raw_mel']); codes of
+        data['raw_mel'] (encode); GPT latents of (raw_mel, raw_spec_length, text, text_length, codes, raw_wav_length) with
+        return_latent=True, clip_inputs=False; conditioning_latent = get_conditioning(y); diffuser.training_losses on the 200-step
+        schedule; the mean of the rows' losses, added in row order.  y_lengths is unused, as in the reference.
+
+        t [B] (integers in [0, 200), checked on the host) and noise [B,128,T] default to host-drawn timesteps (draw_timesteps(seed, B))
+        and Philox noise keyed by (seed, row): neither can equal torch's RNG, so a caller who wants the reference's numbers passes
+        both.  The reference's GPT forward here is a rectangle without an attention mask while this one is ragged (text_length,
+        raw_wav_length): the two agree when every row has the full text width and a full-length raw_wav_length."""
+        raw_mel = torch.as_tensor(data["raw_mel"]).to(self.device, torch.float32).contiguous()
+        B = raw_mel.shape[0]
+        ts = draw_timesteps(seed, B, self.desired_diffusion_steps) if t is None else check_timesteps(t, B, self.diffuser.num_timesteps)
+        if self.rt.get_option("trunk_fp16"):
+            raise NotImplementedError("forward_diff runs the three-product trunk only: switch the fp16 trunk mode off for this call "
+                                      "(diffusion.enable_fp16 = False)")
+        if noise is not None:
+            noise = torch.as_tensor(noise).to(self.device, torch.float32).contiguous()
+        code, _ = self.encode(raw_mel, data["raw_spec_length"])
+        aligned = self.gpt(raw_mel, data["raw_spec_length"], data["text"], data["text_length"], code, data["raw_wav_length"],
+                           return_latent=True, clip_inputs=False)
+        cond = self.diffusion.get_conditioning(torch.as_tensor(y).to(self.device, torch.float32))
+        sched = self.rt.diff_schedule(self.diffuser.timestep_map)
+        x_start, _, noise = self.rt.diff_q_sample(sched, raw_mel, ts, noise=noise, seed=seed, normalize=True)
+        losses = self.diffuser.training_losses(self.diffusion, x_start, ts, noise=noise,
+                                               model_kwargs={"aligned_conditioning": aligned, "conditioning_latent": cond})["loss"]
+        total = losses[0]
+        for b in range(1, B):                                      # .mean() over the rows in a fixed order
+            total = total + losses[b]
+        return total / B
+
+    def forward_vq(self, y, y_lengths, data=None):
+        """vqvae/model_24k.py:654-666, the VQ stage's validation loss -> a 0-d fp32 CUDA tensor: L1(vq_dec(quantizer(vq_enc(y)) +
+        vq_ref_enc(y * mask, mask)), y), the mean over the whole [B,128,T] rectangle.  In eval mode the reference quantizer's commit
+        loss is the constant 0 (vqvae/modules/core_vq.py:311-319), so the reconstruction loss is the whole of it."""
+        y = torch.as_tensor(y)
+        if y.shape[-1] % 4 != 0:
+            raise ValueError(f"forward_vq needs a frame count divisible by 4 (the reference asserts it), not {y.shape[-1]}")
+        y = y.to(self.device, torch.float32).contiguous()
+        yl = [int(v) for v in torch.as_tensor(y_lengths).reshape(-1).tolist()]
+        codes, _ = self.rt.vq_encode(y)                            # vq_enc sees the whole rectangle (:659)
+        codes = codes.cpu().numpy()
+        recon = self.rt.vq_decode([codes[b] for b in range(y.shape[0])], y, yl)      # vq_ref_enc(y * mask, mask): lengths y_lengths
+        return self.rt.l1_mean(recon, y)
+
+    def forward(self, y, y_lengths, data):
+        """vqvae/model_24k.py:740-751: the stage loss cfg['train']['target'] names - 'vqvae' -> forward_vq, 'gpt' -> forward_gpt,
+        'diff' -> forward_diff.  'flowvae' and the default (all stages) need enc_q and a forward-direction flow, which are not on the
+        device: NotImplementedError."""
+        name = FORWARD_TARGETS.get(self.target)
+        if name is None:
+            raise NotImplementedError(f"forward for train.target = {self.target!r} needs enc_q (the posterior encoder) and a forward-direction "
+                                      "flow, which are not implemented on the device; targets 'vqvae', 'gpt' and 'diff' are")
+        return getattr(self, name)(y, y_lengths, data)
+
+    __call__ = forward
 
     def infer_vqvae(self, y, noise_scale=NOISE_SCALE, *, seed=0, sample_ids=None):
         """vqvae/model_24k.py:864-876: mel -> codes -> quantised latent + vq_ref_enc -> vq_dec -> (recon, wav); first row only"""

@@ -1,7 +1,7 @@
-"""Sampler object mirroring the subset of the reference's SpacedDiffusion that inference uses
+"""Sampler object mirroring the subset of the reference's SpacedDiffusion that inference and evaluation use
 (vqvae/utils/diffusion.py:179-228 + 1172-1272; p_sample_loop :654-742, ddim_sample_loop :819-899, k_diffusion_sample_loop :487-581,
-sample_loop :640-652).  The arithmetic lives in libdetail_hip.so (dtts_diff_sample_ex); this class carries the schedule constants and
-the call surface."""
+sample_loop :640-652; q_sample :243-260, training_losses :930-1012).  The arithmetic lives in libdetail_hip.so (dtts_diff_sample_ex,
+dtts_diff_q_sample, dtts_diff_training_losses); this class carries the schedule constants and the call surface."""
 from __future__ import annotations
 
 import numpy as np
@@ -34,6 +34,19 @@ def space_timesteps(num_timesteps, section_counts):
             cur += stride
         start += size
     return set(out)
+
+
+def check_timesteps(t, batch, num_timesteps):
+    """Host-side check of training_losses' / q_sample's `t`, before any launch -> list of `batch` ints in [0, num_timesteps)."""
+    a = np.asarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t)
+    if a.shape != (batch,):
+        raise ValueError(f"t must hold one timestep per batch row (shape ({batch},)), not shape {tuple(a.shape)}")
+    if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) or np.all(a == np.floor(a))):
+        raise ValueError("t must hold integer timesteps")
+    a = a.astype(np.int64)
+    if a.min() < 0 or a.max() >= num_timesteps:
+        raise ValueError(f"t must lie in [0, {num_timesteps}), not {a.tolist()}")
+    return [int(v) for v in a]
 
 
 def get_named_beta_schedule(name, n):
@@ -81,6 +94,43 @@ class SpacedDiffusion:
             self.posterior_log_variance_clipped = np.log(np.append(pv[1 if len(pv) > 1 else 0], pv[1:]))
         self.posterior_mean_coef1 = betas * np.sqrt(self.alphas_cumprod_prev) / (1.0 - self.alphas_cumprod)
         self.posterior_mean_coef2 = (1.0 - self.alphas_cumprod_prev) * np.sqrt(alphas) / (1.0 - self.alphas_cumprod)
+        self.rt = None                # the Runtime q_sample runs on (SynthesizerTrn binds its diffusers; training_losses takes the model's)
+
+    # ---------------------------------------------------------------------------------------------------- evaluation losses
+    def q_sample(self, x_start, t, noise=None, *, seed=0, sample_ids=None):
+        """vqvae/utils/diffusion.py:243-260 on the device: x_t = sqrt_alphas_cumprod[t] x_start + sqrt_one_minus_alphas_cumprod[t] noise.
+        x_start [B,128,T] fp32 CUDA, t [B] integers in [0, num_timesteps) (checked on the host).  noise None: drawn from the Philox
+        spec on its own stage (5), keyed by (seed, sample_ids[b]) - never torch's RNG; (x_t, noise) is returned then, else x_t."""
+        if self.rt is None:
+            raise RuntimeError("q_sample needs a Runtime: set `diffuser.rt` (SynthesizerTrn does for its own diffusers)")
+        ts = check_timesteps(t, x_start.shape[0], self.num_timesteps)
+        _, x_t, z = self.rt.diff_q_sample(self.rt.diff_schedule(self.timestep_map), x_start.float().contiguous(), ts, noise=noise, seed=seed,
+                                          sample_ids=sample_ids)
+        return x_t if noise is not None else (x_t, z)
+
+    def training_losses(self, model, x_start, t, model_kwargs=None, noise=None, *, seed=0, sample_ids=None):
+        """vqvae/utils/diffusion.py:930-1012 for the model's epsilon / learned_range / mse configuration, eval() semantics, no gradients:
+        -> dict(loss, mse, vb: fp32 CUDA [B]; x_start_predicted [B,128,T]).  model: a detail_tts_amd DiffusionTts.  t [B]: integers in
+        [0, num_timesteps), one per row, checked on the host before any launch; row b's trunk forward runs at model timestep
+        timestep_map[t[b]] (dtts_diff_training_losses on this diffuser's schedule, built once and cached).  model_kwargs carries
+        precomputed_aligned_embeddings, or aligned_conditioning + conditioning_latent as forward_diff passes them.  noise None: drawn
+        as in q_sample.  The losses are means over every row's whole [128, T] rectangle (mean_flat).  The loss path runs the default
+        three-product trunk: with the model's fp16 mode on (option trunk_fp16) the call is refused."""
+        B, _, T = x_start.shape
+        ts = check_timesteps(t, B, self.num_timesteps)
+        kw = dict(model_kwargs or {})
+        emb = kw.get("precomputed_aligned_embeddings")
+        if emb is None and (kw.get("aligned_conditioning") is None or kw.get("conditioning_latent") is None):
+            raise ValueError("model_kwargs needs precomputed_aligned_embeddings, or aligned_conditioning and conditioning_latent")
+        rt = model.rt
+        if rt.get_option("trunk_fp16"):
+            raise NotImplementedError("training_losses runs the three-product trunk only: switch the fp16 trunk mode off for this call "
+                                      "(diffusion.enable_fp16 = False)")
+        if emb is None:
+            emb = model.timestep_independent(kw["aligned_conditioning"], kw["conditioning_latent"], T)
+        terms, pred = rt.diff_training_losses(rt.diff_schedule(self.timestep_map), x_start.float().contiguous(), ts, emb, noise=noise,
+                                              seed=seed, sample_ids=sample_ids)
+        return {"loss": terms[:, 2].contiguous(), "mse": terms[:, 0].contiguous(), "vb": terms[:, 1].contiguous(), "x_start_predicted": pred}
 
     # ---------------------------------------------------------------------------------------------------- sampling loops
     def _check(self, sampler):

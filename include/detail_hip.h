@@ -284,6 +284,55 @@ int dtts_diff_step_dpm(dtts_handle* h, int id, float* x, float* x0_hist, const f
 int dtts_diff_forward_tf(dtts_handle* h, const float* x, const float* code_emb, const int* lens, int B, int T, float timestep,
                          int cond_free, float* out, void* stream);
 
+/* DiffusionTts.forward (vqvae/diff_model.py:262-322), conditional branch only, with every batch row at its OWN timestep: row b is
+ * evaluated at column steps[b] (HOST [B], each in [0, steps of the schedule)) of integer-timestep schedule `id` (dtts_diff_schedule),
+ * in the three conditioning_timestep_integrator layers and in every ResBlock of the stack and tail - what training_losses needs, which
+ * draws one t per row.  x [B,128,T], code_emb [B,768,T], lens HOST [B] or NULL, out [B,256,T].  Only the conditional branch runs: a
+ * B-sample stack on `stream`, no unconditional rows.  The default three-product trunk with GroupNorm as its own pass (option gn_fuse
+ * does not apply here); with option trunk_fp16 = 1 the call is refused before any launch.  Arguments are checked on the host. */
+int dtts_diff_forward_rows(dtts_handle* h, int id, const float* x, const float* code_emb, const int* lens, int B, int T, const int* steps,
+                           float* out, void* stream);
+
+/* Host copy of the forward-process tables of schedule `id`: *n_out steps; table [cap][2] (may be NULL) per step
+ * {sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod} as fp32 (vqvae/utils/diffusion.py:212-213; float64 -> fp32 like the tables of
+ * dtts_diff_schedule_coefs, whose [cap][9] layout is unchanged). */
+int dtts_diff_schedule_qtable(dtts_handle* h, int id, float* table, int cap, int* n_out);
+
+/* ---- evaluation losses of the diffusion and VQ stages (SynthesizerTrn.forward_diff / forward_vq, vqvae/model_24k.py:654-696) --------
+ * eval() semantics, no gradients.  `t` HOST [B]: every row's step of integer-timestep schedule `id`, checked against [0, steps) before
+ * any launch.  All kernels are fp32 and use no atomics: sums are block partials in a fixed order and one finishing pass, so two calls
+ * give the same bits and a row's values do not depend on the rest of the batch.  The losses are means over the whole [128, T]
+ * rectangle of every row, as in the reference (mean_flat, no mask): ragged lengths for the loss are out of scope (`lens` of
+ * dtts_diff_training_losses reaches the trunk's forward only).  Buffers are 16-byte aligned.  Asynchronous on `stream`.
+ *
+ * GaussianDiffusion.q_sample (vqvae/utils/diffusion.py:243-260): x_start = normalize ? normalize_torch_mel(mel) : mel;
+ * x_t = sqrt_alphas_cumprod[t_b] x_start + sqrt_one_minus_alphas_cumprod[t_b] noise.  mel, noise, x_start_out, x_t_out, noise_out
+ * DEVICE [B,128,T].  noise NULL: drawn from the Philox spec on noise stage 5 (step 0, stream sample_ids[b] HOST, element order
+ * [128, T]; no other site draws from this stage) and written to noise_out.  x_start_out / noise_out may be NULL. */
+int dtts_diff_q_sample(dtts_handle* h, int id, const float* mel, int normalize, const int* t, const float* noise, unsigned long long seed,
+                       const int* sample_ids, int B, int T, float* x_start_out, float* x_t_out, float* noise_out, void* stream);
+
+/* The loss arithmetic of GaussianDiffusion.training_losses (vqvae/utils/diffusion.py:930-1012; epsilon / learned_range / mse) on a given
+ * model output.  model_out DEVICE [B,256,T] (eps | var); x_start, x_t, noise DEVICE [B,128,T].  terms_out DEVICE [B][3] =
+ * (mse, vb, loss = mse + vb) per row: mse = mean (noise - eps)^2; vb = _vb_terms_bpd (:903-928) of the frozen output - x0 from eps
+ * clamped to +-1, q_posterior_mean_variance of the true and the predicted start, the learned-range log-variance between
+ * posterior_log_variance_clipped[t] and log(betas[t]), normal_kl (:17-35), the discretised-Gaussian NLL (:38-73: tanh CDF, 1e-12 clamps,
+ * the x < -0.999 / x > 0.999 branches), where(t == 0, nll, kl) / ln 2.  pred_xstart (may be NULL) DEVICE [B,128,T] receives
+ * _predict_xstart_from_eps unclamped, the reference's terms["x_start_predicted"]. */
+int dtts_diff_loss_terms(dtts_handle* h, int id, const float* model_out, const float* x_start, const float* x_t, const float* noise,
+                         const int* t, int B, int T, float* terms_out, float* pred_xstart, void* stream);
+
+/* training_losses composed: dtts_diff_q_sample (x_start given, normalised already) -> dtts_diff_forward_rows at steps = t ->
+ * dtts_diff_loss_terms, with x_t, drawn noise and the model output in the handle's workspace.  noise NULL: drawn as in
+ * dtts_diff_q_sample from (seed, sample_ids).  code_emb DEVICE [B,768,T] (dtts_diff_timestep_independent).  Refused with trunk_fp16 = 1. */
+int dtts_diff_training_losses(dtts_handle* h, int id, const float* x_start, const int* t, const float* noise, unsigned long long seed,
+                              const int* sample_ids, const float* code_emb, const int* lens, int B, int T, float* terms_out,
+                              float* pred_xstart, void* stream);
+
+/* out[0] = mean |a - b| over a [B,C,T] rectangle (nn.L1Loss of forward_vq, vqvae/model_24k.py:664); B C T a multiple of 4.  The same
+ * fixed-order reduction as dtts_diff_loss_terms. */
+int dtts_l1_mean(dtts_handle* h, const float* a, const float* b, int B, int C, int T, float* out, void* stream);
+
 /* ---- stage C: flow-VAE front + HiFiGAN generator -------------------------------------------------- */
 
 /* SynthesizerTrn.infer_flowvae (vqvae/model_24k.py:848-863): ref_enc -> in_proj -> enc_p -> z_p -> flow^-1 -> dec.
