@@ -33,6 +33,11 @@ class DttsGptOptions(C.Structure):
                 ("forced_uniforms", C.c_void_p), ("forced_codes", c_int_p), ("row_seeds", c_u64_p), ("typical_mass", C.c_float), ("token_wgs", C.c_int)]
 
 
+class DttsConvX3Info(C.Structure):
+    _fields_ = [("epi", C.c_int), ("kw3", C.c_int), ("stages", C.c_int), ("ksplit", C.c_int), ("p1", C.c_int), ("epi_vec", C.c_int),
+                ("cols", C.c_int), ("workgroups", C.c_int)]
+
+
 class DttsKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("launches", C.c_longlong), ("total_ms", C.c_double), ("union_ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -123,6 +128,9 @@ SIGNATURES = {
     "dtts_op_enc_p": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dtts_op_conv1d": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "dtts_op_conv1d_x3": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(DttsConvX3Info),
+                                    C.c_void_p]),
     "dtts_op_philox_normal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_ulonglong, c_int_p, C.c_int, C.c_int, C.c_void_p]),
 }
 

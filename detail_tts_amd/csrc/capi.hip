@@ -496,6 +496,19 @@ int dtts_op_conv1d(dtts_handle* h, const char* name, const float* x, const int* 
     DTTS_API_END(h)
 }
 
+int dtts_op_conv1d_x3(dtts_handle* h, const char* name, const float* x, const int* lens, int B, int Cin, int T, int Cout, int KW,
+                      int epi_act, float out_scale, int gate, const float* badd, const float* res, int p1, int ksplit_max, float* y,
+                      dtts_conv_x3_info* info, void* stream) {
+    DTTS_API_BEGIN
+    dtts::ConvX3Launch c;
+    h->m->op_conv1d_x3(name, x, lens, B, Cin, T, Cout, KW, epi_act, out_scale, gate, badd, res, p1, ksplit_max, y, &c, (hipStream_t)stream);
+    if (info) {
+        info->epi = c.epi; info->kw3 = c.kw3; info->stages = c.stages; info->ksplit = c.ksplit;
+        info->p1 = c.p1; info->epi_vec = c.epi_vec; info->cols = c.cols; info->workgroups = c.workgroups;
+    }
+    DTTS_API_END(h)
+}
+
 int dtts_op_philox_normal(dtts_handle* h, float* out, int n, int B, unsigned long long seed, const int* sample_ids, int stage,
                           int step, void* stream) {
     DTTS_API_BEGIN

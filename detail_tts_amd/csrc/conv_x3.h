@@ -41,7 +41,16 @@ void launch_gn_split_planes(const float* x, long long x_bs, int x_cs, const int*
 // as a 1x1 conv without residual (EPI 4: the WaveNet in_layers over launch_split_planes_taps planes)
 // p.p1 (the trunk's fp16 mode, option "trunk_fp16"): ONE product h0 h0' on plane 0 of the same images, 32 channels per K-step, instead of
 // three (Cin a multiple of 32, no gate); plane 1 is neither fetched nor multiplied (conv_x3.hip)
-void launch_conv_x3(const ConvParams& p, hipStream_t s);
+// `chosen` (host side, may be null): what the launcher picked for this launch, filled just before the launch - the instantiation
+// (epi 0..4, kw3, stages 2..4, p1), the split, the epilogue form (epi_vec 1: LDS-staged 16-byte stores, 0: scalar), whether a live-column
+// table is attached and the grid size.  How tests/test_gpu_conv_x3.py asserts that a case ran the variant it was written for.
+struct ConvX3Launch {
+    int epi = -1, kw3 = 0, stages = 0, ksplit = 0, p1 = 0, epi_vec = 0, cols = 0, workgroups = 0;
+};
+void launch_conv_x3(const ConvParams& p, hipStream_t s, ConvX3Launch* chosen = nullptr);
+// option "conv_stages" (process-wide): 2 / 3 / 4 forces that many LDS stages, 0 = by launch size (the launcher's rule), n < 0 = back to
+// the initial value (DTTS_CONV_STAGES, else 0)
+void set_conv_stages(int n);
 
 // Split scratch of a launch stream (conv_x3's split-K slabs; the trunk attention's key-split partials use the same slot: launches on one
 // stream are ordered): `part` = nslabs slabs of X3_SLAB_FLOATS floats, `count` = X3_SPLIT_COUNTERS arrival counters that are zero

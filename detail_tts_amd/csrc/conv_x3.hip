@@ -6,6 +6,7 @@
 // tools/ubench/gemm_x3v.hip (M = 768 / 2304, B = 16, T = 936): 128 x 192 beats 128 x 128 by 8-10 % (2.5 instead of 8.6 % padded
 // columns, 17 % fewer LDS-DMA bytes per MFMA); deeper pipelines and 256-row tiles measured within +-3 % of it.
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <mutex>
 #include <type_traits>
@@ -1276,7 +1277,18 @@ bool conv_x3_gn_fusable(int Cout, int CoutP, int Cin, int KW, int groups, int B,
     return nt <= GN_FUSE_MAX_NT;
 }
 
-void launch_conv_x3(const ConvParams& p_in, hipStream_t s) {
+// option "conv_stages" / DTTS_CONV_STAGES (process-wide, like conv_small_tiles): the number of LDS stages of every conv_x3 launch
+static int conv_stages_default() {
+    static const int v = []() { const int n = (int)env_int("DTTS_CONV_STAGES", 0); return n >= 2 && n <= 4 ? n : 0; }();
+    return v;
+}
+static std::atomic<int> g_conv_stages{-1};
+void set_conv_stages(int n) {
+    DTTS_REQUIRE(n <= 0 || (n >= 2 && n <= 4), "conv_stages: 0 (by launch size), 2, 3 or 4");
+    g_conv_stages.store(n < 0 ? -1 : n, std::memory_order_relaxed);
+}
+
+void launch_conv_x3(const ConvParams& p_in, hipStream_t s, ConvX3Launch* chosen) {
     ConvParams p = p_in;
     DTTS_REQUIRE(p.w3 && p.x3 && (p.y || p.qkv_planes || p.gn_out3) && p.x3_tp > 0, "conv_x3: operands");
     const bool gn = p.gn_out3 != nullptr;
@@ -1302,8 +1314,9 @@ void launch_conv_x3(const ConvParams& p_in, hipStream_t s) {
     // LDS stages by launch size.  Small launches expose each workgroup's own dependency chain DMA -> barrier -> fragment reads -> MFMA,
     // so the loads run further ahead (counted vmcnt): four stages (82 KiB, one workgroup per CU) up to DTTS_CONV_STAGES4_MAXWG = 128
     // workgroups (half the CUs: batch 1), three (61 KiB, two per CU) up to DTTS_CONV_STAGES3_MAXWG = 600, two (41 KiB, three per CU)
-    // for launches that fill the chip several times over.  DTTS_CONV_STAGES = 2 / 3 / 4 forces one.
-    static const int force_stg = []() { const int n = env_int("DTTS_CONV_STAGES", 0); return n >= 2 && n <= 4 ? n : 0; }();
+    // for launches that fill the chip several times over.  Option "conv_stages" / DTTS_CONV_STAGES = 2 / 3 / 4 forces one.
+    const int stg_opt = g_conv_stages.load(std::memory_order_relaxed);
+    const int force_stg = stg_opt >= 0 ? stg_opt : conv_stages_default();
     static const long long max3 = env_int("DTTS_CONV_STAGES3_MAXWG", 600);
     static const long long max4 = env_int("DTTS_CONV_STAGES4_MAXWG", 128);
     if (gn) p.cols = nullptr;                                            // the fused GroupNorm's id order is per sample
@@ -1346,6 +1359,16 @@ void launch_conv_x3(const ConvParams& p_in, hipStream_t s) {
         else if (by_shape) tag = p.KW == 3 ? "conv_x3 k3" : (p.Cout > 1024 ? "conv_x3 k1 M=2304" : (p.res ? "conv_x3 k1 +res" : "conv_x3 k1"));
         ProfScope ps(tag, flops, bytes, s);
         const bool epi = p.epi_act != ACT_NONE || p.out_scale != 1.f;
+        if (chosen) {
+            chosen->epi = gn ? 3 : (gated ? 4 : (p.qkv_planes ? 2 : (epi ? 1 : 0)));
+            chosen->kw3 = p.KW == 3 ? 1 : 0;
+            chosen->stages = nstg;
+            chosen->ksplit = S;
+            chosen->p1 = p1 ? 1 : 0;
+            chosen->epi_vec = p.epi_vec;
+            chosen->cols = p.cols ? 1 : 0;
+            chosen->workgroups = (int)nwg;
+        }
 #define DTTS_LAUNCH_X3P1(E, K3)                                                                                        \
     do {                                                                                                               \
         if (nstg == 4) { lds_optin(reinterpret_cast<const void*>(conv_x3_kernel<E, K3, 4, true>), l4); hipLaunchKernelGGL((conv_x3_kernel<E, K3, 4, true>), grid, dim3(256), lds, s, p); } \

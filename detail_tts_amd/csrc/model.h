@@ -259,6 +259,12 @@ public:
     void op_conv1d(const char* name, const float* x, const int* lens_in_host, int B, int Cin, int Tin, int Cout, int KW, int stride,
                    int dil, int pad, int pro_act, int epi_act, int gate, int phases, const float* res, float* y, int Tout_alloc,
                    hipStream_t s);
+    // ONE conv through the split-precision kernel (conv_x3.h) on packed fp32 weights `name`: x [B, Cin, T] -> y [B, rows, T] (rows = Cout,
+    // Cout / 2 when gated), k = 1 or 3 with "same" padding.  Every shape the kernel or the split passes cannot take is refused before
+    // anything is launched; `chosen` receives what the launcher picked.
+    void op_conv1d_x3(const char* name, const float* x, const int* lens_host, int B, int Cin, int T, int Cout, int KW, int epi_act,
+                      float out_scale, int gate, const float* badd, const float* res, int p1, int ksplit_max, float* y, ConvX3Launch* chosen,
+                      hipStream_t s);
     void op_philox_normal(float* out, int n, int B, unsigned long long seed, const int* sample_ids_host, int stage, int step,
                           hipStream_t s);
 
@@ -293,6 +299,7 @@ public:
         // process-wide: the small-launch tile rule of the exact fp32 conv (conv_gemm.h).  A kernel choice made at launch time; the only
         // captured graphs, stage A's decode graphs, hold no conv_gemm launch (the prefill, which does, is never captured): nothing to drop
         else if (key == "conv_small_tiles") set_conv_small_tiles(value);
+        else if (key == "conv_stages") set_conv_stages(value);               // process-wide: LDS stages of the split-precision conv (conv_x3.h); a launch-time choice like the above
         else if (key == "integ_pipeline") opt_integ_pipeline_ = value;      // 0 (default) / 1; -1: by batch size (on up to batch 4)
         else throw Error(-1, "unknown option '" + key + "'");
     }
@@ -359,7 +366,7 @@ private:
     void register_cols(const int* lens_dev, const int* lens_host, int nb, int T, hipStream_t s);
 
     // building blocks on [B, C, T] buffers (all lens are device pointers)
-    void run_conv(const PackedConv& pc, ConvParams p, hipStream_t s) const;
+    void run_conv(const PackedConv& pc, ConvParams p, hipStream_t s, ConvX3Launch* chosen = nullptr) const;
     // GnNext / GnFuse: the GroupNorm + activation + split that FOLLOWS a block runs in the epilogue of the block's last conv
     // (conv_x3.h "fused GroupNorm").  TrunkIo::f carries the second planes buffer (producer and consumer planes ping-pong between xs and
     // f->xs_alt), the exchange buffer of the launch stream and whether xs ALREADY holds the block's normalised input (written by the

@@ -299,7 +299,7 @@ static void attach_cols(ConvParams& p) {
 }
 
 // (p.p1, the one-product mode of option "trunk_fp16", is the caller's: the trunk's blocks set it, everything else leaves it 0)
-void Model::run_conv(const PackedConv& pc, ConvParams p, hipStream_t s) const {
+void Model::run_conv(const PackedConv& pc, ConvParams p, hipStream_t s, ConvX3Launch* chosen) const {
     p.w = pc.w;
     if (!p.bias) p.bias = pc.b;
     p.Cin = pc.Cin;
@@ -311,7 +311,7 @@ void Model::run_conv(const PackedConv& pc, ConvParams p, hipStream_t s) const {
         DTTS_REQUIRE(pc.w3, "conv has no split-precision weights");
         p.w3 = pc.w3;
         attach_cols(p);
-        launch_conv_x3(p, s);
+        launch_conv_x3(p, s, chosen);
         return;
     }
     launch_conv_gemm(p, s);
@@ -346,6 +346,71 @@ void Model::op_conv1d(const char* name, const float* x, const int* lens_in_host,
     p.phases = phases > 1 ? phases : 1;
     if (res) with_res(p, res, p.y_bs, Tout_alloc);
     run_conv(pc, p, s);
+}
+
+// Single-conv entry of the split-precision kernel for parity tests: the weights are split into the workspace per call, the input
+// planes are written with the lengths folded in (no affine, no activation) and a ragged batch goes through the live-column table as in
+// the trunk.  Everything launch_conv_x3 and the split passes require is checked HERE, before the first launch or upload: a bad shape
+// never reaches a kernel.
+void Model::op_conv1d_x3(const char* name, const float* x, const int* lens_host, int B, int Cin, int T, int Cout, int KW, int epi_act,
+                         float out_scale, int gate, const float* badd, const float* res, int p1, int ksplit_max, float* y,
+                         ConvX3Launch* chosen, hipStream_t s) {
+    DTTS_REQUIRE(!weights_.empty(), "weights not bound");
+    DTTS_REQUIRE(name && x && y, "op_conv1d_x3: null argument");
+    DTTS_REQUIRE(B > 0 && B <= 65535 && T > 0 && T <= (1 << 20) && Cin > 0 && Cin <= (1 << 16) && Cout > 0 && Cout <= (1 << 16), "op_conv1d_x3: sizes");
+    DTTS_REQUIRE(KW == 1 || KW == 3, "op_conv1d_x3: k = 1 or k = 3 (same padding) only");
+    DTTS_REQUIRE(Cin % 16 == 0, "op_conv1d_x3: input channels must be a multiple of 16 (one K-step; the split passes write 8-channel chunks)");
+    const int CoutP = packed_cout(Cout);
+    DTTS_REQUIRE(CoutP % 128 == 0, "op_conv1d_x3: packed output rows must be a multiple of the 128-row tile (Cout > 64)");
+    DTTS_REQUIRE(p1 == 0 || p1 == 1, "op_conv1d_x3: p1 is 0 or 1");
+    DTTS_REQUIRE(gate == GATE_NONE || gate == GATE_TANH_SIGMOID, "op_conv1d_x3: gate is none or tanh * sigmoid");
+    DTTS_REQUIRE(!p1 || (Cin % 32 == 0 && gate == GATE_NONE), "op_conv1d_x3 one-product mode: input channels a multiple of 32, no gate");
+    DTTS_REQUIRE(epi_act == ACT_NONE || epi_act == ACT_SILU || epi_act == ACT_LRELU || epi_act == ACT_TANH, "op_conv1d_x3: epilogue activation");
+    DTTS_REQUIRE(ksplit_max >= 0, "op_conv1d_x3: ksplit_max");
+    const bool rows16 = (reinterpret_cast<unsigned long long>(y) & 15ull) == 0 && T % 4 == 0;
+    if (gate != GATE_NONE) {
+        DTTS_REQUIRE(KW == 1 && !res && epi_act == ACT_NONE && out_scale == 1.f && Cout % 2 == 0,
+                     "op_conv1d_x3 gated epilogue: 1x1 conv, no residual / activation / scale, an even number of rows");
+        DTTS_REQUIRE(rows16, "op_conv1d_x3 gated epilogue: rows of y must be 16-byte aligned (T a multiple of 4)");
+    } else {
+        DTTS_REQUIRE(!badd, "op_conv1d_x3: badd only with the gate");
+    }
+    const int nt = cdiv(T, X3_BN);
+    DTTS_REQUIRE((long long)(CoutP / 128) * nt * B <= (1 << 22), "op_conv1d_x3: launch too large");
+    std::vector<int> l(B);
+    for (int b = 0; b < B; ++b) {
+        l[b] = lens_host ? lens_host[b] : T;
+        DTTS_REQUIRE(l[b] >= 0 && l[b] <= T, "op_conv1d_x3: lengths must lie in [0, T]");
+    }
+    PackedConv pc = conv(name, Cin, Cout, KW, Wopt(std::string(name) + ".bp", (size_t)CoutP) != nullptr);
+    DTTS_REQUIRE(pc.CinP == Cin && pc.CoutP == CoutP, "op_conv1d_x3: packed weight shape");
+    // ---- nothing has been launched or uploaded up to here
+    const size_t w3_bytes = (size_t)KW * (Cin / 8) * 2 * CoutP * 16;      // [tap][Cin/8][2 planes][CoutP] 16-byte chunks (conv_x3.h)
+    ws().ensure(w3_bytes + x3_bytes(B, Cin, T) + 8192);
+    void* w3 = ws().raw(w3_bytes);
+    void* xs = ws().raw(x3_bytes(B, Cin, T));
+    launch_split_weights(pc.w, KW, pc.CinP, pc.CoutP, w3, s);
+    pc.w3 = w3;
+    const int* dl = upload_ints(l.data(), B, s);
+    const long long x_bs = (long long)Cin * T;
+    launch_split_planes(x, x_bs, T, nullptr, ACT_NONE, dl, T, B, Cin, xs, s);
+    register_cols(dl, l.data(), B, T, s);
+    ConvParams p = cp(x, Cin, y, gate != GATE_NONE ? Cout / 2 : Cout, B, T, T, dl);
+    p.pad = KW == 3 ? 1 : 0;
+    p.epi_act = epi_act;
+    p.epi_slope = 0.1f;
+    p.out_scale = out_scale;
+    p.gate = gate;
+    if (badd) {
+        p.badd = badd;              // [B][Cout] in packed row order
+        p.badd_bs = Cout;
+    }
+    if (res) with_res(p, res, p.y_bs, T);
+    with_planes(p, xs, T);
+    p.p1 = p1;
+    p.ksplit_max = ksplit_max;
+    run_conv(pc, p, s, chosen);
+    register_cols(dl, nullptr, 0, T, s);                               // enqueued: forget this call's table
 }
 
 void Model::op_philox_normal(float* out, int n, int B, unsigned long long seed, const int* sample_ids_host, int stage, int step,

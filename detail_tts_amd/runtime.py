@@ -710,6 +710,24 @@ class Runtime:
                                          pro_act, epi_act, gate, phases, _ptr(res), _ptr(y), tout, self._stream()))
         return y
 
+    def op_conv1d_x3(self, name, x, cout, kw, epi_act=0, out_scale=1.0, gate=0, badd=None, res=None, lens=None, p1=0, ksplit_max=0):
+        """One conv through the split-precision kernel (csrc/conv_x3.hip) on the packed weight `name`: x [B, Cin, T] -> (y, info, guard).
+        y [B, rows, T] is zero-filled before the call; guard is one more sample-sized slab directly behind y in the same allocation,
+        filled with NaN: a store past the batch shows there.  info: the variant the launcher chose (epi, kw3, stages, ksplit, p1, epi_vec,
+        cols, workgroups).  badd [B, cout] in packed row order (gate only)."""
+        _check(x, "x"); _check(res, "res"); _check(badd, "badd")
+        B, Cin, T = x.shape
+        rows = cout // 2 if gate else cout
+        buf = torch.zeros((B + 1, rows, T), device=self.device, dtype=torch.float32)
+        y, guard = buf[:B], buf[B]
+        guard.fill_(float("nan"))
+        li = _ints(lens)
+        info = _lib.DttsConvX3Info()
+        self._rc(self.lib.dtts_op_conv1d_x3(self.h, name.encode(), _ptr(x), li[0] if li else None, B, Cin, T, int(cout), int(kw), int(epi_act),
+                                            float(out_scale), int(gate), _ptr(badd), _ptr(res), int(p1), int(ksplit_max), _ptr(y),
+                                            C.byref(info), self._stream()))
+        return y, {k: int(getattr(info, k)) for k, _ in _lib.DttsConvX3Info._fields_}, guard
+
     def diff_p_sample(self, x, code_emb, step, seed, sample_ids, lens=None, noise=None, return_x0=False):
         """one GaussianDiffusion.p_sample at sampling step `step` (49 = first): returns the new x (and pred_xstart)"""
         _check(x, "x"); _check(code_emb, "code_emb"); _check(noise, "noise")

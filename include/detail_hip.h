@@ -451,6 +451,10 @@ int dtts_spectrogram(dtts_handle* h, const float* wav, const int* lens, int B, i
  *                 launcher picks among the 128- / 64- / 32-row tiles by shape alone - how tests/test_gpu_conv_tiles.py reaches every
  *                 tile at a tiny shape; < 0 = back to the default; env DTTS_CONV_SMALL_TILES sets the default.  A launch-time kernel
  *                 choice: the captured graphs (stage A's decode graphs) hold no conv launch, none is dropped;
+ *   "conv_stages" (default 0; process-wide): LDS stages of the split-precision conv (csrc/conv_x3.hip).  0 = by launch size (four
+ *                 stages up to 128 workgroups, three up to 600, two beyond); 2 / 3 / 4 = every launch takes that many - how
+ *                 tests/test_gpu_conv_x3.py reaches every pipeline depth at a tiny shape; < 0 = back to the initial value, which env
+ *                 DTTS_CONV_STAGES sets.  The K order does not depend on it: bit-identical output.  A launch-time kernel choice;
  *   "integ_pipeline" (default 0): 1 (-1: up to batch 4) = only the first chunk of the conditioning_timestep_integrator's step outputs is
  *                 evaluated in front of the sampling loop, the later chunks on a stream of their own under the first sampling steps
  *                 (bit-identical; returns 1 ms at batch 1 but can cost a pipelined request 60 ms in a process with many live
@@ -514,6 +518,26 @@ int dtts_op_resblock(dtts_handle* h, const char* prefix, const float* x, const i
 int dtts_op_conv1d(dtts_handle* h, const char* name, const float* x, const int* lens_in, int B, int Cin, int Tin, int Cout,
                    int KW, int stride, int dil, int pad, int pro_act, int epi_act, int gate, int phases, const float* res,
                    float* y, int Tout_alloc, void* stream);
+/* ONE Conv1d (k = 1, or k = 3 with padding 1; stride 1) through the split-precision kernel (csrc/conv_x3.h) on the packed fp32 weight
+ * `name` (`name.wp` / `name.bp`): the weights are split per call, x [B, Cin, T] DEVICE is written as fp16 planes with lens (HOST, null
+ * -> T) folded in, a ragged batch takes the live-column table ("conv_cols") -> y DEVICE [B, rows, T], rows = Cout (Cout / 2 with
+ * gate = 1: tanh * sigmoid over packed row pairs, k = 1 only, T % 4 == 0, optional badd DEVICE [B, Cout] in packed row order).
+ * epi_act 0 / 1 silu / 2 leaky-relu (0.1) / 5 tanh, then out_scale, then + res (DEVICE, as y, may be null).  p1 = 1: the one-product
+ * fp16 mode.  ksplit_max > 0 caps the split-K.  Cin % 16 == 0 (% 32 with p1) and Cout > 64; anything the kernel cannot take is
+ * refused before a launch.  info (may be null): what the launcher chose. */
+typedef struct dtts_conv_x3_info {
+    int epi;         /* epilogue instantiation: 0 bias (+ res), 1 + activation / scale, 4 gated */
+    int kw3;         /* 1: the three-tap instantiation */
+    int stages;      /* LDS stages 2 / 3 / 4 */
+    int ksplit;      /* workgroups per output tile along K */
+    int p1;          /* 1: one fp16 product */
+    int epi_vec;     /* 1: LDS-staged epilogue with 16-byte stores, 0: scalar stores */
+    int cols;        /* 1: a live-column table was attached */
+    int workgroups;  /* grid size */
+} dtts_conv_x3_info;
+int dtts_op_conv1d_x3(dtts_handle* h, const char* name, const float* x, const int* lens, int B, int Cin, int T, int Cout, int KW,
+                      int epi_act, float out_scale, int gate, const float* badd, const float* res, int p1, int ksplit_max, float* y,
+                      dtts_conv_x3_info* info, void* stream);
 /* The device sampler on given logits rows: HF RepetitionPenalty / Temperature / TopK / TopP processors as the reference's
  * generate() applies them (vqvae/model_24k.py:786-792) + the inverse-CDF draw on uniforms[r].  logits DEVICE [R][V] (R <= 16),
  * history HOST [R][hist_len] ids present in the row's input_ids, uniforms DEVICE [R] -> tokens HOST [R].  Synchronises. */
