@@ -112,6 +112,15 @@ SIGNATURES = {
     "dtts_diff_training_losses": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, c_int_p, C.c_void_p, C.c_ulonglong, c_int_p, C.c_void_p, c_int_p,
                                             C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dtts_l1_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dtts_posterior_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_int_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_ulonglong, c_int_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dtts_flow_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dtts_slice_segments": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dtts_kl_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                               C.c_void_p]),
+    "dtts_flowvae_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_ulonglong, c_int_p,
+                                       c_int_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
     "dtts_vocoder": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_ulonglong, c_int_p, C.c_float, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "dtts_vocoder_stream": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_ulonglong, c_int_p, C.c_float, C.c_void_p,

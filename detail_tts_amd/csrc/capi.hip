@@ -66,6 +66,41 @@ int dtts_op_enc_p(dtts_handle* h, const float* mel, const int* lens, int B, int 
     DTTS_API_END(h)
 }
 
+int dtts_posterior_encode(dtts_handle* h, const float* spec, int spec_channels, const int* lens, const float* g, int B, int T,
+                          const float* noise, unsigned long long seed, const int* sample_ids, float* z, float* m_q, float* logs_q, void* stream) {
+    DTTS_API_BEGIN
+    h->m->posterior_encode(spec, spec_channels, lens, g, B, T, noise, seed, sample_ids, z, m_q, logs_q, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_flow_forward(dtts_handle* h, const float* z, const float* g, const int* lens, int B, int T, float* z_p, void* stream) {
+    DTTS_API_BEGIN
+    h->m->flow_forward(z, g, lens, B, T, z_p, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_slice_segments(dtts_handle* h, const float* x, const int* ids, int B, int C, int T, int seg, float* out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->slice_segments(x, ids, B, C, T, seg, out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_kl_loss(dtts_handle* h, const float* z_p, const float* logs_q, const float* m_p, const float* logs_p, const int* lens, int B, int C,
+                 int T, float* out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->kl_loss(z_p, logs_q, m_p, logs_p, lens, B, C, T, out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_flowvae_forward(dtts_handle* h, const float* mel, const float* spec, int spec_channels, const int* lens, int B, int T,
+                         const float* noise, unsigned long long seed, const int* sample_ids, const int* ids_slice, int seg, float* o,
+                         float* z, float* z_p, float* m_p, float* logs_p, float* m_q, float* logs_q, float* quantized, void* stream) {
+    DTTS_API_BEGIN
+    h->m->flowvae_forward(mel, spec, spec_channels, lens, B, T, noise, seed, sample_ids, ids_slice, seg, o, z, z_p, m_p, logs_p, m_q, logs_q,
+                          quantized, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
 int dtts_vq_decode(dtts_handle* h, const int* codes, const int* ncodes, int nmax, const float* refer, const int* refer_lens, int Tr,
                    int B, float* mel_out, void* stream) {
     DTTS_API_BEGIN

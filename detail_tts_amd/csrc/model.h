@@ -20,6 +20,7 @@
 #include "conv_x3.h"
 #include "diff_loss.h"
 #include "diff_schedule.h"
+#include "flowvae_fwd.h"
 #include "gpt_kernels.h"
 #include "ops.h"
 #include "../../include/detail_hip.h"
@@ -69,9 +70,21 @@ struct EncLayerW {           // attentions.Encoder layer (vqvae/modules/attentio
     const float *ek = nullptr, *ev = nullptr, *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr;
 };
 
-struct CouplingW {           // ResidualCouplingLayer + WN (vqvae/modules/modules.py:421-475, 152-229)
-    PackedConv pre, post, cond;
-    PackedConv in[4], res[3], skip[4];
+struct WnW {                 // modules.WN of n_layers gated layers (vqvae/modules/modules.py:152-229): the flows' have 4, enc_q's 16
+    PackedConv cond;
+    std::vector<PackedConv> in, res, skip;      // in / skip: n_layers; res: n_layers - 1 (the last layer has no residual half)
+    int n_layers = 0;
+};
+
+struct CouplingW {           // ResidualCouplingLayer (vqvae/modules/modules.py:421-475)
+    PackedConv pre, post;
+    WnW enc;
+};
+
+struct PosteriorW {          // PosteriorEncoder / enc_q (vqvae/model_24k.py:172-218); optional, bound when the blob carries it
+    PackedConv pre, proj;
+    WnW enc;
+    int spec_channels = 0;   // filter_length / 2 + 1, read from the bound blob (enc_q.pre.cin)
 };
 
 struct GptLayerW {
@@ -230,7 +243,7 @@ public:
                             int B, float* losses_out, float* text_logprob, float* mel_logprob, float* mel_logits, hipStream_t s);
     // ---- stage C
     void mel_style(const MelStyleW& w, const float* mel, const int* lens_dev, const int* lens_host, int B, int T, float* g_out,
-                   hipStream_t s);
+                   hipStream_t s, bool padded_batch = false);
     void op_mel_style(const char* which, const float* mel, const int* lens_host, int B, int T, float* g_out, hipStream_t s);
     void vocoder(const float* mel, const int* lens_host, int B, int T, unsigned long long seed, const int* sample_ids_host,
                  float noise_scale, const float* noise_override, float* wav, float* trace_z, hipStream_t s, int gen_chunk = 0);
@@ -240,10 +253,25 @@ public:
     bool rb_fused_ok(const GenStageW& st, int ch) const;
     void rb_fused(const GenStageW& st, const float* x, float* y, int ch, const int* lens, int B, int T, int branch_mask, float scale, hipStream_t s);
     void op_resblock1(int stage, int branch, const float* x, const int* lens_host, int B, int T, float* y, hipStream_t s);
+    // flow 0 .. 3: the WaveNet of that coupling layer; flow -1: enc_q's 16-layer WaveNet
     void op_wn(int flow, const float* h, const float* g, const int* lens_host, int B, int T, float* out, hipStream_t s);
+    // ---- the flow-VAE stage forward (SynthesizerTrn.forward_flowvae, vqvae/model_24k.py:706-737); needs enc_q in the bound blob
+    // enc_q: spec [B, spec_channels, T], g [B, gin] -> z, m_q, logs_q [B, inter, T] (zeros beyond each row's length); noise [B, inter, T]
+    // or null: Philox STAGE_POSTERIOR keyed (seed, sample_ids[b])
+    void posterior_encode(const float* spec, int spec_ch, const int* lens_host, const float* g, int B, int T, const float* noise, unsigned long long seed,
+                          const int* sample_ids_host, float* z, float* m_q, float* logs_q, hipStream_t s);
+    // flow(z, mask, g) in the forward direction: C0, Flip, C2, Flip, C4, Flip, C6, Flip -> z_p [B, inter, T], zero tails
+    void flow_forward(const float* z, const float* g, const int* lens_host, int B, int T, float* z_p, hipStream_t s);
+    void slice_segments(const float* x, const int* ids_host, int B, int C, int T, int seg, float* out, hipStream_t s);
+    void kl_loss(const float* z_p, const float* logs_q, const float* m_p, const float* logs_p, const int* lens_host, int B, int C, int T,
+                 float* out, hipStream_t s);
+    // the whole stage in one stage-C arena and one range-check ticket: ref_enc, enc_p, enc_q, flow, segment slice, generator
+    void flowvae_forward(const float* mel, const float* spec, int spec_ch, const int* lens_host, int B, int T, const float* noise, unsigned long long seed,
+                         const int* sample_ids_host, const int* ids_slice_host, int seg, float* o, float* z, float* z_p, float* m_p,
+                         float* logs_p, float* m_q, float* logs_q, float* quantized, hipStream_t s);
     void op_enc_p(const float* mel, const int* lens_host, int B, int T, float* m_p, float* logs_p, hipStream_t s);
     void enc_p_fwd(const float* mel, const int* dl, int B, int T, float* x, float* y, float* qkv, float* att, float* ffn, float* relk, float* ml,
-                   float* stats, hipStream_t s);
+                   float* stats, hipStream_t s, bool padded_batch = false);
     // ---- VQ decode path (infer_gpt)
     void vq_decode(const int* codes_host, const int* ncodes_host, int nmax, const float* refer, const int* refer_lens_host, int Tr,
                    int B, float* mel_out, hipStream_t s);
@@ -322,8 +350,16 @@ private:
     void resblock1_fwd(const ResBlock1W& rb, const float* x, float* tmp, float* out, int ch, const int* lens, int B, int T, hipStream_t s,
                        void* xs = nullptr);
     bool vocoder_x3() const;
-    void wn_fwd(const CouplingW& c, float* h, const float* g, int gin, float* Gc, float* acts, float* h2, float* skip, const int* dl, int B,
+    void wn_fwd(const WnW& c, float* h, const float* g, int gin, float* Gc, float* acts, float* h2, float* skip, const int* dl, int B,
                 int T, hipStream_t s);
+    WnW wn_w(const std::string& prefix, int n_layers) const;
+    // enc_q up to stats = proj(h) * mask [B, 2 inter, T] (live columns only), and the forward flow; both carve their scratch from ws()
+    // (enc_q_ws_bytes / flow_ws_bytes, which the entry point has ensured) and give it back
+    void enc_q_fwd(const float* spec, int spec_ch, const float* g, const int* dl, int B, int T, float* stats, hipStream_t s);
+    void flow_fwd(const float* z, const float* g, const int* dl, int B, int T, float* z_p, hipStream_t s);
+    size_t enc_q_ws_bytes(int B, int T) const;
+    size_t flow_ws_bytes(int B, int T) const;
+    std::vector<int> stage_lens(const int* lens_host, int B, int T, const char* who) const;
     void build_diffusion(hipStream_t s);
     void build_vocoder(hipStream_t s);
     void build_gpt(hipStream_t s);
@@ -467,6 +503,8 @@ private:
     PackedConv in_proj_, enc_out_, enc_proj_, dec_pre_, dec_cond_, dec_post_;
     std::vector<EncLayerW> enc_layers_;
     std::vector<CouplingW> flows_;
+    PosteriorW enc_q_;
+    bool has_enc_q_ = false;
     std::vector<GenStageW> gen_;
 
     // gpt

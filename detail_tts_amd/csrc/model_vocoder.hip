@@ -23,6 +23,20 @@ MelStyleW Model::mel_style_w(const std::string& p, int n_mel, int hidden, int ou
     return w;
 }
 
+// modules.WN under `p` (".enc"): cond_layer rows gate-interleaved per layer, res_skip split into .res / .skip by the packer
+WnW Model::wn_w(const std::string& p, int n_layers) const {
+    const int hid = cfg.hidden_channels;
+    WnW w;
+    w.n_layers = n_layers;
+    w.cond = conv(p + ".cond_layer", cfg.gin_channels, 2 * hid * n_layers, 1);
+    for (int l = 0; l < n_layers; ++l) {
+        w.in.push_back(conv(p + ".in_layers." + std::to_string(l), hid, 2 * hid, 5));
+        if (l < n_layers - 1) w.res.push_back(conv(p + ".res_skip_layers." + std::to_string(l) + ".res", hid, hid, 1));
+        w.skip.push_back(conv(p + ".res_skip_layers." + std::to_string(l) + ".skip", hid, hid, 1));
+    }
+    return w;
+}
+
 void Model::build_vocoder(hipStream_t stream) {
     const int inter = cfg.inter_channels, hid = cfg.hidden_channels, filt = cfg.filter_channels, gin = cfg.gin_channels;
     ref_enc_ = mel_style_w("ref_enc", cfg.mel_channels, 128, gin);
@@ -52,13 +66,22 @@ void Model::build_vocoder(hipStream_t stream) {
         const std::string p = "flow.flows." + std::to_string(f);
         c.pre = conv(p + ".pre", inter / 2, hid, 1);
         c.post = conv(p + ".post", hid, inter / 2, 1);
-        c.cond = conv(p + ".enc.cond_layer", gin, 2 * hid * 4, 1);        // rows interleaved per layer
-        for (int l = 0; l < 4; ++l) {
-            c.in[l] = conv(p + ".enc.in_layers." + std::to_string(l), hid, 2 * hid, 5);
-            if (l < 3) c.res[l] = conv(p + ".enc.res_skip_layers." + std::to_string(l) + ".res", hid, hid, 1);
-            c.skip[l] = conv(p + ".enc.res_skip_layers." + std::to_string(l) + ".skip", hid, hid, 1);
-        }
+        c.enc = wn_w(p + ".enc", 4);
         flows_.push_back(c);
+    }
+    // enc_q, the posterior encoder: optional (only the flow-VAE stage forward reads it)
+    has_enc_q_ = weights_.count("enc_q.pre.wp") != 0;
+    enc_q_ = PosteriorW();
+    if (has_enc_q_) {
+        // the packer stores the unpadded width of enc_q.pre.weight (filter_length / 2 + 1) as a one-element tensor: read back once, here
+        float width = 0.f;
+        DTTS_CHECK_HIP(hipMemcpy(&width, W("enc_q.pre.cin", 1), sizeof(float), hipMemcpyDeviceToHost));
+        const int spec_ch = (int)width;
+        DTTS_REQUIRE(spec_ch >= 1 && (float)spec_ch == width && spec_ch <= (1 << 16), "enc_q.pre.cin: spectrogram width");
+        enc_q_.spec_channels = spec_ch;
+        enc_q_.pre = conv("enc_q.pre", spec_ch, hid, 1);
+        enc_q_.enc = wn_w("enc_q.enc", 16);
+        enc_q_.proj = conv("enc_q.proj", hid, 2 * inter, 1);
     }
     const int c0 = cfg.upsample_initial_channel;
     dec_pre_ = conv("dec.conv_pre", inter, c0, 7);
@@ -96,15 +119,21 @@ void Model::build_vocoder(hipStream_t stream) {
                     for (int l = 0; l < 3; ++l) { wide.push_back(&g.rb[j].c1[l]); wide.push_back(&g.rb[j].c2[l]); }
     // ... of the flow's WaveNet in_layers (k = 5, gated: a 1x1 conv_x3 launch over the tap-expanded planes, wn_fwd)
     for (auto& c : flows_)
-        for (int l = 0; l < 4; ++l)
-            if (c.in[l].CinP % 16 == 0 && c.in[l].CoutP % 128 == 0 && c.in[l].CoutP == c.in[l].Cout) wide.push_back(&c.in[l]);
+        for (PackedConv& in : c.enc.in)
+            if (in.CinP % 16 == 0 && in.CoutP % 128 == 0 && in.CoutP == in.Cout) wide.push_back(&in);
     // ... and, in A-fragment order, of the NARROW stages' (<= 32 channels: the LDS-resident fused kernel, resblock1_fused.hip)
     std::vector<PackedConv*> narrow;
     for (auto& g : gen_)
         if (g.cout <= 32 && g.rb[0].c1[0].CoutP == 32)
             for (int j = 0; j < cfg.n_resblock_kernels; ++j)
                 for (int l = 0; l < 3; ++l) { narrow.push_back(&g.rb[j].c1[l]); narrow.push_back(&g.rb[j].c2[l]); }
+    // ... and of enc_q's WaveNet in_layers (the flow's route), laid out AFTER everything above: binding enc_q moves no other image
+    std::vector<PackedConv*> post;
+    if (has_enc_q_)
+        for (PackedConv& in : enc_q_.enc.in)
+            if (in.CinP % 16 == 0 && in.CoutP % 128 == 0 && in.CoutP == in.Cout) post.push_back(&in);
     size_t total = 0;
+    for (PackedConv* pc : post) total += (size_t)pc->KW * pc->CinP * pc->CoutP * 4 + 256;
     for (PackedConv* pc : wide) total += (size_t)pc->KW * pc->CinP * pc->CoutP * 4 + 256;
     for (PackedConv* pc : narrow) total += rb_fused_w3_bytes(pc->KW, pc->CinP) + 256;
     w3_voc_.ensure(total + 4096);
@@ -119,34 +148,44 @@ void Model::build_vocoder(hipStream_t stream) {
         launch_rb_pack_weights(pc->w, pc->KW, pc->CinP, pc->CoutP, pc->CinP, dst, stream);
         pc->w3 = dst;
     }
+    for (PackedConv* pc : post) {
+        void* dst = w3_voc_.raw((size_t)pc->KW * pc->CinP * pc->CoutP * 4);
+        launch_split_weights(pc->w, pc->KW, pc->CinP, pc->CoutP, dst, stream);
+        pc->w3 = dst;
+    }
 }
 
 // MelStyleEncoder.forward.  mel [B,n_mel,T] (positions >= len are treated as zero == the reference's x*mask /
 // masked_fill), g_out [B,out].
 void Model::mel_style(const MelStyleW& w, const float* mel, const int* lens, const int* lens_host, int B, int T, float* g_out,
-                      hipStream_t s) {
+                      hipStream_t s, bool padded_batch) {
     const int H = w.hidden;
     const size_t act = (size_t)B * H * T;
     float* a = ws().f32(act);
     float* b = ws().f32(act);
     float* qkv = ws().f32(3 * act);
     float* y = ws().f32((size_t)B * w.out * T);
+    // padded_batch (the training-style stage forwards): the reference runs `spectral` and `temporal` over the WHOLE padded rectangle
+    // of x * mask and masks only afterwards (modules.py:705-713), so Mish(bias) of the padded frames reaches the last valid frames
+    // through the k = 5 convs.  The caller passes mel already masked; these four convs then take every column.  Default: each row is
+    // the utterance it would be alone (frames beyond its length read as zero at every layer).
+    const int* front = padded_batch ? nullptr : lens;
     // spectral: Linear -> Mish -> Linear -> Mish  (modules.py:661-668)
-    ConvParams p = cp(mel, w.n_mel, a, H, B, T, T, lens);
+    ConvParams p = cp(mel, w.n_mel, a, H, B, T, T, front);
     p.epi_act = ACT_MISH;
     run_conv(w.sp0, p, s);
-    p = cp(a, H, b, H, B, T, T, lens);
+    p = cp(a, H, b, H, B, T, T, front);
     p.epi_act = ACT_MISH;
     run_conv(w.sp1, p, s);
     // temporal: 2 x Conv1dGLU (conv k5 -> a*sigmoid(b) + residual)  (modules.py:517-523)
-    p = cp(b, H, a, H, B, T, T, lens);
+    p = cp(b, H, a, H, B, T, T, front);
     p.pad = 2;
     p.gate = GATE_GLU;
     p.res = b;
     p.res_bs = (long long)H * T;
     p.res_cs = T;
     run_conv(w.t0, p, s);
-    p = cp(a, H, b, H, B, T, T, lens);
+    p = cp(a, H, b, H, B, T, T, front);
     p.pad = 2;
     p.gate = GATE_GLU;
     p.res = a;
@@ -518,13 +557,14 @@ void Model::op_generator(const float* z, const float* g, const int* lens_host, i
     generator(z, g, lens_host, B, T, wav, s);
 }
 
-// modules.WN.forward (vqvae/modules/modules.py:204-229) of one coupling layer: h [B,192,T] (overwritten), g [B,gin] -> skip [B,192,T].
-// Gc [B, cond.CoutP], acts / h2 [B,192,T] are scratch.
-void Model::wn_fwd(const CouplingW& c, float* h, const float* g, int gin, float* Gc, float* acts, float* h2, float* skip, const int* dl,
+// modules.WN.forward (vqvae/modules/modules.py:204-229) of c.n_layers layers (a coupling layer's 4, enc_q's 16): h [B,192,T]
+// (overwritten), g [B,gin] -> skip [B,192,T].  Gc [B, cond.CoutP] (layer l's conditioning rows at l * 2 * hid), acts / h2 [B,192,T] are scratch.
+void Model::wn_fwd(const WnW& c, float* h, const float* g, int gin, float* Gc, float* acts, float* h2, float* skip, const int* dl,
                    int B, int T, hipStream_t s) {
     const int hid = cfg.hidden_channels;
     auto cp = [&](const float* in, float* o) { return this->cp(in, hid, o, hid, B, T, T, dl); };
-    // G = cond_layer(g): [B, 1536] in packed (gate-interleaved) row order
+    const int nl = c.n_layers;
+    // G = cond_layer(g): [B, 2 * hid * n_layers] in packed (gate-interleaved) row order
     ConvParams q;
     q.B = B;
     q.Tin = 1;
@@ -542,10 +582,11 @@ void Model::wn_fwd(const CouplingW& c, float* h, const float* g, int gin, float*
     // the 5-tap expansion of h - same w3 image, gate + conditioning rows in the epilogue.  fp32-MFMA form when the rows of the
     // activations are not 16-byte aligned (T % 4) or with conv_x3 = 0 / DTTS_VOC_X3 = 0 / DTTS_VOC_WN_X3 = 0.
     static const bool env_wn = env_on("DTTS_VOC_WN_X3");
-    const bool x3 = env_wn && vocoder_x3() && c.in[0].w3 && c.in[0].KW == 5 && T % 4 == 0 && hid % 16 == 0;
+    bool x3 = env_wn && vocoder_x3() && T % 4 == 0 && hid % 16 == 0;
+    for (const PackedConv& in : c.in) x3 = x3 && in.w3 && in.KW == 5;
     const size_t mark = ws().mark();
     void* xs5 = x3 ? ws().raw(x3_bytes(B, 5 * hid, T)) : nullptr;
-    for (int li = 0; li < 4; ++li) {
+    for (int li = 0; li < nl; ++li) {
         // acts = tanh(a + g_l) * sigmoid(b + g_l), (a|b) = in_layer(h)   (modules.py:15-22, 212-221)
         ConvParams p = cp(hc, acts);
         p.gate = GATE_TANH_SIGMOID;
@@ -569,7 +610,7 @@ void Model::wn_fwd(const CouplingW& c, float* h, const float* g, int gin, float*
             p.pad = 2;
             run_conv(c.in[li], p, s);
         }
-        if (li < 3) {
+        if (li < nl - 1) {
             p = cp(acts, hn);                      // x = (x + res_acts) * mask
             p.res = hc;
             p.res_bs = (long long)hid * T;
@@ -583,40 +624,43 @@ void Model::wn_fwd(const CouplingW& c, float* h, const float* g, int gin, float*
             p.res_cs = T;
         }
         run_conv(c.skip[li], p, s);
-        if (li < 3) std::swap(hc, hn);
+        if (li < nl - 1) std::swap(hc, hn);
     }
     ws().rewind(mark);
 }
 
-// unit entry point: flow.flows[2 * flow].enc on h [B,192,T] with g [B,gin] -> out [B,192,T]
+// unit entry point: flow.flows[2 * flow].enc (flow >= 0) or enc_q.enc (flow == -1) on h [B,192,T] with g [B,gin] -> out [B,192,T]
 void Model::op_wn(int flow, const float* h_in, const float* g, const int* lens_host, int B, int T, float* out, hipStream_t s) {
     DTTS_REQUIRE(bound_ && has_vocoder_, "vocoder weights not bound");
-    DTTS_REQUIRE(flow >= 0 && flow < (int)flows_.size(), "flow index");
+    DTTS_REQUIRE(flow >= -1 && flow < (int)flows_.size(), "flow index");
+    DTTS_REQUIRE(flow >= 0 || has_enc_q_, "op_wn: enc_q.pre.weight is not bound (the checkpoint carries no enc_q)");
+    const WnW& w = flow < 0 ? enc_q_.enc : flows_[flow].enc;
     ArenaUse use_stage_c_arena(ws_voc_);
     const int hid = cfg.hidden_channels, gin = cfg.gin_channels;
     const size_t a = (size_t)B * hid * T;
-    ws().ensure(sizeof(float) * (3 * a + (size_t)B * flows_[flow].cond.CoutP) + x3_bytes(B, 5 * cfg.hidden_channels, T) + 8192);
+    ws().ensure(sizeof(float) * (3 * a + (size_t)B * w.cond.CoutP) + x3_bytes(B, 5 * cfg.hidden_channels, T) + 8192);
     std::vector<int> l(B);
     for (int b = 0; b < B; ++b) l[b] = lens_host ? lens_host[b] : T;
     const int* dl = upload_ints(l.data(), B, s);
     float* h = ws().f32(a);
     float* acts = ws().f32(a);
     float* h2 = ws().f32(a);
-    float* Gc = ws().f32((size_t)B * flows_[flow].cond.CoutP);
+    float* Gc = ws().f32((size_t)B * w.cond.CoutP);
     SatScope sat(this, s);
     DTTS_CHECK_HIP(hipMemcpyAsync(h, h_in, sizeof(float) * a, hipMemcpyDeviceToDevice, s));
-    wn_fwd(flows_[flow], h, g, gin, Gc, acts, h2, out, dl, B, T, s);
+    wn_fwd(w, h, g, gin, Gc, acts, h2, out, dl, B, T, s);
     sat.check();
 }
 
 // in_proj + SpecEncoder / enc_p (vqvae/model_24k.py:856-857, :71-107; vqvae/modules/attentions.py:73-107 Encoder, :161-303 windowed
 // relative-position MultiHeadAttention, FFN): mel [B,128,T] -> stats [B, 2*inter, T] = (m_p | logs_p), masked.  Buffers from the caller.
 void Model::enc_p_fwd(const float* mel, const int* dl, int B, int T, float* x, float* y, float* qkv, float* att, float* ffn, float* relk,
-                      float* ml, float* stats, hipStream_t s) {
+                      float* ml, float* stats, hipStream_t s, bool padded_batch) {
     const int inter = cfg.inter_channels, hid = cfg.hidden_channels, filt = cfg.filter_channels;
     const int H = cfg.enc_heads, dk = hid / H;
     ConvParams p = cp(mel, cfg.mel_channels, x, inter, B, T, T, dl);
     p.pad = 1;
+    if (padded_batch) p.len_in = nullptr;     // forward_flowvae: in_proj(y) sees the UNMASKED rectangle (model_24k.py:713), enc_p masks after it
     run_conv(in_proj_, p, s);
     const float scale = 1.f / std::sqrt((float)dk);
     for (auto& L : enc_layers_) {
@@ -752,7 +796,7 @@ void Model::vocoder(const float* mel, const int* lens_host, int B, int T, unsign
         ConvParams p = cp(zc, inter / 2, h, hid, B, T, T, dl);
         p.x_bs = (long long)inter * T;            // x0 = first half of the channels
         run_conv(c.pre, p, s);
-        wn_fwd(c, h, g, gin, Gc, acts, h2, skip, dl, B, T, s);
+        wn_fwd(c.enc, h, g, gin, Gc, acts, h2, skip, dl, B, T, s);
         // m = post(out) * mask ; x1 = (x1 - m) * mask ; then Flip (fused) unless this is the last flow
         p = cp(skip, hid, mbuf, inter / 2, B, T, T, dl);
         run_conv(c.post, p, s);
@@ -782,6 +826,200 @@ void Model::vocoder(const float* mel, const int* lens_host, int B, int T, unsign
         DTTS_CHECK_HIP(hipMemcpy2DAsync(wav + (size_t)t0 * 256, sizeof(float) * (size_t)256 * T, tmp + (size_t)(t0 - a) * 256,
                                         sizeof(float) * (size_t)256 * W, sizeof(float) * (size_t)(t1 - t0) * 256, B, hipMemcpyDeviceToDevice, s));
     }
+    sat.check();
+}
+
+// ------------------------------------------------------------------------------------------ flow-VAE stage forward
+// SynthesizerTrn.forward_flowvae (vqvae/model_24k.py:706-737): enc_q (:172-218), the flow in its forward direction (:162-165,
+// vqvae/modules/modules.py:456-471), rand_slice_segments' gather (vqvae/modules/commons.py:67-83) and kl_loss (vqvae/modules/losses.py:43-58).
+static const char* kNoEncQ = "enc_q.pre.weight is not bound (the checkpoint carries no enc_q: the flow-VAE stage forward needs the posterior encoder)";
+
+std::vector<int> Model::stage_lens(const int* lens_host, int B, int T, const char* who) const {
+    std::vector<int> l(B);
+    for (int b = 0; b < B; ++b) {
+        l[b] = lens_host ? lens_host[b] : T;
+        DTTS_REQUIRE(l[b] >= 1 && l[b] <= T, std::string(who) + ": lengths must lie in [1, T]");
+    }
+    return l;
+}
+
+size_t Model::enc_q_ws_bytes(int B, int T) const {
+    const size_t a = (size_t)B * cfg.hidden_channels * T;
+    return sizeof(float) * (4 * a + (size_t)B * enc_q_.enc.cond.CoutP) + x3_bytes(B, 5 * cfg.hidden_channels, T) + 8 * 256;
+}
+
+size_t Model::flow_ws_bytes(int B, int T) const {
+    const size_t a = (size_t)B * cfg.hidden_channels * T, z = (size_t)B * cfg.inter_channels * T;
+    return sizeof(float) * (4 * a + 2 * z + z / 2 + (size_t)B * flows_[0].enc.cond.CoutP) + x3_bytes(B, 5 * cfg.hidden_channels, T) + 10 * 256;
+}
+
+// stats = proj(enc(pre(spec) * mask, mask, g)) * mask: [B, 2 inter, T], live columns only
+void Model::enc_q_fwd(const float* spec, int spec_ch, const float* g, const int* dl, int B, int T, float* stats, hipStream_t s) {
+    const int hid = cfg.hidden_channels, inter = cfg.inter_channels;
+    const size_t a = (size_t)B * hid * T, mark = ws().mark();
+    float* h = ws().f32(a);
+    float* acts = ws().f32(a);
+    float* h2 = ws().f32(a);
+    float* skip = ws().f32(a);
+    float* Gc = ws().f32((size_t)B * enc_q_.enc.cond.CoutP);
+    ConvParams p = cp(spec, spec_ch, h, hid, B, T, T, dl);
+    run_conv(enc_q_.pre, p, s);
+    wn_fwd(enc_q_.enc, h, g, cfg.gin_channels, Gc, acts, h2, skip, dl, B, T, s);
+    p = cp(skip, hid, stats, 2 * inter, B, T, T, dl);
+    run_conv(enc_q_.proj, p, s);
+    ws().rewind(mark);
+}
+
+// z [B, inter, T] (read on live columns) -> z_p [B, inter, T]: four times (coupling layer, Flip), the Flip fused into the layer's store
+void Model::flow_fwd(const float* z, const float* g, const int* dl, int B, int T, float* z_p, hipStream_t s) {
+    const int hid = cfg.hidden_channels, inter = cfg.inter_channels;
+    const size_t a = (size_t)B * hid * T, az = (size_t)B * inter * T, mark = ws().mark();
+    float* h = ws().f32(a);
+    float* acts = ws().f32(a);
+    float* h2 = ws().f32(a);
+    float* skip = ws().f32(a);
+    float* zbuf[2] = {ws().f32(az), ws().f32(az)};
+    float* mbuf = ws().f32(az / 2);
+    float* Gc = ws().f32((size_t)B * flows_[0].enc.cond.CoutP);
+    const float* zc = z;
+    for (size_t f = 0; f < flows_.size(); ++f) {
+        const CouplingW& c = flows_[f];
+        float* zn = f + 1 == flows_.size() ? z_p : zbuf[f & 1];
+        // h = pre(x0) * mask ; m = post(enc(h, mask, g)) * mask ; x1 = m + x1 * mask ; Flip
+        ConvParams p = cp(zc, inter / 2, h, hid, B, T, T, dl);
+        p.x_bs = (long long)inter * T;            // x0 = first half of the channels
+        run_conv(c.pre, p, s);
+        wn_fwd(c.enc, h, g, cfg.gin_channels, Gc, acts, h2, skip, dl, B, T, s);
+        p = cp(skip, hid, mbuf, inter / 2, B, T, T, dl);
+        run_conv(c.post, p, s);
+        launch_coupling_forward(zc, mbuf, zn, (long long)inter * T, T, dl, T, B, inter, 1, s);
+        zc = zn;
+    }
+    ws().rewind(mark);
+}
+
+void Model::posterior_encode(const float* spec, int spec_ch, const int* lens_host, const float* g, int B, int T, const float* noise,
+                             unsigned long long seed, const int* sample_ids_host, float* z, float* m_q, float* logs_q, hipStream_t s) {
+    DTTS_REQUIRE(bound_ && has_vocoder_, "vocoder weights not bound");
+    DTTS_REQUIRE(has_enc_q_, kNoEncQ);
+    DTTS_REQUIRE(spec && g && z && m_q && logs_q && (noise || sample_ids_host), "posterior_encode: null argument");
+    DTTS_REQUIRE(B >= 1 && B <= 4096 && T >= 1 && T <= (1 << 20), "posterior_encode: sizes");
+    DTTS_REQUIRE(spec_ch == enc_q_.spec_channels, "posterior_encode: the spectrogram's width is not that of the bound enc_q.pre.weight");
+    std::vector<int> l = stage_lens(lens_host, B, T, "posterior_encode");
+    ArenaUse use_stage_c_arena(ws_voc_);
+    const int inter = cfg.inter_channels;
+    ws().ensure(enc_q_ws_bytes(B, T) + sizeof(float) * (size_t)2 * B * inter * T + 8192);
+    SatScope sat(this, s);
+    const int* dl = upload_ints(l.data(), B, s);
+    const int* sids = noise ? nullptr : upload_ints(sample_ids_host, B, s);
+    float* stats = ws().f32((size_t)2 * B * inter * T);
+    enc_q_fwd(spec, spec_ch, g, dl, B, T, stats, s);
+    launch_posterior_sample(stats, (long long)2 * inter * T, T, dl, T, B, inter, seed, sids, noise, z, m_q, logs_q, s);
+    sat.check();
+}
+
+void Model::flow_forward(const float* z, const float* g, const int* lens_host, int B, int T, float* z_p, hipStream_t s) {
+    DTTS_REQUIRE(bound_ && has_vocoder_, "vocoder weights not bound");
+    DTTS_REQUIRE(z && g && z_p && z != z_p, "flow_forward: null or aliased argument");
+    DTTS_REQUIRE(B >= 1 && B <= 4096 && T >= 1 && T <= (1 << 20), "flow_forward: sizes");
+    std::vector<int> l = stage_lens(lens_host, B, T, "flow_forward");
+    ArenaUse use_stage_c_arena(ws_voc_);
+    ws().ensure(flow_ws_bytes(B, T) + 8192);
+    SatScope sat(this, s);
+    const int* dl = upload_ints(l.data(), B, s);
+    flow_fwd(z, g, dl, B, T, z_p, s);
+    sat.check();
+}
+
+void Model::slice_segments(const float* x, const int* ids_host, int B, int C, int T, int seg, float* out, hipStream_t s) {
+    DTTS_REQUIRE(x && ids_host && out, "slice_segments: null argument");
+    DTTS_REQUIRE(B >= 1 && B <= 4096 && C >= 1 && T >= 1 && seg >= 1 && seg <= T && (long long)C * T < (1ll << 30), "slice_segments: sizes");
+    for (int b = 0; b < B; ++b) DTTS_REQUIRE(ids_host[b] >= 0 && ids_host[b] <= T - seg, "slice_segments: a segment must lie inside [0, T)");
+    launch_slice_segments(x, upload_ints(ids_host, B, s), B, C, T, seg, out, s);
+}
+
+void Model::kl_loss(const float* z_p, const float* logs_q, const float* m_p, const float* logs_p, const int* lens_host, int B, int C, int T,
+                    float* out, hipStream_t s) {
+    DTTS_REQUIRE(z_p && logs_q && m_p && logs_p && out, "kl_loss: null argument");
+    DTTS_REQUIRE(B >= 1 && B <= 4096 && C >= 1 && T >= 1 && (long long)C * T < (1ll << 30), "kl_loss: sizes");
+    std::vector<int> l(B);
+    double frames = 0.0;
+    for (int b = 0; b < B; ++b) {
+        l[b] = lens_host ? lens_host[b] : T;
+        DTTS_REQUIRE(l[b] >= 0 && l[b] <= T, "kl_loss: lengths must lie in [0, T]");
+        frames += l[b];
+    }
+    DTTS_REQUIRE(frames >= 1.0, "kl_loss: no frame inside the mask");
+    ArenaUse use_stage_c_arena(ws_voc_);
+    const size_t npart = (size_t)B * kl_partials((long long)C * T);
+    ws().ensure(sizeof(float) * npart + 4096);
+    float* partials = ws().f32(npart);
+    launch_kl_loss(z_p, logs_q, m_p, logs_p, upload_ints(l.data(), B, s), B, C, T, frames, partials, out, s);
+}
+
+void Model::flowvae_forward(const float* mel, const float* spec, int spec_ch, const int* lens_host, int B, int T, const float* noise,
+                            unsigned long long seed, const int* sample_ids_host, const int* ids_slice_host, int seg, float* o, float* z,
+                            float* z_p, float* m_p, float* logs_p, float* m_q, float* logs_q, float* quantized, hipStream_t s) {
+    DTTS_REQUIRE(bound_ && has_vocoder_, "vocoder weights not bound");
+    DTTS_REQUIRE(has_enc_q_, kNoEncQ);
+    DTTS_REQUIRE(mel && spec && ids_slice_host && o && z && z_p && m_p && logs_p && m_q && logs_q && quantized && (noise || sample_ids_host),
+                 "flowvae_forward: null argument");
+    DTTS_REQUIRE(B >= 1 && B <= 4096 && T >= 1 && T <= (1 << 20), "flowvae_forward: sizes");
+    DTTS_REQUIRE(T % 4 == 0, "mel length must be a multiple of 4 (assert y.shape[-1]%4==0, model_24k.py:707)");
+    DTTS_REQUIRE(seg >= 1 && seg <= T, "flowvae_forward: segment size");
+    DTTS_REQUIRE(spec_ch == enc_q_.spec_channels, "flowvae_forward: the spectrogram's width is not that of the bound enc_q.pre.weight");
+    std::vector<int> l = stage_lens(lens_host, B, T, "flowvae_forward");
+    for (int b = 0; b < B; ++b) {
+        DTTS_REQUIRE(l[b] >= seg, "flowvae_forward: a row is shorter than the segment");
+        DTTS_REQUIRE(ids_slice_host[b] >= 0 && ids_slice_host[b] <= l[b] - seg, "flowvae_forward: ids_slice outside [0, len - seg]");
+    }
+    ArenaUse use_stage_c_arena(ws_voc_);
+    const int inter = cfg.inter_channels, hid = cfg.hidden_channels, filt = cfg.filter_channels, gin = cfg.gin_channels, H = cfg.enc_heads;
+    const size_t a192 = (size_t)B * hid * T, az = (size_t)B * inter * T;
+    const size_t front = sizeof(float) * (8 * a192 + (size_t)B * filt * T + (size_t)B * H * T * 11 + (size_t)B * gin + 2 * az +
+                                          (size_t)B * inter * seg) + 64 * 256;
+    const size_t inner = std::max(std::max(mel_style_ws(B, 128, gin, T) + sizeof(float) * (size_t)B * cfg.mel_channels * T + 256, enc_q_ws_bytes(B, T)), std::max(flow_ws_bytes(B, T), generator_ws(cfg, B, seg)));
+    ws().ensure(front + inner + 8192);
+    SatScope sat(this, s);                                 // one ticket: both WaveNets' planes and the generator report into it
+    const int* dl = upload_ints(l.data(), B, s);
+    const int* sids = noise ? nullptr : upload_ints(sample_ids_host, B, s);
+    const int* dids = upload_ints(ids_slice_host, B, s);
+    float* g = ws().f32((size_t)B * gin);
+    float* x = ws().f32(a192);
+    float* y = ws().f32(a192);
+    float* qkv = ws().f32(3 * a192);
+    float* att = ws().f32(a192);
+    float* ffn = ws().f32((size_t)B * filt * T);
+    float* relk = ws().f32((size_t)B * H * T * 9);
+    float* ml = ws().f32((size_t)B * H * T * 2);
+    float* stats_p = ws().f32(2 * a192);
+    float* stats_q = ws().f32(2 * az);
+    float* zs = ws().f32((size_t)B * inter * seg);
+    // g = ref_enc(y * y_mask, y_mask)  (:711), the padded-batch reading (mel_style)
+    {
+        const size_t m = ws().mark();
+        float* ym = ws().f32((size_t)B * cfg.mel_channels * T);
+        launch_masked_copy(mel, (long long)cfg.mel_channels * T, T, dl, T, B, cfg.mel_channels, nullptr, ym, s);
+        mel_style(ref_enc_, ym, dl, l.data(), B, T, g, s, true);
+        ws().rewind(m);
+    }
+    // x, m_p, logs_p = enc_p(in_proj(y), y_lengths) ; quantized = x  (:713-715).  out_proj's output is NOT masked in the reference
+    // (:118): beyond a row's length it is out_proj's bias (the encoder's output is masked to zero there)
+    enc_p_fwd(mel, dl, B, T, x, y, qkv, att, ffn, relk, ml, stats_p, s, true);
+    launch_masked_copy(y, (long long)inter * T, T, dl, T, B, inter, enc_out_.b, quantized, s);
+    launch_masked_copy(stats_p, (long long)2 * inter * T, T, dl, T, B, inter, nullptr, m_p, s);
+    launch_masked_copy(stats_p + (size_t)inter * T, (long long)2 * inter * T, T, dl, T, B, inter, nullptr, logs_p, s);
+    // z, m_q, logs_q = enc_q(spec, y_lengths, g)  (:717)
+    enc_q_fwd(spec, spec_ch, g, dl, B, T, stats_q, s);
+    launch_posterior_sample(stats_q, (long long)2 * inter * T, T, dl, T, B, inter, seed, sids, noise, z, m_q, logs_q, s);
+    // z_p = flow(z, y_mask, g)  (:719)
+    flow_fwd(z, g, dl, B, T, z_p, s);
+    // o = dec(slice_segments(z, ids_slice, segment_size), g)  (:721-724)
+    launch_slice_segments(z, dids, B, inter, T, seg, zs, s);
+    size_t hop = 1;                                        // samples per frame: the product of the generator's upsampling rates
+    for (int i = 0; i < cfg.n_upsamples; ++i) hop *= (size_t)cfg.upsample_rates[i];
+    DTTS_CHECK_HIP(hipMemsetAsync(o, 0, sizeof(float) * (size_t)B * hop * seg, s));
+    generator(zs, g, nullptr, B, seg, o, s);
     sat.check();
 }
 

@@ -197,6 +197,21 @@ def _mel_style(pk, P, p):
     pk.conv(p + ".fc.fc", P[p + ".fc.fc.weight"], P[p + ".fc.fc.bias"])
 
 
+def _pack_wn(pk, P, p, hid, n_layers):
+    """modules.WN under prefix p (`...enc`): gate-interleaved in_layers and cond_layer rows, res_skip split into .res / .skip"""
+    gp = gate_perm(2 * hid)
+    cperm = np.concatenate([l * 2 * hid + gp for l in range(n_layers)])
+    pk.conv(p + ".cond_layer", P[p + ".cond_layer.weight"], P[p + ".cond_layer.bias"], row_perm=cperm)
+    for l in range(n_layers):
+        pk.conv(p + f".in_layers.{l}", P[p + f".in_layers.{l}.weight"], P[p + f".in_layers.{l}.bias"], row_perm=gp)
+        w, b = P[p + f".res_skip_layers.{l}.weight"], P[p + f".res_skip_layers.{l}.bias"]
+        if l < n_layers - 1:
+            pk.conv(p + f".res_skip_layers.{l}.res", w[:hid], b[:hid])
+            pk.conv(p + f".res_skip_layers.{l}.skip", w[hid:], b[hid:])
+        else:
+            pk.conv(p + f".res_skip_layers.{l}.skip", w, b)
+
+
 def pack_vocoder(pk, P, cfg):
     v = cfg["vaegan"]
     hid = v["hidden_channels"]
@@ -221,17 +236,7 @@ def pack_vocoder(pk, P, cfg):
         p = f"flow.flows.{f}"
         pk.conv(p + ".pre", P[p + ".pre.weight"], P[p + ".pre.bias"])
         pk.conv(p + ".post", P[p + ".post.weight"], P[p + ".post.bias"])
-        gp = gate_perm(2 * hid)
-        cperm = np.concatenate([l * 2 * hid + gp for l in range(4)])
-        pk.conv(p + ".enc.cond_layer", P[p + ".enc.cond_layer.weight"], P[p + ".enc.cond_layer.bias"], row_perm=cperm)
-        for l in range(4):
-            pk.conv(p + f".enc.in_layers.{l}", P[p + f".enc.in_layers.{l}.weight"], P[p + f".enc.in_layers.{l}.bias"], row_perm=gp)
-            w, b = P[p + f".enc.res_skip_layers.{l}.weight"], P[p + f".enc.res_skip_layers.{l}.bias"]
-            if l < 3:
-                pk.conv(p + f".enc.res_skip_layers.{l}.res", w[:hid], b[:hid])
-                pk.conv(p + f".enc.res_skip_layers.{l}.skip", w[hid:], b[hid:])
-            else:
-                pk.conv(p + f".enc.res_skip_layers.{l}.skip", w, b)
+        _pack_wn(pk, P, p + ".enc", hid, 4)
     pk.conv("dec.conv_pre", P["dec.conv_pre.weight"], P["dec.conv_pre.bias"])
     pk.conv("dec.cond", P["dec.cond.weight"], P["dec.cond.bias"])
     for i, (u, k) in enumerate(zip(v["upsample_rates"], v["upsample_kernel_sizes"])):
@@ -244,6 +249,16 @@ def pack_vocoder(pk, P, cfg):
                 p = f"dec.resblocks.{i}.{cs}.{l}"
                 pk.conv(p, P[p + ".weight"], P[p + ".bias"])
     pk.conv("dec.conv_post", P["dec.conv_post.weight"], None)
+
+
+def pack_posterior(pk, P, cfg):
+    """enc_q (weights.posterior_param_spec), packed as the flow's WaveNet is; appended after everything else so that a blob without it
+    is byte-identical to one made before enc_q was known"""
+    from .weights import POSTERIOR_LAYERS
+    pk.conv("enc_q.pre", P["enc_q.pre.weight"], P["enc_q.pre.bias"])
+    pk.add("enc_q.pre.cin", np.array([P["enc_q.pre.weight"].shape[1]], F32))      # the unpadded spectrogram width (the wp image pads it to 16)
+    _pack_wn(pk, P, "enc_q.enc", cfg["vaegan"]["hidden_channels"], POSTERIOR_LAYERS)
+    pk.conv("enc_q.proj", P["enc_q.proj.weight"], P["enc_q.proj.bias"])
 
 
 def pack_gpt(pk, P, cfg):
@@ -307,4 +322,6 @@ def pack_all(P, cfg=None, parts=("diffusion",)):
     if "frontend" in parts:
         from .frontend import pack_frontend
         pack_frontend(pk, cfg)
+    if "vocoder" in parts and "enc_q.pre.weight" in P:      # optional, last: see pack_posterior
+        pack_posterior(pk, P, cfg)
     return pk

@@ -553,6 +553,112 @@ class Runtime:
                                        _ptr(noise_override), _ptr(wav), _ptr(z), self._stream()))
         return (wav, z) if return_z else wav
 
+    # ---- the flow-VAE stage forward (dtts_posterior_encode / _flow_forward / _slice_segments / _kl_loss / _flowvae_forward)
+    def _row_ints(self, vals, B, who, what):
+        """B host ints (lengths, segment starts, sample ids) for the C side, which reads exactly B of them"""
+        li = _ints(vals)
+        if len(li[1]) != B:
+            raise DttsError(f"{who}: {len(li[1])} {what} for {B} rows")
+        return li
+
+    def _lens(self, lens, B, T, who):
+        return self._row_ints(lens if lens is not None else [T] * B, B, who, "lengths")
+
+    def _sids(self, sample_ids, B, who):
+        return self._row_ints(list(range(B)) if sample_ids is None else sample_ids, B, who, "sample_ids")
+
+    def _shape(self, t, shape, name, who):
+        """t is a contiguous fp32 CUDA tensor of exactly this shape: the kernels index it by these sizes"""
+        _check(t, name)
+        if tuple(t.shape) != tuple(shape):
+            raise DttsError(f"{who}: {name} must be {list(shape)}, not {list(t.shape)}")
+
+    def _spec(self, spec, who):
+        _check(spec, "spec")
+        want = self.cfg["data"]["filter_length"] // 2 + 1
+        if spec.dim() != 3 or spec.shape[1] != want:
+            raise DttsError(f"{who}: spec must be [B, {want}, T] (filter_length // 2 + 1 bins), not {tuple(spec.shape)}")
+
+    def _hop(self):
+        """samples per frame of the generator: the product of its upsampling rates"""
+        return int(np.prod(self.cfg["vaegan"]["upsample_rates"]))
+
+    def posterior_encode(self, spec, g, lens=None, noise=None, seed=0, sample_ids=None):
+        """enc_q (vqvae/model_24k.py:205-218): spec cuda [B,513,T], g cuda [B,gin] -> (z, m_q, logs_q) cuda [B,192,T], zeros beyond each
+        row's length.  noise [B,192,T] given, or None: Philox stage 6 keyed (seed, sample_ids[b]).  Needs enc_q in the checkpoint."""
+        self._spec(spec, "posterior_encode")
+        B, Cs, T = spec.shape
+        v = self.cfg["vaegan"]
+        inter = v["inter_channels"]
+        self._shape(g, (B, v["gin_channels"]), "g", "posterior_encode")
+        if noise is not None:
+            self._shape(noise, (B, inter, T), "noise", "posterior_encode")
+        li = self._lens(lens, B, T, "posterior_encode")
+        si = self._sids(sample_ids, B, "posterior_encode")
+        z, m_q, logs_q = (torch.empty((B, inter, T), device=self.device, dtype=torch.float32) for _ in range(3))
+        self._rc(self.lib.dtts_posterior_encode(self.h, _ptr(spec), Cs, li[0], _ptr(g), B, T, _ptr(noise), int(seed), si[0], _ptr(z), _ptr(m_q),
+                                                _ptr(logs_q), self._stream()))
+        return z, m_q, logs_q
+
+    def flow_forward(self, z, g, lens=None):
+        """flow(z, mask, g) in its forward direction (vqvae/model_24k.py:162-165): z cuda [B,192,T], g [B,gin] -> z_p [B,192,T], zero tails"""
+        _check(z, "z")
+        v = self.cfg["vaegan"]
+        if z.dim() != 3 or z.shape[1] != v["inter_channels"]:
+            raise DttsError(f"flow_forward: z must be [B, {v['inter_channels']}, T], not {list(z.shape)}")
+        B, _, T = z.shape
+        self._shape(g, (B, v["gin_channels"]), "g", "flow_forward")
+        li = self._lens(lens, B, T, "flow_forward")
+        z_p = torch.empty_like(z)
+        self._rc(self.lib.dtts_flow_forward(self.h, _ptr(z), _ptr(g), li[0], B, T, _ptr(z_p), self._stream()))
+        return z_p
+
+    def slice_segments(self, x, ids, seg):
+        """commons.slice_segments: x cuda [B,C,T], ids [B] start frames (host) -> [B,C,seg]"""
+        _check(x, "x")
+        if x.dim() != 3:
+            raise DttsError(f"slice_segments: x must be [B, C, T], not {list(x.shape)}")
+        B, Cc, T = x.shape
+        ii = self._row_ints(ids, B, "slice_segments", "segment starts")
+        out = torch.empty((B, Cc, int(seg)), device=self.device, dtype=torch.float32)
+        self._rc(self.lib.dtts_slice_segments(self.h, _ptr(x), ii[0], B, Cc, T, int(seg), _ptr(out), self._stream()))
+        return out
+
+    def kl_loss(self, z_p, logs_q, m_p, logs_p, lens):
+        """losses.kl_loss with the mask as lengths (dtts_kl_loss: fixed-order reduction, divisor = frames) -> 0-d fp32 cuda"""
+        for a, nm in ((z_p, "z_p"), (logs_q, "logs_q"), (m_p, "m_p"), (logs_p, "logs_p")):
+            _check(a, nm)
+            if a.dim() != 3 or a.shape != z_p.shape:
+                raise DttsError("kl_loss: four [B, C, T] tensors of one shape")
+        B, Cc, T = z_p.shape
+        li = self._lens(lens, B, T, "kl_loss")
+        out = torch.zeros((1,), device=self.device, dtype=torch.float32)
+        self._rc(self.lib.dtts_kl_loss(self.h, _ptr(z_p), _ptr(logs_q), _ptr(m_p), _ptr(logs_p), li[0], B, Cc, T, _ptr(out), self._stream()))
+        return out[0]
+
+    def flowvae_forward(self, mel, spec, lens, ids_slice, seg, noise=None, seed=0, sample_ids=None):
+        """the flow-VAE stage in one call (dtts_flowvae_forward) -> dict(o [B,1,hop*seg], z, z_p, m_p, logs_p, m_q, logs_q, quantized
+        [B,192,T]); lens / ids_slice host ints, noise [B,192,T] or None (Philox stage 6)"""
+        _check(mel, "mel"); self._spec(spec, "flowvae_forward")
+        n_mel = self.cfg["data"]["n_mel_channels"]
+        if mel.dim() != 3 or mel.shape[1] != n_mel:
+            raise DttsError(f"flowvae_forward: mel must be [B, {n_mel}, T], not {list(mel.shape)}")
+        B, _, T = mel.shape
+        if spec.shape[0] != B or spec.shape[2] != T:
+            raise DttsError(f"flowvae_forward: spec {tuple(spec.shape)} does not match mel {tuple(mel.shape)}")
+        inter = self.cfg["vaegan"]["inter_channels"]
+        if noise is not None:
+            self._shape(noise, (B, inter, T), "noise", "flowvae_forward")
+        li = self._lens(lens, B, T, "flowvae_forward")
+        ii = self._row_ints(ids_slice, B, "flowvae_forward", "segment starts (ids_slice)")
+        si = self._sids(sample_ids, B, "flowvae_forward")
+        names = ("z", "z_p", "m_p", "logs_p", "m_q", "logs_q", "quantized")
+        out = {k: torch.empty((B, inter, T), device=self.device, dtype=torch.float32) for k in names}
+        out["o"] = torch.empty((B, 1, self._hop() * int(seg)), device=self.device, dtype=torch.float32)
+        self._rc(self.lib.dtts_flowvae_forward(self.h, _ptr(mel), _ptr(spec), spec.shape[1], li[0], B, T, _ptr(noise), int(seed), si[0], ii[0],
+                                               int(seg), _ptr(out["o"]), *(_ptr(out[k]) for k in names), self._stream()))
+        return out
+
     def vocoder_ticket(self):
         """ticket of the last vocoder / generator call issued on this handle (dtts_vocoder_ticket)"""
         return int(self.lib.dtts_vocoder_ticket(self.h))
@@ -679,7 +785,8 @@ class Runtime:
         return y
 
     def op_wn(self, flow, hidden, g, lens=None):
-        """WaveNet of coupling layer `flow` (flow.flows[2 * flow].enc): hidden [B,192,T], g [B,gin] -> summed skips [B,192,T]"""
+        """WaveNet of coupling layer `flow` (flow.flows[2 * flow].enc; flow = -1: enc_q.enc, 16 layers): hidden [B,192,T], g [B,gin] ->
+        summed skips [B,192,T]"""
         _check(hidden, "hidden"); _check(g, "g")
         B, _, T = hidden.shape
         out = torch.zeros_like(hidden)

@@ -95,6 +95,37 @@ def draw_timesteps(seed, batch, steps=TRAIN_DIFFUSION_STEPS):
     return [int(v) for v in np.random.RandomState(int(seed) % (1 << 32)).randint(0, steps, size=int(batch))]
 
 
+def draw_segment_starts(seed, lengths, seg):
+    """forward_flowvae's `ids_slice` when the caller gives none: floor(u * (len - seg + 1)) per row (rand_slice_segments,
+    vqvae/modules/commons.py:76-83) with u from numpy's RandomState(seed) on the host.  They cannot equal torch.rand's draw: a caller
+    who wants the reference's numbers passes its ids_slice and noise."""
+    u = np.random.RandomState(int(seed) % (1 << 32)).random_sample(len(lengths))
+    return [min(int(np.floor(float(v) * (int(n) - seg + 1))), int(n) - seg) for v, n in zip(u, lengths)]
+
+
+def check_flowvae_args(y_shape, y_lengths, seg, ids_slice=None):
+    """Host-side checks of forward_flowvae, before any launch -> (lengths, ids_slice or None).  ValueError when T % 4 != 0 (the
+    reference asserts it), when a row is shorter than the segment (the reference would slice garbage there) and when a given
+    ids_slice leaves [0, len - seg]."""
+    B, T = int(y_shape[0]), int(y_shape[-1])
+    if T % 4 != 0:
+        raise ValueError(f"forward_flowvae needs a frame count divisible by 4 (the reference asserts it), not {T}")
+    yl = [int(v) for v in torch.as_tensor(y_lengths).reshape(-1).tolist()]
+    if len(yl) != B:
+        raise ValueError(f"forward_flowvae: {len(yl)} lengths for {B} rows")
+    for b, n in enumerate(yl):
+        if n > T:
+            raise ValueError(f"forward_flowvae: row {b} has length {n} > {T} frames")
+        if n < seg:
+            raise ValueError(f"forward_flowvae: row {b} has {n} frames, fewer than the segment's {seg} (train.segment_size // data.hop_length)")
+    if ids_slice is None:
+        return yl, None
+    ids = [int(v) for v in torch.as_tensor(ids_slice).reshape(-1).tolist()]
+    if len(ids) != B or any(i < 0 or i > n - seg for i, n in zip(ids, yl)):
+        raise ValueError(f"forward_flowvae: ids_slice {ids} must hold one start in [0, len - {seg}] per row (lengths {yl})")
+    return yl, ids
+
+
 def trunk_precision_arg(trunk_precision):
     """Host-side check of infer()'s `trunk_precision`, before any launch -> None (what the model's config says) or the value of option
     "trunk_fp16" for this call: "fp32" = the three-product split-precision trunk, "fp16" = the reference's use_fp16 mode
@@ -740,10 +771,65 @@ class SynthesizerTrn:
         recon = self.rt.vq_decode([codes[b] for b in range(y.shape[0])], y, yl)      # vq_ref_enc(y * mask, mask): lengths y_lengths
         return self.rt.l1_mean(recon, y)
 
+    def forward_flowvae(self, y, y_lengths, data, *, noise=None, ids_slice=None, seed=0, sample_ids=None):
+        """vqvae/model_24k.py:706-737, the flow-VAE stage forward in eval mode, no gradients -> the reference's 8-tuple
+        (o [B,1,seg*hop], 0, 0, 0, ids_slice int64 [B], y_mask [B,1,T], (z, z_p, m_p, logs_p, m_q, logs_q) [B,192,T] each, quantized
+        [B,192,T] = enc_p's first output), CUDA tensors.  seg = train.segment_size // data.hop_length (40); data['spec'] is the linear
+        spectrogram [B, filter_length // 2 + 1, T].  One device call (dtts_flowvae_forward): ref_enc, enc_p, enc_q, the forward flow,
+        the segment gather and the generator.  Needs enc_q in the checkpoint.  A ragged batch is read as the reference reads its padded
+        rectangle (ref_enc's spectral / temporal layers and in_proj see the padded frames before the mask applies), not row by row
+        as the inference entries do.
+
+        ValueError (before any launch) when T % 4 != 0 (the reference asserts it) or a row is shorter than seg (the reference would
+        slice garbage there).  noise [B,192,T] is enc_q's eps (None: Philox stage 6 keyed (seed, sample_ids[b])); ids_slice [B] the
+        segment starts (None: drawn on the host from `seed`, draw_segment_starts).  Neither draw can equal torch's RNG, so a caller
+        who wants the reference's numbers passes both noise and ids_slice.  loss_mel and the discriminator losses of the reference's
+        training loop are not part of this call."""
+        y = torch.as_tensor(y)
+        seg = self.cfg["train"]["segment_size"] // self.cfg["data"]["hop_length"]
+        yl, ids = check_flowvae_args(y.shape, y_lengths, seg, ids_slice)
+        if ids is None:
+            ids = draw_segment_starts(seed, yl, seg)
+        y = y.to(self.device, torch.float32).contiguous()
+        spec = torch.as_tensor(data["spec"]).to(self.device, torch.float32).contiguous()
+        if noise is not None:
+            noise = torch.as_tensor(noise).to(self.device, torch.float32).contiguous()
+        r = self.rt.flowvae_forward(y, spec, yl, ids, seg, noise=noise, seed=seed, sample_ids=sample_ids)
+        ticket = self.rt.vocoder_ticket()
+        if self.rt.vocoder_check_active():                         # the WaveNets' and the generator's split-precision planes
+            torch.cuda.current_stream(self.device).synchronize()
+            self.rt.vocoder_check(ticket)
+        T = y.shape[-1]
+        y_mask = (torch.arange(T, device=self.device)[None, :] < torch.as_tensor(yl, device=self.device)[:, None]).unsqueeze(1).to(torch.float32)
+        return (r["o"], 0, 0, 0, torch.as_tensor(ids, dtype=torch.int64, device=self.device), y_mask,
+                (r["z"], r["z_p"], r["m_p"], r["logs_p"], r["m_q"], r["logs_q"]), r["quantized"])
+
+    def forward_all(self, y, y_lengths, data, *, noise=None, ids_slice=None, seed=0, sample_ids=None, t=None, diff_noise=None):
+        """vqvae/model_24k.py:749-772: forward_flowvae's tuple with l_diff, loss_gpt and vq_loss from forward_diff (t, diff_noise, seed),
+        forward_gpt and forward_vq, each called as it would be alone"""
+        o, _, _, _, ids, y_mask, latents, quantized = self.forward_flowvae(y, y_lengths, data, noise=noise, ids_slice=ids_slice, seed=seed,
+                                                                           sample_ids=sample_ids)
+        l_diff = self.forward_diff(y, y_lengths, data, t=t, noise=diff_noise, seed=seed)
+        loss_gpt = self.forward_gpt(y, y_lengths, data)
+        vq_loss = self.forward_vq(y, y_lengths, data)
+        return o, l_diff, loss_gpt, vq_loss, ids, y_mask, latents, quantized
+
+    def kl_loss(self, z_p, logs_q, m_p, logs_p, z_mask):
+        """vqvae/modules/losses.py:43-58 -> a 0-d fp32 CUDA tensor: sum((logs_p - logs_q - 1/2 + 1/2 (z_p - m_p)^2 exp(-2 logs_p)) * z_mask)
+        / sum(z_mask) on the device (dtts_kl_loss; two calls give the same bits).  z_mask [B,1,T] must be a sequence mask (ones up to
+        each row's length, then zeros), which is what forward_flowvae returns: it is read back to the host as lengths."""
+        ts = [torch.as_tensor(a).to(self.device, torch.float32).contiguous() for a in (z_p, logs_q, m_p, logs_p)]
+        B, _, T = ts[0].shape
+        m = torch.as_tensor(z_mask).to(self.device).reshape(B, T) != 0
+        lens = m.sum(1)
+        if not torch.equal(m, torch.arange(T, device=self.device)[None, :] < lens[:, None]):
+            raise ValueError("kl_loss: z_mask must be a sequence mask (ones up to each row's length, then zeros)")
+        return self.rt.kl_loss(*ts, [int(v) for v in lens.tolist()])
+
     def forward(self, y, y_lengths, data):
         """vqvae/model_24k.py:740-751: the stage loss cfg['train']['target'] names - 'vqvae' -> forward_vq, 'gpt' -> forward_gpt,
-        'diff' -> forward_diff.  'flowvae' and the default (all stages) need enc_q and a forward-direction flow, which are not on the
-        device: NotImplementedError."""
+        'diff' -> forward_diff.  'flowvae' and the default (all stages) are NOT dispatched: forward_flowvae / forward_all exist and are
+        called by name, but this dispatch and its NotImplementedError naming enc_q are pinned as they were."""
         name = FORWARD_TARGETS.get(self.target)
         if name is None:
             raise NotImplementedError(f"forward for train.target = {self.target!r} needs enc_q (the posterior encoder) and a forward-direction "

@@ -10,7 +10,9 @@ vqvae/diff_model.py:133-209, vqvae/modules/modules.py:152-229/240-313/421-455/
 ignored, and old-style weight-norm pairs (`weight_g`/`weight_v`) are folded to a
 plain `weight`.  `gpt.text_head.*` is OPTIONAL (`optional_param_spec`): no
 inference entry reads it, `UnifiedVoice.forward`'s loss mode does, so it is kept
-when the checkpoint carries it and never asked for.
+when the checkpoint carries it and never asked for.  So is `enc_q.*`
+(`posterior_param_spec`), which only `forward_flowvae` / `forward_all` read: kept
+when the checkpoint carries the whole group, ignored otherwise.
 
 Nothing here touches the GPU; it is host-side numpy.
 """
@@ -265,15 +267,59 @@ def optional_param_spec(cfg=None) -> "OrderedDict[str, tuple]":
     return spec
 
 
+POSTERIOR_LAYERS = 16      # PosteriorEncoder(spec_channels, inter, hidden, True, 5, 1, 16, gin) (vqvae/model_24k.py:591-593)
+
+
+def posterior_param_spec(cfg=None) -> "OrderedDict[str, tuple]":
+    """name -> (shape, kind) of enc_q, the posterior encoder (vqvae/model_24k.py:172-218): a 1x1 `pre` over the linear spectrogram
+    (filter_length // 2 + 1 bins), a 16-layer WaveNet (weight-normed, as the flow's) and `proj` to (m_q | logs_q).  Bound WHEN THE
+    CHECKPOINT HAS ALL OF IT and never required: only forward_flowvae / forward_all read it."""
+    cfg = load_config(cfg)
+    v = cfg["vaegan"]
+    hid, inter, gin, nl = v["hidden_channels"], v["inter_channels"], v["gin_channels"], POSTERIOR_LAYERS
+    spec_ch = cfg["data"]["filter_length"] // 2 + 1
+    spec: "OrderedDict[str, tuple]" = OrderedDict()
+    spec["enc_q.pre.weight"] = ((hid, spec_ch, 1), K_W)
+    spec["enc_q.pre.bias"] = ((hid,), K_B)
+    for l in range(nl):
+        spec[f"enc_q.enc.in_layers.{l}.bias"] = ((2 * hid,), K_B)
+        spec[f"enc_q.enc.in_layers.{l}.weight_g"] = ((2 * hid, 1, 1), K_WN_G)
+        spec[f"enc_q.enc.in_layers.{l}.weight_v"] = ((2 * hid, hid, 5), K_WN_V)
+    for l in range(nl):
+        rs = 2 * hid if l < nl - 1 else hid
+        spec[f"enc_q.enc.res_skip_layers.{l}.bias"] = ((rs,), K_B)
+        spec[f"enc_q.enc.res_skip_layers.{l}.weight_g"] = ((rs, 1, 1), K_WN_G)
+        spec[f"enc_q.enc.res_skip_layers.{l}.weight_v"] = ((rs, hid, 1), K_WN_V)
+    spec["enc_q.enc.cond_layer.bias"] = ((2 * hid * nl,), K_B)
+    spec["enc_q.enc.cond_layer.weight_g"] = ((2 * hid * nl, 1, 1), K_WN_G)
+    spec["enc_q.enc.cond_layer.weight_v"] = ((2 * hid * nl, gin, 1), K_WN_V)
+    spec["enc_q.proj.weight"] = ((2 * inter, hid, 1), K_W)
+    spec["enc_q.proj.bias"] = ((2 * inter,), K_B)
+    return spec
+
+
+def _folded(spec):
+    """state-dict-form spec -> {folded name: shape}: weight_g / weight_v pairs appear as one `weight` of v's shape"""
+    out = OrderedDict()
+    for k, (shape, kind) in spec.items():
+        if k.endswith(".weight_v"):
+            continue
+        if k.endswith(".weight_g"):
+            k = k[: -len("_g")]
+            shape = spec[k + "_v"][0]
+        out[k] = tuple(shape)
+    return out
+
+
 def _rng_for(seed: int, name: str) -> np.random.Generator:
     return np.random.Generator(np.random.Philox(key=[int(seed) & 0xFFFFFFFFFFFFFFFF, zlib.crc32(name.encode())]))
 
 
-def synthetic_state_dict(seed: int = 0, cfg=None, only_prefixes=None, variant=None, optional=False) -> "OrderedDict[str, np.ndarray]":
+def synthetic_state_dict(seed: int = 0, cfg=None, only_prefixes=None, variant=None, optional=False, posterior=False) -> "OrderedDict[str, np.ndarray]":
     """Deterministic random-init weights in *state-dict form* (fp32 numpy).
 
-    ``optional=True`` appends the tensors of ``optional_param_spec`` (gpt.text_head); every tensor has its own stream, so the others
-    keep their values.
+    ``optional=True`` appends the tensors of ``optional_param_spec`` (gpt.text_head), ``posterior=True`` those of
+    ``posterior_param_spec`` (enc_q); every tensor has its own stream, so the others keep their values.
 
     ``variant="signal"``: the same draws, rescaled so that the vocoder's output DEPENDS ON ITS INPUT.  With the plain fan-in
     init every generator conv attenuates its input by ~0.58 (uniform +-1/sqrt(fan_in) has std 1/sqrt(3 fan_in)) while every bias
@@ -292,6 +338,8 @@ def synthetic_state_dict(seed: int = 0, cfg=None, only_prefixes=None, variant=No
     spec = inference_param_spec(cfg)
     if optional:
         spec.update(optional_param_spec(cfg))
+    if posterior:
+        spec.update(posterior_param_spec(cfg))
     out: "OrderedDict[str, np.ndarray]" = OrderedDict()
     for name, (shape, kind) in spec.items():
         if only_prefixes is not None and not name.startswith(tuple(only_prefixes)):
@@ -408,7 +456,8 @@ def folded_param_names(cfg=None):
 
 def select_inference_params(state: dict, cfg=None) -> "OrderedDict[str, np.ndarray]":
     """Fold + keep exactly the tensors the hot path needs; raise on missing/mis-shaped.  The tensors of optional_param_spec
-    (gpt.text_head) pass through when the checkpoint has them all (mis-shaped ones raise); their absence is never an error."""
+    (gpt.text_head) pass through when the checkpoint has them all (mis-shaped ones raise); their absence is never an error.  So does
+    the enc_q group (posterior_param_spec): complete -> kept (mis-shaped raises), partial or absent -> ignored."""
     folded = fold_weight_norm({k: v for k, v in state.items() if not k.startswith("gpt.inference_model.")})
     spec = inference_param_spec(cfg)
     out: "OrderedDict[str, np.ndarray]" = OrderedDict()
@@ -430,5 +479,12 @@ def select_inference_params(state: dict, cfg=None) -> "OrderedDict[str, np.ndarr
             a = np.ascontiguousarray(_np(folded[k]), dtype=np.float32)
             if tuple(a.shape) != tuple(shape):
                 raise ValueError(f"'{k}': expected shape {tuple(shape)}, got {tuple(a.shape)}")
+            out[k] = a
+    post = _folded(posterior_param_spec(cfg))
+    if all(k in folded for k in post):
+        for k, shape in post.items():
+            a = np.ascontiguousarray(_np(folded[k]), dtype=np.float32)
+            if tuple(a.shape) != shape:
+                raise ValueError(f"'{k}': expected shape {shape}, got {tuple(a.shape)}")
             out[k] = a
     return out

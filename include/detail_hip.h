@@ -361,6 +361,44 @@ int dtts_vocoder_check(dtts_handle* h, long long ticket);
  * nothing to report for it, and a caller that would only wait in order to check need not wait */
 int dtts_vocoder_check_active(dtts_handle* h);
 
+/* ---- the flow-VAE stage forward (SynthesizerTrn.forward_flowvae, vqvae/model_24k.py:706-737).  The entries that read enc_q, the posterior
+ * encoder, need it in the bound blob (optional: packed when the checkpoint carries the whole group); without it they return -1 and the
+ * error names enc_q.pre.weight.  All buffers DEVICE fp32, contiguous; lens / ids / sample_ids HOST; every [B,C,T] output is written in
+ * full, zeros beyond each row's length.  The entries run on stage C's own arena; the WaveNets' split-precision planes report into the
+ * call's range-check ticket like the vocoder's (exact fp32 route with conv_x3 = 0 / voc_x3 = 0, or when T % 4 != 0). */
+
+/* enc_q (vqvae/model_24k.py:172-218): spec [B, spec_channels, T] (linear spectrogram; spec_channels must equal the width of the bound
+ * enc_q.pre.weight, filter_length / 2 + 1, which the blob carries as enc_q.pre.cin), g [B, gin] -> m_q, logs_q and z = (m_q + eps * exp(logs_q)) * mask, [B,192,T] each.  eps = noise [B,192,T],
+ * or (noise NULL) Philox stage 6 keyed (seed, sample_ids[b]): a row draws the same noise alone and inside a batch. */
+int dtts_posterior_encode(dtts_handle* h, const float* spec, int spec_channels, const int* lens, const float* g, int B, int T,
+                          const float* noise, unsigned long long seed, const int* sample_ids, float* z, float* m_q, float* logs_q, void* stream);
+
+/* flow(z, mask, g) in its forward direction (vqvae/model_24k.py:162-165; vqvae/modules/modules.py:456-471, mean_only: logs = 0):
+ * C0, Flip, C2, Flip, C4, Flip, C6, Flip.  z [B,192,T], g [B, gin] -> z_p [B,192,T] (not z itself).  The inverse of the flow inside
+ * the vocoder entry. */
+int dtts_flow_forward(dtts_handle* h, const float* z, const float* g, const int* lens, int B, int T, float* z_p, void* stream);
+
+/* commons.slice_segments (vqvae/modules/commons.py:67-73): out[b, c, j] = x[b, c, ids[b] + j] for j < seg; x [B,C,T] -> out [B,C,seg].
+ * Every segment must lie inside [0, T) (checked on the host). */
+int dtts_slice_segments(dtts_handle* h, const float* x, const int* ids, int B, int C, int T, int seg, float* out, void* stream);
+
+/* losses.kl_loss (vqvae/modules/losses.py:43-58) with the mask given as lengths: out[0] = sum over b, c, t < lens[b] of
+ * (logs_p - logs_q - 1/2 + 1/2 (z_p - m_p)^2 exp(-2 logs_p)) / sum_b lens[b] - the divisor counts frames, not frames x channels.
+ * Inputs [B,C,T].  Fixed-order reduction (partials per 1024 elements, then fp64 in index order): two calls give the same bits. */
+int dtts_kl_loss(dtts_handle* h, const float* z_p, const float* logs_q, const float* m_p, const float* logs_p, const int* lens, int B, int C,
+                 int T, float* out, void* stream);
+
+/* The whole stage in one call, one arena and one range-check ticket: g = ref_enc(mel); quantized, m_p, logs_p = enc_p(in_proj(mel));
+ * z, m_q, logs_q = enc_q(spec, g) (noise / seed / sample_ids as above); z_p = flow(z, g); o = dec(slice_segments(z, ids_slice, seg), g).
+ * mel [B,128,T] with T % 4 == 0, every lens[b] >= seg and ids_slice[b] in [0, lens[b] - seg] (HOST; drawing them is the caller's).
+ * Outputs: o [B,1,hop*seg] (hop = the product of the upsampling rates, 256), the six latents and quantized [B,192,T].  quantized is enc_p's out_proj output, which the reference does
+ * not mask: beyond a row's length it holds out_proj's bias.  A ragged batch is read as the reference reads its padded rectangle: ref_enc's
+ * spectral / temporal layers run over the padded frames of mel * mask before the mask is applied, and in_proj sees mel unmasked, so both
+ * reach a row's last valid frames (the inference entries instead treat every row as the utterance it would be alone). */
+int dtts_flowvae_forward(dtts_handle* h, const float* mel, const float* spec, int spec_channels, const int* lens, int B, int T,
+                         const float* noise, unsigned long long seed, const int* sample_ids, const int* ids_slice, int seg, float* o,
+                         float* z, float* z_p, float* m_p, float* logs_p, float* m_q, float* logs_q, float* quantized, void* stream);
+
 /* Generator.forward (vqvae/model_24k.py:269-288): z [B,192,T], g [B,768] (NULL: `g is None`, no conditioning) -> wav [B,1,256*T] */
 int dtts_generator(dtts_handle* h, const float* z, const float* g, const int* lens, int B, int T, float* wav, void* stream);
 
@@ -502,7 +540,8 @@ int dtts_profile_report(dtts_kernel_stat* out, int max_entries);
  * C(stage) = upsample_initial_channel / 2^(stage + 1).  lens HOST (null -> T). */
 int dtts_op_resblock1(dtts_handle* h, int stage, int branch, const float* x, const int* lens, int B, int T, float* y, void* stream);
 /* WaveNet of coupling layer `flow` (`flow.flows[2 * flow].enc`, vqvae/modules/modules.py:204-229): hidden [B, 192, T] (after the layer's
- * `pre` conv), g [B, gin] -> out [B, 192, T] (the summed skip connections, masked). */
+ * `pre` conv), g [B, gin] -> out [B, 192, T] (the summed skip connections, masked).  flow = -1: enc_q's 16-layer WaveNet (`enc_q.enc`;
+ * needs enc_q in the bound blob). */
 int dtts_op_wn(dtts_handle* h, int flow, const float* hidden, const float* g, const int* lens, int B, int T, float* out, void* stream);
 /* in_proj + enc_p / SpecEncoder (vqvae/model_24k.py:856-857 -> :71-107; vqvae/modules/attentions.py:73-107 Encoder, :161-303 windowed
  * relative-position attention + FFN): mel [B,128,T] (de-normalised log-mel) -> m_p, logs_p [B,192,T] each (masked), the prior statistics
