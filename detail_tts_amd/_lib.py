@@ -12,6 +12,12 @@ LIB_PATH = os.environ.get("DTTS_LIB_PATH") or os.path.join(HERE, "libdetail_hip.
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int)
 c_u64_p = C.POINTER(C.c_ulonglong)
+c_i64_p = C.POINTER(C.c_longlong)
+
+# slots of the loss entries' output (include/detail_hip.h: DTTS_DISC_LOSS_FM and the slots after it)
+DISC_COUNT, DISC_MAPS = 6, 37
+DISC_LOSS_FM, DISC_LOSS_DISC, DISC_LOSS_GEN, DISC_LOSSES_R, DISC_LOSSES_G, DISC_LOSSES_GEN, DISC_MAP_MEANS = 0, 1, 2, 3, 9, 15, 21
+DISC_LOSS_MEL, DISC_LOSS_KL, DISC_LOSS_GEN_ALL, DISC_OUT_FLOATS = 58, 59, 60, 64
 
 
 class DttsConfig(C.Structure):
@@ -121,6 +127,19 @@ SIGNATURES = {
     "dtts_flowvae_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_ulonglong, c_int_p,
                                        c_int_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
+    "dtts_bind_discriminator": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p), c_u64_p, c_u64_p, C.c_int, C.c_void_p]),
+    "dtts_disc_layout": (C.c_int, [C.c_int, C.c_int, c_i64_p, c_int_p]),
+    "dtts_disc_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dtts_disc_losses": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_i64_p, C.c_int, C.POINTER(C.c_void_p),
+                                   C.POINTER(C.c_void_p), c_i64_p, C.c_void_p, C.c_void_p]),
+    "dtts_spec_to_mel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dtts_op_conv1d_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "dtts_op_period_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dtts_flowvae_stage_work": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dtts_flowvae_stage_losses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_ulonglong,
+                                            c_int_p, c_int_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dtts_vocoder": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_ulonglong, c_int_p, C.c_float, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "dtts_vocoder_stream": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_ulonglong, c_int_p, C.c_float, C.c_void_p,

@@ -101,6 +101,72 @@ int dtts_flowvae_forward(dtts_handle* h, const float* mel, const float* spec, in
     DTTS_API_END(h)
 }
 
+int dtts_bind_discriminator(dtts_handle* h, const void* blob, size_t nbytes, const char* const* names, const unsigned long long* offsets,
+                            const unsigned long long* numels, int n, void* stream) {
+    DTTS_API_BEGIN
+    h->m->bind_discriminator(blob, nbytes, names, offsets, numels, n, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_disc_layout(int N, int t, long long* offsets, int* dims) {
+    DTTS_API_BEGIN
+    if (!offsets || !dims || N < 1 || t < 12) throw dtts::Error(-1, "dtts_disc_layout: N >= 1, t >= 12 and two output arrays");
+    const dtts::DiscLayout L = dtts::disc_layout(N, t);
+    for (int m = 0; m < DTTS_DISC_MAPS; ++m) {
+        offsets[m] = L.off[m];
+        dims[4 * m] = L.C[m]; dims[4 * m + 1] = L.H[m]; dims[4 * m + 2] = L.p[m]; dims[4 * m + 3] = N;
+    }
+    offsets[DTTS_DISC_MAPS] = L.off[DTTS_DISC_MAPS];
+    DTTS_API_END(nullptr)
+}
+
+int dtts_disc_forward(dtts_handle* h, const float* y, const float* y_hat, int B, int t, float* maps, void* stream) {
+    DTTS_API_BEGIN
+    h->m->disc_forward(y, y_hat, B, t, maps, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_disc_losses(dtts_handle* h, int n_maps, const float* const* r, const float* const* g, const long long* map_numel, int n_scores,
+                     const float* const* dr, const float* const* dg, const long long* score_numel, float* out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->disc_losses(n_maps, r, g, map_numel, n_scores, dr, dg, score_numel, out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_spec_to_mel(dtts_handle* h, const float* spec, int B, int spec_channels, int T, float* mel_out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->spec_to_mel(spec, B, spec_channels, T, mel_out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_op_conv1d_grouped(dtts_handle* h, const float* x, const float* w, const float* bias, int B, int Cin, int Tin, int Cout, int groups,
+                           int K, int stride, int pad, float slope, float* y, void* stream) {
+    DTTS_API_BEGIN
+    h->m->op_conv1d_grouped(x, w, bias, B, Cin, Tin, Cout, groups, K, stride, pad, slope, y, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_op_period_split(dtts_handle* h, const float* wav, int B, int t, int p, float* out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->op_period_split(wav, B, t, p, out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+long long dtts_flowvae_stage_work(int B, int T, int seg, int hop) {
+    if (B < 1 || T < 1 || seg < 1 || hop < 1 || (long long)seg * hop < 12) return -1;
+    return dtts::flowvae_stage_work_floats(B, T, seg, hop);
+}
+
+int dtts_flowvae_stage_losses(dtts_handle* h, const float* mel, const float* spec, int spec_channels, const int* lens, int B, int T,
+                              const float* noise, unsigned long long seed, const int* sample_ids, const int* ids_slice, int seg,
+                              const float* wav, int L, float* o, float* z, float* z_p, float* m_p, float* logs_p, float* m_q, float* logs_q,
+                              float* quantized, float* work, float* losses, void* stream) {
+    DTTS_API_BEGIN
+    h->m->flowvae_stage_losses(mel, spec, spec_channels, lens, B, T, noise, seed, sample_ids, ids_slice, seg, wav, L, o, z, z_p, m_p, logs_p,
+                               m_q, logs_q, quantized, work, losses, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
 int dtts_vq_decode(dtts_handle* h, const int* codes, const int* ncodes, int nmax, const float* refer, const int* refer_lens, int Tr,
                    int B, float* mel_out, void* stream) {
     DTTS_API_BEGIN

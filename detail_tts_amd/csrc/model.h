@@ -20,6 +20,7 @@
 #include "conv_x3.h"
 #include "diff_loss.h"
 #include "diff_schedule.h"
+#include "disc.h"
 #include "flowvae_fwd.h"
 #include "gpt_kernels.h"
 #include "ops.h"
@@ -86,6 +87,26 @@ struct PosteriorW {          // PosteriorEncoder / enc_q (vqvae/model_24k.py:172
     WnW enc;
     int spec_channels = 0;   // filter_length / 2 + 1, read from the bound blob (enc_q.pre.cin)
 };
+
+struct DiscPeriodW {         // DiscriminatorP (vqvae/model_24k.py:298-374): convs.0 direct, convs.1 .. 3 as de-interleaved 2-tap GEMMs, convs.4, conv_post
+    const float *w0 = nullptr, *b0 = nullptr;
+    PackedConv c[4], post;
+};
+
+struct DiscW {               // MultiPeriodDiscriminator (vqvae/model_24k.py:407-431); bound by bind_discriminator from a blob of its own
+    const float *sw[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *sb[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    PackedConv s5, s_post;   // DiscriminatorS convs.0 .. 4 above (direct / grouped kernels), convs.5 and conv_post as GEMMs
+    DiscPeriodW per[5];
+};
+
+// where dtts_disc_forward puts its 37 maps (include/detail_hip.h dtts_disc_layout): map m is [N][p][C][H] at float offset off[m]
+struct DiscLayout {
+    long long off[DISC_MAPS + 1];
+    int C[DISC_MAPS], H[DISC_MAPS], p[DISC_MAPS];
+    long long numel(int m, int N) const { return (long long)N * p[m] * C[m] * H[m]; }
+};
+DiscLayout disc_layout(int N, int t);
+long long flowvae_stage_work_floats(int B, int T, int seg, int hop);
 
 struct GptLayerW {
     const float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
@@ -269,6 +290,20 @@ public:
     void flowvae_forward(const float* mel, const float* spec, int spec_ch, const int* lens_host, int B, int T, const float* noise, unsigned long long seed,
                          const int* sample_ids_host, const int* ids_slice_host, int seg, float* o, float* z, float* z_p, float* m_p,
                          float* logs_p, float* m_q, float* logs_q, float* quantized, hipStream_t s);
+    // ---- the flow-VAE stage's losses (model_disc.hip; include/detail_hip.h has the contracts)
+    void bind_discriminator(const void* blob, size_t nbytes, const char* const* names, const unsigned long long* offsets,
+                            const unsigned long long* numels, int n, hipStream_t stream);
+    void disc_forward(const float* y, const float* y_hat, int B, int t, float* maps, hipStream_t s);
+    void disc_losses(int n_maps, const float* const* r, const float* const* g, const long long* map_numel, int n_scores,
+                     const float* const* dr, const float* const* dg, const long long* score_numel, float* out, hipStream_t s);
+    void spec_to_mel(const float* spec, int B, int spec_ch, int T, float* mel_out, hipStream_t s);
+    void op_conv1d_grouped(const float* x, const float* w, const float* bias, int B, int Cin, int Tin, int Cout, int groups, int K, int stride,
+                           int pad, float slope, float* y, hipStream_t s);
+    void op_period_split(const float* wav, int B, int t, int p, float* out, hipStream_t s);
+    void flowvae_stage_losses(const float* mel, const float* spec, int spec_ch, const int* lens_host, int B, int T, const float* noise,
+                              unsigned long long seed, const int* sample_ids_host, const int* ids_slice_host, int seg, const float* wav, int L,
+                              float* o, float* z, float* z_p, float* m_p, float* logs_p, float* m_q, float* logs_q, float* quantized,
+                              float* work, float* losses, hipStream_t s);
     void op_enc_p(const float* mel, const int* lens_host, int B, int T, float* m_p, float* logs_p, hipStream_t s);
     void enc_p_fwd(const float* mel, const int* dl, int B, int T, float* x, float* y, float* qkv, float* att, float* ffn, float* relk, float* ml,
                    float* stats, hipStream_t s, bool padded_batch = false);
@@ -506,6 +541,13 @@ private:
     PosteriorW enc_q_;
     bool has_enc_q_ = false;
     std::vector<GenStageW> gen_;
+
+    // discriminator (optional, a blob of its own)
+    std::unordered_map<std::string, std::pair<const float*, size_t>> disc_weights_;
+    DiscW disc_;
+    bool has_disc_ = false;
+    const float* DW(const std::string& name, size_t numel) const;
+    PackedConv disc_conv(const std::string& name, int Cin, int Cout, int KW) const;
 
     // gpt
     std::vector<GptLayerW> gpt_layers_;

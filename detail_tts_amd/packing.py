@@ -307,6 +307,51 @@ def pack_vq(pk, P, cfg):
         pk.add("quantizer.embed_sq", np.square(e).sum(1, dtype=F32))          # embed.pow(2).sum(0) of core_vq.py:180, fp32 like torch
 
 
+def stride3_as_two_taps(w):
+    """w [Cout, Cin, 5] of a (stride 3, zero pad 2) conv -> w_eq [Cout, 3 Cin, 2] of the (stride 1, left pad 1) conv over the input
+    de-interleaved by 3, X[3 c + j][m] = x[c][3 m + j]:  y[n] = sum_k w[k] x[3 n + k - 2] reads X[., n - 1] at j = 1, 2 (k = 0, 1) and
+    X[., n] at j = 0, 1, 2 (k = 2, 3, 4).  The conv GEMM stages at most 192 input columns per tile; 64 outputs at stride 3 need 194."""
+    w = np.asarray(w, F32)
+    cout, cin, k = w.shape
+    assert k == 5, k
+    weq = np.zeros((cout, cin, 3, 2), F32)
+    weq[:, :, 1, 0], weq[:, :, 2, 0] = w[:, :, 0], w[:, :, 1]
+    weq[:, :, 0, 1], weq[:, :, 1, 1], weq[:, :, 2, 1] = w[:, :, 2], w[:, :, 3], w[:, :, 4]
+    return weq.reshape(cout, 3 * cin, 2)
+
+
+def pack_discriminator(P):
+    """The folded 'D' tensors (weights.select_discriminator_params) -> a Packer of their own: the discriminator's blob is bound next
+    to the model's (dtts_bind_discriminator), never inside it, so a blob without it is what it always was.
+      * the Cin = 1 first layers and DiscriminatorS' grouped convs keep the reference's layout ([Cout, Cin / groups, K] rows, `.weight`
+        / `.bias`): direct kernels read them (csrc/disc.hip);
+      * the dense convs (DiscriminatorP convs.1 .. 4, whose (5, 1) kernels act along H only; DiscriminatorS convs.5) and every conv_post
+        (one output row, zero-padded to 32 like dec.conv_post) are K-major GEMM operands (`.wp` / `.bp`, pack_conv); the stride-3 ones
+        in their two-tap form (stride3_as_two_taps)."""
+    from .weights import DISC_P_CONVS, DISC_PERIODS, DISC_S_CONVS
+    pk = Packer()
+
+    def raw(p):
+        pk.add(p + ".weight", P[p + ".weight"].reshape(-1))
+        pk.add(p + ".bias", P[p + ".bias"])
+
+    def gemm(p, stride3=False):
+        w = P[p + ".weight"]
+        w = w[..., 0] if w.ndim == 4 else w
+        pk.conv(p, stride3_as_two_taps(w) if stride3 else w, P[p + ".bias"])
+
+    for i in range(len(DISC_S_CONVS) - 1):
+        raw(f"discriminators.0.convs.{i}")
+    gemm(f"discriminators.0.convs.{len(DISC_S_CONVS) - 1}")
+    gemm("discriminators.0.conv_post")
+    for d in range(1, len(DISC_PERIODS) + 1):
+        raw(f"discriminators.{d}.convs.0")
+        for i in range(1, len(DISC_P_CONVS)):
+            gemm(f"discriminators.{d}.convs.{i}", stride3=DISC_P_CONVS[i][3] == 3)
+        gemm(f"discriminators.{d}.conv_post")
+    return pk
+
+
 def pack_all(P, cfg=None, parts=("diffusion",)):
     """P: folded fp32 dict (weights.select_inference_params). Returns a Packer."""
     cfg = load_config(cfg)

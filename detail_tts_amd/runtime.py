@@ -659,6 +659,144 @@ class Runtime:
                                                int(seg), _ptr(out["o"]), *(_ptr(out[k]) for k in names), self._stream()))
         return out
 
+    # ---- the flow-VAE stage's losses (dtts_bind_discriminator / _disc_forward / _disc_losses / _spec_to_mel / _flowvae_stage_losses)
+    disc_blob = None
+    last_bound_disc = {}          # device -> weak reference to the Runtime that last bound a discriminator there (the loss functions' default handle)
+
+    def bind_discriminator(self, state, folded=False):
+        """Pack the checkpoint's 'D' state dict (reference format, weight-norm pairs accepted; folded=True: already
+        weights.select_discriminator_params' output) into a blob of its own and bind it to this handle next to the model's."""
+        from .packing import pack_discriminator
+        from .weights import select_discriminator_params
+        P = state if folded else select_discriminator_params(state, self.cfg)
+        flat, names, offsets, numels = pack_discriminator(P).blob()
+        self.disc_blob = torch.from_numpy(flat).to(self.device)
+        self._disc_names = [n.encode() for n in names]
+        arr = (C.c_char_p * len(names))(*self._disc_names)
+        offsets, numels = np.ascontiguousarray(offsets), np.ascontiguousarray(numels)
+        self._rc(self.lib.dtts_bind_discriminator(self.h, _ptr(self.disc_blob), self.disc_blob.numel() * 4, arr,
+                                                  offsets.ctypes.data_as(_lib.c_u64_p), numels.ctypes.data_as(_lib.c_u64_p), len(names),
+                                                  self._stream()))
+        import weakref
+        Runtime.last_bound_disc[str(self.device)] = weakref.ref(self)
+
+    def disc_layout(self, N, t):
+        """-> (offsets [38], dims [37][4] = (C, H, p, N)) of dtts_disc_forward's output for N rows of t samples"""
+        off = (C.c_longlong * (_lib.DISC_MAPS + 1))()
+        dims = (C.c_int * (4 * _lib.DISC_MAPS))()
+        self._rc(self.lib.dtts_disc_layout(int(N), int(t), off, dims))
+        return list(off), [tuple(dims[4 * m:4 * m + 4]) for m in range(_lib.DISC_MAPS)]
+
+    def _wave(self, x, name, who):
+        _check(x, name)
+        if x.dim() != 3 or x.shape[1] != 1:
+            raise DttsError(f"{who}: {name} must be [B, 1, t], not {list(x.shape)}")
+        if x.shape[2] < 12:
+            raise DttsError(f"{who}: {name} has {x.shape[2]} samples; t must be at least 12 (every reflect pad shorter than the signal)")
+
+    def disc_forward(self, y, y_hat):
+        """MultiPeriodDiscriminator.forward on y, y_hat cuda [B,1,t] as one batch of 2B rows -> (buf, maps): maps[m] is the view
+        [2B, p, C, H] of map m inside buf (dtts_disc_layout's order), rows [0, B) real, [B, 2B) generated."""
+        self._wave(y, "y", "disc_forward"); self._wave(y_hat, "y_hat", "disc_forward")
+        if y.shape != y_hat.shape:
+            raise DttsError(f"disc_forward: y {list(y.shape)} and y_hat {list(y_hat.shape)} must have one shape [B, 1, t]")
+        B, _, t = y.shape
+        off, dims = self.disc_layout(2 * B, t)
+        buf = torch.empty((off[-1],), device=self.device, dtype=torch.float32)
+        self._rc(self.lib.dtts_disc_forward(self.h, _ptr(y), _ptr(y_hat), B, t, _ptr(buf), self._stream()))
+        return buf, [buf[off[m]:off[m] + 2 * B * p * Cc * H].view(2 * B, p, Cc, H) for m, (Cc, H, p, _) in enumerate(dims)]
+
+    @staticmethod
+    def _ptr_list(ts):
+        n = len(ts)
+        return (C.c_void_p * n)(*[t.data_ptr() for t in ts]), (C.c_longlong * n)(*[t.numel() for t in ts])
+
+    def disc_losses(self, maps_r=(), maps_g=(), scores_r=None, scores_g=()):
+        """One fixed-order reduction over lists of cuda fp32 tensors -> the [64] output of dtts_disc_losses (slots: _lib.DISC_*).  A pair
+        (r, g) must share its memory layout (mean |r - g| is taken over the storage); scores_r None: generator_loss alone."""
+        maps_r, maps_g, scores_g = list(maps_r), list(maps_g), list(scores_g)
+        if len(maps_r) != len(maps_g) or (scores_r is not None and len(scores_r) != len(scores_g)):
+            raise DttsError("disc_losses: the real and the generated list must have one length")
+        if len(maps_r) > _lib.DISC_MAPS or len(scores_g) > _lib.DISC_COUNT or not (maps_r or scores_g):
+            raise DttsError(f"disc_losses: at most {_lib.DISC_MAPS} maps and {_lib.DISC_COUNT} scores, at least one of either")
+        for a, b in zip(maps_r, maps_g):
+            if a.numel() != b.numel() or a.numel() == 0:
+                raise DttsError("disc_losses: a real map and its generated map must have one non-empty shape")
+        out = torch.zeros((_lib.DISC_OUT_FLOATS,), device=self.device, dtype=torch.float32)
+        r, rn = self._ptr_list(maps_r)
+        g, _ = self._ptr_list(maps_g)
+        dg, sn = self._ptr_list(scores_g)
+        dr = self._ptr_list(scores_r)[0] if scores_r is not None else None
+        self._rc(self.lib.dtts_disc_losses(self.h, len(maps_r), r, g, rn, len(scores_g), dr, dg, sn, _ptr(out), self._stream()))
+        return out
+
+    def spec_to_mel(self, spec):
+        """spec_to_mel_torch (vqvae/utils/data_utils.py:89-102): linear magnitudes cuda [B,513,T] -> log-mel [B,128,T]"""
+        self._spec(spec, "spec_to_mel")
+        B, Cs, T = spec.shape
+        out = torch.empty((B, self.cfg["data"]["n_mel_channels"], T), device=self.device, dtype=torch.float32)
+        self._rc(self.lib.dtts_spec_to_mel(self.h, _ptr(spec), B, Cs, T, _ptr(out), self._stream()))
+        return out
+
+    def op_conv1d_grouped(self, x, w, bias, groups, stride, pad, slope=1.0):
+        """One grouped Conv1d + leaky-relu(slope) through the grouped kernel: x [B,Cin,Tin], w [Cout, Cin/groups, K], bias [Cout] or None
+        -> (y [B,Cout,Nout], guard): guard is one more sample-sized slab right behind y in the same allocation, filled with NaN"""
+        _check(x, "x"); _check(w, "w"); _check(bias, "bias")
+        B, Cin, Tin = x.shape
+        Cout, cin_g, K = w.shape
+        if Cin % groups or Cout % groups or cin_g != Cin // groups:
+            raise DttsError(f"op_conv1d_grouped: w {list(w.shape)} does not fit Cin = {Cin} in {groups} groups")
+        if Tin + 2 * pad < K:
+            raise DttsError("op_conv1d_grouped: the padded input is shorter than the kernel")
+        nout = (Tin + 2 * pad - K) // stride + 1
+        buf = torch.zeros((B + 1, Cout, nout), device=self.device, dtype=torch.float32)
+        y, guard = buf[:B], buf[B]
+        guard.fill_(float("nan"))
+        self._rc(self.lib.dtts_op_conv1d_grouped(self.h, _ptr(x), _ptr(w), _ptr(bias), B, Cin, Tin, Cout, int(groups), K, int(stride), int(pad),
+                                                 float(slope), _ptr(y), self._stream()))
+        return y, guard
+
+    def op_period_split(self, wav, p):
+        """wav cuda [B,1,t] -> [B * p, 1, ceil(t / p)]: DiscriminatorP's reflect pad and view, row b * p + w = samples w, w + p, ..."""
+        _check(wav, "wav")
+        if wav.dim() != 3 or wav.shape[1] != 1 or wav.shape[2] <= int(p):
+            raise DttsError(f"op_period_split: wav must be [B, 1, t] with t > p, not {list(wav.shape)}")
+        B, _, t = wav.shape
+        out = torch.empty((B * int(p), 1, -(-t // int(p))), device=self.device, dtype=torch.float32)
+        self._rc(self.lib.dtts_op_period_split(self.h, _ptr(wav), B, t, int(p), _ptr(out), self._stream()))
+        return out
+
+    def flowvae_stage_losses(self, mel, spec, lens, ids_slice, seg, wav, noise=None, seed=0, sample_ids=None):
+        """dtts_flowvae_stage_losses: flowvae_forward's dict plus `losses` (the [64] output, slots _lib.DISC_*); wav cuda [B,1,L]"""
+        _check(mel, "mel"); self._spec(spec, "flowvae_stage_losses"); _check(wav, "wav")
+        n_mel = self.cfg["data"]["n_mel_channels"]
+        if mel.dim() != 3 or mel.shape[1] != n_mel:
+            raise DttsError(f"flowvae_stage_losses: mel must be [B, {n_mel}, T], not {list(mel.shape)}")
+        B, _, T = mel.shape
+        if spec.shape[0] != B or spec.shape[2] != T:
+            raise DttsError(f"flowvae_stage_losses: spec {tuple(spec.shape)} does not match mel {tuple(mel.shape)}")
+        hop = self._hop()
+        if wav.dim() != 3 or wav.shape[0] != B or wav.shape[1] != 1 or wav.shape[2] < T * hop:
+            raise DttsError(f"flowvae_stage_losses: wav must be [{B}, 1, >= {T * hop}] ({hop} samples per frame of mel), not {list(wav.shape)}")
+        inter = self.cfg["vaegan"]["inter_channels"]
+        if noise is not None:
+            self._shape(noise, (B, inter, T), "noise", "flowvae_stage_losses")
+        li = self._lens(lens, B, T, "flowvae_stage_losses")
+        ii = self._row_ints(ids_slice, B, "flowvae_stage_losses", "segment starts (ids_slice)")
+        si = self._sids(sample_ids, B, "flowvae_stage_losses")
+        names = ("z", "z_p", "m_p", "logs_p", "m_q", "logs_q", "quantized")
+        out = {k: torch.empty((B, inter, T), device=self.device, dtype=torch.float32) for k in names}
+        out["o"] = torch.empty((B, 1, hop * int(seg)), device=self.device, dtype=torch.float32)
+        nwork = int(self.lib.dtts_flowvae_stage_work(B, T, int(seg), hop))
+        if nwork < 0:
+            raise DttsError("flowvae_stage_losses: sizes")
+        work = torch.empty((nwork,), device=self.device, dtype=torch.float32)
+        out["losses"] = torch.zeros((_lib.DISC_OUT_FLOATS,), device=self.device, dtype=torch.float32)
+        self._rc(self.lib.dtts_flowvae_stage_losses(self.h, _ptr(mel), _ptr(spec), spec.shape[1], li[0], B, T, _ptr(noise), int(seed), si[0], ii[0],
+                                                    int(seg), _ptr(wav), wav.shape[2], _ptr(out["o"]), *(_ptr(out[k]) for k in names),
+                                                    _ptr(work), _ptr(out["losses"]), self._stream()))
+        return out
+
     def vocoder_ticket(self):
         """ticket of the last vocoder / generator call issued on this handle (dtts_vocoder_ticket)"""
         return int(self.lib.dtts_vocoder_ticket(self.h))

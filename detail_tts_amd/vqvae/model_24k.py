@@ -18,6 +18,7 @@ from ..config import COND_FREE_K, INFER_DIFFUSION_STEPS, MAX_GENERATE_LENGTH, ME
     TOP_P, TORCH_MEL_MAX, TRAINED_DIFFUSION_STEPS, load_config
 from ..gpt.candidates import check_choose, check_num_candidates, expand_sample_ids, rank_candidates
 from ..gpt.model import UnifiedVoice
+from .. import _lib as _lib_slots
 from ..runtime import Runtime
 from .diff_model import DiffusionTts
 from .utils.diffusion import SAMPLERS, SpacedDiffusion, check_timesteps, get_named_beta_schedule, space_timesteps
@@ -177,6 +178,73 @@ def write_wav(path, wav, sample_rate=24000):
         f.setsampwidth(2)
         f.setframerate(int(sample_rate))
         f.writeframes(pcm.tobytes())
+
+
+class MultiPeriodDiscriminator:
+    """vqvae/model_24k.py:407-431 on the device, forward values only: DiscriminatorS and DiscriminatorP of periods 2, 3, 5, 7, 11.
+
+    `state` is the checkpoint's 'D' state dict (train.py:146; weight-norm pairs or the parametrizations form, torch or numpy), or None
+    (load_state_dict later).  `model=` a SynthesizerTrn (or a Runtime): the weights are bound to its handle, next to the model's, which
+    flowvae_stage_losses needs; otherwise `device=` makes a handle that holds nothing else.  The packed weights (about 50 M floats) are
+    a blob of their own: the model's blob is what it is without them."""
+
+    periods = (2, 3, 5, 7, 11)
+
+    def __init__(self, state=None, *, model=None, device=None, cfg=None, use_spectral_norm=False, folded=False):
+        if use_spectral_norm:
+            raise NotImplementedError("use_spectral_norm=True is not implemented on the device (the reference trains with weight_norm)")
+        if model is not None and device is not None:
+            raise ValueError("MultiPeriodDiscriminator: give model= or device=, not both")
+        if model is not None:
+            self.rt = model.rt if hasattr(model, "rt") else model
+        else:
+            self.rt = Runtime({}, cfg, device=device or "cuda:0", parts=(), folded=True)
+        self.device = self.rt.device
+        self.bound = False
+        if state is not None:
+            self.load_state_dict(state, folded=folded)
+
+    def load_state_dict(self, state, strict=True, folded=False):
+        self.rt.bind_discriminator(state, folded=folded)
+        self.bound = True
+        return self
+
+    def eval(self):
+        return self
+
+    def to(self, device):
+        if torch.device(device) != self.device:
+            raise NotImplementedError("re-create the discriminator on the target device (weights are bound to one GPU)")
+        return self
+
+    def forward(self, y, y_hat):
+        """y, y_hat [B,1,t], t >= 12 -> (y_d_rs, y_d_gs, fmap_rs, fmap_gs): 6 scores [B, H p] and 6 lists of maps [B, C, H, p] ([B, C, T]
+        for DiscriminatorS; 7 maps there, 6 in each DiscriminatorP) per side, cuda fp32, in the reference's shapes.  The maps are
+        permuted views of one buffer laid out [2B, p, C, H]; real and generated run as one batch, each weight read once."""
+        y, y_hat = torch.as_tensor(y), torch.as_tensor(y_hat)
+        if y.dim() != 3 or y.shape[1] != 1 or tuple(y.shape) != tuple(y_hat.shape):
+            raise ValueError(f"MultiPeriodDiscriminator: y and y_hat must share one shape [B, 1, t], not {list(y.shape)} and {list(y_hat.shape)}")
+        if y.shape[2] < 12:
+            raise ValueError(f"MultiPeriodDiscriminator: t = {y.shape[2]}; t must be at least 12 (every reflect pad shorter than the signal)")
+        y = y.to(self.device, torch.float32).contiguous()
+        y_hat = y_hat.to(self.device, torch.float32).contiguous()
+        B = y.shape[0]
+        _, maps = self.rt.disc_forward(y, y_hat)
+        y_d_rs, y_d_gs, fmap_rs, fmap_gs = [], [], [], []
+        m = 0
+        for d in range(1 + len(self.periods)):
+            fr, fg = [], []
+            for _ in range(7 if d == 0 else 6):
+                a = maps[m]                                        # [2B, p, C, H]
+                v = a[:, 0] if d == 0 else a.permute(0, 2, 3, 1)   # [2B, C, T] / [2B, C, H, p]
+                fr.append(v[:B]); fg.append(v[B:])
+                m += 1
+            fmap_rs.append(fr); fmap_gs.append(fg)
+            y_d_rs.append(torch.flatten(fr[-1], 1, -1))            # (h, w) order, as the reference flattens [B, 1, H, p]
+            y_d_gs.append(torch.flatten(fg[-1], 1, -1))
+        return y_d_rs, y_d_gs, fmap_rs, fmap_gs
+
+    __call__ = forward
 
 
 class SynthesizerTrn:
@@ -803,6 +871,46 @@ class SynthesizerTrn:
         y_mask = (torch.arange(T, device=self.device)[None, :] < torch.as_tensor(yl, device=self.device)[:, None]).unsqueeze(1).to(torch.float32)
         return (r["o"], 0, 0, 0, torch.as_tensor(ids, dtype=torch.int64, device=self.device), y_mask,
                 (r["z"], r["z_p"], r["m_p"], r["logs_p"], r["m_q"], r["logs_q"]), r["quantized"])
+
+    def flowvae_stage_losses(self, y, y_lengths, data, disc, *, noise=None, ids_slice=None, seed=0, sample_ids=None):
+        """Everything train.py:259-322 logs for target == 'flowvae', in one device call (dtts_flowvae_stage_losses), forward values only:
+        forward_flowvae (same arguments, same bits), y = slice(data['wav'], ids_slice * hop, segment_size), y_mel =
+        slice(spec_to_mel(data['spec']), ids_slice, segment_size // hop), y_hat_mel = mel_spectrogram(o), loss_mel = 45 L1, `disc`
+        (a MultiPeriodDiscriminator bound to THIS model: MultiPeriodDiscriminator(state, model=self)) on (y, o) and the three GAN losses.
+        -> dict: loss_gen, loss_fm, loss_mel, loss_kl, loss_disc, loss_gen_all (= loss_gen + loss_fm + loss_mel + loss_kl; this stage
+        contributes zeros for the others) as 0-d fp32 CUDA tensors, losses_disc_r / losses_disc_g / losses_gen (lists of 6 such
+        scalars) and `outputs`, forward_flowvae's tuple.  data['wav'] [B,1,>= T hop] is the waveform the spectrograms were made of
+        (train.py's data['wav'])."""
+        if getattr(disc, "rt", None) is not self.rt:
+            raise ValueError("flowvae_stage_losses: disc must be a MultiPeriodDiscriminator bound to this model (MultiPeriodDiscriminator(state, model=model))")
+        y = torch.as_tensor(y)
+        seg = self.cfg["train"]["segment_size"] // self.cfg["data"]["hop_length"]
+        yl, ids = check_flowvae_args(y.shape, y_lengths, seg, ids_slice)
+        if ids is None:
+            ids = draw_segment_starts(seed, yl, seg)
+        y = y.to(self.device, torch.float32).contiguous()
+        spec = torch.as_tensor(data["spec"]).to(self.device, torch.float32).contiguous()
+        wav = torch.as_tensor(data["wav"])
+        if wav.dim() != 3 or wav.shape[0] != y.shape[0] or wav.shape[1] != 1:
+            raise ValueError(f"flowvae_stage_losses: data['wav'] must be [B, 1, samples], not {list(wav.shape)}")
+        wav = wav.to(self.device, torch.float32).contiguous()
+        if noise is not None:
+            noise = torch.as_tensor(noise).to(self.device, torch.float32).contiguous()
+        r = self.rt.flowvae_stage_losses(y, spec, yl, ids, seg, wav, noise=noise, seed=seed, sample_ids=sample_ids)
+        ticket = self.rt.vocoder_ticket()
+        if self.rt.vocoder_check_active():
+            torch.cuda.current_stream(self.device).synchronize()
+            self.rt.vocoder_check(ticket)
+        T = y.shape[-1]
+        y_mask = (torch.arange(T, device=self.device)[None, :] < torch.as_tensor(yl, device=self.device)[:, None]).unsqueeze(1).to(torch.float32)
+        L, o = r["losses"], _lib_slots
+        out = {k: L[i] for k, i in (("loss_gen", o.DISC_LOSS_GEN), ("loss_fm", o.DISC_LOSS_FM), ("loss_mel", o.DISC_LOSS_MEL),
+                                    ("loss_kl", o.DISC_LOSS_KL), ("loss_disc", o.DISC_LOSS_DISC), ("loss_gen_all", o.DISC_LOSS_GEN_ALL))}
+        for k, i in (("losses_disc_r", o.DISC_LOSSES_R), ("losses_disc_g", o.DISC_LOSSES_G), ("losses_gen", o.DISC_LOSSES_GEN)):
+            out[k] = [L[i + d] for d in range(o.DISC_COUNT)]
+        out["outputs"] = (r["o"], 0, 0, 0, torch.as_tensor(ids, dtype=torch.int64, device=self.device), y_mask,
+                          (r["z"], r["z_p"], r["m_p"], r["logs_p"], r["m_q"], r["logs_q"]), r["quantized"])
+        return out
 
     def forward_all(self, y, y_lengths, data, *, noise=None, ids_slice=None, seed=0, sample_ids=None, t=None, diff_noise=None):
         """vqvae/model_24k.py:749-772: forward_flowvae's tuple with l_diff, loss_gpt and vq_loss from forward_diff (t, diff_noise, seed),

@@ -35,6 +35,7 @@ K_HFW = "hf_w"     # HF GPT-2 Conv1D weight [in, out], N(0, .02)
 K_HFB = "hf_b"
 K_WN_V = "wn_v"    # weight-norm direction
 K_WN_G = "wn_g"    # weight-norm magnitude
+K_WN_VD = "wn_vd"  # weight-norm direction of a discriminator conv: He-scaled, so that six leaky-relu layers keep O(1) feature maps
 K_RELB = "relbias"
 K_RELE = "relemb"
 K_UNCOND = "uncond"
@@ -298,6 +299,50 @@ def posterior_param_spec(cfg=None) -> "OrderedDict[str, tuple]":
     return spec
 
 
+DISC_PERIODS = (2, 3, 5, 7, 11)      # MultiPeriodDiscriminator (vqvae/model_24k.py:410)
+# DiscriminatorS (vqvae/model_24k.py:381-391): (Cout, Cin, K, stride, groups, pad) of convs.0 .. convs.5; conv_post is (1, 1024, 3, 1, 1, 1)
+DISC_S_CONVS = ((16, 1, 15, 1, 1, 7), (64, 16, 41, 4, 4, 20), (256, 64, 41, 4, 16, 20), (1024, 256, 41, 4, 64, 20),
+                (1024, 1024, 41, 4, 256, 20), (1024, 1024, 5, 1, 1, 2))
+# DiscriminatorP (vqvae/model_24k.py:304-353): (Cout, Cin, K, stride) of convs.0 .. convs.4, zero padding 2; conv_post is (1, 1024, 3, 1)
+DISC_P_CONVS = ((32, 1, 5, 3), (128, 32, 5, 3), (512, 128, 5, 3), (1024, 512, 5, 3), (1024, 1024, 5, 1))
+
+
+def discriminator_param_spec(cfg=None) -> "OrderedDict[str, tuple]":
+    """name -> (shape, kind) of the reference's `D` state dict (train.py:146): MultiPeriodDiscriminator (vqvae/model_24k.py:298-431),
+    discriminators.0 = DiscriminatorS (Conv1d, weights [Cout, Cin / groups, K]), discriminators.1 .. 5 = DiscriminatorP of periods
+    2, 3, 5, 7, 11 (Conv2d with (K, 1) kernels, weights [Cout, Cin, K, 1]); every conv is weight-normed.  A checkpoint entry of its own
+    ('D'), never part of SynthesizerTrn's state: bound only on request (MultiPeriodDiscriminator, load_discriminator)."""
+    spec: "OrderedDict[str, tuple]" = OrderedDict()
+
+    def wn(p, shape):
+        spec[p + ".bias"] = ((shape[0],), K_B)
+        spec[p + ".weight_g"] = ((shape[0],) + (1,) * (len(shape) - 1), K_WN_G)
+        spec[p + ".weight_v"] = (tuple(shape), K_WN_VD)
+
+    for i, (cout, cin, k, _s, groups, _p) in enumerate(DISC_S_CONVS):
+        wn(f"discriminators.0.convs.{i}", (cout, cin // groups, k))
+    wn("discriminators.0.conv_post", (1, 1024, 3))
+    for d in range(1, len(DISC_PERIODS) + 1):
+        for i, (cout, cin, k, _s) in enumerate(DISC_P_CONVS):
+            wn(f"discriminators.{d}.convs.{i}", (cout, cin, k, 1))
+        wn(f"discriminators.{d}.conv_post", (1, 1024, 3, 1))
+    return spec
+
+
+def select_discriminator_params(state: dict, cfg=None) -> "OrderedDict[str, np.ndarray]":
+    """The 'D' state dict, folded, with exactly discriminator_param_spec's tensors; raises on a missing or mis-shaped one"""
+    folded = fold_weight_norm(state)
+    out: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    for k, shape in _folded(discriminator_param_spec(cfg)).items():
+        if k not in folded:
+            raise KeyError(f"discriminator checkpoint is missing '{k}'")
+        a = np.ascontiguousarray(_np(folded[k]), dtype=np.float32)
+        if tuple(a.shape) != shape:
+            raise ValueError(f"'{k}': expected shape {shape}, got {tuple(a.shape)}")
+        out[k] = a
+    return out
+
+
 def _folded(spec):
     """state-dict-form spec -> {folded name: shape}: weight_g / weight_v pairs appear as one `weight` of v's shape"""
     out = OrderedDict()
@@ -315,11 +360,15 @@ def _rng_for(seed: int, name: str) -> np.random.Generator:
     return np.random.Generator(np.random.Philox(key=[int(seed) & 0xFFFFFFFFFFFFFFFF, zlib.crc32(name.encode())]))
 
 
-def synthetic_state_dict(seed: int = 0, cfg=None, only_prefixes=None, variant=None, optional=False, posterior=False) -> "OrderedDict[str, np.ndarray]":
+def synthetic_state_dict(seed: int = 0, cfg=None, only_prefixes=None, variant=None, optional=False, posterior=False,
+                         discriminator=False) -> "OrderedDict[str, np.ndarray]":
     """Deterministic random-init weights in *state-dict form* (fp32 numpy).
 
     ``optional=True`` appends the tensors of ``optional_param_spec`` (gpt.text_head), ``posterior=True`` those of
-    ``posterior_param_spec`` (enc_q); every tensor has its own stream, so the others keep their values.
+    ``posterior_param_spec`` (enc_q), ``discriminator=True`` those of ``discriminator_param_spec`` (the 'D' entry of a checkpoint:
+    callers split them off by prefix, ``only_prefixes=("discriminators.",)``); every tensor has its own stream, so the others keep
+    their values.  The discriminator's directions are He-scaled (uniform +-sqrt(6 / fan_in), fan_in per group): a leaky-relu(0.1)
+    layer then keeps its input's mean square, where the plain fan-in init would shrink it 6 x per layer down to the biases.
 
     ``variant="signal"``: the same draws, rescaled so that the vocoder's output DEPENDS ON ITS INPUT.  With the plain fan-in
     init every generator conv attenuates its input by ~0.58 (uniform +-1/sqrt(fan_in) has std 1/sqrt(3 fan_in)) while every bias
@@ -340,6 +389,8 @@ def synthetic_state_dict(seed: int = 0, cfg=None, only_prefixes=None, variant=No
         spec.update(optional_param_spec(cfg))
     if posterior:
         spec.update(posterior_param_spec(cfg))
+    if discriminator:
+        spec.update(discriminator_param_spec(cfg))
     out: "OrderedDict[str, np.ndarray]" = OrderedDict()
     for name, (shape, kind) in spec.items():
         if only_prefixes is not None and not name.startswith(tuple(only_prefixes)):
@@ -351,6 +402,9 @@ def synthetic_state_dict(seed: int = 0, cfg=None, only_prefixes=None, variant=No
                 # ConvTranspose1d [in, out, k]: each output sample sums in*k/stride taps
                 fan_in = shape[0] * max(1, shape[2] // 2)
             b = 1.0 / np.sqrt(fan_in)
+            a = r.uniform(-b, b, size=shape)
+        elif kind == K_WN_VD:
+            b = np.sqrt(6.0 / int(np.prod(shape[1:])))
             a = r.uniform(-b, b, size=shape)
         elif kind == K_B:
             a = r.uniform(-0.05, 0.05, size=shape)
@@ -401,8 +455,11 @@ def _signal_variant(name, a):
 def synthetic_tensor(seed, name, spec=None):
     spec = spec or inference_param_spec()
     shape, kind = spec[name]
-    assert kind in (K_W, K_WN_V)
+    assert kind in (K_W, K_WN_V, K_WN_VD)
     r = _rng_for(seed, name)
+    if kind == K_WN_VD:
+        b = np.sqrt(6.0 / int(np.prod(shape[1:])))
+        return np.ascontiguousarray(r.uniform(-b, b, size=shape), dtype=np.float32)
     fan_in = int(np.prod(shape[1:])) if len(shape) > 1 else shape[0]
     if name.startswith("dec.ups.") and kind == K_WN_V:
         fan_in = shape[0] * max(1, shape[2] // 2)

@@ -399,6 +399,72 @@ int dtts_flowvae_forward(dtts_handle* h, const float* mel, const float* spec, in
                          const float* noise, unsigned long long seed, const int* sample_ids, const int* ids_slice, int seg, float* o,
                          float* z, float* z_p, float* m_p, float* logs_p, float* m_q, float* logs_q, float* quantized, void* stream);
 
+/* ---- the flow-VAE stage's losses: MultiPeriodDiscriminator (vqvae/model_24k.py:298-431: DiscriminatorS and DiscriminatorP of periods
+ * 2, 3, 5, 7, 11), feature_loss / discriminator_loss / generator_loss (vqvae/modules/losses.py:4-40), spec_to_mel_torch
+ * (vqvae/utils/data_utils.py:89-102) and everything train.py:259-322 logs for target == 'flowvae'.  Forward values only, no gradients.
+ *
+ * The discriminator's weights are the checkpoint's 'D' entry, packed by detail_tts_amd.packing.pack_discriminator into a blob of its
+ * own (about 50 M floats) and bound next to the model's; the model's blob and every other entry are untouched by it.  The entries
+ * below are one group: each of them (the unit entries and dtts_spec_to_mel included) fails with a message naming
+ * discriminators.0.convs.0.weight while no discriminator is bound.  The blob stays the caller's. */
+int dtts_bind_discriminator(dtts_handle* h, const void* blob, size_t nbytes, const char* const* names, const unsigned long long* offsets,
+                            const unsigned long long* numels, int n, void* stream);
+
+/* The 37 feature maps of one forward over N waveforms of t samples (N = 2B: rows [0, B) y, rows [B, 2B) y_hat), in the reference's
+ * order: map 0 .. 6 = DiscriminatorS' six convs and its conv_post, map 7 + 6 (d - 1) + l = conv l (5 = conv_post) of the
+ * DiscriminatorP of period DTTS_DISC_PERIODS[d - 1].  Map m is stored [N][p][C][H] (p = 1 for DiscriminatorS) at float offset
+ * offsets[m] of the output buffer; dims[4 m ..] = (C, H, p, N); offsets[37] = the buffer's size in floats.  The reference's map
+ * [N, C, H, p] is the permuted view; its score is conv_post's map flattened in (h, w) order.  Pure host arithmetic. */
+#define DTTS_DISC_COUNT 6
+#define DTTS_DISC_MAPS 37
+int dtts_disc_layout(int N, int t, long long* offsets, int* dims);
+
+/* y, y_hat [B,1,t] (t >= 12: every reflect pad is shorter than the signal) -> the maps, laid out as dtts_disc_layout says.  Real and
+ * generated run as one batch of N = 2B rows, so every weight is read once.  y_hat NULL: y alone (N = B). */
+int dtts_disc_forward(dtts_handle* h, const float* y, const float* y_hat, int B, int t, float* maps, void* stream);
+
+/* The three loss functions in one fixed-order reduction (two calls give the same bits): n_maps pairs (r[k], g[k]) of map_numel[k]
+ * floats each -> mean |r - g|; n_scores pairs (dr[k], dg[k]) of score_numel[k] floats -> mean (1 - dr)^2, mean dg^2, mean (1 - dg)^2
+ * (dr NULL: generator_loss alone).  r, g, dr, dg are HOST arrays of DEVICE pointers (n_maps <= 37, n_scores <= 6).  out DEVICE
+ * [DTTS_DISC_OUT_FLOATS]: loss_fm = 2 sum of the map means, loss_disc = sum (r_loss + g_loss), loss_gen = sum gen_loss, each summed in
+ * list order in fp32, and the per-item means.  Slots of absent items are left as they were. */
+#define DTTS_DISC_LOSS_FM 0
+#define DTTS_DISC_LOSS_DISC 1
+#define DTTS_DISC_LOSS_GEN 2
+#define DTTS_DISC_LOSSES_R 3        /* 6 */
+#define DTTS_DISC_LOSSES_G 9        /* 6 */
+#define DTTS_DISC_LOSSES_GEN 15     /* 6 */
+#define DTTS_DISC_MAP_MEANS 21      /* 37 */
+#define DTTS_DISC_LOSS_MEL 58       /* the stage call only */
+#define DTTS_DISC_LOSS_KL 59
+#define DTTS_DISC_LOSS_GEN_ALL 60
+#define DTTS_DISC_OUT_FLOATS 64
+int dtts_disc_losses(dtts_handle* h, int n_maps, const float* const* r, const float* const* g, const long long* map_numel, int n_scores,
+                     const float* const* dr, const float* const* dg, const long long* score_numel, float* out, void* stream);
+
+/* spec_to_mel_torch: spec [B, n_fft/2+1, T] (linear magnitudes) -> log(clamp(mel_basis @ spec, 1e-5)) [B,128,T]; needs the front-end part */
+int dtts_spec_to_mel(dtts_handle* h, const float* spec, int B, int spec_channels, int T, float* mel_out, void* stream);
+
+/* One grouped Conv1d + leaky-relu(slope; 1 = none) through the grouped kernel (csrc/disc.hip): x [B,Cin,Tin], w [Cout, Cin/groups, K]
+ * and bias [Cout] (NULL: none) DEVICE, in the reference's layout -> y [B, Cout, (Tin + 2 pad - K) / stride + 1].  4 or 16 output
+ * channels per group. */
+int dtts_op_conv1d_grouped(dtts_handle* h, const float* x, const float* w, const float* bias, int B, int Cin, int Tin, int Cout, int groups,
+                           int K, int stride, int pad, float slope, float* y, void* stream);
+
+/* wav [B,1,t] -> [B * p, 1, ceil(t / p)]: the period split with its reflect pad (row b * p + w holds samples w, w + p, ...) */
+int dtts_op_period_split(dtts_handle* h, const float* wav, int B, int t, int p, float* out, void* stream);
+
+/* dtts_flowvae_forward and, chained behind it on the same stream with no host synchronisation: y = slice(wav, ids_slice * hop, seg * hop)
+ * (wav [B,1,L]), y_mel = slice(spec_to_mel(spec), ids_slice, seg), y_hat_mel = mel_spectrogram(o), loss_mel = 45 mean |y_mel - y_hat_mel|,
+ * the discriminator on (y, o), the three losses and the KL.  losses DEVICE [DTTS_DISC_OUT_FLOATS] (every slot written; loss_gen_all =
+ * loss_gen + loss_fm + loss_mel + loss_kl).  work DEVICE: dtts_flowvae_stage_work(B, T, seg, hop) floats of caller scratch that hold
+ * what lives across the chained calls (the sliced wav, the mels, the maps). */
+long long dtts_flowvae_stage_work(int B, int T, int seg, int hop);
+int dtts_flowvae_stage_losses(dtts_handle* h, const float* mel, const float* spec, int spec_channels, const int* lens, int B, int T,
+                              const float* noise, unsigned long long seed, const int* sample_ids, const int* ids_slice, int seg,
+                              const float* wav, int L, float* o, float* z, float* z_p, float* m_p, float* logs_p, float* m_q, float* logs_q,
+                              float* quantized, float* work, float* losses, void* stream);
+
 /* Generator.forward (vqvae/model_24k.py:269-288): z [B,192,T], g [B,768] (NULL: `g is None`, no conditioning) -> wav [B,1,256*T] */
 int dtts_generator(dtts_handle* h, const float* z, const float* g, const int* lens, int B, int T, float* wav, void* stream);
 
