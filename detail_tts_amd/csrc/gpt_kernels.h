@@ -28,6 +28,8 @@ struct GptCtl {
     float* latents;               // optional [B][C][lat_cs] channel-major: column `step` receives final_norm(ln_f(h))
     long long lat_bs;
     int lat_cs;
+    int pos_off[GEMV_MAXB];       // mel positions the row's prefix holds: 1 (start_mel alone) or m + 2 behind an acoustic prompt
+                                  // [1, 8192, c_1 .. c_m]; the input embedding of generated token `step` sits at mel position step + pos_off
 };
 
 // lat = LN2(LN1(res + bias + sum_slices parts)) (ln_f then final_norm, gpt/model.py:173 + HF GPT2Model.ln_f) -> y [B][C] and, when
@@ -80,6 +82,10 @@ void launch_build_prefix(const float* cond, const int* text_ids, int text_stride
                          const float* text_pos, const float* mel_emb, const float* mel_pos, const int* mel_ids, int mel_stride,
                          const int* mel_lens, int B, int C, int Lmax, float* emb, hipStream_t s);
 
+// seen[b][ids[b][i]] = 1 for i < nids[b]: the repetition-penalty history a session starts with (ids DEVICE [B][stride], range-checked
+// by the caller; seen is zeroed by the caller)
+void launch_mark_seen(const int* ids, int stride, const int* nids, int B, int V, unsigned char* seen, hipStream_t s);
+
 // gather column (lens[b]-1 + col_off) of [B,C,L] into [B][C]
 void launch_gather_last(const float* x, long long bs, int cs, const int* lens, int col_off, int B, int C, float* y, hipStream_t s);
 
@@ -97,7 +103,7 @@ struct SamplerParams {
     int codes_stride;
     int eos;
     GptCtl* ctl;
-    // next-step input embedding: x_next[b] = mel_emb[token] + mel_pos[step + 1]  (may be null)
+    // next-step input embedding: x_next[b] = mel_emb[token] + mel_pos[step + ctl->pos_off[b]]  (may be null)
     const float* mel_emb;
     const float* mel_pos;
     float* x_next;

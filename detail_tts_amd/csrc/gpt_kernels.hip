@@ -646,6 +646,19 @@ void launch_build_prefix(const float* cond, const int* text_ids, int text_stride
     DTTS_CHECK_HIP(hipGetLastError());
 }
 
+__global__ void mark_seen_kernel(const int* ids, int stride, const int* nids, int V, unsigned char* seen) {
+    const int b = blockIdx.x, n = nids[b];
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int id = ids[(long long)b * stride + i];
+        if (id >= 0 && id < V) seen[(long long)b * V + id] = 1;      // (duplicates write the same byte)
+    }
+}
+
+void launch_mark_seen(const int* ids, int stride, const int* nids, int B, int V, unsigned char* seen, hipStream_t s) {
+    hipLaunchKernelGGL(mark_seen_kernel, dim3(B), dim3(256), 0, s, ids, stride, nids, V, seen);
+    DTTS_CHECK_HIP(hipGetLastError());
+}
+
 __global__ void gather_last_kernel(const float* x, long long bs, int cs, const int* lens, int col_off, int C, float* y) {
     const int b = blockIdx.y;
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -790,9 +803,10 @@ __global__ __launch_bounds__(SAMP_THREADS) void sampler_kernel(const SamplerPara
     const int sample_id_b = ctl->sample_id[b];
     const int fin_in = p.finished[b];
     if (step >= ctl->max_steps) return;                  // a replayed graph may run past the requested length: no-op
-    float pos_next = 0.f;                                 // mel_pos[step + 1][tid]: C <= SAMP_THREADS is the common case
+    float pos_next = 0.f;                                 // mel_pos[step + pos_off][tid]: C <= SAMP_THREADS is the common case
     const bool pos_pf = p.x_next && p.C <= SAMP_THREADS;
-    if (pos_pf && tid < p.C) pos_next = p.mel_pos[(long long)(step + 1) * p.C + tid];
+    const int pos_row = step + ctl->pos_off[b];           // pos_off = 1 (start_mel alone) or m + 2 behind an acoustic prompt
+    if (pos_pf && tid < p.C) pos_next = p.mel_pos[(long long)pos_row * p.C + tid];
     const int top_k = ctl->top_k;
     const float top_p = ctl->top_p;
     int token;
@@ -1120,12 +1134,12 @@ __global__ __launch_bounds__(SAMP_THREADS) void sampler_kernel(const SamplerPara
         if (token == p.eos) p.finished[b] = 1;
         ctl->step[b] = step + 1;                 // only this workgroup reads or writes step[b] inside this launch
     }
-    // next input embedding: mel_embedding[token] + mel_pos_embedding[step + 1]   (gpt/model.py:134-136 with position k)
+    // next input embedding: mel_embedding[token] + mel_pos_embedding[step + pos_off]   (gpt/model.py:134-136 with position k)
     if (pos_pf) {
         if (tid < p.C) p.x_next[(long long)b * p.C + tid] = p.mel_emb[(long long)token * p.C + tid] + pos_next;
     } else if (p.x_next)
         for (int c = tid; c < p.C; c += SAMP_THREADS)
-            p.x_next[(long long)b * p.C + c] = p.mel_emb[(long long)token * p.C + c] + p.mel_pos[(long long)(step + 1) * p.C + c];
+            p.x_next[(long long)b * p.C + c] = p.mel_emb[(long long)token * p.C + c] + p.mel_pos[(long long)pos_row * p.C + c];
     SSTAMP(14);
 #undef SSTAMP
 }

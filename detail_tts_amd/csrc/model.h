@@ -350,6 +350,9 @@ public:
         else if (key == "gpt_token_wgs") { DTTS_REQUIRE(value == 128 || value == 64 || value == 32, "gpt_token_wgs: 128, 64 or 32"); opt_tok_wgs_ = value; gpt_drop_graphs(); }
         else if (key == "gpt_token_fault") opt_tok_fault_ = value;       // test hook: the n-th token launch from now on times out
         else if (key == "gpt_token_fault_eos") opt_tok_fault_eos_ = value;   // ... and leaves every row flagged finished (a spurious stop token)
+        // test hook: a prompted session's mel stream is [8192, c_1 .. c_m] (no fill id 1 in front, no stop token behind): what a tortoise
+        // session holds after m forced decode steps, so that the prefill route can be compared with the step route
+        else if (key == "gpt_prompt_raw") opt_prompt_raw_ = value != 0;
         else if (key == "cfg_streams") opt_cfg_streams_ = value < 0 ? 0 : value;
         else if (key == "gn_fuse") opt_gn_fuse_ = value != 0;
         else if (key == "conv_cols") opt_conv_cols_ = value != 0;
@@ -572,12 +575,13 @@ private:
     bool tok_failed_ = false;             // an exchange timed out once: this handle stays on the chain (until the option is set again)
     int opt_tok_fault_ = 0;               // option "gpt_token_fault"
     int opt_tok_fault_eos_ = 0;           // option "gpt_token_fault_eos"
+    bool opt_prompt_raw_ = false;         // option "gpt_prompt_raw"
     // what dtts_gpt_prefill was called with, kept so that a session whose token kernel timed out can be replayed on the chain
     struct GptReplay {
         bool valid = false;
         int Tr = 0, Lt_max = 0, B = 0, lat_stride = 0;
         bool has_refer_lens = false, has_text_lens = false;
-        std::vector<int> refer_lens, text, text_lens, sample_ids, forced_codes;
+        std::vector<int> refer_lens, text, text_lens, sample_ids, forced_codes, prompt_codes, prompt_lens;
         std::vector<unsigned long long> row_seeds;
         dtts_gpt_options o;
         float* latents_cm = nullptr;

@@ -202,8 +202,62 @@ static void text_prefix_ids(const int* text, const int* text_lens, int B, int Lt
     }
 }
 
+// The mel stream a session's prefill embeds behind the text (gpt/model.py:528-530 and :561-564 with :132-136), per row:
+//   no prompt : [8192]                          n_p = 1
+//   prompt    : [1, 8192, c_1 .. c_m]           n_p = m + 2: inference_speech_valle's fake_inputs hold 1 + (Lt + 3) + (m + 1) ids - the
+//               first value of build_aligned_inputs_and_targets is [8192, codes], the stop token belongs to its unused targets - and
+//               the cached embedding covers Lt + 3 columns, so ONE fill id 1 is embedded with mel_embedding at mel position 0
+//   raw       : [8192, c_1 .. c_m]              n_p = m + 1 (option gpt_prompt_raw, tests: a tortoise session after m forced steps)
+// mel[b][0 .. np[b]) with row stride np_max; seen[b] = [1, mel[b]...] (row stride np_max + 1): HF's repetition penalty sees every id of
+// input_ids, the fill id 1 of the prefix columns included.  Codes are range-checked here, on the host where they live.
+static void prompt_prefix_ids(const dtts_gpt_options& o, int B, int G, int max_mel_pos, bool raw, std::vector<int>& np, int& np_max,
+                              std::vector<int>& mel, std::vector<int>& seen, std::vector<int>& nseen) {
+    np.assign(B, 1);
+    np_max = 1;
+    DTTS_REQUIRE(o.prompt_codes || !o.prompt_lens, "prompt_lens without prompt_codes");
+    if (o.prompt_codes) {
+        DTTS_REQUIRE(o.prompt_lens && o.prompt_stride >= 0, "prompt_codes needs prompt_lens and prompt_stride");
+        for (int b = 0; b < B; ++b) {
+            const int m = o.prompt_lens[b];
+            DTTS_REQUIRE(m >= 0 && m <= o.prompt_stride, "prompt_lens outside [0, prompt_stride]");
+            // (the sampler reads position row n_p + G - 1 for the input of a token that is never fed: m + 2 + G rows are touched; the
+            // limit keeps one more row spare)
+            DTTS_REQUIRE((long long)m + 3 + G <= max_mel_pos, "prompt_lens: m + 3 + max_generate_length exceeds the mel position table (gpt_max_mel_pos)");
+            for (int k = 0; k < m; ++k) {
+                const int c = o.prompt_codes[(size_t)b * o.prompt_stride + k];
+                DTTS_REQUIRE(c >= 0 && c < 8192, "prompt_codes: code outside [0, 8192)");
+            }
+            np[b] = raw ? m + 1 : m + 2;
+            np_max = std::max(np_max, np[b]);
+        }
+    }
+    mel.assign((size_t)B * np_max, 0);
+    seen.assign((size_t)B * (np_max + 1), 0);
+    nseen.assign(B, 0);
+    for (int b = 0; b < B; ++b) {
+        int* r = mel.data() + (size_t)b * np_max;
+        int n = 0;
+        if (o.prompt_codes) {
+            const int m = o.prompt_lens[b];
+            if (!raw) r[n++] = 1;
+            r[n++] = 8192;
+            for (int k = 0; k < m; ++k) r[n++] = o.prompt_codes[(size_t)b * o.prompt_stride + k];
+        } else {
+            r[n++] = 8192;
+        }
+        int* q = seen.data() + (size_t)b * (np_max + 1);
+        q[0] = 1;
+        std::copy(r, r + n, q + 1);
+        nseen[b] = n + 1;
+    }
+}
+
 // ---- decode session ------------------------------------------------------------------------------------------------------------
-// dtts_gpt_prefill: conditioning encoder + [cond | text | start_mel] prefill (KV cache filled) + the first sampled token.  The session
+// dtts_gpt_prefill: conditioning encoder + [cond | text | start_mel] prefill (KV cache filled) + the first sampled token; with
+// dtts_gpt_options.prompt_codes the prefix is [cond | text | 1, 8192, prompt] (inference_speech_valle, gpt/model.py:546-579): the
+// whole prompt runs through the parallel prefill, no prompt token takes a decode step, and the KV cache, the repetition-penalty history
+// and the mel position counter start behind it.  The latents written while decoding are then the hidden states WITH THE PROMPT IN
+// CONTEXT - not what forward(return_latent=True) on the generated codes alone returns (gpt_teacher_forced computes those).  The session
 // (KV cache, residual rows, sampler state, device control block) lives in the handle's own arena, whose addresses stay fixed from call
 // to call, so the captured decode graphs stay valid.
 void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host,
@@ -224,6 +278,7 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
             r.has_refer_lens = refer_lens_host != nullptr;
             r.has_text_lens = text_lens_host != nullptr;
             r.refer_lens.clear(); r.text_lens.clear(); r.forced_codes.clear(); r.row_seeds.clear();      // nothing of an earlier session survives
+            r.prompt_codes.clear(); r.prompt_lens.clear();
             if (refer_lens_host) r.refer_lens.assign(refer_lens_host, refer_lens_host + B);
             r.text.assign(text_host, text_host + (size_t)B * Lt_max);
             if (text_lens_host) r.text_lens.assign(text_lens_host, text_lens_host + B);
@@ -231,6 +286,11 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
             r.o = o;
             if (o.forced_codes) r.forced_codes.assign(o.forced_codes, o.forced_codes + (size_t)B * o.max_generate_length);
             if (o.row_seeds) r.row_seeds.assign(o.row_seeds, o.row_seeds + B);
+            if (o.prompt_codes && o.prompt_lens && o.prompt_stride >= 0) {
+                r.prompt_codes.assign(o.prompt_codes, o.prompt_codes + (size_t)B * o.prompt_stride);
+                r.prompt_lens.assign(o.prompt_lens, o.prompt_lens + B);
+                if (r.prompt_codes.empty()) r.prompt_codes.push_back(0);      // (stride 0: the replayed options still need a pointer)
+            }
             r.valid = true;
         }
     }
@@ -241,10 +301,11 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
     int tl_max;
     text_prefix_ids(text_host, text_lens_host, B, Lt_max, cfg.gpt_text_tokens, ids, tl, tl_max);
     DTTS_REQUIRE(tl_max <= cfg.gpt_max_text_pos, "text too long");
-    std::vector<int> lp(B), ml(B, 1), mel0(B, 8192);
-    int Lp = 0;
+    std::vector<int> lp(B), ml, mel0, seen0, nseen;
+    int Lp = 0, np_max;
+    prompt_prefix_ids(o, B, G, cfg.gpt_max_mel_pos, opt_prompt_raw_, ml, np_max, mel0, seen0, nseen);
     for (int b = 0; b < B; ++b) {
-        lp[b] = 1 + tl[b] + 1;
+        lp[b] = 1 + tl[b] + ml[b];
         Lp = std::max(Lp, lp[b]);
     }
     if (o.forced_codes)
@@ -309,12 +370,14 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
     const int* d_ids = upload_ints(ids.data(), B * tl_max, s);
     const int* d_tl = upload_ints(tl.data(), B, s);
     const int* d_ml = upload_ints(ml.data(), B, s);
-    const int* d_mel0 = upload_ints(mel0.data(), B, s);
+    const int* d_mel0 = upload_ints(mel0.data(), B * np_max, s);
     const int* d_lp = upload_ints(lp.data(), B, s);
+    const int* d_seen0 = upload_ints(seen0.data(), B * (np_max + 1), s);
+    const int* d_nseen = upload_ints(nseen.data(), B, s);
     // control block (host copy kept in the handle: the asynchronous upload reads it)
     GptCtl& c = ctl_host_;
     std::memset(&c, 0, sizeof(c));
-    for (int b = 0; b < B; ++b) { c.lp[b] = lp[b]; c.sample_id[b] = o.sample_ids[b]; c.seed[b] = o.row_seeds ? o.row_seeds[b] : o.seed; }
+    for (int b = 0; b < B; ++b) { c.lp[b] = lp[b]; c.pos_off[b] = ml[b]; c.sample_id[b] = o.sample_ids[b]; c.seed[b] = o.row_seeds ? o.row_seeds[b] : o.seed; }
     c.repetition_penalty = o.repetition_penalty;
     c.temperature = o.temperature;
     c.top_p = o.top_p;
@@ -336,21 +399,19 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
     c.lat_cs = lat_stride;
     DTTS_CHECK_HIP(hipMemcpyAsync(gs_.ctl, &c, sizeof(c), hipMemcpyHostToDevice, s));
     if (o.forced_codes) DTTS_CHECK_HIP(hipMemcpyAsync(gs_.forced, o.forced_codes, sizeof(int) * (size_t)B * G, hipMemcpyHostToDevice, s));
-    // seen = ids of the fake prefix: 1 (all prefix slots) and start_mel 8192  (gpt/model.py:528-530)
+    // seen = ids of the fake prefix: 1 (all prefix slots) and start_mel 8192  (gpt/model.py:528-530); behind a prompt also its codes
+    // (:561-564)
     DTTS_CHECK_HIP(hipMemsetAsync(gs_.seen, 0, (size_t)B * V, s));
     DTTS_CHECK_HIP(hipMemsetAsync(gs_.finished, 0, sizeof(int) * B, s));
-    for (int b = 0; b < B; ++b) {
-        DTTS_CHECK_HIP(hipMemsetAsync(gs_.seen + (size_t)b * V + 1, 1, 1, s));
-        DTTS_CHECK_HIP(hipMemsetAsync(gs_.seen + (size_t)b * V + 8192, 1, 1, s));
-    }
+    launch_mark_seen(d_seen0, np_max + 1, d_nseen, B, V, gs_.seen, s);
     {   // rows that finish early are padded with 8193 (HF pad_token_id)
         std::vector<int> pad((size_t)B * G, 8193);
         DTTS_CHECK_HIP(hipMemcpyAsync(gs_.codes, pad.data(), sizeof(int) * pad.size(), hipMemcpyHostToDevice, s));
         DTTS_CHECK_HIP(hipStreamSynchronize(s));          // host temporaries (ids, pad, forced codes) are consumed
     }
-    // ---- prefill over [cond | text | start_mel]
+    // ---- prefill over [cond | text | start_mel] or [cond | text | 1, start_mel, prompt]
     DTTS_CHECK_HIP(hipMemsetAsync(emb, 0, sizeof(float) * (size_t)B * C * Lp, s));
-    launch_build_prefix(cond, d_ids, tl_max, d_tl, text_emb_, text_pos_, mel_emb_, mel_pos_, d_mel0, 1, d_ml, B, C, Lp, emb, s);
+    launch_build_prefix(cond, d_ids, tl_max, d_tl, text_emb_, text_pos_, mel_emb_, mel_pos_, d_mel0, np_max, d_ml, B, C, Lp, emb, s);
     gpt_prefill_layers(emb, d_lp, B, Lp, gs_.kv, kv_layer, kv_bs, cap, s);
     launch_gather_last(emb, (long long)C * Lp, Lp, d_lp, 0, B, C, gs_.xa, s);
     // first token: lm_head = (final_norm, mel_head) applied to ln_f(h)   (gpt/model.py:41, 173)
@@ -632,6 +693,7 @@ void Model::gpt_finish(int* codes_host, int* ncodes_host, hipStream_t s) {
         o.sample_ids = r.sample_ids.data();
         o.forced_codes = r.forced_codes.empty() ? nullptr : r.forced_codes.data();
         o.row_seeds = r.row_seeds.empty() ? nullptr : r.row_seeds.data();
+        if (o.prompt_codes) { o.prompt_codes = r.prompt_codes.data(); o.prompt_lens = r.prompt_lens.data(); }
         replaying_ = true;
         try {
             gpt_replay_.reset();
@@ -667,7 +729,8 @@ void Model::gpt_finish(int* codes_host, int* ncodes_host, hipStream_t s) {
     gs_.active = false;
 }
 
-// UnifiedVoice.inference_speech_tortoise (gpt/model.py:514-545): prefill + decode loop + results.  Batches larger than one session
+// UnifiedVoice.inference_speech_tortoise (gpt/model.py:514-545) or, with prompt_codes, inference_speech_valle (:546-579): prefill +
+// decode loop + results.  Batches larger than one session
 // (8 rows) run group after group; the finish flags are polled once per 16-token graph (never per token).
 void Model::gpt_generate(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host,
                          int Lt_max, int B, const dtts_gpt_options& o, int* codes_host, int* ncodes_host, float* latents_cm,
@@ -682,6 +745,8 @@ void Model::gpt_generate(const float* refer, const int* refer_lens_host, int Tr,
         if (o.forced_uniforms) og.forced_uniforms = o.forced_uniforms + (size_t)g0 * G;
         if (o.forced_codes) og.forced_codes = o.forced_codes + (size_t)g0 * G;
         if (o.row_seeds) og.row_seeds = o.row_seeds + g0;
+        if (o.prompt_codes) og.prompt_codes = o.prompt_codes + (size_t)g0 * o.prompt_stride;
+        if (o.prompt_lens) og.prompt_lens = o.prompt_lens + g0;
         gpt_prefill(refer + (size_t)g0 * cfg.mel_channels * Tr, refer_lens_host ? refer_lens_host + g0 : nullptr, Tr,
                     text_host + (size_t)g0 * Lt_max, text_lens_host ? text_lens_host + g0 : nullptr, Lt_max, nb, og,
                     latents_cm ? latents_cm + (size_t)g0 * C * lat_stride : nullptr, lat_stride, s);

@@ -65,6 +65,37 @@ class UnifiedVoice:
         sample_ids[b] + r - the expanded ids must be distinct, else ValueError), `input_tokens [rows, k]` (mel tokens in front of the generated ones; with num_return_sequences = n > 1 the
         reference tiles them AND lets HF expand the batch again: n * n rows of the single prompt, reproduced), `typical_sampling`
         (HF TypicalLogitsWarper(mass=typical_mass), which HF applies between the repetition penalty and the temperature)."""
+        return self._generate(speech_conditioning_latent, cond_lengths, text_inputs, None, input_tokens, num_return_sequences,
+                              max_generate_length, typical_sampling, typical_mass, text_lengths, seed, sample_ids, suppress_eos,
+                              forced_uniforms, hf_generate_kwargs)
+
+    def inference_speech_valle(self, speech_conditioning_latent, cond_lengths, text_inputs, mel_codes, input_tokens=None,
+                               num_return_sequences=1, max_generate_length=None, typical_sampling=False, typical_mass=.9,
+                               text_lengths=None, seed=0, sample_ids=None, suppress_eos=False, forced_uniforms=None,
+                               **hf_generate_kwargs):
+        """gpt/model.py:546-579: inference_speech_tortoise continued from an acoustic prompt.  mel_codes [B, m] (or a list of B
+        one-dimensional arrays: per-row lengths are an extension, the reference takes a rectangle) are mel codes in [0, 8192), e.g.
+        SynthesizerTrn.encode's of a prompt mel.  Returns the GENERATED tokens only (input_tokens in front, as in tortoise); every other
+        argument, num_return_sequences (prompt rows repeat as the conditioning rows do) and the extra keywords behave as there.
+
+        Reproduced from the reference, its quirk included (gpt/prompt.py): the mel stream is [1, 8192, c_1 .. c_m] - the fill id 1 of
+        the prefix columns sits at mel position 0, embedded as a mel token - and the repetition penalty starts with {1, 8192} and the
+        prompt's codes.  No stop token closes the prompt (the reference keeps build_aligned_inputs_and_targets' inputs, not its
+        targets), so the stop token is not in the penalty history.  The whole prompt runs in the parallel prefill; m + 3 +
+        max_generate_length may not exceed the 1603 rows of mel_pos_embedding (ValueError before any launch; the reference dies with
+        IndexError a little later, from m + max_generate_length = 1603).  last_latents are the hidden states with the prompt in
+        context.  How a trained checkpoint sounds with a prompt is unmeasured."""
+        if mel_codes is None:
+            raise ValueError("inference_speech_valle: mel_codes (the acoustic prompt) is required")
+        return self._generate(speech_conditioning_latent, cond_lengths, text_inputs, mel_codes, input_tokens, num_return_sequences,
+                              max_generate_length, typical_sampling, typical_mass, text_lengths, seed, sample_ids, suppress_eos,
+                              forced_uniforms, hf_generate_kwargs)
+
+    def _generate(self, speech_conditioning_latent, cond_lengths, text_inputs, mel_codes, input_tokens, num_return_sequences,
+                  max_generate_length, typical_sampling, typical_mass, text_lengths, seed, sample_ids, suppress_eos, forced_uniforms,
+                  hf_generate_kwargs):
+        """What inference_speech_tortoise and inference_speech_valle share (gpt/model.py:528-545 and :561-579 differ in fake_inputs only):
+        the row expansion, the id checks, the greedy mapping and the decode session; mel_codes = None is the tortoise session."""
         nrs = int(num_return_sequences)
         assert nrs >= 1
         do_sample = bool(hf_generate_kwargs.get("do_sample", True))
@@ -86,11 +117,16 @@ class UnifiedVoice:
                 nrs = nrs * nrs
         cl = None if cond_lengths is None else torch.as_tensor(cond_lengths).reshape(-1).tolist()
         texts = self._texts(text_inputs, text_lengths)
+        prompt = None
+        if mel_codes is not None:
+            from .prompt import prompt_rows
+            prompt = prompt_rows(mel_codes, B)
         ids = list(range(B * nrs)) if sample_ids is None else list(sample_ids)
         if nrs > 1:
             refer = refer.repeat_interleave(nrs, 0).contiguous()
             cl = None if cl is None else [v for v in cl for _ in range(nrs)]
             texts = [t for t in texts for _ in range(nrs)]
+            prompt = None if prompt is None else [p for p in prompt for _ in range(nrs)]
             if len(ids) == B:
                 ids = [i + r for i in ids for r in range(nrs)]
         assert len(ids) == B * nrs, "sample_ids: one per returned sequence (or one per prompt)"
@@ -112,7 +148,7 @@ class UnifiedVoice:
         codes, ncodes, lat = self.rt.gpt_generate(
             refer, cl, texts, seed, ids, max_generate_length=G, repetition_penalty=hf_generate_kwargs.get("repetition_penalty", 1.0),
             suppress_eos=suppress_eos, forced_uniforms=forced_uniforms, forced_codes=forced, forced_fill=-1,
-            typical_mass=float(typical_mass) if typical_sampling else 0.0, **samp)
+            typical_mass=float(typical_mass) if typical_sampling else 0.0, **samp, **({} if prompt is None else dict(prompt_codes=prompt)))
         self.last_latents, self.last_ncodes = lat, ncodes
         n = int(ncodes.max())
         return torch.from_numpy(codes[:, :n].astype(np.int64)).to(refer.device)

@@ -158,13 +158,23 @@ class Runtime:
             out[i, :len(t)] = np.asarray(t, np.int32)
         return out, lens
 
+    @staticmethod
+    def _prompt(prompt_codes, B, text_lens, G):
+        """prompt_codes -> None or (codes int32 [B, stride], lens int32 [B]), checked on the host (gpt/prompt.py): ValueError before any launch"""
+        if prompt_codes is None:
+            return None
+        from .gpt.prompt import pack_prompt
+        return pack_prompt(prompt_codes, B, text_lens, G)
+
     def gpt_generate(self, refer, refer_lens, texts, seed, sample_ids, max_generate_length=600, top_k=50, top_p=0.8,
-                     temperature=0.8, repetition_penalty=2.0, suppress_eos=False, forced_uniforms=None, forced_codes=None, forced_fill=8193, typical_mass=0.0, token_wgs=0):
-        """-> (codes int32 [B,G] incl. stop, ncodes [B], latents_cm float32 cuda [B,768,G])"""
-        _check(refer, "refer"); _check(forced_uniforms, "forced_uniforms")
+                     temperature=0.8, repetition_penalty=2.0, suppress_eos=False, forced_uniforms=None, forced_codes=None, forced_fill=8193, typical_mass=0.0, token_wgs=0, prompt_codes=None):
+        """-> (codes int32 [B,G] incl. stop, ncodes [B], latents_cm float32 cuda [B,768,G]).  prompt_codes ([B, m] or a list of B
+        one-dimensional arrays): the acoustic prompt of inference_speech_valle, see gpt_prefill."""
         B, _, Tr = refer.shape
         text, tl = self._pad_text(texts)
         G = int(max_generate_length)
+        prompt = self._prompt(prompt_codes, B, tl, G)          # (refusals come before any library call)
+        _check(refer, "refer"); _check(forced_uniforms, "forced_uniforms")
         si = _ints(sample_ids)
         rl = _ints(refer_lens if refer_lens is not None else [Tr] * B)
         o = _lib.DttsGptOptions()
@@ -180,6 +190,8 @@ class Runtime:
         o.suppress_eos = 1 if suppress_eos else 0
         o.typical_mass = float(typical_mass or 0.0)
         o.token_wgs = int(token_wgs or 0)       # 0: the handle's gpt_token_wgs option; 64 / 32: this session decodes on fewer workgroups (same bits)
+        if prompt is not None:
+            o.prompt_codes, o.prompt_lens, o.prompt_stride = prompt[0].ctypes.data_as(_lib.c_int_p), prompt[1].ctypes.data_as(_lib.c_int_p), prompt[0].shape[1]
         o.forced_uniforms = forced_uniforms.data_ptr() if forced_uniforms is not None else None
         fc = None
         if forced_codes is not None:
@@ -198,12 +210,18 @@ class Runtime:
 
     # decode session (include/detail_hip.h: dtts_gpt_prefill / _decode_step / _decode / _all_finished / _finish), <= 16 rows
     def gpt_prefill(self, refer, refer_lens, texts, seed, sample_ids, max_generate_length=600, top_k=50, top_p=0.8, temperature=0.8,
-                    repetition_penalty=2.0, suppress_eos=False, forced_uniforms=None, forced_codes=None, forced_fill=8193, typical_mass=0.0, token_wgs=0):
-        """conditioning encoder + prefill + first token; returns the latents tensor [B,768,G] the steps fill column by column"""
-        _check(refer, "refer"); _check(forced_uniforms, "forced_uniforms")
+                    repetition_penalty=2.0, suppress_eos=False, forced_uniforms=None, forced_codes=None, forced_fill=8193, typical_mass=0.0, token_wgs=0, prompt_codes=None):
+        """conditioning encoder + prefill + first token; returns the latents tensor [B,768,G] the steps fill column by column.
+
+        prompt_codes ([B, m] array or a list of B one-dimensional arrays; per-row lengths are an extension, the reference takes a
+        rectangle): the acoustic prompt of UnifiedVoice.inference_speech_valle (gpt/model.py:546-579).  The prefill then covers
+        [cond | text | 1, 8192, prompt], the codes returned are the generated ones only, and the latents are the hidden states
+        with the prompt in context (not gpt_latents of the generated codes alone).  gpt/prompt.py states the layout and the checks."""
         B, _, Tr = refer.shape
         text, tl = self._pad_text(texts)
         G = int(max_generate_length)
+        prompt = self._prompt(prompt_codes, B, tl, G)          # (refusals come before any library call)
+        _check(refer, "refer"); _check(forced_uniforms, "forced_uniforms")
         si = _ints(sample_ids)
         rl = _ints(refer_lens if refer_lens is not None else [Tr] * B)
         o = _lib.DttsGptOptions()
@@ -219,6 +237,8 @@ class Runtime:
         o.suppress_eos = 1 if suppress_eos else 0
         o.typical_mass = float(typical_mass or 0.0)
         o.token_wgs = int(token_wgs or 0)       # 0: the handle's gpt_token_wgs option; 64 / 32: this session decodes on fewer workgroups (same bits)
+        if prompt is not None:
+            o.prompt_codes, o.prompt_lens, o.prompt_stride = prompt[0].ctypes.data_as(_lib.c_int_p), prompt[1].ctypes.data_as(_lib.c_int_p), prompt[0].shape[1]
         o.forced_uniforms = forced_uniforms.data_ptr() if forced_uniforms is not None else None
         if forced_codes is not None:
             fc = np.full((B, G), int(forced_fill), np.int32)      # steps past a row's list: the stop token, or -1 = sample there (a forced PREFIX)

@@ -17,6 +17,7 @@ import torch
 from ..config import COND_FREE_K, INFER_DIFFUSION_STEPS, MAX_GENERATE_LENGTH, MEL_MIN, NOISE_SCALE, REPETITION_PENALTY, TEMPERATURE, \
     TOP_P, TORCH_MEL_MAX, TRAINED_DIFFUSION_STEPS, load_config
 from ..gpt.candidates import check_choose, check_num_candidates, expand_sample_ids, rank_candidates
+from ..gpt.prompt import check_prompt_args, prompt_rows
 from ..gpt.model import UnifiedVoice
 from .. import _lib as _lib_slots
 from ..runtime import Runtime
@@ -311,8 +312,14 @@ class SynthesizerTrn:
     def infer(self, text, text_length, refer, refer_lengths, noise_scale=NOISE_SCALE, *, batch=False, seed=None, sample_ids=None,
               forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False, return_lengths=False,
               stream_vocoder=False, vocoder_chunk=256, wait=True, check_range=True, diffusion_steps=None, sampler="p", eta=0.0,
-              trunk_precision=None, num_candidates=1, choose=None, return_candidates=False):
+              trunk_precision=None, num_candidates=1, choose=None, return_candidates=False, prompt_codes=None):
         """vqvae/model_24k.py:774-810.  Returns wav [B,1,1024*n_max] (B=1 unless batch=True).
+
+        prompt_codes ([B, m] or a list of B one-dimensional arrays of mel codes, e.g. encode()'s of a prompt mel; not with forced_codes or
+        num_candidates > 1): the reference's own composition with line 782 calling UnifiedVoice.inference_speech_valle - stage A continues
+        the code sequence from the acoustic prompt (one prefill over [cond | text | prompt], gpt/prompt.py) and the diffusion latents
+        come from the teacher-forced pass on the GENERATED codes alone (:795-799, gpt_latents), not from the session's decode-time latents,
+        which have the prompt in context.  None: today's path, untouched.
 
         num_candidates = N in 1 .. 16 (not with forced_codes): stage A samples N code sequences per utterance (rows expanded with
         repeat_interleave; candidate c of utterance b draws from Philox stream sample_ids[b] + c * 2**20, so candidate 0 IS the N = 1
@@ -343,6 +350,7 @@ class SynthesizerTrn:
         sched_ts, sampler_id, eta = sampling_args(diffusion_steps, sampler, eta)
         prec = SynthesizerTrn._check_trunk_precision(self, trunk_precision)
         ncand = check_num_candidates(num_candidates, forced_codes)
+        check_prompt_args(prompt_codes, forced_codes, ncand)
         text = torch.as_tensor(text)
         refer = torch.as_tensor(refer)
         tl = torch.as_tensor(text_length).reshape(-1).tolist()
@@ -351,7 +359,11 @@ class SynthesizerTrn:
             text, refer, tl, rl = text[:1], refer[:1], tl[:1], rl[:1]
             if forced_codes is not None:
                 forced_codes = forced_codes[:1]
+            if prompt_codes is not None:
+                prompt_codes = prompt_codes[:1]
         B = text.shape[0]
+        if prompt_codes is not None:
+            prompt_codes = prompt_rows(prompt_codes, B)              # (ValueError on a bad row count or code: before any launch)
         choose = check_choose(choose, B, ncand)
         candidates = (ncand > 1 or return_candidates) and forced_codes is None
         if return_candidates and not candidates:
@@ -378,6 +390,8 @@ class SynthesizerTrn:
         if forced_codes is None:
             kw = dict(max_generate_length=max_generate_length, top_k=top_k, top_p=TOP_P, temperature=TEMPERATURE,
                       repetition_penalty=REPETITION_PENALTY, suppress_eos=suppress_eos)
+            if prompt_codes is not None:
+                kw["prompt_codes"] = prompt_codes
             a_refer, a_rl, a_texts, a_ids = refer, rl, texts, sample_ids
             if candidates and ncand > 1:                            # HF's num_return_sequences expansion: every row N times
                 a_refer = refer.repeat_interleave(ncand, 0).contiguous()
@@ -414,7 +428,10 @@ class SynthesizerTrn:
             n = [int(c) - 1 for c in ncodes]                       # codes = codes[:, :-1]  (:795)
             if min(n) < 1:
                 raise ValueError("an utterance produced no mel codes (stop token first)")
-            lat = lat[:, :, : max(n)].contiguous()                 # decode-time latents == return_latent pass
+            if prompt_codes is None:
+                lat = lat[:, :, : max(n)].contiguous()             # decode-time latents == return_latent pass
+            else:       # behind a prompt they are not: the reference's return_latent pass sees the generated codes alone (:796-799)
+                lat = self.rt.gpt_latents(refer, rl, texts, [codes[b, : n[b]] for b in range(B)])
         else:
             n = [len(c) for c in forced_codes]
             lat = self.rt.gpt_latents(refer, rl, texts, forced_codes)
@@ -745,8 +762,10 @@ class SynthesizerTrn:
     EMPTY_CODE_FRAMES = 16
 
     def infer_gpt(self, text, text_length, refer, refer_lengths, noise_scale=NOISE_SCALE, *, batch=False, seed=None, sample_ids=None,
-                  forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False):
-        """vqvae/model_24k.py:811-847: GPT codes -> quantizer.decode + vq_ref_enc -> vq_dec -> infer_flowvae (no diffusion)."""
+                  forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False, prompt_codes=None):
+        """vqvae/model_24k.py:811-847: GPT codes -> quantizer.decode + vq_ref_enc -> vq_dec -> infer_flowvae (no diffusion).
+        prompt_codes (not with forced_codes): line 819 calls UnifiedVoice.inference_speech_valle, see infer."""
+        check_prompt_args(prompt_codes, forced_codes, 1)
         text = torch.as_tensor(text)
         refer = torch.as_tensor(refer)
         tl = torch.as_tensor(text_length).reshape(-1).tolist()
@@ -755,7 +774,10 @@ class SynthesizerTrn:
             text, refer, tl, rl = text[:1], refer[:1], tl[:1], rl[:1]
             if forced_codes is not None:
                 forced_codes = forced_codes[:1]
+            if prompt_codes is not None:
+                prompt_codes = prompt_codes[:1]
         B = text.shape[0]
+        pkw = {} if prompt_codes is None else dict(prompt_codes=prompt_rows(prompt_codes, B))
         refer = refer.to(self.device, torch.float32).contiguous()
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -764,7 +786,7 @@ class SynthesizerTrn:
             texts = [text[b, : int(tl[b])].cpu().numpy().astype(np.int32) for b in range(B)]
             codes, ncodes, _ = self.rt.gpt_generate(refer, rl, texts, seed, sample_ids, max_generate_length=max_generate_length,
                                                     top_k=top_k, top_p=TOP_P, temperature=TEMPERATURE,
-                                                    repetition_penalty=REPETITION_PENALTY, suppress_eos=suppress_eos)
+                                                    repetition_penalty=REPETITION_PENALTY, suppress_eos=suppress_eos, **pkw)
             code_list = [codes[b, : int(ncodes[b]) - 1] for b in range(B)]          # codes[:, :-1]  (:828)
         else:
             code_list = [np.asarray(c) for c in forced_codes]

@@ -114,6 +114,15 @@ typedef struct dtts_gpt_options {
                                      * codes and latents bit for bit; fewer workgroups decode longer on fewer CUs - what a session that runs
                                      * NEXT TO another request's diffusion should ask for: SynthesizerTrn.infer_stream passes 64); 0 = the
                                      * handle's "gpt_token_wgs" option (default 128: the fastest decode when nothing else runs) */
+    const int* prompt_codes;        /* HOST [B][prompt_stride] acoustic prompt of UnifiedVoice.inference_speech_valle (gpt/model.py:546-579): mel
+                                     * codes in [0, 8192) the session continues from, or NULL: the tortoise session [cond | text | 8192].  With a
+                                     * prompt row b's mel stream is [1, 8192, c_1 .. c_m] (the reference's fill id 1 sits at mel position 0; no stop
+                                     * token closes the prompt), all of it in the parallel prefill; ids 1, 8192 and the codes start in the
+                                     * repetition-penalty history; generated token j takes mel position m + 2 + j, and
+                                     * m + 3 + max_generate_length may not exceed the position table (1603 rows; one row is kept spare) */
+    const int* prompt_lens;         /* HOST [B] codes of each row's prompt, 0 .. prompt_stride (per-row lengths are an extension: the reference
+                                     * takes a rectangle); required with prompt_codes, refused without */
+    int prompt_stride;              /* row stride of prompt_codes */
 } dtts_gpt_options;
 
 /* struct_size + the reference's sampling call (vqvae/model_24k.py:782-792: top_p 0.8, temperature 0.8, repetition_penalty 2.0,
@@ -126,6 +135,9 @@ void dtts_gpt_options_init(dtts_gpt_options* o);
  * Outputs: codes HOST int32 [B][max_generate_length] (stop token included, rows padded with 8193), ncodes HOST [B],
  * latents_cm DEVICE [B,768,lat_stride]: column k = final_norm(ln_f(h)) at decode step k, i.e. the same values the
  * reference recomputes with UnifiedVoice.forward(return_latent=True).
+ * With opts->prompt_codes (inference_speech_valle, gpt/model.py:546-579) the prefill covers [cond | text | 1, 8192, prompt]
+ * and the codes returned are the generated ones only.  The decode-time latents are then the hidden states WITH THE PROMPT IN
+ * CONTEXT: they are not what forward(return_latent=True) on the generated codes alone returns (dtts_gpt_latents computes those).
  * = dtts_gpt_prefill + dtts_gpt_decode in 16-token hipGraph replays + dtts_gpt_finish; any B (groups of 16 rows run one
  * after the other).  Synchronises once per 16 tokens (finish flags; never when suppress_eos) and at the end (codes). */
 int dtts_gpt_generate(dtts_handle* h, const float* refer, const int* refer_lens, int Tr, const int* text, const int* text_lens,
