@@ -45,6 +45,10 @@ class DttsConvX3Info(C.Structure):
                 ("cols", C.c_int), ("workgroups", C.c_int)]
 
 
+class DttsAttnX3Info(C.Structure):
+    _fields_ = [("conv", DttsConvX3Info), ("attn_ksplit", C.c_int), ("attn_p1", C.c_int), ("attn_workgroups", C.c_int)]
+
+
 class DttsKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("launches", C.c_longlong), ("total_ms", C.c_double), ("union_ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -160,6 +164,9 @@ SIGNATURES = {
     "dtts_op_conv1d_x3": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(DttsConvX3Info),
                                     C.c_void_p]),
+    "dtts_attn_x3_image_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "dtts_op_attention_x3": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.POINTER(DttsAttnX3Info), C.c_void_p]),
     "dtts_op_philox_normal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_ulonglong, c_int_p, C.c_int, C.c_int, C.c_void_p]),
 }
 

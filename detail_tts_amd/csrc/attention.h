@@ -57,8 +57,13 @@ struct AttnPlanes {
     __host__ __device__ static inline size_t bytes(int B, int H, int T) { return (size_t)B * H * head_bytes(T); }
 };
 
-void launch_flash_attention(const AttnParams& p, hipStream_t stream);
-void launch_flash_attention_x3b(const AttnParams& p, hipStream_t stream);  // called by launch_flash_attention when p.planes
+// `chosen` (host side, may be null; filled by the split-precision launcher only, just before its launch): the key split actually used,
+// the product mode and the grid size.  How tests/test_gpu_attn_x3.py asserts that a case ran the variant it was written for.
+struct AttnX3Launch {
+    int ksplit = 0, p1 = 0, workgroups = 0;
+};
+void launch_flash_attention(const AttnParams& p, hipStream_t stream, AttnX3Launch* chosen = nullptr);
+void launch_flash_attention_x3b(const AttnParams& p, hipStream_t stream, AttnX3Launch* chosen = nullptr);  // called by launch_flash_attention when p.planes
 void set_attn_ksplit(int n);      // key ranges per (sample, head, query block) of attention_x3b launches of <= 2 samples that do not fill the CUs: 1 = off, 2 .. 4 (default: up to 4); process-wide
 void set_attn_ksplit_cus(int n);  // ... split only while workgroups x S <= n (default 256)
 int attn_ksplit();

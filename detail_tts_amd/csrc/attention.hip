@@ -253,14 +253,14 @@ static void launch_d(const AttnParams& p, dim3 grid, size_t lds, hipStream_t str
     }
 }
 
-void launch_flash_attention(const AttnParams& p, hipStream_t stream) {
+void launch_flash_attention(const AttnParams& p, hipStream_t stream, AttnX3Launch* chosen) {
     DTTS_REQUIRE(p.B > 0 && p.H > 0 && p.T > 0, "empty attention");
     dim3 grid(cdiv(p.T, QPB) * p.H * p.B);
     const char* tag = p.D == 48 ? "flash_attn_kernel<48>" : p.D == 64 ? "flash_attn_kernel<64>" : p.D == 96 ? "flash_attn_kernel<96>" : "flash_attn_kernel<192>";
     const double pairs = (double)p.B * p.H * (double)p.T * p.T * (p.causal ? 0.5 : 1.0);
     if (p.planes) {          // the split-precision kernel on the qkv conv's operand images (attention_x3b.hip)
         ProfScope ps3(p.p1 ? "flash_attn_x3b_kernel<fp16>" : "flash_attn_x3b_kernel", 4.0 * pairs * p.D, 4.0 * (double)p.B * p.H * p.D * p.T * 4.0, stream);
-        launch_flash_attention_x3b(p, stream);
+        launch_flash_attention_x3b(p, stream, chosen);
         return;
     }
     DTTS_REQUIRE(!p.p1, "one-product attention needs operand images (split-precision kernel: head dim 48, T5 bias)");

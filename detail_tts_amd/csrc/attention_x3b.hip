@@ -591,7 +591,7 @@ int attn_ksplit() {
 
 // operands = AttnPlanes images (p.planes).  Two workgroups per CU: 218 registers; the 1024 workgroups of the headline launch are two
 // full rounds of 512 (three per CU spilled).
-void launch_flash_attention_x3b(const AttnParams& p, hipStream_t stream) {
+void launch_flash_attention_x3b(const AttnParams& p, hipStream_t stream, AttnX3Launch* chosen) {
     DTTS_REQUIRE(p.D == 48 && p.bias_tab && !p.causal && !p.band && !p.ml_out && p.planes, "attention_x3b covers head dim 48 with the T5 bias on operand images");
     constexpr int NW = 4;
     const int base = cdiv(p.T, NW * QPW) * p.H * p.B;
@@ -612,6 +612,11 @@ void launch_flash_attention_x3b(const AttnParams& p, hipStream_t stream) {
     if (S > 1) {
         q.ksplit = S;
         x3_split_workspace(stream, (size_t)base * S, &q.kpart, &q.kcount);
+    }
+    if (chosen) {
+        chosen->ksplit = S;
+        chosen->p1 = p.p1 ? 1 : 0;
+        chosen->workgroups = base * S;
     }
     auto go = [&](auto kern) {
         lds_optin(reinterpret_cast<const void*>(kern), LDS_BYTES);

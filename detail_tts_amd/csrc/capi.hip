@@ -612,6 +612,24 @@ int dtts_op_conv1d_x3(dtts_handle* h, const char* name, const float* x, const in
     DTTS_API_END(h)
 }
 
+size_t dtts_attn_x3_image_bytes(int B, int H, int T) {
+    return (B > 0 && H > 0 && T > 0) ? dtts::AttnPlanes::bytes(B, H, T) : 0;
+}
+
+int dtts_op_attention_x3(dtts_handle* h, const char* name, const float* x, const int* lens, int B, int Cin, int T, int H,
+                         const float* bias_tab, int p1, int out_f32, void* y, void* img_out, dtts_attn_x3_info* info, void* stream) {
+    DTTS_API_BEGIN
+    dtts::ConvX3Launch c;
+    dtts::AttnX3Launch a;
+    h->m->op_attention_x3(name, x, lens, B, Cin, T, H, bias_tab, p1, out_f32, y, img_out, &c, &a, (hipStream_t)stream);
+    if (info) {
+        info->conv.epi = c.epi; info->conv.kw3 = c.kw3; info->conv.stages = c.stages; info->conv.ksplit = c.ksplit;
+        info->conv.p1 = c.p1; info->conv.epi_vec = c.epi_vec; info->conv.cols = c.cols; info->conv.workgroups = c.workgroups;
+        info->attn_ksplit = a.ksplit; info->attn_p1 = a.p1; info->attn_workgroups = a.workgroups;
+    }
+    DTTS_API_END(h)
+}
+
 int dtts_op_philox_normal(dtts_handle* h, float* out, int n, int B, unsigned long long seed, const int* sample_ids, int stage,
                           int step, void* stream) {
     DTTS_API_BEGIN

@@ -328,6 +328,10 @@ public:
     void op_conv1d_x3(const char* name, const float* x, const int* lens_host, int B, int Cin, int T, int Cout, int KW, int epi_act,
                       float out_scale, int gate, const float* badd, const float* res, int p1, int ksplit_max, float* y, ConvX3Launch* chosen,
                       hipStream_t s);
+    // The trunk attention's split-precision path alone: the 1 x 1 qkv conv `name` (144 H rows) writing the operand images, then
+    // flash_attn_x3b on them -> y (the proj conv's input planes, or fp32 rows with out_f32); img_out (may be null): a copy of the images.
+    void op_attention_x3(const char* name, const float* x, const int* lens_host, int B, int Cin, int T, int H, const float* bias_tab, int p1,
+                         int out_f32, void* y, void* img_out, ConvX3Launch* conv_chosen, AttnX3Launch* attn_chosen, hipStream_t s);
     void op_philox_normal(float* out, int n, int B, unsigned long long seed, const int* sample_ids_host, int stage, int step,
                           hipStream_t s);
 

@@ -1,6 +1,7 @@
 // Model runtime core: workspace arenas, int upload ring, weight lookup and binding, the conv launch (see model.h).
 #include "model.h"
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 namespace dtts {
@@ -411,6 +412,85 @@ void Model::op_conv1d_x3(const char* name, const float* x, const int* lens_host,
     p.ksplit_max = ksplit_max;
     run_conv(pc, p, s, chosen);
     register_cols(dl, nullptr, 0, T, s);                               // enqueued: forget this call's table
+}
+
+// The trunk attention's split-precision path on its own, for parity tests: split_weights -> split_planes (no affine, no activation,
+// lengths folded in) -> conv_x3 writing the Q / K / V operand images (EPI 2) -> flash_attn_x3b on those images, on one stream.  `name`
+// is a packed 1 x 1 conv of 144 H rows in QKVAttentionLegacy order; bias_tab is a DEVICE [H][129] table in AttnParams::bias_tab's
+// convention.  y receives the attention output before proj_out in the production form - the proj conv's input planes
+// [B][6 H][2][x3_tp(T)][8 fp16] (zero-filled here first: the kernel's contract is that unwritten columns keep the previous writer's
+// zeros) - or, out_f32, as fp32 rows [B][48 H][T].  That fp32 epilogue exists in flash_attn_x3b_kernel but the trunk never reaches it
+// today (attention_block takes the planes form whenever T + 1 < x3_tp(T), which always holds); it is kept, and reachable from here
+// only.  The image buffer is filled with 0xFF bytes (every fp16 a NaN) before the conv: in production it holds whatever its previous
+// user left, so the conv and the attention must agree exactly on which chunks are live; img_out (may be null) receives a copy.
+// Everything the launches require is checked before the first launch or upload.  No kernel and no production launch changes for this.
+void Model::op_attention_x3(const char* name, const float* x, const int* lens_host, int B, int Cin, int T, int H, const float* bias_tab,
+                            int p1, int out_f32, void* y, void* img_out, ConvX3Launch* conv_chosen, AttnX3Launch* attn_chosen, hipStream_t s) {
+    DTTS_REQUIRE(!weights_.empty(), "weights not bound");
+    DTTS_REQUIRE(name && x && y && bias_tab, "op_attention_x3: null argument");
+    DTTS_REQUIRE(B > 0 && B <= 65535 && T > 0 && T <= (1 << 16) && Cin > 0 && Cin <= (1 << 16) && H > 0 && H <= 64, "op_attention_x3: sizes");
+    DTTS_REQUIRE(Cin % 16 == 0, "op_attention_x3: input channels must be a multiple of 16 (one K-step; the split passes write 8-channel chunks)");
+    DTTS_REQUIRE(p1 == 0 || p1 == 1, "op_attention_x3: p1 is 0 or 1");
+    DTTS_REQUIRE(!p1 || Cin % 32 == 0, "op_attention_x3 one-product mode: input channels a multiple of 32");
+    constexpr int D = AttnPlanes::D;
+    const int Cout = 3 * D * H, CoutP = packed_cout(Cout);
+    DTTS_REQUIRE(CoutP % 128 == 0, "op_attention_x3: packed rows");
+    DTTS_REQUIRE((long long)(CoutP / 128) * cdiv(T, X3_BN) * B <= (1 << 22) && (long long)cdiv(T, 128) * H * B <= (1 << 22), "op_attention_x3: launch too large");
+    DTTS_REQUIRE((reinterpret_cast<unsigned long long>(y) & 15ull) == 0 && (!img_out || (reinterpret_cast<unsigned long long>(img_out) & 15ull) == 0),
+                 "op_attention_x3: 16-byte aligned outputs");
+    std::vector<int> l(B);
+    for (int b = 0; b < B; ++b) {
+        l[b] = lens_host ? lens_host[b] : T;
+        DTTS_REQUIRE(l[b] >= 0 && l[b] <= T, "op_attention_x3: lengths must lie in [0, T]");
+    }
+    const size_t w3_bytes = (size_t)(Cin / 8) * 2 * CoutP * 16, xs_bytes = x3_bytes(B, Cin, T), img_bytes = AttnPlanes::bytes(B, H, T);
+    const size_t out_bytes = out_f32 ? (size_t)B * H * D * T * sizeof(float) : x3_bytes(B, H * D, T);
+    DTTS_REQUIRE(w3_bytes + xs_bytes + img_bytes <= ((size_t)1 << 31), "op_attention_x3: workspace beyond 2 GiB");
+    PackedConv pc = conv(name, Cin, Cout, 1, true);
+    DTTS_REQUIRE(pc.CinP == Cin && pc.CoutP == CoutP && pc.w && pc.b, "op_attention_x3: packed weight shape (144 H rows, with bias)");
+    // ---- nothing has been launched or uploaded up to here
+    ws().ensure(w3_bytes + xs_bytes + img_bytes + 8192);
+    void* w3 = ws().raw(w3_bytes);
+    void* xs = ws().raw(xs_bytes);
+    void* img = ws().raw(img_bytes);
+    DTTS_CHECK_HIP(hipMemsetAsync(img, 0xFF, img_bytes, s));
+    if (!out_f32) DTTS_CHECK_HIP(hipMemsetAsync(y, 0, out_bytes, s));
+    launch_split_weights(pc.w, 1, pc.CinP, pc.CoutP, w3, s);
+    pc.w3 = w3;
+    const int* dl = upload_ints(l.data(), B, s);
+    launch_split_planes(x, (long long)Cin * T, T, nullptr, ACT_NONE, dl, T, B, Cin, xs, s);
+    register_cols(dl, l.data(), B, T, s);
+    ConvParams p = cp(x, Cin, static_cast<float*>(img), Cout, B, T, T, dl);
+    with_planes(p, xs, T);
+    p.p1 = p1;
+    p.qkv_planes = img;                                  // as attention_block sets them
+    p.qkv_heads = H;
+    p.qkv_nt64 = AttnPlanes::nt64(T);
+    p.qkv_tq = AttnPlanes::tq(T);
+    p.qkv_qscale = (1.f / std::sqrt((float)D)) * 1.4426950408889634f;
+    run_conv(pc, p, s, conv_chosen);
+    register_cols(dl, nullptr, 0, T, s);                 // enqueued: forget this call's table
+    if (img_out) DTTS_CHECK_HIP(hipMemcpyAsync(img_out, img, img_bytes, hipMemcpyDeviceToDevice, s));
+    AttnParams a;
+    a.qkv = static_cast<const float*>(img);
+    a.lens = dl;
+    a.T = T;
+    a.B = B;
+    a.H = H;
+    a.D = D;
+    a.scale = 1.f / std::sqrt((float)D);
+    a.bias_tab = bias_tab;
+    a.planes = img;
+    a.p1 = p1;
+    if (out_f32) {
+        a.out = static_cast<float*>(y);
+        a.o_bs = (long long)H * D * T;
+        a.o_cs = T;
+    } else {
+        a.out_x3 = y;
+        a.x3_tp = x3_tp(T);
+    }
+    launch_flash_attention(a, s, attn_chosen);
 }
 
 void Model::op_philox_normal(float* out, int n, int B, unsigned long long seed, const int* sample_ids_host, int stage, int step,

@@ -993,6 +993,35 @@ class Runtime:
                                             C.byref(info), self._stream()))
         return y, {k: int(getattr(info, k)) for k, _ in _lib.DttsConvX3Info._fields_}, guard
 
+    def op_attention_x3(self, name, x, heads, bias_tab, lens=None, p1=0, out_f32=False):
+        """The trunk attention's split-precision path alone (csrc/attention_x3b.hip): the packed 1 x 1 conv `name` of 144 * heads rows
+        writes the Q / K / V operand images (conv_x3's EPI 2) and the attention runs on them with bias_tab [heads, 129] ->
+        (y, image, info, guard).  y: the production output form, the projection conv's input planes [B][6 heads][2][Tp][8 fp16] as raw
+        bytes (uint8, zero-filled by the call), or with out_f32 the fp32 rows [B, 48 heads, T], handed over filled with NaN (the
+        kernel leaves columns >= len untouched).  guard: one more sample-sized slab directly behind y in the same allocation, NaN
+        (bytes 0xFF): a store past the batch shows there.  image: the operand images as raw bytes (the buffer is filled with 0xFF
+        before the conv).  info: what the two launchers chose (conv: epi, ..., attn_ksplit, attn_p1, attn_workgroups)."""
+        _check(x, "x"); _check(bias_tab, "bias_tab")
+        B, Cin, T = x.shape
+        heads = int(heads)
+        if tuple(bias_tab.shape) != (heads, 129):
+            raise ValueError("bias_tab must be [heads, 129]")
+        nimg = int(self.lib.dtts_attn_x3_image_bytes(B, max(heads, 1), T))
+        image = torch.zeros((max(nimg, 16),), device=self.device, dtype=torch.uint8)
+        if out_f32:
+            buf = torch.full((B + 1, 48 * max(heads, 1), T), float("nan"), device=self.device, dtype=torch.float32)
+        else:
+            tp = (T + 191) // 192 * 192 + 2
+            buf = torch.full((B + 1, 6 * max(heads, 1) * 2 * tp * 16), 0xFF, device=self.device, dtype=torch.uint8)
+        y, guard = buf[:B], buf[B]
+        li = _ints(lens)
+        info = _lib.DttsAttnX3Info()
+        self._rc(self.lib.dtts_op_attention_x3(self.h, name.encode(), _ptr(x), li[0] if li else None, B, Cin, T, heads, _ptr(bias_tab), int(p1),
+                                               int(bool(out_f32)), _ptr(y), _ptr(image), C.byref(info), self._stream()))
+        out = {k: int(getattr(info.conv, k)) for k, _ in _lib.DttsConvX3Info._fields_}
+        out.update(attn_ksplit=int(info.attn_ksplit), attn_p1=int(info.attn_p1), attn_workgroups=int(info.attn_workgroups))
+        return y, image[:nimg], out, guard
+
     def diff_p_sample(self, x, code_emb, step, seed, sample_ids, lens=None, noise=None, return_x0=False):
         """one GaussianDiffusion.p_sample at sampling step `step` (49 = first): returns the new x (and pred_xstart)"""
         _check(x, "x"); _check(code_emb, "code_emb"); _check(noise, "noise")

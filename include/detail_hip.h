@@ -655,6 +655,25 @@ typedef struct dtts_conv_x3_info {
 int dtts_op_conv1d_x3(dtts_handle* h, const char* name, const float* x, const int* lens, int B, int Cin, int T, int Cout, int KW,
                       int epi_act, float out_scale, int gate, const float* badd, const float* res, int p1, int ksplit_max, float* y,
                       dtts_conv_x3_info* info, void* stream);
+/* The diffusion trunk's split-precision attention path on its own (csrc/attention.h): the packed 1 x 1 conv `name` of 144 H rows in
+ * QKVAttentionLegacy order (head h = rows 144 h + [q 48 | k 48 | v 48]) runs through the split-precision kernel with the epilogue that
+ * writes the attention's Q / K / V operand images, then the split-precision attention (head dim 48) runs on them with bias_tab DEVICE
+ * [H][129]: out[h, :, t] = sum_s softmax_s(q_t . k_s / sqrt(48) + bias_tab[h][clamp(s - t, -64, 64) + 64]) v_s over s < len.
+ * x DEVICE [B, Cin, T], Cin % 16 == 0 (% 32 with p1 = 1, the one-product mode), independent of 48 H; lens HOST in [0, T] (null -> T).
+ * y DEVICE, 16-byte aligned: out_f32 = 0 - the output as the projection conv's input planes [B][6 H][2][round_up(T, 192) + 2][8 fp16]
+ * (two fp16 planes of 16 x value, column t + 1; zero-filled by the call, columns >= len stay zero); out_f32 = 1 - fp32 [B][48 H][T],
+ * columns >= len untouched.  img_out (may be null) DEVICE: a copy of the operand images, dtts_attn_x3_image_bytes(B, H, T) bytes; the
+ * image buffer is filled with 0xFF bytes before the conv, so what neither kernel may touch still reads as fp16 NaN.  Anything the
+ * launches cannot take is refused before a launch.  info (may be null): what the two launchers chose. */
+typedef struct dtts_attn_x3_info {
+    dtts_conv_x3_info conv; /* the qkv conv (epi == 2) */
+    int attn_ksplit;        /* key ranges per (sample, head, 128-query block) actually used */
+    int attn_p1;            /* 1: one fp16 product */
+    int attn_workgroups;    /* grid size of the attention */
+} dtts_attn_x3_info;
+size_t dtts_attn_x3_image_bytes(int B, int H, int T);
+int dtts_op_attention_x3(dtts_handle* h, const char* name, const float* x, const int* lens, int B, int Cin, int T, int H,
+                         const float* bias_tab, int p1, int out_f32, void* y, void* img_out, dtts_attn_x3_info* info, void* stream);
 /* The device sampler on given logits rows: HF RepetitionPenalty / Temperature / TopK / TopP processors as the reference's
  * generate() applies them (vqvae/model_24k.py:786-792) + the inverse-CDF draw on uniforms[r].  logits DEVICE [R][V] (R <= 16),
  * history HOST [R][hist_len] ids present in the row's input_ids, uniforms DEVICE [R] -> tokens HOST [R].  Synchronises. */
