@@ -58,22 +58,6 @@ struct ConvParams {
     void* qkv_planes = nullptr;
     int qkv_heads = 0, qkv_nt64 = 0, qkv_tq = 0;
     float qkv_qscale = 1.f;        // softmax scale * log2(e), folded into the Q planes
-    // conv_x3 only, filled by its launcher: split-K for launches far smaller than the chip (batch 1).  The channel blocks are divided
-    // among `ksplit` workgroups per output tile; each leaves its raw accumulators in `kpart`, the last to arrive (counter in `kcount`)
-    // sums them in split order - deterministic - and runs the epilogue.
-    // conv_x3 only: the GroupNorm that FOLLOWS this conv folded into its epilogue (conv_x3.h "fused GroupNorm"): the tile publishes
-    // partial statistics of its output, waits for the partials of the groups its rows belong to, applies GN (x AdaGN (1 + scale) + shift),
-    // the activation and the fp16 split in registers and writes the consumer's operand planes.  y may then be null (no fp32 output).
-    void* gn_out3 = nullptr;           // planes of the normalised output [B][Cout/8][2][x3_tp][8 fp16]; null = no fused norm
-    const float *gn_gamma = nullptr, *gn_beta = nullptr;
-    const float* gn_ada = nullptr;     // AdaGN table: scale = 1 + ada[c * stride + off], shift = ada[(Cout + c) * stride + off]
-    int gn_ada_stride = 0;
-    const int* gn_ada_idx = nullptr;   // [B] per-sample offset `off` into the table (null: 0)
-    int gn_act = ACT_NONE, gn_groups = 32;
-    float gn_eps = 1e-5f;
-    void* gn_xch = nullptr;            // exchange words (conv_x3_gn_xch_bytes), one buffer per launch stream
-    unsigned gn_tag = 0;               // != 0, unique per launch on this buffer
-    int* gn_err = nullptr;             // raised (system scope) when a poll gives up
     // conv_x3 only, ragged batches: the launch's LIVE (sample, N tile) columns as a table (packed sample << 8 | N tile, samples counted
     // from cols_b0), so that the grid holds no workgroup that would exit at once: with per-sample column ranges in the id space and the
     // XCD-contiguous id order, the XCDs holding short samples ran out of tiles early (Model::register_cols builds it; null: all columns)
@@ -85,6 +69,9 @@ struct ConvParams {
     int next_c8 = 0, next_tp = 0, next_halo = 0, next_act = ACT_NONE;
     float next_slope = 0.f;
     int* next_sat = nullptr;       // raised when a scaled value leaves fp16's range (as launch_split_planes_ex)
+    // conv_x3 only, filled by its launcher: split-K for launches far smaller than the chip (batch 1).  The channel blocks are divided
+    // among `ksplit` workgroups per output tile; each leaves its raw accumulators in `kpart`, the last to arrive (counter in `kcount`)
+    // sums them in split order - deterministic - and runs the epilogue.
     int ksplit = 1;
     int ksplit_max = 0;            // conv_x3: caller's cap on the split (0: the launcher's rule)
     int p1 = 0;                    // conv_x3: 1 = one fp16 product (plane 0 of both operands, 32 channels per K-step) instead of three (conv_x3.h)

@@ -42,7 +42,7 @@ void launch_gn_split_planes(const float* x, long long x_bs, int x_cs, const int*
 // p.p1 (the trunk's fp16 mode, option "trunk_fp16"): ONE product h0 h0' on plane 0 of the same images, 32 channels per K-step, instead of
 // three (Cin a multiple of 32, no gate); plane 1 is neither fetched nor multiplied (conv_x3.hip)
 // `chosen` (host side, may be null): what the launcher picked for this launch, filled just before the launch - the instantiation
-// (epi 0..4, kw3, stages 2..4, p1), the split, the epilogue form (epi_vec 1: LDS-staged 16-byte stores, 0: scalar), whether a live-column
+// (epi 0, 1, 2 or 4, kw3, stages 2..4, p1), the split, the epilogue form (epi_vec 1: LDS-staged 16-byte stores, 0: scalar), whether a live-column
 // table is attached and the grid size.  How tests/test_gpu_conv_x3.py asserts that a case ran the variant it was written for.
 struct ConvX3Launch {
     int epi = -1, kw3 = 0, stages = 0, ksplit = 0, p1 = 0, epi_vec = 0, cols = 0, workgroups = 0;
@@ -57,23 +57,6 @@ void set_conv_stages(int n);
 // between launches (the reducing workgroup / wave resets its counter).
 constexpr size_t X3_SLAB_FLOATS = 96 * 256, X3_MAX_SLABS = 1024, X3_SPLIT_COUNTERS = 4096;
 void x3_split_workspace(hipStream_t s, size_t nslabs, float** part, int** count);
-
-// ---- fused GroupNorm (p.gn_out3): the norm + activation + split that FOLLOWS a trunk conv runs in that conv's epilogue.  A tile holds
-// 128 rows x 192 columns of one sample; a GroupNorm group is 24 channels x all T columns, so a tile needs the statistics of the <= 7
-// groups its rows touch over ALL N tiles (and, for the groups that straddle its row range, of the neighbouring M tile).  Every wave
-// publishes {mean, M2, count, tag} of its 8 row chunks x 96 columns as 16-byte words (agent scope, the token kernel's protocol), a
-// tile polls the words of its groups, combines them in a fixed order (Chan's parallel variance: deterministic, no cancellation) and
-// normalises its accumulators where they sit.  Tiles of a fused launch are ordered (sample, M tile, N tile): a tile waits only for
-// tiles at most 2 N - 1 positions ahead of it in dispatch order, so at most that many workgroups per XCD can ever be waiting for an
-// undispatched one - with N <= GN_FUSE_MAX_NT that is far below the workgroup slots of an XCD even with a second fused launch on
-// another stream and the persistent GPT token kernel holding CUs.  Longer sequences keep the separate gn_split_planes
-// pass.  Split-K launches (batches 1 - 2) carry it too (round 5): only a tile's reducing workgroup reaches the epilogue - built for
-// configs[1] (a batch-1 forward is a chain of ~125 launches of 10 - 40 us), measured SLOWER there as well (forward pair 2751 -> 2896 us:
-// the fused tails cost a conv ~10 us, the pass they replace ~5 us + a launch gap), so it stays an option (gn_fuse), default off.
-constexpr int GN_FUSE_MAX_NT = 6;
-size_t conv_x3_gn_xch_bytes(int B, int Cout, int T);
-// whether launch_conv_x3 can run p with the fused norm (else: conv to p.y, then launch_gn_split_planes)
-bool conv_x3_gn_fusable(int Cout, int CoutP, int Cin, int KW, int groups, int B, int T);
 
 // ---- dilated / wide-kernel variant (conv_x3d.hip): HiFiGAN ResBlock1 convs, k = 3 / 7 / 11, any dilation with (k - 1) dil <= 64
 constexpr int X3D_HALO = 32;                          // left zero columns of its planes (>= the largest pad: (11 * 5 - 5) / 2 = 25)

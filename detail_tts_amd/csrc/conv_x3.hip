@@ -28,12 +28,6 @@ constexpr int BM = 128, BN = X3_BN;
 constexpr int WTILE = NK * BM * 16;                  // 8 KiB: [kind][128 rows][16 B]
 constexpr int XMAIN = NK * BN * 16;                  // 12 KiB: [kind][192 columns][16 B]
 constexpr int XBUF = XMAIN + NK * 2 * 16;            // + 2 halo columns per kind
-// fused GroupNorm epilogue (EPI 3): exchange words are 16-byte {mean, M2, count, tag}, agent-scope (sc1) raw-buffer accesses
-typedef unsigned gn_u4 __attribute__((ext_vector_type(4)));
-constexpr int GN_AUX_SC1 = 16;                       // gfx940+ cache policy bit 4 = sc1
-constexpr int GN_MAXW = 8;                           // (unused words area kept small)
-constexpr int GN_SPIN_LIMIT = 1 << 22;
-static_assert(7 * 32 <= 256 && 3 * GN_FUSE_MAX_NT <= 32 && (4 * 16 * 104 + 4 * GN_MAXW + 16 + 2 * BM) * 4 <= 2 * (WTILE + XBUF), "fused GroupNorm epilogue: LDS / lanes");
 
 __global__ __launch_bounds__(256) void split_weights_kernel(const float* __restrict__ wp, int C8, int CoutP, uint4* __restrict__ out) {
     const int m = blockIdx.x * 256 + threadIdx.x, c8 = blockIdx.y, tap = blockIdx.z;
@@ -277,7 +271,7 @@ __global__ __launch_bounds__(1024) void gn_split_planes_reg_kernel(const float* 
 // (chunk_of) and a block is 4 chunks wide - while the step issues 12 MFMAs (2 x 3 tiles x 2 k-halves) for 32 channels instead of 36.
 // No piece, fragment read or MFMA of plane 1 exists in these instantiations; a tile runs half as many steps and barriers.
 template <int EPI, bool KW3, int NSTG, bool P1 = false>
-__global__ __launch_bounds__(256, (NSTG == 2 && EPI != 3) ? 3 : 2) void conv_x3_kernel(ConvParams p) {
+__global__ __launch_bounds__(256, NSTG == 2 ? 3 : 2) void conv_x3_kernel(ConvParams p) {
     constexpr int KW = KW3 ? 3 : 1, D = NSTG - 1;       // D: prefetch distance in steps (W, X of k = 1) / channel blocks (X of k = 3)
     constexpr int CB = P1 ? 4 : 2;                      // 8-channel chunks of a K-step's channel block
     constexpr int NT = P1 ? 2 : 3;                      // MFMA terms of a K-step: (k-half, k-half) pairs / split cross products
@@ -289,11 +283,9 @@ __global__ __launch_bounds__(256, (NSTG == 2 && EPI != 3) ? 3 : 2) void conv_x3_
     const int mtiles = p.CoutP / BM, ntiles = (p.Nout + BN - 1) / BN;
     const int Ls = xcd_remap(blockIdx.x, gridDim.x);
     const int S = p.ksplit, L = Ls / S, z = Ls - L * S;                  // the splits of a tile are adjacent logical ids (one XCD)
-    // EPI 3 (fused GroupNorm): (sample, M tile, N tile) order - a tile waits for statistics of tiles at most 2 N - 1 ids ahead (conv_x3.h)
-    const bool mt_major = EPI == 3 && !(p.ablate & 16);
-    int mt = mt_major ? (L / ntiles) % mtiles : L % mtiles;
-    int b = mt_major ? L / (ntiles * mtiles) : (L / mtiles) / ntiles;
-    int nti = mt_major ? L % ntiles : (L / mtiles) - b * ntiles;
+    int mt = L % mtiles;
+    int b = (L / mtiles) / ntiles;
+    int nti = (L / mtiles) - b * ntiles;
     int bn = L / mtiles;                                                 // (sample, N tile) column of this tile: index into p.cols
     if (EPI == 2 && mtiles > 6 && mtiles % 6 == 0 && !(p.ablate & 1024)) {
         // Tall launches (the qkv conv: 18 M tiles): with the M tiles of an X tile adjacent, the ~30 workgroups an XCD runs at a time
@@ -307,7 +299,7 @@ __global__ __launch_bounds__(256, (NSTG == 2 && EPI != 3) ? 3 : 2) void conv_x3_
         b = bn / ntiles;
         nti = bn - b * ntiles;
     }
-    if (p.cols) {                                                        // ragged batch: live columns only (never with EPI 3)
+    if (p.cols) {                                                        // ragged batch: live columns only
         const int pk = __builtin_amdgcn_readfirstlane(p.cols[bn]);
         b = (pk >> 8) - p.cols_b0;
         nti = pk & 255;
@@ -404,22 +396,6 @@ __global__ __launch_bounds__(256, (NSTG == 2 && EPI != 3) ? 3 : 2) void conv_x3_
     // the tile's 128 bias values -> LDS (read back in the epilogue; the first K-step barrier orders the write)
     float* bias_s = reinterpret_cast<float*>(smem + XOFF + NSTG * XBUF);
     if (tid < BM) bias_s[tid] = (p.bias && m0 + tid < p.Cout) ? p.bias[m0 + tid] : 0.f;
-    // fused GroupNorm: the norm's per-row affine with the AdaGN (1 + scale, shift) folded in -> LDS now, so that the kernel's tail has
-    // no global round trip left but the statistics exchange itself:  y_hat = (y - mu) rstd ga + gb
-    float* ga_s = bias_s + BM + 4;
-    float* gb_s = ga_s + BM;
-    if (EPI == 3 && tid < BM) {
-        const int c = m0 + tid;
-        float ga = p.gn_gamma[c], gb = p.gn_beta[c];
-        if (p.gn_ada) {
-            const float* ad = p.gn_ada + (p.gn_ada_idx ? (long long)p.gn_ada_idx[b] : 0);
-            const float sc = 1.f + ad[(long long)c * p.gn_ada_stride], sh = ad[(long long)(p.Cout + c) * p.gn_ada_stride];
-            ga *= sc;
-            gb = gb * sc + sh;
-        }
-        ga_s[tid] = ga;
-        gb_s[tid] = gb;
-    }
 
     int c16 = 0, tap = 0;                               // the step being computed
     int sw = 0, sx = 0;                                 // its W stage / X buffer; the step being issued uses (sw + D) % NSTG, (sx + D) % NSTG
@@ -626,244 +602,6 @@ __global__ __launch_bounds__(256, (NSTG == 2 && EPI != 3) ? 3 : 2) void conv_x3_
                     for (int r = 0; r < 16; ++r)
                         acc[i][j][r] += __hip_atomic_load(src + ((i * 3 + j) * 16 + r) * 256, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-    }
-
-    if (EPI == 3) {
-        // ---- fused GroupNorm epilogue (conv_x3.h).  Phases: (1) y = acc * s + bias (+ residual, transposed through the LDS so that its
-        // rows arrive 16 B per lane); (2) two-pass statistics of the wave's 8 row chunks x 96 columns -> published as tagged words;
-        // (3) the fp32 rows of y, if anybody needs them (16-byte stores through the LDS) - issued BEFORE the poll so that the neighbours'
-        // latency is spent on useful stores; (4) poll the words of the tile's groups, combine, per-row coefficients; (5) normalise,
-        // activate, split and store the planes from the registers (a lane pair exchanges half chunks: v_permlane32_swap).
-        constexpr int EP_LD = 104;
-        if (p.ablate & 64) return;
-        __syncthreads();                                               // every wave has left the K loop: its LDS stages are free
-        float* st = reinterpret_cast<float*>(smem) + wave * (16 * EP_LD);
-        float* prt = reinterpret_cast<float*>(smem) + 4 * 16 * EP_LD;   // [word][4]: mean, M2, count of one (chunk, N tile, column half)
-        float* gst = prt + 4 * GN_MAXW;                                 // [8 groups][2]: mean, rstd
-        float* sa = gst + 16;                                           // [128 rows]: y -> a y + d
-        float* sd = sa + BM;
-        const int ncol0 = n0 + wn0;
-        const float* rb = p.res ? p.res + (long long)(p.res_bmod ? b % p.res_bmod : b) * p.res_bs : nullptr;
-        // every residual load of the tile is in flight before the first one is used: one memory latency instead of four
-        float4 rv[4][6];
-        if (rb) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    const int idx = lane + 64 * k, rl = idx / 24, c4 = idx - rl * 24, row = m0 + wm0 + (q >> 1) * 32 + (q & 1) * 16 + rl, n = ncol0 + c4 * 4;
-                    const float* src = rb + (long long)row * p.res_cs + n;
-                    rv[q][k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (n + 3 < nvalid) rv[q][k] = *reinterpret_cast<const float4*>(src);
-                    else if (n < nvalid) {
-                        rv[q][k].x = src[0];
-                        if (n + 1 < nvalid) rv[q][k].y = src[1];
-                        if (n + 2 < nvalid) rv[q][k].z = src[2];
-                    }
-                }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int i = q >> 1, rowt0 = wm0 + i * 32 + (q & 1) * 16;
-            if (rb) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    const int idx = lane + 64 * k, rl = idx / 24, c4 = idx - rl * 24;
-                    *reinterpret_cast<float4*>(st + rl * EP_LD + c4 * 4) = rv[q][k];
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_wave_barrier();
-            }
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-#pragma unroll
-                for (int rr = 0; rr < 8; ++rr) {
-                    const int r = (q & 1) * 8 + rr, rl = (rr & 3) + 8 * (rr >> 2) + 4 * lhi;
-                    float v = acc[i][j][r] * XS_ACC_SCALE + bias_s[rowt0 + rl];
-                    if (rb) v += p.res_scale * st[rl * EP_LD + j * 32 + l31];
-                    acc[i][j][r] = v;
-                }
-            if (rb) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
-        // ---- (2) statistics of chunk ck = i * 4 + (r >> 2) (8 rows x this wave's valid columns), two passes in registers
-        bool okj[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) okj[j] = ncol0 + j * 32 + l31 < nvalid;
-        const int nvh = min(max(nvalid - ncol0, 0), 96);
-        const float cnt = 8.f * (float)nvh, rcnt = nvh > 0 ? 1.f / cnt : 0.f;
-        float s8[8];
-#pragma unroll
-        for (int ck = 0; ck < 8; ++ck) {
-            float a = 0.f;
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) a += okj[j] ? acc[ck >> 2][j][4 * (ck & 3) + e] : 0.f;
-            s8[ck] = a;
-        }
-        const float tot = wave_sum8(s8, lane);
-#pragma unroll
-        for (int ck = 0; ck < 8; ++ck) {
-            const float mu = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, tot), 8 * ck)) * rcnt;
-            float a = 0.f;
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float dv = acc[ck >> 2][j][4 * (ck & 3) + e] - mu;
-                    a += okj[j] ? dv * dv : 0.f;
-                }
-            s8[ck] = a;
-        }
-        const float m2 = wave_sum8(s8, lane);
-        const int C8o = p.Cout >> 3, NTs = ntiles;
-        const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(p.gn_xch, (short)0, (int)((size_t)p.B * C8o * NTs * 2 * 16), 0x00020000);
-        if ((lane & 7) == 0) {
-            const int chunk = ((m0 + wm0) >> 3) + (lane >> 3);
-            const gn_u4 wv = {__float_as_uint(tot * rcnt), __float_as_uint(m2), __float_as_uint(cnt), p.gn_tag};
-            __builtin_amdgcn_raw_buffer_store_b128(wv, xrs, (((b * C8o + chunk) * NTs + nti) * 2 + (wave & 1)) * 16, 0, GN_AUX_SC1);
-        }
-        // ---- (3) fp32 rows of y (residual stream), 16 bytes per lane through the LDS
-        if (p.y) {
-            float* yb = p.y + (long long)b * p.y_bs;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int i = q >> 1, rowt0 = wm0 + i * 32 + (q & 1) * 16;
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-#pragma unroll
-                    for (int rr = 0; rr < 8; ++rr) {
-                        const int r = (q & 1) * 8 + rr, rl = (rr & 3) + 8 * (rr >> 2) + 4 * lhi;
-                        st[rl * EP_LD + j * 32 + l31] = acc[i][j][r];
-                    }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    const int idx = lane + 64 * k, rl = idx / 24, c4 = idx - rl * 24, row = m0 + rowt0 + rl, n = ncol0 + c4 * 4;
-                    const float4 a4 = *reinterpret_cast<const float4*>(st + rl * EP_LD + c4 * 4);
-                    if (n < nvalid) {
-                        float* dst = yb + (long long)row * p.y_cs + n;
-                        if (n + 3 < nvalid) *reinterpret_cast<float4*>(dst) = a4;
-                        else {
-                            dst[0] = a4.x;
-                            if (n + 1 < nvalid) dst[1] = a4.y;
-                            if (n + 2 < nvalid) dst[2] = a4.z;
-                        }
-                    }
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
-        if (p.ablate & 128) return;
-        // ---- (4) the statistics of the groups this tile's rows belong to.  Thread (group slot, k): k = (chunk of the group, valid N
-        // tile) polls the TWO column-half words of that (chunk, N tile) and combines them; a group's 3 x nvt pairs sit in one 16- or
-        // 32-lane segment of a wave and are combined there with xor shuffles (Chan's parallel variance, fixed order: deterministic)
-        const int cpg8 = (p.Cout / p.gn_groups) >> 3;                                  // chunks per group (3)
-        const int ct0 = m0 >> 3, g_lo = ct0 / cpg8, g_hi = (ct0 + BM / 8 - 1) / cpg8;
-        const int nvt = (nvalid + BN - 1) / BN, ppg = cpg8 * nvt;                      // valid N tiles; pairs per group (<= 18)
-        const int SL = ppg <= 16 ? 16 : 32;
-        {
-            const int gs = tid / SL, k = tid - gs * SL;
-            const bool active = gs <= g_hi - g_lo && k < ppg;
-            float pn = 0.f, pm = 0.f, pq = 0.f;
-            if (active) {
-                const int ch = k / nvt, nt = k - ch * nvt;
-                const int off = (((b * C8o + (g_lo + gs) * cpg8 + ch) * NTs + nt) * 2) * 16;
-                gn_u4 v0, v1;
-                int spins = 0;
-                for (;;) {
-                    v0 = __builtin_amdgcn_raw_buffer_load_b128(xrs, off, 0, GN_AUX_SC1);
-                    v1 = __builtin_amdgcn_raw_buffer_load_b128(xrs, off + 16, 0, GN_AUX_SC1);
-                    if ((v0.w == p.gn_tag && v1.w == p.gn_tag) || (p.ablate & 8)) break;
-                    if (++spins > GN_SPIN_LIMIT) {
-                        __hip_atomic_store(p.gn_err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-                const float m0v = __uint_as_float(v0.x), q0v = __uint_as_float(v0.y), n0v = __uint_as_float(v0.z);
-                const float m1v = __uint_as_float(v1.x), q1v = __uint_as_float(v1.y), n1v = __uint_as_float(v1.z);
-                pn = n0v + n1v;
-                const float rn = pn > 0.f ? 1.f / pn : 0.f, dm = m0v - m1v;
-                pm = (n0v * m0v + n1v * m1v) * rn;
-                pq = q0v + q1v + n0v * n1v * rn * dm * dm;
-            }
-            float N = pn, S = pn * pm;
-            for (int o = 1; o < SL; o <<= 1) {
-                N += __shfl_xor(N, o);
-                S += __shfl_xor(S, o);
-            }
-            const float mu = N > 0.f ? S / N : 0.f, dmu = pm - mu;
-            float M2 = pq + pn * dmu * dmu;
-            for (int o = 1; o < SL; o <<= 1) M2 += __shfl_xor(M2, o);
-            if (active && k == 0) {
-                gst[2 * gs] = mu;
-                gst[2 * gs + 1] = rsqrtf((N > 0.f ? M2 / N : 0.f) + p.gn_eps);
-            }
-        }
-        __syncthreads();
-        if (tid < BM) {                                                                // y_hat = a y + d per row
-            const int g = (m0 + tid) / (p.Cout / p.gn_groups) - g_lo;
-            const float a = gst[2 * g + 1] * ga_s[tid];
-            sa[tid] = a;
-            sd[tid] = gb_s[tid] - gst[2 * g] * a;
-        }
-        __syncthreads();
-        if (p.ablate & 256) return;
-        // ---- (5) normalise + activation + split -> the consumer's planes.  Columns of the tile beyond the sample's length are
-        // written as zeros (a k = 3 consumer reads one column past the end), and so are the halo columns next to the valid range.
-        const int Tp = p.x3_tp;
-        unsigned char* ob = static_cast<unsigned char*>(p.gn_out3) + (size_t)b * C8o * NPL * Tp * 16;
-        const bool silu = p.gn_act == ACT_SILU;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const int n = ncol0 + j * 32 + l31;
-                const bool ok = n < nvalid;
-#pragma unroll
-                for (int k2 = 0; k2 < 2; ++k2) {
-                    const int r16 = wm0 + i * 32 + 16 * k2;
-                    float ve[4], vo[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int ra = r16 + e + 4 * lhi, rb2 = ra + 8;
-                        float x0 = acc[i][j][8 * k2 + e] * sa[ra] + sd[ra], x1 = acc[i][j][8 * k2 + 4 + e] * sa[rb2] + sd[rb2];
-                        if (silu) {
-                            x0 = x0 * __frcp_rn(1.f + __expf(-x0));
-                            x1 = x1 * __frcp_rn(1.f + __expf(-x1));
-                        }
-                        ve[e] = ok ? x0 * XS_SCALE_X : 0.f;
-                        vo[e] = ok ? x1 * XS_SCALE_X : 0.f;
-                    }
-                    unsigned we0[2], we1[2], wo0[2], wo1[2];
-                    split_pair(ve[0], ve[1], we0[0], we1[0]);
-                    split_pair(ve[2], ve[3], we0[1], we1[1]);
-                    split_pair(vo[0], vo[1], wo0[0], wo1[0]);
-                    split_pair(vo[2], vo[3], wo0[1], wo1[1]);
-                    const auto s00 = __builtin_amdgcn_permlane32_swap(we0[0], wo0[0], false, false);
-                    const auto s01 = __builtin_amdgcn_permlane32_swap(we0[1], wo0[1], false, false);
-                    const auto s10 = __builtin_amdgcn_permlane32_swap(we1[0], wo1[0], false, false);
-                    const auto s11 = __builtin_amdgcn_permlane32_swap(we1[1], wo1[1], false, false);
-                    const int c8 = ((m0 + r16) >> 3) + lhi;
-                    unsigned char* o = ob + ((size_t)c8 * NPL * Tp + n + X3_HALO) * 16;
-                    if (p.ablate & 32) continue;
-                    *reinterpret_cast<uint4*>(o) = make_uint4(s00[0], s01[0], s00[1], s01[1]);
-                    *reinterpret_cast<uint4*>(o + (size_t)Tp * 16) = make_uint4(s10[0], s11[0], s10[1], s11[1]);
-                }
-            }
-        if (tid < 64) {                                                                // halo columns: 16 chunks x 2 planes each
-            const int side = tid >> 5, c8 = (m0 >> 3) + ((tid & 31) >> 1), pl = tid & 1;
-            const int tp = side == 0 ? 0 : n0 + BN + X3_HALO;
-            if (side == 0 ? n0 == 0 : (n0 + BN >= nvalid && tp < Tp))
-                *reinterpret_cast<uint4*>(ob + ((size_t)(c8 * NPL + pl) * Tp + tp) * 16) = make_uint4(0, 0, 0, 0);
-        }
-        return;
     }
 
     if (EPI != 2 && p.epi_vec) {
@@ -1260,21 +998,9 @@ void x3_split_workspace(hipStream_t s, size_t nslabs, float** part, int** count)
     *count = w.count;
 }
 
-size_t conv_x3_gn_xch_bytes(int B, int Cout, int T) { return (size_t)B * (Cout / 8) * cdiv(T, BN) * 2 * 16; }
-
 static long long split_tiles_max() {
     static const long long v = env_int("DTTS_CONV_KSPLIT_MAXTILE", 128);
     return v;
-}
-
-bool conv_x3_gn_fusable(int Cout, int CoutP, int Cin, int KW, int groups, int B, int T) {
-    if (Cout != CoutP || Cout % BM || groups <= 0 || Cout % groups || Cout / groups != 24 || Cin % 16 || (KW != 1 && KW != 3)) return false;
-    const int nt = cdiv(T, BN);
-    // long sequences keep the separate pass (conv_x3.h).  Split-K launches (<= 128 tiles: batches 1 - 2) carry the fused norm since
-    // round 5: the tile's LAST workgroup to arrive reduces the slabs and runs the fused epilogue like any other tile (the others have
-    // left by then, so the tiles a reducer may wait for are never behind more workgroups than the launch has)
-    (void)B;
-    return nt <= GN_FUSE_MAX_NT;
 }
 
 // option "conv_stages" / DTTS_CONV_STAGES (process-wide, like conv_small_tiles): the number of LDS stages of every conv_x3 launch
@@ -1290,24 +1016,16 @@ void set_conv_stages(int n) {
 
 void launch_conv_x3(const ConvParams& p_in, hipStream_t s, ConvX3Launch* chosen) {
     ConvParams p = p_in;
-    DTTS_REQUIRE(p.w3 && p.x3 && (p.y || p.qkv_planes || p.gn_out3) && p.x3_tp > 0, "conv_x3: operands");
-    const bool gn = p.gn_out3 != nullptr;
+    DTTS_REQUIRE(p.w3 && p.x3 && (p.y || p.qkv_planes) && p.x3_tp > 0, "conv_x3: operands");
     static const int env_ablate = env_int("DTTS_CONV_ABLATE", 0);
     if (env_ablate) p.ablate = env_ablate;
-    if (gn) {
-        DTTS_REQUIRE(conv_x3_gn_fusable(p.Cout, p.CoutP, p.Cin, p.KW, p.gn_groups, p.B, p.Nout), "conv_x3: this launch cannot carry a fused GroupNorm");
-        DTTS_REQUIRE(p.gn_gamma && p.gn_beta && p.gn_xch && p.gn_tag && p.gn_err && !p.qkv_planes && p.epi_act == ACT_NONE && p.out_scale == 1.f &&
-                         (p.gn_act == ACT_NONE || p.gn_act == ACT_SILU), "conv_x3 fused GroupNorm: parameters");
-        auto a16 = [](const void* q, long long bs, int cs) { return (reinterpret_cast<unsigned long long>(q) & 15ull) == 0 && (bs & 3) == 0 && (cs & 3) == 0; };
-        DTTS_REQUIRE((!p.y || a16(p.y, p.y_bs, p.y_cs)) && (!p.res || a16(p.res, p.res_bs, p.res_cs)), "conv_x3 fused GroupNorm: 16-byte aligned rows");
-    }
     DTTS_REQUIRE(p.B > 0 && p.Nout > 0 && p.Cout > 0, "empty conv");
     DTTS_REQUIRE(p.Cin % 16 == 0 && p.CoutP % BM == 0, "conv_x3: channel padding");
     const bool p1 = p.p1 != 0;
     DTTS_REQUIRE(!p1 || (p.Cin % 32 == 0 && p.gate == GATE_NONE), "conv_x3 one-product mode: input channels a multiple of 32, no gate");
     const bool gated = p.gate == GATE_TANH_SIGMOID;         // WN in_layers as a 1x1 conv over the tap-expanded planes (launch_split_planes_taps)
     DTTS_REQUIRE(p.stride == 1 && p.dil == 1 && p.phases == 1 && (p.gate == GATE_NONE ? !p.badd : gated), "conv_x3: unsupported conv form");
-    DTTS_REQUIRE(!gated || (p.KW == 1 && !gn && !p.qkv_planes && !p.res && p.epi_act == ACT_NONE && p.out_scale == 1.f && p.Cout % 2 == 0),
+    DTTS_REQUIRE(!gated || (p.KW == 1 && !p.qkv_planes && !p.res && p.epi_act == ACT_NONE && p.out_scale == 1.f && p.Cout % 2 == 0),
                  "conv_x3 gated epilogue: 1x1 conv, no residual / activation");
     DTTS_REQUIRE((p.KW == 1 && p.pad == 0) || (p.KW == 3 && p.pad == 1), "conv_x3: k = 1 or k = 3 (same padding) only");
     DTTS_REQUIRE(round_up(p.Nout, BN) + 2 * X3_HALO <= p.x3_tp, "conv_x3: time padding");
@@ -1319,7 +1037,6 @@ void launch_conv_x3(const ConvParams& p_in, hipStream_t s, ConvX3Launch* chosen)
     const int force_stg = stg_opt >= 0 ? stg_opt : conv_stages_default();
     static const long long max3 = env_int("DTTS_CONV_STAGES3_MAXWG", 600);
     static const long long max4 = env_int("DTTS_CONV_STAGES4_MAXWG", 128);
-    if (gn) p.cols = nullptr;                                            // the fused GroupNorm's id order is per sample
     DTTS_REQUIRE(!p.cols || (p.ncols > 0 && p.ncols <= cdiv(p.Nout, BN) * p.B && cdiv(p.Nout, BN) < 256), "conv_x3: column table");
     const long long ntile = (long long)(p.CoutP / BM) * (p.cols ? p.ncols : cdiv(p.Nout, BN) * p.B);
     // split-K: launches of at most 128 tiles (half the CUs: batch 1) divide the channel blocks among up to 4 workgroups per tile
@@ -1346,8 +1063,8 @@ void launch_conv_x3(const ConvParams& p_in, hipStream_t s, ConvX3Launch* chosen)
     const long long nwg = ntile * S;
     static const long long max4k3 = env_int("DTTS_CONV_STAGES4_MAXWG_K3", 128);
     const int nstg = force_stg ? force_stg : (nwg <= (p.KW == 3 ? max4k3 : max4) ? 4 : (nwg <= max3 ? 3 : 2));
-    const size_t lds = (size_t)nstg * (WTILE + XBUF) + BM * sizeof(float) + 16 + (gn ? 2 * BM * sizeof(float) : 0);
-    const int l4 = 4 * (WTILE + XBUF) + 3 * BM * (int)sizeof(float) + 16;      // the attribute is a maximum: every instantiation gets the 4-stage size
+    const size_t lds = (size_t)nstg * (WTILE + XBUF) + BM * sizeof(float) + 16;
+    const int l4 = 4 * (WTILE + XBUF) + BM * (int)sizeof(float) + 16;      // the attribute is a maximum: every instantiation gets the 4-stage size
     const dim3 grid((unsigned)nwg);
     const double cols = (double)p.B * p.Nout;
     const double flops = 2.0 * p.Cout * p.Cin * p.KW * cols;                      // fp32-equivalent; the MFMA pipe executes 3x this in fp16 (p1: 1x)
@@ -1360,7 +1077,7 @@ void launch_conv_x3(const ConvParams& p_in, hipStream_t s, ConvX3Launch* chosen)
         ProfScope ps(tag, flops, bytes, s);
         const bool epi = p.epi_act != ACT_NONE || p.out_scale != 1.f;
         if (chosen) {
-            chosen->epi = gn ? 3 : (gated ? 4 : (p.qkv_planes ? 2 : (epi ? 1 : 0)));
+            chosen->epi = gated ? 4 : (p.qkv_planes ? 2 : (epi ? 1 : 0));
             chosen->kw3 = p.KW == 3 ? 1 : 0;
             chosen->stages = nstg;
             chosen->ksplit = S;
@@ -1386,10 +1103,7 @@ void launch_conv_x3(const ConvParams& p_in, hipStream_t s, ConvX3Launch* chosen)
         else if (nstg == 3) { lds_optin(reinterpret_cast<const void*>(conv_x3_kernel<E, K3, 3>), l4); hipLaunchKernelGGL((conv_x3_kernel<E, K3, 3>), grid, dim3(256), lds, s, p); } \
         else { lds_optin(reinterpret_cast<const void*>(conv_x3_kernel<E, K3, 2>), l4); hipLaunchKernelGGL((conv_x3_kernel<E, K3, 2>), grid, dim3(256), lds, s, p); } \
     } while (0)
-        if (gn) {
-            if (p.KW == 3) DTTS_LAUNCH_X3(3, true);
-            else DTTS_LAUNCH_X3(3, false);
-        } else if (gated) {
+        if (gated) {
             DTTS_REQUIRE(p.epi_vec, "conv_x3 gated epilogue: rows of y must be 16-byte aligned");
             DTTS_LAUNCH_X3N(4, false);
         } else if (p.qkv_planes) {

@@ -358,7 +358,6 @@ public:
         // session holds after m forced decode steps, so that the prefill route can be compared with the step route
         else if (key == "gpt_prompt_raw") opt_prompt_raw_ = value != 0;
         else if (key == "cfg_streams") opt_cfg_streams_ = value < 0 ? 0 : value;
-        else if (key == "gn_fuse") opt_gn_fuse_ = value != 0;
         else if (key == "conv_cols") opt_conv_cols_ = value != 0;
         else if (key == "voc_chain_planes") opt_voc_chain_ = value != 0;
         else if (key == "voc_x3") opt_voc_x3_ = value != 0;                 // 0: stage C on the exact fp32 kernels only (the trunk keeps conv_x3's choice)
@@ -370,7 +369,6 @@ public:
         // captured graphs, stage A's decode graphs, hold no conv_gemm launch (the prefill, which does, is never captured): nothing to drop
         else if (key == "conv_small_tiles") set_conv_small_tiles(value);
         else if (key == "conv_stages") set_conv_stages(value);               // process-wide: LDS stages of the split-precision conv (conv_x3.h); a launch-time choice like the above
-        else if (key == "integ_pipeline") opt_integ_pipeline_ = value;      // 0 (default) / 1; -1: by batch size (on up to batch 4)
         else throw Error(-1, "unknown option '" + key + "'");
     }
     int get_option(const std::string& key) const {      // the options a caller restores after a per-call override
@@ -445,19 +443,6 @@ private:
 
     // building blocks on [B, C, T] buffers (all lens are device pointers)
     void run_conv(const PackedConv& pc, ConvParams p, hipStream_t s, ConvX3Launch* chosen = nullptr) const;
-    // GnNext / GnFuse: the GroupNorm + activation + split that FOLLOWS a block runs in the epilogue of the block's last conv
-    // (conv_x3.h "fused GroupNorm").  TrunkIo::f carries the second planes buffer (producer and consumer planes ping-pong between xs and
-    // f->xs_alt), the exchange buffer of the launch stream and whether xs ALREADY holds the block's normalised input (written by the
-    // previous block's last conv).  next == nullptr: the block's output is left un-normalised (fp32 rows only).
-    struct GnNext {
-        const float *gamma = nullptr, *beta = nullptr;
-        int act = ACT_NONE;
-    };
-    struct GnFuse {
-        void* xs_alt = nullptr;
-        int slot = 0;                // exchange buffer / tag counter of this launch stream (gn_xch_)
-        bool in_ready = false;
-    };
     // what every launch of a trunk block shares: the batch, its stream and scratch, and the kernel mode
     struct TrunkIo {
         const int* lens;             // device lengths [B]
@@ -465,30 +450,13 @@ private:
         hipStream_t s;
         float* ab;                   // GroupNorm coefficients [B, C, 2] of the exact fp32 path
         void* xs = nullptr;          // scratch for the split-precision input planes (x3_bytes(B, C, T)); null -> exact fp32 MFMA path
-        GnFuse* f = nullptr;
         bool p1 = false;             // option "trunk_fp16" covers this block: one fp16 product (ConvParams::p1 / AttnParams::p1) instead of three
         const int* step_idx = nullptr;   // ResBlock: per-sample step (device) of a batch whose samples sit at different sampling steps
     };
-    // the norm in front of a block's first conv: planes of act(GN(x)) in io.xs (x3), else coefficients in io.ab for the conv's prologue;
-    // nothing when the previous conv's fused epilogue has written the planes already
+    // the norm in front of a block's first conv: planes of act(GN(x)) in io.xs (x3), else coefficients in io.ab for the conv's prologue
     void norm_input(const float* x, int C, const float* gamma, const float* beta, int act, bool x3, const TrunkIo& io);
-    void attention_block(const AttnBlockW& w, const float* x, float* y, float* qkv, float* att, const TrunkIo& io, const GnNext* next = nullptr);
-    void res_block_fwd(const Schedule& sc, const ResBlockW& w, const float* x, float* h1, float* y, int step, const TrunkIo& io,
-                       const GnNext* next = nullptr);
-    // fused-GroupNorm plumbing: per launch stream an exchange buffer (zeroed when (re)allocated; only ever holds tags of earlier
-    // launches) and a tag counter; one host-mapped error flag the kernels raise when a poll gives up
-    struct GnXch {
-        void* buf = nullptr;
-        size_t bytes = 0;
-        unsigned tag = 0;
-    };
-    static constexpr int GN_SLOTS = 8;
-    GnXch gn_xch_[GN_SLOTS];
-    int* gn_err_host_ = nullptr;
-    int* gn_err_dev_ = nullptr;
-    bool opt_gn_fuse_ = false;            // option "gn_fuse" (measured neutral-to-negative at every batch size: DESIGN.md par. 4; DTTS_GN_FUSE=0/1 overrides)
-    void gn_fill(ConvParams& p, int slot, size_t bytes, const GnNext& n, void* out3, int groups, hipStream_t s);
-    void gn_check();                      // throws when a fused-GroupNorm poll timed out since the last check
+    void attention_block(const AttnBlockW& w, const float* x, float* y, float* qkv, float* att, const TrunkIo& io);
+    void res_block_fwd(const Schedule& sc, const ResBlockW& w, const float* x, float* h1, float* y, int step, const TrunkIo& io);
     bool use_x3() const;
     // cbuf0: [B + Nu, C, T] = B conditional code embeddings followed by Nu unconditional inputs (one per distinct length)
     // integ (optional): [B + Nu, C, T] outputs of the conditioning_timestep_integrator for this step (precompute_integrator)
@@ -496,9 +464,8 @@ private:
                            int T, int step, float* out2, hipStream_t s, const float* integ = nullptr);
     // The integrator sees (code embedding | unconditioned embedding, timestep) only - never x_t - so its output for every sampling
     // step is known before the loop starts: steps are evaluated J at a time as one batch of J*(B+Nu) samples, each at its own step.
-    // ready != null: only the first chunk runs on s, the later ones on si_; (first step, event) per later chunk is appended to *ready
     void precompute_integrator(const Schedule& sc, const float* cbuf0, const int* lens_i_host, int B, int Nu, int T, const std::vector<int>& steps,
-                               float* integ_all, hipStream_t s, std::vector<std::pair<int, hipEvent_t>>* ready = nullptr);
+                               float* integ_all, hipStream_t s);
     struct PairPlan { const int *lens2, *lens_i, *umap; int Nu; std::vector<int> ulen; };
     PairPlan plan_pair(const int* lens_host, int B, int T, hipStream_t s);
     // what the entry points around one diff_forward_pair share: the workspace sized for the call (+ extra_bytes, + hist_floats), the plan,
@@ -646,9 +613,6 @@ private:
     static constexpr int MAX_CFG_STREAMS = 4;
     hipStream_t sx_[MAX_CFG_STREAMS - 1] = {nullptr, nullptr, nullptr};   // extra streams of the diffusion forward
     hipEvent_t ev_fork_ = nullptr, ev_joinx_[MAX_CFG_STREAMS - 1] = {nullptr, nullptr, nullptr};
-    int opt_integ_pipeline_ = 0;          // option "integ_pipeline": the integrator's later step chunks under the first sampling steps (off: DESIGN.md par. 4.5)
-    hipStream_t si_ = nullptr;            // their low-priority stream
-    std::vector<hipEvent_t> ev_integ_;    // one per chunk
 
     // prompt front-end
     bool has_frontend_ = false;

@@ -43,18 +43,14 @@ Model::Model(const dtts_config& c, int dev) : cfg(c), device(dev) { DTTS_CHECK_H
 Model::~Model() {
     gpt_drop_graphs();
     if (x3_sat_) (void)hipHostFree(x3_sat_);
-    for (auto& g : gn_xch_)
-        if (g.buf) (void)hipFree(g.buf);
-    if (gn_err_host_) (void)hipHostFree(gn_err_host_);
     for (auto& kv : int_rings_) {
         IntRing& r = *kv.second;
         if (r.dev) (void)hipFree(r.dev);
         if (r.pinned) (void)hipHostFree(r.pinned);
         if (r.ev) (void)hipEventDestroy(r.ev);
     }
-    for (hipStream_t st : {sx_[0], sx_[1], sx_[2], sg_, si_})
+    for (hipStream_t st : {sx_[0], sx_[1], sx_[2], sg_})
         if (st) (void)hipStreamDestroy(st);
-    for (hipEvent_t e : ev_integ_) (void)hipEventDestroy(e);
     for (hipEvent_t e : {ev_fork_, ev_joinx_[0], ev_joinx_[1], ev_joinx_[2], ev_g0_, ev_g1_})
         if (e) (void)hipEventDestroy(e);
 }

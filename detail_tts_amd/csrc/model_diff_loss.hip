@@ -63,7 +63,6 @@ void Model::diff_loss_terms(int sched_id, const float* model_out, const float* x
 void Model::diff_training_losses(int sched_id, const float* x_start, const int* t_host, const float* noise, unsigned long long seed,
                                  const int* sample_ids_host, const float* code_emb, const int* lens_host, int B, int T, float* terms_out,
                                  float* pred_xstart, hipStream_t s) {
-    gn_check();
     const Schedule& sc = loss_schedule(sched_id, t_host, B, "diff_training_losses");
     DTTS_REQUIRE(x_start && code_emb && terms_out && T >= 1 && (noise || sample_ids_host), "diff_training_losses: null argument");
     DTTS_REQUIRE(!opt_trunk_fp16_, "diff_training_losses runs the three-product trunk only: set trunk_fp16 = 0 for this call");

@@ -232,67 +232,18 @@ bool Model::use_x3() const {
     return on && opt_conv_x3_;
 }
 
-// ------------------------------------------------------------------------------ fused GroupNorm plumbing (conv_x3.h)
-void Model::gn_fill(ConvParams& p, int slot, size_t bytes, const GnNext& n, void* out3, int groups, hipStream_t s) {
-    DTTS_REQUIRE(slot >= 0 && slot < GN_SLOTS, "fused GroupNorm: exchange slot");
-    GnXch& g = gn_xch_[slot];
-    if (!gn_err_host_) {
-        DTTS_CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&gn_err_host_), sizeof(int), hipHostMallocMapped));
-        *gn_err_host_ = 0;
-        DTTS_CHECK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&gn_err_dev_), gn_err_host_, 0));
-    }
-    if (bytes > g.bytes) {
-        DTTS_CHECK_HIP(hipDeviceSynchronize());
-        if (g.buf) DTTS_CHECK_HIP(hipFree(g.buf));
-        g.buf = nullptr;
-        g.bytes = 0;
-        const size_t want = bytes + bytes / 4 + 4096;
-        DTTS_CHECK_HIP(hipMalloc(&g.buf, want));
-        DTTS_CHECK_HIP(hipMemsetAsync(g.buf, 0, want, s));
-        g.bytes = want;
-        g.tag = 0;
-    }
-    if (++g.tag == 0) {                    // 2^32 launches: stale tags could match again - start over from a clean buffer
-        DTTS_CHECK_HIP(hipMemsetAsync(g.buf, 0, g.bytes, s));
-        g.tag = 1;
-    }
-    p.gn_out3 = out3;
-    p.gn_gamma = n.gamma;
-    p.gn_beta = n.beta;
-    p.gn_act = n.act;
-    p.gn_groups = groups;
-    p.gn_eps = 1e-5f;
-    p.gn_xch = g.buf;
-    p.gn_tag = g.tag;
-    p.gn_err = gn_err_dev_;
-}
-
-void Model::gn_check() {
-    if (gn_err_host_ && *gn_err_host_) {
-        *gn_err_host_ = 0;
-        throw Error(-4, "fused GroupNorm: a statistics exchange timed out (the result of the previous diffusion call is invalid); "
-                        "dtts_set_option(\"gn_fuse\", 0) selects the separate pass");
-    }
-}
-
 // ------------------------------------------------------------------------------ building blocks
 void Model::norm_input(const float* x, int C, const float* gamma, const float* beta, int act, bool x3, const TrunkIo& io) {
-    if (io.f && io.f->in_ready) {                       // io.xs already holds act(GN(x)): written by the previous conv's epilogue
-        io.f->in_ready = false;
-        return;
-    }
     const long long bs = (long long)C * io.Ta;
     if (x3) launch_gn_split_planes(x, bs, io.Ta, io.lens, io.T, io.B, C, gn_groups(C), gamma, beta, 1e-5f, nullptr, 0, 0, act, io.xs, io.s);
     else launch_gn_coeffs(x, bs, io.Ta, io.lens, io.T, io.B, C, gn_groups(C), gamma, beta, 1e-5f, nullptr, 0, 0, io.ab, io.s);
 }
 
 // AttentionBlock (vqvae/utils/diff_util.py:209-215): y = x + proj(attn(qkv(GN(x))))
-void Model::attention_block(const AttnBlockW& w, const float* x, float* y, float* qkv, float* att, const TrunkIo& io, const GnNext* next) {
+void Model::attention_block(const AttnBlockW& w, const float* x, float* y, float* qkv, float* att, const TrunkIo& io) {
     const int C = w.C, D = C / w.H, B = io.B, T = io.T, Ta = io.Ta;
     const long long bs = (long long)C * Ta;
-    GnFuse* f = io.f;
     const bool x3 = io.xs && w.qkv.w3 && w.proj.w3;
-    DTTS_REQUIRE(!f || x3, "fused GroupNorm needs the split-precision path");
     norm_input(x, C, w.gn_g, w.gn_b, ACT_NONE, x3, io);
     ConvParams p = cp(x, C, qkv, 3 * C, B, T, Ta, io.lens);
     p.pro_ab = io.ab;
@@ -334,10 +285,8 @@ void Model::attention_block(const AttnBlockW& w, const float* x, float* y, float
     // the proj conv's input planes come straight from the attention epilogue; xs still holds the zero halo / tail columns that
     // gn_split_planes wrote for the qkv conv (same B, T, lens), and the qkv conv has consumed the rest
     const bool att_planes = planes && T + 1 < x3_tp(T);
-    DTTS_REQUIRE(!f || att_planes, "fused GroupNorm: the attention must write the proj conv's planes");
-    void* xs_att = f ? f->xs_alt : io.xs;               // fused: the proj conv reads xs_alt and its epilogue writes xs (the next block's input)
     if (att_planes) {
-        a.out_x3 = xs_att;
+        a.out_x3 = io.xs;
         a.x3_tp = x3_tp(T);
     }
     launch_flash_attention(a, io.s);
@@ -345,24 +294,17 @@ void Model::attention_block(const AttnBlockW& w, const float* x, float* y, float
     with_res(q, x, bs, Ta);
     if (x3) {
         if (!att_planes) launch_split_planes(att, bs, Ta, nullptr, ACT_NONE, io.lens, T, B, C, io.xs, io.s);
-        with_planes(q, xs_att, T);
+        with_planes(q, io.xs, T);
         q.p1 = io.p1;
-    }
-    if (f && next) {                                    // the norm of the NEXT block in this conv's epilogue -> xs
-        gn_fill(q, f->slot, conv_x3_gn_xch_bytes(B, C, T), *next, io.xs, gn_groups(C), io.s);
-        f->in_ready = true;
     }
     run_conv(w.proj, q, io.s);
 }
 
 // diffusion ResBlock (vqvae/diff_model.py:106-119): y = x + conv3(SiLU(AdaGN(conv1(SiLU(GN(x))))))
-void Model::res_block_fwd(const Schedule& sc, const ResBlockW& w, const float* x, float* h1, float* y, int step, const TrunkIo& io,
-                          const GnNext* next) {
+void Model::res_block_fwd(const Schedule& sc, const ResBlockW& w, const float* x, float* h1, float* y, int step, const TrunkIo& io) {
     const int C = cfg.diff_channels, B = io.B, T = io.T, Ta = io.Ta, groups = gn_groups(C);
     const long long bs = (long long)C * Ta;
-    GnFuse* f = io.f;
     const bool x3 = io.xs && w.c1.w3 && w.c2.w3;
-    DTTS_REQUIRE(!f || x3, "fused GroupNorm needs the split-precision path");
     norm_input(x, C, w.gn1_g, w.gn1_b, ACT_SILU, x3, io);
     ConvParams p = cp(x, C, h1, C, B, T, Ta, io.lens);
     p.pro_ab = io.ab;
@@ -372,35 +314,14 @@ void Model::res_block_fwd(const Schedule& sc, const ResBlockW& w, const float* x
         p.p1 = io.p1;
     }
     const float* ada = sc.ss_table + (size_t)w.index * 2 * C * sc.n + (io.step_idx ? 0 : step);   // step_idx: per-sample steps
-    if (f) {                                            // AdaGN + SiLU + split of h1 in the 1x1 conv's epilogue; h1 itself is never stored (:106-119)
-        GnNext n2;
-        n2.gamma = w.gn2_g;
-        n2.beta = w.gn2_b;
-        n2.act = ACT_SILU;
-        ConvParams pf = p;
-        pf.y = nullptr;
-        gn_fill(pf, f->slot, conv_x3_gn_xch_bytes(B, C, T), n2, f->xs_alt, groups, io.s);
-        pf.gn_ada = ada;
-        pf.gn_ada_stride = sc.n;
-        pf.gn_ada_idx = io.step_idx;
-        run_conv(w.c1, pf, io.s);
-    } else {
-        run_conv(w.c1, p, io.s);
-        if (x3) launch_gn_split_planes(h1, bs, Ta, io.lens, T, B, C, groups, w.gn2_g, w.gn2_b, 1e-5f, ada, sc.n, 0, ACT_SILU, io.xs, io.s, io.step_idx);
-        else launch_gn_coeffs(h1, bs, Ta, io.lens, T, B, C, groups, w.gn2_g, w.gn2_b, 1e-5f, ada, sc.n, 0, io.ab, io.s, io.step_idx);
-    }
+    run_conv(w.c1, p, io.s);
+    if (x3) launch_gn_split_planes(h1, bs, Ta, io.lens, T, B, C, groups, w.gn2_g, w.gn2_b, 1e-5f, ada, sc.n, 0, ACT_SILU, io.xs, io.s, io.step_idx);
+    else launch_gn_coeffs(h1, bs, Ta, io.lens, T, B, C, groups, w.gn2_g, w.gn2_b, 1e-5f, ada, sc.n, 0, io.ab, io.s, io.step_idx);
     ConvParams q = p;
     q.x = h1;
     q.pad = 1;
     q.y = y;
     with_res(q, x, bs, Ta);
-    if (f) {
-        q.x3 = f->xs_alt;
-        if (next) {                                     // the norm of the NEXT block in this conv's epilogue -> xs
-            gn_fill(q, f->slot, conv_x3_gn_xch_bytes(B, C, T), *next, io.xs, groups, io.s);
-            f->in_ready = true;
-        }
-    }
     run_conv(w.c2, q, io.s);
 }
 
@@ -443,7 +364,6 @@ void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* c
     const long long bs = (long long)C * Ta;
     static const bool env_two = env_on("DTTS_TWO_STREAMS");
     const bool two_streams = env_two && opt_two_streams_;
-    const int groups = gn_groups(C);
     const bool x3 = use_x3();
     DTTS_REQUIRE(!opt_trunk_fp16_ || x3, "trunk_fp16 = 1 needs the split-precision kernels (conv_x3 = 1)");
 
@@ -523,40 +443,12 @@ void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* c
         float* qkv = ws().f32(qkv_floats(n, C, T));
         TrunkIo io{lens, n, T, Ta, st, ws().f32((size_t)n * C * 2)};
         io.xs = x3 ? ws().raw(x3_bytes(n, C, T)) : nullptr;
-        // fused GroupNorm (conv_x3.h): every GN + activation + split of the stack runs in the epilogue of the conv in front of it
-        // (8 -> 5 launches per DiffusionLayer); planes ping-pong between xs and xs2; chunk k uses exchange slot k
-        static const int env_fuse = env_tri("DTTS_GN_FUSE");
-        const bool fuse = x3 && (env_fuse >= 0 ? env_fuse != 0 : opt_gn_fuse_) && conv_x3_gn_fusable(C, C, C, 3, groups, n, T) && T + 1 < x3_tp(T);
-        GnFuse fz;
-        if (fuse) {
-            fz.xs_alt = ws().raw(x3_bytes(n, C, T));
-            fz.slot = k;
-            io.f = &fz;
-        }
-        auto norm_of = [](const float* g, const float* be, int act) {
-            GnNext nn;
-            nn.gamma = g;
-            nn.beta = be;
-            nn.act = act;
-            return nn;
-        };
         // integrating_conv, code half, accumulated onto the shared x-path term (the residual of stack sample b is xpath[b % B])
         ConvParams r = cp(code_path, C, bufB, C, n, T, Ta, lens);
         with_res(r, xpath + (size_t)(b0 % B) * C * Ta, bs, Ta);
         r.res_bmod = n > B ? B : 0;
         r.x_bidx = umap + b0;                          // code-path sample of stack sample b (uncond samples share one per length)
         if (x3) with_planes(r, xs_code, T);
-        const GnNext out_norm = norm_of(out_gn_g_, out_gn_b_, ACT_SILU);
-        auto first_norm = [&](size_t li, size_t ti) {      // GN1 of layer li of the stack, else of tail block ti, else the out norm
-            if (li < layers_.size()) return norm_of(layers_[li].rb.gn1_g, layers_[li].rb.gn1_b, ACT_SILU);
-            if (ti < tail_.size()) return norm_of(tail_[ti].gn1_g, tail_[ti].gn1_b, ACT_SILU);
-            return out_norm;
-        };
-        if (fuse) {
-            const GnNext n0 = first_norm(0, 0);
-            gn_fill(r, fz.slot, conv_x3_gn_xch_bytes(n, C, T), n0, io.xs, groups, st);
-            fz.in_ready = true;
-        }
         run_conv(integ2_, r, st);
         // main stack (:299-309)
         float* cur = bufB;
@@ -565,14 +457,12 @@ void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* c
         for (size_t li = 0; li < layers_.size(); ++li) {   // output back into `cur` (x is dead after the residual add)
             const auto& l = layers_[li];
             io.p1 = opt_trunk_fp16_ && li >= 1;             // layers[0] keeps the three-product kernels (:305-307)
-            const GnNext na = norm_of(l.at.gn_g, l.at.gn_b, ACT_NONE), nn = first_norm(li + 1, 0);
-            res_block_fwd(sc, l.rb, cur, t1, t2, step, io, &na);
-            attention_block(l.at, t2, cur, qkv, t1, io, &nn);
+            res_block_fwd(sc, l.rb, cur, t1, t2, step, io);
+            attention_block(l.at, t2, cur, qkv, t1, io);
         }
         io.p1 = opt_trunk_fp16_;
         for (size_t ti = 0; ti < tail_.size(); ++ti) {
-            const GnNext nn = first_norm(layers_.size(), ti + 1);
-            res_block_fwd(sc, tail_[ti], cur, t1, t2, step, io, &nn);
+            res_block_fwd(sc, tail_[ti], cur, t1, t2, step, io);
             std::swap(cur, t2);
         }
         // out: GN, SiLU, conv k3 (:312); three products like the x path
@@ -598,7 +488,7 @@ size_t Model::rows_ws_bytes(int B, int C, int T) {
 
 // DiffusionTts.forward (vqvae/diff_model.py:262-322), conditional branch only, every row at its own column of sc: the launch sequence of
 // one chunk of diff_forward_pair on the B conditional samples, on s alone, with TrunkIo::step_idx set in the integrator, the stack and
-// the tail.  GroupNorm runs as its own pass (the fused epilogue route has never carried a per-row index and is not taken here).
+// the tail.
 void Model::diff_forward_rows_s(const Schedule& sc, const float* x, const float* code_emb, const int* lens_host, int B, int T,
                                 const int* step_of_row, float* out, hipStream_t s) {
     const int C = cfg.diff_channels, Ta = T, OC = cfg.diff_out_channels;
@@ -679,7 +569,6 @@ void Model::diff_forward_rows_s(const Schedule& sc, const float* x, const float*
 
 void Model::diff_forward_rows(int sched_id, const float* x, const float* code_emb, const int* lens_host, int B, int T, const int* step_of_row,
                               float* out, hipStream_t s) {
-    gn_check();
     DTTS_REQUIRE(bound_, "weights not bound");
     DTTS_REQUIRE(x && code_emb && step_of_row && out && B >= 1 && T >= 1, "diff_forward_rows: x, code_emb, steps, out");
     DTTS_REQUIRE(!opt_trunk_fp16_, "diff_forward_rows runs the three-product trunk only: set trunk_fp16 = 0 for this call");
@@ -696,49 +585,21 @@ static size_t integ_ws_bytes(int Bv, int C, int T) {
 }
 static int integ_chunk(int Bi) {     // steps per batched evaluation (~36 samples per launch; DTTS_INTEG_SAMPLES overrides)
     // (batch 1, 12 / 20 / 36 / 52 / 100 samples per launch: diff_sample 122.8 - 126.2 / 123.1 / 123.5 - 124.2 / 123.4 / 123.6 ms - flat within the
-    // run-to-run spread, profiles/r05_integ_pipeline_ab.txt)
+    // run-to-run spread, the integrator A/B record under profiles/)
     static const int target = env_int("DTTS_INTEG_SAMPLES", 36);
     return std::max(1, target / Bi);
 }
 
 void Model::precompute_integrator(const Schedule& sc, const float* cbuf0, const int* lens_i_host, int B, int Nu, int T, const std::vector<int>& steps,
-                                  float* integ_all, hipStream_t s, std::vector<std::pair<int, hipEvent_t>>* ready) {
+                                  float* integ_all, hipStream_t s) {
     const int C = cfg.diff_channels, Bi = B + Nu, J = integ_chunk(Bi), NS = (int)steps.size();
     const size_t ct = (size_t)C * T, mark = ws().mark();
     const int Bv = J * Bi;
     const bool x3 = use_x3();
     static const bool env_two = env_on("DTTS_TWO_STREAMS");
-    // `ready` (the latency regime: diff_sample asks for it when the sampling loop is one launch sequence that cannot fill the chip):
-    // only the FIRST chunk of steps is evaluated on s; the later ones go to the low-priority stream si_ and run UNDER the loop's first
-    // steps, which wait for a chunk's event when they reach its first step.  Same launches on the same inputs: same values.  The
-    // scratch then stays carved until the caller rewinds (after the loop).
-    const bool piped = ready != nullptr && NS > J;
-    const bool two = (env_two && opt_two_streams_) || piped;
-    if (piped) {
-        if (!si_) {
-            // The chunks are chip-filling launches (36 samples): next to them every launch of the loop queues for CU slots, so the
-            // overlap returns 1 ms of the ~10 the chunks take (batch 1: 124.6 -> 123.7 ms, profiles/r05_integ_pipeline_ab.txt).
-            // Confining the chunks to DTTS_INTEG_CUS CUs (the mask's low bits) was measured and is OFF: 32 / 64 / 128 CUs gave 167 / 148 /
-            // 139 ms - a masked queue runs these launches far slower than its share of the chip.  Default: a low-priority stream.
-            static const int cus = env_int("DTTS_INTEG_CUS", 0);
-            if (cus > 0 && cus < 256) {
-                make_masked_stream(&si_, cus);
-            } else {
-                // DTTS_INTEG_PRIO=low: the lowest stream priority (measured: no different from the normal one)
-                static const bool low = []() { const char* v = env_str("DTTS_INTEG_PRIO"); return v && v[0] == 'l'; }();
-                int least = 0, greatest = 0;
-                DTTS_CHECK_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-                DTTS_CHECK_HIP(hipStreamCreateWithPriority(&si_, hipStreamNonBlocking, low ? least : 0));
-            }
-        }
-        while ((int)ev_integ_.size() < cdiv(NS, J)) {
-            hipEvent_t e;
-            DTTS_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            ev_integ_.push_back(e);
-        }
-    }
-    hipStream_t side = piped ? si_ : sx_[0];
-    if (two && !piped && !sx_[0]) { make_side_stream(&sx_[0]); side = sx_[0]; }
+    const bool two = env_two && opt_two_streams_;
+    if (two && !sx_[0]) make_side_stream(&sx_[0]);
+    hipStream_t side = sx_[0];
     if (two) ensure_fork_events();
     float* vin = ws().f32((size_t)Bv * ct);
     for (int j = 0; j < J; ++j)
@@ -766,7 +627,7 @@ void Model::precompute_integrator(const Schedule& sc, const float* cbuf0, const 
     // pairs 0 and 5 of 7 bracketed 32 % of it, and bench.py's busy share - union x step_every - counted the pre-pass 1.6 x: VERDICT r05)
     const int prof_rot = prof_rot_++;
     for (int k0 = 0; k0 < NS; k0 += J, ++ci) {
-        const Lane& L = lanes[piped ? (ci ? 1 : 0) : (two ? (ci & 1) : 0)];
+        const Lane& L = lanes[two ? (ci & 1) : 0];
         Profiler::gate() = ((ci / 2 + prof_rot) % Profiler::get().step_every) == 0;
         const int jn = std::min(J, NS - k0), nb = jn * Bi;
         for (int j = 0; j < jn; ++j)
@@ -789,13 +650,8 @@ void Model::precompute_integrator(const Schedule& sc, const float* cbuf0, const 
         dlayer(integ_[1], L.bufA, L.bufA);
         dlayer(integ_[2], L.bufA, outp);
         register_cols(dl, nullptr, 0, T, L.st);                        // enqueued: forget this chunk's table
-        if (piped && ci) {
-            DTTS_CHECK_HIP(hipEventRecord(ev_integ_[ci], si_));
-            ready->emplace_back(k0, ev_integ_[ci]);
-        }
     }
     Profiler::gate() = true;
-    if (piped) return;                                                 // the caller's loop waits per chunk and rewinds
     if (two) {
         DTTS_CHECK_HIP(hipEventRecord(ev_joinx_[0], sx_[0]));
         DTTS_CHECK_HIP(hipStreamWaitEvent(s, ev_joinx_[0], 0));
@@ -831,7 +687,6 @@ Model::PairCall Model::begin_pair(const float* code_emb, const int* lens_host, c
 // ------------------------------------------------------------------------------ stage entry points
 void Model::diff_forward(const float* x, const float* code_emb, const int* lens_host, int B, int T, int step, int cond_free,
                          float* out, hipStream_t s) {
-    gn_check();
     DTTS_REQUIRE(bound_, "weights not bound");
     DTTS_REQUIRE(step >= 0 && step < sched0_.n, "step out of range");
     diff_forward_s(sched0_, x, code_emb, lens_host, B, T, step, cond_free, out, s);
@@ -849,7 +704,6 @@ void Model::diff_forward_s(Schedule& sc, const float* x, const float* code_emb, 
 
 void Model::diff_forward_t(const float* x, const float* code_emb, const int* lens_host, int B, int T, int timestep, int cond_free,
                            float* out, hipStream_t s) {
-    gn_check();
     DTTS_REQUIRE(bound_, "weights not bound");
     DTTS_REQUIRE(timestep >= 0 && timestep < cfg.diff_trained_steps, "timestep out of [0, diff_trained_steps)");
     const auto it = std::lower_bound(sched0_.tmap.begin(), sched0_.tmap.end(), timestep);
@@ -864,7 +718,6 @@ void Model::diff_forward_t(const float* x, const float* code_emb, const int* len
 
 void Model::diff_forward_tf(const float* x, const float* code_emb, const int* lens_host, int B, int T, float timestep, int cond_free,
                             float* out, hipStream_t s) {
-    gn_check();
     DTTS_REQUIRE(bound_, "weights not bound");
     DTTS_REQUIRE(std::isfinite(timestep) && timestep >= 0.f && timestep < (float)cfg.diff_trained_steps,
                  "timestep out of [0, diff_trained_steps)");
@@ -890,7 +743,6 @@ void Model::diff_sample(const float* code_emb, const int* lens_host, int B, int 
 void Model::diff_sample_ex(int sched_id, int sampler, float eta, const float* code_emb, const int* lens_host, int B, int T,
                            unsigned long long seed, const int* sample_ids_host, int n_steps, const float* x_init, const float* step_noise,
                            float* mel_out, int denorm, hipStream_t s) {
-    gn_check();
     DTTS_REQUIRE(bound_, "weights not bound");
     DTTS_REQUIRE(sampler == 0 || sampler == 1 || sampler == 2, "sampler: 0 (p), 1 (ddim) or 2 (dpmsolver++)");
     DTTS_REQUIRE(eta >= 0.f, "eta must be >= 0");
@@ -937,31 +789,19 @@ void Model::diff_sample_ex(int sched_id, int sampler, float eta, const float* co
     }
     float* integ_all = nullptr;
     const int Bi = B + pl.Nu;
-    // option "integ_pipeline" (DTTS_INTEG_PIPELINE overrides; 1 = on, -1 = on up to batch 4, where a forward is ONE launch sequence in
-    // the latency regime): the integrator's later step chunks run under the first sampling steps instead of in front of the loop.
-    // OFF by default: it returns 1 ms of a blocking batch-1 call, but in a process that holds more streams (after batch-8 requests) the
-    // extra stream shares a hardware queue with the next request's stage A and a pipelined single-utterance request takes 208 instead
-    // of 147 ms (profiles/r05_integ_pipeline_ab.txt)
-    static const int env_pipe = env_int("DTTS_INTEG_PIPELINE", -1);
-    const int pipe_opt = env_pipe >= 0 ? env_pipe : opt_integ_pipeline_;
-    const bool pipe = pipe_opt < 0 ? B <= 4 : pipe_opt != 0;
-    std::vector<std::pair<int, hipEvent_t>> ready;
     if (env_pre) {
         std::vector<int> steps(n_steps), li(Bi);
         for (int k = 0; k < n_steps; ++k) steps[k] = sc.n - 1 - k;
         for (int b = 0; b < B; ++b) li[b] = lens_host ? lens_host[b] : T;
         for (int u = 0; u < pl.Nu; ++u) li[B + u] = pl.ulen[u];
         integ_all = ws().f32((size_t)n_steps * Bi * C * T);
-        precompute_integrator(sc, cbuf0, li.data(), B, pl.Nu, T, steps, integ_all, s, pipe ? &ready : nullptr);
+        precompute_integrator(sc, cbuf0, li.data(), B, pl.Nu, T, steps, integ_all, s);
     }
     const size_t mark = ws().mark();
-    size_t next_ready = 0;
     for (int k = 0; k < n_steps; ++k) {
         const int i = sc.n - 1 - k;
         Profiler::gate() = (k % Profiler::get().step_every) == 0;
         ws().rewind(mark);                              // the forward's scratch is re-carved every step
-        if (next_ready < ready.size() && ready[next_ready].first == k)
-            DTTS_CHECK_HIP(hipStreamWaitEvent(s, ready[next_ready++].second, 0));
         diff_forward_pair(sc, x, cbuf0, lens2, pl.lens_i, pl.umap, B, pl.Nu, T, i, out2, s,
                           integ_all ? integ_all + (size_t)k * Bi * C * T : nullptr);
         const bool last = (k == n_steps - 1);
@@ -987,7 +827,6 @@ void Model::diff_p_sample(float* x, const float* code_emb, const int* lens_host,
 // one p_sample (vqvae/utils/diffusion.py:445-485) or ddim_sample (:744-783) of schedule `sched_id` at spaced step `step`, x in place
 void Model::diff_step(int sched_id, int sampler, float eta, float* x, const float* code_emb, const int* lens_host, int B, int T, int step,
                       unsigned long long seed, const int* sample_ids_host, const float* noise, float* x0_out, hipStream_t s) {
-    gn_check();
     DTTS_REQUIRE(bound_, "weights not bound");
     DTTS_REQUIRE(sampler == 0 || sampler == 1, "sampler: 0 (p) or 1 (ddim)");
     DTTS_REQUIRE(eta >= 0.f, "eta must be >= 0");
@@ -1011,7 +850,6 @@ void Model::diff_step(int sched_id, int sampler, float eta, float* x, const floa
 // one DPM-Solver++(2M) step (vqvae/utils/dpm_solver.py:1176-1208 per step) of DPM schedule `sched_id` at step index `step`, x in place
 void Model::diff_step_dpm(int sched_id, float* x, float* x0_hist, const float* code_emb, const int* lens_host, int B, int T, int step,
                           float* x0_out, hipStream_t s) {
-    gn_check();
     DTTS_REQUIRE(bound_, "weights not bound");
     Schedule& sc = schedule(sched_id);
     DTTS_REQUIRE(sc.kind == 1, "diff_step_dpm runs on a DPM schedule (dtts_diff_schedule_dpm)");

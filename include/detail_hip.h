@@ -300,8 +300,8 @@ int dtts_diff_forward_tf(dtts_handle* h, const float* x, const float* code_emb, 
  * evaluated at column steps[b] (HOST [B], each in [0, steps of the schedule)) of integer-timestep schedule `id` (dtts_diff_schedule),
  * in the three conditioning_timestep_integrator layers and in every ResBlock of the stack and tail - what training_losses needs, which
  * draws one t per row.  x [B,128,T], code_emb [B,768,T], lens HOST [B] or NULL, out [B,256,T].  Only the conditional branch runs: a
- * B-sample stack on `stream`, no unconditional rows.  The default three-product trunk with GroupNorm as its own pass (option gn_fuse
- * does not apply here); with option trunk_fp16 = 1 the call is refused before any launch.  Arguments are checked on the host. */
+ * B-sample stack on `stream`, no unconditional rows.  The default three-product trunk; with option trunk_fp16 = 1 the call is refused
+ * before any launch.  Arguments are checked on the host. */
 int dtts_diff_forward_rows(dtts_handle* h, int id, const float* x, const float* code_emb, const int* lens, int B, int T, const int* steps,
                            float* out, void* stream);
 
@@ -547,11 +547,6 @@ int dtts_spectrogram(dtts_handle* h, const float* wav, const int* lens, int B, i
  *                 8-row one); 4 / 8 = the smallest allowed is the 4- / 8-row kernel; env DTTS_GPT_TOKEN_MIN_ROWS;
  *   "gpt_token_fault" (test hook, default 0): n > 0 makes the n-th token-kernel launch from now on behave like an exchange time-out;
  *   "gpt_token_fault_eos" (test hook, default 0): 1 = that fault also leaves every row flagged finished (a spurious stop token);
- *   "gn_fuse" (default 0): 1 = every GroupNorm + activation + split of the diffusion trunk (T <= 1152) runs in the epilogue of the conv
- *                 in front of it (tiles exchange partial statistics through tagged words; 8 -> 5 launches per layer, csrc/conv_x3.h
- *                 "fused GroupNorm"; since round 5 also on the split-K launches of batches 1 - 2).  Same values up to the summation
- *                 order of the statistics.  Measured neutral alone and 1.6 % slower under the three-stream pipeline at the headline
- *                 batch, 5 % slower at batch 1, hence off; env DTTS_GN_FUSE;
  *   "conv_cols" (default 1): ragged batches - the split-precision trunk convs launch one workgroup per LIVE (sample, N tile) column
  *                 (a table built from the host lengths of the call) instead of a grid over the padded length whose surplus workgroups
  *                 exit at once: the ids are dealt to the 8 XCDs in contiguous ranges, so the XCDs holding short samples used to run
@@ -571,10 +566,6 @@ int dtts_spectrogram(dtts_handle* h, const float* wav, const int* lens, int B, i
  *                 stages up to 128 workgroups, three up to 600, two beyond); 2 / 3 / 4 = every launch takes that many - how
  *                 tests/test_gpu_conv_x3.py reaches every pipeline depth at a tiny shape; < 0 = back to the initial value, which env
  *                 DTTS_CONV_STAGES sets.  The K order does not depend on it: bit-identical output.  A launch-time kernel choice;
- *   "integ_pipeline" (default 0): 1 (-1: up to batch 4) = only the first chunk of the conditioning_timestep_integrator's step outputs is
- *                 evaluated in front of the sampling loop, the later chunks on a stream of their own under the first sampling steps
- *                 (bit-identical; returns 1 ms at batch 1 but can cost a pipelined request 60 ms in a process with many live
- *                 streams: DESIGN.md par. 4.5); env DTTS_INTEG_PIPELINE;
  *   "x3_range_check" (default 0): 1 = a stage-C call checks that the inputs of its split-precision convs (ResBlock1, WaveNet in_layers:
  *                 unnormalised activations) stay inside the fp16 planes' range (|x| <= 4094); a violation fails the call instead of
  *                 saturating silently.  Reads a flag back at the end of the call (synchronises the stream); env DTTS_X3_RANGE_CHECK=1.
@@ -589,7 +580,9 @@ int dtts_spectrogram(dtts_handle* h, const float* wav, const int* lens, int B, i
  *                 conditioning integrator, the time embedding / AdaGN tables and the out conv keep the three-product kernels; GroupNorm,
  *                 softmax, residual adds and every activation between kernels stay fp32.  All samplers, any step count.  Refused with
  *                 conv_x3 = 0 (the exact fp32 kernels have no such mode), and conv_x3 = 0 is refused while it is 1.  A launch-time
- *                 kernel choice: the captured graphs (stage A's decode graphs) hold no trunk launch, none is dropped. */
+ *                 kernel choice: the captured graphs (stage A's decode graphs) hold no trunk launch, none is dropped.
+ * Any other key fails with -1 "unknown option" - also the keys of the two experiments that earlier versions carried and that were
+ * removed with their code: the fused-GroupNorm conv epilogue and the pipelined integrator chunks (DESIGN_APPENDIX.md 4.3, 4.5). */
 int dtts_set_option(dtts_handle* h, const char* key, int value);
 /* Reads back "conv_x3" (1 only if DTTS_CONV_X3 does not disable it) or "trunk_fp16": what a caller needs to restore after a per-call override. */
 int dtts_get_option(dtts_handle* h, const char* key, int* value);

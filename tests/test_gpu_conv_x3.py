@@ -1,10 +1,9 @@
-"""GPU parity of every instantiation of the split-precision conv (csrc/conv_x3.hip) the launcher can pick outside EPI 2 / 3, one conv at a
+"""GPU parity of every instantiation of the split-precision conv (csrc/conv_x3.hip) the launcher can pick outside EPI 2, one conv at a
 time through Runtime.op_conv1d_x3: EPI 0 (bias, + residual), 1 (activation, out_scale, residual) and 4 (gated), k = 1 and k = 3, the
 one-product mode p1, split-K 1 .. 4 (uneven splits included), the live-column table of ragged batches and both epilogue forms (LDS-staged
 16-byte stores / scalar stores).  The launcher picks the LDS stage count by launch size, so unit-test shapes would only ever see four
 stages: option "conv_stages" forces 2, 3 and 4 on every case.  EPI 2 (the qkv conv's operand images) has its own unit tests, with the
-attention that reads them, in tests/test_gpu_attn_x3.py (Runtime.op_attention_x3).  Out of scope: EPI 3 (fused GroupNorm), an
-off-by-default option whose output is another kernel's input format; it stays covered by test_gpu_fullsize.py.
+attention that reads them, in tests/test_gpu_attn_x3.py (Runtime.op_attention_x3).
 
 The table, its data and the float64 references are in tests/conv_x3_model.py; tests/test_host_conv_x3.py shows on the CPU that the gate
 used here separates the scheme (3 - 6e-7) from a dropped cross product, a zeroed low plane of one seam column, a dropped tap and an

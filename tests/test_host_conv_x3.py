@@ -79,7 +79,7 @@ def test_case_table_lands_on_the_variants_it_names_and_covers_every_instantiatio
         assert got == want, (c["name"], got, want)
         assert c["cin"] * c["k"] <= 2304 and min(M.lens_of(c)) >= 1 and max(M.lens_of(c)) == c["T"] == M.lens_of(c)[0]
     inst = {(c["epi"], c["k"], c["p1"]) for c in M.CASES}
-    # every (epi, k, p1) the launcher can pick outside EPI 2 / 3; the GPU test runs each under 2, 3 and 4 stages
+    # every (epi, k, p1) the launcher can pick outside EPI 2; the GPU test runs each under 2, 3 and 4 stages
     assert inst == {(0, 1, 0), (0, 3, 0), (1, 1, 0), (1, 3, 0), (4, 1, 0), (0, 1, 1), (0, 3, 1), (1, 1, 1), (1, 3, 1)}, inst
     assert {c["ksplit"] for c in M.CASES} == {1, 2, 3, 4}
     # one uneven split: 25 channel blocks over 3, 17 over 2

@@ -1,5 +1,5 @@
 """Per-kernel timings of one DiffusionTts.forward pair (cond | uncond) at the bench's per-stream shape: B = 4 -> one 8-sample chunk,
-T = 936 (BB / TT override).  DTTS_PROF_SHAPES=1 names the conv shapes; DTTS_GN_FUSE=0/1 selects the GroupNorm path."""
+T = 936 (BB / TT override).  DTTS_PROF_SHAPES=1 names the conv shapes."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("DTTS_PROF_SHAPES", "1")
