@@ -39,6 +39,7 @@ struct ConvParams {
     int res_cs = 0;
     float res_scale = 1.f;
     int res_bmod = 0;              // residual batch index = b % res_bmod (0: b) — shared residual across batch halves
+    const int* res_bidx = nullptr; // optional [B] (conv_x3 and the fp32 kernel; conv_x3d has none): residual batch index of output sample b, instead of the above
     int mask_out = 0;              // unused rows/cols are never written; kept for clarity
     // output
     float* y = nullptr;

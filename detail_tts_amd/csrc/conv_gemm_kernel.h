@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvParams p) {
 
     // ---- epilogue.  C layout of 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
     float* yb = p.y + (long long)b * p.y_bs;
-    const float* rb = p.res ? p.res + (long long)(p.res_bmod ? b % p.res_bmod : b) * p.res_bs : nullptr;
+    const float* rb = p.res ? p.res + (long long)(p.res_bidx ? p.res_bidx[b] : (p.res_bmod ? b % p.res_bmod : b)) * p.res_bs : nullptr;
     const float* bad = p.badd ? p.badd + (long long)b * p.badd_bs : nullptr;
     const int cpp = p.Cout / p.phases;   // real rows per phase
 #pragma unroll

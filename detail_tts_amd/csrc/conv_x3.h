@@ -33,10 +33,10 @@ void launch_split_planes(const float* x, long long x_bs, int x_cs, const float* 
 void launch_split_planes_taps(const float* x, long long x_bs, int x_cs, const int* lens, int T, int B, int C, int KW, int pad, void* out,
                               hipStream_t s, int* sat = nullptr);
 // GroupNorm (statistics + affine, optional AdaGN (1 + scale, shift) from `ada`) + activation + split in one pass; arguments as
-// launch_gn_coeffs (ops.h)
+// launch_gn_coeffs (ops.h), x_bmod included
 void launch_gn_split_planes(const float* x, long long x_bs, int x_cs, const int* lens, int T, int B, int C, int groups,
                             const float* gamma, const float* beta, float eps, const float* ada, int ada_stride, int ada_bs, int act,
-                            void* out, hipStream_t s, const int* ada_idx = nullptr);
+                            void* out, hipStream_t s, const int* ada_idx = nullptr, int x_bmod = 0);
 // uses p.w3 / p.x3 / p.x3_tp (+ the epilogue fields of ConvParams); stride 1, dilation 1, pad <= X3_HALO, no phases; gate (tanh * sigmoid on packed row pairs) + badd only
 // as a 1x1 conv without residual (EPI 4: the WaveNet in_layers over launch_split_planes_taps planes)
 // p.p1 (the trunk's fp16 mode, option "trunk_fp16"): ONE product h0 h0' on plane 0 of the same images, 32 channels per K-step, instead of

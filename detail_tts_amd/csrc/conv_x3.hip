@@ -81,13 +81,13 @@ __global__ __launch_bounds__(1024) void gn_split_planes_kernel(const float* __re
                                                               const int* __restrict__ lens, int T, int C, int groups,
                                                               const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                                                               const float* __restrict__ ada, int ada_stride, int ada_bs, int Tp,
-                                                              uint4* __restrict__ out, const int* __restrict__ ada_idx) {
+                                                              uint4* __restrict__ out, const int* __restrict__ ada_idx, int x_bmod) {
     __shared__ float red[2][16];
     __shared__ float sa[64], sd[64];
     const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthr = blockDim.x;
     const int len = lens ? lens[b] : T;
     const int cpg = C / groups;
-    const float* xg = x + (long long)b * x_bs + (long long)(g * cpg) * x_cs;
+    const float* xg = x + (long long)(x_bmod ? b % x_bmod : b) * x_bs + (long long)(g * cpg) * x_cs;
     const float k = xg[0];
     float s1 = 0.f, s2 = 0.f;
     const bool vec = ((x_cs & 3) == 0) && ((reinterpret_cast<unsigned long long>(xg) & 15ull) == 0);
@@ -183,13 +183,13 @@ __global__ __launch_bounds__(1024) void gn_split_planes_reg_kernel(const float* 
                                                                   const int* __restrict__ lens, int T, int C, int groups,
                                                                   const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                                                                   const float* __restrict__ ada, int ada_stride, int ada_bs, int Tp,
-                                                                  uint4* __restrict__ out, const int* __restrict__ ada_idx) {
+                                                                  uint4* __restrict__ out, const int* __restrict__ ada_idx, int x_bmod) {
     __shared__ float red[2][16];
     __shared__ float sa[64], sd[64];
     const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int len = lens ? lens[b] : T;
     const int cpg = C / groups, c8n = cpg >> 3, C8 = C >> 3, nitems = c8n * Tp;
-    const float* xg = x + (long long)b * x_bs + (long long)(g * cpg) * x_cs;
+    const float* xg = x + (long long)(x_bmod ? b % x_bmod : b) * x_bs + (long long)(g * cpg) * x_cs;
     const float k = xg[0];
     float v[NI][8];
     float s1 = 0.f, s2 = 0.f;
@@ -613,7 +613,7 @@ __global__ __launch_bounds__(256, NSTG == 2 ? 3 : 2) void conv_x3_kernel(ConvPar
         // stages are free once every wave has left it: one barrier).
         constexpr int EP_LD = 104;
         float* yb = p.y + (long long)b * p.y_bs;
-        const float* rb = p.res ? p.res + (long long)(p.res_bmod ? b % p.res_bmod : b) * p.res_bs : nullptr;
+        const float* rb = p.res ? p.res + (long long)(p.res_bidx ? p.res_bidx[b] : (p.res_bmod ? b % p.res_bmod : b)) * p.res_bs : nullptr;
         const int ncol0 = n0 + wn0;
         // Residual rows: with >= 3 LDS stages (register budget 256) ALL 24 loads of the tile are in flight before the first round -
         // one memory latency for the tile instead of one per round (the rounds' LDS fences keep the compiler from hoisting them)
@@ -818,7 +818,7 @@ __global__ __launch_bounds__(256, NSTG == 2 ? 3 : 2) void conv_x3_kernel(ConvPar
         return;
     }
     float* yb = p.y + (long long)b * p.y_bs;
-    const float* rb = p.res ? p.res + (long long)(p.res_bmod ? b % p.res_bmod : b) * p.res_bs : nullptr;
+    const float* rb = p.res ? p.res + (long long)(p.res_bidx ? p.res_bidx[b] : (p.res_bmod ? b % p.res_bmod : b)) * p.res_bs : nullptr;
     // The residual usually IS the output buffer (in-place x += f(x)): the compiler must keep every residual load behind the
     // previous store, which would serialise 64 load latencies.  Element (row, n) is read and written by this lane only, so per
     // 32 x 32 tile the 16 residual loads are issued first, into registers, and the 16 stores follow.
@@ -917,7 +917,7 @@ void launch_split_planes(const float* x, long long x_bs, int x_cs, const float* 
 
 void launch_gn_split_planes(const float* x, long long x_bs, int x_cs, const int* lens, int T, int B, int C, int groups,
                             const float* gamma, const float* beta, float eps, const float* ada, int ada_stride, int ada_bs, int act,
-                            void* out, hipStream_t s, const int* ada_idx) {
+                            void* out, hipStream_t s, const int* ada_idx, int x_bmod) {
     DTTS_REQUIRE(C % groups == 0 && (C / groups) % 8 == 0 && C / groups <= 64, "gn_split_planes: group size");
     DTTS_REQUIRE(act == ACT_NONE || act == ACT_SILU, "gn_split_planes: activation");
     const int Tp = x3_tp(T);
@@ -930,19 +930,19 @@ void launch_gn_split_planes(const float* x, long long x_bs, int x_cs, const int*
     if (reg_ok && ns == 1 && (C / groups / 8) * Tp <= NI * 1024) {          // the slab fits the workgroup's registers: one HBM read
         if (act == ACT_SILU)
             hipLaunchKernelGGL((gn_split_planes_reg_kernel<ACT_SILU, NI>), dim3(groups, B), dim3(1024), 0, s, x, x_bs, x_cs, lens, T, C, groups,
-                               gamma, beta, eps, ada, ada_stride, ada_bs, Tp, o, ada_idx);
+                               gamma, beta, eps, ada, ada_stride, ada_bs, Tp, o, ada_idx, x_bmod);
         else
             hipLaunchKernelGGL((gn_split_planes_reg_kernel<ACT_NONE, NI>), dim3(groups, B), dim3(1024), 0, s, x, x_bs, x_cs, lens, T, C, groups,
-                               gamma, beta, eps, ada, ada_stride, ada_bs, Tp, o, ada_idx);
+                               gamma, beta, eps, ada, ada_stride, ada_bs, Tp, o, ada_idx, x_bmod);
         DTTS_CHECK_HIP(hipGetLastError());
         return;
     }
     if (act == ACT_SILU)
         hipLaunchKernelGGL(gn_split_planes_kernel<ACT_SILU>, dim3(groups, B, ns), dim3(nt), 0, s, x, x_bs, x_cs, lens, T, C, groups, gamma,
-                           beta, eps, ada, ada_stride, ada_bs, Tp, o, ada_idx);
+                           beta, eps, ada, ada_stride, ada_bs, Tp, o, ada_idx, x_bmod);
     else
         hipLaunchKernelGGL(gn_split_planes_kernel<ACT_NONE>, dim3(groups, B, ns), dim3(nt), 0, s, x, x_bs, x_cs, lens, T, C, groups, gamma,
-                           beta, eps, ada, ada_stride, ada_bs, Tp, o, ada_idx);
+                           beta, eps, ada, ada_stride, ada_bs, Tp, o, ada_idx, x_bmod);
     DTTS_CHECK_HIP(hipGetLastError());
 }
 

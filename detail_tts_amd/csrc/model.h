@@ -457,17 +457,25 @@ private:
     void norm_input(const float* x, int C, const float* gamma, const float* beta, int act, bool x3, const TrunkIo& io);
     void attention_block(const AttnBlockW& w, const float* x, float* y, float* qkv, float* att, const TrunkIo& io);
     void res_block_fwd(const Schedule& sc, const ResBlockW& w, const float* x, float* h1, float* y, int step, const TrunkIo& io);
+    // its two halves: h1 = conv1(SiLU(GN(x))) | y = x + conv3(SiLU(AdaGN(h1))), where alone the timestep enters.  bmod != 0: sample b reads
+    // h1 and x of sample b % bmod (bidx [B]: that index on the device, for the exact fp32 conv)
+    void res_block_front(const ResBlockW& w, const float* x, float* h1, const TrunkIo& io);
+    void res_block_back(const Schedule& sc, const ResBlockW& w, const float* h1, const float* x, float* y, int step, const TrunkIo& io, int bmod = 0,
+                        const int* bidx = nullptr);
+    void code_half(const float* in, float* P, const TrunkIo& io);   // P = W_integ2 . in: the code half of integrating_conv
     bool use_x3() const;
-    // cbuf0: [B + Nu, C, T] = B conditional code embeddings followed by Nu unconditional inputs (one per distinct length)
-    // integ (optional): [B + Nu, C, T] outputs of the conditioning_timestep_integrator for this step (precompute_integrator)
-    void diff_forward_pair(const Schedule& sc, const float* x, const float* cbuf0, const int* lens2, const int* lens_i, const int* umap, int B, int Nu,
-                           int T, int step, float* out2, hipStream_t s, const float* integ = nullptr);
-    // The integrator sees (code embedding | unconditioned embedding, timestep) only - never x_t - so its output for every sampling
-    // step is known before the loop starts: steps are evaluated J at a time as one batch of J*(B+Nu) samples, each at its own step.
-    void precompute_integrator(const Schedule& sc, const float* cbuf0, const int* lens_i_host, int B, int Nu, int T, const std::vector<int>& steps,
-                               float* integ_all, hipStream_t s);
-    struct PairPlan { const int *lens2, *lens_i, *umap; int Nu; std::vector<int> ulen; };
+    // lens2 [2B]: the stack's lengths; lens_i [B + Nu]: the integrator batch's; umap [2B]: integrator sample of stack sample b; xmap [2B]: b % B
+    struct PairPlan { const int *lens2, *lens_i, *umap, *xmap; int Nu; std::vector<int> ulen; };
     PairPlan plan_pair(const int* lens_host, int B, int T, hipStream_t s);
+    // cbuf0: [B + Nu, C, T] = B conditional code embeddings followed by Nu unconditional inputs (one per distinct length)
+    // integ (optional): [B + Nu, C, T] code-path terms P = W_integ2 . conditioning_timestep_integrator(cbuf0) of this step (precompute_integrator)
+    void diff_forward_pair(const Schedule& sc, const float* x, const float* cbuf0, const PairPlan& pl, int B, int T, int step, float* out2,
+                           hipStream_t s, const float* integ = nullptr);
+    // The integrator sees (code embedding | unconditioned embedding, timestep) only - never x_t - so its output for every sampling
+    // step, and the code half of integrating_conv on it, is known before the loop starts: steps are evaluated J at a time as one batch of
+    // J*(B+Nu) samples, each at its own step; the step-invariant front of its first ResBlock once.  lens_i: plan_pair's (device).
+    void precompute_integrator(const Schedule& sc, const float* cbuf0, const int* lens_i, const int* lens_i_host, int B, int Nu, int T,
+                               const std::vector<int>& steps, float* integ_all, hipStream_t s);
     // what the entry points around one diff_forward_pair share: the workspace sized for the call (+ extra_bytes, + hist_floats), the plan,
     // the sample ids (optional), cbuf0 = (code_emb, or the unconditioned embedding when null | unconditional inputs), out2 [2B, OC, T]
     // and the DPM-Solver++ history [hist_floats]
@@ -478,7 +486,7 @@ private:
     // the per-row driver behind diff_forward_rows / diff_training_losses: carves rows_ws_bytes(B, C, T) of ws(), which the caller has sized
     void diff_forward_rows_s(const Schedule& sc, const float* x, const float* code_emb, const int* lens_host, int B, int T, const int* step_of_row,
                              float* out, hipStream_t s);
-    static size_t rows_ws_bytes(int B, int C, int T);
+    size_t rows_ws_bytes(int B, int C, int T) const;
     // the integer-timestep schedule `sched_id` with t_host [B] checked against its columns; the rows' coefficients on the device
     const Schedule& loss_schedule(int sched_id, const int* t_host, int B, const char* who);
     const DiffLossCoefs* upload_loss_coefs(const Schedule& sc, const int* t_host, int B, hipStream_t s);
@@ -490,7 +498,8 @@ private:
     std::vector<DiffLayerW> integ_, layers_;
     std::vector<ResBlockW> tail_;
     std::vector<AttnBlockW> latcond_, ctx_;
-    PackedConv inp_block_, integ1_, integ2_, out_conv_, latcond0_, ctx0_, ctx1_, te0_, te2_;
+    PackedConv xpath_;               // inp_block composed with the x half of integrating_conv (+ both biases): built at bind time in persist_
+    PackedConv integ2_, out_conv_, latcond0_, ctx0_, ctx1_, te0_, te2_;
     const float *out_gn_g_ = nullptr, *out_gn_b_ = nullptr, *code_gn_g_ = nullptr, *code_gn_b_ = nullptr, *uncond_ = nullptr;
     int n_resblocks_ = 0;
     Schedule sched0_;                // the default schedule (cfg.diff_steps), tables in persist_

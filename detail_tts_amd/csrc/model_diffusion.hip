@@ -139,6 +139,21 @@ int Model::diff_schedule_info(int sched_id, int* tmap, float* coefs, int cap) {
     return sc.n;
 }
 
+// The x path of DiffusionTts.forward is two linear convs in a row (vqvae/diff_model.py:296-298: inp_block, k = 3, then the x columns of the
+// 1 x 1 integrating_conv, no activation or norm between them), so they are ONE k = 3 conv whose weights depend on the checkpoint only:
+//   W'[tap] = W1 . W_inp[tap],  b' = W1 . b_inp + b1        (packed layout [tap][ci][co]; W1 = integrating_conv.a)
+// One thread per output element, the sum over the M middle channels in fp64, rounded once to fp32.  Row r < rows: weight row (tap, ci); row `rows`: the bias.
+__global__ __launch_bounds__(256) void compose_xpath_kernel(const float* __restrict__ w_inp, const float* __restrict__ b_inp, int inp_ld,
+                                                            const float* __restrict__ w1, const float* __restrict__ b1, int M, int CoutP,
+                                                            int rows, float* __restrict__ w_out, float* __restrict__ b_out) {
+    const int co = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
+    if (co >= CoutP) return;
+    const float* a = r < rows ? w_inp + (size_t)r * inp_ld : b_inp;
+    double acc = r < rows ? 0.0 : (double)b1[co];
+    for (int m = 0; m < M; ++m) acc += (double)a[m] * (double)w1[(size_t)m * CoutP + co];
+    (r < rows ? w_out + (size_t)r * CoutP : b_out)[co] = (float)acc;
+}
+
 void Model::build_diffusion(hipStream_t s) {
     const int C = cfg.diff_channels, H = cfg.diff_heads, NL = cfg.diff_layers;
     {
@@ -161,8 +176,8 @@ void Model::build_diffusion(hipStream_t s) {
         layers_.push_back({res_block(p + ".resblk", C, rbi++), attn_block(p + ".attn", C, H)});
     }
     for (int i = NL; i < NL + 3; ++i) tail_.push_back(res_block(d + "layers." + std::to_string(i), C, rbi++));
-    inp_block_ = conv(d + "inp_block", cfg.mel_channels, C, 3);
-    integ1_ = conv(d + "integrating_conv.a", C, C, 1);           // columns 0..C-1 of the 1x1 (x path) + bias
+    const PackedConv inp_block = conv(d + "inp_block", cfg.mel_channels, C, 3);
+    const PackedConv integ1 = conv(d + "integrating_conv.a", C, C, 1);   // columns 0..C-1 of the 1x1 (x path) + bias: both only feed xpath_ below
     integ2_ = conv(d + "integrating_conv.b", C, C, 1, false);    // columns C..2C-1 (code path)
     out_gn_g_ = W(d + "out.0.weight", C);
     out_gn_b_ = W(d + "out.0.bias", C);
@@ -184,15 +199,30 @@ void Model::build_diffusion(hipStream_t s) {
 
     // ---- timestep tables on the device (build_ss_table) in the bind-time arena
     const int NS = sched0_.n, NRB = rbi;
-    persist_.ensure(sizeof(float) * ((size_t)NRB * 2 * C * NS + 3 * (size_t)C * NS) + sizeof(int) * NS + 4096);
+    xpath_ = inp_block;                                          // k = 3, mel_channels -> C: the composition keeps inp_block's shape
+    DTTS_REQUIRE(integ1.Cin <= inp_block.CoutP && integ1.CoutP == inp_block.CoutP, "x path: inp_block and integrating_conv do not compose");
+    const size_t xw = (size_t)xpath_.KW * xpath_.CinP * xpath_.CoutP;
+    persist_.ensure(sizeof(float) * ((size_t)NRB * 2 * C * NS + 3 * (size_t)C * NS + xw + xpath_.CoutP) + sizeof(int) * NS + 4096);
     float* ss_table = persist_.f32((size_t)NRB * 2 * C * NS);
     float* scratch = persist_.f32(3 * (size_t)C * NS);
     int* ts_dev = persist_.i32(NS);
     sched0_.ss_table = ss_table;
     build_ss_table(sched0_, ss_table, scratch, ts_dev, s);
 
+    // ---- the composed x-path conv (compose_xpath_kernel), rebuilt with every (re)bind like the tables above
+    {
+        float* w = persist_.f32(xw);
+        float* b = persist_.f32(xpath_.CoutP);
+        const int rows = xpath_.KW * xpath_.CinP;
+        hipLaunchKernelGGL(compose_xpath_kernel, dim3(cdiv(xpath_.CoutP, 256), rows + 1), dim3(256), 0, s, inp_block.w, inp_block.b, inp_block.CoutP,
+                           integ1.w, integ1.b, integ1.Cin, xpath_.CoutP, rows, w, b);
+        DTTS_CHECK_HIP(hipGetLastError());
+        xpath_.w = w;
+        xpath_.b = b;
+    }
+
     // ---- split-precision (3 x bf16) copies of the trunk's conv weights (conv_x3.h)
-    std::vector<PackedConv*> hot = {&inp_block_, &integ1_, &integ2_, &out_conv_};
+    std::vector<PackedConv*> hot = {&xpath_, &integ2_, &out_conv_};
     auto add_layer = [&](DiffLayerW& l) {
         hot.push_back(&l.rb.c1);
         hot.push_back(&l.rb.c2);
@@ -302,26 +332,49 @@ void Model::attention_block(const AttnBlockW& w, const float* x, float* y, float
 
 // diffusion ResBlock (vqvae/diff_model.py:106-119): y = x + conv3(SiLU(AdaGN(conv1(SiLU(GN(x))))))
 void Model::res_block_fwd(const Schedule& sc, const ResBlockW& w, const float* x, float* h1, float* y, int step, const TrunkIo& io) {
-    const int C = cfg.diff_channels, B = io.B, T = io.T, Ta = io.Ta, groups = gn_groups(C);
-    const long long bs = (long long)C * Ta;
+    res_block_front(w, x, h1, io);
+    res_block_back(sc, w, h1, x, y, step, io);
+}
+
+// ... its front, h1 = conv1(SiLU(GN(x))): no timestep enters here
+void Model::res_block_front(const ResBlockW& w, const float* x, float* h1, const TrunkIo& io) {
+    const int C = cfg.diff_channels;
     const bool x3 = io.xs && w.c1.w3 && w.c2.w3;
     norm_input(x, C, w.gn1_g, w.gn1_b, ACT_SILU, x3, io);
-    ConvParams p = cp(x, C, h1, C, B, T, Ta, io.lens);
+    ConvParams p = cp(x, C, h1, C, io.B, io.T, io.Ta, io.lens);
     p.pro_ab = io.ab;
     p.pro_act = ACT_SILU;
     if (x3) {
-        with_planes(p, io.xs, T);
+        with_planes(p, io.xs, io.T);
         p.p1 = io.p1;
     }
-    const float* ada = sc.ss_table + (size_t)w.index * 2 * C * sc.n + (io.step_idx ? 0 : step);   // step_idx: per-sample steps
     run_conv(w.c1, p, io.s);
-    if (x3) launch_gn_split_planes(h1, bs, Ta, io.lens, T, B, C, groups, w.gn2_g, w.gn2_b, 1e-5f, ada, sc.n, 0, ACT_SILU, io.xs, io.s, io.step_idx);
-    else launch_gn_coeffs(h1, bs, Ta, io.lens, T, B, C, groups, w.gn2_g, w.gn2_b, 1e-5f, ada, sc.n, 0, io.ab, io.s, io.step_idx);
-    ConvParams q = p;
-    q.x = h1;
+}
+
+// ... and its back, y = x + conv3(SiLU(AdaGN(h1))).  bmod != 0: h1 and x hold bmod samples and sample b of the batch reads sample
+// b % bmod of both (the same front under several timesteps: precompute_integrator); bidx [B] = b % bmod on the device, which the exact
+// fp32 conv reads h1 through.  The statistics of h1 are still taken inside the norm pass of every sample.
+void Model::res_block_back(const Schedule& sc, const ResBlockW& w, const float* h1, const float* x, float* y, int step, const TrunkIo& io,
+                           int bmod, const int* bidx) {
+    const int C = cfg.diff_channels, B = io.B, T = io.T, Ta = io.Ta, groups = gn_groups(C);
+    const long long bs = (long long)C * Ta;
+    const bool x3 = io.xs && w.c1.w3 && w.c2.w3;
+    const float* ada = sc.ss_table + (size_t)w.index * 2 * C * sc.n + (io.step_idx ? 0 : step);   // step_idx: per-sample steps
+    if (x3) launch_gn_split_planes(h1, bs, Ta, io.lens, T, B, C, groups, w.gn2_g, w.gn2_b, 1e-5f, ada, sc.n, 0, ACT_SILU, io.xs, io.s, io.step_idx, bmod);
+    else launch_gn_coeffs(h1, bs, Ta, io.lens, T, B, C, groups, w.gn2_g, w.gn2_b, 1e-5f, ada, sc.n, 0, io.ab, io.s, io.step_idx, bmod);
+    ConvParams q = cp(h1, C, y, C, B, T, Ta, io.lens);
+    q.pro_ab = io.ab;
+    q.pro_act = ACT_SILU;
     q.pad = 1;
-    q.y = y;
+    if (x3) {
+        with_planes(q, io.xs, T);
+        q.p1 = io.p1;
+    } else if (bmod) {
+        DTTS_REQUIRE(bidx, "res_block_back: a shared h1 needs the sample index table");
+        q.x_bidx = bidx;
+    }
     with_res(q, x, bs, Ta);
+    q.res_bmod = bmod;
     run_conv(w.c2, q, io.s);
 }
 
@@ -331,12 +384,13 @@ void Model::res_block_fwd(const Schedule& sc, const ResBlockW& w, const float* x
 // unconditioned_embedding), so its output depends only on (timestep, length): it is evaluated once per DISTINCT length in
 // the batch instead of once per utterance (identical values, 3 of 16 layers x half the batch less work).
 Model::PairPlan Model::plan_pair(const int* lens_host, int B, int T, hipStream_t s) {
-    std::vector<int> l2(2 * B), li, um(2 * B), ul;
+    std::vector<int> l2(2 * B), li, um(4 * B), ul;       // um: umap [2B], then xmap [2B]
     for (int b = 0; b < B; ++b) {
         const int len = lens_host ? lens_host[b] : T;
         l2[b] = l2[B + b] = len;
         li.push_back(len);
         um[b] = b;
+        um[2 * B + b] = um[3 * B + b] = b;
         int gidx = -1;
         for (size_t k = 0; k < ul.size(); ++k)
             if (ul[k] == len) gidx = (int)k;
@@ -349,46 +403,39 @@ Model::PairPlan Model::plan_pair(const int* lens_host, int B, int T, hipStream_t
     pl.ulen = ul;
     pl.lens2 = upload_ints(l2.data(), 2 * B, s);
     pl.lens_i = upload_ints(li.data(), (int)li.size(), s);
-    pl.umap = upload_ints(um.data(), 2 * B, s);
+    pl.umap = upload_ints(um.data(), 4 * B, s);
+    pl.xmap = pl.umap + 2 * B;                    // (one table, one copy)
     register_cols(pl.lens2, l2.data(), 2 * B, T, s);
     register_cols(pl.lens_i, li.data(), (int)li.size(), T, s);
     return pl;
 }
 
 // One batched (cond | uncond) DiffusionTts.forward.  The two halves are independent until the sampler update, so they run on
-// two HIP streams (fork after the shared x-path, join before returning): the per-launch prologue/epilogue of one half's
-// kernels overlaps the matrix work of the other's (measured +6..9 % on the conv GEMMs).  DTTS_TWO_STREAMS=0 disables it.
-void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* cbuf0, const int* lens2, const int* lens_i, const int* umap, int B, int Nu,
-                              int T, int step, float* out2, hipStream_t s, const float* integ) {
-    const int C = cfg.diff_channels, Ta = T, OC = cfg.diff_out_channels;
+// HIP streams of their own (fork, join before returning): the per-launch prologue/epilogue of one chunk's kernels overlaps the matrix
+// work of the other's (measured +6..9 % on the conv GEMMs).  DTTS_TWO_STREAMS=0 disables it.
+// What a step runs in front of the fork is ONE launch, the split of x_t into planes (none on the exact fp32 kernels).  Each chunk then
+// opens with the composed x-path conv (xpath_: inp_block and the x half of integrating_conv, folded at bind time) on the planes of its
+// samples' x_t, with the code-path term P = W_integ2 . integrator_output as its residual: stack sample b reads x_t of sample xmap[b] and
+// P of sample umap[b] (the unconditional samples share one P per distinct length).  integ: the step's P from precompute_integrator's
+// table; without it (diff_step, diff_forward*, a table beyond DTTS_INTEG_MAX_GB) the integrator and one integ2_ launch over its
+// B + Nu outputs run here first.
+void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* cbuf0, const PairPlan& pl, int B, int T, int step, float* out2,
+                              hipStream_t s, const float* integ) {
+    const int C = cfg.diff_channels, Ta = T, OC = cfg.diff_out_channels, MC = cfg.mel_channels, Nu = pl.Nu;
+    const int *lens2 = pl.lens2, *lens_i = pl.lens_i;
     const long long bs = (long long)C * Ta;
     static const bool env_two = env_on("DTTS_TWO_STREAMS");
     const bool two_streams = env_two && opt_two_streams_;
     const bool x3 = use_x3();
     DTTS_REQUIRE(!opt_trunk_fp16_ || x3, "trunk_fp16 = 1 needs the split-precision kernels (conv_x3 = 1)");
 
-    // shared x path: inp_block + the x-half of integrating_conv (+ bias) on the B samples (vqvae/diff_model.py:296-298)
-    float* xin = ws().f32((size_t)B * C * Ta);
-    float* xpath = ws().f32((size_t)B * C * Ta);
-    {
-        ConvParams p = cp(x, cfg.mel_channels, T, T, lens2, xin, C, T, Ta, lens2, B);
-        p.pad = 1;
-        ConvParams q = cp(xin, C, xpath, C, B, T, Ta, lens2);
-        if (x3) {
-            void* xs0 = ws().raw(x3_bytes(B, C, T));
-            launch_split_planes(x, p.x_bs, T, nullptr, ACT_NONE, lens2, T, B, cfg.mel_channels, xs0, s);
-            with_planes(p, xs0, T);
-            run_conv(inp_block_, p, s);
-            launch_split_planes(xin, bs, Ta, nullptr, ACT_NONE, lens2, T, B, C, xs0, s);
-            with_planes(q, xs0, T);
-            run_conv(integ1_, q, s);
-        } else {
-            run_conv(inp_block_, p, s);
-            run_conv(integ1_, q, s);
-        }
+    void* xs0 = nullptr;                                // planes of x_t, read by every chunk's opening conv
+    if (x3) {
+        xs0 = ws().raw(x3_bytes(B, MC, T));
+        launch_split_planes(x, (long long)MC * T, T, nullptr, ACT_NONE, lens2, T, B, MC, xs0, s);
     }
     // Both CFG halves are the same B-sample stack on the same weights: the 2B samples form ONE stack that is cut into NS equal
-    // chunks, each a launch sequence on its own HIP stream (fork after the shared x-path, join before returning).  NS = 1: one
+    // chunks, each a launch sequence on its own HIP stream (fork after the split of x_t, join before returning).  NS = 1: one
     // 2B-sample launch per layer (best per-kernel efficiency: a 768-channel conv is one full wave of workgroups); NS = 2 (default):
     // cond | uncond on two streams - the HBM-bound GroupNorm/split passes and the VALU-bound attention of one chunk run under the
     // matrix work of the other (measured 3.3 % faster end to end than NS = 1 with the fp16-plane kernels); option "cfg_streams".
@@ -402,13 +449,15 @@ void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* c
     for (int k = 1; k < NS; ++k)
         if (!sx_[k - 1]) make_side_stream(&sx_[k - 1]);
     if (NS > 1) ensure_fork_events();
-    // conditioning_timestep_integrator (vqvae/diff_model.py:295) on B code embeddings | Nu unconditional inputs: precomputed for all
-    // steps before the loop (precompute_integrator), or evaluated here as one (B + Nu)-sample batch
-    const float* code_path = integ;
+    // conditioning_timestep_integrator (vqvae/diff_model.py:295) on B code embeddings | Nu unconditional inputs, then the code half of
+    // integrating_conv (:298) on its outputs: precomputed for all steps before the loop (precompute_integrator), or evaluated here as one
+    // (B + Nu)-sample batch
+    const float* P = integ;
     if (!integ) {
-        float* bufI = ws().f32((size_t)Bi * C * Ta);
+        float* bufP = ws().f32((size_t)Bi * C * Ta);
         const size_t mark = ws().mark();
         const size_t act = (size_t)Bi * C * Ta;
+        float* bufI = ws().f32(act);
         float* tA = ws().f32(act);
         float* tB = ws().f32(act);
         float* qkv = ws().f32(qkv_floats(Bi, C, T));
@@ -420,13 +469,9 @@ void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* c
             attention_block(integ_[l].at, tB, bufI, qkv, tA, io);
             in = bufI;
         }
+        code_half(bufI, bufP, io);
         ws().rewind(mark);
-        code_path = bufI;
-    }
-    void* xs_code = nullptr;
-    if (x3) {
-        xs_code = ws().raw(x3_bytes(Bi, C, T));
-        launch_split_planes(code_path, bs, Ta, nullptr, ACT_NONE, lens_i, T, Bi, C, xs_code, s);
+        P = bufP;
     }
     if (NS > 1) {
         DTTS_CHECK_HIP(hipEventRecord(ev_fork_, s));
@@ -443,13 +488,14 @@ void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* c
         float* qkv = ws().f32(qkv_floats(n, C, T));
         TrunkIo io{lens, n, T, Ta, st, ws().f32((size_t)n * C * 2)};
         io.xs = x3 ? ws().raw(x3_bytes(n, C, T)) : nullptr;
-        // integrating_conv, code half, accumulated onto the shared x-path term (the residual of stack sample b is xpath[b % B])
-        ConvParams r = cp(code_path, C, bufB, C, n, T, Ta, lens);
-        with_res(r, xpath + (size_t)(b0 % B) * C * Ta, bs, Ta);
-        r.res_bmod = n > B ? B : 0;
-        r.x_bidx = umap + b0;                          // code-path sample of stack sample b (uncond samples share one per length)
-        if (x3) with_planes(r, xs_code, T);
-        run_conv(integ2_, r, st);
+        // inp_block + integrating_conv (:296-298): the composed x-path conv on x_t, the code-path term as its residual
+        ConvParams r = cp(x, MC, T, T, lens, bufB, C, T, Ta, lens, n);
+        r.pad = 1;
+        r.x_bidx = pl.xmap + b0;                       // x_t of stack sample b: (b0 + b) % B
+        with_res(r, P, bs, Ta);
+        r.res_bidx = pl.umap + b0;                     // code-path sample of stack sample b (uncond samples share one per length)
+        if (x3) with_planes(r, xs0, T);
+        run_conv(xpath_, r, st);
         // main stack (:299-309)
         float* cur = bufB;
         float* t1 = bufA;
@@ -480,10 +526,21 @@ void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* c
     }
 }
 
-size_t Model::rows_ws_bytes(int B, int C, int T) {
+// the code half of integrating_conv on the integrator's outputs: P = W_integ2 . in (no bias: that is in xpath_), on io's batch and stream
+void Model::code_half(const float* in, float* P, const TrunkIo& io) {
+    const int C = cfg.diff_channels;
+    ConvParams r = cp(in, C, P, C, io.B, io.T, io.Ta, io.lens);
+    if (io.xs && integ2_.w3) {
+        launch_split_planes(in, (long long)C * io.Ta, io.Ta, nullptr, ACT_NONE, io.lens, io.T, io.B, C, io.xs, io.s);
+        with_planes(r, io.xs, io.T);
+    }
+    run_conv(integ2_, r, io.s);
+}
+
+size_t Model::rows_ws_bytes(int B, int C, int T) const {
     const size_t act = (size_t)B * C * T;
-    // x path (2 act) + integrator output (act) + one block's scratch (3 act + qkv + coefficients); planes: x path, code path, blocks
-    return sizeof(float) * (6 * act + qkv_floats(B, C, T) + (size_t)2 * B * C) + 3 * x3_bytes(B, C, T) + 32 * 256;
+    // integrator output (act) + one block's scratch (3 act + qkv + coefficients); planes: x_t, blocks
+    return sizeof(float) * (4 * act + qkv_floats(B, C, T) + (size_t)2 * B * C) + x3_bytes(B, cfg.mel_channels, T) + x3_bytes(B, C, T) + 32 * 256;
 }
 
 // DiffusionTts.forward (vqvae/diff_model.py:262-322), conditional branch only, every row at its own column of sc: the launch sequence of
@@ -500,35 +557,15 @@ void Model::diff_forward_rows_s(const Schedule& sc, const float* x, const float*
     const int* lens = upload_ints(l.data(), B, s);
     const int* steps = upload_ints(step_of_row, B, s);
     register_cols(lens, l.data(), B, T, s);
-    float* xin = ws().f32(act);
-    float* xpath = ws().f32(act);
     float* bufI = ws().f32(act);
     float* bufA = ws().f32(act);
     float* bufB = ws().f32(act);
     float* bufC = ws().f32(act);
     float* qkv = ws().f32(qkv_floats(B, C, T));
     TrunkIo io{lens, B, T, Ta, s, ws().f32((size_t)B * C * 2)};
-    void* xs0 = x3 ? ws().raw(x3_bytes(B, C, T)) : nullptr;
-    void* xs_code = x3 ? ws().raw(x3_bytes(B, C, T)) : nullptr;
+    void* xs0 = x3 ? ws().raw(x3_bytes(B, cfg.mel_channels, T)) : nullptr;
     io.xs = x3 ? ws().raw(x3_bytes(B, C, T)) : nullptr;
     io.step_idx = steps;
-    // x path: inp_block + the x-half of integrating_conv (+ bias)  (:296-298)
-    {
-        ConvParams p = cp(x, cfg.mel_channels, T, T, lens, xin, C, T, Ta, lens, B);
-        p.pad = 1;
-        ConvParams q = cp(xin, C, xpath, C, B, T, Ta, lens);
-        if (x3) {
-            launch_split_planes(x, p.x_bs, T, nullptr, ACT_NONE, lens, T, B, cfg.mel_channels, xs0, s);
-            with_planes(p, xs0, T);
-            run_conv(inp_block_, p, s);
-            launch_split_planes(xin, bs, Ta, nullptr, ACT_NONE, lens, T, B, C, xs0, s);
-            with_planes(q, xs0, T);
-            run_conv(integ1_, q, s);
-        } else {
-            run_conv(inp_block_, p, s);
-            run_conv(integ1_, q, s);
-        }
-    }
     // conditioning_timestep_integrator (:295) on the B code embeddings
     const float* in = code_emb;
     for (int li = 0; li < 3; ++li) {
@@ -536,14 +573,17 @@ void Model::diff_forward_rows_s(const Schedule& sc, const float* x, const float*
         attention_block(integ_[li].at, bufB, bufI, qkv, bufA, io);
         in = bufI;
     }
-    // integrating_conv, code half, accumulated onto the x-path term
-    ConvParams r = cp(bufI, C, bufB, C, B, T, Ta, lens);
-    with_res(r, xpath, bs, Ta);
+    // integrating_conv, code half (into bufC, free until the first block's c2), then inp_block + the x half as the composed x-path conv
+    // (:296-298) with that term as its residual
+    code_half(bufI, bufC, io);
+    ConvParams r = cp(x, cfg.mel_channels, T, T, lens, bufB, C, T, Ta, lens, B);
+    r.pad = 1;
+    with_res(r, bufC, bs, Ta);
     if (x3) {
-        launch_split_planes(bufI, bs, Ta, nullptr, ACT_NONE, lens, T, B, C, xs_code, s);
-        with_planes(r, xs_code, T);
+        launch_split_planes(x, r.x_bs, T, nullptr, ACT_NONE, lens, T, B, cfg.mel_channels, xs0, s);
+        with_planes(r, xs0, T);
     }
-    run_conv(integ2_, r, s);
+    run_conv(xpath_, r, s);
     // main stack and tail (:299-309), three products throughout
     float* cur = bufB;
     float* t1 = bufA;
@@ -579,9 +619,10 @@ void Model::diff_forward_rows(int sched_id, const float* x, const float* code_em
     diff_forward_rows_s(sc, x, code_emb, lens_host, B, T, step_of_row, out, s);
 }
 
-static size_t integ_ws_bytes(int Bv, int C, int T) {
+// scratch of precompute_integrator: layer 0's shared h1 (Bi samples) + two lanes of Bv samples each
+static size_t integ_ws_bytes(int Bi, int Bv, int C, int T) {
     const size_t act = (size_t)Bv * C * T;
-    return sizeof(float) * (act + 2 * (3 * act + qkv_floats(Bv, C, T) + (size_t)2 * Bv * C)) + 2 * x3_bytes(Bv, C, T) + 32 * 256;
+    return sizeof(float) * ((size_t)Bi * C * T + 2 * (3 * act + qkv_floats(Bv, C, T) + (size_t)2 * Bv * C)) + 2 * x3_bytes(Bv, C, T) + 32 * 256;
 }
 static int integ_chunk(int Bi) {     // steps per batched evaluation (~36 samples per launch; DTTS_INTEG_SAMPLES overrides)
     // (batch 1, 12 / 20 / 36 / 52 / 100 samples per launch: diff_sample 122.8 - 126.2 / 123.1 / 123.5 - 124.2 / 123.4 / 123.6 ms - flat within the
@@ -590,8 +631,8 @@ static int integ_chunk(int Bi) {     // steps per batched evaluation (~36 sample
     return std::max(1, target / Bi);
 }
 
-void Model::precompute_integrator(const Schedule& sc, const float* cbuf0, const int* lens_i_host, int B, int Nu, int T, const std::vector<int>& steps,
-                                  float* integ_all, hipStream_t s) {
+void Model::precompute_integrator(const Schedule& sc, const float* cbuf0, const int* lens_i, const int* lens_i_host, int B, int Nu, int T,
+                                  const std::vector<int>& steps, float* integ_all, hipStream_t s) {
     const int C = cfg.diff_channels, Bi = B + Nu, J = integ_chunk(Bi), NS = (int)steps.size();
     const size_t ct = (size_t)C * T, mark = ws().mark();
     const int Bv = J * Bi;
@@ -601,9 +642,7 @@ void Model::precompute_integrator(const Schedule& sc, const float* cbuf0, const 
     if (two && !sx_[0]) make_side_stream(&sx_[0]);
     hipStream_t side = sx_[0];
     if (two) ensure_fork_events();
-    float* vin = ws().f32((size_t)Bv * ct);
-    for (int j = 0; j < J; ++j)
-        DTTS_CHECK_HIP(hipMemcpyAsync(vin + (size_t)j * Bi * ct, cbuf0, sizeof(float) * (size_t)Bi * ct, hipMemcpyDeviceToDevice, s));
+    float* h1 = ws().f32((size_t)Bi * ct);
     // chunks of J steps alternate between the two streams (independent of each other), each with its own scratch
     struct Lane { hipStream_t st; float *bufA, *bufB, *bufC, *qkv, *ab; void* xs; };
     Lane lanes[2];
@@ -616,11 +655,18 @@ void Model::precompute_integrator(const Schedule& sc, const float* cbuf0, const 
         lanes[q].ab = ws().f32((size_t)2 * Bv * C);
         lanes[q].xs = x3 ? ws().raw(x3_bytes(Bv, C, T)) : nullptr;
     }
+    // Layer 0's front, h1 = c1(SiLU(GN(cbuf0))), sees no timestep (it enters a ResBlock at the second norm): once per request on the
+    // Bi inputs, in front of the fork; every chunk's sample j * Bi + b then reads h1 - and cbuf0, the block's residual - of sample b
+    {
+        TrunkIo io0{lens_i, Bi, T, T, s, lanes[0].ab};
+        io0.xs = lanes[0].xs;
+        res_block_front(integ_[0].rb, cbuf0, h1, io0);
+    }
     if (two) {
         DTTS_CHECK_HIP(hipEventRecord(ev_fork_, s));
         DTTS_CHECK_HIP(hipStreamWaitEvent(side, ev_fork_, 0));
     }
-    std::vector<int> lv(Bv), sv(Bv);
+    std::vector<int> lv(Bv), sv(Bv), bv(Bv);
     int ci = 0;
     // profile sampling: both lanes of a chunk pair, or neither - and WHICH pairs rotates from call to call, so that over step_every calls
     // every pair is bracketed exactly once: the bracketed share of this pre-pass is 1 / step_every like the loop's (a fixed choice of
@@ -634,9 +680,11 @@ void Model::precompute_integrator(const Schedule& sc, const float* cbuf0, const 
             for (int b = 0; b < Bi; ++b) {
                 lv[j * Bi + b] = lens_i_host[b];
                 sv[j * Bi + b] = steps[k0 + j];
+                bv[j * Bi + b] = b;
             }
         const int* dl = upload_ints(lv.data(), nb, L.st);
         const int* ds = upload_ints(sv.data(), nb, L.st);
+        const int* db = x3 ? nullptr : upload_ints(bv.data(), nb, L.st);      // (the exact fp32 conv reads the shared h1 through it)
         register_cols(dl, lv.data(), nb, T, L.st);
         float* outp = integ_all + (size_t)k0 * Bi * ct;
         TrunkIo io{dl, nb, T, T, L.st, L.ab};              // (the integrator always takes three products)
@@ -646,9 +694,11 @@ void Model::precompute_integrator(const Schedule& sc, const float* cbuf0, const 
             res_block_fwd(sc, l.rb, in, L.bufB, L.bufC, 0, io);
             attention_block(l.at, L.bufC, o, L.qkv, L.bufB, io);
         };
-        dlayer(integ_[0], vin, L.bufA);
+        res_block_back(sc, integ_[0].rb, h1, cbuf0, L.bufC, 0, io, Bi, db);
+        attention_block(integ_[0].at, L.bufC, L.bufA, L.qkv, L.bufB, io);
         dlayer(integ_[1], L.bufA, L.bufA);
-        dlayer(integ_[2], L.bufA, outp);
+        dlayer(integ_[2], L.bufA, L.bufA);
+        code_half(L.bufA, outp, io);                                       // the table holds P = W_integ2 . integrator output
         register_cols(dl, nullptr, 0, T, L.st);                        // enqueued: forget this chunk's table
     }
     Profiler::gate() = true;
@@ -659,19 +709,18 @@ void Model::precompute_integrator(const Schedule& sc, const float* cbuf0, const 
     ws().rewind(mark);
 }
 
-static size_t pair_ws_bytes(int B, int C, int T) {
+static size_t pair_ws_bytes(int B, int C, int MC, int T) {
     const size_t act = (size_t)B * C * T;
-    // x path (2 act) + the chunks' scratch over the 2B stack (2 x 6 act) + the integrator evaluated in place (2 act out + 2 x 6 act
-    // scratch, only without the precomputed integrator) ; split planes: x path (B) + chunks (2B) + code path (2B) + integrator (2B)
-    return sizeof(float) * (2 * act + 2 * (3 * act + qkv_floats(B, C, T) + (size_t)2 * B * C) + 2 * act + 2 * (2 * act + qkv_floats(B, C, T) + (size_t)2 * B * C)) +
-           9 * x3_bytes(B, C, T) + 64 * 256;
+    // the code-path term of a step without the table (B + Nu <= 2B samples) + the scratch of a 2B-sample stack (3 x 2 act + qkv +
+    // coefficients + planes): the chunks' together, or in front of them - and given back - the in-step integrator's; planes of x_t
+    return sizeof(float) * (2 * act + 2 * (3 * act + qkv_floats(B, C, T) + (size_t)2 * B * C)) + 2 * x3_bytes(B, C, T) + x3_bytes(B, MC, T) + 64 * 256;
 }
 
 Model::PairCall Model::begin_pair(const float* code_emb, const int* lens_host, const int* sample_ids_host, int B, int T, hipStream_t s,
                                   size_t extra_bytes, size_t hist_floats) {
     const int C = cfg.diff_channels, OC = cfg.diff_out_channels;
     const size_t half = (size_t)B * C * T;
-    ws().ensure(pair_ws_bytes(B, C, T) + extra_bytes + sizeof(float) * (2 * half + (size_t)2 * B * OC * T + hist_floats) + 8192);
+    ws().ensure(pair_ws_bytes(B, C, cfg.mel_channels, T) + extra_bytes + sizeof(float) * (2 * half + (size_t)2 * B * OC * T + hist_floats) + 8192);
     PairCall pc;
     pc.pl = plan_pair(lens_host, B, T, s);
     pc.sids = sample_ids_host ? upload_ints(sample_ids_host, B, s) : nullptr;
@@ -697,7 +746,7 @@ void Model::diff_forward_s(Schedule& sc, const float* x, const float* code_emb, 
     const int OC = cfg.diff_out_channels;
     const PairCall pc = begin_pair(code_emb, lens_host, nullptr, B, T, s);
     const PairPlan& pl = pc.pl;
-    diff_forward_pair(sc, x, pc.cbuf0, pl.lens2, pl.lens_i, pl.umap, B, pl.Nu, T, step, pc.out2, s);
+    diff_forward_pair(sc, x, pc.cbuf0, pl, B, T, step, pc.out2, s);
     const float* src = pc.out2 + (cond_free ? (size_t)B * OC * T : 0);
     DTTS_CHECK_HIP(hipMemcpyAsync(out, src, sizeof(float) * (size_t)B * OC * T, hipMemcpyDeviceToDevice, s));
 }
@@ -753,14 +802,15 @@ void Model::diff_sample_ex(int sched_id, int sampler, float eta, const float* co
     DTTS_REQUIRE(!dpm || (eta == 0.f && !step_noise), "dpmsolver++ draws no noise: eta must be 0 and step_noise NULL");
     const int C = cfg.diff_channels, OC = cfg.diff_out_channels, MC = cfg.mel_channels;
     if (n_steps <= 0 || n_steps > sc.n) n_steps = sc.n;
-    // the integrator outputs of all steps are evaluated up front (opt-out: DTTS_INTEG_PRECOMPUTE=0); Nu <= B distinct lengths
+    // the code-path terms of all steps (the integrator's outputs through the code half of integrating_conv) are evaluated up front
+    // (opt-out: DTTS_INTEG_PRECOMPUTE=0); Nu <= B distinct lengths
     static const bool env_pre_on = env_on("DTTS_INTEG_PRECOMPUTE");
-    // the precomputed integrator outputs of all steps cost n_steps * 2B * C * T floats (3 GB at batch 8 x 10 s, 11 GB at batch 4 x 60 s):
-    // beyond DTTS_INTEG_MAX_GB (default 24) the integrator is evaluated inside every step instead (same values, no table)
+    // the precomputed terms of all steps cost n_steps * 2B * C * T floats (3 GB at batch 8 x 10 s, 11 GB at batch 4 x 60 s):
+    // beyond DTTS_INTEG_MAX_GB (default 24) the integrator and the code half run inside every step instead (same values, no table)
     static const double max_gb = []() { const char* v = env_str("DTTS_INTEG_MAX_GB"); return v ? atof(v) : 24.0; }();
     const size_t integ_table = sizeof(float) * (size_t)n_steps * 2 * B * C * T;
     const bool env_pre = env_pre_on && (double)integ_table <= max_gb * 1073741824.0;
-    const size_t integ_bytes = env_pre ? integ_table + integ_ws_bytes(integ_chunk(B + 1) * 2 * B, C, T) : 0;
+    const size_t integ_bytes = env_pre ? integ_table + integ_ws_bytes(2 * B, integ_chunk(B + 1) * 2 * B, C, T) : 0;
     const size_t hist_floats = dpm ? (size_t)B * MC * T : 0;          // DPM-Solver++(2M): the previous step's x0
     const PairCall pc = begin_pair(code_emb, lens_host, sample_ids_host, B, T, s, integ_bytes, hist_floats);
     const PairPlan& pl = pc.pl;
@@ -795,15 +845,14 @@ void Model::diff_sample_ex(int sched_id, int sampler, float eta, const float* co
         for (int b = 0; b < B; ++b) li[b] = lens_host ? lens_host[b] : T;
         for (int u = 0; u < pl.Nu; ++u) li[B + u] = pl.ulen[u];
         integ_all = ws().f32((size_t)n_steps * Bi * C * T);
-        precompute_integrator(sc, cbuf0, li.data(), B, pl.Nu, T, steps, integ_all, s);
+        precompute_integrator(sc, cbuf0, pl.lens_i, li.data(), B, pl.Nu, T, steps, integ_all, s);
     }
     const size_t mark = ws().mark();
     for (int k = 0; k < n_steps; ++k) {
         const int i = sc.n - 1 - k;
         Profiler::gate() = (k % Profiler::get().step_every) == 0;
         ws().rewind(mark);                              // the forward's scratch is re-carved every step
-        diff_forward_pair(sc, x, cbuf0, lens2, pl.lens_i, pl.umap, B, pl.Nu, T, i, out2, s,
-                          integ_all ? integ_all + (size_t)k * Bi * C * T : nullptr);
+        diff_forward_pair(sc, x, cbuf0, pl, B, T, i, out2, s, integ_all ? integ_all + (size_t)k * Bi * C * T : nullptr);
         const bool last = (k == n_steps - 1);
         const float* nz = step_noise ? step_noise + (size_t)k * B * MC * T : nullptr;
         if (dpm)
@@ -837,7 +886,7 @@ void Model::diff_step(int sched_id, int sampler, float eta, float* x, const floa
     const int OC = cfg.diff_out_channels, MC = cfg.mel_channels;
     const PairCall pc = begin_pair(code_emb, lens_host, sample_ids_host, B, T, s);
     const PairPlan& pl = pc.pl;
-    diff_forward_pair(sc, x, pc.cbuf0, pl.lens2, pl.lens_i, pl.umap, B, pl.Nu, T, step, pc.out2, s);
+    diff_forward_pair(sc, x, pc.cbuf0, pl, B, T, step, pc.out2, s);
     if (sampler == 1)
         launch_ddim_update(x, (long long)MC * T, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.ddim(step, eta), seed, pc.sids, step,
                            noise, 0, s, x0_out);
@@ -858,7 +907,7 @@ void Model::diff_step_dpm(int sched_id, float* x, float* x0_hist, const float* c
     const int OC = cfg.diff_out_channels, MC = cfg.mel_channels;
     const PairCall pc = begin_pair(code_emb, lens_host, nullptr, B, T, s);
     const PairPlan& pl = pc.pl;
-    diff_forward_pair(sc, x, pc.cbuf0, pl.lens2, pl.lens_i, pl.umap, B, pl.Nu, T, step, pc.out2, s);
+    diff_forward_pair(sc, x, pc.cbuf0, pl, B, T, step, pc.out2, s);
     launch_dpm_update(x, (long long)MC * T, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.dpm[step], x0_hist, 0, s, x0_out);
     DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
 }

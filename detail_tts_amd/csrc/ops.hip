@@ -28,12 +28,12 @@ __device__ __forceinline__ float block_sum(float v, float* red) {   // red: >= 4
 // problem even when |mean| >> std), float4 loads when the rows are 16-byte aligned.
 __global__ __launch_bounds__(256) void gn_coeffs_kernel(const float* x, long long x_bs, int x_cs, const int* lens, int T, int C,
                                                         int groups, const float* gamma, const float* beta, float eps,
-                                                        const float* ada, int ada_stride, int ada_bs, float* ab_out, const int* ada_idx) {
+                                                        const float* ada, int ada_stride, int ada_bs, float* ab_out, const int* ada_idx, int x_bmod) {
     __shared__ float red[8];
     const int g = blockIdx.x, b = blockIdx.y;
     const int len = lens ? lens[b] : T;
     const int cpg = C / groups;
-    const float* xg = x + (long long)b * x_bs + (long long)(g * cpg) * x_cs;
+    const float* xg = x + (long long)(x_bmod ? b % x_bmod : b) * x_bs + (long long)(g * cpg) * x_cs;
     const int n = cpg * len;
     const float k = xg[0];
     float s1 = 0.f, s2 = 0.f;
@@ -101,10 +101,10 @@ __global__ __launch_bounds__(256) void gn_coeffs_kernel(const float* x, long lon
 
 void launch_gn_coeffs(const float* x, long long x_bs, int x_cs, const int* lens, int T, int B, int C, int groups,
                       const float* gamma, const float* beta, float eps, const float* ada, int ada_stride, int ada_bs,
-                      float* ab_out, hipStream_t s, const int* ada_idx) {
+                      float* ab_out, hipStream_t s, const int* ada_idx, int x_bmod) {
     DTTS_REQUIRE(C % groups == 0 && C / groups <= 256, "group size");
     hipLaunchKernelGGL(gn_coeffs_kernel, dim3(groups, B), dim3(256), 0, s, x, x_bs, x_cs, lens, T, C, groups, gamma, beta, eps,
-                       ada, ada_stride, ada_bs, ab_out, ada_idx);
+                       ada, ada_stride, ada_bs, ab_out, ada_idx, x_bmod);
     DTTS_CHECK_HIP(hipGetLastError());
 }
 

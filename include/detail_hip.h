@@ -576,8 +576,9 @@ int dtts_spectrogram(dtts_handle* h, const float* wav, const int* lens, int B, i
  *   "trunk_fp16"  (default 0): the reference's DiffusionTts.enable_fp16 / config "use_fp16" (vqvae/diff_model.py:143-157, 299-309: every
  *                 trunk layer except the first under autocast).  1 = layers[1:] of the diffusion trunk (9 of the 10 DiffusionLayers, the 3
  *                 ResBlocks) run their convs and their attention products QK^T, PV as ONE fp16 product with fp32 accumulation - plane 0
- *                 of the same operand images, 32 channels per K-step - instead of three.  layers[0], inp_block, integrating_conv, the
- *                 conditioning integrator, the time embedding / AdaGN tables and the out conv keep the three-product kernels; GroupNorm,
+ *                 of the same operand images, 32 channels per K-step - instead of three.  layers[0], the x-path conv (inp_block composed with
+ *                 the x half of integrating_conv at bind time), integrating_conv's code half, the conditioning integrator, the time
+ *                 embedding / AdaGN tables and the out conv keep the three-product kernels; GroupNorm,
  *                 softmax, residual adds and every activation between kernels stay fp32.  All samplers, any step count.  Refused with
  *                 conv_x3 = 0 (the exact fp32 kernels have no such mode), and conv_x3 = 0 is refused while it is 1.  A launch-time
  *                 kernel choice: the captured graphs (stage A's decode graphs) hold no trunk launch, none is dropped.
