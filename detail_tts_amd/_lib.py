@@ -122,6 +122,11 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "dtts_diff_training_losses": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, c_int_p, C.c_void_p, C.c_ulonglong, c_int_p, C.c_void_p, c_int_p,
                                             C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dtts_diff_bpd_terms": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dtts_diff_prior_bpd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dtts_diff_calc_bpd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_ulonglong, c_int_p,
+                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dtts_l1_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dtts_posterior_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_int_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_ulonglong, c_int_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -37,6 +37,7 @@ struct AttnParams {
     // attention_x3b only (set by its launcher): the keys of a (sample, head, query block) split over `ksplit` workgroups, whose waves
     // leave their unnormalised (O, l, m) in kpart; the last wave to arrive (kcount) merges them in split order
     int ksplit = 1;
+    int ksplit_max = 0;            // caller's cap on that split (0: the launcher's rule)
     float* kpart = nullptr;
     int* kcount = nullptr;
 };

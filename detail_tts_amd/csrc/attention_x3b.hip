@@ -608,6 +608,7 @@ void launch_flash_attention_x3b(const AttnParams& p, hipStream_t stream, AttnX3L
         S = ks_env;
         while (S > 1 && ((long long)base * S > ks_cus || AttnPlanes::nt64(p.T) < 2 * S || (size_t)base * S > X3_MAX_SLABS || (size_t)base * NW > X3_SPLIT_COUNTERS)) --S;
     }
+    if (p.ksplit_max > 0) S = std::min(S, p.ksplit_max);
     AttnParams q = p;
     if (S > 1) {
         q.ksplit = S;

@@ -543,6 +543,28 @@ int dtts_diff_training_losses(dtts_handle* h, int id, const float* x_start, cons
     DTTS_API_END(h)
 }
 
+int dtts_diff_bpd_terms(dtts_handle* h, int id, const float* model_out, const float* x_start, const float* x_t, const float* noise, const int* t,
+                        int R, int T, float* terms_out, float* pred_xstart, void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_bpd_terms(id, model_out, x_start, x_t, noise, t, R, T, terms_out, pred_xstart, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_diff_prior_bpd(dtts_handle* h, int id, const float* x_start, int B, int T, float* prior_out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_prior_bpd(id, x_start, B, T, prior_out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_diff_calc_bpd(dtts_handle* h, int id, const float* x_start, const float* code_emb, const int* lens, int B, int T, const float* noise,
+                       unsigned long long seed, const int* sample_ids, int rows_per_pass, float* vb, float* xstart_mse, float* mse, float* prior,
+                       float* total, void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_calc_bpd(id, x_start, code_emb, lens, B, T, noise, seed, sample_ids, rows_per_pass, vb, xstart_mse, mse, prior, total,
+                        (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
 int dtts_l1_mean(dtts_handle* h, const float* a, const float* b, int B, int C, int T, float* out, void* stream) {
     DTTS_API_BEGIN
     h->m->l1_mean(a, b, B, C, T, out, (hipStream_t)stream);

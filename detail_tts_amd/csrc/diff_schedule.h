@@ -18,6 +18,7 @@ struct ScheduleTables {
     std::vector<DiffStepCoefs> p;         // ancestral sampler (p_sample)
     std::vector<float> ac, ac_prev;       // fp32 alphas_cumprod / alphas_cumprod_prev (DDIM: the eta-dependent terms are per call)
     std::vector<float> sqrt_ac, sqrt_1m_ac;   // kind 0: fp32 sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod (q_sample, :243-260)
+    std::vector<float> log_1m_ac;         // kind 0: fp32 log_one_minus_alphas_cumprod (q_mean_variance, :230-241: _prior_bpd)
     std::vector<DpmStepCoefs> dpm;        // kind 1: the update of column i
     float cfk_k = 0.f;
     int n = 0;

@@ -54,6 +54,7 @@ void make_schedule(int trained, const std::vector<int>& tmap, float cfk_k, Sched
     sc.ac_prev.resize(n);
     sc.sqrt_ac.resize(n);
     sc.sqrt_1m_ac.resize(n);
+    sc.log_1m_ac.resize(n);
     for (int i = 0; i < n; ++i) {
         DiffStepCoefs k;
         k.sqrt_recip_ac = (float)std::sqrt(1.0 / acp[i]);
@@ -70,6 +71,7 @@ void make_schedule(int trained, const std::vector<int>& tmap, float cfk_k, Sched
         sc.ac_prev[i] = (float)acp_prev[i];
         sc.sqrt_ac[i] = (float)std::sqrt(acp[i]);
         sc.sqrt_1m_ac[i] = (float)std::sqrt(1.0 - acp[i]);
+        sc.log_1m_ac[i] = (float)std::log(1.0 - acp[i]);
     }
 }
 

@@ -177,6 +177,21 @@ private:
 };
 Arena* arena_override();     // the calling thread's stand-in (nullptr: none)
 
+// While one lives ON THE CALLING THREAD, the trunk's launches make no choice by the number of samples they cover: Model::run_conv caps
+// conv_x3's split-K at 1 and attention_block the attention's key split, the two places where the batch size picks a summation order.
+// A sample's result is then the same bits whatever rows share its launch (diff_calc_bpd: any rows_per_pass gives the same bits).
+class RowInvariantLaunches {
+public:
+    RowInvariantLaunches();
+    ~RowInvariantLaunches();
+    RowInvariantLaunches(const RowInvariantLaunches&) = delete;
+    RowInvariantLaunches& operator=(const RowInvariantLaunches&) = delete;
+    static bool on();
+
+private:
+    bool prev_;
+};
+
 class Model {
 public:
     Model(const dtts_config& cfg, int device);
@@ -231,6 +246,15 @@ public:
                               const int* sample_ids_host, const float* code_emb, const int* lens_host, int B, int T, float* terms_out,
                               float* pred_xstart, hipStream_t s);
     void l1_mean(const float* a, const float* b, int B, int C, int T, float* out, hipStream_t s);
+    // ---- the variational bound in bits per dimension (diff_bpd.h; calc_bpd_loop, _vb_terms_bpd, _prior_bpd,
+    // vqvae/utils/diffusion.py:903-928, 1098-1169).  terms_out [R][3] = (vb, xstart_mse, mse); vb / xstart_mse / mse [B][S], column j =
+    // timestep S - 1 - j; noise [S][B][128][T] by timestep or null (Philox STAGE_DIFF_BPD); rows_per_pass 0: the library's choice
+    void diff_bpd_terms(int sched_id, const float* model_out, const float* x_start, const float* x_t, const float* noise, const int* t_host,
+                        int R, int T, float* terms_out, float* pred_xstart, hipStream_t s);
+    void diff_prior_bpd(int sched_id, const float* x_start, int B, int T, float* prior_out, hipStream_t s);
+    void diff_calc_bpd(int sched_id, const float* x_start, const float* code_emb, const int* lens_host, int B, int T, const float* noise,
+                       unsigned long long seed, const int* sample_ids_host, int rows_per_pass, float* vb, float* xstart_mse, float* mse,
+                       float* prior, float* total, hipStream_t s);
     // host copy of a schedule's forward-process tables: out[i] = {sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod} of column i
     int diff_schedule_qtable(int sched_id, float* out, int cap);
     // one p_sample at `step` on x in place (unit entry of the sampler parity tests)

@@ -12,6 +12,11 @@ Arena* arena_override() { return t_arena_override; }
 ArenaUse::ArenaUse(Arena& a) : prev_(t_arena_override) { t_arena_override = &a; }
 ArenaUse::~ArenaUse() { t_arena_override = prev_; }
 
+static thread_local bool t_row_invariant = false;
+RowInvariantLaunches::RowInvariantLaunches() : prev_(t_row_invariant) { t_row_invariant = true; }
+RowInvariantLaunches::~RowInvariantLaunches() { t_row_invariant = prev_; }
+bool RowInvariantLaunches::on() { return t_row_invariant; }
+
 Arena::~Arena() {
     if (base_) (void)hipFree(base_);
 }
@@ -308,6 +313,7 @@ void Model::run_conv(const PackedConv& pc, ConvParams p, hipStream_t s, ConvX3La
         DTTS_REQUIRE(pc.w3, "conv has no split-precision weights");
         p.w3 = pc.w3;
         attach_cols(p);
+        if (RowInvariantLaunches::on()) p.ksplit_max = 1;
         launch_conv_x3(p, s, chosen);
         return;
     }

@@ -312,6 +312,7 @@ void Model::attention_block(const AttnBlockW& w, const float* x, float* y, float
     a.bias_tab = w.bias_tab;
     if (planes) a.planes = qkv;
     a.p1 = io.p1;
+    if (RowInvariantLaunches::on()) a.ksplit_max = 1;
     // the proj conv's input planes come straight from the attention epilogue; xs still holds the zero halo / tail columns that
     // gn_split_planes wrote for the qkv conv (same B, T, lens), and the qkv conv has consumed the rest
     const bool att_planes = planes && T + 1 < x3_tp(T);

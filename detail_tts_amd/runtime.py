@@ -547,6 +547,54 @@ class Runtime:
                                                     li[0] if li else None, B, T, _ptr(terms), _ptr(pred), self._stream()))
         return terms, pred
 
+    def diff_bpd_terms(self, sched, model_out, x_start, x_t, noise, t, want_pred=False):
+        """one timestep's terms of calc_bpd_loop on a given model output (dtts_diff_bpd_terms) -> terms cuda fp32 [R, 3] =
+        (vb, xstart_mse, mse) per row [, the clamped pred_xstart [R,128,T] with want_pred]"""
+        for a, nm in ((model_out, "model_out"), (x_start, "x_start"), (x_t, "x_t"), (noise, "noise")):
+            _check(a, nm)
+        R, _, T = x_start.shape
+        if tuple(model_out.shape) != (R, 2 * x_start.shape[1], T) or x_t.shape != x_start.shape or noise.shape != x_start.shape:
+            raise DttsError("diff_bpd_terms: model_out [R,256,T] and x_start / x_t / noise [R,128,T]")
+        ti = self._loss_t(t, R, "diff_bpd_terms")
+        terms = torch.zeros((R, 3), device=self.device, dtype=torch.float32)
+        pred = torch.empty_like(x_start) if want_pred else None
+        self._rc(self.lib.dtts_diff_bpd_terms(self.h, int(sched), _ptr(model_out), _ptr(x_start), _ptr(x_t), _ptr(noise), ti[0], R, T,
+                                              _ptr(terms), _ptr(pred), self._stream()))
+        return (terms, pred) if want_pred else terms
+
+    def diff_prior_bpd(self, sched, x_start):
+        """_prior_bpd on the last step of schedule `sched` (dtts_diff_prior_bpd) -> cuda fp32 [B]"""
+        _check(x_start, "x_start")
+        B, _, T = x_start.shape
+        prior = torch.zeros((B,), device=self.device, dtype=torch.float32)
+        self._rc(self.lib.dtts_diff_prior_bpd(self.h, int(sched), _ptr(x_start), B, T, _ptr(prior), self._stream()))
+        return prior
+
+    def diff_calc_bpd(self, sched, x_start, code_emb, noise=None, seed=0, sample_ids=None, lens=None, rows_per_pass=0):
+        """calc_bpd_loop on the S steps of schedule `sched` (dtts_diff_calc_bpd) -> dict(total_bpd [B], prior_bpd [B], vb / xstart_mse /
+        mse [B, S], column j = timestep S - 1 - j), cuda fp32.  noise [S, B, 128, T] indexed by timestep, or None: Philox stage 7 from
+        (seed, sample_ids).  rows_per_pass (utterance, timestep) pairs per trunk pass (0: the library's choice); same bits for any."""
+        _check(x_start, "x_start"); _check(code_emb, "code_emb"); _check(noise, "noise")
+        B, _, T = x_start.shape
+        if code_emb is None or tuple(code_emb.shape[::2]) != (B, T):
+            raise DttsError("diff_calc_bpd: code_emb [B,768,T] is required")
+        if isinstance(rows_per_pass, bool) or not isinstance(rows_per_pass, (int, np.integer)) or rows_per_pass < 0:
+            raise DttsError(f"diff_calc_bpd: rows_per_pass must be an integer >= 0, not {rows_per_pass!r}")
+        n = C.c_int(0)
+        self._rc(self.lib.dtts_diff_schedule_qtable(self.h, int(sched), None, 0, C.byref(n)))
+        S = n.value
+        if noise is not None and tuple(noise.shape) != (S, B) + tuple(x_start.shape[1:]):
+            raise DttsError(f"diff_calc_bpd: noise must be [{S}, {B}, {x_start.shape[1]}, {T}] (indexed by timestep), not {tuple(noise.shape)}")
+        si = self._row_ints(list(range(B)) if sample_ids is None else sample_ids, B, "diff_calc_bpd", "sample_ids")
+        li = self._row_ints(lens, B, "diff_calc_bpd", "lens") if lens is not None else None
+        out = {k: torch.zeros((B, S), device=self.device, dtype=torch.float32) for k in ("vb", "xstart_mse", "mse")}
+        out["prior_bpd"] = torch.zeros((B,), device=self.device, dtype=torch.float32)
+        out["total_bpd"] = torch.zeros((B,), device=self.device, dtype=torch.float32)
+        self._rc(self.lib.dtts_diff_calc_bpd(self.h, int(sched), _ptr(x_start), _ptr(code_emb), li[0] if li else None, B, T, _ptr(noise),
+                                             int(seed), si[0], int(rows_per_pass), _ptr(out["vb"]), _ptr(out["xstart_mse"]), _ptr(out["mse"]),
+                                             _ptr(out["prior_bpd"]), _ptr(out["total_bpd"]), self._stream()))
+        return out
+
     def l1_mean(self, a, b):
         """mean |a - b| over two [B, C, T] tensors (dtts_l1_mean: fixed-order reduction) -> 0-d fp32 cuda"""
         _check(a, "a"); _check(b, "b")

@@ -847,6 +847,29 @@ class SynthesizerTrn:
             total = total + losses[b]
         return total / B
 
+    def diffusion_bpd(self, y, y_lengths, data, *, noise=None, seed=0, rows_per_pass=0):
+        """The diffusion decoder's variational bound in bits per dimension on one validation batch: forward_diff's preparation
+        (x_start = normalize_torch_mel(data['raw_mel']), encode, the GPT latents with return_latent=True, clip_inputs=False,
+        conditioning_latent = get_conditioning(y)), then diffuser.calc_bpd_loop (vqvae/utils/diffusion.py:1114-1169) on the 200-step
+        schedule -> its dict: total_bpd, prior_bpd [B]; vb, xstart_mse, mse [B, 200] (column j = timestep 199 - j), fp32 CUDA.
+        noise [200, B, 128, T] indexed by timestep, or None: Philox noise keyed by (seed, row, timestep).  y_lengths is unused, as in
+        forward_diff.  The unguided model's likelihood: self.diffuser is built with conditioning_free=False."""
+        raw_mel = torch.as_tensor(data["raw_mel"]).to(self.device, torch.float32).contiguous()
+        if self.rt.get_option("trunk_fp16"):
+            raise NotImplementedError("diffusion_bpd runs the three-product trunk only: switch the fp16 trunk mode off for this call "
+                                      "(diffusion.enable_fp16 = False)")
+        if noise is not None:
+            noise = torch.as_tensor(noise).to(self.device, torch.float32).contiguous()
+        code, _ = self.encode(raw_mel, data["raw_spec_length"])
+        aligned = self.gpt(raw_mel, data["raw_spec_length"], data["text"], data["text_length"], code, data["raw_wav_length"],
+                           return_latent=True, clip_inputs=False)
+        cond = self.diffusion.get_conditioning(torch.as_tensor(y).to(self.device, torch.float32))
+        sched = self.rt.diff_schedule(self.diffuser.timestep_map)
+        # forward_diff's normalisation kernel (the x_t it also forms, at t = 0 with raw_mel standing in for the noise, is dropped)
+        x_start, _, _ = self.rt.diff_q_sample(sched, raw_mel, [0] * raw_mel.shape[0], noise=raw_mel, normalize=True)
+        return self.diffuser.calc_bpd_loop(self.diffusion, x_start, noise=noise, seed=seed, rows_per_pass=rows_per_pass,
+                                           model_kwargs={"aligned_conditioning": aligned, "conditioning_latent": cond})
+
     def forward_vq(self, y, y_lengths, data=None):
         """vqvae/model_24k.py:654-666, the VQ stage's validation loss -> a 0-d fp32 CUDA tensor: L1(vq_dec(quantizer(vq_enc(y)) +
         vq_ref_enc(y * mask, mask)), y), the mean over the whole [B,128,T] rectangle.  In eval mode the reference quantizer's commit

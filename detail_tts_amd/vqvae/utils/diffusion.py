@@ -1,7 +1,8 @@
 """Sampler object mirroring the subset of the reference's SpacedDiffusion that inference and evaluation use
 (vqvae/utils/diffusion.py:179-228 + 1172-1272; p_sample_loop :654-742, ddim_sample_loop :819-899, k_diffusion_sample_loop :487-581,
-sample_loop :640-652; q_sample :243-260, training_losses :930-1012).  The arithmetic lives in libdetail_hip.so (dtts_diff_sample_ex,
-dtts_diff_q_sample, dtts_diff_training_losses); this class carries the schedule constants and the call surface."""
+sample_loop :640-652; q_sample :243-260, training_losses :930-1012; calc_bpd_loop :1114-1169, _vb_terms_bpd :903-928, _prior_bpd
+:1098-1112).  The arithmetic lives in libdetail_hip.so (dtts_diff_sample_ex, dtts_diff_q_sample, dtts_diff_training_losses,
+dtts_diff_calc_bpd); this class carries the schedule constants and the call surface."""
 from __future__ import annotations
 
 import numpy as np
@@ -131,6 +132,71 @@ class SpacedDiffusion:
         terms, pred = rt.diff_training_losses(rt.diff_schedule(self.timestep_map), x_start.float().contiguous(), ts, emb, noise=noise,
                                               seed=seed, sample_ids=sample_ids)
         return {"loss": terms[:, 2].contiguous(), "mse": terms[:, 0].contiguous(), "vb": terms[:, 1].contiguous(), "x_start_predicted": pred}
+
+    # ---------------------------------------------------------------------------------------------------- bits per dimension
+    def _bpd_conditioning(self, who, model, T, clip_denoised, model_kwargs):
+        """what calc_bpd_loop and _vb_terms_bpd refuse, before any launch -> (runtime, code embedding [B,768,T]).  These entries evaluate
+        the model once per (row, timestep) and run no sampling loop, so they do not pass through _check."""
+        if clip_denoised is not True:
+            raise ValueError(f"{who}: clip_denoised must be True (the reference's p_mean_variance asserts it)")
+        if self.conditioning_free:
+            raise NotImplementedError(f"{who} on a conditioning_free=True diffuser: the bound of a guided (cond / uncond mixed) mean is not "
+                                      "a likelihood of any model and is not implemented; use a conditioning_free=False diffuser "
+                                      "(SynthesizerTrn.diffuser)")
+        kw = dict(model_kwargs or {})
+        emb = kw.get("precomputed_aligned_embeddings")
+        if emb is None and (kw.get("aligned_conditioning") is None or kw.get("conditioning_latent") is None):
+            raise ValueError("model_kwargs needs precomputed_aligned_embeddings, or aligned_conditioning and conditioning_latent")
+        rt = model.rt
+        if rt.get_option("trunk_fp16"):
+            raise NotImplementedError(f"{who} runs the three-product trunk only: switch the fp16 trunk mode off for this call "
+                                      "(diffusion.enable_fp16 = False)")
+        if emb is None:
+            emb = model.timestep_independent(kw["aligned_conditioning"], kw["conditioning_latent"], T)
+        return rt, emb
+
+    def _prior_bpd(self, x_start):
+        """vqvae/utils/diffusion.py:1098-1112 on the device -> fp32 CUDA [B]: the mean over [128, T] of normal_kl(sqrt_alphas_cumprod[S-1]
+        x_start, log_one_minus_alphas_cumprod[S-1], 0, 0) / ln 2.  Runs on `diffuser.rt`, as q_sample does."""
+        if self.rt is None:
+            raise RuntimeError("_prior_bpd needs a Runtime: set `diffuser.rt` (SynthesizerTrn does for its own diffusers)")
+        return self.rt.diff_prior_bpd(self.rt.diff_schedule(self.timestep_map), x_start.float().contiguous())
+
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
+        """vqvae/utils/diffusion.py:903-928 -> dict(output: fp32 CUDA [B] in bits, the decoder NLL where t == 0 and the KL elsewhere;
+        pred_xstart [B,128,T], clamped to [-1, 1]).  t [B]: integers in [0, num_timesteps), checked on the host; row b's forward runs at
+        timestep_map[t[b]] (dtts_diff_forward_rows), then dtts_diff_bpd_terms.  Refusals as in calc_bpd_loop."""
+        B, _, T = x_start.shape
+        ts = check_timesteps(t, B, self.num_timesteps)
+        rt, emb = self._bpd_conditioning("_vb_terms_bpd", model, T, clip_denoised, model_kwargs)
+        sched = rt.diff_schedule(self.timestep_map)
+        x_start, x_t = x_start.float().contiguous(), x_t.float().contiguous()
+        out = rt.diff_forward_rows(x_t, ts, emb, sched=sched)
+        # (the ε MSE the kernel also forms needs the noise, which this entry does not have: x_t stands in and that column is dropped)
+        terms, pred = rt.diff_bpd_terms(sched, out, x_start, x_t, x_t, ts, want_pred=True)
+        return {"output": terms[:, 0].contiguous(), "pred_xstart": pred}
+
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, *, noise=None, seed=0, sample_ids=None, rows_per_pass=0):
+        """vqvae/utils/diffusion.py:1114-1169, the whole variational bound in bits per dimension, eval() semantics, no gradients ->
+        dict(total_bpd [B], prior_bpd [B], vb / xstart_mse / mse [B, num_timesteps]; fp32 CUDA).  Column j of the three tables is
+        timestep num_timesteps - 1 - j, as the reference stacks them.  model: a detail_tts_amd DiffusionTts; model_kwargs as in
+        training_losses.  One device call (dtts_diff_calc_bpd): the (row, timestep) pairs run rows_per_pass at a time (0: the library's
+        choice) as rows of the per-row trunk forward; the results are the same bits for every rows_per_pass.
+
+        noise None: every (row, timestep) draws from the Philox spec on its own stage (7), keyed by (seed, sample_ids[b], t) - never
+        torch's RNG, and independent of the batch.  noise [num_timesteps, B, 128, T]: noise[t] is used AT TIMESTEP t; the reference
+        draws with randn_like in loop order (t = num_timesteps - 1 first), so a caller who wants its numbers stores its k-th draw at
+        noise[num_timesteps - 1 - k].
+
+        Refused before any launch: clip_denoised=False (ValueError: the reference asserts it), a conditioning_free=True diffuser
+        (NotImplementedError: a guided bound is not a likelihood), the fp16 trunk mode (NotImplementedError), missing conditioning
+        (ValueError)."""
+        B, _, T = x_start.shape
+        rt, emb = self._bpd_conditioning("calc_bpd_loop", model, T, clip_denoised, model_kwargs)
+        if noise is not None:
+            noise = noise.float().contiguous()
+        return rt.diff_calc_bpd(rt.diff_schedule(self.timestep_map), x_start.float().contiguous(), emb, noise=noise, seed=seed,
+                                sample_ids=sample_ids, rows_per_pass=rows_per_pass)
 
     # ---------------------------------------------------------------------------------------------------- sampling loops
     def _check(self, sampler):

@@ -345,6 +345,41 @@ int dtts_diff_training_losses(dtts_handle* h, int id, const float* x_start, cons
  * fixed-order reduction as dtts_diff_loss_terms. */
 int dtts_l1_mean(dtts_handle* h, const float* a, const float* b, int B, int C, int T, float* out, void* stream);
 
+/* ---- the diffusion decoder's variational bound in bits per dimension (GaussianDiffusion.calc_bpd_loop, vqvae/utils/diffusion.py:1114-1169)
+ * The likelihood figure of the UNGUIDED model: one conditional trunk forward per (utterance, timestep), no unconditional rows.  The same
+ * contract as the evaluation losses above: eval() semantics, fp32, no atomics, fixed-order sums (two calls give the same bits, a row's
+ * values do not depend on the rows evaluated with it), means over every utterance's whole [128, T] rectangle, 16-byte aligned buffers,
+ * integer arguments checked on the host before any launch, asynchronous on `stream`, allocation outside the launch path only.
+ *
+ * The per-timestep terms on a given model output.  model_out DEVICE [R,256,T] (eps | var); x_start, x_t, noise DEVICE [R,128,T]; t HOST
+ * [R].  terms_out DEVICE [R][3] = (vb, xstart_mse, mse) per row: vb = _vb_terms_bpd's output (:903-928) exactly as dtts_diff_loss_terms
+ * computes it; xstart_mse = mean (pred_xstart - x_start)^2 with pred_xstart = clamp(_predict_xstart_from_eps, -1, 1), p_mean_variance's
+ * clip_denoised start (:357-375, 1153); mse = mean (eps' - noise)^2 with eps' = _predict_eps_from_xstart of that CLAMPED start
+ * (:402-405, 1154-1155), not the model's eps.  pred_xstart (may be NULL) DEVICE [R,128,T] receives the clamped start. */
+int dtts_diff_bpd_terms(dtts_handle* h, int id, const float* model_out, const float* x_start, const float* x_t, const float* noise, const int* t,
+                        int R, int T, float* terms_out, float* pred_xstart, void* stream);
+
+/* _prior_bpd (vqvae/utils/diffusion.py:1098-1112): prior_out DEVICE [B] = mean normal_kl(sqrt_alphas_cumprod[S-1] x_start,
+ * log_one_minus_alphas_cumprod[S-1], 0, 0) / ln 2 (q_mean_variance :230-241, normal_kl :17-35) on the last step of schedule `id`. */
+int dtts_diff_prior_bpd(dtts_handle* h, int id, const float* x_start, int B, int T, float* prior_out, void* stream);
+
+/* calc_bpd_loop (vqvae/utils/diffusion.py:1114-1169) on the S steps of integer-timestep schedule `id`: for every t, q_sample of x_start
+ * (:1140-1141), the trunk's forward, the three terms above; then the prior and total = sum_t vb + prior (:1161-1162).
+ * x_start DEVICE [B,128,T] (normalised mel), code_emb DEVICE [B,768,T] (dtts_diff_timestep_independent), lens HOST [B] or NULL (reaches the
+ * trunk's forward only).  vb, xstart_mse, mse DEVICE [B][S]: column j is timestep S - 1 - j, as the reference stacks them (:1138, 1157-1159);
+ * prior, total DEVICE [B].  noise DEVICE [S][B][128][T] INDEXED BY TIMESTEP (noise[t] is what the loop uses at timestep t, whatever the
+ * order it was drawn in), a test hook; NULL: drawn from the Philox spec on noise stage 7 (step t, stream sample_ids[b] HOST, element order
+ * [128, T]; no other site draws from this stage), so an utterance's noise at a timestep depends neither on the batch nor on the grouping
+ * below.  The B S (utterance, timestep) pairs run rows_per_pass at a time (0: the library's choice, about 32) as rows of the
+ * dtts_diff_forward_rows launch sequence, every row at its own timestep; the workspace is that of ONE pass, never of B S rows, and the
+ * results are the same bits for every rows_per_pass: for the duration of the call the trunk's launches make no choice by the number of
+ * rows they cover (no split-K in the convs, no key split in the attention - elsewhere, dtts_diff_forward_rows included, those rules
+ * stand).  Refused with trunk_fp16 = 1, like dtts_diff_training_losses, and with conv_x3 = 0 (the exact fp32 convs pick their tile,
+ * and with it a row's summation order, by the launch size). */
+int dtts_diff_calc_bpd(dtts_handle* h, int id, const float* x_start, const float* code_emb, const int* lens, int B, int T, const float* noise,
+                       unsigned long long seed, const int* sample_ids, int rows_per_pass, float* vb, float* xstart_mse, float* mse, float* prior,
+                       float* total, void* stream);
+
 /* ---- stage C: flow-VAE front + HiFiGAN generator -------------------------------------------------- */
 
 /* SynthesizerTrn.infer_flowvae (vqvae/model_24k.py:848-863): ref_enc -> in_proj -> enc_p -> z_p -> flow^-1 -> dec.
