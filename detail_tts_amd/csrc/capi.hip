@@ -652,6 +652,22 @@ int dtts_op_attention_x3(dtts_handle* h, const char* name, const float* x, const
     DTTS_API_END(h)
 }
 
+int dtts_op_attention(dtts_handle* h, const float* qkv, const int* lens, int B, int rows, int cs, int T, int H, int D, int q_off,
+                      int k_off, int v_off, int head_stride, float scale, const float* bias_tab, int causal, const float* band,
+                      int band_w, float* y, float* ml, void* stream) {
+    DTTS_API_BEGIN
+    h->m->op_attention(qkv, lens, B, rows, cs, T, H, D, q_off, k_off, v_off, head_stride, scale, bias_tab, causal, band, band_w, y, ml,
+                       (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_op_attention_rel(dtts_handle* h, const float* qkv, const int* lens, int B, int T, int H, int D, const float* ek,
+                          const float* ev, int window, float scale, float* y, float* relk, float* ml, void* stream) {
+    DTTS_API_BEGIN
+    h->m->op_attention_rel(qkv, lens, B, T, H, D, ek, ev, window, scale, y, relk, ml, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
 int dtts_op_philox_normal(dtts_handle* h, float* out, int n, int B, unsigned long long seed, const int* sample_ids, int stage,
                           int step, void* stream) {
     DTTS_API_BEGIN

@@ -356,6 +356,15 @@ public:
     // flash_attn_x3b on them -> y (the proj conv's input planes, or fp32 rows with out_f32); img_out (may be null): a copy of the images.
     void op_attention_x3(const char* name, const float* x, const int* lens_host, int B, int Cin, int T, int H, const float* bias_tab, int p1,
                          int out_f32, void* y, void* img_out, ConvX3Launch* conv_chosen, AttnX3Launch* attn_chosen, hipStream_t s);
+    // ONE launch_flash_attention (flash_attn_kernel<D, MODE> of attention.hip) on the caller's fp32 rows qkv [B, rows, cs >= T] ->
+    // y [B, H D, T] (+ ml [B, H, T, 2] unless null), columns < len only; at most one of bias_tab [H, 129], causal, band [B, H, T, 2 W + 1].
+    void op_attention(const float* qkv, const int* lens_host, int B, int rows, int cs, int T, int H, int D, int q_off, int k_off, int v_off,
+                      int head_stride, float scale, const float* bias_tab, int causal, const float* band, int band_w, float* y, float* ml,
+                      hipStream_t s);
+    // enc_p's windowed relative-position attention alone, with enc_p_fwd's strides: rel_key -> band-mode flash kernel (ml_out) ->
+    // rel_value on qkv [B, 3 H D, T] (blocks [Q | K | V]), ek / ev [2 W + 1, D] -> y [B, H D, T], relk [B, H, T, 2 W + 1], ml [B, H, T, 2].
+    void op_attention_rel(const float* qkv, const int* lens_host, int B, int T, int H, int D, const float* ek, const float* ev, int W,
+                          float scale, float* y, float* relk, float* ml, hipStream_t s);
     void op_philox_normal(float* out, int n, int B, unsigned long long seed, const int* sample_ids_host, int stage, int step,
                           hipStream_t s);
 

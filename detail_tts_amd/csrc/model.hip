@@ -495,6 +495,109 @@ void Model::op_attention_x3(const char* name, const float* x, const int* lens_ho
     launch_flash_attention(a, s, attn_chosen);
 }
 
+// What both fp32 attention unit entries check before anything is launched or uploaded; fills l[b] (null lens -> T).
+static void attn_f32_args(const char* who, const int* lens_host, int B, int rows, int cs, int T, int H, int D, int q_off, int k_off,
+                          int v_off, int head_stride, std::vector<int>& l) {
+    const std::string w(who);
+    DTTS_REQUIRE(B > 0 && B <= 65535 && T > 0 && T <= (1 << 16) && H > 0 && H <= 64 && rows > 0 && rows <= (1 << 16), (w + ": sizes").c_str());
+    DTTS_REQUIRE(D == 48 || D == 64 || D == 96 || D == 192, (w + ": head dim outside the launcher's set (48, 64, 96, 192)").c_str());
+    DTTS_REQUIRE(cs >= T && cs <= (1 << 17), (w + ": the row stride must be at least T").c_str());
+    DTTS_REQUIRE(head_stride >= 0 && head_stride <= rows, (w + ": head stride").c_str());
+    const int offs[3] = {q_off, k_off, v_off};
+    for (int off : offs)
+        DTTS_REQUIRE(off >= 0 && (long long)off + (long long)(H - 1) * head_stride + D <= rows, (w + ": q / k / v rows leave the tensor").c_str());
+    DTTS_REQUIRE((long long)cdiv(T, 128) * H * B <= (1 << 22), (w + ": launch too large").c_str());
+    l.resize(B);
+    for (int b = 0; b < B; ++b) {
+        l[b] = lens_host ? lens_host[b] : T;
+        DTTS_REQUIRE(l[b] >= 0 && l[b] <= T, (w + ": lengths must lie in [0, T]").c_str());
+    }
+}
+
+// ONE launch_flash_attention on the caller's fp32 rows, for parity tests (tests/test_gpu_attn_f32.py): flash_attn_kernel<D, MODE> of
+// csrc/attention.hip with D in {48, 64, 96, 192} and MODE plain / T5 bias table / causal / VITS rel-key band, exactly as the four
+// production call sites drive it (GPT prefill, enc_p, MelStyleEncoder, the trunk under conv_x3 = 0).  qkv DEVICE [B][rows][cs], cs >= T
+// (the trunk's Ta); row of (head h, dim c) = off + h * head_stride + c.  y DEVICE [B][H D][T] and ml DEVICE [B][H][T][2] (may be null)
+// are the caller's, written at columns t < len only.  bias_tab DEVICE [H][129], band DEVICE [B][H][T][2 band_w + 1]; at most one of
+// bias_tab, causal, band (the launcher has no kernel for a combination).  A sample of length 0 is legal: its workgroups return at once.
+// Everything is checked before the first launch or upload.  No kernel and no production launch changes for this.
+void Model::op_attention(const float* qkv, const int* lens_host, int B, int rows, int cs, int T, int H, int D, int q_off, int k_off,
+                         int v_off, int head_stride, float scale, const float* bias_tab, int causal, const float* band, int band_w,
+                         float* y, float* ml, hipStream_t s) {
+    DTTS_REQUIRE(qkv && y, "op_attention: null argument");
+    std::vector<int> l;
+    attn_f32_args("op_attention", lens_host, B, rows, cs, T, H, D, q_off, k_off, v_off, head_stride, l);
+    DTTS_REQUIRE(causal == 0 || causal == 1, "op_attention: causal is 0 or 1");
+    DTTS_REQUIRE((bias_tab ? 1 : 0) + causal + (band ? 1 : 0) <= 1, "op_attention: at most one of bias table, causal and band");
+    DTTS_REQUIRE(band ? (band_w >= 0 && 2 * band_w + 1 <= 16) : band_w == 0, "op_attention: band window (2 W + 1 <= 16; 0 without a band)");
+    DTTS_REQUIRE(std::isfinite(scale), "op_attention: scale");
+    // ---- nothing has been launched or uploaded up to here
+    AttnParams a;
+    a.qkv = qkv;
+    a.bs = (long long)rows * cs;
+    a.cs = cs;
+    a.q_off = q_off;
+    a.k_off = k_off;
+    a.v_off = v_off;
+    a.head_stride = head_stride;
+    a.out = y;
+    a.o_bs = (long long)H * D * T;
+    a.o_cs = T;
+    a.lens = upload_ints(l.data(), B, s);
+    a.T = T;
+    a.B = B;
+    a.H = H;
+    a.D = D;
+    a.scale = scale;
+    a.bias_tab = bias_tab;
+    a.causal = causal;
+    a.band = band;
+    a.band_w = band_w;
+    a.ml_out = ml;
+    launch_flash_attention(a, s);
+}
+
+// The windowed relative-position attention of enc_p alone (vqvae/modules/attentions.py:161-303 MultiHeadAttention.attention, minus the
+// convs): launch_vits_rel_key -> the band-mode flash kernel with ml_out -> launch_vits_rel_value, with the strides, offsets and buffers
+// of Model::enc_p_fwd: qkv DEVICE [B][3 H D][T] as blocks [Q | K | V] of all heads (q_off 0, k_off H D, v_off 2 H D, head stride D,
+// row stride T), ek / ev DEVICE [2 W + 1][D] (emb_rel_k / emb_rel_v, already sliced to the window), scale multiplies q . k and q . ek.
+// y DEVICE [B][H D][T], relk DEVICE [B][H][T][2 W + 1] and ml DEVICE [B][H][T][2] are the caller's, written at t < len only.
+void Model::op_attention_rel(const float* qkv, const int* lens_host, int B, int T, int H, int D, const float* ek, const float* ev, int W,
+                             float scale, float* y, float* relk, float* ml, hipStream_t s) {
+    DTTS_REQUIRE(qkv && ek && ev && y && relk && ml, "op_attention_rel: null argument");
+    DTTS_REQUIRE(H > 0 && H <= 64 && (D == 48 || D == 64 || D == 96 || D == 192), "op_attention_rel: heads / head dim outside the launcher's set (48, 64, 96, 192)");
+    const int hid = H * D;
+    std::vector<int> l;
+    attn_f32_args("op_attention_rel", lens_host, B, 3 * hid, T, T, H, D, 0, hid, 2 * hid, D, l);
+    DTTS_REQUIRE(W >= 1 && 2 * W + 1 <= 16, "op_attention_rel: window (1 <= W, 2 W + 1 <= 16)");
+    DTTS_REQUIRE(std::isfinite(scale), "op_attention_rel: scale");
+    // ---- nothing has been launched or uploaded up to here
+    const int* dl = upload_ints(l.data(), B, s);
+    launch_vits_rel_key(qkv, (long long)3 * hid * T, T, 0, D, ek, relk, dl, B, H, D, T, W, scale, s);
+    AttnParams at;
+    at.qkv = qkv;
+    at.bs = (long long)3 * hid * T;
+    at.cs = T;
+    at.q_off = 0;
+    at.k_off = hid;
+    at.v_off = 2 * hid;
+    at.head_stride = D;
+    at.out = y;
+    at.o_bs = (long long)hid * T;
+    at.o_cs = T;
+    at.lens = dl;
+    at.T = T;
+    at.B = B;
+    at.H = H;
+    at.D = D;
+    at.scale = scale;
+    at.band = relk;
+    at.band_w = W;
+    at.ml_out = ml;
+    launch_flash_attention(at, s);
+    launch_vits_rel_value(qkv, (long long)3 * hid * T, T, 0, hid, D, relk, ml, ev, y, (long long)hid * T, T, dl, B, H, D, T, W, scale, s);
+}
+
 void Model::op_philox_normal(float* out, int n, int B, unsigned long long seed, const int* sample_ids_host, int stage, int step,
                              hipStream_t s) {
     const int* sids = upload_ints(sample_ids_host, B, s);

@@ -1070,6 +1070,69 @@ class Runtime:
         out.update(attn_ksplit=int(info.attn_ksplit), attn_p1=int(info.attn_p1), attn_workgroups=int(info.attn_workgroups))
         return y, image[:nimg], out, guard
 
+    def _nan_with_guard(self, B, *shape):
+        """-> (y [B, *shape], guard [*shape]): one NaN-filled allocation, the guard slab directly behind the batch"""
+        buf = torch.full((B + 1,) + tuple(shape), float("nan"), device=self.device, dtype=torch.float32)
+        return buf[:B], buf[B]
+
+    def op_attention(self, qkv, heads, dim, q_off, k_off, v_off, head_stride, scale, lens=None, bias_tab=None, causal=False, band=None,
+                     band_w=0, want_ml=False, T=None):
+        """ONE launch of the exact-fp32 flash attention (csrc/attention.hip, flash_attn_kernel<dim, mode>) on the caller's rows
+        qkv [B, rows, cs]: row of (head h, channel c) = off + h * head_stride + c, cs the allocated row stride, T <= cs the logical
+        length (default cs; the trunk calls the kernel with cs = Ta > T) -> (y, ml, guard).
+        y[b, h dim + c, t] = sum_{s < len} softmax_s(scale q_t . k_s + extra) v[c, s] with extra = bias_tab[h, clamp(s - t, -64, 64) + 64]
+        (bias_tab [heads, 129]), or -inf at s > t (causal), or band[b, h, t, s - t + band_w] inside |s - t| <= band_w (band
+        [B, heads, T, 2 band_w + 1]); at most one of the three.  y [B, heads * dim, T] is handed over filled with NaN: the kernel
+        leaves columns >= len untouched.  guard: one more sample-sized NaN slab directly behind y in the same allocation.  ml
+        [B, heads, T, 2] (want_ml; else None), NaN-filled: (m, l) with m + log(l) the row's log-sum-exp.  Whatever the launcher cannot
+        take - a head dim outside 48 / 64 / 96 / 192, rows that leave the tensor, a length outside [0, T], wrong bias_tab / band
+        shapes, two modes at once - raises DttsError before anything is launched; a sample of length 0 is legal."""
+        _check(qkv, "qkv"); _check(bias_tab, "bias_tab"); _check(band, "band")
+        if qkv.dim() != 3:
+            raise DttsError("op_attention: qkv must be [B, rows, cs]")
+        B, rows, cs = qkv.shape
+        T = cs if T is None else int(T)
+        heads, dim, band_w = int(heads), int(dim), int(band_w)
+        li = _ints(lens)
+        if li is not None and li[1].size != B:
+            raise DttsError("op_attention: one length per sample")
+        if bias_tab is not None and tuple(bias_tab.shape) != (heads, 129):
+            raise DttsError("op_attention: bias_tab must be [heads, 129]")
+        if band is not None and (band_w < 0 or tuple(band.shape) != (B, heads, T, 2 * band_w + 1)):
+            raise DttsError("op_attention: band must be [B, heads, T, 2 * band_w + 1]")
+        if min(B, heads, dim, T) < 1:
+            raise DttsError("op_attention: empty attention")
+        y, guard = self._nan_with_guard(B, heads * dim, T)
+        ml = torch.full((B, heads, T, 2), float("nan"), device=self.device, dtype=torch.float32) if want_ml else None
+        self._rc(self.lib.dtts_op_attention(self.h, _ptr(qkv), li[0] if li else None, B, rows, cs, T, heads, dim, int(q_off), int(k_off),
+                                            int(v_off), int(head_stride), float(scale), _ptr(bias_tab), int(bool(causal)), _ptr(band), band_w,
+                                            _ptr(y), _ptr(ml), self._stream()))
+        return y, ml, guard
+
+    def op_attention_rel(self, qkv, heads, dim, ek, ev, window, scale, lens=None, want_ml=False):
+        """enc_p's windowed relative-position attention alone (vqvae/modules/attentions.py MultiHeadAttention.attention, minus the
+        convs), launched as Model::enc_p_fwd launches it: vits_rel_key_kernel -> the band-mode flash kernel with ml_out ->
+        vits_rel_value_kernel.  qkv [B, 3 heads dim, T] in blocks [Q | K | V] of all heads, ek / ev [2 window + 1, dim] (emb_rel_k /
+        emb_rel_v sliced to the window) -> (y, relk, guard) (with want_ml: (y, relk, guard, ml)).  y [B, heads * dim, T] and relk
+        [B, heads, T, 2 window + 1] (= scale q_t . ek[r]) are handed over filled with NaN and written at t < len only; guard: one more
+        sample-sized NaN slab directly behind y in the same allocation."""
+        _check(qkv, "qkv"); _check(ek, "ek"); _check(ev, "ev")
+        heads, dim, window = int(heads), int(dim), int(window)
+        if qkv.dim() != 3 or min(heads, dim) < 1 or qkv.shape[1] != 3 * heads * dim or min(qkv.shape) < 1:
+            raise DttsError("op_attention_rel: qkv must be [B, 3 * heads * dim, T]")
+        B, _, T = qkv.shape
+        li = _ints(lens)
+        if li is not None and li[1].size != B:
+            raise DttsError("op_attention_rel: one length per sample")
+        if window < 1 or tuple(ek.shape) != (2 * window + 1, dim) or tuple(ev.shape) != (2 * window + 1, dim):
+            raise DttsError("op_attention_rel: ek and ev must be [2 * window + 1, dim]")
+        y, guard = self._nan_with_guard(B, heads * dim, T)
+        relk = torch.full((B, heads, T, 2 * window + 1), float("nan"), device=self.device, dtype=torch.float32)
+        ml = torch.full((B, heads, T, 2), float("nan"), device=self.device, dtype=torch.float32)
+        self._rc(self.lib.dtts_op_attention_rel(self.h, _ptr(qkv), li[0] if li else None, B, T, heads, dim, _ptr(ek), _ptr(ev), window,
+                                                float(scale), _ptr(y), _ptr(relk), _ptr(ml), self._stream()))
+        return (y, relk, guard, ml) if want_ml else (y, relk, guard)
+
     def diff_p_sample(self, x, code_emb, step, seed, sample_ids, lens=None, noise=None, return_x0=False):
         """one GaussianDiffusion.p_sample at sampling step `step` (49 = first): returns the new x (and pred_xstart)"""
         _check(x, "x"); _check(code_emb, "code_emb"); _check(noise, "noise")

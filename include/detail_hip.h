@@ -703,6 +703,25 @@ typedef struct dtts_attn_x3_info {
 size_t dtts_attn_x3_image_bytes(int B, int H, int T);
 int dtts_op_attention_x3(dtts_handle* h, const char* name, const float* x, const int* lens, int B, int Cin, int T, int H,
                          const float* bias_tab, int p1, int out_f32, void* y, void* img_out, dtts_attn_x3_info* info, void* stream);
+/* ONE launch of the exact-fp32 flash attention (csrc/attention.hip, flash_attn_kernel<D, MODE>) on the caller's rows - the kernel
+ * behind the GPT prefill (causal), enc_p (band), the MelStyleEncoders (plain) and the trunk under conv_x3 = 0 (bias table):
+ *   y[b, h D + c, t] = sum_{s < len_b} softmax_s(scale q_t . k_s + extra(h, t, s)) v[c, s],   t < len_b
+ * qkv DEVICE [B][rows][cs], cs >= T the allocated row stride; row of (head h, dim c) = {q,k,v}_off + h * head_stride + c, which must
+ * stay inside [0, rows).  D in {48, 64, 96, 192}.  lens HOST in [0, T] (null -> T); a sample of length 0 is legal and untouched.
+ * extra: bias_tab DEVICE [H][129] -> bias_tab[h][clamp(s - t, -64, 64) + 64]; causal = 1 -> keys s > t are masked; band DEVICE
+ * [B][H][T][2 band_w + 1] -> band[b][h][t][s - t + band_w] where |s - t| <= band_w (2 band_w + 1 <= 16).  At most one of the three.
+ * y DEVICE [B][H D][T] and ml DEVICE [B][H][T][2] (may be null; (m, l) with m + log(l) = the row's log-sum-exp) are written at
+ * columns t < len only; columns >= len of qkv and band are never read.  Anything else is refused before a launch. */
+int dtts_op_attention(dtts_handle* h, const float* qkv, const int* lens, int B, int rows, int cs, int T, int H, int D, int q_off,
+                      int k_off, int v_off, int head_stride, float scale, const float* bias_tab, int causal, const float* band,
+                      int band_w, float* y, float* ml, void* stream);
+/* enc_p's windowed relative-position attention alone (vqvae/modules/attentions.py MultiHeadAttention.attention with window_size =
+ * window, minus the convs), as Model::enc_p_fwd launches it: relk[b][h][t][r] = scale q_t . ek[r], the band-mode flash kernel with ml,
+ * then y[b, h D + c, t] += sum_r p(t, t + r - window) ev[r][c].  qkv DEVICE [B][3 H D][T] in blocks [Q | K | V] of all heads,
+ * ek / ev DEVICE [2 window + 1][D] (the reference's emb_rel_k / emb_rel_v sliced to the window), 1 <= window, 2 window + 1 <= 16.
+ * y DEVICE [B][H D][T], relk DEVICE [B][H][T][2 window + 1], ml DEVICE [B][H][T][2]: written at t < len only. */
+int dtts_op_attention_rel(dtts_handle* h, const float* qkv, const int* lens, int B, int T, int H, int D, const float* ek,
+                          const float* ev, int window, float scale, float* y, float* relk, float* ml, void* stream);
 /* The device sampler on given logits rows: HF RepetitionPenalty / Temperature / TopK / TopP processors as the reference's
  * generate() applies them (vqvae/model_24k.py:786-792) + the inverse-CDF draw on uniforms[r].  logits DEVICE [R][V] (R <= 16),
  * history HOST [R][hist_len] ids present in the row's input_ids, uniforms DEVICE [R] -> tokens HOST [R].  Synchronises. */
