@@ -1,0 +1,203 @@
+"""The request pipeline under SynthesizerTrn.infer / infer_stream / infer_gpt (vqvae/model_24k.py), every stage written once.
+
+Host bookkeeping (normalize_request, group_requests, merge_session, split_session: pure functions on lists and arrays, no device,
+no library) and the stages' launch sequences (drain_session, stage_b, stage_c, stream_stage_a), which take the runtime / model they
+launch on.  Nothing here synchronises beyond what a decode session's results need (gpt_finish, on stage A's stream)."""
+from __future__ import annotations
+
+import itertools
+import time
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+SESSION_ROWS = 16       # utterances one decode session holds
+PAIR_ROWS = 8           # ... and the most a request may have to share one with its neighbour (infer_stream(pair_stage_a=True))
+
+
+@dataclass
+class Request:
+    """one request batch: what the caller gave, normalised (host values; `refer` as given until stage A moves it to the device),
+    then what stage A leaves for stages B and C"""
+    B: int
+    rl: list
+    seed: int
+    sids: list
+    texts: list
+    refer: object
+    forced: object = None
+    lat: object = None          # stage A: latents [B,768,max(n)], code counts n, the event stage B waits on
+    n: list = None
+    a_done: object = None
+    tr: dict = None             # this request's entry of SynthesizerTrn.stream_trace
+
+
+def normalize_request(text, text_length, refer, refer_lengths, seed=None, sample_ids=None, forced_codes=None, *, batch=True):
+    """the arguments of infer() / one request dict of infer_stream() -> Request: B, integer rl, a drawn seed when none is given,
+    default sample ids range(B), per-row int32 text arrays cut at their own lengths.  batch=False keeps the first row only (the
+    reference: text = text[0].unsqueeze(0) ..., vqvae/model_24k.py:775-778).  No device transfer: refer stays where it is."""
+    text = torch.as_tensor(text)
+    refer = torch.as_tensor(refer)
+    tl = torch.as_tensor(text_length).reshape(-1).tolist()
+    rl = [int(v) for v in torch.as_tensor(refer_lengths).reshape(-1).tolist()]
+    if not batch:
+        text, refer, tl, rl = text[:1], refer[:1], tl[:1], rl[:1]
+        if forced_codes is not None:
+            forced_codes = forced_codes[:1]
+    B = text.shape[0]
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    sids = list(range(B)) if sample_ids is None else list(sample_ids)
+    texts = [text[b, : int(tl[b])].cpu().numpy().astype(np.int32) for b in range(B)]
+    return Request(B=B, rl=rl, seed=seed, sids=sids, texts=texts, refer=refer, forced=forced_codes)
+
+
+def group_requests(requests, pair=False):
+    """requests -> stage-A groups (lists of one or two request dicts), reading at most two requests ahead of the group it yields.
+    With `pair`, two consecutive requests of <= 8 utterances each share one decode session; every other request is alone."""
+    it, held = iter(requests), []
+    while True:
+        held += itertools.islice(it, 2 - len(held))
+        if not held:
+            return
+        nrows = [torch.as_tensor(r["text"]).shape[0] for r in held]
+        take = 2 if pair and len(held) == 2 and nrows[0] <= PAIR_ROWS and nrows[1] <= PAIR_ROWS else 1
+        yield [held.pop(0) for _ in range(take)]
+
+
+def merge_session(sts):
+    """the Requests of one decode session -> (rl, texts, sample ids, seeds, forced codes), rows concatenated in order; seeds is the
+    request's own seed for one request, else one seed per row"""
+    seeds = sts[0].seed if len(sts) == 1 else [st.seed for st in sts for _ in range(st.B)]
+    forced = None
+    if any(st.forced is not None for st in sts):
+        assert all(st.forced is not None for st in sts), "forced_codes: all requests of a shared session or none"
+        forced = [c for st in sts for c in st.forced]
+    return [v for st in sts for v in st.rl], [t for st in sts for t in st.texts], [v for st in sts for v in st.sids], seeds, forced
+
+
+def split_session(ncodes, sizes):
+    """a session's code counts (stop token included) -> per request of `sizes` rows its n = ncodes - 1 (codes = codes[:, :-1],
+    vqvae/model_24k.py:795)"""
+    out, r0 = [], 0
+    for B in sizes:
+        n = [int(c) - 1 for c in ncodes[r0:r0 + B]]
+        if min(n) < 1:
+            raise ValueError("an utterance produced no mel codes (stop token first)")
+        out.append(n)
+        r0 += B
+    return out
+
+
+def merge_refer(sts, dev):
+    """the session's prompt batch: one request's own, or one zero-padded batch (every kernel takes the per-row length)"""
+    if len(sts) == 1:
+        return sts[0].refer
+    refer = torch.zeros((sum(st.B for st in sts), sts[0].refer.shape[1], max(st.refer.shape[2] for st in sts)), device=dev, dtype=torch.float32)
+    r0 = 0
+    for st in sts:
+        refer[r0:r0 + st.B, :, : st.refer.shape[2]] = st.refer
+        r0 += st.B
+    return refer
+
+
+def split_latents(lat, sts, ns):
+    """each request's rows of the session's decode-time latents (== the return_latent pass), cut at its longest utterance"""
+    r0 = 0
+    for st, n in zip(sts, ns):
+        st.lat, st.n = lat[r0:r0 + st.B, :, : max(n)].contiguous(), n
+        r0 += st.B
+
+
+def drain_session(rt, max_generate_length, suppress_eos):
+    """the decode session after its prefill: 16-token chunks, finish flags polled per chunk -> gpt_finish()'s (codes, ncodes, latents)"""
+    while rt.gpt_steps() < max_generate_length:
+        if not suppress_eos and rt.gpt_all_finished():
+            break
+        rt.gpt_decode(16)
+    return rt.gpt_finish()
+
+
+def stage_b(model, st, sampler_id, eta, prec, *, sched=None, sched_ts=None, mark=lambda name: None):
+    """stage B of one request on the current stream (vqvae/model_24k.py:802-804) -> (mel, lens_t).  sched None: the schedule of
+    `sched_ts` is looked up (built on first use) between the embedding and the sampling launches."""
+    rt = model.rt
+    cond = rt.diff_conditioning(st.refer, st.rl)
+    code_emb = rt.diff_timestep_independent(st.lat, cond, st.n)
+    mark("diff_cond")
+    lens_t = [4 * v for v in st.n]
+    if sched is None:
+        sched = rt.sampler_schedule(sched_ts, sampler_id)
+    with model._trunk_precision(prec):
+        mel = rt.diff_sample_ex(code_emb, st.seed, st.sids, sched=sched, sampler=sampler_id, eta=eta, lens=lens_t, denorm=True)
+    return mel, lens_t
+
+
+def stage_c(rt, stream, home, mel, st, lens_t, noise_scale, chunk, *, wait=True, tr=None):
+    """stage C of one request on `stream` (vqvae/model_24k.py:805-809) -> (wav, its completion event, its range-check ticket).
+    `home` is the stream that made `mel` and reads the waveform; wait=False when mel is known complete (a re-run)."""
+    if wait:
+        ready = torch.cuda.Event()
+        ready.record(home)
+        if tr:
+            tr["ev_b1"].record(home)
+    with torch.cuda.stream(stream):
+        if wait:
+            stream.wait_event(ready)
+        wav = rt.vocoder(mel, st.seed, st.sids, lens=lens_t, noise_scale=noise_scale, stream_chunk=int(chunk or 0))
+        ticket = rt.vocoder_ticket()
+        mel.record_stream(stream)
+        done = torch.cuda.Event()
+        done.record(stream)
+        if tr:
+            tr["ev_c1"].record(stream)
+            tr["host_b1"] = time.perf_counter()
+    wav.record_stream(home)
+    return wav, done, ticket
+
+
+def stream_stage_a(rt, sa, group, kw, token_wgs, trace=None):
+    """infer_stream's stage A of one group on stream `sa` -> its Requests, with refer on the device and lat / n / a_done set.
+
+    One request, or TWO requests of <= 8 utterances each as ONE decode session (<= 16 rows, per-row Philox seeds): the 308 MB of GPT
+    weights stream once per token for both, and the chain of ~12 400 dependent launches is paid once.  A request of more than 16
+    rows is decoded session after session (gpt_generate).  `kw`: the sampling arguments; next(token_wgs): a session's token-kernel width."""
+    dev = rt.device
+    sts = [normalize_request(r["text"], r["text_length"], r["refer"], r["refer_lengths"], r.get("seed"), r.get("sample_ids"),
+                             r.get("forced_codes")) for r in group]
+    tr = None
+    if trace is not None:
+        tr = dict(host_a0=time.perf_counter(), ev_a0=torch.cuda.Event(enable_timing=True), ev_a1=torch.cuda.Event(enable_timing=True))
+    with torch.cuda.stream(sa):
+        if tr:
+            tr["ev_a0"].record(sa)
+        for st in sts:
+            st.refer = st.refer.to(dev, torch.float32).contiguous()
+            if tr:
+                st.tr = dict(tr, ev_b0=torch.cuda.Event(enable_timing=True), ev_b1=torch.cuda.Event(enable_timing=True),
+                             ev_c1=torch.cuda.Event(enable_timing=True))
+                trace.append(st.tr)
+        session = sum(st.B for st in sts) <= SESSION_ROWS
+        if session:
+            rl, texts, sids, seeds, forced = merge_session(sts)
+            rt.gpt_prefill(merge_refer(sts, dev), rl, texts, seeds, sids, forced_codes=forced, **kw, token_wgs=next(token_wgs))
+            if kw["suppress_eos"]:                         # fixed length: the whole decode is enqueued without a host round trip
+                rt.gpt_decode(kw["max_generate_length"])
+        else:                                              # more than one decode session: group after group, on this thread / stream
+            st = sts[0]
+            _, ncodes, lat = rt.gpt_generate(st.refer, st.rl, st.texts, st.seed, st.sids, forced_codes=st.forced, **kw)
+        for st in sts:
+            if st.tr:
+                st.tr["host_a1"] = time.perf_counter()
+        if session:
+            _, ncodes, lat = drain_session(rt, kw["max_generate_length"], kw["suppress_eos"])      # waits for stream A only
+        split_latents(lat, sts, split_session(ncodes, [st.B for st in sts]))
+        done = torch.cuda.Event()
+        done.record(sa)
+        for st in sts:
+            st.a_done = done
+            if st.tr:
+                st.tr["ev_a1"].record(sa)
+                st.tr["host_a2"] = time.perf_counter()
+    return sts

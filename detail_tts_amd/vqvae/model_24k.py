@@ -7,6 +7,7 @@ would be alone), the noise seed / per-utterance stream ids, and forced codes (pa
 from __future__ import annotations
 
 import contextlib
+import itertools
 import os
 import time
 from concurrent.futures import ThreadPoolExecutor
@@ -20,6 +21,7 @@ from ..gpt.candidates import check_choose, check_num_candidates, expand_sample_i
 from ..gpt.prompt import check_prompt_args, prompt_rows
 from ..gpt.model import UnifiedVoice
 from .. import _lib as _lib_slots
+from ..pipeline import drain_session, group_requests, normalize_request, split_latents, split_session, stage_b, stage_c, stream_stage_a
 from ..runtime import Runtime
 from .diff_model import DiffusionTts
 from .utils.diffusion import SAMPLERS, SpacedDiffusion, check_timesteps, get_named_beta_schedule, space_timesteps
@@ -351,32 +353,17 @@ class SynthesizerTrn:
         prec = SynthesizerTrn._check_trunk_precision(self, trunk_precision)
         ncand = check_num_candidates(num_candidates, forced_codes)
         check_prompt_args(prompt_codes, forced_codes, ncand)
-        text = torch.as_tensor(text)
-        refer = torch.as_tensor(refer)
-        tl = torch.as_tensor(text_length).reshape(-1).tolist()
-        rl = torch.as_tensor(refer_lengths).reshape(-1).tolist()
-        if not batch:                                             # reference: text = text[0].unsqueeze(0) ... (:775-778)
-            text, refer, tl, rl = text[:1], refer[:1], tl[:1], rl[:1]
-            if forced_codes is not None:
-                forced_codes = forced_codes[:1]
-            if prompt_codes is not None:
-                prompt_codes = prompt_codes[:1]
-        B = text.shape[0]
-        if prompt_codes is not None:
-            prompt_codes = prompt_rows(prompt_codes, B)              # (ValueError on a bad row count or code: before any launch)
+        st = normalize_request(text, text_length, refer, refer_lengths, seed, sample_ids, forced_codes, batch=batch)
+        B, rl, texts, seed, sample_ids, forced_codes = st.B, st.rl, st.texts, st.seed, st.sids, st.forced
+        if prompt_codes is not None:       # (ValueError on a bad row count or code: before any launch)
+            prompt_codes = prompt_rows(prompt_codes if batch else prompt_codes[:1], B)
         choose = check_choose(choose, B, ncand)
         candidates = (ncand > 1 or return_candidates) and forced_codes is None
         if return_candidates and not candidates:
             raise ValueError("return_candidates: forced_codes leave no candidates to report")
-        sample_ids = list(range(B)) if sample_ids is None else list(sample_ids)
         cand_ids = expand_sample_ids(sample_ids, ncand) if candidates else None      # (ValueError on colliding streams: before any launch)
-        refer = refer.to(self.device, torch.float32).contiguous()
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        texts = [text[b, : int(tl[b])].cpu().numpy().astype(np.int32) for b in range(B)]
-        rl = [int(v) for v in rl]
-        ev = []
-        cand = None
+        refer = st.refer = st.refer.to(self.device, torch.float32).contiguous()
+        ev, cand = [], None
 
         def mark(name):
             if self.stage_ms is not None:
@@ -402,11 +389,7 @@ class SynthesizerTrn:
             if session:         # one decode session: prefill (+ first token), then 16-token chunks; finish flags polled per chunk
                 self.rt.gpt_prefill(a_refer, a_rl, a_texts, seed, a_ids, **kw)
                 mark("gpt_prefill")
-                while self.rt.gpt_steps() < max_generate_length:
-                    if not suppress_eos and self.rt.gpt_all_finished():
-                        break
-                    self.rt.gpt_decode(16)
-                codes, ncodes, lat = self.rt.gpt_finish()
+                codes, ncodes, lat = drain_session(self.rt, max_generate_length, suppress_eos)
             else:
                 codes, ncodes, lat = self.rt.gpt_generate(a_refer, a_rl, a_texts, seed, a_ids, **kw)
             if candidates:
@@ -425,45 +408,29 @@ class SynthesizerTrn:
                 ncodes = ncodes[rows]
                 if ncand > 1:                                       # the winners' latent rows, gathered on the device
                     lat = lat.index_select(0, torch.as_tensor(rows, device=self.device))
-            n = [int(c) - 1 for c in ncodes]                       # codes = codes[:, :-1]  (:795)
-            if min(n) < 1:
-                raise ValueError("an utterance produced no mel codes (stop token first)")
+            n, = split_session(ncodes, [B])
             if prompt_codes is None:
-                lat = lat[:, :, : max(n)].contiguous()             # decode-time latents == return_latent pass
+                split_latents(lat, [st], [n])
             else:       # behind a prompt they are not: the reference's return_latent pass sees the generated codes alone (:796-799)
-                lat = self.rt.gpt_latents(refer, rl, texts, [codes[b, : n[b]] for b in range(B)])
+                st.lat, st.n = self.rt.gpt_latents(refer, rl, texts, [codes[b, : n[b]] for b in range(B)]), n
         else:
-            n = [len(c) for c in forced_codes]
-            lat = self.rt.gpt_latents(refer, rl, texts, forced_codes)
+            n = st.n = [len(c) for c in forced_codes]
+            st.lat = self.rt.gpt_latents(refer, rl, texts, forced_codes)
         mark("gpt_decode" if session else "gpt")
         # ---- stage B (:802-804)
-        cond = self.rt.diff_conditioning(refer, rl)
-        code_emb = self.rt.diff_timestep_independent(lat, cond, n)
-        mark("diff_cond")
-        lens_t = [4 * v for v in n]
-        sched = self.rt.sampler_schedule(sched_ts, sampler_id)
-        with self._trunk_precision(prec):
-            mel = self.rt.diff_sample_ex(code_emb, seed, sample_ids, sched=sched, sampler=sampler_id, eta=eta, lens=lens_t, denorm=True)
+        mel, lens_t = stage_b(self, st, sampler_id, eta, prec, sched_ts=sched_ts, mark=mark)
         mark("diff_sample")
         # ---- stage C (:805-809)
         if stream_vocoder:
             cur = torch.cuda.current_stream(self.device)
             if self._voc_stream is None:
                 self._voc_stream = torch.cuda.Stream(self.device)
-            ready = torch.cuda.Event()
-            ready.record(cur)
-            with torch.cuda.stream(self._voc_stream):
-                self._voc_stream.wait_event(ready)
-                wav = self.rt.vocoder(mel, seed, sample_ids, lens=lens_t, noise_scale=noise_scale, stream_chunk=int(vocoder_chunk or 0))
-                mel.record_stream(self._voc_stream)
-                self.vocoder_done = torch.cuda.Event()
-                self.vocoder_done.record(self._voc_stream)
-            wav.record_stream(cur)
+            wav, self.vocoder_done, self.vocoder_ticket = stage_c(self.rt, self._voc_stream, cur, mel, st, lens_t, noise_scale, vocoder_chunk)
             if wait:
                 cur.wait_event(self.vocoder_done)
         else:
             wav = self.rt.vocoder(mel, seed, sample_ids, lens=lens_t, noise_scale=noise_scale)
-        self.vocoder_ticket = self.rt.vocoder_ticket()
+            self.vocoder_ticket = self.rt.vocoder_ticket()
         if wait and check_range and self.rt.vocoder_check_active():      # (check off - DTTS_X3_RANGE_CHECK=0, conv_x3 / voc_x3 = 0: nothing to wait for)
             torch.cuda.current_stream(self.device).synchronize()
             self.rt.vocoder_check(self.vocoder_ticket)
@@ -513,150 +480,37 @@ class SynthesizerTrn:
         cur = torch.cuda.current_stream(dev)
         sched = self.rt.sampler_schedule(sched_ts, sampler_id)      # built here, once: no table allocation inside the pipelined loop
         if self._gpt_stream is None:
-            lo, hi = torch.cuda.Stream.priority_range() if hasattr(torch.cuda.Stream, "priority_range") else (0, -1)
-            self._gpt_stream = torch.cuda.Stream(dev, priority=lo if os.environ.get("DTTS_STAGE_A_PRIORITY") == "low" else hi)
+            hi = torch.cuda.Stream.priority_range()[1] if hasattr(torch.cuda.Stream, "priority_range") else -1
+            self._gpt_stream = torch.cuda.Stream(dev, priority=hi)
         if self._voc_stream is None:
             self._voc_stream = torch.cuda.Stream(dev)
         sa, sc = self._gpt_stream, self._voc_stream
-        # DTTS_SERIAL_VOCODER=1: stage C on stage B's stream, between two requests' diffusions, instead of on a third stream under the
-        # next request's diffusion (measurement knob: under the pipeline the concurrent vocoder costs stage B more than its own 20 ms)
-        serial_c = os.environ.get("DTTS_SERIAL_VOCODER", "0") == "1"
         trace = self.stream_trace          # a list: per-request host times and stream events (tools/pipeline_trace.py)
         kw = dict(max_generate_length=max_generate_length, top_k=top_k, top_p=TOP_P, temperature=TEMPERATURE,
                   repetition_penalty=REPETITION_PENALTY, suppress_eos=suppress_eos)
         # Stage A here decodes NEXT TO the previous request's diffusion: its sessions of 5 .. 8 rows take the 64-workgroup token kernel
         # (gpt_token_n.hip: the same codes and latents bit for bit, 105 instead of 80 ms alone, but half the CUs for 1.3 x as long:
         # -5 .. -7 ms per pipelined request, profiles/r06_token_wgs.txt); a blocking infer() keeps the 128-workgroup kernel.
-        kw_a = dict(kw, token_wgs=int(os.environ.get("DTTS_STREAM_TOKEN_WGS", "64")))
-        # ... except the FIRST group of a stream: nothing runs next to it, so it takes the fastest decode (128 workgroups, 80 ms)
-        a_state = {"first": True}
+        # ... except the FIRST session of a stream: nothing runs next to it, so it takes the fastest decode (0: 128 workgroups, 80 ms)
+        token_wgs = itertools.chain([0], itertools.repeat(int(os.environ.get("DTTS_STREAM_TOKEN_WGS", "64"))))
 
-        def parse(req):
-            text = torch.as_tensor(req["text"])
-            tl = torch.as_tensor(req["text_length"]).reshape(-1).tolist()
-            rl = [int(v) for v in torch.as_tensor(req["refer_lengths"]).reshape(-1).tolist()]
-            B = text.shape[0]
-            seed = req.get("seed")
-            if seed is None:
-                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-            sids = list(range(B)) if req.get("sample_ids") is None else list(req["sample_ids"])
-            texts = [text[b, : int(tl[b])].cpu().numpy().astype(np.int32) for b in range(B)]
-            return dict(B=B, rl=rl, seed=seed, sids=sids, texts=texts, refer_in=req["refer"], forced=req.get("forced_codes"))
-
-        def launch_a(group):
-            """stage A of one request, or of TWO requests of <= 8 utterances each as ONE decode session (<= 16 rows, per-row Philox
-            seeds): the 308 MB of GPT weights stream once per token for both, and the chain of ~12 400 dependent launches is paid once."""
-            sts = [parse(r) for r in group]
-            tr = None
-            if trace is not None:
-                tr = dict(host_a0=time.perf_counter(), ev_a0=torch.cuda.Event(enable_timing=True), ev_a1=torch.cuda.Event(enable_timing=True))
-            with torch.cuda.stream(sa):
-                if tr:
-                    tr["ev_a0"].record(sa)
-                for st in sts:
-                    st["refer"] = torch.as_tensor(st.pop("refer_in")).to(dev, torch.float32).contiguous()
-                    st["gen"] = None
-                    st["tr"] = None
-                    if trace is not None:
-                        st["tr"] = dict(tr, ev_b0=torch.cuda.Event(enable_timing=True), ev_b1=torch.cuda.Event(enable_timing=True),
-                                        ev_c1=torch.cuda.Event(enable_timing=True))
-                        trace.append(st["tr"])
-                rows = sum(st["B"] for st in sts)
-                if rows <= 16:
-                    if len(sts) == 1:
-                        refer, seeds = sts[0]["refer"], sts[0]["seed"]
-                    else:                                      # one padded prompt batch; every kernel takes the per-row length
-                        Tr = max(st["refer"].shape[2] for st in sts)
-                        refer = torch.zeros((rows, sts[0]["refer"].shape[1], Tr), device=dev, dtype=torch.float32)
-                        r0 = 0
-                        for st in sts:
-                            refer[r0:r0 + st["B"], :, : st["refer"].shape[2]] = st["refer"]
-                            r0 += st["B"]
-                        seeds = [st["seed"] for st in sts for _ in range(st["B"])]
-                    forced = None
-                    if any(st["forced"] is not None for st in sts):
-                        assert all(st["forced"] is not None for st in sts), "forced_codes: all requests of a shared session or none"
-                        forced = [c for st in sts for c in st["forced"]]
-                    self.rt.gpt_prefill(refer, [v for st in sts for v in st["rl"]], [t for st in sts for t in st["texts"]], seeds,
-                                        [v for st in sts for v in st["sids"]], forced_codes=forced, **(kw if a_state["first"] else kw_a))
-                    a_state["first"] = False
-                    if suppress_eos:                           # fixed length: the whole decode is enqueued without a host round trip
-                        self.rt.gpt_decode(max_generate_length)
-                else:                                          # more than one decode session: group after group, on this thread / stream
-                    st = sts[0]
-                    st["gen"] = self.rt.gpt_generate(st["refer"], st["rl"], st["texts"], st["seed"], st["sids"], forced_codes=st["forced"], **kw)
-            if tr:
-                for st in sts:
-                    st["tr"]["host_a1"] = time.perf_counter()
-            return sts
-
-        def finish_a(sts):
-            with torch.cuda.stream(sa):
-                if sts[0]["gen"] is not None:
-                    codes, ncodes, lat = sts[0].pop("gen")
-                else:
-                    while self.rt.gpt_steps() < max_generate_length:
-                        if not suppress_eos and self.rt.gpt_all_finished():
-                            break
-                        self.rt.gpt_decode(16)
-                    codes, ncodes, lat = self.rt.gpt_finish()      # waits for stream A only
-                r0 = 0
-                for st in sts:
-                    n = [int(c) - 1 for c in ncodes[r0:r0 + st["B"]]]
-                    if min(n) < 1:
-                        raise ValueError("an utterance produced no mel codes (stop token first)")
-                    st["lat"] = lat[r0:r0 + st["B"], :, : max(n)].contiguous()
-                    st["n"] = n
-                    r0 += st["B"]
-                done = torch.cuda.Event()
-                done.record(sa)
-                for st in sts:
-                    st["a_done"] = done
-                    if st["tr"]:
-                        st["tr"]["ev_a1"].record(sa)
-                        st["tr"]["host_a2"] = time.perf_counter()
-            return sts
-
-        skip_c_state = {}
+        # Stage A is issued from its own host thread: a kernel-launch call blocks once its stream's hardware queue is full, so one
+        # thread could not enqueue request i+1's decode (12 K launches) while it is still feeding request i's diffusion (10 K).  The
+        # library supports exactly this split (include/detail_hip.h, "Threads"); ctypes releases the GIL inside the calls.
+        def stage_a(group):
+            torch.cuda.set_device(dev)
+            return stream_stage_a(self.rt, sa, group, kw, token_wgs, trace)
 
         def launch_bc(st):
-            cur.wait_event(st["a_done"])
-            refer, lat, n = st["refer"], st["lat"], st["n"]
-            refer.record_stream(cur)
-            lat.record_stream(cur)
-            tr = st["tr"]
-            if tr:
-                tr["host_b0"] = time.perf_counter()
-                tr["ev_b0"].record(cur)
-            cond = self.rt.diff_conditioning(refer, st["rl"])
-            code_emb = self.rt.diff_timestep_independent(lat, cond, n)
-            lens_t = [4 * v for v in n]
-            with self._trunk_precision(prec):
-                mel = self.rt.diff_sample_ex(code_emb, st["seed"], st["sids"], sched=sched, sampler=sampler_id, eta=eta, lens=lens_t, denorm=True)
-            ready = torch.cuda.Event()
-            ready.record(cur)
-            if tr:
-                tr["ev_b1"].record(cur)
-            with torch.cuda.stream(cur if serial_c else sc):
-                if not serial_c:
-                    sc.wait_event(ready)
-                # DTTS_EXPERIMENT_SKIP_C=1 (measurement only, results are NOT valid synthesis): every request after the first hands out the
-                # first request's waveform instead of running stage C - what stage C costs the step (profiles/r06_stage_c_floor.txt)
-                skip_c = os.environ.get("DTTS_EXPERIMENT_SKIP_C") == "1" and skip_c_state.get("wav") is not None and skip_c_state["n"] == n
-                if skip_c:
-                    wav, ticket = skip_c_state["wav"], skip_c_state["ticket"]
-                else:
-                    wav = self.rt.vocoder(mel, st["seed"], st["sids"], lens=lens_t, noise_scale=noise_scale, stream_chunk=int(vocoder_chunk or 0))
-                    ticket = self.vocoder_ticket = self.rt.vocoder_ticket()
-                    skip_c_state.update(wav=wav, ticket=ticket, n=list(n))
-                mel.record_stream(cur if serial_c else sc)
-                self.vocoder_done = torch.cuda.Event()
-                self.vocoder_done.record(cur if serial_c else sc)
-                if tr:
-                    tr["ev_c1"].record(cur if serial_c else sc)
-                    tr["host_b1"] = time.perf_counter()
-            wav.record_stream(cur)
-            return wav, [1024 * v for v in n], self.vocoder_done, ticket, (mel, st["seed"], st["sids"], lens_t)
+            cur.wait_event(st.a_done)
+            st.refer.record_stream(cur)
+            st.lat.record_stream(cur)
+            if st.tr:
+                st.tr["host_b0"] = time.perf_counter()
+                st.tr["ev_b0"].record(cur)
+            mel, lens_t = stage_b(self, st, sampler_id, eta, prec, sched=sched)
+            wav, self.vocoder_done, self.vocoder_ticket = stage_c(self.rt, sc, cur, mel, st, lens_t, noise_scale, vocoder_chunk, tr=st.tr)
+            return wav, [1024 * v for v in st.n], self.vocoder_done, self.vocoder_ticket, (mel, st, lens_t)
 
         def hand_out(out):
             """wait for this request's waveform; a saturated stage C is re-run on the exact fp32 kernels (this thread issues every stage-C
@@ -667,67 +521,21 @@ class SynthesizerTrn:
             except Exception:
                 if on_saturation == "raise":
                     raise
-                mel, seed, sids, lens_t = out[4]
                 self.saturated_requests += 1
                 self.rt.set_option("voc_x3", 0)
                 try:
-                    with torch.cuda.stream(cur if serial_c else sc):
-                        wav = self.rt.vocoder(mel, seed, sids, lens=lens_t, noise_scale=noise_scale, stream_chunk=int(vocoder_chunk or 0))
-                        redo = torch.cuda.Event()
-                        redo.record(cur if serial_c else sc)
+                    wav, redo, _ = stage_c(self.rt, sc, cur, *out[4], noise_scale, vocoder_chunk, wait=False)
                 finally:
                     self.rt.set_option("voc_x3", 1)
-                wav.record_stream(cur)
                 redo.synchronize()
                 return wav, out[1]
             return out[0], out[1]
 
-        # Stage A is issued from its own host thread: a kernel-launch call blocks once its stream's hardware queue is full, so one
-        # thread could not enqueue request i+1's decode (12 K launches) while it is still feeding request i's diffusion (10 K).  The
-        # library supports exactly this split (include/detail_hip.h, "Threads"); ctypes releases the GIL inside the calls.
-        skip_state = {"i": 0, "last": None}
-
-        def stage_a(group):
-            torch.cuda.set_device(dev)
-            # DTTS_EXPERIMENT_SKIP_A=1 (measurement only, results are NOT valid synthesis): every second request reuses the previous
-            # request's codes / latents instead of running stage A - an upper bound on what halving stage A's work could give stage B
-            if os.environ.get("DTTS_EXPERIMENT_SKIP_A") == "1":
-                skip_state["i"] += 1
-                if skip_state["i"] % 2 == 0 and skip_state["last"] is not None and len(group) == 1:
-                    prev = skip_state["last"][0]
-                    st = parse(group[0])
-                    if st["B"] == prev["B"]:
-                        with torch.cuda.stream(sa):
-                            st["refer"] = torch.as_tensor(st.pop("refer_in")).to(dev, torch.float32).contiguous()
-                        st.update(gen=None, tr=None, lat=prev["lat"], n=prev["n"], a_done=prev["a_done"])
-                        return [st]
-            out = finish_a(launch_a(group))
-            skip_state["last"] = out
-            return out
-
-        # requests -> stage-A groups: with pair_stage_a (or DTTS_PAIR_STAGE_A=1) two consecutive requests of <= 8 utterances share a decode
-        # session.  Off by default: a 16-row decode step costs 1.6x an 8-row one (161 vs 103 ms per 234 tokens alone), and under the
-        # three-stream pipeline the longer chain measured 505 vs 482 ms per batch of 8 (bench.py, 10 steps).
-        pair = bool(pair_stage_a) or os.environ.get("DTTS_PAIR_STAGE_A", "0") == "1"
-        it = iter(requests)
-        held = []
-
-        def next_group():
-            while len(held) < 2:
-                try:
-                    held.append(next(it))
-                except StopIteration:
-                    break
-            if not held:
-                return None
-            nrows = [torch.as_tensor(r["text"]).shape[0] for r in held]
-            if pair and len(held) == 2 and nrows[0] <= 8 and nrows[1] <= 8:
-                g = [held.pop(0), held.pop(0)]
-            else:
-                g = [held.pop(0)]
-            return g
-
-        first = next_group()
+        # requests -> stage-A groups: with pair_stage_a two consecutive requests of <= 8 utterances share a decode session.  Off by
+        # default: a 16-row decode step costs 1.6x an 8-row one (161 vs 103 ms per 234 tokens alone), and under the three-stream
+        # pipeline the longer chain measured 505 vs 482 ms per batch of 8 (bench.py, 10 steps).
+        groups = group_requests(requests, bool(pair_stage_a))
+        first = next(groups, None)
         if first is None:
             return
         if self._a_pool is None:
@@ -737,7 +545,7 @@ class SynthesizerTrn:
         try:
             while fut is not None:
                 sts, fut = fut.result(), None   # the only wait on the GPU: this group's codes (their lengths size stage B)
-                g = next_group()
+                g = next(groups, None)
                 if g is not None:
                     fut = self._a_pool.submit(stage_a, g)            # the next group's stage A starts now, under this group's diffusion
                 for st in sts:
@@ -766,30 +574,17 @@ class SynthesizerTrn:
         """vqvae/model_24k.py:811-847: GPT codes -> quantizer.decode + vq_ref_enc -> vq_dec -> infer_flowvae (no diffusion).
         prompt_codes (not with forced_codes): line 819 calls UnifiedVoice.inference_speech_valle, see infer."""
         check_prompt_args(prompt_codes, forced_codes, 1)
-        text = torch.as_tensor(text)
-        refer = torch.as_tensor(refer)
-        tl = torch.as_tensor(text_length).reshape(-1).tolist()
-        rl = [int(v) for v in torch.as_tensor(refer_lengths).reshape(-1).tolist()]
-        if not batch:
-            text, refer, tl, rl = text[:1], refer[:1], tl[:1], rl[:1]
-            if forced_codes is not None:
-                forced_codes = forced_codes[:1]
-            if prompt_codes is not None:
-                prompt_codes = prompt_codes[:1]
-        B = text.shape[0]
-        pkw = {} if prompt_codes is None else dict(prompt_codes=prompt_rows(prompt_codes, B))
-        refer = refer.to(self.device, torch.float32).contiguous()
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        sample_ids = list(range(B)) if sample_ids is None else list(sample_ids)
-        if forced_codes is None:
-            texts = [text[b, : int(tl[b])].cpu().numpy().astype(np.int32) for b in range(B)]
-            codes, ncodes, _ = self.rt.gpt_generate(refer, rl, texts, seed, sample_ids, max_generate_length=max_generate_length,
+        st = normalize_request(text, text_length, refer, refer_lengths, seed, sample_ids, forced_codes, batch=batch)
+        B, rl, seed, sample_ids = st.B, st.rl, st.seed, st.sids
+        pkw = {} if prompt_codes is None else dict(prompt_codes=prompt_rows(prompt_codes if batch else prompt_codes[:1], B))
+        refer = st.refer.to(self.device, torch.float32).contiguous()
+        if st.forced is None:
+            codes, ncodes, _ = self.rt.gpt_generate(refer, rl, st.texts, seed, sample_ids, max_generate_length=max_generate_length,
                                                     top_k=top_k, top_p=TOP_P, temperature=TEMPERATURE,
                                                     repetition_penalty=REPETITION_PENALTY, suppress_eos=suppress_eos, **pkw)
             code_list = [codes[b, : int(ncodes[b]) - 1] for b in range(B)]          # codes[:, :-1]  (:828)
         else:
-            code_list = [np.asarray(c) for c in forced_codes]
+            code_list = [np.asarray(c) for c in st.forced]
         # vqvae/model_24k.py:833-834: the stop token came first -> the reference decodes a ZERO latent of 16 frames (64 mel frames);
         # code -1 is that zero vector in dtts_vq_decode
         code_list = [c if len(c) else np.full(self.EMPTY_CODE_FRAMES, -1, np.int64) for c in code_list]
