@@ -36,8 +36,11 @@ class DttsConfig(C.Structure):
 class DttsGptOptions(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("seed", C.c_ulonglong), ("sample_ids", c_int_p), ("max_generate_length", C.c_int), ("top_k", C.c_int),
                 ("top_p", C.c_float), ("temperature", C.c_float), ("repetition_penalty", C.c_float), ("suppress_eos", C.c_int),
-                ("forced_uniforms", C.c_void_p), ("forced_codes", c_int_p), ("row_seeds", c_u64_p), ("typical_mass", C.c_float), ("token_wgs", C.c_int),
-                ("prompt_codes", c_int_p), ("prompt_lens", c_int_p), ("prompt_stride", C.c_int)]
+                ("forced_uniforms", C.c_void_p), ("forced_codes", c_int_p), ("row_seeds", c_u64_p), ("typical_mass", C.c_float),
+                ("no_repeat_ngram_size", C.c_int), ("min_length", C.c_int), ("min_new_tokens", C.c_int), ("exp_decay_start", C.c_int),
+                ("exp_decay_factor", C.c_double), ("suppress_tokens", c_int_p), ("n_suppress_tokens", C.c_int),
+                ("begin_suppress_tokens", c_int_p), ("n_begin_suppress_tokens", C.c_int), ("min_p", C.c_float), ("epsilon_cutoff", C.c_float),
+                ("token_wgs", C.c_int), ("prompt_codes", c_int_p), ("prompt_lens", c_int_p), ("prompt_stride", C.c_int)]
 
 
 class DttsConvX3Info(C.Structure):
@@ -86,6 +89,10 @@ SIGNATURES = {
                                         C.c_float, C.c_float, c_int_p, C.c_void_p]),
     "dtts_op_sample_logits_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_int_p, C.c_int, C.c_void_p, C.c_int, C.c_float,
                                            C.c_float, C.c_float, C.c_float, C.c_int, c_int_p, C.c_void_p]),
+    "dtts_op_sample_logits_opts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DttsGptOptions), c_int_p, C.c_int, c_int_p,
+                                             c_int_p, c_int_p, C.c_void_p, c_int_p, C.c_void_p]),
+    "dtts_gpt_first_stop_step": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dtts_gpt_decay_multipliers": (None, [C.c_double, C.c_int, C.c_void_p]),
     "dtts_sampler_max_vocab": (C.c_int, []),
     "dtts_diff_p_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_ulonglong, c_int_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),

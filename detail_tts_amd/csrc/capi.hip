@@ -294,6 +294,22 @@ void dtts_gpt_options_init(dtts_gpt_options* o) {
     o->repetition_penalty = 2.0f;
 }
 
+// HF's remaining logits processors: the ranges their constructors accept (0 / NULL = off); NaN fails every range
+static void check_gpt_processors(const dtts_gpt_options* o, int V) {
+    DTTS_REQUIRE(o->no_repeat_ngram_size >= 0 && o->no_repeat_ngram_size <= dtts::SAMP_NGRAM_MAX, "options: no_repeat_ngram_size outside 0 .. 16 (0 = off)");
+    DTTS_REQUIRE(o->min_length >= 0 && o->min_new_tokens >= 0, "options: min_length / min_new_tokens negative");
+    DTTS_REQUIRE(o->exp_decay_factor == 0.0 || (o->exp_decay_factor > 1.0 && o->exp_decay_factor < (double)INFINITY && o->exp_decay_start >= 0),
+                 "options: exp_decay_factor is 0 (off) or > 1 with exp_decay_start >= 0");
+    DTTS_REQUIRE(o->n_suppress_tokens >= 0 && o->n_begin_suppress_tokens >= 0 && (o->n_suppress_tokens == 0 || o->suppress_tokens) &&
+                     (o->n_begin_suppress_tokens == 0 || o->begin_suppress_tokens), "options: suppress_tokens / begin_suppress_tokens list without ids");
+    for (int i = 0; i < o->n_suppress_tokens; ++i)
+        DTTS_REQUIRE(o->suppress_tokens[i] >= 0 && o->suppress_tokens[i] < V, "options: suppress_tokens id outside the vocabulary");
+    for (int i = 0; i < o->n_begin_suppress_tokens; ++i)
+        DTTS_REQUIRE(o->begin_suppress_tokens[i] >= 0 && o->begin_suppress_tokens[i] < V, "options: begin_suppress_tokens id outside the vocabulary");
+    DTTS_REQUIRE(o->min_p >= 0.f && o->min_p <= 1.f, "options: min_p outside [0, 1] (0 = off)");
+    DTTS_REQUIRE(o->epsilon_cutoff >= 0.f && o->epsilon_cutoff < 1.f, "options: epsilon_cutoff outside [0, 1) (0 = off)");
+}
+
 static void check_gpt_options(const dtts_gpt_options* o) {
     DTTS_REQUIRE(o, "options");
     DTTS_REQUIRE(o->struct_size == sizeof(dtts_gpt_options),
@@ -305,6 +321,7 @@ static void check_gpt_options(const dtts_gpt_options* o) {
     DTTS_REQUIRE(!o->prompt_codes || (o->prompt_lens && o->prompt_stride >= 0), "options: prompt_codes needs prompt_lens and prompt_stride >= 0");
     DTTS_REQUIRE(o->temperature > 0.f && o->temperature < INFINITY && o->top_p >= 0.f && o->top_p <= 1.f && o->repetition_penalty > 0.f &&
                      o->repetition_penalty < INFINITY, "options: temperature / top_p / repetition_penalty out of range");
+    check_gpt_processors(o, 8194);
 }
 
 int dtts_gpt_generate(dtts_handle* h, const float* refer, const int* refer_lens, int Tr, const int* text, const int* text_lens,
@@ -367,6 +384,30 @@ int dtts_op_sample_logits_ex(dtts_handle* h, const float* logits, int R, int V, 
     h->m->op_sample_logits(logits, R, V, history, hist_len, uniforms, top_k, top_p, temperature, repetition_penalty, typical_mass,
                            suppress_eos, tokens_out, (hipStream_t)stream);
     DTTS_API_END(h)
+}
+
+int dtts_op_sample_logits_opts(dtts_handle* h, const float* logits, int R, int V, const dtts_gpt_options* opts, const int* history,
+                               int hist_stride, const int* hist_lens, const int* fills, const int* prompt_lens, const float* uniforms,
+                               int* tokens_out, void* stream) {
+    DTTS_API_BEGIN
+    DTTS_REQUIRE(opts, "options");
+    DTTS_REQUIRE(opts->struct_size == sizeof(dtts_gpt_options),
+                 "dtts_gpt_options.struct_size does not match this library's layout: start from dtts_gpt_options_init()");
+    DTTS_REQUIRE(opts->typical_mass >= 0.f && opts->typical_mass <= 1.f, "op_sample_logits_opts: typical_mass outside [0, 1] (0 = off)");
+    DTTS_REQUIRE(opts->temperature > 0.f && opts->temperature < INFINITY && opts->top_p >= 0.f && opts->top_p <= 1.f &&
+                     opts->repetition_penalty > 0.f && opts->repetition_penalty < INFINITY, "options: temperature / top_p / repetition_penalty out of range");
+    check_gpt_processors(opts, V);
+    h->m->op_sample_logits_opts(logits, R, V, *opts, history, hist_stride, hist_lens, fills, prompt_lens, uniforms, tokens_out,
+                                (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_gpt_first_stop_step(int input_len, int forced_prefix, int min_length, int min_new_tokens) {
+    return dtts::gpt_first_stop_step(input_len, forced_prefix, min_length, min_new_tokens);
+}
+
+void dtts_gpt_decay_multipliers(double factor, int n, float* out) {
+    if (out && n > 0) dtts::gpt_decay_multipliers(factor, n, out);
 }
 
 int dtts_sampler_max_vocab(void) { return dtts::sampler_max_vocab(); }

@@ -30,7 +30,23 @@ struct GptCtl {
     int lat_cs;
     int pos_off[GEMV_MAXB];       // mel positions the row's prefix holds: 1 (start_mel alone) or m + 2 behind an acoustic prompt
                                   // [1, 8192, c_1 .. c_m]; the input embedding of generated token `step` sits at mel position step + pos_off
+    // ---- HF's remaining decode-time logits processors (generation/logits_process.py), each behind a field that is uniform over the
+    // workgroup; all zero / null = off (the sampler then does what it did without them).  "Step" is the row's ctl->step.
+    int ngram;                    // NoRepeatNGramLogitsProcessor(n), 1 .. SAMP_NGRAM_MAX; 0: off.  Needs hist
+    int* hist;                    // [B][hist_stride] the row's ORDERED input_ids without the fill-id-1 prefix columns: hist_n0[b] ids seeded
+    int hist_stride;              // at prefill (8192, an acoustic prompt's codes), then one token per step appended by the sampler
+    int hist_n0[GEMV_MAXB];
+    int nfill[GEMV_MAXB];         // min(n, fill ids in front of hist): the only fill ids an n-gram can reach (the prefix is not materialised)
+    int stop_from[GEMV_MAXB];     // MinLength + MinNewTokensLength folded: the first step at which the stop token may be drawn
+    const float* decay_mul;       // ExponentialDecayLengthPenalty: [decay_n] float(factor^i - 1), i = step - decay_off[b] > 0; null: off
+    int decay_n;
+    int decay_off[GEMV_MAXB];
+    const unsigned char* tok_mask;      // [V] bit 0: SuppressTokens (always -inf), bit 1: SuppressTokensAtBegin (at step begin_step[b]); null: off
+    int begin_step[GEMV_MAXB];
+    float min_p;                  // MinPLogitsWarper (after top-k / top-p); <= 0: off
+    float eps_cutoff;             // EpsilonLogitsWarper (after min_p); <= 0: off
 };
+constexpr int SAMP_NGRAM_MAX = 16;
 
 // lat = LN2(LN1(res + bias + sum_slices parts)) (ln_f then final_norm, gpt/model.py:173 + HF GPT2Model.ln_f) -> y [B][C] and, when
 // ctl->latents is set, column ctl->step[b] of the latents tensor.  in_slices == 0: res alone.

@@ -809,6 +809,12 @@ __global__ __launch_bounds__(SAMP_THREADS) void sampler_kernel(const SamplerPara
     if (pos_pf && tid < p.C) pos_next = p.mel_pos[(long long)pos_row * p.C + tid];
     const int top_k = ctl->top_k;
     const float top_p = ctl->top_p;
+    // (the switches of HF's remaining processors are requested here, with the fields above, so that no phase behind a barrier starts
+    // with a load of its own)
+    int* const hist = ctl->hist;                          // null unless the n-gram processor runs: the row's ordered token history
+    const int ngram = ctl->ngram;
+    const unsigned char* const tok_mask = ctl->tok_mask;
+    const float min_p = ctl->min_p, eps_cutoff = ctl->eps_cutoff;
     int token;
     // forced token of this (row, step), or -1: sample.  A row may be forced for a prefix only (UnifiedVoice.inference_speech_tortoise's
     // input_tokens, gpt/model.py:533-537) - the choice is uniform over the workgroup (one row per workgroup)
@@ -819,7 +825,19 @@ __global__ __launch_bounds__(SAMP_THREADS) void sampler_kernel(const SamplerPara
         // 1. logits = head GEMV partials + bias (its finish), repetition penalty over every id in the row's input_ids, temperature
         const unsigned char* seen = p.seen + (long long)b * V;
         const float rp = ctl->repetition_penalty, temp = ctl->temperature;
-        const int eos_off = ctl->suppress_eos ? p.eos : -1;
+        // MinLength / MinNewTokensLength (HF runs them behind the penalty: -inf either way) share suppress_eos' compare
+        const int eos_off = (ctl->suppress_eos || step < ctl->stop_from[b]) ? p.eos : -1;
+        // ExponentialDecayLengthPenalty: stop score += |stop score| * float(factor^i - 1), behind the penalty and in front of the
+        // temperature; two rounded float operations as torch does them (no contraction).  A stop score that is -inf stays -inf.
+        int eos_dec = -1;
+        float dmul = 0.f;
+        if (ctl->decay_mul && eos_off < 0) {
+            const int i = step - ctl->decay_off[b];
+            if (i > 0) {
+                dmul = ctl->decay_mul[i < ctl->decay_n ? i : ctl->decay_n - 1];
+                eos_dec = p.eos;
+            }
+        }
         const bool typical = ctl->typical_mass > 0.f && ctl->typical_mass < 1.f;
         // (the maximum of the processed scores rides along: top-k keeps it, so it is the softmax maximum of step 3 unless the typical
         // warper - which may drop the most probable token - runs; a maximum does not depend on the order it is taken in)
@@ -833,6 +851,7 @@ __global__ __launch_bounds__(SAMP_THREADS) void sampler_kernel(const SamplerPara
                     x += pf_x[i];
                     if (v == eos_off) x = -INFINITY;
                     if (pf_seen[i]) x = x < 0.f ? x * rp : x / rp;
+                    if (v == eos_dec) x = __fadd_rn(x, __fmul_rn(fabsf(x), dmul));
                     const float y = typical ? x : x / temp;
                     sv[v] = y;
                     tmax = fmaxf(tmax, y);
@@ -845,6 +864,7 @@ __global__ __launch_bounds__(SAMP_THREADS) void sampler_kernel(const SamplerPara
             x += sum_parts(p.parts, p.slices, (long long)p.B * p.Vs, (long long)b * p.Vs + v);
             if (v == eos_off) x = -INFINITY;
             if (seen[v]) x = x < 0.f ? x * rp : x / rp;
+            if (v == eos_dec) x = __fadd_rn(x, __fmul_rn(fabsf(x), dmul));
             const float y = typical ? x : x / temp;
             sv[v] = y;
             tmax = fmaxf(tmax, y);
@@ -857,6 +877,36 @@ __global__ __launch_bounds__(SAMP_THREADS) void sampler_kernel(const SamplerPara
         float mx_early = -INFINITY;
         for (int i = 0; i < SAMP_THREADS / 64; ++i) mx_early = fmaxf(mx_early, red[i]);
         SSTAMP(1);
+        // 1a. the processors that only ban ids (HF order: NoRepeatNGram, then - behind the stop-token ones above - SuppressTokens and
+        // SuppressTokensAtBegin; all in front of the typical warper and the temperature, and -inf commutes with the division).
+        if (ngram > 0 || tok_mask) {
+            if (ngram > 0) {
+                // input_ids = nf fill ids (1), then hist[0 .. n0 + step).  The next token would complete an n-gram that starts with the
+                // last n-1 ids: every window whose first n-1 ids equal them bans its own last id.  One window start per thread.
+                const int* h = hist + (long long)b * ctl->hist_stride;
+                const int nf = ctl->nfill[b], L = nf + ctl->hist_n0[b] + step;
+#define SEQ(i) ((i) < nf ? 1 : h[(i) - nf])
+                for (int i = tid; i <= L - ngram; i += SAMP_THREADS) {
+                    bool same = true;
+                    for (int j = 0; j < ngram - 1; ++j) same = same && SEQ(i + j) == SEQ(L - ngram + 1 + j);
+                    if (same) {
+                        const int t = SEQ(i + ngram - 1);
+                        if (t >= 0 && t < V) sv[t] = -INFINITY;
+                    }
+                }
+#undef SEQ
+            }
+            if (tok_mask) {
+                const unsigned on = step == ctl->begin_step[b] ? 3u : 1u;
+                for (int v = tid; v < V; v += SAMP_THREADS)
+                    if (tok_mask[v] & on) sv[v] = -INFINITY;
+            }
+            __syncthreads();
+            // the maximum that rode along may have been banned
+            float m1 = -INFINITY;
+            for (int v = tid; v < V; v += SAMP_THREADS) m1 = fmaxf(m1, sv[v]);
+            mx_early = block_reduce_max(m1, red);
+        }
         // 1b. HF TypicalLogitsWarper (inference_speech_tortoise(typical_sampling=True), gpt/model.py:539; it sits between the repetition
         // penalty and the temperature): key = | -log p - H |, ascending sort of the whole vocabulary by it, keep the keys up to the
         // first whose cumulative probability reaches the mass.  Off the infer path: the full 16 K-slot bitonic sort is fine here.
@@ -1094,6 +1144,22 @@ __global__ __launch_bounds__(SAMP_THREADS) void sampler_kernel(const SamplerPara
             SSTAMP(11);
             }
         }
+        // 4b. HF MinPLogitsWarper, then EpsilonLogitsWarper, on the softmax of what top-k and top-p kept (whichever top-p path ran):
+        // p < min_p * p_max goes (p_max = 1 / Z: the largest score is mx), then p < epsilon unless the score is the largest.  A thread
+        // reads and writes its own strided ids only, so the two passes need no barrier between them.
+        if (min_p > 0.f || eps_cutoff > 0.f) {
+            for (int pass = 0; pass < 2; ++pass) {
+                if (!((pass == 0 ? min_p : eps_cutoff) > 0.f)) continue;
+                float z = 0.f;
+                for (int v = tid; v < V; v += SAMP_THREADS)
+                    if (sv[v] > -INFINITY) z += expf(sv[v] - mx);
+                z = block_reduce_sum(z, red);
+                const float thr = pass == 0 ? __fmul_rn(min_p, 1.0f / z) : eps_cutoff;
+                for (int v = tid; v < V; v += SAMP_THREADS)
+                    if (sv[v] > -INFINITY && sv[v] < mx && expf(sv[v] - mx) / z < thr) sv[v] = -INFINITY;
+            }
+            __syncthreads();
+        }
         // 5. inverse-CDF draw in vocabulary order
         const int per = (V + SAMP_THREADS - 1) / SAMP_THREADS;
         const int v0 = tid * per;
@@ -1132,6 +1198,7 @@ __global__ __launch_bounds__(SAMP_THREADS) void sampler_kernel(const SamplerPara
         p.codes[(long long)b * p.codes_stride + step] = token;
         p.seen[(long long)b * V + token] = 1;
         if (token == p.eos) p.finished[b] = 1;
+        if (hist) hist[(long long)b * ctl->hist_stride + ctl->hist_n0[b] + step] = token;      // (step < max_steps: inside the row)
         ctl->step[b] = step + 1;                 // only this workgroup reads or writes step[b] inside this launch
     }
     // next input embedding: mel_embedding[token] + mel_pos_embedding[step + pos_off]   (gpt/model.py:134-136 with position k)

@@ -115,6 +115,10 @@ struct GptLayerW {
     const float *attn_c = nullptr, *attn_d = nullptr, *fc_c = nullptr, *fc_d = nullptr;
 };
 
+// host arithmetic of HF's length processors and decay penalty (model_gpt.hip; also behind dtts_gpt_first_stop_step / dtts_gpt_decay_multipliers)
+int gpt_first_stop_step(int input_len, int forced_prefix, int min_length, int min_new_tokens);
+void gpt_decay_multipliers(double factor, int n, float* out);
+
 // A GPT decode session (dtts_gpt_prefill .. dtts_gpt_finish): device state of <= 8 sequences in the handle's own arena
 struct GptSession {
     int B = 0, cap = 0, G = 0, steps = 0;      // rows, KV capacity (columns), max_generate_length, tokens generated so far
@@ -124,6 +128,9 @@ struct GptSession {
           *st1 = nullptr, *st2 = nullptr;
     unsigned char* seen = nullptr;
     int *finished = nullptr, *codes = nullptr, *forced = nullptr;
+    int* hist = nullptr;               // [B][cap] ordered token history (no_repeat_ngram_size)
+    unsigned char* tok_mask = nullptr; // [V] suppress_tokens / begin_suppress_tokens bits
+    float* decay_mul = nullptr;        // [G + 1] exponential_decay_length_penalty multipliers
     GptCtl* ctl = nullptr;
     // persistent token kernel (gpt_token.hip): exchange arena, logits rows, error flag, launch counter
     unsigned long long* xch = nullptr;
@@ -275,6 +282,9 @@ public:
     void op_sample_logits(const float* logits, int R, int V, const int* history_host, int hist_len, const float* uniforms, int top_k,
                           float top_p, float temperature, float repetition_penalty, float typical_mass, int suppress_eos, int* tokens_host,
                           hipStream_t s);
+    void op_sample_logits_opts(const float* logits, int R, int V, const dtts_gpt_options& o, const int* history_host, int hist_stride,
+                               const int* hist_lens, const int* fills, const int* prompt_lens, const float* uniforms, int* tokens_host,
+                               hipStream_t s);
     void gpt_latents(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host,
                      int Lt_max, const int* codes_host, const int* ncodes_host, int n_max, int B, float* latents_cm, int lat_stride,
                      hipStream_t s);
@@ -594,7 +604,7 @@ private:
         bool valid = false;
         int Tr = 0, Lt_max = 0, B = 0, lat_stride = 0;
         bool has_refer_lens = false, has_text_lens = false;
-        std::vector<int> refer_lens, text, text_lens, sample_ids, forced_codes, prompt_codes, prompt_lens;
+        std::vector<int> refer_lens, text, text_lens, sample_ids, forced_codes, prompt_codes, prompt_lens, suppress, begin_suppress;
         std::vector<unsigned long long> row_seeds;
         dtts_gpt_options o;
         float* latents_cm = nullptr;

@@ -252,6 +252,45 @@ static void prompt_prefix_ids(const dtts_gpt_options& o, int B, int G, int max_m
     }
 }
 
+// ---- HF's remaining logits processors: what the host prepares for the sampler's control block -----------------------------------
+// [V] bit 0 = suppress_tokens, bit 1 = begin_suppress_tokens (ids were range-checked by check_gpt_options against 8194; here against V)
+static std::vector<unsigned char> processor_token_mask(const dtts_gpt_options& o, int V) {
+    std::vector<unsigned char> m(V, 0);
+    for (int i = 0; i < o.n_suppress_tokens; ++i) {
+        DTTS_REQUIRE(o.suppress_tokens[i] >= 0 && o.suppress_tokens[i] < V, "suppress_tokens: id outside [0, V)");
+        m[o.suppress_tokens[i]] |= 1;
+    }
+    for (int i = 0; i < o.n_begin_suppress_tokens; ++i) {
+        DTTS_REQUIRE(o.begin_suppress_tokens[i] >= 0 && o.begin_suppress_tokens[i] < V, "begin_suppress_tokens: id outside [0, V)");
+        m[o.begin_suppress_tokens[i]] |= 2;
+    }
+    return m;
+}
+// ExponentialDecayLengthPenalty's multipliers: t[i] = float(pow(factor, i) - 1), the power and the difference in double as Python
+// evaluates them (float.__pow__ is the C library's pow), rounded once to the float32 torch multiplies |score| by.  Saturated at
+// DECAY_MUL_MAX: far behind `start` HF's multiplier leaves float32 (inf: |score| * inf, then inf - inf = NaN in its softmax) or Python's
+// pow raises OverflowError; here the stop score stays finite and so large that the stop token is the only one left - what the
+// penalty is for.  No factor is refused for the length of the call.
+constexpr double DECAY_MUL_MAX = 1e30;
+void gpt_decay_multipliers(double factor, int n, float* out) {
+    for (int i = 0; i < n; ++i) {
+        const double m = i == 0 ? 0.0 : std::pow(factor, (double)i) - 1.0;
+        out[i] = (float)(m < DECAY_MUL_MAX ? m : DECAY_MUL_MAX);
+    }
+}
+static std::vector<float> processor_decay_table(double factor, int n) {
+    std::vector<float> t(n, 0.f);
+    gpt_decay_multipliers(factor, n, t.data());
+    return t;
+}
+// MinLength and MinNewTokensLength folded: the first decode step at which the stop token may be drawn.  At step j HF sees
+// input_len + j ids, j - forced_prefix of them behind its prompt: the stop is -inf while input_len + j < min_length or
+// j - forced_prefix < min_new_tokens.  (forced_prefix < 0: the unit entry's rows, which are already some tokens behind the prompt.)
+int gpt_first_stop_step(int input_len, int forced_prefix, int min_length, int min_new_tokens) {
+    return std::max(0, std::max(min_length - input_len, min_new_tokens > 0 ? forced_prefix + min_new_tokens : 0));
+}
+static bool processors_mask_on(const dtts_gpt_options& o) { return o.n_suppress_tokens > 0 || o.n_begin_suppress_tokens > 0; }
+
 // ---- decode session ------------------------------------------------------------------------------------------------------------
 // dtts_gpt_prefill: conditioning encoder + [cond | text | start_mel] prefill (KV cache filled) + the first sampled token; with
 // dtts_gpt_options.prompt_codes the prefix is [cond | text | 1, 8192, prompt] (inference_speech_valle, gpt/model.py:546-579): the
@@ -278,7 +317,9 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
             r.has_refer_lens = refer_lens_host != nullptr;
             r.has_text_lens = text_lens_host != nullptr;
             r.refer_lens.clear(); r.text_lens.clear(); r.forced_codes.clear(); r.row_seeds.clear();      // nothing of an earlier session survives
-            r.prompt_codes.clear(); r.prompt_lens.clear();
+            r.prompt_codes.clear(); r.prompt_lens.clear(); r.suppress.clear(); r.begin_suppress.clear();
+            if (o.n_suppress_tokens > 0) r.suppress.assign(o.suppress_tokens, o.suppress_tokens + o.n_suppress_tokens);
+            if (o.n_begin_suppress_tokens > 0) r.begin_suppress.assign(o.begin_suppress_tokens, o.begin_suppress_tokens + o.n_begin_suppress_tokens);
             if (refer_lens_host) r.refer_lens.assign(refer_lens_host, refer_lens_host + B);
             r.text.assign(text_host, text_host + (size_t)B * Lt_max);
             if (text_lens_host) r.text_lens.assign(text_lens_host, text_lens_host + B);
@@ -316,6 +357,7 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
     const long long kv_bs = (long long)2 * C * cap, kv_layer = kv_bs * B;
     const size_t need = sizeof(float) * ((size_t)NL * kv_layer + (size_t)B * (4 * C + cfg.gpt_heads * 8 * ATT_REC) + (size_t)2 * B * GEMV_PART_FLOATS + 2 * 64 * GEMV_MAXB * 2) +
                         (size_t)B * V + sizeof(int) * ((size_t)2 * B * G + 64) + sizeof(GptCtl) + 64 * 256 +
+                        sizeof(int) * (size_t)B * cap + (size_t)V + sizeof(float) * ((size_t)G + 1) + 4 * 256 +
                         (tok_ok_ && B <= GPT_TOKEN_ROWS ? sizeof(unsigned long long) * GPT_TOKEN_XCH_WORDS + sizeof(float) * GPT_TOKEN_ROWS * GPT_TOKEN_VS + 1024 : 0);
     if (need > gpt_state_.capacity() || gs_.B != B || gs_.cap != cap || gs_.G != G) {
         gpt_drop_graphs();
@@ -337,6 +379,9 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
         n.finished = gpt_state_.i32(B);
         n.codes = gpt_state_.i32((size_t)B * G);
         n.forced = gpt_state_.i32((size_t)B * G);
+        n.hist = gpt_state_.i32((size_t)B * cap);
+        n.tok_mask = static_cast<unsigned char*>(gpt_state_.raw((size_t)V));
+        n.decay_mul = gpt_state_.f32((size_t)G + 1);
         n.ctl = static_cast<GptCtl*>(gpt_state_.raw(sizeof(GptCtl)));
         if (tok_ok_ && B <= GPT_TOKEN_ROWS) {
             n.xch = static_cast<unsigned long long*>(gpt_state_.raw(sizeof(unsigned long long) * GPT_TOKEN_XCH_WORDS));
@@ -397,6 +442,46 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
     c.latents = latents_cm;
     c.lat_bs = (long long)C * lat_stride;
     c.lat_cs = lat_stride;
+    // ---- HF's remaining processors.  A row's input_ids at step j are fills + nn ids: fills = lp - nn fill ids (1) in front of the nn
+    // ordered ids [8192, prompt codes] (the prompt's own leading 1 is a fill id), then j tokens.  HF's prompt ends behind the forced
+    // prefix (input_tokens): k = the leading forced codes >= 0.
+    std::vector<int> hist0;
+    std::vector<unsigned char> mask0;
+    std::vector<float> decay0;
+    {
+        const int n = o.no_repeat_ngram_size;
+        DTTS_REQUIRE(n >= 0 && n <= SAMP_NGRAM_MAX, "no_repeat_ngram_size outside 0 .. 16");
+        c.ngram = n;
+        c.hist = n > 0 ? gs_.hist : nullptr;
+        c.hist_stride = cap;
+        if (n > 0) hist0.assign((size_t)B * cap, 0);
+        for (int b = 0; b < B; ++b) {
+            const int lead = o.prompt_codes && !opt_prompt_raw_ ? 1 : 0, nn = ml[b] - lead;
+            int k = 0;
+            if (o.forced_codes)
+                while (k < G && o.forced_codes[(size_t)b * G + k] >= 0) ++k;
+            c.hist_n0[b] = nn;
+            c.nfill[b] = std::min(n, lp[b] - nn);
+            if (n > 0) std::copy(mel0.data() + (size_t)b * np_max + lead, mel0.data() + (size_t)b * np_max + ml[b], hist0.data() + (size_t)b * cap);
+            c.stop_from[b] = gpt_first_stop_step(lp[b], k, o.min_length, o.min_new_tokens);
+            c.decay_off[b] = k + o.exp_decay_start;
+            c.begin_step[b] = k;
+        }
+        if (processors_mask_on(o)) {
+            mask0 = processor_token_mask(o, V);
+            c.tok_mask = gs_.tok_mask;
+            DTTS_CHECK_HIP(hipMemcpyAsync(gs_.tok_mask, mask0.data(), mask0.size(), hipMemcpyHostToDevice, s));
+        }
+        if (o.exp_decay_factor > 0.0) {
+            decay0 = processor_decay_table(o.exp_decay_factor, G + 1);
+            c.decay_mul = gs_.decay_mul;
+            c.decay_n = G + 1;
+            DTTS_CHECK_HIP(hipMemcpyAsync(gs_.decay_mul, decay0.data(), sizeof(float) * decay0.size(), hipMemcpyHostToDevice, s));
+        }
+        if (n > 0) DTTS_CHECK_HIP(hipMemcpyAsync(gs_.hist, hist0.data(), sizeof(int) * hist0.size(), hipMemcpyHostToDevice, s));
+        c.min_p = o.min_p;
+        c.eps_cutoff = o.epsilon_cutoff;
+    }
     DTTS_CHECK_HIP(hipMemcpyAsync(gs_.ctl, &c, sizeof(c), hipMemcpyHostToDevice, s));
     if (o.forced_codes) DTTS_CHECK_HIP(hipMemcpyAsync(gs_.forced, o.forced_codes, sizeof(int) * (size_t)B * G, hipMemcpyHostToDevice, s));
     // seen = ids of the fake prefix: 1 (all prefix slots) and start_mel 8192  (gpt/model.py:528-530); behind a prompt also its codes
@@ -694,6 +779,8 @@ void Model::gpt_finish(int* codes_host, int* ncodes_host, hipStream_t s) {
         o.forced_codes = r.forced_codes.empty() ? nullptr : r.forced_codes.data();
         o.row_seeds = r.row_seeds.empty() ? nullptr : r.row_seeds.data();
         if (o.prompt_codes) { o.prompt_codes = r.prompt_codes.data(); o.prompt_lens = r.prompt_lens.data(); }
+        o.suppress_tokens = r.suppress.empty() ? nullptr : r.suppress.data();
+        o.begin_suppress_tokens = r.begin_suppress.empty() ? nullptr : r.begin_suppress.data();
         replaying_ = true;
         try {
             gpt_replay_.reset();
@@ -798,6 +885,103 @@ void Model::op_sample_logits(const float* logits, int R, int V, const int* histo
     sp.V = V;
     sp.B = R;
     sp.seen = seen;
+    sp.finished = finished;
+    sp.codes = codes;
+    sp.codes_stride = 1;
+    sp.eos = V - 1;
+    sp.ctl = dctl;
+    sp.mel_emb = nullptr;
+    sp.mel_pos = nullptr;
+    sp.x_next = nullptr;
+    sp.C = 0;
+    launch_sampler(sp, s);
+    DTTS_CHECK_HIP(hipMemcpyAsync(tokens_host, codes, sizeof(int) * R, hipMemcpyDeviceToHost, s));
+    DTTS_CHECK_HIP(hipStreamSynchronize(s));
+}
+
+// unit entry: the sampler under a whole option block, on rows whose input_ids are `fills[r]` fill ids followed by an ordered history
+void Model::op_sample_logits_opts(const float* logits, int R, int V, const dtts_gpt_options& o, const int* history_host, int hist_stride,
+                                  const int* hist_lens, const int* fills, const int* prompt_lens, const float* uniforms, int* tokens_host,
+                                  hipStream_t s) {
+    DTTS_REQUIRE(R >= 1 && R <= GEMV_MAXB, "op_sample_logits_opts: rows 1..16");
+    DTTS_REQUIRE(V >= 2 && V <= sampler_max_vocab(), "op_sample_logits_opts: vocabulary outside 2 .. the LDS sampler's maximum");
+    DTTS_REQUIRE(logits && uniforms && tokens_host && hist_lens && fills && prompt_lens && hist_stride >= 0, "op_sample_logits_opts: operands");
+    const int n = o.no_repeat_ngram_size;
+    DTTS_REQUIRE(n >= 0 && n <= SAMP_NGRAM_MAX, "no_repeat_ngram_size outside 0 .. 16");
+    const int hs = hist_stride + 1;                       // the sampler appends the drawn token behind the row's history
+    std::vector<unsigned char> seen((size_t)R * V, 0);
+    std::vector<int> hist((size_t)R * hs, 0);
+    GptCtl c;
+    std::memset(&c, 0, sizeof(c));
+    int decay_n = 2;
+    for (int r = 0; r < R; ++r) {
+        DTTS_REQUIRE(hist_lens[r] >= 0 && hist_lens[r] <= hist_stride && fills[r] >= 0, "op_sample_logits_opts: hist_lens / fills");
+        DTTS_REQUIRE(hist_lens[r] == 0 || history_host, "op_sample_logits_opts: history");
+        const int cur = fills[r] + hist_lens[r];          // len(input_ids)
+        DTTS_REQUIRE(prompt_lens[r] >= 0 && prompt_lens[r] <= cur, "op_sample_logits_opts: prompt_lens outside [0, fills + hist_lens]");
+        if (fills[r] > 0) seen[(size_t)r * V + 1] = 1;
+        for (int j = 0; j < hist_lens[r]; ++j) {
+            const int id = history_host[(size_t)r * hist_stride + j];
+            DTTS_REQUIRE(id >= 0 && id < V, "history id");
+            seen[(size_t)r * V + id] = 1;
+            hist[(size_t)r * hs + j] = id;
+        }
+        c.hist_n0[r] = hist_lens[r];
+        c.nfill[r] = std::min(n, fills[r]);
+        const int fresh = cur - prompt_lens[r];           // tokens behind HF's prompt
+        c.stop_from[r] = gpt_first_stop_step(cur, -fresh, o.min_length, o.min_new_tokens);      // > 0: the sampler's step 0 is in front of it
+        const int i = fresh - o.exp_decay_start;          // the sampler's step is 0: i = step - decay_off
+        c.decay_off[r] = -i;
+        decay_n = std::max(decay_n, i + 1);
+        c.begin_step[r] = fresh == 0 ? 0 : -1;
+    }
+    ws().ensure((size_t)R * V + sizeof(int) * ((size_t)R * hs + 4 * R) + sizeof(GptCtl) + (size_t)V + sizeof(float) * decay_n + 16 * 256);
+    unsigned char* d_seen = static_cast<unsigned char*>(ws().raw((size_t)R * V));
+    int* finished = ws().i32(R);
+    int* codes = ws().i32(R);
+    int* d_hist = ws().i32((size_t)R * hs);
+    unsigned char* d_mask = static_cast<unsigned char*>(ws().raw((size_t)V));
+    float* d_decay = ws().f32(decay_n);
+    GptCtl* dctl = static_cast<GptCtl*>(ws().raw(sizeof(GptCtl)));
+    c.repetition_penalty = o.repetition_penalty;
+    c.temperature = o.temperature;
+    c.top_p = o.top_p;
+    c.top_k = o.top_k;
+    c.typical_mass = o.typical_mass;
+    c.suppress_eos = o.suppress_eos;
+    c.max_steps = 1;
+    c.forced_u = uniforms;
+    c.u_stride = 1;
+    c.ngram = n;
+    c.hist = n > 0 ? d_hist : nullptr;
+    c.hist_stride = hs;
+    c.min_p = o.min_p;
+    c.eps_cutoff = o.epsilon_cutoff;
+    std::vector<unsigned char> mask0;
+    std::vector<float> decay0;
+    if (processors_mask_on(o)) {
+        mask0 = processor_token_mask(o, V);
+        c.tok_mask = d_mask;
+        DTTS_CHECK_HIP(hipMemcpyAsync(d_mask, mask0.data(), mask0.size(), hipMemcpyHostToDevice, s));
+    }
+    if (o.exp_decay_factor > 0.0) {
+        decay0 = processor_decay_table(o.exp_decay_factor, decay_n);
+        c.decay_mul = d_decay;
+        c.decay_n = decay_n;
+        DTTS_CHECK_HIP(hipMemcpyAsync(d_decay, decay0.data(), sizeof(float) * decay0.size(), hipMemcpyHostToDevice, s));
+    }
+    DTTS_CHECK_HIP(hipMemcpyAsync(dctl, &c, sizeof(c), hipMemcpyHostToDevice, s));
+    DTTS_CHECK_HIP(hipMemcpyAsync(d_seen, seen.data(), seen.size(), hipMemcpyHostToDevice, s));
+    DTTS_CHECK_HIP(hipMemcpyAsync(d_hist, hist.data(), sizeof(int) * hist.size(), hipMemcpyHostToDevice, s));
+    DTTS_CHECK_HIP(hipMemsetAsync(finished, 0, sizeof(int) * R, s));
+    SamplerParams sp;
+    sp.parts = logits;
+    sp.slices = 1;
+    sp.bias = nullptr;
+    sp.Vs = V;
+    sp.V = V;
+    sp.B = R;
+    sp.seen = d_seen;
     sp.finished = finished;
     sp.codes = codes;
     sp.codes_stride = 1;

@@ -57,7 +57,11 @@ class UnifiedVoice:
                                   text_lengths=None, seed=0, sample_ids=None, suppress_eos=False, forced_uniforms=None,
                                   **hf_generate_kwargs):
         """gpt/model.py:514-545.  hf_generate_kwargs understood: do_sample, top_p, top_k, temperature, repetition_penalty, length_penalty
-        (inert without beams).  Returns LongTensor [B * num_return_sequences, <=max] incl. the stop token (and input_tokens in front).
+        (inert without beams), and HF's remaining decode-time processors, served by the device sampler in HF's order
+        (gpt/decode_options.py states the counting rules): no_repeat_ngram_size (1 .. 16), min_length, min_new_tokens,
+        exponential_decay_length_penalty = (start, factor > 1), suppress_tokens, begin_suppress_tokens, and - under do_sample=True only,
+        as in HF - min_p and epsilon_cutoff.  Bad values raise ValueError before any launch.  Any other keyword is still dropped
+        (bad_words_ids, sequence_bias, typical_p, eta_cutoff, top_h, encoder_*, beams: INTEGRATION.md 1).  Returns LongTensor [B * num_return_sequences, <=max] incl. the stop token (and input_tokens in front).
 
         Off the `infer` path but part of the reference's surface: `do_sample=False` (HF greedy search: only the repetition penalty is a
         logits processor there, argmax), `num_return_sequences = n` (HF repeats every row n times - repeat_interleave - and samples the
@@ -99,6 +103,8 @@ class UnifiedVoice:
         nrs = int(num_return_sequences)
         assert nrs >= 1
         do_sample = bool(hf_generate_kwargs.get("do_sample", True))
+        from .decode_options import validate_decode_options
+        processors = validate_decode_options(hf_generate_kwargs, do_sample=do_sample, strict=False)      # (ValueError before any launch)
         refer = speech_conditioning_latent.float().contiguous()
         B = refer.shape[0]
         it = None
@@ -148,7 +154,8 @@ class UnifiedVoice:
         codes, ncodes, lat = self.rt.gpt_generate(
             refer, cl, texts, seed, ids, max_generate_length=G, repetition_penalty=hf_generate_kwargs.get("repetition_penalty", 1.0),
             suppress_eos=suppress_eos, forced_uniforms=forced_uniforms, forced_codes=forced, forced_fill=-1,
-            typical_mass=float(typical_mass) if typical_sampling else 0.0, **samp, **({} if prompt is None else dict(prompt_codes=prompt)))
+            typical_mass=float(typical_mass) if typical_sampling else 0.0, **samp, **({} if prompt is None else dict(prompt_codes=prompt)),
+            **({"processors": processors} if processors else {}))
         self.last_latents, self.last_ncodes = lat, ncodes
         n = int(ncodes.max())
         return torch.from_numpy(codes[:, :n].astype(np.int64)).to(refer.device)

@@ -166,10 +166,37 @@ class Runtime:
         from .gpt.prompt import pack_prompt
         return pack_prompt(prompt_codes, B, text_lens, G)
 
+    @staticmethod
+    def _processors(o, processors, vocab=8194):
+        """HF's remaining logits processors -> the fields at the end of dtts_gpt_options.  processors: None / {} (all off) or the keywords
+        of gpt/decode_options.py, validated there (again here: every refusal comes before the library call).  Returns the arrays the
+        struct points into - keep them until the call returns."""
+        if not processors:
+            return None
+        from .gpt.decode_options import validate_decode_options
+        p = validate_decode_options(processors, vocab=vocab)
+        o.no_repeat_ngram_size = p.get("no_repeat_ngram_size", 0)
+        o.min_length, o.min_new_tokens = p.get("min_length", 0), p.get("min_new_tokens", 0)
+        if "exponential_decay_length_penalty" in p:
+            o.exp_decay_start, o.exp_decay_factor = p["exponential_decay_length_penalty"]
+        keep = []
+        for key, ptr, cnt in (("suppress_tokens", "suppress_tokens", "n_suppress_tokens"),
+                              ("begin_suppress_tokens", "begin_suppress_tokens", "n_begin_suppress_tokens")):
+            if key in p:
+                a = np.ascontiguousarray(np.asarray(p[key], np.int32))
+                setattr(o, ptr, a.ctypes.data_as(_lib.c_int_p))
+                setattr(o, cnt, int(a.size))
+                keep.append(a)
+        o.min_p, o.epsilon_cutoff = p.get("min_p", 0.0), p.get("epsilon_cutoff", 0.0)
+        return keep
+
     def gpt_generate(self, refer, refer_lens, texts, seed, sample_ids, max_generate_length=600, top_k=50, top_p=0.8,
-                     temperature=0.8, repetition_penalty=2.0, suppress_eos=False, forced_uniforms=None, forced_codes=None, forced_fill=8193, typical_mass=0.0, token_wgs=0, prompt_codes=None):
+                     temperature=0.8, repetition_penalty=2.0, suppress_eos=False, forced_uniforms=None, forced_codes=None, forced_fill=8193, typical_mass=0.0, token_wgs=0, prompt_codes=None,
+                     processors=None):
         """-> (codes int32 [B,G] incl. stop, ncodes [B], latents_cm float32 cuda [B,768,G]).  prompt_codes ([B, m] or a list of B
-        one-dimensional arrays): the acoustic prompt of inference_speech_valle, see gpt_prefill."""
+        one-dimensional arrays): the acoustic prompt of inference_speech_valle, see gpt_prefill.  processors: None or a dict of HF's
+        remaining decode-time keywords (gpt/decode_options.py: no_repeat_ngram_size, min_length, min_new_tokens,
+        exponential_decay_length_penalty, suppress_tokens, begin_suppress_tokens, min_p, epsilon_cutoff)."""
         B, _, Tr = refer.shape
         text, tl = self._pad_text(texts)
         G = int(max_generate_length)
@@ -190,6 +217,7 @@ class Runtime:
         o.suppress_eos = 1 if suppress_eos else 0
         o.typical_mass = float(typical_mass or 0.0)
         o.token_wgs = int(token_wgs or 0)       # 0: the handle's gpt_token_wgs option; 64 / 32: this session decodes on fewer workgroups (same bits)
+        keep_proc = self._processors(o, processors)      # noqa: F841  (ValueError before any library call; the arrays live to the call's end)
         if prompt is not None:
             o.prompt_codes, o.prompt_lens, o.prompt_stride = prompt[0].ctypes.data_as(_lib.c_int_p), prompt[1].ctypes.data_as(_lib.c_int_p), prompt[0].shape[1]
         o.forced_uniforms = forced_uniforms.data_ptr() if forced_uniforms is not None else None
@@ -210,8 +238,10 @@ class Runtime:
 
     # decode session (include/detail_hip.h: dtts_gpt_prefill / _decode_step / _decode / _all_finished / _finish), <= 16 rows
     def gpt_prefill(self, refer, refer_lens, texts, seed, sample_ids, max_generate_length=600, top_k=50, top_p=0.8, temperature=0.8,
-                    repetition_penalty=2.0, suppress_eos=False, forced_uniforms=None, forced_codes=None, forced_fill=8193, typical_mass=0.0, token_wgs=0, prompt_codes=None):
+                    repetition_penalty=2.0, suppress_eos=False, forced_uniforms=None, forced_codes=None, forced_fill=8193, typical_mass=0.0, token_wgs=0, prompt_codes=None,
+                    processors=None):
         """conditioning encoder + prefill + first token; returns the latents tensor [B,768,G] the steps fill column by column.
+        processors: as in gpt_generate (the session decodes under them; None / {}: off).
 
         prompt_codes ([B, m] array or a list of B one-dimensional arrays; per-row lengths are an extension, the reference takes a
         rectangle): the acoustic prompt of UnifiedVoice.inference_speech_valle (gpt/model.py:546-579).  The prefill then covers
@@ -237,6 +267,7 @@ class Runtime:
         o.suppress_eos = 1 if suppress_eos else 0
         o.typical_mass = float(typical_mass or 0.0)
         o.token_wgs = int(token_wgs or 0)       # 0: the handle's gpt_token_wgs option; 64 / 32: this session decodes on fewer workgroups (same bits)
+        keep_proc = self._processors(o, processors)      # noqa: F841  (ValueError before any library call; the arrays live to the call's end)
         if prompt is not None:
             o.prompt_codes, o.prompt_lens, o.prompt_stride = prompt[0].ctypes.data_as(_lib.c_int_p), prompt[1].ctypes.data_as(_lib.c_int_p), prompt[0].shape[1]
         o.forced_uniforms = forced_uniforms.data_ptr() if forced_uniforms is not None else None
@@ -1156,6 +1187,31 @@ class Runtime:
                                                    _ptr(uniforms), int(top_k or 0), float(top_p if top_p is not None else 1.0),
                                                    float(temperature), float(repetition_penalty), float(typical_mass or 0.0),
                                                    int(bool(suppress_eos)), out.ctypes.data_as(_lib.c_int_p), self._stream()))
+        return out
+
+    def op_sample_logits_opts(self, logits, histories, fills, prompt_lens, uniforms, top_k=50, top_p=0.8, temperature=0.8,
+                              repetition_penalty=2.0, typical_mass=None, suppress_eos=False, processors=None):
+        """op_sample_logits under HF's remaining processors (dtts_op_sample_logits_opts).  Row r's input_ids are fills[r] fill ids (1)
+        followed by the ORDERED ids histories[r] (a list of R one-dimensional arrays); prompt_lens[r] is HF's prompt length of the
+        row, fill ids included.  The stop token is V - 1.  -> token ids int32 [R]."""
+        _check(logits, "logits"); _check(uniforms, "uniforms")
+        R, V = logits.shape
+        hl = np.array([len(h) for h in histories], np.int32)
+        assert hl.shape == (R,) and len(fills) == R and len(prompt_lens) == R
+        hist = np.zeros((R, max(1, int(hl.max()))), np.int32)
+        for r, h in enumerate(histories):
+            hist[r, :len(h)] = np.asarray(h, np.int32)
+        fl, pl = np.ascontiguousarray(np.asarray(fills, np.int32)), np.ascontiguousarray(np.asarray(prompt_lens, np.int32))
+        o = _lib.DttsGptOptions()
+        self.lib.dtts_gpt_options_init(C.byref(o))
+        o.top_k, o.top_p, o.temperature = int(top_k or 0), float(top_p if top_p is not None else 1.0), float(temperature)
+        o.repetition_penalty, o.typical_mass, o.suppress_eos = float(repetition_penalty), float(typical_mass or 0.0), int(bool(suppress_eos))
+        keep_proc = self._processors(o, processors, vocab=V)      # noqa: F841
+        out = np.zeros((R,), np.int32)
+        self._rc(self.lib.dtts_op_sample_logits_opts(self.h, _ptr(logits), R, V, C.byref(o), hist.ctypes.data_as(_lib.c_int_p), hist.shape[1],
+                                                     hl.ctypes.data_as(_lib.c_int_p), fl.ctypes.data_as(_lib.c_int_p),
+                                                     pl.ctypes.data_as(_lib.c_int_p), _ptr(uniforms), out.ctypes.data_as(_lib.c_int_p),
+                                                     self._stream()))
         return out
 
     def op_philox_normal(self, n, seed, sample_ids, stage, step):

@@ -17,6 +17,7 @@ import torch
 
 from ..config import COND_FREE_K, INFER_DIFFUSION_STEPS, MAX_GENERATE_LENGTH, MEL_MIN, NOISE_SCALE, REPETITION_PENALTY, TEMPERATURE, \
     TOP_P, TORCH_MEL_MAX, TRAINED_DIFFUSION_STEPS, load_config
+from ..gpt.decode_options import validate_decode_options
 from ..gpt.candidates import check_choose, check_num_candidates, expand_sample_ids, rank_candidates
 from ..gpt.prompt import check_prompt_args, prompt_rows
 from ..gpt.model import UnifiedVoice
@@ -314,8 +315,14 @@ class SynthesizerTrn:
     def infer(self, text, text_length, refer, refer_lengths, noise_scale=NOISE_SCALE, *, batch=False, seed=None, sample_ids=None,
               forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False, return_lengths=False,
               stream_vocoder=False, vocoder_chunk=256, wait=True, check_range=True, diffusion_steps=None, sampler="p", eta=0.0,
-              trunk_precision=None, num_candidates=1, choose=None, return_candidates=False, prompt_codes=None):
+              trunk_precision=None, num_candidates=1, choose=None, return_candidates=False, prompt_codes=None, decode_options=None):
         """vqvae/model_24k.py:774-810.  Returns wav [B,1,1024*n_max] (B=1 unless batch=True).
+
+        decode_options: None or a dict of HF generate()'s remaining decode-time keywords, which the reference's inference_speech_*
+        would hand to HF (gpt/decode_options.py: no_repeat_ngram_size, min_length, min_new_tokens, exponential_decay_length_penalty,
+        suppress_tokens, begin_suppress_tokens, min_p, epsilon_cutoff), checked on the host before any launch and served by the device
+        sampler.  None or {}: today's decode, bit for bit.  With num_candidates > 1 every candidate decodes under the options; its
+        score stays the unconstrained model's log-probability.
 
         prompt_codes ([B, m] or a list of B one-dimensional arrays of mel codes, e.g. encode()'s of a prompt mel; not with forced_codes or
         num_candidates > 1): the reference's own composition with line 782 calling UnifiedVoice.inference_speech_valle - stage A continues
@@ -353,6 +360,7 @@ class SynthesizerTrn:
         prec = SynthesizerTrn._check_trunk_precision(self, trunk_precision)
         ncand = check_num_candidates(num_candidates, forced_codes)
         check_prompt_args(prompt_codes, forced_codes, ncand)
+        processors = validate_decode_options(decode_options)
         st = normalize_request(text, text_length, refer, refer_lengths, seed, sample_ids, forced_codes, batch=batch)
         B, rl, texts, seed, sample_ids, forced_codes = st.B, st.rl, st.texts, st.seed, st.sids, st.forced
         if prompt_codes is not None:       # (ValueError on a bad row count or code: before any launch)
@@ -379,6 +387,8 @@ class SynthesizerTrn:
                       repetition_penalty=REPETITION_PENALTY, suppress_eos=suppress_eos)
             if prompt_codes is not None:
                 kw["prompt_codes"] = prompt_codes
+            if processors:
+                kw["processors"] = processors
             a_refer, a_rl, a_texts, a_ids = refer, rl, texts, sample_ids
             if candidates and ncand > 1:                            # HF's num_return_sequences expansion: every row N times
                 a_refer = refer.repeat_interleave(ncand, 0).contiguous()
@@ -450,7 +460,7 @@ class SynthesizerTrn:
     # ------------------------------------------------------------------------------------------------------------
     def infer_stream(self, requests, noise_scale=NOISE_SCALE, *, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False,
                      vocoder_chunk=0, pair_stage_a=False, on_saturation="rerun_fp32", diffusion_steps=None, sampler="p", eta=0.0,
-                     trunk_precision=None):
+                     trunk_precision=None, decode_options=None):
         """Batch server: `infer(..., batch=True)` over a sequence of request batches, software-pipelined over three HIP streams.
 
         requests: iterable of dicts with keys text [B,Lt], text_length [B], refer [B,128,Tr], refer_lengths [B] and optionally seed,
@@ -472,8 +482,11 @@ class SynthesizerTrn:
         "raise": the error leaves the generator (and ends the stream).
 
         diffusion_steps / sampler / eta / trunk_precision: as in infer(), one schedule and one trunk mode for every request of the stream
-        (the option is set around each request's diffusion launches only, on this thread: nothing leaks into other calls)."""
+        (the option is set around each request's diffusion launches only, on this thread: nothing leaks into other calls).
+
+        decode_options: as in infer(), one set for every request of the stream (None or {}: today's decode)."""
         assert on_saturation in ("rerun_fp32", "raise")
+        processors = validate_decode_options(decode_options)
         sched_ts, sampler_id, eta = sampling_args(diffusion_steps, sampler, eta)
         prec = SynthesizerTrn._check_trunk_precision(self, trunk_precision)
         dev = self.device
@@ -488,6 +501,8 @@ class SynthesizerTrn:
         trace = self.stream_trace          # a list: per-request host times and stream events (tools/pipeline_trace.py)
         kw = dict(max_generate_length=max_generate_length, top_k=top_k, top_p=TOP_P, temperature=TEMPERATURE,
                   repetition_penalty=REPETITION_PENALTY, suppress_eos=suppress_eos)
+        if processors:
+            kw["processors"] = processors
         # Stage A here decodes NEXT TO the previous request's diffusion: its sessions of 5 .. 8 rows take the 64-workgroup token kernel
         # (gpt_token_n.hip: the same codes and latents bit for bit, 105 instead of 80 ms alone, but half the CUs for 1.3 x as long:
         # -5 .. -7 ms per pipelined request, profiles/r06_token_wgs.txt); a blocking infer() keeps the 128-workgroup kernel.
@@ -570,13 +585,17 @@ class SynthesizerTrn:
     EMPTY_CODE_FRAMES = 16
 
     def infer_gpt(self, text, text_length, refer, refer_lengths, noise_scale=NOISE_SCALE, *, batch=False, seed=None, sample_ids=None,
-                  forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False, prompt_codes=None):
+                  forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False, prompt_codes=None,
+                  decode_options=None):
         """vqvae/model_24k.py:811-847: GPT codes -> quantizer.decode + vq_ref_enc -> vq_dec -> infer_flowvae (no diffusion).
-        prompt_codes (not with forced_codes): line 819 calls UnifiedVoice.inference_speech_valle, see infer."""
+        prompt_codes (not with forced_codes): line 819 calls UnifiedVoice.inference_speech_valle, see infer.  decode_options: see infer."""
         check_prompt_args(prompt_codes, forced_codes, 1)
+        processors = validate_decode_options(decode_options)
         st = normalize_request(text, text_length, refer, refer_lengths, seed, sample_ids, forced_codes, batch=batch)
         B, rl, seed, sample_ids = st.B, st.rl, st.seed, st.sids
         pkw = {} if prompt_codes is None else dict(prompt_codes=prompt_rows(prompt_codes if batch else prompt_codes[:1], B))
+        if processors:
+            pkw["processors"] = processors
         refer = st.refer.to(self.device, torch.float32).contiguous()
         if st.forced is None:
             codes, ncodes, _ = self.rt.gpt_generate(refer, rl, st.texts, seed, sample_ids, max_generate_length=max_generate_length,

@@ -110,6 +110,23 @@ typedef struct dtts_gpt_options {
     float typical_mass;             /* inference_speech_tortoise(typical_sampling=True, typical_mass): HF TypicalLogitsWarper, applied between
                                      * the repetition penalty and the temperature (gpt/model.py:539); 0 (or 1): off; values outside
                                      * [0, 1] or not finite are rejected */
+    /* ---- HF generate()'s remaining decode-time logits processors (transformers generation/logits_process.py), applied on the device in
+     * the order of GenerationMixin._get_logits_processor: behind the repetition penalty and in front of the typical warper and the
+     * temperature (the first five), behind top-k and top-p (the last two).  HF's input_ids of a row are its fill-id-1 prefix columns,
+     * 8192, an acoustic prompt's codes, a forced prefix (forced_codes: the leading codes >= 0 = input_tokens) and the generated tokens;
+     * its "prompt" is all of that but the generated tokens.  All zero / NULL (dtts_gpt_options_init) = off.
+     * (The block sits in front of token_wgs; struct_size refuses a caller built against the layout without it.) */
+    int no_repeat_ngram_size;       /* NoRepeatNGramLogitsProcessor(n) over the whole of input_ids, fill ids included; 1 .. 16, 0 = off */
+    int min_length;                 /* MinLengthLogitsProcessor: the stop token is -inf while len(input_ids) < min_length (prefix columns count) */
+    int min_new_tokens;             /* MinNewTokensLengthLogitsProcessor: ... while fewer than this many tokens follow the prompt */
+    int exp_decay_start;            /* ExponentialDecayLengthPenalty((start, factor)): once i = len(input_ids) - prompt length - start > 0 the */
+    double exp_decay_factor;        /* stop score s becomes s + |s| * float(factor^i - 1), the power in double as Python's; factor > 1, 0 = off */
+    const int* suppress_tokens;     /* SuppressTokensLogitsProcessor: HOST [n_suppress_tokens] ids in [0, V) that are always -inf, or NULL */
+    int n_suppress_tokens;
+    const int* begin_suppress_tokens;      /* SuppressTokensAtBeginLogitsProcessor: HOST ids that are -inf at the first generated step only */
+    int n_begin_suppress_tokens;
+    float min_p;                    /* MinPLogitsWarper: p < min_p * p_max goes, over the softmax of what top-k and top-p kept; [0, 1], 0 = off */
+    float epsilon_cutoff;           /* EpsilonLogitsWarper: p < epsilon goes (the largest score stays); [0, 1), 0 = off */
     int token_wgs;                  /* workgroups of the persistent decode-token kernel for THIS session of 5 .. 8 rows: 128, 64 or 32 (the same
                                      * codes and latents bit for bit; fewer workgroups decode longer on fewer CUs - what a session that runs
                                      * NEXT TO another request's diffusion should ask for: SynthesizerTrn.infer_stream passes 64); 0 = the
@@ -735,6 +752,21 @@ int dtts_op_sample_logits(dtts_handle* h, const float* logits, int R, int V, con
 int dtts_op_sample_logits_ex(dtts_handle* h, const float* logits, int R, int V, const int* history, int hist_len,
                              const float* uniforms, int top_k, float top_p, float temperature, float repetition_penalty,
                              float typical_mass, int suppress_eos, int* tokens_out, void* stream);
+/* The sampler under a whole option block: opts carries top_k .. typical_mass, suppress_eos and the processors above (max_generate_length,
+ * seeds, ids and pointers other than the two suppress lists are ignored).  Row r's input_ids are fills[r] fill ids (1) followed by the
+ * ORDERED ids history[r][0 .. hist_lens[r]) (HOST, row stride hist_stride, each in [0, V)); prompt_lens[r] is HF's prompt length of the
+ * row, fill ids included (0 .. fills[r] + hist_lens[r]).  The stop token is V - 1.  One token per row, R <= 16. */
+int dtts_op_sample_logits_opts(dtts_handle* h, const float* logits, int R, int V, const dtts_gpt_options* opts, const int* history,
+                               int hist_stride, const int* hist_lens, const int* fills, const int* prompt_lens, const float* uniforms,
+                               int* tokens_out, void* stream);
+/* Host only (no device, no handle): the arithmetic the library applies for the processors above.
+ * dtts_gpt_first_stop_step: min_length and min_new_tokens folded - the first decode step at which the stop token may be drawn by a row
+ * whose input_ids hold input_len ids at step 0 (prefix columns, 8192 and an acoustic prompt's codes included), forced_prefix of whose
+ * first steps are a forced prefix (input_tokens, which HF counts as prompt).
+ * dtts_gpt_decay_multipliers: out[i] = float(factor^i - 1), i = 0 .. n - 1, the power in double; saturated at 1e30, where HF's
+ * multiplier would leave float32 (the stop token is then the only one left; no factor is refused for the length of a call). */
+int dtts_gpt_first_stop_step(int input_len, int forced_prefix, int min_length, int min_new_tokens);
+void dtts_gpt_decay_multipliers(double factor, int n, float* out);
 /* The largest vocabulary the device sampler holds in LDS (host-only, no device needed). */
 int dtts_sampler_max_vocab(void);
 /* Philox normal fill: out[b, 0..n) for (seed, sample_ids[b], stage, step) */
