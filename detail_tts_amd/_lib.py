@@ -40,6 +40,7 @@ class DttsGptOptions(C.Structure):
                 ("no_repeat_ngram_size", C.c_int), ("min_length", C.c_int), ("min_new_tokens", C.c_int), ("exp_decay_start", C.c_int),
                 ("exp_decay_factor", C.c_double), ("suppress_tokens", c_int_p), ("n_suppress_tokens", C.c_int),
                 ("begin_suppress_tokens", c_int_p), ("n_begin_suppress_tokens", C.c_int), ("min_p", C.c_float), ("epsilon_cutoff", C.c_float),
+                ("num_beams", C.c_int), ("length_penalty", C.c_float), ("early_stopping", C.c_int),
                 ("token_wgs", C.c_int), ("prompt_codes", c_int_p), ("prompt_lens", c_int_p), ("prompt_stride", C.c_int)]
 
 
@@ -91,6 +92,12 @@ SIGNATURES = {
                                            C.c_float, C.c_float, C.c_float, C.c_int, c_int_p, C.c_void_p]),
     "dtts_op_sample_logits_opts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DttsGptOptions), c_int_p, C.c_int, c_int_p,
                                              c_int_p, c_int_p, C.c_void_p, c_int_p, C.c_void_p]),
+    "dtts_gpt_beam_generate": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, c_int_p, c_int_p, C.c_int, C.c_int,
+                                         C.POINTER(DttsGptOptions), C.c_int, c_int_p, c_int_p, c_float_p, C.c_void_p]),
+    "dtts_gpt_beam_finish": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p, c_float_p, C.c_void_p]),
+    "dtts_op_beam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DttsGptOptions), C.c_int, c_int_p, C.c_int,
+                                    c_int_p, c_float_p, c_int_p, c_float_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p,
+                                    c_float_p, c_int_p, c_int_p, C.c_void_p]),
     "dtts_gpt_first_stop_step": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "dtts_gpt_decay_multipliers": (None, [C.c_double, C.c_int, C.c_void_p]),
     "dtts_sampler_max_vocab": (C.c_int, []),

@@ -292,6 +292,7 @@ void dtts_gpt_options_init(dtts_gpt_options* o) {
     o->top_p = 0.8f;
     o->temperature = 0.8f;
     o->repetition_penalty = 2.0f;
+    o->length_penalty = 1.0f;
 }
 
 // HF's remaining logits processors: the ranges their constructors accept (0 / NULL = off); NaN fails every range
@@ -310,6 +311,18 @@ static void check_gpt_processors(const dtts_gpt_options* o, int V) {
     DTTS_REQUIRE(o->epsilon_cutoff >= 0.f && o->epsilon_cutoff < 1.f, "options: epsilon_cutoff outside [0, 1) (0 = off)");
 }
 
+// beam search (num_beams 0 / 1 = off): what may not be combined with it is refused here, before any launch
+static void check_gpt_beams(const dtts_gpt_options* o) {
+    DTTS_REQUIRE(o->num_beams >= 0 && o->num_beams <= dtts::BEAM_MAXK, "options: num_beams outside 0 .. 16 (a session holds 16 rows)");
+    DTTS_REQUIRE(o->early_stopping >= 0 && o->early_stopping <= 2, "options: early_stopping is 0 (False), 1 (True) or 2 (\"never\")");
+    DTTS_REQUIRE(o->length_penalty > -INFINITY && o->length_penalty < INFINITY, "options: length_penalty is not finite");
+    if (o->num_beams > 1) {
+        DTTS_REQUIRE(!o->forced_codes, "options: num_beams with forced_codes (input_tokens under beams is not served)");
+        DTTS_REQUIRE(!o->forced_uniforms, "options: num_beams with forced_uniforms (beam search draws nothing)");
+        DTTS_REQUIRE(!(o->typical_mass > 0.f && o->typical_mass < 1.f), "options: num_beams with typical sampling (beam-sample is not served)");
+    }
+}
+
 static void check_gpt_options(const dtts_gpt_options* o) {
     DTTS_REQUIRE(o, "options");
     DTTS_REQUIRE(o->struct_size == sizeof(dtts_gpt_options),
@@ -322,6 +335,7 @@ static void check_gpt_options(const dtts_gpt_options* o) {
     DTTS_REQUIRE(o->temperature > 0.f && o->temperature < INFINITY && o->top_p >= 0.f && o->top_p <= 1.f && o->repetition_penalty > 0.f &&
                      o->repetition_penalty < INFINITY, "options: temperature / top_p / repetition_penalty out of range");
     check_gpt_processors(o, 8194);
+    check_gpt_beams(o);
 }
 
 int dtts_gpt_generate(dtts_handle* h, const float* refer, const int* refer_lens, int Tr, const int* text, const int* text_lens,
@@ -339,6 +353,42 @@ int dtts_gpt_prefill(dtts_handle* h, const float* refer, const int* refer_lens, 
     DTTS_API_BEGIN
     check_gpt_options(opts);
     h->m->gpt_prefill(refer, refer_lens, Tr, text, text_lens, Lt_max, B, *opts, latents_cm, lat_stride, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_gpt_beam_generate(dtts_handle* h, const float* refer, const int* refer_lens, int Tr, const int* text, const int* text_lens,
+                           int Lt_max, int B, const dtts_gpt_options* opts, int nrs, int* seqs_out, int* lens_out, float* scores_out,
+                           void* stream) {
+    DTTS_API_BEGIN
+    check_gpt_options(opts);
+    DTTS_REQUIRE(opts->num_beams > 1, "dtts_gpt_beam_generate: options.num_beams has to be 2 .. 16");
+    DTTS_REQUIRE(nrs >= 1 && nrs <= opts->num_beams, "dtts_gpt_beam_generate: num_return_sequences outside 1 .. num_beams");
+    DTTS_REQUIRE(seqs_out && lens_out && scores_out, "dtts_gpt_beam_generate: null output");
+    h->m->gpt_beam_generate(refer, refer_lens, Tr, text, text_lens, Lt_max, B, *opts, nrs, seqs_out, lens_out, scores_out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_gpt_beam_finish(dtts_handle* h, int nrs, int* seqs_out, int* lens_out, float* scores_out, void* stream) {
+    DTTS_API_BEGIN
+    DTTS_REQUIRE(seqs_out && lens_out && scores_out, "dtts_gpt_beam_finish: null output");
+    h->m->gpt_beam_finish(nrs, seqs_out, lens_out, scores_out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_op_beam_step(dtts_handle* h, const float* logits, int U, int V, const dtts_gpt_options* opts, int step, const int* prompt,
+                      int prompt_len, int* run_seq, float* run_score, int* fin_seq, float* fin_score, int* fin_flag, int* fin_len,
+                      int* unsat, int* done, int* parents, int* tokens, float* cand_score, int* cand_beam, int* cand_tok, void* stream) {
+    DTTS_API_BEGIN
+    DTTS_REQUIRE(opts, "options");
+    DTTS_REQUIRE(opts->struct_size == sizeof(dtts_gpt_options),
+                 "dtts_gpt_options.struct_size does not match this library's layout: start from dtts_gpt_options_init()");
+    DTTS_REQUIRE(opts->repetition_penalty > 0.f && opts->repetition_penalty < INFINITY, "options: repetition_penalty out of range");
+    DTTS_REQUIRE(V >= 2 && V <= dtts::BEAM_V_MAX, "op_beam_step: vocabulary outside 2 .. 12288");
+    check_gpt_processors(opts, V);
+    check_gpt_beams(opts);
+    DTTS_REQUIRE(opts->num_beams >= 1, "op_beam_step: options.num_beams has to be 1 .. 16");
+    h->m->op_beam_step(logits, U, V, *opts, step, prompt, prompt_len, run_seq, run_score, fin_seq, fin_score, fin_flag, fin_len, unsat, done,
+                       parents, tokens, cand_score, cand_beam, cand_tok, (hipStream_t)stream);
     DTTS_API_END(h)
 }
 

@@ -129,6 +129,50 @@ struct SamplerParams {
 void launch_sampler(const SamplerParams& p, hipStream_t s);
 int sampler_max_vocab();          // the largest V launch_sampler admits (from the kernel's LDS budget)
 
+// ---- beam search (gpt_beam.hip): HF GenerationMixin._beam_search, do_sample=False, on the device.  A beam session's rows are U utterances
+// x K beams (row u * K + k).  beam_step_kernel takes the sampler's place behind the logits, beam_reorder_kernel follows it.
+constexpr int BEAM_MAXK = 16;                // beams per utterance at most (= rows of a session)
+constexpr int BEAM_V_MAX = 12288;            // largest vocabulary of the beam step (one row's scores sit in LDS)
+struct BeamParams {
+    const float* parts;       // logits exactly as SamplerParams hands them: partials [slices][U * K][Vs] + bias, or plain rows
+    int slices;
+    const float* bias;
+    int Vs, V, U, K;
+    const unsigned char* seen;     // [U * K][V] ids in the row's input_ids (repetition penalty); maintained by the reorder kernel
+    int* finished;            // [U * K] raised for every row of an utterance that is done (may be null)
+    int eos;
+    GptCtl* ctl;              // step (advanced here), max_steps = max new tokens, the processors' fields, pos_off
+    const float* mel_emb;     // next input embedding of row j: mel_emb[token] + mel_pos[step + pos_off]  (x_next may be null)
+    const float* mel_pos;
+    float* x_next;
+    int C;
+    // the beam state, all DEVICE.  Sequences hold generated tokens only; unwritten positions hold the fill id the host put there.
+    int *run_seq, *fin_seq;   // [U * K][seq_stride]
+    int seq_stride;
+    float *run_score, *fin_score;      // [U * K]: running_beam_scores ([0, -1e9, ...] at the start) / beam_scores (-1e9)
+    int *fin_flag, *fin_len;  // [U * K]: is_sent_finished / generated length of the finished hypothesis
+    int *unsat, *done;        // [U]: is_early_stop_heuristic_unsatisfied (1 at the start) / the utterance's loop has ended
+    int *parents, *tokens;    // [U * K] out: the beam (0 .. K-1) row j continues, and its new token
+    int *last_step, *ident;   // [U] out: the step this launch served (-1: none - over-run or done) / its parents are the identity
+    const float* len_div;     // [max_steps + 1]: float(i ** length_penalty), the power in double as Python evaluates it
+    float length_penalty;
+    int early_stopping;       // 0 False, 1 True, 2 "never"
+    float* cand_score;        // optional [U][2K] out (unit entry): the candidates' accumulated scores, beams and tokens, best first
+    int *cand_beam, *cand_tok;
+};
+void launch_beam_step(const BeamParams& p, hipStream_t s);
+struct BeamReorderParams {
+    float* kv;                // the session's KV cache (GptTokenParams::kv layout); generated columns lp .. lp + step - 1 are moved
+    long long kv_layer, kv_bs;
+    int cap, NL, C;
+    unsigned char* seen;      // [U * K][V]
+    int V, U, K;
+    const GptCtl* ctl;        // lp, hist, hist_stride, hist_n0
+    const int *parents, *tokens, *last_step, *ident;
+    int skip_kv;              // test hook (option gpt_beam_skip_reorder): leave the cache as it is
+};
+void launch_beam_reorder(const BeamReorderParams& p, hipStream_t s);
+
 // ---- one decode token as ONE persistent kernel (gpt_token.hip): 128 resident workgroups, activations exchanged through memory as
 // {value, tag} words.  Replaces the 5-launches-per-layer chain for sessions of <= 8 rows on the GPT-2 shape of the reference config.
 constexpr int GPT_TOKEN_WGS = 128;

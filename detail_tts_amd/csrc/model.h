@@ -138,6 +138,13 @@ struct GptSession {
     int* tok_err = nullptr;
     unsigned* tok_epoch = nullptr;
     int tok_wgs = 128;                 // workgroups of the token kernel for this session (dtts_gpt_options.token_wgs, else option gpt_token_wgs)
+    // beam search (gpt_beam.hip): beam_K > 1 = the rows are B / beam_K utterances x beam_K beams and the beam kernels take the sampler's
+    // place.  The buffers are laid out for every session (their addresses do not depend on K); graphs are dropped when K changes.
+    int beam_K = 0, beam_es = 0;
+    float beam_lp = 1.f;
+    int *b_run_seq = nullptr, *b_fin_seq = nullptr, *b_fin_flag = nullptr, *b_fin_len = nullptr, *b_unsat = nullptr, *b_done = nullptr,
+        *b_parents = nullptr, *b_tokens = nullptr, *b_last_step = nullptr, *b_ident = nullptr;
+    float *b_run_score = nullptr, *b_fin_score = nullptr, *b_len_div = nullptr;
 };
 
 struct ResBlock1W {
@@ -279,6 +286,13 @@ public:
     int gpt_all_finished(hipStream_t s);
     void gpt_finish(int* codes_host, int* ncodes_host, hipStream_t s);
     int gpt_steps() const { return gs_.active ? gs_.steps : 0; }
+    // beam search: B utterances x o.num_beams beams, whole utterances per session; per utterance the best nrs finished hypotheses (HOST)
+    void gpt_beam_generate(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host, int Lt_max,
+                           int B, const dtts_gpt_options& o, int nrs, int* seqs_host, int* lens_host, float* scores_host, hipStream_t s);
+    void gpt_beam_finish(int nrs, int* seqs_host, int* lens_host, float* scores_host, hipStream_t s);
+    void op_beam_step(const float* logits, int U, int V, const dtts_gpt_options& o, int step, const int* prompt_host, int prompt_len,
+                      int* run_seq, float* run_score, int* fin_seq, float* fin_score, int* fin_flag, int* fin_len, int* unsat, int* done,
+                      int* parents, int* tokens, float* cand_score, int* cand_beam, int* cand_tok, hipStream_t s);
     void op_sample_logits(const float* logits, int R, int V, const int* history_host, int hist_len, const float* uniforms, int top_k,
                           float top_p, float temperature, float repetition_penalty, float typical_mass, int suppress_eos, int* tokens_host,
                           hipStream_t s);
@@ -400,6 +414,8 @@ public:
         // test hook: a prompted session's mel stream is [8192, c_1 .. c_m] (no fill id 1 in front, no stop token behind): what a tortoise
         // session holds after m forced decode steps, so that the prefill route can be compared with the step route
         else if (key == "gpt_prompt_raw") opt_prompt_raw_ = value != 0;
+        // test hook: a beam session leaves the KV cache where it is (rows keep their own past instead of their parent's)
+        else if (key == "gpt_beam_skip_reorder") { opt_beam_skip_reorder_ = value != 0; gpt_drop_graphs(); }
         else if (key == "cfg_streams") opt_cfg_streams_ = value < 0 ? 0 : value;
         else if (key == "conv_cols") opt_conv_cols_ = value != 0;
         else if (key == "voc_chain_planes") opt_voc_chain_ = value != 0;
@@ -599,6 +615,10 @@ private:
     int opt_tok_fault_ = 0;               // option "gpt_token_fault"
     int opt_tok_fault_eos_ = 0;           // option "gpt_token_fault_eos"
     bool opt_prompt_raw_ = false;         // option "gpt_prompt_raw"
+    bool opt_beam_skip_reorder_ = false;  // option "gpt_beam_skip_reorder"
+    Arena gpt_beam_in_;                   // the prompt mels of a beam group, one copy per beam row
+    void gpt_beam_launches(const float* parts, int slices, const float* bias, int Vs, hipStream_t s);      // beam step + reorder behind the logits
+    bool gpt_replay_failed(const GptCtl& hctl, hipStream_t s);      // a timed-out token kernel: replay the session on the chain
     // what dtts_gpt_prefill was called with, kept so that a session whose token kernel timed out can be replayed on the chain
     struct GptReplay {
         bool valid = false;

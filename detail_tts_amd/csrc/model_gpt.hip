@@ -306,6 +306,13 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
     DTTS_REQUIRE(o.max_generate_length >= 1 && o.max_generate_length + 1 <= cfg.gpt_max_mel_pos, "max_generate_length");
     DTTS_REQUIRE(!latents_cm || lat_stride >= o.max_generate_length, "latent buffer too small");
     DTTS_REQUIRE(o.sample_ids, "sample_ids");
+    const int beamK = o.num_beams > 1 ? o.num_beams : 0;
+    if (beamK) {
+        DTTS_REQUIRE(beamK <= BEAM_MAXK && B % beamK == 0, "a beam session's rows are whole utterances: B has to be a multiple of num_beams");
+        DTTS_REQUIRE(!o.forced_codes && !o.forced_uniforms, "num_beams with forced_codes / forced_uniforms");
+        DTTS_REQUIRE(cfg.gpt_mel_codes <= BEAM_V_MAX, "num_beams: vocabulary too large for the beam step");
+        latents_cm = nullptr;                        // rows change lineage: no decode-time latents (dtts_gpt_latents on the chosen codes)
+    }
     if (!replaying_) {                               // keep the call's inputs: a timed-out token kernel is replayed on the chain (gpt_finish)
         GptReplay& r = replay_;
         r.valid = false;
@@ -358,6 +365,7 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
     const size_t need = sizeof(float) * ((size_t)NL * kv_layer + (size_t)B * (4 * C + cfg.gpt_heads * 8 * ATT_REC) + (size_t)2 * B * GEMV_PART_FLOATS + 2 * 64 * GEMV_MAXB * 2) +
                         (size_t)B * V + sizeof(int) * ((size_t)2 * B * G + 64) + sizeof(GptCtl) + 64 * 256 +
                         sizeof(int) * (size_t)B * cap + (size_t)V + sizeof(float) * ((size_t)G + 1) + 4 * 256 +
+                        sizeof(int) * ((size_t)2 * B * G + 8 * GEMV_MAXB) + sizeof(float) * ((size_t)G + 1 + 2 * GEMV_MAXB) + 16 * 256 +
                         (tok_ok_ && B <= GPT_TOKEN_ROWS ? sizeof(unsigned long long) * GPT_TOKEN_XCH_WORDS + sizeof(float) * GPT_TOKEN_ROWS * GPT_TOKEN_VS + 1024 : 0);
     if (need > gpt_state_.capacity() || gs_.B != B || gs_.cap != cap || gs_.G != G) {
         gpt_drop_graphs();
@@ -394,8 +402,20 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
             DTTS_CHECK_HIP(hipMemcpyAsync(n.tok_err, init, sizeof(init), hipMemcpyHostToDevice, s));
             DTTS_CHECK_HIP(hipStreamSynchronize(s));
         }
+        // the beam state comes LAST: every buffer the sampled decode uses keeps the offset it had without it
+        n.b_run_seq = gpt_state_.i32((size_t)B * G);
+        n.b_fin_seq = gpt_state_.i32((size_t)B * G);
+        n.b_fin_flag = gpt_state_.i32(GEMV_MAXB); n.b_fin_len = gpt_state_.i32(GEMV_MAXB); n.b_unsat = gpt_state_.i32(GEMV_MAXB);
+        n.b_done = gpt_state_.i32(GEMV_MAXB); n.b_parents = gpt_state_.i32(GEMV_MAXB); n.b_tokens = gpt_state_.i32(GEMV_MAXB);
+        n.b_last_step = gpt_state_.i32(GEMV_MAXB); n.b_ident = gpt_state_.i32(GEMV_MAXB);
+        n.b_run_score = gpt_state_.f32(GEMV_MAXB); n.b_fin_score = gpt_state_.f32(GEMV_MAXB);
+        n.b_len_div = gpt_state_.f32((size_t)G + 1);
         gs_ = n;
     }
+    if (gs_.beam_K != beamK) gpt_drop_graphs();      // (the captured steps hold the sampler or the beam kernels)
+    gs_.beam_K = beamK;
+    gs_.beam_lp = o.length_penalty;
+    gs_.beam_es = o.early_stopping;
     gs_.kv_bs = kv_bs;
     gs_.kv_layer = kv_layer;
     gs_.steps = 0;
@@ -492,6 +512,21 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
     {   // rows that finish early are padded with 8193 (HF pad_token_id)
         std::vector<int> pad((size_t)B * G, 8193);
         DTTS_CHECK_HIP(hipMemcpyAsync(gs_.codes, pad.data(), sizeof(int) * pad.size(), hipMemcpyHostToDevice, s));
+        std::vector<float> rs0(GEMV_MAXB, -1.0e9f), fs0(GEMV_MAXB, -1.0e9f), ld0((size_t)G + 1, 1.f);
+        std::vector<int> zero(GEMV_MAXB, 0), one(GEMV_MAXB, 1), minus(GEMV_MAXB, -1);
+        if (beamK) {                                 // HF's initial beam state: running scores [0, -1e9, ...], an empty finished set
+            for (int b = 0; b < B; b += beamK) rs0[b] = 0.f;
+            for (int i = 0; i <= G; ++i) ld0[i] = (float)std::pow((double)i, (double)o.length_penalty);     // Python's int ** float, rounded once
+            DTTS_CHECK_HIP(hipMemcpyAsync(gs_.b_run_seq, pad.data(), sizeof(int) * pad.size(), hipMemcpyHostToDevice, s));
+            DTTS_CHECK_HIP(hipMemcpyAsync(gs_.b_fin_seq, pad.data(), sizeof(int) * pad.size(), hipMemcpyHostToDevice, s));
+            DTTS_CHECK_HIP(hipMemcpyAsync(gs_.b_run_score, rs0.data(), sizeof(float) * GEMV_MAXB, hipMemcpyHostToDevice, s));
+            DTTS_CHECK_HIP(hipMemcpyAsync(gs_.b_fin_score, fs0.data(), sizeof(float) * GEMV_MAXB, hipMemcpyHostToDevice, s));
+            DTTS_CHECK_HIP(hipMemcpyAsync(gs_.b_len_div, ld0.data(), sizeof(float) * ld0.size(), hipMemcpyHostToDevice, s));
+            for (int* z : {gs_.b_fin_flag, gs_.b_fin_len, gs_.b_done, gs_.b_parents, gs_.b_tokens, gs_.b_ident})
+                DTTS_CHECK_HIP(hipMemcpyAsync(z, zero.data(), sizeof(int) * GEMV_MAXB, hipMemcpyHostToDevice, s));
+            DTTS_CHECK_HIP(hipMemcpyAsync(gs_.b_unsat, one.data(), sizeof(int) * GEMV_MAXB, hipMemcpyHostToDevice, s));
+            DTTS_CHECK_HIP(hipMemcpyAsync(gs_.b_last_step, minus.data(), sizeof(int) * GEMV_MAXB, hipMemcpyHostToDevice, s));
+        }
         DTTS_CHECK_HIP(hipStreamSynchronize(s));          // host temporaries (ids, pad, forced codes) are consumed
     }
     // ---- prefill over [cond | text | start_mel] or [cond | text | 1, start_mel, prompt]
@@ -513,6 +548,10 @@ void Model::gpt_head_and_sample(hipStream_t s) {
     in.x = gs_.lat;
     in.x_stride = C;
     launch_gemv_block(GP_PLAIN, mel_head_.w, C, VP, in, B, gs_.part, s);
+    if (gs_.beam_K) {
+        gpt_beam_launches(gs_.part, gemv_block_slices(C, VP), mel_head_.b, VP, s);
+        return;
+    }
     SamplerParams sp;
     sp.parts = gs_.part;
     sp.slices = gemv_block_slices(C, VP);
@@ -531,6 +570,33 @@ void Model::gpt_head_and_sample(hipStream_t s) {
     sp.x_next = gs_.y;
     sp.C = C;
     launch_sampler(sp, s);
+}
+
+// Beam session: beam_step_kernel in the sampler's place (same logits, same control block), then beam_reorder_kernel.  Fixed arguments:
+// capturable like the sampler.
+void Model::gpt_beam_launches(const float* parts, int slices, const float* bias, int Vs, hipStream_t s) {
+    const int K = gs_.beam_K, U = gs_.B / K;
+    BeamParams p{};
+    p.parts = parts; p.slices = slices; p.bias = bias; p.Vs = Vs;
+    p.V = cfg.gpt_mel_codes; p.U = U; p.K = K;
+    p.seen = gs_.seen; p.finished = gs_.finished; p.eos = 8193; p.ctl = gs_.ctl;
+    p.mel_emb = mel_emb_; p.mel_pos = mel_pos_; p.x_next = gs_.y; p.C = cfg.gpt_dim;
+    p.run_seq = gs_.b_run_seq; p.fin_seq = gs_.b_fin_seq; p.seq_stride = gs_.G;
+    p.run_score = gs_.b_run_score; p.fin_score = gs_.b_fin_score; p.fin_flag = gs_.b_fin_flag; p.fin_len = gs_.b_fin_len;
+    p.unsat = gs_.b_unsat; p.done = gs_.b_done; p.parents = gs_.b_parents; p.tokens = gs_.b_tokens;
+    p.last_step = gs_.b_last_step; p.ident = gs_.b_ident; p.len_div = gs_.b_len_div;
+    p.length_penalty = gs_.beam_lp; p.early_stopping = gs_.beam_es;
+    {
+        ProfScope ps("beam_step", 0.0, 0.0, s);
+        launch_beam_step(p, s);
+    }
+    BeamReorderParams r{};
+    r.kv = gs_.kv; r.kv_layer = gs_.kv_layer; r.kv_bs = gs_.kv_bs; r.cap = gs_.cap; r.NL = (int)gpt_layers_.size(); r.C = cfg.gpt_dim;
+    r.seen = gs_.seen; r.V = cfg.gpt_mel_codes; r.U = U; r.K = K; r.ctl = gs_.ctl;
+    r.parents = gs_.b_parents; r.tokens = gs_.b_tokens; r.last_step = gs_.b_last_step; r.ident = gs_.b_ident;
+    r.skip_kv = opt_beam_skip_reorder_ ? 1 : 0;
+    ProfScope ps("beam_reorder", 0.0, 0.0, s);
+    launch_beam_reorder(r, s);
 }
 
 // One token for every row of the session: 5 launches per layer + final LayerNorms + mel_head + sampler, all with fixed arguments
@@ -575,6 +641,10 @@ void Model::gpt_step_launches(hipStream_t s) {
         {
             ProfScope ps("gpt_token", 0.0, 0.0, s);
             launch_gpt_token(p, s);
+        }
+        if (gs_.beam_K) {
+            gpt_beam_launches(gs_.logits, 1, nullptr, GPT_TOKEN_VS, s);
+            return;
         }
         SamplerParams sp;
         sp.parts = gs_.logits;
@@ -739,9 +809,64 @@ int Model::gpt_all_finished(hipStream_t s) {
     return std::all_of(fin, fin + gs_.B, [](int f) { return f != 0; }) ? 1 : 0;
 }
 
+// A session whose persistent token kernel raised its error flag is replayed from its prefill on the launch-per-GEMV chain; the caller
+// then reads the results again.  hctl: the failed session's control block.
+bool Model::gpt_replay_failed(const GptCtl& hctl, hipStream_t s) {
+    const int B = gs_.B, G = gs_.G;
+    // An exchange poll of the persistent token kernel gave up (its 128 workgroups were not all resident: CU mask, partition mode,
+    // another process holding CUs).  The handle leaves the token kernel for good and THIS session is replayed from its prefill on
+    // the launch-per-GEMV chain - same sampler, same Philox draws, so the codes are the ones the chain would have produced.
+    // Did the FAILED session look finished?  Once the kernel is dead the sampler draws from stale logits, so rows may have drawn the
+    // stop token spuriously and the caller's decode loop (gpt_all_finished) stopped on that: the replay must then go on past the
+    // failed session's step count until the chain's own rows have finished (silently truncated audio otherwise).
+    int fin[GEMV_MAXB];
+    DTTS_CHECK_HIP(hipMemcpyAsync(fin, gs_.finished, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+    DTTS_CHECK_HIP(hipMemsetAsync(gs_.tok_err, 0, sizeof(int), s));
+    DTTS_CHECK_HIP(hipStreamSynchronize(s));
+    const bool failed_looked_finished = std::all_of(fin, fin + B, [](int f) { return f != 0; });
+    gs_.active = false;
+    tok_failed_ = true;
+    gpt_drop_graphs();
+    int steps = gs_.steps;
+    for (int b = 0; b < B; ++b) steps = std::max(steps, std::min(hctl.step[b], G));
+    fprintf(stderr, "[detail_hip] persistent decode kernel: an activation exchange timed out; replaying %d tokens on the launch-per-GEMV chain "
+                    "(this handle stays on the chain)\n", steps);
+    DTTS_REQUIRE(replay_.valid && !replaying_, "persistent decode kernel: an activation exchange timed out and the session cannot be replayed; "
+                                               "set DTTS_GPT_TOKEN_KERNEL=0");
+    GptReplay& r = replay_;
+    dtts_gpt_options o = r.o;
+    o.sample_ids = r.sample_ids.data();
+    o.forced_codes = r.forced_codes.empty() ? nullptr : r.forced_codes.data();
+    o.row_seeds = r.row_seeds.empty() ? nullptr : r.row_seeds.data();
+    if (o.prompt_codes) { o.prompt_codes = r.prompt_codes.data(); o.prompt_lens = r.prompt_lens.data(); }
+    o.suppress_tokens = r.suppress.empty() ? nullptr : r.suppress.data();
+    o.begin_suppress_tokens = r.begin_suppress.empty() ? nullptr : r.begin_suppress.data();
+    replaying_ = true;
+    try {
+        gpt_replay_.reset();
+        const float* refer = gpt_replay_.f32((size_t)r.B * cfg.mel_channels * r.Tr);
+        gpt_prefill(refer, r.has_refer_lens ? r.refer_lens.data() : nullptr, r.Tr, r.text.data(), r.has_text_lens ? r.text_lens.data() : nullptr,
+                    r.Lt_max, r.B, o, r.latents_cm, r.lat_stride, s);
+        for (int i = 1; i < steps; ++i) gpt_step_launches(s);
+        gs_.steps = steps;
+        if (!o.suppress_eos && failed_looked_finished)
+            while (gs_.steps < G && !gpt_all_finished(s)) {
+                const int n = std::min(16, G - gs_.steps);
+                for (int i = 0; i < n; ++i) gpt_step_launches(s);
+                gs_.steps += n;
+            }
+    } catch (...) {
+        replaying_ = false;
+        throw;
+    }
+    replaying_ = false;
+    return true;
+}
+
 // results: codes include the stop token; rows that finished early are padded with 8193 (HF pad_token_id).  Synchronises.
 void Model::gpt_finish(int* codes_host, int* ncodes_host, hipStream_t s) {
     DTTS_REQUIRE(gs_.active, "dtts_gpt_finish: no session");
+    DTTS_REQUIRE(!gs_.beam_K, "dtts_gpt_finish: a beam session's results are hypotheses and scores: call dtts_gpt_beam_finish");
     const int B = gs_.B, G = gs_.G, Ga = gs_.G;
     std::vector<int> hc((size_t)B * Ga, 8193);
     GptCtl hctl;
@@ -752,54 +877,7 @@ void Model::gpt_finish(int* codes_host, int* ncodes_host, hipStream_t s) {
     int tok_err = 0;
     if (gs_.tok_err) DTTS_CHECK_HIP(hipMemcpyAsync(&tok_err, gs_.tok_err, sizeof(int), hipMemcpyDeviceToHost, s));
     DTTS_CHECK_HIP(hipStreamSynchronize(s));
-    if (tok_err) {
-        // An exchange poll of the persistent token kernel gave up (its 128 workgroups were not all resident: CU mask, partition mode,
-        // another process holding CUs).  The handle leaves the token kernel for good and THIS session is replayed from its prefill on
-        // the launch-per-GEMV chain - same sampler, same Philox draws, so the codes are the ones the chain would have produced.
-        // Did the FAILED session look finished?  Once the kernel is dead the sampler draws from stale logits, so rows may have drawn the
-        // stop token spuriously and the caller's decode loop (gpt_all_finished) stopped on that: the replay must then go on past the
-        // failed session's step count until the chain's own rows have finished (silently truncated audio otherwise).
-        int fin[GEMV_MAXB];
-        DTTS_CHECK_HIP(hipMemcpyAsync(fin, gs_.finished, sizeof(int) * B, hipMemcpyDeviceToHost, s));
-        DTTS_CHECK_HIP(hipMemsetAsync(gs_.tok_err, 0, sizeof(int), s));
-        DTTS_CHECK_HIP(hipStreamSynchronize(s));
-        const bool failed_looked_finished = std::all_of(fin, fin + B, [](int f) { return f != 0; });
-        gs_.active = false;
-        tok_failed_ = true;
-        gpt_drop_graphs();
-        int steps = gs_.steps;
-        for (int b = 0; b < B; ++b) steps = std::max(steps, std::min(hctl.step[b], G));
-        fprintf(stderr, "[detail_hip] persistent decode kernel: an activation exchange timed out; replaying %d tokens on the launch-per-GEMV chain "
-                        "(this handle stays on the chain)\n", steps);
-        DTTS_REQUIRE(replay_.valid && !replaying_, "persistent decode kernel: an activation exchange timed out and the session cannot be replayed; "
-                                                   "set DTTS_GPT_TOKEN_KERNEL=0");
-        GptReplay& r = replay_;
-        dtts_gpt_options o = r.o;
-        o.sample_ids = r.sample_ids.data();
-        o.forced_codes = r.forced_codes.empty() ? nullptr : r.forced_codes.data();
-        o.row_seeds = r.row_seeds.empty() ? nullptr : r.row_seeds.data();
-        if (o.prompt_codes) { o.prompt_codes = r.prompt_codes.data(); o.prompt_lens = r.prompt_lens.data(); }
-        o.suppress_tokens = r.suppress.empty() ? nullptr : r.suppress.data();
-        o.begin_suppress_tokens = r.begin_suppress.empty() ? nullptr : r.begin_suppress.data();
-        replaying_ = true;
-        try {
-            gpt_replay_.reset();
-            const float* refer = gpt_replay_.f32((size_t)r.B * cfg.mel_channels * r.Tr);
-            gpt_prefill(refer, r.has_refer_lens ? r.refer_lens.data() : nullptr, r.Tr, r.text.data(), r.has_text_lens ? r.text_lens.data() : nullptr,
-                        r.Lt_max, r.B, o, r.latents_cm, r.lat_stride, s);
-            for (int i = 1; i < steps; ++i) gpt_step_launches(s);
-            gs_.steps = steps;
-            if (!o.suppress_eos && failed_looked_finished)
-                while (gs_.steps < G && !gpt_all_finished(s)) {
-                    const int n = std::min(16, G - gs_.steps);
-                    for (int i = 0; i < n; ++i) gpt_step_launches(s);
-                    gs_.steps += n;
-                }
-        } catch (...) {
-            replaying_ = false;
-            throw;
-        }
-        replaying_ = false;
+    if (tok_err && gpt_replay_failed(hctl, s)) {
         DTTS_CHECK_HIP(hipMemcpyAsync(hc.data(), gs_.codes, sizeof(int) * hc.size(), hipMemcpyDeviceToHost, s));
         DTTS_CHECK_HIP(hipMemcpyAsync(&hctl, gs_.ctl, sizeof(GptCtl), hipMemcpyDeviceToHost, s));
         DTTS_CHECK_HIP(hipStreamSynchronize(s));
@@ -824,6 +902,7 @@ void Model::gpt_generate(const float* refer, const int* refer_lens_host, int Tr,
                          int lat_stride, hipStream_t s) {
     DTTS_REQUIRE(B >= 1, "gpt batch");
     DTTS_REQUIRE(o.sample_ids, "sample_ids");
+    DTTS_REQUIRE(o.num_beams <= 1, "dtts_gpt_generate: num_beams > 1 returns hypotheses and scores: call dtts_gpt_beam_generate");
     const int C = cfg.gpt_dim, G = o.max_generate_length, chunk = gpt_graph_chunk();
     for (int g0 = 0; g0 < B; g0 += GEMV_MAXB) {
         const int nb = std::min(GEMV_MAXB, B - g0);
@@ -843,6 +922,185 @@ void Model::gpt_generate(const float* refer, const int* refer_lens_host, int Tr,
         }
         gpt_finish(codes_host + (size_t)g0 * G, ncodes_host + g0, s);
     }
+}
+
+// results of a beam session: per utterance the best nrs finished hypotheses in score order (HF: sequences[:, :num_return_sequences]),
+// their generated lengths and sequences_scores.  Synchronises; ends the session.
+void Model::gpt_beam_finish(int nrs, int* seqs_host, int* lens_host, float* scores_host, hipStream_t s) {
+    DTTS_REQUIRE(gs_.active && gs_.beam_K > 1, "dtts_gpt_beam_finish: no beam session");
+    const int B = gs_.B, G = gs_.G, K = gs_.beam_K, U = B / K;
+    DTTS_REQUIRE(nrs >= 1 && nrs <= K, "dtts_gpt_beam_finish: num_return_sequences outside 1 .. num_beams");
+    std::vector<int> hseq((size_t)B * G), hlen(GEMV_MAXB);
+    std::vector<float> hsc(GEMV_MAXB);
+    GptCtl hctl;
+    int tok_err = 0;
+    auto fetch = [&]() {
+        DTTS_CHECK_HIP(hipMemcpyAsync(hseq.data(), gs_.b_fin_seq, sizeof(int) * hseq.size(), hipMemcpyDeviceToHost, s));
+        DTTS_CHECK_HIP(hipMemcpyAsync(hlen.data(), gs_.b_fin_len, sizeof(int) * GEMV_MAXB, hipMemcpyDeviceToHost, s));
+        DTTS_CHECK_HIP(hipMemcpyAsync(hsc.data(), gs_.b_fin_score, sizeof(float) * GEMV_MAXB, hipMemcpyDeviceToHost, s));
+        DTTS_CHECK_HIP(hipMemcpyAsync(&hctl, gs_.ctl, sizeof(GptCtl), hipMemcpyDeviceToHost, s));
+        DTTS_CHECK_HIP(hipStreamSynchronize(s));
+    };
+    if (gs_.tok_err) DTTS_CHECK_HIP(hipMemcpyAsync(&tok_err, gs_.tok_err, sizeof(int), hipMemcpyDeviceToHost, s));
+    fetch();
+    if (tok_err && gpt_replay_failed(hctl, s)) fetch();      // (the replay record carries the beam fields: still a beam session)
+    for (int u = 0; u < U; ++u)
+        for (int j = 0; j < nrs; ++j) {
+            const int row = u * K + j;
+            const size_t o = (size_t)u * nrs + j;
+            lens_host[o] = hlen[row];
+            scores_host[o] = hsc[row];
+            for (int t = 0; t < G; ++t) seqs_host[o * G + t] = t < hlen[row] ? hseq[(size_t)row * G + t] : 8193;
+        }
+    gs_.active = false;
+}
+
+// dtts_gpt_generate under num_beams = K: every utterance becomes K replica rows (HF's repeat_interleave); a group is floor(16 / K) whole
+// utterances.  The K prefills of an utterance are computed K times (sharing them is a follow-up).
+void Model::gpt_beam_generate(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host,
+                              int Lt_max, int B, const dtts_gpt_options& o, int nrs, int* seqs_host, int* lens_host, float* scores_host,
+                              hipStream_t s) {
+    DTTS_REQUIRE(B >= 1, "gpt batch");
+    const int K = o.num_beams, G = o.max_generate_length, chunk = gpt_graph_chunk();
+    DTTS_REQUIRE(K > 1 && K <= BEAM_MAXK && nrs >= 1 && nrs <= K, "gpt_beam_generate: num_beams 2 .. 16, num_return_sequences 1 .. num_beams");
+    DTTS_REQUIRE(refer && text_host && Lt_max >= 0 && Tr >= 1, "gpt_beam_generate: operands");
+    const int per = GEMV_MAXB / K;
+    const size_t mel = (size_t)cfg.mel_channels * Tr;
+    gpt_beam_in_.ensure(sizeof(float) * mel * GEMV_MAXB + 4096);
+    for (int g0 = 0; g0 < B; g0 += per) {
+        const int nu = std::min(per, B - g0), R = nu * K;
+        gpt_beam_in_.reset();
+        float* rf = gpt_beam_in_.f32(mel * R);
+        std::vector<int> rl(R), tx((size_t)R * std::max(Lt_max, 1), 0), tl(R), sid(R), pc, pl;
+        if (o.prompt_codes) { pc.assign((size_t)R * std::max(o.prompt_stride, 1), 0); pl.assign(R, 0); }
+        for (int r = 0; r < R; ++r) {
+            const int b = g0 + r / K;
+            DTTS_CHECK_HIP(hipMemcpyAsync(rf + mel * r, refer + mel * b, sizeof(float) * mel, hipMemcpyDeviceToDevice, s));
+            rl[r] = refer_lens_host ? refer_lens_host[b] : Tr;
+            tl[r] = text_lens_host ? text_lens_host[b] : Lt_max;
+            std::copy(text_host + (size_t)b * Lt_max, text_host + (size_t)(b + 1) * Lt_max, tx.begin() + (size_t)r * Lt_max);
+            sid[r] = o.sample_ids ? o.sample_ids[b] : 0;
+            if (o.prompt_codes) {
+                pl[r] = o.prompt_lens[b];
+                std::copy(o.prompt_codes + (size_t)b * o.prompt_stride, o.prompt_codes + (size_t)(b + 1) * o.prompt_stride,
+                          pc.begin() + (size_t)r * o.prompt_stride);
+            }
+        }
+        dtts_gpt_options og = o;
+        og.sample_ids = sid.data();
+        og.row_seeds = nullptr;
+        if (o.prompt_codes) { og.prompt_codes = pc.data(); og.prompt_lens = pl.data(); }
+        gpt_prefill(rf, rl.data(), Tr, tx.data(), tl.data(), Lt_max, R, og, nullptr, 0, s);
+        while (gs_.steps < G) {
+            if (gpt_all_finished(s)) break;
+            gpt_decode(chunk, s);
+        }
+        gpt_beam_finish(nrs, seqs_host + (size_t)g0 * nrs * G, lens_host + (size_t)g0 * nrs, scores_host + (size_t)g0 * nrs, s);
+    }
+}
+
+// unit entry: ONE beam step on given logits, the state handed in and out on the host (tests/test_gpu_beam.py)
+void Model::op_beam_step(const float* logits, int U, int V, const dtts_gpt_options& o, int step, const int* prompt_host, int prompt_len,
+                         int* run_seq, float* run_score, int* fin_seq, float* fin_score, int* fin_flag, int* fin_len, int* unsat, int* done,
+                         int* parents, int* tokens, float* cand_score, int* cand_beam, int* cand_tok, hipStream_t s) {
+    const int K = o.num_beams, G = o.max_generate_length, R = U * K, n = o.no_repeat_ngram_size;
+    DTTS_REQUIRE(K >= 1 && K <= BEAM_MAXK && U >= 1 && R <= GEMV_MAXB, "op_beam_step: 1 .. 16 beams, at most 16 rows");
+    DTTS_REQUIRE(V >= 2 && V <= BEAM_V_MAX && G >= 1 && step >= 0 && step < G && prompt_len >= 0, "op_beam_step: V, max_generate_length, step");
+    DTTS_REQUIRE(logits && run_seq && run_score && fin_seq && fin_score && fin_flag && fin_len && unsat && done && parents && tokens &&
+                     cand_score && cand_beam && cand_tok && (prompt_host || prompt_len == 0), "op_beam_step: null argument");
+    DTTS_REQUIRE(n >= 0 && n <= SAMP_NGRAM_MAX, "no_repeat_ngram_size outside 0 .. 16");
+    const int hs = prompt_len + G;
+    std::vector<unsigned char> seen((size_t)R * V, 0);
+    std::vector<int> hist((size_t)R * hs, 0);
+    GptCtl c;
+    std::memset(&c, 0, sizeof(c));
+    for (int r = 0; r < R; ++r) {
+        int* h = hist.data() + (size_t)r * hs;
+        for (int j = 0; j < prompt_len; ++j) h[j] = prompt_host[(size_t)(r / K) * prompt_len + j];
+        for (int j = 0; j < step; ++j) h[prompt_len + j] = run_seq[(size_t)r * G + j];
+        for (int j = 0; j < prompt_len + step; ++j) {
+            DTTS_REQUIRE(h[j] >= 0 && h[j] < V, "op_beam_step: id outside the vocabulary");
+            seen[(size_t)r * V + h[j]] = 1;
+        }
+        c.step[r] = step;
+        c.hist_n0[r] = prompt_len;
+        c.stop_from[r] = gpt_first_stop_step(prompt_len, 0, o.min_length, o.min_new_tokens);
+        c.decay_off[r] = o.exp_decay_start;
+    }
+    std::vector<float> ld((size_t)G + 1);
+    for (int i = 0; i <= G; ++i) ld[i] = (float)std::pow((double)i, (double)o.length_penalty);
+    std::vector<unsigned char> mask0;
+    std::vector<float> decay0;
+    const size_t ni = (size_t)2 * R * G + (size_t)R * hs + 8 * GEMV_MAXB + 2 * GEMV_MAXB * 2, nf = (size_t)G + 1 + 2 * GEMV_MAXB + 2 * GEMV_MAXB + G + 1;
+    ws().ensure((size_t)R * V + (size_t)V + sizeof(int) * ni + sizeof(float) * nf + sizeof(GptCtl) + 40 * 256);
+    unsigned char* d_seen = static_cast<unsigned char*>(ws().raw((size_t)R * V));
+    unsigned char* d_mask = static_cast<unsigned char*>(ws().raw((size_t)V));
+    int* d_hist = ws().i32((size_t)R * hs);
+    int *d_rs = ws().i32((size_t)R * G), *d_fs = ws().i32((size_t)R * G);
+    int *d_flag = ws().i32(GEMV_MAXB), *d_len = ws().i32(GEMV_MAXB), *d_unsat = ws().i32(GEMV_MAXB), *d_done = ws().i32(GEMV_MAXB);
+    int *d_par = ws().i32(GEMV_MAXB), *d_tok = ws().i32(GEMV_MAXB), *d_last = ws().i32(GEMV_MAXB), *d_ident = ws().i32(GEMV_MAXB);
+    int *d_cb = ws().i32(2 * GEMV_MAXB), *d_ct = ws().i32(2 * GEMV_MAXB);
+    float *d_rsc = ws().f32(GEMV_MAXB), *d_fsc = ws().f32(GEMV_MAXB), *d_ld = ws().f32((size_t)G + 1), *d_cs = ws().f32(2 * GEMV_MAXB);
+    float* d_decay = ws().f32((size_t)G + 1);
+    GptCtl* dctl = static_cast<GptCtl*>(ws().raw(sizeof(GptCtl)));
+    c.repetition_penalty = o.repetition_penalty;
+    c.suppress_eos = o.suppress_eos;
+    c.max_steps = G;
+    c.ngram = n;
+    c.hist = n > 0 ? d_hist : nullptr;
+    c.hist_stride = hs;
+    if (processors_mask_on(o)) {
+        mask0 = processor_token_mask(o, V);
+        c.tok_mask = d_mask;
+        DTTS_CHECK_HIP(hipMemcpyAsync(d_mask, mask0.data(), mask0.size(), hipMemcpyHostToDevice, s));
+    }
+    if (o.exp_decay_factor > 0.0) {
+        decay0 = processor_decay_table(o.exp_decay_factor, G + 1);
+        c.decay_mul = d_decay;
+        c.decay_n = G + 1;
+        DTTS_CHECK_HIP(hipMemcpyAsync(d_decay, decay0.data(), sizeof(float) * decay0.size(), hipMemcpyHostToDevice, s));
+    }
+    auto up = [&](void* d, const void* h, size_t bytes) { DTTS_CHECK_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s)); };
+    auto down = [&](void* h, const void* d, size_t bytes) { DTTS_CHECK_HIP(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s)); };
+    up(dctl, &c, sizeof(c));
+    up(d_seen, seen.data(), seen.size());
+    up(d_hist, hist.data(), sizeof(int) * hist.size());
+    up(d_rs, run_seq, sizeof(int) * (size_t)R * G);
+    up(d_fs, fin_seq, sizeof(int) * (size_t)R * G);
+    up(d_flag, fin_flag, sizeof(int) * R);
+    up(d_len, fin_len, sizeof(int) * R);
+    up(d_unsat, unsat, sizeof(int) * U);
+    up(d_done, done, sizeof(int) * U);
+    up(d_rsc, run_score, sizeof(float) * R);
+    up(d_fsc, fin_score, sizeof(float) * R);
+    up(d_ld, ld.data(), sizeof(float) * ld.size());
+    DTTS_CHECK_HIP(hipMemsetAsync(d_par, 0, sizeof(int) * GEMV_MAXB, s));
+    DTTS_CHECK_HIP(hipMemsetAsync(d_tok, 0, sizeof(int) * GEMV_MAXB, s));
+    DTTS_CHECK_HIP(hipMemsetAsync(d_cs, 0, sizeof(float) * 2 * GEMV_MAXB, s));
+    DTTS_CHECK_HIP(hipMemsetAsync(d_cb, 0, sizeof(int) * 2 * GEMV_MAXB, s));
+    DTTS_CHECK_HIP(hipMemsetAsync(d_ct, 0, sizeof(int) * 2 * GEMV_MAXB, s));
+    BeamParams p{};
+    p.parts = logits; p.slices = 1; p.bias = nullptr; p.Vs = V; p.V = V; p.U = U; p.K = K;
+    p.seen = d_seen; p.finished = nullptr; p.eos = V - 1; p.ctl = dctl;
+    p.run_seq = d_rs; p.fin_seq = d_fs; p.seq_stride = G; p.run_score = d_rsc; p.fin_score = d_fsc; p.fin_flag = d_flag; p.fin_len = d_len;
+    p.unsat = d_unsat; p.done = d_done; p.parents = d_par; p.tokens = d_tok; p.last_step = d_last; p.ident = d_ident; p.len_div = d_ld;
+    p.length_penalty = o.length_penalty; p.early_stopping = o.early_stopping;
+    p.cand_score = d_cs; p.cand_beam = d_cb; p.cand_tok = d_ct;
+    launch_beam_step(p, s);
+    down(run_seq, d_rs, sizeof(int) * (size_t)R * G);
+    down(fin_seq, d_fs, sizeof(int) * (size_t)R * G);
+    down(fin_flag, d_flag, sizeof(int) * R);
+    down(fin_len, d_len, sizeof(int) * R);
+    down(unsat, d_unsat, sizeof(int) * U);
+    down(done, d_done, sizeof(int) * U);
+    down(run_score, d_rsc, sizeof(float) * R);
+    down(fin_score, d_fsc, sizeof(float) * R);
+    down(parents, d_par, sizeof(int) * R);
+    down(tokens, d_tok, sizeof(int) * R);
+    down(cand_score, d_cs, sizeof(float) * (size_t)U * 2 * K);
+    down(cand_beam, d_cb, sizeof(int) * (size_t)U * 2 * K);
+    down(cand_tok, d_ct, sizeof(int) * (size_t)U * 2 * K);
+    DTTS_CHECK_HIP(hipStreamSynchronize(s));
 }
 
 // unit entry: the device sampler on given logits rows (HF logits processors + inverse-CDF draw), one token per row

@@ -14,6 +14,11 @@ HF constructors (transformers generation/logits_process.py), and returns what Ru
     begin_suppress_tokens             SuppressTokensAtBeginLogitsProcessor      None, []
     min_p                             MinPLogitsWarper        (do_sample only)  None, 0
     epsilon_cutoff                    EpsilonLogitsWarper     (do_sample only)  None, 0
+    num_beams = K                     _beam_search (do_sample=False)            None, 1      (2 .. 16: csrc/gpt_beam.hip)
+    length_penalty, early_stopping    its two knobs (False / True / "never")    read under beams only
+Under beams nothing is sampled, and HF runs the processors on LOG-PROBABILITIES: the repetition penalty multiplies the (negative) scores
+of seen ids.  `split_beam_options` takes the three beam keys out of a validated dict; `beam_request` is what the public entries call (it also
+refuses what beams exclude); Runtime refuses a processors dict that still carries a beam key.
 
 Counting (HF's input_ids of a row = its fill-id-1 prefix columns, 8192, an acoustic prompt's codes, input_tokens, generated tokens):
 min_length counts all of it; min_new_tokens, the decay's start and begin_suppress_tokens count from the end of HF's prompt, which holds
@@ -48,7 +53,14 @@ def validate_decode_options(options, vocab=8194, do_sample=True, strict=True):
     if not hasattr(options, "items"):
         raise ValueError(f"decode_options has to be a dict of {', '.join(KEYS)}, not {type(options).__name__}")
     out = {}
+    if any(k in options for k in BEAM_KEYS):          # the beam keywords travel in the same dict; K = 1 / None leaves nothing behind
+        K, lp, es = validate_beam_options(options.get("num_beams"), options.get("length_penalty"), options.get("early_stopping"))
+        if K:
+            out.update(num_beams=K, length_penalty=lp, early_stopping={0: False, 1: True, 2: "never"}[es])
+            do_sample = False
     for k, v in options.items():
+        if k in BEAM_KEYS:
+            continue
         if k not in KEYS:
             if strict:
                 raise ValueError(f"decode_options: unknown keyword {k!r} (served: {', '.join(KEYS)})")
@@ -89,6 +101,64 @@ def validate_decode_options(options, vocab=8194, do_sample=True, strict=True):
             if v > 0 and do_sample:
                 out[k] = float(v)
     return out
+
+
+BEAMS_MAX = 16          # BEAM_MAXK of csrc/gpt_kernels.h: the K beams of an utterance are rows of ONE decode session
+BEAM_KEYS = ("num_beams", "length_penalty", "early_stopping")
+
+
+def validate_beam_options(num_beams=None, length_penalty=None, early_stopping=None, **other):
+    """HF generate()'s beam keywords -> (K, length_penalty, early_stopping code 0 / 1 / 2); K = 0 means no beam search (num_beams None
+    or 1: today's decode, the other two keywords are then only checked, as HF ignores them without beams).  `other`: what the call also
+    carries and beams exclude - do_sample, typical_sampling, input_tokens, forced_codes, forced_uniforms, num_candidates,
+    num_return_sequences, stream; each refusal is a ValueError that names its keyword, before any launch."""
+    if num_beams is None:
+        num_beams = 1
+    if not _is_int(num_beams) or num_beams < 1:
+        raise ValueError(f"`num_beams` has to be an integer >= 1, but is {num_beams!r}")
+    if length_penalty is None:
+        length_penalty = 1.0
+    if isinstance(length_penalty, bool) or not isinstance(length_penalty, numbers.Real) or not float("-inf") < float(length_penalty) < float("inf"):
+        raise ValueError(f"`length_penalty` has to be a finite float, but is {length_penalty!r}")
+    if early_stopping is None:
+        early_stopping = False
+    if not (isinstance(early_stopping, bool) or early_stopping == "never"):
+        raise ValueError(f"`early_stopping` must be a boolean or 'never', but is {early_stopping!r}")
+    es = 2 if early_stopping == "never" else int(bool(early_stopping))
+    K = int(num_beams)
+    nrs = other.get("num_return_sequences")
+    if K == 1:
+        return 0, float(length_penalty), es
+    if K > BEAMS_MAX:
+        raise ValueError(f"`num_beams` = {K} does not fit a decode session: the beams of an utterance are rows of one session of {BEAMS_MAX}")
+    if other.get("do_sample"):
+        raise ValueError("`do_sample`=True with `num_beams` > 1 (beam-sample) is not served: pass do_sample=False")
+    for key in ("typical_sampling", "input_tokens", "forced_codes", "forced_uniforms", "stream"):
+        if other.get(key) is not None and other.get(key) is not False:
+            raise ValueError(f"`{key}` cannot be combined with `num_beams` > 1")
+    if (other.get("num_candidates") or 1) > 1:
+        raise ValueError("`num_candidates` > 1 cannot be combined with `num_beams` > 1 (the beams are the candidates)")
+    if nrs is not None and (not _is_int(nrs) or not 1 <= nrs <= K):
+        raise ValueError(f"`num_return_sequences` ({nrs}) has to be smaller or equal to `num_beams` ({K})")
+    return K, float(length_penalty), es
+
+
+def split_beam_options(validated):
+    """validated decode options -> (processors without the beam keys, None or dict(num_beams, length_penalty, early_stopping))"""
+    proc = {k: v for k, v in validated.items() if k not in BEAM_KEYS}
+    beam = {k: validated[k] for k in BEAM_KEYS if k in validated}
+    return proc, (beam if beam.get("num_beams", 0) > 1 else None)
+
+
+def beam_request(decode_options, forced_codes=None, num_candidates=1, return_candidates=False, stream=False):
+    """What infer / infer_gpt / infer_stream do with their decode_options: validate, split, and refuse - by the keyword's name, before any
+    launch - what a beam search cannot be combined with.  -> (processors, None or dict(num_beams, length_penalty, early_stopping))"""
+    proc, beam = split_beam_options(validate_decode_options(decode_options))
+    if beam:
+        validate_beam_options(**beam, forced_codes=forced_codes, num_candidates=num_candidates, stream=True if stream else None)
+        if return_candidates:
+            raise ValueError("`return_candidates` cannot be combined with `num_beams` > 1 (the beams are the candidates)")
+    return proc, beam
 
 
 def first_stop_step(input_len, forced_prefix, min_length=0, min_new_tokens=0):

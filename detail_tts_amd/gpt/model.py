@@ -60,8 +60,11 @@ class UnifiedVoice:
         (inert without beams), and HF's remaining decode-time processors, served by the device sampler in HF's order
         (gpt/decode_options.py states the counting rules): no_repeat_ngram_size (1 .. 16), min_length, min_new_tokens,
         exponential_decay_length_penalty = (start, factor > 1), suppress_tokens, begin_suppress_tokens, and - under do_sample=True only,
-        as in HF - min_p and epsilon_cutoff.  Bad values raise ValueError before any launch.  Any other keyword is still dropped
-        (bad_words_ids, sequence_bias, typical_p, eta_cutoff, top_h, encoder_*, beams: INTEGRATION.md 1).  Returns LongTensor [B * num_return_sequences, <=max] incl. the stop token (and input_tokens in front).
+        as in HF - min_p and epsilon_cutoff.  Bad values raise ValueError before any launch.  `num_beams` = K in 2 .. 16 (with
+        `length_penalty`, `early_stopping` in False / True / "never") runs HF's beam search on the device (csrc/gpt_beam.hip): do_sample
+        has to be False or absent, `num_return_sequences` <= K then means HF's best n of the K beams, the extension keyword
+        `return_scores=True` returns (sequences, sequences_scores), and last_latents is None.  Any other keyword is still dropped
+        (bad_words_ids, sequence_bias, typical_p, eta_cutoff, top_h, encoder_*, group / constrained beams: INTEGRATION.md 1).  Returns LongTensor [B * num_return_sequences, <=max] incl. the stop token (and input_tokens in front).
 
         Off the `infer` path but part of the reference's surface: `do_sample=False` (HF greedy search: only the repetition penalty is a
         logits processor there, argmax), `num_return_sequences = n` (HF repeats every row n times - repeat_interleave - and samples the
@@ -102,9 +105,37 @@ class UnifiedVoice:
         the row expansion, the id checks, the greedy mapping and the decode session; mel_codes = None is the tortoise session."""
         nrs = int(num_return_sequences)
         assert nrs >= 1
-        do_sample = bool(hf_generate_kwargs.get("do_sample", True))
-        from .decode_options import validate_decode_options
-        processors = validate_decode_options(hf_generate_kwargs, do_sample=do_sample, strict=False)      # (ValueError before any launch)
+        from .decode_options import validate_beam_options, validate_decode_options
+        # beam search (HF _beam_search, csrc/gpt_beam.hip): num_beams / length_penalty / early_stopping as the reference's
+        # **hf_generate_kwargs carry them (gpt/model.py:542-544); every refusal is a ValueError before any launch
+        beams, lp, es = validate_beam_options(hf_generate_kwargs.get("num_beams"), hf_generate_kwargs.get("length_penalty"),
+                                              hf_generate_kwargs.get("early_stopping"), do_sample=hf_generate_kwargs.get("do_sample"),
+                                              typical_sampling=typical_sampling or None, input_tokens=input_tokens,
+                                              forced_uniforms=forced_uniforms, num_return_sequences=nrs)
+        return_scores = bool(hf_generate_kwargs.get("return_scores", False))
+        if return_scores and not beams:
+            raise ValueError("`return_scores` needs `num_beams` > 1 (sequences_scores are a beam search's)")
+        do_sample = False if beams else bool(hf_generate_kwargs.get("do_sample", True))
+        processors = validate_decode_options({k: v for k, v in hf_generate_kwargs.items() if k not in ("num_beams", "length_penalty", "early_stopping")},
+                                             do_sample=do_sample, strict=False)      # (ValueError before any launch)
+        if beams:
+            refer = speech_conditioning_latent.float().contiguous()
+            B = refer.shape[0]
+            cl = None if cond_lengths is None else torch.as_tensor(cond_lengths).reshape(-1).tolist()
+            prompt = None
+            if mel_codes is not None:
+                from .prompt import prompt_rows
+                prompt = prompt_rows(mel_codes, B)
+            G = self.max_mel_tokens - 1 if max_generate_length is None else int(max_generate_length)
+            seqs, lens, scores = self.rt.gpt_generate_beams(
+                refer, cl, self._texts(text_inputs, text_lengths), beams, num_return_sequences=nrs, max_generate_length=G, length_penalty=lp,
+                early_stopping={0: False, 1: True, 2: "never"}[es], repetition_penalty=hf_generate_kwargs.get("repetition_penalty", 1.0),
+                suppress_eos=suppress_eos, prompt_codes=prompt, processors=processors or None)
+            # rows change lineage while decoding: no decode-time latents (forward(return_latent=True) on the chosen codes gives them)
+            self.last_latents, self.last_ncodes = None, lens.reshape(-1)
+            self.last_scores = torch.from_numpy(scores.reshape(-1).copy())
+            out = torch.from_numpy(seqs.reshape(B * nrs, G)[:, :int(lens.max())].astype(np.int64)).to(refer.device)
+            return (out, self.last_scores) if return_scores else out
         refer = speech_conditioning_latent.float().contiguous()
         B = refer.shape[0]
         it = None

@@ -173,7 +173,10 @@ class Runtime:
         struct points into - keep them until the call returns."""
         if not processors:
             return None
-        from .gpt.decode_options import validate_decode_options
+        from .gpt.decode_options import BEAM_KEYS, validate_decode_options
+        stray = [k for k in BEAM_KEYS if k in processors]
+        if stray:       # a beam search is gpt_generate_beams' business: dropped here it would decode sampled and tell nobody
+            raise ValueError(f"processors: `{stray[0]}` is a beam-search keyword, not a logits processor (gpt_generate_beams takes it)")
         p = validate_decode_options(processors, vocab=vocab)
         o.no_repeat_ngram_size = p.get("no_repeat_ngram_size", 0)
         o.min_length, o.min_new_tokens = p.get("min_length", 0), p.get("min_new_tokens", 0)
@@ -1213,6 +1216,78 @@ class Runtime:
                                                      pl.ctypes.data_as(_lib.c_int_p), _ptr(uniforms), out.ctypes.data_as(_lib.c_int_p),
                                                      self._stream()))
         return out
+
+    @staticmethod
+    def _beams(o, num_beams, length_penalty, early_stopping):
+        """num_beams / length_penalty / early_stopping -> dtts_gpt_options (gpt/decode_options.py validates; ValueError before any call)"""
+        from .gpt.decode_options import validate_beam_options
+        K, lp, es = validate_beam_options(num_beams, length_penalty, early_stopping)
+        o.num_beams, o.length_penalty, o.early_stopping = K, lp, es
+        return K
+
+    def op_beam_step(self, logits, state, prompt, step, num_beams, max_new_tokens, length_penalty=1.0, early_stopping=False,
+                     repetition_penalty=1.0, processors=None):
+        """ONE step of HF's _beam_search on the device (dtts_op_beam_step, csrc/gpt_beam.hip), weight-free.  logits cuda float32
+        [U * K, V] (stop token V - 1); state: dict of numpy arrays run_seq / fin_seq [U, K, G], run_score / fin_score [U, K], fin_flag,
+        fin_len [U, K], unsat, done [U] (generated tokens only; tests/beam_model.py::init_state); prompt int [U, P].
+        -> (new state, info) with info = dict(parents, tokens [U, K], cand_score, cand_beam, cand_tok [U, 2K])."""
+        _check(logits, "logits")
+        R, V = logits.shape
+        o = _lib.DttsGptOptions()
+        self.lib.dtts_gpt_options_init(C.byref(o))
+        K = self._beams(o, num_beams, length_penalty, early_stopping) or 1
+        o.num_beams = K
+        U, G = R // K, int(max_new_tokens)
+        assert U * K == R and state["run_seq"].shape == (U, K, G)
+        o.max_generate_length, o.repetition_penalty = G, float(repetition_penalty)
+        keep_proc = self._processors(o, processors, vocab=V)      # noqa: F841
+        i32 = lambda a: np.ascontiguousarray(np.asarray(a).astype(np.int32))      # noqa: E731
+        f32 = lambda a: np.ascontiguousarray(np.asarray(a).astype(np.float32))      # noqa: E731
+        st = dict(run_seq=i32(state["run_seq"]), fin_seq=i32(state["fin_seq"]), run_score=f32(state["run_score"]),
+                  fin_score=f32(state["fin_score"]), fin_flag=i32(state["fin_flag"]), fin_len=i32(state["fin_len"]),
+                  unsat=i32(state["unsat"]), done=i32(state["done"]))
+        pr = i32(prompt)
+        info = dict(parents=np.zeros((U, K), np.int32), tokens=np.zeros((U, K), np.int32), cand_score=np.zeros((U, 2 * K), np.float32),
+                    cand_beam=np.zeros((U, 2 * K), np.int32), cand_tok=np.zeros((U, 2 * K), np.int32))
+        ip, fp = (lambda a: a.ctypes.data_as(_lib.c_int_p)), (lambda a: a.ctypes.data_as(_lib.c_float_p))
+        self._rc(self.lib.dtts_op_beam_step(self.h, _ptr(logits), U, V, C.byref(o), int(step), ip(pr), pr.shape[1] if pr.ndim == 2 else 0,
+                                            ip(st["run_seq"]), fp(st["run_score"]), ip(st["fin_seq"]), fp(st["fin_score"]), ip(st["fin_flag"]),
+                                            ip(st["fin_len"]), ip(st["unsat"]), ip(st["done"]), ip(info["parents"]), ip(info["tokens"]),
+                                            fp(info["cand_score"]), ip(info["cand_beam"]), ip(info["cand_tok"]), self._stream()))
+        st["fin_flag"], st["unsat"], st["done"] = st["fin_flag"].astype(bool), st["unsat"].astype(bool), st["done"].astype(bool)
+        return st, info
+
+    def gpt_generate_beams(self, refer, refer_lens, texts, num_beams, num_return_sequences=1, max_generate_length=600, length_penalty=1.0,
+                           early_stopping=False, repetition_penalty=2.0, suppress_eos=False, token_wgs=0, prompt_codes=None, processors=None):
+        """Beam search (HF generate(num_beams=K, do_sample=False)) on the device: dtts_gpt_beam_generate.  -> (seqs int32 [B, nrs, G]
+        padded with 8193, lens int32 [B, nrs], scores float32 [B, nrs] = HF's sequences_scores), the best nrs <= K finished hypotheses
+        of every utterance in score order.  prompt_codes / processors as in gpt_generate; nothing is sampled."""
+        B, _, Tr = refer.shape
+        text, tl = self._pad_text(texts)
+        G, nrs = int(max_generate_length), int(num_return_sequences)
+        prompt = self._prompt(prompt_codes, B, tl, G)
+        _check(refer, "refer")
+        o = _lib.DttsGptOptions()
+        self.lib.dtts_gpt_options_init(C.byref(o))
+        K = self._beams(o, num_beams, length_penalty, early_stopping)
+        if K < 2:
+            raise ValueError(f"`num_beams` has to be 2 .. 16 for a beam search, but is {num_beams}")
+        if not 1 <= nrs <= K:
+            raise ValueError(f"`num_return_sequences` ({nrs}) has to be smaller or equal to `num_beams` ({K})")
+        si = _ints([0] * B)
+        rl = _ints(refer_lens if refer_lens is not None else [Tr] * B)
+        o.sample_ids, o.max_generate_length, o.repetition_penalty = si[0], G, float(repetition_penalty)
+        o.suppress_eos, o.token_wgs = 1 if suppress_eos else 0, int(token_wgs or 0)
+        keep_proc = self._processors(o, processors)      # noqa: F841
+        if prompt is not None:
+            o.prompt_codes, o.prompt_lens, o.prompt_stride = prompt[0].ctypes.data_as(_lib.c_int_p), prompt[1].ctypes.data_as(_lib.c_int_p), prompt[0].shape[1]
+        seqs = np.zeros((B, nrs, G), np.int32)
+        lens = np.zeros((B, nrs), np.int32)
+        scores = np.zeros((B, nrs), np.float32)
+        self._rc(self.lib.dtts_gpt_beam_generate(self.h, _ptr(refer), rl[0], Tr, text.ctypes.data_as(_lib.c_int_p), tl.ctypes.data_as(_lib.c_int_p),
+                                                 text.shape[1], B, C.byref(o), nrs, seqs.ctypes.data_as(_lib.c_int_p),
+                                                 lens.ctypes.data_as(_lib.c_int_p), scores.ctypes.data_as(_lib.c_float_p), self._stream()))
+        return seqs, lens, scores
 
     def op_philox_normal(self, n, seed, sample_ids, stage, step):
         si = _ints(sample_ids)

@@ -17,7 +17,7 @@ import torch
 
 from ..config import COND_FREE_K, INFER_DIFFUSION_STEPS, MAX_GENERATE_LENGTH, MEL_MIN, NOISE_SCALE, REPETITION_PENALTY, TEMPERATURE, \
     TOP_P, TORCH_MEL_MAX, TRAINED_DIFFUSION_STEPS, load_config
-from ..gpt.decode_options import validate_decode_options
+from ..gpt.decode_options import beam_request
 from ..gpt.candidates import check_choose, check_num_candidates, expand_sample_ids, rank_candidates
 from ..gpt.prompt import check_prompt_args, prompt_rows
 from ..gpt.model import UnifiedVoice
@@ -360,7 +360,7 @@ class SynthesizerTrn:
         prec = SynthesizerTrn._check_trunk_precision(self, trunk_precision)
         ncand = check_num_candidates(num_candidates, forced_codes)
         check_prompt_args(prompt_codes, forced_codes, ncand)
-        processors = validate_decode_options(decode_options)
+        processors, beam = beam_request(decode_options, forced_codes=forced_codes, num_candidates=ncand, return_candidates=return_candidates)
         st = normalize_request(text, text_length, refer, refer_lengths, seed, sample_ids, forced_codes, batch=batch)
         B, rl, texts, seed, sample_ids, forced_codes = st.B, st.rl, st.texts, st.seed, st.sids, st.forced
         if prompt_codes is not None:       # (ValueError on a bad row count or code: before any launch)
@@ -381,8 +381,14 @@ class SynthesizerTrn:
 
         mark("start")
         # ---- stage A: codes + latents (:782-799)
-        session = forced_codes is None and B * (ncand if candidates else 1) <= 16
-        if forced_codes is None:
+        session = forced_codes is None and B * (ncand if candidates else 1) <= 16 and not beam
+        if beam:        # HF's beam search on the device; the best hypothesis's latents come from the return_latent pass, as behind a prompt
+            seqs, blens, _ = self.rt.gpt_generate_beams(refer, rl, texts, num_return_sequences=1, max_generate_length=max_generate_length,
+                                                        repetition_penalty=REPETITION_PENALTY, suppress_eos=suppress_eos,
+                                                        prompt_codes=prompt_codes, processors=processors or None, **beam)
+            n, = split_session(blens[:, 0], [B])
+            st.lat, st.n = self.rt.gpt_latents(refer, rl, texts, [seqs[b, 0, : n[b]] for b in range(B)]), n
+        elif forced_codes is None:
             kw = dict(max_generate_length=max_generate_length, top_k=top_k, top_p=TOP_P, temperature=TEMPERATURE,
                       repetition_penalty=REPETITION_PENALTY, suppress_eos=suppress_eos)
             if prompt_codes is not None:
@@ -484,9 +490,10 @@ class SynthesizerTrn:
         diffusion_steps / sampler / eta / trunk_precision: as in infer(), one schedule and one trunk mode for every request of the stream
         (the option is set around each request's diffusion launches only, on this thread: nothing leaks into other calls).
 
-        decode_options: as in infer(), one set for every request of the stream (None or {}: today's decode)."""
+        decode_options: as in infer(), one set for every request of the stream (None or {}: today's decode).  A beam search
+        (`num_beams` > 1) is refused with a ValueError before anything starts: a beam session cannot share its rows with another request."""
         assert on_saturation in ("rerun_fp32", "raise")
-        processors = validate_decode_options(decode_options)
+        processors, _ = beam_request(decode_options, stream=True)
         sched_ts, sampler_id, eta = sampling_args(diffusion_steps, sampler, eta)
         prec = SynthesizerTrn._check_trunk_precision(self, trunk_precision)
         dev = self.device
@@ -590,14 +597,18 @@ class SynthesizerTrn:
         """vqvae/model_24k.py:811-847: GPT codes -> quantizer.decode + vq_ref_enc -> vq_dec -> infer_flowvae (no diffusion).
         prompt_codes (not with forced_codes): line 819 calls UnifiedVoice.inference_speech_valle, see infer.  decode_options: see infer."""
         check_prompt_args(prompt_codes, forced_codes, 1)
-        processors = validate_decode_options(decode_options)
+        processors, beam = beam_request(decode_options, forced_codes=forced_codes)
         st = normalize_request(text, text_length, refer, refer_lengths, seed, sample_ids, forced_codes, batch=batch)
         B, rl, seed, sample_ids = st.B, st.rl, st.seed, st.sids
         pkw = {} if prompt_codes is None else dict(prompt_codes=prompt_rows(prompt_codes if batch else prompt_codes[:1], B))
         if processors:
             pkw["processors"] = processors
         refer = st.refer.to(self.device, torch.float32).contiguous()
-        if st.forced is None:
+        if st.forced is None and beam:
+            seqs, blens, _ = self.rt.gpt_generate_beams(refer, rl, st.texts, num_return_sequences=1, max_generate_length=max_generate_length,
+                                                        repetition_penalty=REPETITION_PENALTY, suppress_eos=suppress_eos, **pkw, **beam)
+            code_list = [seqs[b, 0, : int(blens[b, 0]) - 1] for b in range(B)]
+        elif st.forced is None:
             codes, ncodes, _ = self.rt.gpt_generate(refer, rl, st.texts, seed, sample_ids, max_generate_length=max_generate_length,
                                                     top_k=top_k, top_p=TOP_P, temperature=TEMPERATURE,
                                                     repetition_penalty=REPETITION_PENALTY, suppress_eos=suppress_eos, **pkw)

@@ -127,6 +127,14 @@ typedef struct dtts_gpt_options {
     int n_begin_suppress_tokens;
     float min_p;                    /* MinPLogitsWarper: p < min_p * p_max goes, over the softmax of what top-k and top-p kept; [0, 1], 0 = off */
     float epsilon_cutoff;           /* EpsilonLogitsWarper: p < epsilon goes (the largest score stays); [0, 1), 0 = off */
+    /* ---- beam search: HF GenerationMixin._beam_search (do_sample=False) on the device (csrc/gpt_beam.hip; the reference's generate()
+     * call hands these on, gpt/model.py:542-544, and ships _reorder_cache for them, :187-200).  With num_beams = K > 1 the B utterances
+     * decode as B * K rows (whole utterances per 16-row session), nothing is sampled - seed, top_k, top_p, temperature, typical_mass, min_p,
+     * epsilon_cutoff and forced_uniforms are not read - and the repetition penalty and the other processors act on LOG-PROBABILITIES, as
+     * HF applies them under beams.  forced_codes is refused.  Results: dtts_gpt_beam_generate.  (In front of token_wgs, as above.) */
+    int num_beams;                  /* 0 / 1 = off; 2 .. 16 */
+    float length_penalty;           /* finished scores are divided by generated_length ** length_penalty (HF default 1.0) */
+    int early_stopping;             /* HF's early_stopping: 0 False, 1 True, 2 "never" */
     int token_wgs;                  /* workgroups of the persistent decode-token kernel for THIS session of 5 .. 8 rows: 128, 64 or 32 (the same
                                      * codes and latents bit for bit; fewer workgroups decode longer on fewer CUs - what a session that runs
                                      * NEXT TO another request's diffusion should ask for: SynthesizerTrn.infer_stream passes 64); 0 = the
@@ -185,6 +193,18 @@ int dtts_gpt_steps(dtts_handle* h);
 int dtts_gpt_all_finished(dtts_handle* h, int* all_finished, void* stream);
 /* codes HOST int32 [B][max_generate_length] / ncodes HOST [B] as dtts_gpt_generate; ends the session.  Synchronises. */
 int dtts_gpt_finish(dtts_handle* h, int* codes_out, int* ncodes_out, void* stream);
+
+/* dtts_gpt_generate under opts->num_beams = K > 1: per utterance the best nrs <= K finished hypotheses in score order, as HF returns
+ * them.  seqs_out HOST int32 [B][nrs][max_generate_length] (stop token included when the hypothesis drew it; unfilled positions 8193),
+ * lens_out HOST [B][nrs] (generated length), scores_out HOST float [B][nrs] (HF's sequences_scores: the accumulated log-probability
+ * divided by length ** length_penalty).  Utterances run in groups of floor(16 / K); no decode-time latents are handed out (rows change
+ * lineage: take them from dtts_gpt_latents on the chosen codes).  Every refusal comes before a launch. */
+int dtts_gpt_beam_generate(dtts_handle* h, const float* refer, const int* refer_lens, int Tr, const int* text, const int* text_lens,
+                           int Lt_max, int B, const dtts_gpt_options* opts, int nrs, int* seqs_out, int* lens_out, float* scores_out,
+                           void* stream);
+/* results of a beam SESSION (dtts_gpt_prefill with num_beams = K on B * K rows, utterance-major, then the decode calls): as above for
+ * the session's B utterances; ends the session.  Synchronises. */
+int dtts_gpt_beam_finish(dtts_handle* h, int nrs, int* seqs_out, int* lens_out, float* scores_out, void* stream);
 
 /* UnifiedVoice.forward(..., return_latent=True) (gpt/model.py:429-491) as called at vqvae/model_24k.py:796-799:
  * teacher-forced pass over [cond | text | start, codes, stop]; codes HOST [B][n_max], ncodes HOST [B] ->
@@ -745,6 +765,17 @@ int dtts_op_attention_rel(dtts_handle* h, const float* qkv, const int* lens, int
 int dtts_op_sample_logits(dtts_handle* h, const float* logits, int R, int V, const int* history, int hist_len,
                           const float* uniforms, int top_k, float top_p, float temperature, float repetition_penalty,
                           int* tokens_out, void* stream);
+/* Unit entry of the beam step (csrc/gpt_beam.hip beam_step_kernel), weight-free: ONE step of HF's _beam_search for U utterances x K beams
+ * on given logits.  logits DEVICE [U * K][V] (stop token V - 1); opts: num_beams = K, length_penalty, early_stopping, max_generate_length
+ * = the new tokens allowed (a continuation also stops when step + 1 reaches it), repetition_penalty and the processors; step = index of
+ * the token being chosen; prompt HOST [U][prompt_len] ids in front of the generated tokens (what the processors see besides the row's
+ * own sequence).  State in / out, all HOST, generated tokens only, row stride max_generate_length: run_seq / fin_seq int [U * K][G],
+ * run_score / fin_score float [U * K], fin_flag / fin_len int [U * K], unsat / done int [U].  Out only: parents / tokens int [U * K],
+ * cand_score float [U][2K], cand_beam / cand_tok int [U][2K] (the 2K continuations, best first; untouched for a done utterance). */
+int dtts_op_beam_step(dtts_handle* h, const float* logits, int U, int V, const dtts_gpt_options* opts, int step, const int* prompt,
+                      int prompt_len, int* run_seq, float* run_score, int* fin_seq, float* fin_score, int* fin_flag, int* fin_len,
+                      int* unsat, int* done, int* parents, int* tokens, float* cand_score, int* cand_beam, int* cand_tok, void* stream);
+
 /* dtts_op_sample_logits plus the two remaining sampler options of dtts_gpt_options: typical_mass in (0, 1) runs the reference's
  * TypicalLogitsWarper (gpt/modules/typical_sampling.py:11-33) between the repetition penalty and the temperature (0 = off);
  * suppress_eos != 0 sets the logit of id V - 1 (the stop token's place in a row) to -inf before every processor.
