@@ -119,6 +119,15 @@ SIGNATURES = {
                                       c_int_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "dtts_diff_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int,
                                  C.c_ulonglong, c_int_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dtts_diff_invert": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "dtts_diff_sample_from": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, c_int_p, C.c_int, C.c_int,
+                                        C.c_ulonglong, c_int_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "dtts_diff_reverse_step": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_void_p]),
+    "dtts_diff_mean_variance": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dtts_ddim_reverse_table": (C.c_int, [c_int_p, C.c_int, C.c_int, C.c_float, c_float_p, C.c_int, c_int_p]),
     "dtts_diff_forward_t": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                       C.c_void_p]),
     "dtts_dpm_schedule_table": (C.c_int, [C.c_int, c_float_p, c_float_p, c_float_p, C.c_int, c_int_p]),

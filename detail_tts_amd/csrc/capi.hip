@@ -1,4 +1,5 @@
 // extern "C" surface of libdetail_hip.so (see include/detail_hip.h).
+#include <algorithm>
 #include <mutex>
 
 #include "model.h"
@@ -549,6 +550,56 @@ int dtts_diff_step(dtts_handle* h, int id, int sampler, float eta, float* x, con
     DTTS_API_BEGIN
     h->m->diff_step(id, sampler, eta, x, code_emb, lens, B, T, step, seed, sample_ids, noise, x0_out, (hipStream_t)stream);
     DTTS_API_END(h)
+}
+
+int dtts_diff_invert(dtts_handle* h, int id, const float* code_emb, const int* lens, int B, int T, const float* x_start, int depth,
+                     float* x_out, float* x_traj, float* x0_traj, void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_invert(id, code_emb, lens, B, T, x_start, depth, x_out, x_traj, x0_traj, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_diff_sample_from(dtts_handle* h, int id, int sampler, float eta, int first_step, const float* code_emb, const int* lens, int B,
+                          int T, unsigned long long seed, const int* sample_ids, const float* x_init, const float* step_noise,
+                          float* mel_out, int denorm, void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_sample_from(id, sampler, eta, first_step, code_emb, lens, B, T, seed, sample_ids, x_init, step_noise, mel_out, denorm,
+                           (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_diff_reverse_step(dtts_handle* h, int id, float* x, const float* code_emb, const int* lens, int B, int T, int step, float* x0_out,
+                           void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_reverse_step(id, x, code_emb, lens, B, T, step, x0_out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_diff_mean_variance(dtts_handle* h, int id, const float* x, const float* code_emb, const int* lens, int B, int T, int step,
+                            float* mean, float* variance, float* log_variance, float* pred_xstart, void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_mean_variance(id, x, code_emb, lens, B, T, step, mean, variance, log_variance, pred_xstart, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_ddim_reverse_table(const int* timesteps, int n, int trained_steps, float cond_free_k, float* coefs, int cap, int* n_out) {
+    DTTS_API_BEGIN
+    DTTS_REQUIRE(timesteps && n >= 1 && trained_steps >= 1, "timesteps, n >= 1, trained_steps >= 1");
+    std::vector<int> tmap(timesteps, timesteps + n);
+    for (int t : tmap) DTTS_REQUIRE(t >= 0 && t < trained_steps, "timestep out of [0, trained_steps)");
+    std::sort(tmap.begin(), tmap.end());
+    tmap.erase(std::unique(tmap.begin(), tmap.end()), tmap.end());
+    dtts::ScheduleTables sc;
+    dtts::make_schedule(trained_steps, tmap, cond_free_k, sc);
+    if (n_out) *n_out = sc.n;
+    DTTS_REQUIRE(!coefs || cap >= sc.n, "cap < n");
+    if (coefs)
+        for (int i = 0; i < sc.n; ++i) {
+            const dtts::DdimReverseCoefs k = sc.ddim_reverse(i);
+            const float v[6] = {sc.ac_next[i], k.sqrt_recip_ac, k.sqrt_recipm1_ac, k.sqrt_ac_next, k.sqrt_1m_ac_next, k.cfk};
+            std::memcpy(coefs + (size_t)6 * i, v, sizeof(v));
+        }
+    DTTS_API_END(nullptr)
 }
 
 int dtts_diff_forward_t(dtts_handle* h, const float* x, const float* code_emb, const int* lens, int B, int T, int timestep,

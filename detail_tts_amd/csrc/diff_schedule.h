@@ -17,12 +17,14 @@ struct ScheduleTables {
     std::vector<float> ftimes;            // kinds 1, 2: fp32 model time of column i, ascending (kind 1: t_{n-1-i} * 1000)
     std::vector<DiffStepCoefs> p;         // ancestral sampler (p_sample)
     std::vector<float> ac, ac_prev;       // fp32 alphas_cumprod / alphas_cumprod_prev (DDIM: the eta-dependent terms are per call)
+    std::vector<float> ac_next;           // kind 0: fp32 alphas_cumprod_next (ddim_reverse_sample, :812); 0 at the last step
     std::vector<float> sqrt_ac, sqrt_1m_ac;   // kind 0: fp32 sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod (q_sample, :243-260)
     std::vector<float> log_1m_ac;         // kind 0: fp32 log_one_minus_alphas_cumprod (q_mean_variance, :230-241: _prior_bpd)
     std::vector<DpmStepCoefs> dpm;        // kind 1: the update of column i
     float cfk_k = 0.f;
     int n = 0;
     DdimStepCoefs ddim(int i, float eta) const;
+    DdimReverseCoefs ddim_reverse(int i) const;
     bool same_key(const ScheduleTables& o) const { return kind == o.kind && tmap == o.tmap && ftimes == o.ftimes; }
 };
 

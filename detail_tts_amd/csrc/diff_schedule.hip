@@ -52,6 +52,7 @@ void make_schedule(int trained, const std::vector<int>& tmap, float cfk_k, Sched
     sc.p.resize(n);
     sc.ac.resize(n);
     sc.ac_prev.resize(n);
+    sc.ac_next.resize(n);
     sc.sqrt_ac.resize(n);
     sc.sqrt_1m_ac.resize(n);
     sc.log_1m_ac.resize(n);
@@ -69,6 +70,7 @@ void make_schedule(int trained, const std::vector<int>& tmap, float cfk_k, Sched
         sc.p[i] = k;
         sc.ac[i] = (float)acp[i];
         sc.ac_prev[i] = (float)acp_prev[i];
+        sc.ac_next[i] = i + 1 < n ? (float)acp[i + 1] : 0.f;              // np.append(alphas_cumprod[1:], 0.0)
         sc.sqrt_ac[i] = (float)std::sqrt(acp[i]);
         sc.sqrt_1m_ac[i] = (float)std::sqrt(1.0 - acp[i]);
         sc.log_1m_ac[i] = (float)std::log(1.0 - acp[i]);
@@ -86,6 +88,19 @@ DdimStepCoefs ScheduleTables::ddim(int i, float eta) const {
     k.sqrt_ac_prev = std::sqrt(ap);
     k.dir = std::sqrt(1.f - ap - k.sigma * k.sigma);
     k.nonzero = i != 0;
+    return k;
+}
+
+// ddim_reverse_sample's scalars (vqvae/utils/diffusion.py:809-815): alphas_cumprod_next is cast to fp32 by _extract_into_tensor, then
+// th.sqrt and 1 - . run on the fp32 tensor
+DdimReverseCoefs ScheduleTables::ddim_reverse(int i) const {
+    DdimReverseCoefs k;
+    k.sqrt_recip_ac = p[i].sqrt_recip_ac;
+    k.sqrt_recipm1_ac = p[i].sqrt_recipm1_ac;
+    k.cfk = p[i].cfk;
+    const float an = ac_next[i];
+    k.sqrt_ac_next = std::sqrt(an);
+    k.sqrt_1m_ac_next = std::sqrt(1.f - an);
     return k;
 }
 

@@ -229,6 +229,22 @@ public:
     // one sampler step of schedule `sched_id` on x in place (unit entry of the sampler parity tests)
     void diff_step(int sched_id, int sampler, float eta, float* x, const float* code_emb, const int* lens_host, int B, int T, int step,
                    unsigned long long seed, const int* sample_ids_host, const float* noise, float* x0_out, hipStream_t s);
+    // DDIM inversion (ddim_reverse_sample, vqvae/utils/diffusion.py:785-817, iterated): steps 0 .. depth - 1 of integer-timestep schedule
+    // `sched_id` upwards from x_start; x_out [B,128,T] = x at the level of step index `depth`; x_traj / x0_traj (optional)
+    // [depth][B,128,T]: x after every step / every step's pred_xstart
+    void diff_invert(int sched_id, const float* code_emb, const int* lens_host, int B, int T, const float* x_start, int depth, float* x_out,
+                     float* x_traj, float* x0_traj, hipStream_t s);
+    // diff_sample_ex from below the top of the schedule: x_init is x at the level of step `first_step`, steps first_step .. 0 run
+    // (samplers 0 and 1).  The code-path table is evaluated in the launches the whole loop would make, so the result is the whole loop's.
+    void diff_sample_from(int sched_id, int sampler, float eta, int first_step, const float* code_emb, const int* lens_host, int B, int T,
+                          unsigned long long seed, const int* sample_ids_host, const float* x_init, const float* step_noise, float* mel_out,
+                          int denorm, hipStream_t s);
+    // one ddim_reverse_sample at spaced step `step`, x in place (diff_invert's step: the same bits)
+    void diff_reverse_step(int sched_id, float* x, const float* code_emb, const int* lens_host, int B, int T, int step, float* x0_out,
+                           hipStream_t s);
+    // p_mean_variance (:284-386) at spaced step `step`: mean, variance, log_variance, pred_xstart [B,128,T]; x is read only
+    void diff_mean_variance(int sched_id, const float* x, const float* code_emb, const int* lens_host, int B, int T, int step, float* mean,
+                            float* variance, float* log_variance, float* pred_xstart, hipStream_t s);
     // DiffusionTts.forward at any model timestep in [0, diff_trained_steps): default-schedule timesteps take their step of that schedule
     void diff_forward_t(const float* x, const float* code_emb, const int* lens_host, int B, int T, int timestep, int cond_free,
                         float* out, hipStream_t s);

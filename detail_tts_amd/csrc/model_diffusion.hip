@@ -897,6 +897,165 @@ void Model::diff_step(int sched_id, int sampler, float eta, float* x, const floa
     if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
 }
 
+// ---- DDIM inversion, partial-depth sampling, p_mean_variance
+static void check_lens(const int* lens_host, int B, int T) {
+    for (int b = 0; lens_host && b < B; ++b) DTTS_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= T, "lens: every length in [1, T]");
+}
+// may the code-path table of `nst` steps be built (diff_sample_ex's rule: DTTS_INTEG_PRECOMPUTE, DTTS_INTEG_MAX_GB)
+static bool integ_table_fits(int nst, int B, int C, int T) {
+    static const bool env_pre_on = env_on("DTTS_INTEG_PRECOMPUTE");
+    static const double max_gb = []() { const char* v = env_str("DTTS_INTEG_MAX_GB"); return v ? atof(v) : 24.0; }();
+    return env_pre_on && (double)(sizeof(float) * (size_t)nst * 2 * B * C * T) <= max_gb * 1073741824.0;
+}
+static size_t integ_call_bytes(int nst, int B, int C, int T) {        // the table of nst steps + precompute_integrator's scratch
+    return sizeof(float) * (size_t)nst * 2 * B * C * T + integ_ws_bytes(2 * B, integ_chunk(B + 1) * 2 * B, C, T);
+}
+
+// GaussianDiffusion.ddim_reverse_sample (vqvae/utils/diffusion.py:785-817) for t = 0 .. depth - 1.  The code-path terms are evaluated for
+// exactly those steps, in that order, under RowInvariantLaunches: a row of the table is then the same bits whatever shares its launch, so
+// diff_reverse_step - a table of one step - computes this loop's step bit for bit.  A table beyond DTTS_INTEG_MAX_GB is built one step at
+// a time inside the loop (same values).
+void Model::diff_invert(int sched_id, const float* code_emb, const int* lens_host, int B, int T, const float* x_start, int depth,
+                        float* x_out, float* x_traj, float* x0_traj, hipStream_t s) {
+    DTTS_REQUIRE(bound_, "weights not bound");
+    DTTS_REQUIRE(code_emb && x_start && x_out && B >= 1 && T >= 1, "diff_invert: code_emb, x_start, x_out");
+    Schedule& sc = schedule(sched_id);
+    DTTS_REQUIRE(sc.kind == 0, "diff_invert runs on an integer-timestep schedule (dtts_diff_schedule)");
+    DTTS_REQUIRE(depth >= 1 && depth <= sc.n, "diff_invert: depth out of [1, steps of the schedule]");
+    check_lens(lens_host, B, T);
+    const int C = cfg.diff_channels, OC = cfg.diff_out_channels, MC = cfg.mel_channels;
+    const bool table = integ_table_fits(depth, B, C, T);
+    const int nst = table ? depth : 1;
+    const PairCall pc = begin_pair(code_emb, lens_host, nullptr, B, T, s, integ_call_bytes(nst, B, C, T));
+    const PairPlan& pl = pc.pl;
+    const size_t plane = (size_t)B * MC * T;
+    float* x = x_out;
+    const long long xbs = (long long)MC * T;
+    if (x != x_start) DTTS_CHECK_HIP(hipMemcpyAsync(x, x_start, sizeof(float) * plane, hipMemcpyDeviceToDevice, s));
+    const int Bi = B + pl.Nu;
+    std::vector<int> li(Bi);
+    for (int b = 0; b < B; ++b) li[b] = lens_host ? lens_host[b] : T;
+    for (int u = 0; u < pl.Nu; ++u) li[B + u] = pl.ulen[u];
+    float* integ_all = ws().f32((size_t)nst * Bi * C * T);
+    if (table) {
+        std::vector<int> steps(depth);
+        for (int k = 0; k < depth; ++k) steps[k] = k;
+        RowInvariantLaunches pin;
+        precompute_integrator(sc, pc.cbuf0, pl.lens_i, li.data(), B, pl.Nu, T, steps, integ_all, s);
+    }
+    const size_t mark = ws().mark();
+    for (int i = 0; i < depth; ++i) {
+        Profiler::gate() = (i % Profiler::get().step_every) == 0;
+        ws().rewind(mark);
+        if (!table) {
+            RowInvariantLaunches pin;
+            precompute_integrator(sc, pc.cbuf0, pl.lens_i, li.data(), B, pl.Nu, T, std::vector<int>{i}, integ_all, s);
+        }
+        diff_forward_pair(sc, x, pc.cbuf0, pl, B, T, i, pc.out2, s, integ_all + (table ? (size_t)i * Bi * C * T : 0));
+        launch_ddim_reverse_update(x, xbs, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.ddim_reverse(i), s,
+                                   x0_traj ? x0_traj + (size_t)i * plane : nullptr);
+        if (x_traj) DTTS_CHECK_HIP(hipMemcpyAsync(x_traj + (size_t)i * plane, x, sizeof(float) * plane, hipMemcpyDeviceToDevice, s));
+    }
+    Profiler::gate() = true;
+    if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
+}
+
+// one ddim_reverse_sample at spaced step `step`: diff_invert's step (a one-step table under RowInvariantLaunches), x in place
+void Model::diff_reverse_step(int sched_id, float* x, const float* code_emb, const int* lens_host, int B, int T, int step, float* x0_out,
+                              hipStream_t s) {
+    DTTS_REQUIRE(bound_, "weights not bound");
+    DTTS_REQUIRE(x && code_emb && B >= 1 && T >= 1, "diff_reverse_step: x, code_emb");
+    Schedule& sc = schedule(sched_id);
+    DTTS_REQUIRE(sc.kind == 0, "diff_reverse_step runs on an integer-timestep schedule (dtts_diff_schedule)");
+    DTTS_REQUIRE(step >= 0 && step < sc.n, "step out of range");
+    check_lens(lens_host, B, T);
+    const int C = cfg.diff_channels, OC = cfg.diff_out_channels, MC = cfg.mel_channels;
+    const PairCall pc = begin_pair(code_emb, lens_host, nullptr, B, T, s, integ_call_bytes(1, B, C, T));
+    const PairPlan& pl = pc.pl;
+    const int Bi = B + pl.Nu;
+    std::vector<int> li(Bi);
+    for (int b = 0; b < B; ++b) li[b] = lens_host ? lens_host[b] : T;
+    for (int u = 0; u < pl.Nu; ++u) li[B + u] = pl.ulen[u];
+    float* integ = ws().f32((size_t)Bi * C * T);
+    {
+        RowInvariantLaunches pin;
+        precompute_integrator(sc, pc.cbuf0, pl.lens_i, li.data(), B, pl.Nu, T, std::vector<int>{step}, integ, s);
+    }
+    diff_forward_pair(sc, x, pc.cbuf0, pl, B, T, step, pc.out2, s, integ);
+    launch_ddim_reverse_update(x, (long long)MC * T, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.ddim_reverse(step), s, x0_out);
+    if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
+}
+
+// GaussianDiffusion.p_mean_variance (vqvae/utils/diffusion.py:284-386) at spaced step `step`: diff_step's forward, nothing sampled
+void Model::diff_mean_variance(int sched_id, const float* x, const float* code_emb, const int* lens_host, int B, int T, int step,
+                               float* mean, float* variance, float* log_variance, float* pred_xstart, hipStream_t s) {
+    DTTS_REQUIRE(bound_, "weights not bound");
+    DTTS_REQUIRE(x && code_emb && mean && variance && log_variance && pred_xstart && B >= 1 && T >= 1,
+                 "diff_mean_variance: x, code_emb and the four outputs");
+    Schedule& sc = schedule(sched_id);
+    DTTS_REQUIRE(sc.kind == 0, "diff_mean_variance runs on an integer-timestep schedule (dtts_diff_schedule)");
+    DTTS_REQUIRE(step >= 0 && step < sc.n, "step out of range");
+    check_lens(lens_host, B, T);
+    const int OC = cfg.diff_out_channels, MC = cfg.mel_channels;
+    const PairCall pc = begin_pair(code_emb, lens_host, nullptr, B, T, s);
+    const PairPlan& pl = pc.pl;
+    diff_forward_pair(sc, x, pc.cbuf0, pl, B, T, step, pc.out2, s);
+    launch_diff_mean_variance(x, (long long)MC * T, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.p[step], mean, variance,
+                              log_variance, pred_xstart, s);
+    if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
+}
+
+// diff_sample_ex entered at step `first_step`: x_init is x at that level, steps first_step .. 0 run, Philox noise keyed by the step index
+// as in the whole loop.  The whole loop evaluates its code-path table J steps per launch from step n - 1 down, and a launch's split-K
+// follows its width; here the launches that hold a needed step are made whole, unneeded steps included (at most J - 1 of them), so every
+// step reads the bits the whole loop reads and a loop cut in two equals the loop run through.
+void Model::diff_sample_from(int sched_id, int sampler, float eta, int first_step, const float* code_emb, const int* lens_host, int B, int T,
+                             unsigned long long seed, const int* sample_ids_host, const float* x_init, const float* step_noise,
+                             float* mel_out, int denorm, hipStream_t s) {
+    DTTS_REQUIRE(bound_, "weights not bound");
+    DTTS_REQUIRE(sampler == 0 || sampler == 1, "diff_sample_from: sampler 0 (p) or 1 (ddim)");
+    DTTS_REQUIRE(eta >= 0.f, "eta must be >= 0");
+    DTTS_REQUIRE(code_emb && x_init && mel_out && sample_ids_host && B >= 1 && T >= 1, "diff_sample_from: code_emb, x_init, mel_out, sample_ids");
+    Schedule& sc = schedule(sched_id);
+    DTTS_REQUIRE(sc.kind == 0, "diff_sample_from runs on an integer-timestep schedule (dtts_diff_schedule)");
+    DTTS_REQUIRE(first_step >= 0 && first_step < sc.n, "diff_sample_from: first_step out of [0, steps of the schedule)");
+    check_lens(lens_host, B, T);
+    const int C = cfg.diff_channels, OC = cfg.diff_out_channels, MC = cfg.mel_channels;
+    const bool table = integ_table_fits(sc.n, B, C, T);                  // the whole loop's decision
+    const PairCall pc = begin_pair(code_emb, lens_host, sample_ids_host, B, T, s, table ? integ_call_bytes(sc.n, B, C, T) : 0);
+    const PairPlan& pl = pc.pl;
+    float* x = mel_out;
+    const long long xbs = (long long)MC * T;
+    if (x != x_init) DTTS_CHECK_HIP(hipMemcpyAsync(x, x_init, sizeof(float) * (size_t)B * MC * T, hipMemcpyDeviceToDevice, s));
+    const int Bi = B + pl.Nu, k_first = sc.n - 1 - first_step;           // loop position of first_step
+    float* integ_all = nullptr;
+    int k_table = k_first;
+    if (table) {
+        k_table = k_first / integ_chunk(Bi) * integ_chunk(Bi);           // the whole loop's launch that holds first_step starts here
+        std::vector<int> steps(sc.n - k_table), li(Bi);
+        for (int k = k_table; k < sc.n; ++k) steps[k - k_table] = sc.n - 1 - k;
+        for (int b = 0; b < B; ++b) li[b] = lens_host ? lens_host[b] : T;
+        for (int u = 0; u < pl.Nu; ++u) li[B + u] = pl.ulen[u];
+        integ_all = ws().f32(steps.size() * (size_t)Bi * C * T);
+        precompute_integrator(sc, pc.cbuf0, pl.lens_i, li.data(), B, pl.Nu, T, steps, integ_all, s);
+    }
+    const size_t mark = ws().mark();
+    for (int k = k_first; k < sc.n; ++k) {
+        const int i = sc.n - 1 - k;
+        Profiler::gate() = ((k - k_first) % Profiler::get().step_every) == 0;
+        ws().rewind(mark);
+        diff_forward_pair(sc, x, pc.cbuf0, pl, B, T, i, pc.out2, s, integ_all ? integ_all + (size_t)(k - k_table) * Bi * C * T : nullptr);
+        const int dn = (denorm && i == 0) ? 1 : 0;
+        const float* nz = step_noise ? step_noise + (size_t)(k - k_first) * B * MC * T : nullptr;
+        if (sampler == 1)
+            launch_ddim_update(x, xbs, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.ddim(i, eta), seed, pc.sids, i, nz, dn, s);
+        else
+            launch_diff_update(x, xbs, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.p[i], seed, pc.sids, i, nz, dn, s);
+    }
+    Profiler::gate() = true;
+    if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
+}
+
 // one DPM-Solver++(2M) step (vqvae/utils/dpm_solver.py:1176-1208 per step) of DPM schedule `sched_id` at step index `step`, x in place
 void Model::diff_step_dpm(int sched_id, float* x, float* x0_hist, const float* code_emb, const int* lens_host, int B, int T, int step,
                           float* x0_out, hipStream_t s) {

@@ -65,6 +65,23 @@ void launch_ddim_update(float* x, long long x_bs, int x_cs, const float* model_o
                         int T, int B, int C, DdimStepCoefs k, unsigned long long seed, const int* sample_ids, int step,
                         const float* noise_override, int final_denorm, hipStream_t s, float* x0_out = nullptr);
 
+struct DdimReverseCoefs {   // one step of the DDIM ODE run upwards (vqvae/utils/diffusion.py:785-817), fp32 as _extract_into_tensor hands them out
+    float sqrt_recip_ac, sqrt_recipm1_ac, cfk;
+    float sqrt_ac_next;     // sqrt(alpha_bar_next), the root taken in fp32 of the fp32 cast
+    float sqrt_1m_ac_next;  // sqrt(1 - alpha_bar_next), likewise
+};
+// One ddim_reverse_sample update on the same [2B, 2C, T] (cond | uncond) forward output as launch_ddim_update, same element walk and
+// ragged lens: CFG combine, x0 clamp, eps re-derived from the clamped x0 (a division), x <- x0 sqrt(ab_next) + sqrt(1 - ab_next) eps'.
+// No noise, no de-normalisation; every operation is rounded on its own, in the reference's order.  x0_out (optional): pred_xstart.
+void launch_ddim_reverse_update(float* x, long long x_bs, int x_cs, const float* model_out, long long m_bs, int m_cs, const int* lens,
+                                int T, int B, int C, DdimReverseCoefs k, hipStream_t s, float* x0_out = nullptr);
+
+// p_mean_variance (vqvae/utils/diffusion.py:284-386) on the same forward output: mean, variance, log_variance and pred_xstart, each a
+// dense [B,C,T]; x is read only.  Columns at or beyond lens[b] are not written.
+void launch_diff_mean_variance(const float* x, long long x_bs, int x_cs, const float* model_out, long long m_bs, int m_cs, const int* lens,
+                               int T, int B, int C, DiffStepCoefs k, float* mean, float* variance, float* log_variance, float* pred_xstart,
+                               hipStream_t s);
+
 struct DpmStepCoefs {    // one DPM-Solver++(2M) step s -> t (vqvae/utils/dpm_solver.py:547-580, 796-831), fp32 as the reference computes them
     float cfk;           // constant guidance scale: eps = eps_u + cfk (eps_c - eps_u)   (:322-330)
     float alpha_s, sigma_s;   // data prediction x0 = (x - sigma_s eps) / alpha_s, no clamp   (:433-442)

@@ -419,6 +419,91 @@ void launch_ddim_update(float* x, long long x_bs, int x_cs, const float* model_o
     DTTS_CHECK_HIP(hipGetLastError());
 }
 
+// ddim_reverse_sample update (vqvae/utils/diffusion.py:785-817 on p_mean_variance :284-386): the DDIM ODE from x_t up to x_{t+1}.
+// Same element walk and ragged lens as ddim_update_kernel; no noise.  No contraction: at t = 0 sqrt_recipm1_ac is ~0.005 and eps' takes
+// one ulp of sqrt_recip_ac x - x0 two hundred times over, so a fused multiply-add would move the result off the reference's fp32.
+__global__ void ddim_reverse_update_kernel(float* x, long long x_bs, int x_cs, const float* mo, long long m_bs, int m_cs, const int* lens,
+                                           int T, int B, int C, DdimReverseCoefs k, float* x0_out) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.y;
+    const int len = lens ? lens[b] : T;
+    float* xb = x + (long long)b * x_bs;
+    const float* mc = mo + (long long)b * m_bs;
+    const float* mu = mo + (long long)(B + b) * m_bs;
+    const int n = C * len;
+    const int nblk = (n + 3) / 4;
+    for (int blk = blockIdx.x * blockDim.x + threadIdx.x; blk < nblk; blk += gridDim.x * blockDim.x) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = blk * 4 + i;
+            if (e >= n) break;
+            const int c = e / len, t = e - c * len;
+            const float xv = xb[(long long)c * x_cs + t];
+            const float eps_c = mc[(long long)c * m_cs + t];
+            const float eps_u = mu[(long long)c * m_cs + t];
+            const float eps = (1.f + k.cfk) * eps_c - k.cfk * eps_u;
+            const float sx = k.sqrt_recip_ac * xv;
+            float x0 = sx - k.sqrt_recipm1_ac * eps;
+            x0 = fminf(fmaxf(x0, -1.f), 1.f);
+            if (x0_out) x0_out[(long long)b * C * T + (long long)c * T + t] = x0;
+            const float eps2 = (sx - x0) / k.sqrt_recipm1_ac;          // re-derived from the clamped x0: a division, as the reference
+            xb[(long long)c * x_cs + t] = x0 * k.sqrt_ac_next + k.sqrt_1m_ac_next * eps2;
+        }
+    }
+}
+
+void launch_ddim_reverse_update(float* x, long long x_bs, int x_cs, const float* model_out, long long m_bs, int m_cs, const int* lens,
+                                int T, int B, int C, DdimReverseCoefs k, hipStream_t s, float* x0_out) {
+    const int nblk = (C * T + 3) / 4;
+    hipLaunchKernelGGL(ddim_reverse_update_kernel, dim3(cdiv(nblk, 256) > 64 ? 64 : cdiv(nblk, 256), B), dim3(256), 0, s, x, x_bs, x_cs,
+                       model_out, m_bs, m_cs, lens, T, B, C, k, x0_out);
+    DTTS_CHECK_HIP(hipGetLastError());
+}
+
+// p_mean_variance (vqvae/utils/diffusion.py:284-386): the four tensors of one step, nothing sampled.  Same element walk; no contraction.
+__global__ void diff_mean_variance_kernel(const float* x, long long x_bs, int x_cs, const float* mo, long long m_bs, int m_cs,
+                                          const int* lens, int T, int B, int C, DiffStepCoefs k, float* mean, float* variance,
+                                          float* log_variance, float* pred_xstart) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.y;
+    const int len = lens ? lens[b] : T;
+    const float* xb = x + (long long)b * x_bs;
+    const float* mc = mo + (long long)b * m_bs;
+    const float* mu = mo + (long long)(B + b) * m_bs;
+    const int n = C * len;
+    const int nblk = (n + 3) / 4;
+    for (int blk = blockIdx.x * blockDim.x + threadIdx.x; blk < nblk; blk += gridDim.x * blockDim.x) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = blk * 4 + i;
+            if (e >= n) break;
+            const int c = e / len, t = e - c * len;
+            const float xv = xb[(long long)c * x_cs + t];
+            const float eps_c = mc[(long long)c * m_cs + t], vv = mc[(long long)(C + c) * m_cs + t];
+            const float eps_u = mu[(long long)c * m_cs + t];
+            const float frac = (vv + 1.f) / 2.f;
+            const float log_var = frac * k.max_log + (1.f - frac) * k.min_log;
+            const float eps = (1.f + k.cfk) * eps_c - k.cfk * eps_u;
+            float x0 = k.sqrt_recip_ac * xv - k.sqrt_recipm1_ac * eps;
+            x0 = fminf(fmaxf(x0, -1.f), 1.f);
+            const long long o = (long long)b * C * T + (long long)c * T + t;
+            mean[o] = k.coef1 * x0 + k.coef2 * xv;                     // q_posterior_mean_variance (:262-282)
+            variance[o] = expf(log_var);
+            log_variance[o] = log_var;
+            pred_xstart[o] = x0;
+        }
+    }
+}
+
+void launch_diff_mean_variance(const float* x, long long x_bs, int x_cs, const float* model_out, long long m_bs, int m_cs, const int* lens,
+                               int T, int B, int C, DiffStepCoefs k, float* mean, float* variance, float* log_variance, float* pred_xstart,
+                               hipStream_t s) {
+    const int nblk = (C * T + 3) / 4;
+    hipLaunchKernelGGL(diff_mean_variance_kernel, dim3(cdiv(nblk, 256) > 64 ? 64 : cdiv(nblk, 256), B), dim3(256), 0, s, x, x_bs, x_cs,
+                       model_out, m_bs, m_cs, lens, T, B, C, k, mean, variance, log_variance, pred_xstart);
+    DTTS_CHECK_HIP(hipGetLastError());
+}
+
 // DPM-Solver++(2M) update (vqvae/utils/dpm_solver.py:433-442 data prediction, :547-580 first order, :796-831 second order, guidance
 // :322-330).  Same element walk and ragged lens as diff_update_kernel; no noise.  Every product and difference is rounded on its own
 // (no contraction), in the reference's order: its fp32 tensors are evaluated one operation at a time.

@@ -447,6 +447,70 @@ class Runtime:
                                          int(step), int(seed), si[0], _ptr(noise), _ptr(x0), self._stream()))
         return (xo, x0) if return_x0 else xo
 
+    def diff_invert(self, x_start, code_emb, depth, sched, lens=None, return_trajectory=False):
+        """DDIM inversion (dtts_diff_invert): ddim_reverse_sample for t = 0 .. depth - 1 of schedule `sched` from x_start [B,128,T] ->
+        x at the level of step index `depth`; with return_trajectory (x, x after each step [depth,B,128,T], each step's pred_xstart)"""
+        _check(x_start, "x_start"); _check(code_emb, "code_emb")
+        B, _, T = x_start.shape
+        out = torch.zeros_like(x_start)
+        traj = torch.zeros((int(depth),) + tuple(x_start.shape), device=self.device, dtype=torch.float32) if return_trajectory else None
+        x0s = torch.zeros_like(traj) if return_trajectory else None
+        li = _ints(lens)
+        self._rc(self.lib.dtts_diff_invert(self.h, int(sched), _ptr(code_emb), li[0] if li else None, B, T, _ptr(x_start), int(depth),
+                                           _ptr(out), _ptr(traj), _ptr(x0s), self._stream()))
+        return (out, traj, x0s) if return_trajectory else out
+
+    def diff_sample_from(self, x_init, code_emb, first_step, seed, sample_ids, sched=0, sampler=0, eta=0.0, lens=None, step_noise=None,
+                         denorm=True):
+        """diff_sample_ex entered at spaced step `first_step` (dtts_diff_sample_from): x_init is x at that level, steps first_step .. 0
+        run; samplers 0 (p) and 1 (ddim)"""
+        _check(x_init, "x_init"); _check(code_emb, "code_emb"); _check(step_noise, "step_noise")
+        B, _, T = code_emb.shape
+        out = torch.zeros((B, self.cfg["diffusion"]["in_channels"], T), device=self.device, dtype=torch.float32)
+        li, si = _ints(lens), _ints(sample_ids)
+        self._rc(self.lib.dtts_diff_sample_from(self.h, int(sched), int(sampler), float(eta), int(first_step), _ptr(code_emb),
+                                                li[0] if li else None, B, T, int(seed), si[0], _ptr(x_init), _ptr(step_noise), _ptr(out),
+                                                1 if denorm else 0, self._stream()))
+        return out
+
+    def diff_reverse_step(self, x, code_emb, step, sched, lens=None, return_x0=False):
+        """one ddim_reverse_sample of schedule `sched` at spaced step `step`: x at the level of step + 1 (and pred_xstart)"""
+        _check(x, "x"); _check(code_emb, "code_emb")
+        B, _, T = x.shape
+        xo = x.clone()
+        x0 = torch.zeros_like(x) if return_x0 else None
+        li = _ints(lens)
+        self._rc(self.lib.dtts_diff_reverse_step(self.h, int(sched), _ptr(xo), _ptr(code_emb), li[0] if li else None, B, T, int(step),
+                                                 _ptr(x0), self._stream()))
+        return (xo, x0) if return_x0 else xo
+
+    def diff_mean_variance(self, x, code_emb, step, sched, lens=None):
+        """p_mean_variance of schedule `sched` at spaced step `step` -> (mean, variance, log_variance, pred_xstart), each [B,128,T]"""
+        _check(x, "x"); _check(code_emb, "code_emb")
+        B, _, T = x.shape
+        outs = [torch.zeros_like(x) for _ in range(4)]
+        li = _ints(lens)
+        self._rc(self.lib.dtts_diff_mean_variance(self.h, int(sched), _ptr(x), _ptr(code_emb), li[0] if li else None, B, T, int(step),
+                                                  _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]), self._stream()))
+        return tuple(outs)
+
+    @staticmethod
+    def ddim_reverse_table(timesteps, trained_steps=None, cond_free_k=None):
+        """host-only (no GPU): ddim_reverse_sample's fp32 scalars of the spaced schedule of `timesteps` (dtts_ddim_reverse_table) ->
+        [n, 6]: alphas_cumprod_next, sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, sqrt(ab_next), sqrt(1 - ab_next), cfk"""
+        from .config import COND_FREE_K, TRAINED_DIFFUSION_STEPS
+        trained_steps = TRAINED_DIFFUSION_STEPS if trained_steps is None else trained_steps
+        cond_free_k = COND_FREE_K if cond_free_k is None else cond_free_k
+        ts = np.ascontiguousarray(np.asarray(sorted(set(int(t) for t in timesteps)), np.int32))
+        lib = _lib.load()
+        coefs = np.zeros((len(ts), 6), np.float32)
+        nout = C.c_int(0)
+        rc = lib.dtts_ddim_reverse_table(ts.ctypes.data_as(_lib.c_int_p), len(ts), int(trained_steps), float(cond_free_k),
+                                         coefs.ctypes.data_as(_lib.c_float_p), len(ts), C.byref(nout))
+        if rc != 0:
+            raise DttsError(f"libdetail_hip error {rc} in dtts_ddim_reverse_table")
+        return coefs[:nout.value]
+
     def diff_forward_t(self, x, timestep, code_emb=None, cond_free=False, lens=None):
         """DiffusionTts.forward at MODEL timestep `timestep` in [0, 4000)"""
         _check(x, "x"); _check(code_emb, "code_emb")

@@ -1,8 +1,9 @@
 """Sampler object mirroring the subset of the reference's SpacedDiffusion that inference and evaluation use
 (vqvae/utils/diffusion.py:179-228 + 1172-1272; p_sample_loop :654-742, ddim_sample_loop :819-899, k_diffusion_sample_loop :487-581,
 sample_loop :640-652; q_sample :243-260, training_losses :930-1012; calc_bpd_loop :1114-1169, _vb_terms_bpd :903-928, _prior_bpd
-:1098-1112).  The arithmetic lives in libdetail_hip.so (dtts_diff_sample_ex, dtts_diff_q_sample, dtts_diff_training_losses,
-dtts_diff_calc_bpd); this class carries the schedule constants and the call surface."""
+:1098-1112; p_mean_variance :284-386, p_sample :445-485, ddim_sample :744-783, ddim_reverse_sample :785-817 and the progressive
+loops).  The arithmetic lives in libdetail_hip.so (dtts_diff_sample_ex, dtts_diff_sample_from, dtts_diff_invert, dtts_diff_step,
+dtts_diff_q_sample, dtts_diff_training_losses, dtts_diff_calc_bpd); this class carries the schedule constants and the call surface."""
 from __future__ import annotations
 
 import numpy as np
@@ -211,6 +212,142 @@ class SpacedDiffusion:
         if self.rescale_timesteps and sampler != "dpmsolver++":
             raise NotImplementedError("rescale_timesteps=True (float timesteps) is not implemented on the device")
 
+    # ---------------------------------------------------------------------------------------------------- single steps, inversion
+    def _step_args(self, who, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, sampler="ddim"):
+        """what the single-step entries refuse, on the host before any launch -> (runtime, schedule id, step index, x, code embedding)"""
+        self._check(sampler)
+        if clip_denoised is not True:
+            raise ValueError(f"{who}: clip_denoised must be True (the reference's p_mean_variance asserts it)")
+        if denoised_fn is not None:
+            raise ValueError(f"{who}: denoised_fn must be None (the reference's p_mean_variance asserts it)")
+        if cond_fn is not None:
+            raise ValueError(f"{who}: cond_fn (condition_mean / condition_score) is not implemented on the device")
+        ts = check_timesteps(t, x.shape[0], self.num_timesteps)
+        if len(set(ts)) != 1:
+            raise ValueError(f"{who}: every row of a call must sit at the same t (the reference's guidance ramp reads t[0]), not {ts}")
+        emb = (model_kwargs or {}).get("precomputed_aligned_embeddings")
+        if emb is None:
+            raise ValueError("precomputed_aligned_embeddings is required (as in do_spectrogram_diffusion)")
+        rt = model.rt
+        return rt, rt.diff_schedule(self.timestep_map), ts[0], x.float().contiguous(), emb
+
+    def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, *, lens=None):
+        """vqvae/utils/diffusion.py:284-386 on the device (dtts_diff_mean_variance) -> dict(mean, variance, log_variance, pred_xstart),
+        each [B,128,T]: both model forwards at timestep_map[t], the guided eps with t's ramp value, pred_xstart clamped to [-1, 1], the
+        posterior mean of it and the learned-range variance.  t [B]: one integer step for all rows.  Refusals: see ddim_reverse_sample."""
+        rt, sched, i, x, emb = self._step_args("p_mean_variance", model, x, t, clip_denoised, denoised_fn, None, model_kwargs)
+        mean, var, logvar, x0 = rt.diff_mean_variance(x, emb, i, sched, lens=lens)
+        return {"mean": mean, "variance": var, "log_variance": logvar, "pred_xstart": x0}
+
+    def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, *, noise=None, seed=0,
+                 sample_ids=None, lens=None):
+        """vqvae/utils/diffusion.py:445-485 (dtts_diff_step, sampler p) -> dict(sample, pred_xstart).  The noise of a step t != 0 is the
+        Philox draw the loops make at that step, keyed by (seed, sample_ids[b], t), unless `noise` [B,128,T] is given."""
+        rt, sched, i, x, emb = self._step_args("p_sample", model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, "p")
+        sample_ids = list(range(x.shape[0])) if sample_ids is None else sample_ids
+        xs, x0 = rt.diff_step(x, emb, i, seed, sample_ids, sched=sched, sampler=0, lens=lens, noise=noise, return_x0=True)
+        return {"sample": xs, "pred_xstart": x0}
+
+    def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0, *, noise=None,
+                    seed=0, sample_ids=None, lens=None):
+        """vqvae/utils/diffusion.py:744-783 (dtts_diff_step, sampler ddim) -> dict(sample, pred_xstart); noise as in p_sample, drawn
+        only when eta > 0 and t != 0."""
+        if eta < 0:
+            raise ValueError("eta must be >= 0")
+        rt, sched, i, x, emb = self._step_args("ddim_sample", model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs)
+        sample_ids = list(range(x.shape[0])) if sample_ids is None else sample_ids
+        xs, x0 = rt.diff_step(x, emb, i, seed, sample_ids, sched=sched, sampler=1, eta=float(eta), lens=lens, noise=noise, return_x0=True)
+        return {"sample": xs, "pred_xstart": x0}
+
+    def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0, *, lens=None):
+        """vqvae/utils/diffusion.py:785-817 on the device (dtts_diff_reverse_step): one step of the deterministic DDIM ODE upwards, from x
+        at the level of step t to the level of step t + 1 -> dict(sample, pred_xstart).  At t = num_timesteps - 1 alphas_cumprod_next
+        is 0 and the sample is the re-derived eps alone.
+
+        Refused on the host before any launch (ValueError): eta != 0; clip_denoised other than True or a denoised_fn (the reference
+        asserts both); rows at different t (the reference's guidance ramp reads t[0]); t out of [0, num_timesteps).  A
+        conditioning_free=False or rescale_timesteps=True diffuser is refused as by the sampling loops."""
+        if eta != 0.0:
+            raise ValueError("Reverse ODE only for deterministic path")
+        rt, sched, i, x, emb = self._step_args("ddim_reverse_sample", model, x, t, clip_denoised, denoised_fn, None, model_kwargs)
+        xs, x0 = rt.diff_reverse_step(x, emb, i, sched, lens=lens, return_x0=True)
+        return {"sample": xs, "pred_xstart": x0}
+
+    def invert_depth(self, depth):
+        """the depth of an inversion, checked: None is num_timesteps.  Inverting to depth d yields x at the level of step index d, which
+        ddim_sample_loop(noise=x, t_start=d) consumes for d <= num_timesteps - 1; depth num_timesteps ends at alphas_cumprod_next = 0,
+        yields pure eps' and can only feed a full loop as `noise` -> (depth, t_start or None for the full loop)"""
+        d = self.num_timesteps if depth is None else depth
+        if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or not 1 <= d <= self.num_timesteps:
+            raise ValueError(f"depth must be an integer in [1, {self.num_timesteps}], not {depth!r}")
+        return int(d), (int(d) if d < self.num_timesteps else None)
+
+    def ddim_reverse_sample_loop(self, model, x_start, model_kwargs=None, *, depth=None, lens=None, return_trajectory=False):
+        """DDIM inversion: ddim_reverse_sample iterated for t = 0 .. depth - 1 in ONE device call (dtts_diff_invert), the fast path.  The
+        reference has the step (vqvae/utils/diffusion.py:785-817) and no loop of its own; this is that step fed its own output, and
+        equals calling ddim_reverse_sample depth times bit for bit.  -> x at the level of step index `depth` [B,128,T]; with
+        return_trajectory a dict(sample, trajectory [depth,B,128,T] = x after each step, pred_xstart [depth,B,128,T]).
+
+        depth (default num_timesteps) and t_start pair up as follows: depth d <= num_timesteps - 1 is consumed by
+        ddim_sample_loop(noise=x, t_start=d); depth num_timesteps ends at alphas_cumprod_next = 0, is pure eps' and can only feed a
+        full loop as `noise` (invert_depth).  Inversion followed by DDIM at eta = 0 is NOT the identity: the guidance and the clamp of
+        pred_xstart are not invertible (the reference's own round trip on the test weights misses x_start by 0.88 max-abs from depth 5
+        of 10 and by 1.37 from depth 9)."""
+        self._check("ddim")
+        d, _ = self.invert_depth(depth)
+        emb = (model_kwargs or {}).get("precomputed_aligned_embeddings")
+        if emb is None:
+            raise ValueError("precomputed_aligned_embeddings is required (as in do_spectrogram_diffusion)")
+        rt = model.rt
+        r = rt.diff_invert(x_start.float().contiguous(), emb, d, rt.diff_schedule(self.timestep_map), lens=lens,
+                           return_trajectory=return_trajectory)
+        return {"sample": r[0], "trajectory": r[1], "pred_xstart": r[2]} if return_trajectory else r
+
+    def _progressive(self, step, model, shape, noise, seed, sample_ids, kw):
+        B = shape[0]
+        sample_ids = list(range(B)) if sample_ids is None else sample_ids
+        if noise is None:
+            raise ValueError("the progressive generators need `noise` (x_T): the loop calls draw it on the device")
+        img = noise
+        for i in range(self.num_timesteps - 1, -1, -1):
+            out = step(model, img, np.full(B, i, np.int64), seed=seed, sample_ids=sample_ids, **kw)
+            yield out
+            img = out["sample"]
+
+    def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                                  device=None, progress=False, *, seed=0, sample_ids=None, lens=None):
+        """vqvae/utils/diffusion.py:700-742: a generator over p_sample's dicts, t = num_timesteps - 1 .. 0.  A host loop, one device
+        call per step with the code-path terms evaluated inside every step: p_sample_loop is the fast path.  `noise` (x_T) is required."""
+        return self._progressive(self.p_sample, model, shape, noise, seed, sample_ids,
+                                 dict(clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs, lens=lens))
+
+    def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                                     device=None, progress=False, eta=0.0, *, seed=0, sample_ids=None, lens=None):
+        """vqvae/utils/diffusion.py:853-901: a generator over ddim_sample's dicts.  A host loop, one device call per step:
+        ddim_sample_loop is the fast path.  `noise` (x_T) is required."""
+        return self._progressive(self.ddim_sample, model, shape, noise, seed, sample_ids,
+                                 dict(clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs, eta=eta,
+                                      lens=lens))
+
+    def _loop_from(self, sampler, model, shape, noise, model_kwargs, seed, sample_ids, lens, eta, t_start, denorm=False):
+        """a sampling loop entered at step t_start: `noise` is x at that level and steps t_start .. 0 run (dtts_diff_sample_from)"""
+        self._check(sampler)
+        if sampler == "dpmsolver++":
+            raise ValueError("t_start is not available with dpmsolver++ (a multistep solver has no state below its first step)")
+        if eta < 0:
+            raise ValueError("eta must be >= 0")
+        if isinstance(t_start, bool) or not isinstance(t_start, (int, np.integer)) or not 0 <= t_start < self.num_timesteps:
+            raise ValueError(f"t_start must be an integer in [0, {self.num_timesteps}), not {t_start!r}")
+        if noise is None:
+            raise ValueError("t_start needs `noise`: x at the level of step t_start")
+        emb = (model_kwargs or {}).get("precomputed_aligned_embeddings")
+        if emb is None:
+            raise ValueError("precomputed_aligned_embeddings is required (as in do_spectrogram_diffusion)")
+        sample_ids = list(range(shape[0])) if sample_ids is None else sample_ids
+        rt = model.rt
+        return rt.diff_sample_from(noise.float().contiguous(), emb, int(t_start), seed, sample_ids, sched=rt.diff_schedule(self.timestep_map),
+                                   sampler=SAMPLERS[sampler], eta=eta, lens=lens, denorm=denorm)
+
     def _loop(self, sampler, model, shape, noise, model_kwargs, seed, sample_ids, lens, eta, denorm=False):
         self._check(sampler)
         if eta < 0:
@@ -233,21 +370,32 @@ class SpacedDiffusion:
         return rt.diff_sample_ex(emb, seed, sample_ids, sched=sched, sampler=SAMPLERS[sampler], eta=eta, lens=lens, x_init=noise,
                                  denorm=denorm)
 
-    def p_sample_loop(self, model, shape, noise=None, model_kwargs=None, progress=False, seed=0, sample_ids=None, lens=None, **_):
-        """model: a detail_tts_amd DiffusionTts; returns x_0 (normalised mel) [B,128,T] of THIS diffuser's schedule."""
+    def p_sample_loop(self, model, shape, noise=None, model_kwargs=None, progress=False, seed=0, sample_ids=None, lens=None, t_start=None,
+                      **_):
+        """model: a detail_tts_amd DiffusionTts; returns x_0 (normalised mel) [B,128,T] of THIS diffuser's schedule.  t_start = s: `noise`
+        (required then) is x at the level of step s and steps s .. 0 run, with the Philox noise the whole loop draws at those steps;
+        t_start = num_timesteps - 1 is the whole loop from x_T = noise.  None: the whole loop."""
+        if t_start is not None:
+            return self._loop_from("p", model, shape, noise, model_kwargs, seed, sample_ids, lens, 0.0, t_start)
         return self._loop("p", model, shape, noise, model_kwargs, seed, sample_ids, lens, 0.0)
 
     def ddim_sample_loop(self, model, shape, noise=None, model_kwargs=None, progress=False, eta=0.0, seed=0, sample_ids=None, lens=None,
-                         **_):
-        """vqvae/utils/diffusion.py:819-851 (ddim_sample :744-783 per step, Philox noise when eta > 0)"""
+                         t_start=None, **_):
+        """vqvae/utils/diffusion.py:819-851 (ddim_sample :744-783 per step, Philox noise when eta > 0).  t_start = s: `noise` (required
+        then) is x at the level of step s and steps s .. 0 run - what ddim_reverse_sample_loop(depth=s) yields, for s <= num_timesteps
+        - 1; an inversion to depth num_timesteps is pure eps' and feeds the whole loop (t_start None) as `noise`."""
+        if t_start is not None:
+            return self._loop_from("ddim", model, shape, noise, model_kwargs, seed, sample_ids, lens, float(eta), t_start)
         return self._loop("ddim", model, shape, noise, model_kwargs, seed, sample_ids, lens, float(eta))
 
     def k_diffusion_sample_loop(self, k_sampler, pbar, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                                device=None, model_kwargs=None, progress=False, seed=0, sample_ids=None, lens=None, **_):
+                                device=None, model_kwargs=None, progress=False, seed=0, sample_ids=None, lens=None, t_start=None, **_):
         """vqvae/utils/diffusion.py:487-581: DPM-Solver++(2M) over num_timesteps steps (vqvae/utils/dpm_solver.py, time_uniform,
         multistep, order 2) with constant guidance cond_free_k; as in the reference, `k_sampler` is ignored.  x_T = `noise` (None: the
         Philox STAGE_DIFF_INIT draw); no noise after it, no clamp.  `pbar` (may be None) is advanced by the num_timesteps model
         evaluations once the loop is enqueued."""
+        if t_start is not None:
+            raise ValueError("t_start is not available with dpmsolver++ (a multistep solver has no state below its first step)")
         if not isinstance(model_kwargs, dict):
             raise ValueError("model_kwargs must be a dict (the reference asserts it)")
         x = self._loop("dpmsolver++", model, shape, noise, model_kwargs, seed, sample_ids, lens, 0.0)

@@ -301,6 +301,44 @@ int dtts_diff_sample_ex(dtts_handle* h, int id, int sampler, float eta, const fl
 int dtts_diff_step(dtts_handle* h, int id, int sampler, float eta, float* x, const float* code_emb, const int* lens, int B, int T,
                    int step, unsigned long long seed, const int* sample_ids, const float* noise, float* x0_out, void* stream);
 
+/* DDIM inversion: GaussianDiffusion.ddim_reverse_sample (vqvae/utils/diffusion.py:785-817) iterated for t = 0, 1, .., depth - 1 on
+ * integer-timestep schedule `id`, 1 <= depth <= steps of the schedule.  Per step: both model forwards, CFG combine with step t's ramp
+ * value, x0 clamp, eps re-derived from the clamped x0, x <- x0 sqrt(ab_next) + sqrt(1 - ab_next) eps' (ab_next of the last step is 0);
+ * fp32, every operation rounded on its own, no noise, no de-normalisation.  x_start, x_out [B,128,T] (x_out = x at the level of step
+ * index `depth`; may alias x_start); x_traj, x0_traj [depth][B,128,T] (may be NULL): x after each step / each step's pred_xstart.
+ * Columns at or beyond lens[b] are left as they are.  The code-path terms are evaluated up front for exactly these steps in this order
+ * (workspace rules of dtts_diff_sample_ex, DTTS_INTEG_MAX_GB included), with launches that do not choose a summation order by their
+ * width: dtts_diff_reverse_step gives the same bits as this loop's step.  Arguments are checked before any launch; asynchronous. */
+int dtts_diff_invert(dtts_handle* h, int id, const float* code_emb, const int* lens, int B, int T, const float* x_start, int depth,
+                     float* x_out, float* x_traj, float* x0_traj, void* stream);
+
+/* dtts_diff_sample_ex entered below the top of the schedule: x_init [B,128,T] (required) is x at the level of step `first_step` in
+ * [0, steps), and steps first_step, .., 0 run.  Samplers 0 (p) and 1 (ddim) only.  Philox noise stays keyed by the step index, so a
+ * loop cut in two (dtts_diff_sample_ex with n_steps = steps - 1 - s, then this with first_step = s) draws the whole loop's noise;
+ * step_noise [first_step + 1][B,128,T] (may be NULL) replaces it, first_step's first.  first_step = steps - 1 is dtts_diff_sample_ex
+ * with x_init.  The code-path table is evaluated in the launches the whole loop makes. */
+int dtts_diff_sample_from(dtts_handle* h, int id, int sampler, float eta, int first_step, const float* code_emb, const int* lens, int B,
+                          int T, unsigned long long seed, const int* sample_ids, const float* x_init, const float* step_noise,
+                          float* mel_out, int denorm, void* stream);
+
+/* One ddim_reverse_sample (vqvae/utils/diffusion.py:785-817) of schedule `id` at spaced step `step`: x [B,128,T] IN PLACE becomes x at
+ * the level of step + 1; x0_out (may be NULL) receives pred_xstart.  The same bits as step `step` of dtts_diff_invert. */
+int dtts_diff_reverse_step(dtts_handle* h, int id, float* x, const float* code_emb, const int* lens, int B, int T, int step, float* x0_out,
+                           void* stream);
+
+/* GaussianDiffusion.p_mean_variance (vqvae/utils/diffusion.py:284-386) of schedule `id` at spaced step `step`: both model forwards, CFG
+ * combine, then mean (q_posterior of the clamped x0), variance, log_variance (learned range) and pred_xstart, each [B,128,T]; x is
+ * read only.  Columns at or beyond lens[b] of the outputs are not written. */
+int dtts_diff_mean_variance(dtts_handle* h, int id, const float* x, const float* code_emb, const int* lens, int B, int T, int step,
+                            float* mean, float* variance, float* log_variance, float* pred_xstart, void* stream);
+
+/* The fp32 scalars of ddim_reverse_sample for the spaced schedule of `timesteps` [n] (any order, duplicates ignored) over linear betas
+ * of `trained_steps`, as the reference hands them out: float64 tables, cast to fp32 by _extract_into_tensor, then sqrt and 1 - . in
+ * fp32.  HOST ONLY: no handle, no GPU.  *n_out = steps; coefs [cap][6] (may be NULL) per step {alphas_cumprod_next,
+ * sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, sqrt(alphas_cumprod_next), sqrt(1 - alphas_cumprod_next), guidance cfk =
+ * cond_free_k (1 - step / steps)}. */
+int dtts_ddim_reverse_table(const int* timesteps, int n, int trained_steps, float cond_free_k, float* coefs, int cap, int* n_out);
+
 /* DiffusionTts.forward (vqvae/diff_model.py:262-322) at MODEL timestep `timestep` in [0, diff_trained_steps), as the reference's
  * model accepts any t.  Arguments as dtts_diff_forward. */
 int dtts_diff_forward_t(dtts_handle* h, const float* x, const float* code_emb, const int* lens, int B, int T, int timestep,
