@@ -108,6 +108,18 @@ SIGNATURES = {
     "dtts_gpt_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_int_p, c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dtts_gpt_forward_losses": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, c_int_p, C.c_int, c_int_p, C.c_int, C.c_int, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dtts_voice_pool": (C.c_int, [C.c_void_p, C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dtts_gpt_generate_cond": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, C.c_int, C.POINTER(DttsGptOptions), c_int_p, c_int_p,
+                                         C.c_void_p, C.c_int, C.c_void_p]),
+    "dtts_gpt_prefill_cond": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, C.c_int, C.POINTER(DttsGptOptions), C.c_void_p,
+                                        C.c_int, C.c_void_p]),
+    "dtts_gpt_beam_generate_cond": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, C.c_int, C.POINTER(DttsGptOptions), C.c_int,
+                                              c_int_p, c_int_p, c_float_p, C.c_void_p]),
+    "dtts_gpt_latents_cond": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, c_int_p, c_int_p, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_int, C.c_void_p]),
+    "dtts_gpt_forward_losses_cond": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dtts_vq_decode_cond": (C.c_int, [C.c_void_p, c_int_p, c_int_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "dtts_diff_conditioning": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dtts_diff_timestep_independent": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dtts_diff_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

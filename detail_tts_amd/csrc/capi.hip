@@ -494,6 +494,67 @@ int dtts_gpt_forward_losses(dtts_handle* h, const float* refer, const int* refer
     DTTS_API_END(h)
 }
 
+// ---- latents in: the entries above with the conditioning encoder's output handed in (include/detail_hip.h, "voices")
+int dtts_gpt_generate_cond(dtts_handle* h, const float* cond, const int* text, const int* text_lens, int Lt_max, int B,
+                           const dtts_gpt_options* opts, int* codes_out, int* ncodes_out, float* latents_cm, int lat_stride, void* stream) {
+    DTTS_API_BEGIN
+    check_gpt_options(opts);
+    DTTS_REQUIRE(cond, "dtts_gpt_generate_cond: cond");
+    h->m->gpt_generate(nullptr, nullptr, 0, text, text_lens, Lt_max, B, *opts, codes_out, ncodes_out, latents_cm, lat_stride, (hipStream_t)stream, cond);
+    DTTS_API_END(h)
+}
+
+int dtts_gpt_prefill_cond(dtts_handle* h, const float* cond, const int* text, const int* text_lens, int Lt_max, int B,
+                          const dtts_gpt_options* opts, float* latents_cm, int lat_stride, void* stream) {
+    DTTS_API_BEGIN
+    check_gpt_options(opts);
+    DTTS_REQUIRE(cond, "dtts_gpt_prefill_cond: cond");
+    h->m->gpt_prefill(nullptr, nullptr, 0, text, text_lens, Lt_max, B, *opts, latents_cm, lat_stride, (hipStream_t)stream, cond);
+    DTTS_API_END(h)
+}
+
+int dtts_gpt_beam_generate_cond(dtts_handle* h, const float* cond, const int* text, const int* text_lens, int Lt_max, int B,
+                                const dtts_gpt_options* opts, int nrs, int* seqs_out, int* lens_out, float* scores_out, void* stream) {
+    DTTS_API_BEGIN
+    check_gpt_options(opts);
+    DTTS_REQUIRE(cond, "dtts_gpt_beam_generate_cond: cond");
+    DTTS_REQUIRE(opts->num_beams > 1, "dtts_gpt_beam_generate: options.num_beams has to be 2 .. 16");
+    DTTS_REQUIRE(nrs >= 1 && nrs <= opts->num_beams, "dtts_gpt_beam_generate: num_return_sequences outside 1 .. num_beams");
+    DTTS_REQUIRE(seqs_out && lens_out && scores_out, "dtts_gpt_beam_generate: null output");
+    h->m->gpt_beam_generate(nullptr, nullptr, 0, text, text_lens, Lt_max, B, *opts, nrs, seqs_out, lens_out, scores_out, (hipStream_t)stream, cond);
+    DTTS_API_END(h)
+}
+
+int dtts_gpt_latents_cond(dtts_handle* h, const float* cond, const int* text, const int* text_lens, int Lt_max, const int* codes,
+                          const int* ncodes, int n_max, int B, float* latents_cm, int lat_stride, void* stream) {
+    DTTS_API_BEGIN
+    DTTS_REQUIRE(cond, "dtts_gpt_latents_cond: cond");
+    h->m->gpt_latents(nullptr, nullptr, 0, text, text_lens, Lt_max, codes, ncodes, n_max, B, latents_cm, lat_stride, (hipStream_t)stream, cond);
+    DTTS_API_END(h)
+}
+
+int dtts_gpt_forward_losses_cond(dtts_handle* h, const float* cond, const int* text_ids, int Lt, const int* mel_codes, int n, int B,
+                                 float* losses_out, float* text_logprob, float* mel_logprob, float* mel_logits, void* stream) {
+    DTTS_API_BEGIN
+    DTTS_REQUIRE(cond, "dtts_gpt_forward_losses_cond: cond");
+    h->m->gpt_forward_losses(nullptr, nullptr, 0, text_ids, Lt, mel_codes, n, B, losses_out, text_logprob, mel_logprob, mel_logits,
+                             (hipStream_t)stream, cond);
+    DTTS_API_END(h)
+}
+
+int dtts_vq_decode_cond(dtts_handle* h, const int* codes, const int* ncodes, int nmax, const float* g_vq, int B, float* mel_out, void* stream) {
+    DTTS_API_BEGIN
+    DTTS_REQUIRE(g_vq, "dtts_vq_decode_cond: g_vq");
+    h->m->vq_decode(codes, ncodes, nmax, nullptr, nullptr, 0, B, mel_out, (hipStream_t)stream, g_vq);
+    DTTS_API_END(h)
+}
+
+int dtts_voice_pool(dtts_handle* h, const float* v, const float* weights, int S, int n, int D, float* out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->voice_pool(v, weights, S, n, D, out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
 int dtts_diff_conditioning(dtts_handle* h, const float* refer, const int* lens, int B, int Tmax, float* cond_out, void* stream) {
     DTTS_API_BEGIN
     h->m->diff_conditioning(refer, lens, B, Tmax, cond_out, (hipStream_t)stream);

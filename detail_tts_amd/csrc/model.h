@@ -290,13 +290,17 @@ public:
     // one p_sample at `step` on x in place (unit entry of the sampler parity tests)
     void diff_p_sample(float* x, const float* code_emb, const int* lens_host, int B, int T, int step, unsigned long long seed,
                        const int* sample_ids_host, const float* noise, float* x0_out, hipStream_t s);
+    // ---- voices (voice.hip): out [S, D] = sum_j w[s][j] v[s, j, :] / sum_j w[s][j] over the n clips of speaker s; w_host nullptr = all 1
+    void voice_pool(const float* v, const float* w_host, int S, int n, int D, float* out, hipStream_t s);
     // ---- stage A
+    // Every stage-A entry that takes the prompt mel `refer` also takes cond_in [B, gpt_dim] (device): the conditioning encoder's output,
+    // computed earlier (a voice, voice.hip).  With cond_in the encoder is not launched and refer / refer_lens_host / Tr are not read.
     void gpt_generate(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host,
                       int Lt_max, int B, const dtts_gpt_options& o, int* codes_host, int* ncodes_host, float* latents_cm,
-                      int lat_stride, hipStream_t s);
+                      int lat_stride, hipStream_t s, const float* cond_in = nullptr);
     // decode session: prefill (+ first token) -> decode steps (eager / captured hipGraphs) -> results
     void gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host, int Lt_max,
-                     int B, const dtts_gpt_options& o, float* latents_cm, int lat_stride, hipStream_t s);
+                     int B, const dtts_gpt_options& o, float* latents_cm, int lat_stride, hipStream_t s, const float* cond_in = nullptr);
     void gpt_decode_step(hipStream_t s);
     int gpt_decode(int n_steps, hipStream_t s);
     int gpt_all_finished(hipStream_t s);
@@ -304,7 +308,8 @@ public:
     int gpt_steps() const { return gs_.active ? gs_.steps : 0; }
     // beam search: B utterances x o.num_beams beams, whole utterances per session; per utterance the best nrs finished hypotheses (HOST)
     void gpt_beam_generate(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host, int Lt_max,
-                           int B, const dtts_gpt_options& o, int nrs, int* seqs_host, int* lens_host, float* scores_host, hipStream_t s);
+                           int B, const dtts_gpt_options& o, int nrs, int* seqs_host, int* lens_host, float* scores_host, hipStream_t s,
+                           const float* cond_in = nullptr);
     void gpt_beam_finish(int nrs, int* seqs_host, int* lens_host, float* scores_host, hipStream_t s);
     void op_beam_step(const float* logits, int U, int V, const dtts_gpt_options& o, int step, const int* prompt_host, int prompt_len,
                       int* run_seq, float* run_score, int* fin_seq, float* fin_score, int* fin_flag, int* fin_len, int* unsat, int* done,
@@ -317,7 +322,7 @@ public:
                                hipStream_t s);
     void gpt_latents(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host,
                      int Lt_max, const int* codes_host, const int* ncodes_host, int n_max, int B, float* latents_cm, int lat_stride,
-                     hipStream_t s);
+                     hipStream_t s, const float* cond_in = nullptr);
     // log p(targets[b][k] | latents_cm[b, :, k]) under the unprocessed distribution (gpt_score.hip); targets / ntargets HOST; asynchronous
     void gpt_score(const float* latents_cm, int lat_stride, const int* targets_host, const int* ntargets_host, int n_max, int B,
                    float* logprob_out, float* logits_out, hipStream_t s);
@@ -325,7 +330,8 @@ public:
     // losses_out DEVICE [2] = (loss_text, loss_mel), the plain means over all B (Lt + 2) / B (n + 2) positions; optional DEVICE outputs:
     // text_logprob [B][Lt + 2], mel_logprob [B][n + 2] (log-softmax at the targets), mel_logits [B][V][n + 2].  Needs gpt.text_head.
     void gpt_forward_losses(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, int Lt, const int* codes_host, int n,
-                            int B, float* losses_out, float* text_logprob, float* mel_logprob, float* mel_logits, hipStream_t s);
+                            int B, float* losses_out, float* text_logprob, float* mel_logprob, float* mel_logits, hipStream_t s,
+                            const float* cond_in = nullptr);
     // ---- stage C
     void mel_style(const MelStyleW& w, const float* mel, const int* lens_dev, const int* lens_host, int B, int T, float* g_out,
                    hipStream_t s, bool padded_batch = false);
@@ -373,7 +379,7 @@ public:
                    float* stats, hipStream_t s, bool padded_batch = false);
     // ---- VQ decode path (infer_gpt)
     void vq_decode(const int* codes_host, const int* ncodes_host, int nmax, const float* refer, const int* refer_lens_host, int Tr,
-                   int B, float* mel_out, hipStream_t s);
+                   int B, float* mel_out, hipStream_t s, const float* g_in = nullptr);
     // ---- prompt front-end
     void resample(const float* x, int B, int L, const float* kernel, int orig, int neu, int width, float* y, int Lout, hipStream_t s);
     void mel_spectrogram(const float* wav, const int* lens_host, int B, int L, int n_fft, int hop, float* mel_out, int Tmax, hipStream_t s,
@@ -489,7 +495,7 @@ private:
     };
     GptForced gpt_teacher_forced(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host,
                                  int Lt_max, const int* codes_host, const int* ncodes_host, int n_max, int B, size_t extra_ws_bytes,
-                                 hipStream_t s);
+                                 hipStream_t s, const float* cond_in = nullptr);
     // one head through gpt_score.hip over columns of lat [B][C][lat_cs] (targets range-checked by the caller), rows in groups of 16
     void score_head(const PackedConv& head, const float* lat, long long lat_bs, int lat_cs, const int* targets_host, const int* ntargets_host,
                     int n_max, int B, float* logprob_out, float* logits_out, hipStream_t s);
@@ -640,12 +646,13 @@ private:
         bool valid = false;
         int Tr = 0, Lt_max = 0, B = 0, lat_stride = 0;
         bool has_refer_lens = false, has_text_lens = false;
+        bool has_cond = false;            // the session was given cond [B, C] instead of a prompt mel: gpt_replay_ holds that vector
         std::vector<int> refer_lens, text, text_lens, sample_ids, forced_codes, prompt_codes, prompt_lens, suppress, begin_suppress;
         std::vector<unsigned long long> row_seeds;
         dtts_gpt_options o;
         float* latents_cm = nullptr;
     } replay_;
-    Arena gpt_replay_;                    // device copy of the prompt mel of the running session
+    Arena gpt_replay_;                    // device copy of the prompt mel (or of the cond vector) of the running session
     bool replaying_ = false;
     bool gpt_use_token_kernel() const;
     Arena gpt_state_;                     // decode session state (fixed addresses: the captured graphs point into it)

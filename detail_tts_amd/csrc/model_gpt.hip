@@ -300,8 +300,11 @@ static bool processors_mask_on(const dtts_gpt_options& o) { return o.n_suppress_
 // (KV cache, residual rows, sampler state, device control block) lives in the handle's own arena, whose addresses stay fixed from call
 // to call, so the captured decode graphs stay valid.
 void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host,
-                        int Lt_max, int B, const dtts_gpt_options& o, float* latents_cm, int lat_stride, hipStream_t s) {
+                        int Lt_max, int B, const dtts_gpt_options& o, float* latents_cm, int lat_stride, hipStream_t s,
+                        const float* cond_in) {
     DTTS_REQUIRE(bound_ && has_gpt_, "gpt weights not bound");
+    DTTS_REQUIRE(cond_in || (refer && Tr >= 1), "gpt_prefill: neither a prompt mel nor its conditioning latent");
+    if (cond_in) Tr = 0;                             // (sizes the encoder's scratch below: none)
     DTTS_REQUIRE(B >= 1 && B <= GEMV_MAXB, "a GPT decode session holds 1..16 sequences (dtts_gpt_generate groups larger batches)");
     DTTS_REQUIRE(o.max_generate_length >= 1 && o.max_generate_length + 1 <= cfg.gpt_max_mel_pos, "max_generate_length");
     DTTS_REQUIRE(!latents_cm || lat_stride >= o.max_generate_length, "latent buffer too small");
@@ -317,9 +320,10 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
         GptReplay& r = replay_;
         r.valid = false;
         if (tok_ok_ && !tok_failed_ && B <= GPT_TOKEN_ROWS) {
-            const size_t nref = (size_t)B * cfg.mel_channels * Tr;
+            const size_t nref = cond_in ? (size_t)B * cfg.gpt_dim : (size_t)B * cfg.mel_channels * Tr;
             gpt_replay_.ensure(sizeof(float) * nref + 256);
-            DTTS_CHECK_HIP(hipMemcpyAsync(gpt_replay_.f32(nref), refer, sizeof(float) * nref, hipMemcpyDeviceToDevice, s));
+            DTTS_CHECK_HIP(hipMemcpyAsync(gpt_replay_.f32(nref), cond_in ? cond_in : refer, sizeof(float) * nref, hipMemcpyDeviceToDevice, s));
+            r.has_cond = cond_in != nullptr;
             r.Tr = Tr; r.Lt_max = Lt_max; r.B = B; r.lat_stride = lat_stride; r.latents_cm = latents_cm;
             r.has_refer_lens = refer_lens_host != nullptr;
             r.has_text_lens = text_lens_host != nullptr;
@@ -420,17 +424,21 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
     gs_.kv_layer = kv_layer;
     gs_.steps = 0;
     gs_.active = false;
-    ws().ensure(std::max(prefill_ws(B, C, Lp) + sizeof(float) * (size_t)B * C * Lp,
-                        sizeof(float) * ((size_t)5 * B * (C / 2) * Tr + (size_t)B * C * Tr + (size_t)B * C)) + 65536);
+    // (the encoder's scratch sits ON TOP of emb: a 6-row beam group with a 64-frame prompt and a 10-column prefix overflowed the arena
+    // while the two were sized side by side)
+    ws().ensure(sizeof(float) * (size_t)B * C * Lp +
+                std::max(prefill_ws(B, C, Lp), sizeof(float) * ((size_t)5 * B * (C / 2) * Tr + (size_t)B * C * Tr + (size_t)B * C)) + 65536);
     float* emb = ws().f32((size_t)B * C * Lp);
-    float* cond = ws().f32((size_t)B * C);
-    {
+    const float* cond = cond_in;                     // UnifiedVoice.compute_embeddings' cond_latents (gpt/model.py:492-513)
+    if (!cond_in) {
+        float* enc = ws().f32((size_t)B * C);
         std::vector<int> rl(B);
         for (int b = 0; b < B; ++b) rl[b] = refer_lens_host ? refer_lens_host[b] : Tr;
         const int* d_rl = upload_ints(rl.data(), B, s);
         const size_t m = ws().mark();
-        mel_style(gpt_cond_, refer, d_rl, rl.data(), B, Tr, cond, s);        // gpt/model.py:521-524
+        mel_style(gpt_cond_, refer, d_rl, rl.data(), B, Tr, enc, s);         // gpt/model.py:521-524
         ws().rewind(m);
+        cond = enc;
     }
     const int* d_ids = upload_ints(ids.data(), B * tl_max, s);
     const int* d_tl = upload_ints(tl.data(), B, s);
@@ -844,9 +852,9 @@ bool Model::gpt_replay_failed(const GptCtl& hctl, hipStream_t s) {
     replaying_ = true;
     try {
         gpt_replay_.reset();
-        const float* refer = gpt_replay_.f32((size_t)r.B * cfg.mel_channels * r.Tr);
-        gpt_prefill(refer, r.has_refer_lens ? r.refer_lens.data() : nullptr, r.Tr, r.text.data(), r.has_text_lens ? r.text_lens.data() : nullptr,
-                    r.Lt_max, r.B, o, r.latents_cm, r.lat_stride, s);
+        const float* kept = gpt_replay_.f32(r.has_cond ? (size_t)r.B * cfg.gpt_dim : (size_t)r.B * cfg.mel_channels * r.Tr);
+        gpt_prefill(r.has_cond ? nullptr : kept, r.has_refer_lens ? r.refer_lens.data() : nullptr, r.Tr, r.text.data(),
+                    r.has_text_lens ? r.text_lens.data() : nullptr, r.Lt_max, r.B, o, r.latents_cm, r.lat_stride, s, r.has_cond ? kept : nullptr);
         for (int i = 1; i < steps; ++i) gpt_step_launches(s);
         gs_.steps = steps;
         if (!o.suppress_eos && failed_looked_finished)
@@ -899,7 +907,7 @@ void Model::gpt_finish(int* codes_host, int* ncodes_host, hipStream_t s) {
 // (8 rows) run group after group; the finish flags are polled once per 16-token graph (never per token).
 void Model::gpt_generate(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host,
                          int Lt_max, int B, const dtts_gpt_options& o, int* codes_host, int* ncodes_host, float* latents_cm,
-                         int lat_stride, hipStream_t s) {
+                         int lat_stride, hipStream_t s, const float* cond_in) {
     DTTS_REQUIRE(B >= 1, "gpt batch");
     DTTS_REQUIRE(o.sample_ids, "sample_ids");
     DTTS_REQUIRE(o.num_beams <= 1, "dtts_gpt_generate: num_beams > 1 returns hypotheses and scores: call dtts_gpt_beam_generate");
@@ -913,9 +921,9 @@ void Model::gpt_generate(const float* refer, const int* refer_lens_host, int Tr,
         if (o.row_seeds) og.row_seeds = o.row_seeds + g0;
         if (o.prompt_codes) og.prompt_codes = o.prompt_codes + (size_t)g0 * o.prompt_stride;
         if (o.prompt_lens) og.prompt_lens = o.prompt_lens + g0;
-        gpt_prefill(refer + (size_t)g0 * cfg.mel_channels * Tr, refer_lens_host ? refer_lens_host + g0 : nullptr, Tr,
+        gpt_prefill(cond_in ? nullptr : refer + (size_t)g0 * cfg.mel_channels * Tr, refer_lens_host ? refer_lens_host + g0 : nullptr, Tr,
                     text_host + (size_t)g0 * Lt_max, text_lens_host ? text_lens_host + g0 : nullptr, Lt_max, nb, og,
-                    latents_cm ? latents_cm + (size_t)g0 * C * lat_stride : nullptr, lat_stride, s);
+                    latents_cm ? latents_cm + (size_t)g0 * C * lat_stride : nullptr, lat_stride, s, cond_in ? cond_in + (size_t)g0 * C : nullptr);
         while (gs_.steps < G) {
             if (!o.suppress_eos && gpt_all_finished(s)) break;
             gpt_decode(chunk, s);
@@ -959,13 +967,14 @@ void Model::gpt_beam_finish(int nrs, int* seqs_host, int* lens_host, float* scor
 // utterances.  The K prefills of an utterance are computed K times (sharing them is a follow-up).
 void Model::gpt_beam_generate(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host,
                               int Lt_max, int B, const dtts_gpt_options& o, int nrs, int* seqs_host, int* lens_host, float* scores_host,
-                              hipStream_t s) {
+                              hipStream_t s, const float* cond_in) {
     DTTS_REQUIRE(B >= 1, "gpt batch");
     const int K = o.num_beams, G = o.max_generate_length, chunk = gpt_graph_chunk();
     DTTS_REQUIRE(K > 1 && K <= BEAM_MAXK && nrs >= 1 && nrs <= K, "gpt_beam_generate: num_beams 2 .. 16, num_return_sequences 1 .. num_beams");
-    DTTS_REQUIRE(refer && text_host && Lt_max >= 0 && Tr >= 1, "gpt_beam_generate: operands");
+    DTTS_REQUIRE((cond_in || (refer && Tr >= 1)) && text_host && Lt_max >= 0, "gpt_beam_generate: operands");
     const int per = GEMV_MAXB / K;
-    const size_t mel = (size_t)cfg.mel_channels * Tr;
+    const float* src = cond_in ? cond_in : refer;    // what a beam row repeats: the utterance's cond vector, or its prompt mel
+    const size_t mel = cond_in ? (size_t)cfg.gpt_dim : (size_t)cfg.mel_channels * Tr;
     gpt_beam_in_.ensure(sizeof(float) * mel * GEMV_MAXB + 4096);
     for (int g0 = 0; g0 < B; g0 += per) {
         const int nu = std::min(per, B - g0), R = nu * K;
@@ -975,8 +984,8 @@ void Model::gpt_beam_generate(const float* refer, const int* refer_lens_host, in
         if (o.prompt_codes) { pc.assign((size_t)R * std::max(o.prompt_stride, 1), 0); pl.assign(R, 0); }
         for (int r = 0; r < R; ++r) {
             const int b = g0 + r / K;
-            DTTS_CHECK_HIP(hipMemcpyAsync(rf + mel * r, refer + mel * b, sizeof(float) * mel, hipMemcpyDeviceToDevice, s));
-            rl[r] = refer_lens_host ? refer_lens_host[b] : Tr;
+            DTTS_CHECK_HIP(hipMemcpyAsync(rf + mel * r, src + mel * b, sizeof(float) * mel, hipMemcpyDeviceToDevice, s));
+            rl[r] = !cond_in && refer_lens_host ? refer_lens_host[b] : Tr;
             tl[r] = text_lens_host ? text_lens_host[b] : Lt_max;
             std::copy(text_host + (size_t)b * Lt_max, text_host + (size_t)(b + 1) * Lt_max, tx.begin() + (size_t)r * Lt_max);
             sid[r] = o.sample_ids ? o.sample_ids[b] : 0;
@@ -990,7 +999,7 @@ void Model::gpt_beam_generate(const float* refer, const int* refer_lens_host, in
         og.sample_ids = sid.data();
         og.row_seeds = nullptr;
         if (o.prompt_codes) { og.prompt_codes = pc.data(); og.prompt_lens = pl.data(); }
-        gpt_prefill(rf, rl.data(), Tr, tx.data(), tl.data(), Lt_max, R, og, nullptr, 0, s);
+        gpt_prefill(cond_in ? nullptr : rf, rl.data(), Tr, tx.data(), tl.data(), Lt_max, R, og, nullptr, 0, s, cond_in ? rf : nullptr);
         while (gs_.steps < G) {
             if (gpt_all_finished(s)) break;
             gpt_decode(chunk, s);
@@ -1257,8 +1266,10 @@ void Model::op_sample_logits_opts(const float* logits, int R, int V, const dtts_
 // The teacher-forced pass over [cond | 255, text, 0 | 8192, codes, 8193] (gpt/model.py:463-476, 392-403): see model.h
 Model::GptForced Model::gpt_teacher_forced(const float* refer, const int* refer_lens_host, int Tr, const int* text_host,
                                            const int* text_lens_host, int Lt_max, const int* codes_host, const int* ncodes_host, int n_max,
-                                           int B, size_t extra_ws_bytes, hipStream_t s) {
+                                           int B, size_t extra_ws_bytes, hipStream_t s, const float* cond_in) {
     DTTS_REQUIRE(bound_ && has_gpt_, "gpt weights not bound");
+    DTTS_REQUIRE(cond_in || (refer && Tr >= 1), "neither a prompt mel nor its conditioning latent");
+    if (cond_in) Tr = 0;
     const int C = cfg.gpt_dim;
     GptForced f;
     std::vector<int> ids;
@@ -1294,17 +1305,19 @@ Model::GptForced Model::gpt_teacher_forced(const float* refer, const int* refer_
                (size_t)sizeof(float) * ((size_t)5 * B * (C / 2) * Tr + (size_t)B * C * Tr) + 65536 + extra_ws_bytes);
     float* emb = ws().f32((size_t)B * C * L);
     float* enc = ws().f32((size_t)B * C * L);
-    float* cond = ws().f32((size_t)B * C);
+    float* enc_cond = ws().f32((size_t)B * C);
     int* d_mids = ws().i32(mids.size());
     DTTS_CHECK_HIP(hipMemcpyAsync(d_mids, mids.data(), sizeof(int) * mids.size(), hipMemcpyHostToDevice, s));
     DTTS_CHECK_HIP(hipStreamSynchronize(s));
-    std::vector<int> rl(B);
-    for (int b = 0; b < B; ++b) rl[b] = refer_lens_host ? refer_lens_host[b] : Tr;
-    const int* d_rl = upload_ints(rl.data(), B, s);
-    {
+    const float* cond = cond_in;
+    if (!cond_in) {
+        std::vector<int> rl(B);
+        for (int b = 0; b < B; ++b) rl[b] = refer_lens_host ? refer_lens_host[b] : Tr;
+        const int* d_rl = upload_ints(rl.data(), B, s);
         const size_t m = ws().mark();
-        mel_style(gpt_cond_, refer, d_rl, rl.data(), B, Tr, cond, s);
+        mel_style(gpt_cond_, refer, d_rl, rl.data(), B, Tr, enc_cond, s);
         ws().rewind(m);
+        cond = enc_cond;
     }
     const int* d_ids = upload_ints(ids.data(), B * tl_max, s);
     const int* d_tl = upload_ints(tl.data(), B, s);
@@ -1325,9 +1338,9 @@ Model::GptForced Model::gpt_teacher_forced(const float* refer, const int* refer_
 // codes [B][n_max] host, n[b] valid -> latents_cm [B, C, lat_stride] (columns 0..n[b]-1)
 void Model::gpt_latents(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host,
                         int Lt_max, const int* codes_host, const int* ncodes_host, int n_max, int B, float* latents_cm, int lat_stride,
-                        hipStream_t s) {
+                        hipStream_t s, const float* cond_in) {
     const int C = cfg.gpt_dim;
-    const GptForced f = gpt_teacher_forced(refer, refer_lens_host, Tr, text_host, text_lens_host, Lt_max, codes_host, ncodes_host, n_max, B, 0, s);
+    const GptForced f = gpt_teacher_forced(refer, refer_lens_host, Tr, text_host, text_lens_host, Lt_max, codes_host, ncodes_host, n_max, B, 0, s, cond_in);
     std::vector<int> c0(B), nn(B);
     for (int b = 0; b < B; ++b) {
         c0[b] = 1 + f.tl[b];                                // column of the start_mel input
@@ -1404,18 +1417,19 @@ void Model::gpt_score(const float* latents_cm, int lat_stride, const int* target
 // targets (build_aligned_inputs_and_targets, :372-375) [text, 0, 0] and [codes, 8193, 8193]; text logits from columns 1 .. Lt + 2 of
 // final_norm's output, mel logits from its last n + 2 columns (:402-415) - both heads read the teacher-forced pass's own buffer.
 void Model::gpt_forward_losses(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, int Lt, const int* codes_host, int n,
-                               int B, float* losses_out, float* text_logprob, float* mel_logprob, float* mel_logits, hipStream_t s) {
+                               int B, float* losses_out, float* text_logprob, float* mel_logprob, float* mel_logits, hipStream_t s,
+                               const float* cond_in) {
     DTTS_REQUIRE(bound_ && has_gpt_, "gpt weights not bound");
     DTTS_REQUIRE(has_text_head_, "gpt_forward_losses: gpt.text_head.weight is not bound (the checkpoint carries no text_head)");
     DTTS_REQUIRE(B >= 1 && Lt >= 0 && n >= 0, "gpt_forward_losses: B, Lt, n");
-    DTTS_REQUIRE(refer && losses_out && text_host && codes_host, "gpt_forward_losses: null argument");
+    DTTS_REQUIRE((refer || cond_in) && losses_out && text_host && codes_host, "gpt_forward_losses: null argument");
     DTTS_REQUIRE(Lt + 2 <= 4096 && n + 2 <= 4096, "gpt_forward_losses: at most 4096 positions per span (gpt_score's limit)");
     DTTS_REQUIRE(text_head_.Cout == cfg.gpt_text_tokens && text_head_.Cout > text_head_.CoutP - 128, "gpt_forward_losses: packed text_head shape");
     const int C = cfg.gpt_dim, nt = Lt + 2, nm = n + 2;
     const size_t lp_floats = (size_t)B * nt + (size_t)B * nm;
     // ids and codes are range-checked in here, before any launch
     const GptForced f = gpt_teacher_forced(refer, refer_lens_host, Tr, text_host, nullptr, Lt, codes_host, nullptr, n, B,
-                                           sizeof(float) * lp_floats + 4 * 256, s);
+                                           sizeof(float) * lp_floats + 4 * 256, s, cond_in);
     if (!text_logprob) text_logprob = ws().f32((size_t)B * nt);
     if (!mel_logprob) mel_logprob = ws().f32((size_t)B * nm);
     std::vector<int> tt((size_t)B * nt, 0), tm((size_t)B * nm, 8193), ntt(B, nt), ntm(B, nm);

@@ -232,6 +232,7 @@ void Model::op_mel_style(const char* which, const float* mel, const int* lens_ho
     const MelStyleW* w = nullptr;
     if (n == "ref_enc" && has_vocoder_) w = &ref_enc_;
     if (n == "gpt.conditioning_encoder" && has_gpt_) w = &gpt_cond_;
+    if (n == "vq_ref_enc" && has_vq_) w = &vq_ref_enc_;
     DTTS_REQUIRE(w, "unknown / unbound MelStyleEncoder");
     ws().ensure(mel_style_ws(B, w->hidden, w->out, T) + 4096);
     std::vector<int> l(B);
@@ -1140,8 +1141,10 @@ void Model::vq_encode(const float* mel, const int* lens_host, int B, int T, int*
 
 // infer_gpt's decode: recon = vq_dec(quantizer.decode(codes) + vq_ref_enc(refer * mask, mask))   (vqvae/model_24k.py:828-845)
 void Model::vq_decode(const int* codes_host, const int* ncodes_host, int nmax, const float* refer, const int* refer_lens_host, int Tr,
-                      int B, float* mel_out, hipStream_t s) {
+                      int B, float* mel_out, hipStream_t s, const float* g_in) {
     DTTS_REQUIRE(bound_ && has_vq_, "vq weights not bound");
+    DTTS_REQUIRE(g_in || (refer && Tr >= 1), "vq_decode: neither a prompt mel nor its vq_ref_enc latent");
+    if (g_in) Tr = 0;                                // g_in [B, 4 inter_channels]: vq_ref_enc's output, computed earlier (a voice); no encoder launch
     const int inter = cfg.inter_channels, C = 4 * inter;
     std::vector<int> n1(B), n2(B), n4(B), rl(B);
     for (int b = 0; b < B; ++b) {
@@ -1155,7 +1158,7 @@ void Model::vq_decode(const int* codes_host, const int* ncodes_host, int nmax, c
     }
     ws().ensure(sizeof(float) * ((size_t)2 * B * C * nmax + (size_t)B * 2 * inter * 2 * nmax + (size_t)B * inter * 4 * nmax + (size_t)B * C) +
                sizeof(int) * (size_t)B * nmax + sizeof(float) * ((size_t)5 * B * 128 * Tr + (size_t)B * C * Tr) + 65536);
-    float* g = ws().f32((size_t)B * C);
+    float* g_enc = ws().f32((size_t)B * C);
     float* lat = ws().f32((size_t)B * C * nmax);
     float* ln = ws().f32((size_t)B * C * nmax);
     float* u1 = ws().f32((size_t)B * 2 * inter * 2 * nmax);
@@ -1167,10 +1170,12 @@ void Model::vq_decode(const int* codes_host, const int* ncodes_host, int nmax, c
     const int* d2 = upload_ints(n2.data(), B, s);
     const int* d4 = upload_ints(n4.data(), B, s);
     const int* drl = upload_ints(rl.data(), B, s);
-    {
+    const float* g = g_in;
+    if (!g_in) {
         const size_t m = ws().mark();
-        mel_style(vq_ref_enc_, refer, drl, rl.data(), B, Tr, g, s);
+        mel_style(vq_ref_enc_, refer, drl, rl.data(), B, Tr, g_enc, s);
         ws().rewind(m);
+        g = g_enc;
     }
     hipLaunchKernelGGL(vq_gather_kernel, dim3(nmax, B), dim3(256), 0, s, vq_table_, dcodes, nmax, d1, g, C, nmax, lat);
     DTTS_CHECK_HIP(hipGetLastError());

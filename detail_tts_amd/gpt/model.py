@@ -52,10 +52,35 @@ class UnifiedVoice:
         tl = torch.as_tensor(text_lengths).reshape(-1).tolist()
         return [r[: int(n)] for r, n in zip(t, tl)]
 
+    def _speaker(self, speech_conditioning_latent, cond_lengths, cond_latents):
+        """-> (refer, cond): the prompt mel [B,128,T] as a contiguous fp32 tensor, or - with cond_latents [B, model_dim] - None and the
+        latents.  Both given, neither, cond_lengths beside cond_latents, or a wrong width: ValueError before any launch."""
+        if cond_latents is None:
+            if speech_conditioning_latent is None:
+                raise ValueError("neither speech_conditioning_latent (the prompt mel) nor cond_latents is given")
+            return speech_conditioning_latent.float().contiguous(), None
+        if speech_conditioning_latent is not None or cond_lengths is not None:
+            raise ValueError("cond_latents stand in the place of speech_conditioning_latent / cond_lengths: those have to be None")
+        cond = torch.as_tensor(cond_latents)
+        if cond.dim() != 2 or cond.shape[1] != self.model_dim:
+            raise ValueError(f"cond_latents have to be [B, {self.model_dim}], but are {tuple(cond.shape)}")
+        return None, cond.to(self.rt.device, torch.float32).contiguous()
+
+    def get_conditioning(self, speech_conditioning_input, cond_lengths=None):
+        """gpt/model.py:419-427: mel [B,128,T], or n clips per speaker [B,n,128,T] -> [B, 768], the conditioning encoder's output, for n
+        clips their mean (conds.mean(dim=1)): the B n clips run as one batch, then one pool launch (csrc/voice.hip).  cond_lengths
+        [B] / [B,n]: every clip's valid length (an extension).  What cond_latents= takes."""
+        from ..voice import check_clips
+        S, n, T, lens = check_clips(speech_conditioning_input, None if speech_conditioning_input.dim() == 4 else cond_lengths,
+                                    cond_lengths if speech_conditioning_input.dim() == 4 else None)
+        x = speech_conditioning_input.to(self.rt.device, torch.float32).reshape(S * n, -1, T).contiguous()
+        g = self.rt.mel_style("gpt.conditioning_encoder", x, lens)
+        return g if n == 1 else self.rt.voice_pool(g.view(S, n, -1))
+
     def inference_speech_tortoise(self, speech_conditioning_latent, cond_lengths, text_inputs, input_tokens=None,
                                   num_return_sequences=1, max_generate_length=None, typical_sampling=False, typical_mass=.9,
-                                  text_lengths=None, seed=0, sample_ids=None, suppress_eos=False, forced_uniforms=None,
-                                  **hf_generate_kwargs):
+                                  text_lengths=None, seed=0, sample_ids=None, suppress_eos=False, forced_uniforms=None, *,
+                                  cond_latents=None, **hf_generate_kwargs):
         """gpt/model.py:514-545.  hf_generate_kwargs understood: do_sample, top_p, top_k, temperature, repetition_penalty, length_penalty
         (inert without beams), and HF's remaining decode-time processors, served by the device sampler in HF's order
         (gpt/decode_options.py states the counting rules): no_repeat_ngram_size (1 .. 16), min_length, min_new_tokens,
@@ -71,15 +96,19 @@ class UnifiedVoice:
         copies independently: `sample_ids` of length B * n name their noise streams, or of length B: copy r of row b draws from
         sample_ids[b] + r - the expanded ids must be distinct, else ValueError), `input_tokens [rows, k]` (mel tokens in front of the generated ones; with num_return_sequences = n > 1 the
         reference tiles them AND lets HF expand the batch again: n * n rows of the single prompt, reproduced), `typical_sampling`
-        (HF TypicalLogitsWarper(mass=typical_mass), which HF applies between the repetition penalty and the temperature)."""
+        (HF TypicalLogitsWarper(mass=typical_mass), which HF applies between the repetition penalty and the temperature).
+
+        cond_latents [B, 768] (here, in inference_speech_valle, forward and mel_logprobs): the conditioning encoder's output handed in -
+        the role of the reference's compute_embeddings(cond_latents, text_inputs) (gpt/model.py:492-513), e.g. get_conditioning's of n
+        clips or a Voice's gpt member; speech_conditioning_latent and cond_lengths are then None and the encoder is not launched."""
         return self._generate(speech_conditioning_latent, cond_lengths, text_inputs, None, input_tokens, num_return_sequences,
                               max_generate_length, typical_sampling, typical_mass, text_lengths, seed, sample_ids, suppress_eos,
-                              forced_uniforms, hf_generate_kwargs)
+                              forced_uniforms, hf_generate_kwargs, cond_latents)
 
     def inference_speech_valle(self, speech_conditioning_latent, cond_lengths, text_inputs, mel_codes, input_tokens=None,
                                num_return_sequences=1, max_generate_length=None, typical_sampling=False, typical_mass=.9,
-                               text_lengths=None, seed=0, sample_ids=None, suppress_eos=False, forced_uniforms=None,
-                               **hf_generate_kwargs):
+                               text_lengths=None, seed=0, sample_ids=None, suppress_eos=False, forced_uniforms=None, *,
+                               cond_latents=None, **hf_generate_kwargs):
         """gpt/model.py:546-579: inference_speech_tortoise continued from an acoustic prompt.  mel_codes [B, m] (or a list of B
         one-dimensional arrays: per-row lengths are an extension, the reference takes a rectangle) are mel codes in [0, 8192), e.g.
         SynthesizerTrn.encode's of a prompt mel.  Returns the GENERATED tokens only (input_tokens in front, as in tortoise); every other
@@ -96,11 +125,11 @@ class UnifiedVoice:
             raise ValueError("inference_speech_valle: mel_codes (the acoustic prompt) is required")
         return self._generate(speech_conditioning_latent, cond_lengths, text_inputs, mel_codes, input_tokens, num_return_sequences,
                               max_generate_length, typical_sampling, typical_mass, text_lengths, seed, sample_ids, suppress_eos,
-                              forced_uniforms, hf_generate_kwargs)
+                              forced_uniforms, hf_generate_kwargs, cond_latents)
 
     def _generate(self, speech_conditioning_latent, cond_lengths, text_inputs, mel_codes, input_tokens, num_return_sequences,
                   max_generate_length, typical_sampling, typical_mass, text_lengths, seed, sample_ids, suppress_eos, forced_uniforms,
-                  hf_generate_kwargs):
+                  hf_generate_kwargs, cond_latents=None):
         """What inference_speech_tortoise and inference_speech_valle share (gpt/model.py:528-545 and :561-579 differ in fake_inputs only):
         the row expansion, the id checks, the greedy mapping and the decode session; mel_codes = None is the tortoise session."""
         nrs = int(num_return_sequences)
@@ -118,9 +147,10 @@ class UnifiedVoice:
         do_sample = False if beams else bool(hf_generate_kwargs.get("do_sample", True))
         processors = validate_decode_options({k: v for k, v in hf_generate_kwargs.items() if k not in ("num_beams", "length_penalty", "early_stopping")},
                                              do_sample=do_sample, strict=False)      # (ValueError before any launch)
+        refer, cond = self._speaker(speech_conditioning_latent, cond_lengths, cond_latents)      # (ValueError before any launch)
+        dev = (refer if cond is None else cond).device
         if beams:
-            refer = speech_conditioning_latent.float().contiguous()
-            B = refer.shape[0]
+            B = (refer if cond is None else cond).shape[0]
             cl = None if cond_lengths is None else torch.as_tensor(cond_lengths).reshape(-1).tolist()
             prompt = None
             if mel_codes is not None:
@@ -130,14 +160,13 @@ class UnifiedVoice:
             seqs, lens, scores = self.rt.gpt_generate_beams(
                 refer, cl, self._texts(text_inputs, text_lengths), beams, num_return_sequences=nrs, max_generate_length=G, length_penalty=lp,
                 early_stopping={0: False, 1: True, 2: "never"}[es], repetition_penalty=hf_generate_kwargs.get("repetition_penalty", 1.0),
-                suppress_eos=suppress_eos, prompt_codes=prompt, processors=processors or None)
+                suppress_eos=suppress_eos, prompt_codes=prompt, processors=processors or None, cond=cond)
             # rows change lineage while decoding: no decode-time latents (forward(return_latent=True) on the chosen codes gives them)
             self.last_latents, self.last_ncodes = None, lens.reshape(-1)
             self.last_scores = torch.from_numpy(scores.reshape(-1).copy())
-            out = torch.from_numpy(seqs.reshape(B * nrs, G)[:, :int(lens.max())].astype(np.int64)).to(refer.device)
+            out = torch.from_numpy(seqs.reshape(B * nrs, G)[:, :int(lens.max())].astype(np.int64)).to(dev)
             return (out, self.last_scores) if return_scores else out
-        refer = speech_conditioning_latent.float().contiguous()
-        B = refer.shape[0]
+        B = (refer if cond is None else cond).shape[0]
         it = None
         if input_tokens is not None:
             it = torch.as_tensor(input_tokens).cpu().numpy().astype(np.int32)
@@ -160,7 +189,8 @@ class UnifiedVoice:
             prompt = prompt_rows(mel_codes, B)
         ids = list(range(B * nrs)) if sample_ids is None else list(sample_ids)
         if nrs > 1:
-            refer = refer.repeat_interleave(nrs, 0).contiguous()
+            refer = None if refer is None else refer.repeat_interleave(nrs, 0).contiguous()
+            cond = None if cond is None else cond.repeat_interleave(nrs, 0).contiguous()
             cl = None if cl is None else [v for v in cl for _ in range(nrs)]
             texts = [t for t in texts for _ in range(nrs)]
             prompt = None if prompt is None else [p for p in prompt for _ in range(nrs)]
@@ -186,13 +216,14 @@ class UnifiedVoice:
             refer, cl, texts, seed, ids, max_generate_length=G, repetition_penalty=hf_generate_kwargs.get("repetition_penalty", 1.0),
             suppress_eos=suppress_eos, forced_uniforms=forced_uniforms, forced_codes=forced, forced_fill=-1,
             typical_mass=float(typical_mass) if typical_sampling else 0.0, **samp, **({} if prompt is None else dict(prompt_codes=prompt)),
-            **({"processors": processors} if processors else {}))
+            **({"processors": processors} if processors else {}), cond=cond)
         self.last_latents, self.last_ncodes = lat, ncodes
         n = int(ncodes.max())
-        return torch.from_numpy(codes[:, :n].astype(np.int64)).to(refer.device)
+        return torch.from_numpy(codes[:, :n].astype(np.int64)).to(dev)
 
     def forward(self, speech_conditioning_latent, cond_lengths, text_inputs, text_lengths, mel_codes, wav_lengths, types=None,
-                text_first=True, raw_mels=None, return_attentions=False, return_latent=False, clip_inputs=False, *, return_logits=True):
+                text_first=True, raw_mels=None, return_attentions=False, return_latent=False, clip_inputs=False, *, return_logits=True,
+                cond_latents=None):
         """gpt/model.py:429-491.
 
         return_latent=True (the inference use, vqvae/model_24k.py:796-799) -> latents [B, n, 768]; rows are ragged there (text_lengths
@@ -206,14 +237,13 @@ class UnifiedVoice:
         if types is not None or raw_mels is not None or not text_first or (return_attentions and not return_latent):
             raise NotImplementedError("UnifiedVoice.forward: types, raw_mels, text_first=False and return_attentions=True are not implemented "
                                       "on the device")
+        refer, cond = self._speaker(speech_conditioning_latent, cond_lengths, cond_latents)
         if not return_latent:
-            refer = speech_conditioning_latent.float().contiguous()
             cl = None if cond_lengths is None else torch.as_tensor(cond_lengths).reshape(-1).tolist()
             text, codes = forward_inputs(_host_ints(text_inputs), _host_ints(text_lengths), _host_ints(mel_codes), _host_ints(wav_lengths),
                                          self.mel_length_compression, self.stop_mel_token, clip_inputs)
-            losses, logits = self.rt.gpt_forward_losses(refer, cl, text, codes, want_logits=bool(return_logits))
+            losses, logits = self.rt.gpt_forward_losses(refer, cl, text, codes, want_logits=bool(return_logits), cond=cond)
             return losses[0], losses[1], logits
-        refer = speech_conditioning_latent.float().contiguous()
         cl = None if cond_lengths is None else torch.as_tensor(cond_lengths).reshape(-1).tolist()
         codes = torch.as_tensor(mel_codes).cpu().numpy().astype(np.int32)
         wl = torch.as_tensor(wav_lengths).reshape(-1).tolist()
@@ -224,18 +254,18 @@ class UnifiedVoice:
             if end < row.shape[-1]:
                 row[end:] = self.stop_mel_token
             code_list.append(row)
-        lat = self.rt.gpt_latents(refer, cl, self._texts(text_inputs, text_lengths), code_list)
+        lat = self.rt.gpt_latents(refer, cl, self._texts(text_inputs, text_lengths), code_list, cond=cond)
         return lat.permute(0, 2, 1).contiguous()
 
-    def mel_logprobs(self, speech_conditioning_latent, cond_lengths, text_inputs, text_lengths, mel_codes_list):
+    def mel_logprobs(self, speech_conditioning_latent, cond_lengths, text_inputs, text_lengths, mel_codes_list, *, cond_latents=None):
         """Teacher-forced log-probabilities: for every row the fp32 numpy array log p(c_k | prompt, c_1 .. c_{k-1}), k = 1 .. n, of its
         codes c_1 .. c_n under the model's unprocessed distribution = log_softmax(mel_logits)[c_k] of the reference's forward
         (gpt/model.py:408-415, 479) at the positions of the codes.  Rows may differ in length; append the stop token (8193) to a row to
         score its stop as well.  Runs rt.gpt_latents, then rt.gpt_score on those latents (no [B, V, n] logits are materialised)."""
-        refer = speech_conditioning_latent.float().contiguous()
+        refer, cond = self._speaker(speech_conditioning_latent, cond_lengths, cond_latents)
         cl = None if cond_lengths is None else torch.as_tensor(cond_lengths).reshape(-1).tolist()
         codes = [np.asarray(torch.as_tensor(c).cpu().numpy() if not isinstance(c, np.ndarray) else c, np.int32).reshape(-1) for c in mel_codes_list]
-        lat = self.rt.gpt_latents(refer, cl, self._texts(text_inputs, text_lengths), codes)
+        lat = self.rt.gpt_latents(refer, cl, self._texts(text_inputs, text_lengths), codes, cond=cond)
         lp = self.rt.gpt_score(lat, codes).cpu().numpy()
         return [lp[b, : len(c)].copy() for b, c in enumerate(codes)]
 

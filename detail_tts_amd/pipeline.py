@@ -31,18 +31,27 @@ class Request:
     n: list = None
     a_done: object = None
     tr: dict = None             # this request's entry of SynthesizerTrn.stream_trace
+    voice: object = None        # the request's speaker as a Voice (voice.py) in the place of refer: S = 1 or B until stage A expands it
 
 
-def normalize_request(text, text_length, refer, refer_lengths, seed=None, sample_ids=None, forced_codes=None, *, batch=True):
+def normalize_request(text, text_length, refer, refer_lengths, seed=None, sample_ids=None, forced_codes=None, *, batch=True,
+                      speaker=None, dims=None):
     """the arguments of infer() / one request dict of infer_stream() -> Request: B, integer rl, a drawn seed when none is given,
     default sample ids range(B), per-row int32 text arrays cut at their own lengths.  batch=False keeps the first row only (the
-    reference: text = text[0].unsqueeze(0) ..., vqvae/model_24k.py:775-778).  No device transfer: refer stays where it is."""
+    reference: text = text[0].unsqueeze(0) ..., vqvae/model_24k.py:775-778).  No device transfer: refer stays where it is.
+    speaker: a Voice in the place of (refer, refer_lengths), which are then None (voice.check_speaker: ValueError otherwise, and on
+    S not in {1, B} or widths other than the model's `dims`); the Request carries it as `voice`, refer = None and rl = zeros."""
     text = torch.as_tensor(text)
-    refer = torch.as_tensor(refer)
     tl = torch.as_tensor(text_length).reshape(-1).tolist()
-    rl = [int(v) for v in torch.as_tensor(refer_lengths).reshape(-1).tolist()]
+    if speaker is not None or refer is None:
+        from .voice import check_speaker
+        check_speaker(speaker, refer, refer_lengths, text.shape[0] if batch else 1, dims)
+        rl = [0] * text.shape[0]
+    else:
+        refer = torch.as_tensor(refer)
+        rl = [int(v) for v in torch.as_tensor(refer_lengths).reshape(-1).tolist()]
     if not batch:
-        text, refer, tl, rl = text[:1], refer[:1], tl[:1], rl[:1]
+        text, refer, tl, rl = text[:1], None if refer is None else refer[:1], tl[:1], rl[:1]
         if forced_codes is not None:
             forced_codes = forced_codes[:1]
     B = text.shape[0]
@@ -50,7 +59,7 @@ def normalize_request(text, text_length, refer, refer_lengths, seed=None, sample
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     sids = list(range(B)) if sample_ids is None else list(sample_ids)
     texts = [text[b, : int(tl[b])].cpu().numpy().astype(np.int32) for b in range(B)]
-    return Request(B=B, rl=rl, seed=seed, sids=sids, texts=texts, refer=refer, forced=forced_codes)
+    return Request(B=B, rl=rl, seed=seed, sids=sids, texts=texts, refer=refer, forced=forced_codes, voice=speaker)
 
 
 def group_requests(requests, pair=False):
@@ -102,6 +111,15 @@ def merge_refer(sts, dev):
     return refer
 
 
+def merge_cond(rt, sts):
+    """the session's conditioning latents [rows, 768] when a request of it carries a voice: its gpt member; a request that carries a
+    prompt mel gets the conditioning encoder's own launch on its rectangle (no request carries a voice: None, and merge_refer serves)"""
+    if all(st.voice is None for st in sts):
+        return None
+    conds = [st.voice.gpt if st.voice is not None else rt.mel_style("gpt.conditioning_encoder", st.refer, st.rl) for st in sts]
+    return conds[0] if len(conds) == 1 else torch.cat(conds, 0).contiguous()
+
+
 def split_latents(lat, sts, ns):
     """each request's rows of the session's decode-time latents (== the return_latent pass), cut at its longest utterance"""
     r0 = 0
@@ -123,7 +141,7 @@ def stage_b(model, st, sampler_id, eta, prec, *, sched=None, sched_ts=None, mark
     """stage B of one request on the current stream (vqvae/model_24k.py:802-804) -> (mel, lens_t).  sched None: the schedule of
     `sched_ts` is looked up (built on first use) between the embedding and the sampling launches."""
     rt = model.rt
-    cond = rt.diff_conditioning(st.refer, st.rl)
+    cond = st.voice.diffusion if st.voice is not None else rt.diff_conditioning(st.refer, st.rl)
     code_emb = rt.diff_timestep_independent(st.lat, cond, st.n)
     mark("diff_cond")
     lens_t = [4 * v for v in st.n]
@@ -157,15 +175,15 @@ def stage_c(rt, stream, home, mel, st, lens_t, noise_scale, chunk, *, wait=True,
     return wav, done, ticket
 
 
-def stream_stage_a(rt, sa, group, kw, token_wgs, trace=None):
+def stream_stage_a(rt, sa, group, kw, token_wgs, trace=None, dims=None):
     """infer_stream's stage A of one group on stream `sa` -> its Requests, with refer on the device and lat / n / a_done set.
 
     One request, or TWO requests of <= 8 utterances each as ONE decode session (<= 16 rows, per-row Philox seeds): the 308 MB of GPT
     weights stream once per token for both, and the chain of ~12 400 dependent launches is paid once.  A request of more than 16
     rows is decoded session after session (gpt_generate).  `kw`: the sampling arguments; next(token_wgs): a session's token-kernel width."""
     dev = rt.device
-    sts = [normalize_request(r["text"], r["text_length"], r["refer"], r["refer_lengths"], r.get("seed"), r.get("sample_ids"),
-                             r.get("forced_codes")) for r in group]
+    sts = [normalize_request(r["text"], r["text_length"], r.get("refer"), r.get("refer_lengths"), r.get("seed"), r.get("sample_ids"),
+                             r.get("forced_codes"), speaker=r.get("speaker"), dims=dims) for r in group]
     tr = None
     if trace is not None:
         tr = dict(host_a0=time.perf_counter(), ev_a0=torch.cuda.Event(enable_timing=True), ev_a1=torch.cuda.Event(enable_timing=True))
@@ -173,7 +191,10 @@ def stream_stage_a(rt, sa, group, kw, token_wgs, trace=None):
         if tr:
             tr["ev_a0"].record(sa)
         for st in sts:
-            st.refer = st.refer.to(dev, torch.float32).contiguous()
+            if st.voice is not None:
+                st.voice = st.voice.for_batch(st.B)
+            else:
+                st.refer = st.refer.to(dev, torch.float32).contiguous()
             if tr:
                 st.tr = dict(tr, ev_b0=torch.cuda.Event(enable_timing=True), ev_b1=torch.cuda.Event(enable_timing=True),
                              ev_c1=torch.cuda.Event(enable_timing=True))
@@ -181,12 +202,15 @@ def stream_stage_a(rt, sa, group, kw, token_wgs, trace=None):
         session = sum(st.B for st in sts) <= SESSION_ROWS
         if session:
             rl, texts, sids, seeds, forced = merge_session(sts)
-            rt.gpt_prefill(merge_refer(sts, dev), rl, texts, seeds, sids, forced_codes=forced, **kw, token_wgs=next(token_wgs))
+            cond = merge_cond(rt, sts)
+            rt.gpt_prefill(merge_refer(sts, dev) if cond is None else None, rl, texts, seeds, sids, forced_codes=forced, **kw,
+                           token_wgs=next(token_wgs), cond=cond)
             if kw["suppress_eos"]:                         # fixed length: the whole decode is enqueued without a host round trip
                 rt.gpt_decode(kw["max_generate_length"])
         else:                                              # more than one decode session: group after group, on this thread / stream
             st = sts[0]
-            _, ncodes, lat = rt.gpt_generate(st.refer, st.rl, st.texts, st.seed, st.sids, forced_codes=st.forced, **kw)
+            _, ncodes, lat = rt.gpt_generate(st.refer, st.rl, st.texts, st.seed, st.sids, forced_codes=st.forced, **kw,
+                                             cond=None if st.voice is None else st.voice.gpt)
         for st in sts:
             if st.tr:
                 st.tr["host_a1"] = time.perf_counter()

@@ -34,6 +34,19 @@ def _check(t, name):
         raise DttsError(f"{name}: expected a contiguous float32 CUDA tensor")
 
 
+def _speaker_shape(refer, cond, width=None, who="cond"):
+    """the speaker of a stage-A / VQ entry: the prompt mel refer [B,128,Tr] or, in its place, the latent its encoder makes of it,
+    cond [B, width] (a Voice's member) -> (B, Tr); Tr = 0 with a latent.  ValueError before any library call."""
+    if (refer is None) == (cond is None):
+        raise ValueError(f"give the prompt mel `refer` or its latent `{who}`: one of the two, not both and not neither")
+    if cond is None:
+        B, _, Tr = refer.shape
+        return B, Tr
+    if cond.dim() != 2 or (width is not None and cond.shape[1] != width):
+        raise ValueError(f"`{who}` has to be [B, {width}], but is {tuple(cond.shape)}")
+    return cond.shape[0], 0
+
+
 ALL_PARTS = ("diffusion", "gpt", "vocoder", "vq", "frontend")
 
 
@@ -99,6 +112,11 @@ class Runtime:
                                         self._offsets.ctypes.data_as(_lib.c_u64_p), self._numels.ctypes.data_as(_lib.c_u64_p),
                                         n, self._stream())
         self._rc(rc)
+
+    def has_tensor(self, prefix):
+        """whether the bound blob carries a tensor whose name starts with `prefix` (optional parts: "vq_ref_enc.", "gpt.text_head.")"""
+        p = prefix.encode()
+        return any(n.startswith(p) for n in self._names)
 
     def set_option(self, key, value):
         self._rc(self.lib.dtts_set_option(self.h, key.encode(), int(value)))
@@ -193,18 +211,26 @@ class Runtime:
         o.min_p, o.epsilon_cutoff = p.get("min_p", 0.0), p.get("epsilon_cutoff", 0.0)
         return keep
 
+    def _check_cond(self, cond):
+        """a conditioning latent handed in: a contiguous float32 CUDA tensor [B, model_dim] of THIS model (ValueError / DttsError before the call)"""
+        if cond is not None and cond.shape[1] != self.cfg["gpt"]["model_dim"]:
+            raise ValueError(f"`cond` has to be [B, {self.cfg['gpt']['model_dim']}], but is {tuple(cond.shape)}")
+        _check(cond, "cond")
+
     def gpt_generate(self, refer, refer_lens, texts, seed, sample_ids, max_generate_length=600, top_k=50, top_p=0.8,
                      temperature=0.8, repetition_penalty=2.0, suppress_eos=False, forced_uniforms=None, forced_codes=None, forced_fill=8193, typical_mass=0.0, token_wgs=0, prompt_codes=None,
-                     processors=None):
-        """-> (codes int32 [B,G] incl. stop, ncodes [B], latents_cm float32 cuda [B,768,G]).  prompt_codes ([B, m] or a list of B
+                     processors=None, cond=None):
+        """-> (codes int32 [B,G] incl. stop, ncodes [B], latents_cm float32 cuda [B,768,G]).  cond cuda [B,768] with refer = None: the
+        conditioning encoder's output handed in (dtts_gpt_generate_cond), here and in gpt_prefill / gpt_generate_beams / gpt_latents /
+        gpt_forward_losses.  prompt_codes ([B, m] or a list of B
         one-dimensional arrays): the acoustic prompt of inference_speech_valle, see gpt_prefill.  processors: None or a dict of HF's
         remaining decode-time keywords (gpt/decode_options.py: no_repeat_ngram_size, min_length, min_new_tokens,
         exponential_decay_length_penalty, suppress_tokens, begin_suppress_tokens, min_p, epsilon_cutoff)."""
-        B, _, Tr = refer.shape
+        B, Tr = _speaker_shape(refer, cond)
         text, tl = self._pad_text(texts)
         G = int(max_generate_length)
         prompt = self._prompt(prompt_codes, B, tl, G)          # (refusals come before any library call)
-        _check(refer, "refer"); _check(forced_uniforms, "forced_uniforms")
+        _check(refer, "refer"); self._check_cond(cond); _check(forced_uniforms, "forced_uniforms")
         si = _ints(sample_ids)
         rl = _ints(refer_lens if refer_lens is not None else [Tr] * B)
         o = _lib.DttsGptOptions()
@@ -233,6 +259,11 @@ class Runtime:
         codes = np.zeros((B, G), np.int32)
         ncodes = np.zeros((B,), np.int32)
         lat = torch.zeros((B, self.cfg["gpt"]["model_dim"], G), device=self.device, dtype=torch.float32)
+        if cond is not None:
+            self._rc(self.lib.dtts_gpt_generate_cond(self.h, _ptr(cond), text.ctypes.data_as(_lib.c_int_p), tl.ctypes.data_as(_lib.c_int_p),
+                                                     text.shape[1], B, C.byref(o), codes.ctypes.data_as(_lib.c_int_p),
+                                                     ncodes.ctypes.data_as(_lib.c_int_p), _ptr(lat), G, self._stream()))
+            return codes, ncodes, lat
         self._rc(self.lib.dtts_gpt_generate(self.h, _ptr(refer), rl[0], Tr, text.ctypes.data_as(_lib.c_int_p),
                                             tl.ctypes.data_as(_lib.c_int_p), text.shape[1], B, C.byref(o),
                                             codes.ctypes.data_as(_lib.c_int_p), ncodes.ctypes.data_as(_lib.c_int_p), _ptr(lat), G,
@@ -242,7 +273,7 @@ class Runtime:
     # decode session (include/detail_hip.h: dtts_gpt_prefill / _decode_step / _decode / _all_finished / _finish), <= 16 rows
     def gpt_prefill(self, refer, refer_lens, texts, seed, sample_ids, max_generate_length=600, top_k=50, top_p=0.8, temperature=0.8,
                     repetition_penalty=2.0, suppress_eos=False, forced_uniforms=None, forced_codes=None, forced_fill=8193, typical_mass=0.0, token_wgs=0, prompt_codes=None,
-                    processors=None):
+                    processors=None, cond=None):
         """conditioning encoder + prefill + first token; returns the latents tensor [B,768,G] the steps fill column by column.
         processors: as in gpt_generate (the session decodes under them; None / {}: off).
 
@@ -250,11 +281,11 @@ class Runtime:
         rectangle): the acoustic prompt of UnifiedVoice.inference_speech_valle (gpt/model.py:546-579).  The prefill then covers
         [cond | text | 1, 8192, prompt], the codes returned are the generated ones only, and the latents are the hidden states
         with the prompt in context (not gpt_latents of the generated codes alone).  gpt/prompt.py states the layout and the checks."""
-        B, _, Tr = refer.shape
+        B, Tr = _speaker_shape(refer, cond)
         text, tl = self._pad_text(texts)
         G = int(max_generate_length)
         prompt = self._prompt(prompt_codes, B, tl, G)          # (refusals come before any library call)
-        _check(refer, "refer"); _check(forced_uniforms, "forced_uniforms")
+        _check(refer, "refer"); self._check_cond(cond); _check(forced_uniforms, "forced_uniforms")
         si = _ints(sample_ids)
         rl = _ints(refer_lens if refer_lens is not None else [Tr] * B)
         o = _lib.DttsGptOptions()
@@ -280,8 +311,12 @@ class Runtime:
                 fc[b, :len(c)] = np.asarray(c, np.int32)
             o.forced_codes = fc.ctypes.data_as(_lib.c_int_p)
         lat = torch.zeros((B, self.cfg["gpt"]["model_dim"], G), device=self.device, dtype=torch.float32)
-        self._rc(self.lib.dtts_gpt_prefill(self.h, _ptr(refer), rl[0], Tr, text.ctypes.data_as(_lib.c_int_p), tl.ctypes.data_as(_lib.c_int_p),
-                                           text.shape[1], B, C.byref(o), _ptr(lat), G, self._stream()))
+        if cond is not None:
+            self._rc(self.lib.dtts_gpt_prefill_cond(self.h, _ptr(cond), text.ctypes.data_as(_lib.c_int_p), tl.ctypes.data_as(_lib.c_int_p),
+                                                    text.shape[1], B, C.byref(o), _ptr(lat), G, self._stream()))
+        else:
+            self._rc(self.lib.dtts_gpt_prefill(self.h, _ptr(refer), rl[0], Tr, text.ctypes.data_as(_lib.c_int_p), tl.ctypes.data_as(_lib.c_int_p),
+                                               text.shape[1], B, C.byref(o), _ptr(lat), G, self._stream()))
         self._session = (B, G, lat, forced_uniforms)      # keeps the device buffers of the session alive
         return lat
 
@@ -310,10 +345,10 @@ class Runtime:
         self._session = None
         return codes, ncodes, lat
 
-    def gpt_latents(self, refer, refer_lens, texts, codes_list):
+    def gpt_latents(self, refer, refer_lens, texts, codes_list, cond=None):
         """teacher-forced latents (UnifiedVoice.forward(return_latent=True)) -> cuda [B,768,n_max] channel-major"""
-        _check(refer, "refer")
-        B, _, Tr = refer.shape
+        B, Tr = _speaker_shape(refer, cond)
+        _check(refer, "refer"); self._check_cond(cond)
         text, tl = self._pad_text(texts)
         nn = np.array([len(c) for c in codes_list], np.int32)
         nmax = int(nn.max())
@@ -322,6 +357,11 @@ class Runtime:
             codes[b, :len(c)] = np.asarray(c, np.int32)
         rl = _ints(refer_lens if refer_lens is not None else [Tr] * B)
         lat = torch.zeros((B, self.cfg["gpt"]["model_dim"], nmax), device=self.device, dtype=torch.float32)
+        if cond is not None:
+            self._rc(self.lib.dtts_gpt_latents_cond(self.h, _ptr(cond), text.ctypes.data_as(_lib.c_int_p), tl.ctypes.data_as(_lib.c_int_p),
+                                                    text.shape[1], codes.ctypes.data_as(_lib.c_int_p), nn.ctypes.data_as(_lib.c_int_p), nmax, B,
+                                                    _ptr(lat), nmax, self._stream()))
+            return lat
         self._rc(self.lib.dtts_gpt_latents(self.h, _ptr(refer), rl[0], Tr, text.ctypes.data_as(_lib.c_int_p), tl.ctypes.data_as(_lib.c_int_p),
                                            text.shape[1], codes.ctypes.data_as(_lib.c_int_p), nn.ctypes.data_as(_lib.c_int_p), nmax, B,
                                            _ptr(lat), nmax, self._stream()))
@@ -347,12 +387,12 @@ class Runtime:
                                          nmax, B, _ptr(out), _ptr(logits), self._stream()))
         return (out, logits) if want_logits else out
 
-    def gpt_forward_losses(self, refer, refer_lens, text, codes, want_logits=True, want_logprobs=False):
+    def gpt_forward_losses(self, refer, refer_lens, text, codes, want_logits=True, want_logprobs=False, cond=None):
         """UnifiedVoice.forward's loss mode on a rectangular batch (dtts_gpt_forward_losses): refer cuda [B,128,Tr], text int [B,Lt] and
         codes int [B,n] host arrays as they stand after clip_inputs / set_mel_padding -> (losses cuda fp32 [2] = (loss_text, loss_mel),
         mel_logits cuda [B, V, n+2] or None[, text_logprob cuda [B, Lt+2], mel_logprob cuda [B, n+2] with want_logprobs]).  Asynchronous."""
-        _check(refer, "refer")
-        B, _, Tr = refer.shape
+        B, Tr = _speaker_shape(refer, cond)
+        _check(refer, "refer"); self._check_cond(cond)
         text = np.ascontiguousarray(np.asarray(text, np.int32))
         codes = np.ascontiguousarray(np.asarray(codes, np.int32))
         if text.ndim != 2 or codes.ndim != 2 or text.shape[0] != B or codes.shape[0] != B:
@@ -363,10 +403,31 @@ class Runtime:
         logits = torch.zeros((B, self.cfg["gpt"]["number_mel_codes"], n + 2), device=self.device, dtype=torch.float32) if want_logits else None
         tlp = torch.zeros((B, Lt + 2), device=self.device, dtype=torch.float32) if want_logprobs else None
         mlp = torch.zeros((B, n + 2), device=self.device, dtype=torch.float32) if want_logprobs else None
-        self._rc(self.lib.dtts_gpt_forward_losses(self.h, _ptr(refer), rl[0], Tr, text.ctypes.data_as(_lib.c_int_p), Lt,
-                                                  codes.ctypes.data_as(_lib.c_int_p), n, B, _ptr(losses), _ptr(tlp), _ptr(mlp), _ptr(logits),
-                                                  self._stream()))
+        if cond is not None:
+            self._rc(self.lib.dtts_gpt_forward_losses_cond(self.h, _ptr(cond), text.ctypes.data_as(_lib.c_int_p), Lt,
+                                                           codes.ctypes.data_as(_lib.c_int_p), n, B, _ptr(losses), _ptr(tlp), _ptr(mlp),
+                                                           _ptr(logits), self._stream()))
+        else:
+            self._rc(self.lib.dtts_gpt_forward_losses(self.h, _ptr(refer), rl[0], Tr, text.ctypes.data_as(_lib.c_int_p), Lt,
+                                                      codes.ctypes.data_as(_lib.c_int_p), n, B, _ptr(losses), _ptr(tlp), _ptr(mlp), _ptr(logits),
+                                                      self._stream()))
         return (losses, logits, tlp, mlp) if want_logprobs else (losses, logits)
+
+    def voice_pool(self, v, weights=None):
+        """out[s, d] = sum_j w[s, j] v[s, j, d] / sum_j w[s, j] (dtts_voice_pool): v cuda [S, n, D], weights host [S, n] (finite, >= 0,
+        a positive sum per speaker) or None (the plain mean) -> cuda [S, D].  fp32, j ascending, no fma; one live clip is copied."""
+        _check(v, "v")
+        if v.dim() != 3 or min(v.shape) < 1:
+            raise ValueError(f"voice_pool: v has to be [S, n, D], but is {tuple(v.shape)}")
+        S, n, D = v.shape
+        w = None
+        if weights is not None:
+            from .voice import check_weights
+            w = check_weights(weights, S, n)
+        out = torch.empty((S, D), device=self.device, dtype=torch.float32)
+        self._rc(self.lib.dtts_voice_pool(self.h, _ptr(v), w.ctypes.data_as(_lib.c_float_p) if w is not None else None, S, n, D, _ptr(out),
+                                          self._stream()))
+        return out
 
     # ------------------------------------------------------------------ stage B
     def diff_conditioning(self, refer, lens=None):
@@ -988,15 +1049,18 @@ class Runtime:
     def mel_style(self, which, mel, lens=None):
         _check(mel, "mel")
         B, _, T = mel.shape
-        out = torch.empty((B, self.cfg["vaegan"]["gin_channels"]), device=self.device, dtype=torch.float32)
+        v = self.cfg["vaegan"]
+        width = {"gpt.conditioning_encoder": self.cfg["gpt"]["model_dim"], "vq_ref_enc": 4 * v["inter_channels"]}.get(which, v["gin_channels"])
+        out = torch.empty((B, width), device=self.device, dtype=torch.float32)
         li = _ints(lens)
         self._rc(self.lib.dtts_op_mel_style(self.h, which.encode(), _ptr(mel), li[0] if li else None, B, T, _ptr(out), self._stream()))
         return out
 
-    def vq_decode(self, codes_list, refer, refer_lens=None):
-        """infer_gpt's decode: list of int arrays (codes without the stop token) + refer [B,128,Tr] -> mel cuda [B,128,4*nmax]"""
-        _check(refer, "refer")
-        B, _, Tr = refer.shape
+    def vq_decode(self, codes_list, refer, refer_lens=None, g_vq=None):
+        """infer_gpt's decode: list of int arrays (codes without the stop token) + refer [B,128,Tr] -> mel cuda [B,128,4*nmax];
+        g_vq cuda [B, 4 inter_channels] with refer = None: vq_ref_enc's output handed in (dtts_vq_decode_cond)"""
+        B, Tr = _speaker_shape(refer, g_vq, 4 * self.cfg["vaegan"]["inter_channels"], "g_vq")
+        _check(refer, "refer"); _check(g_vq, "g_vq")
         nn = np.array([len(c) for c in codes_list], np.int32)
         nmax = int(nn.max())
         codes = np.zeros((B, nmax), np.int32)
@@ -1004,6 +1068,10 @@ class Runtime:
             codes[b, :len(c)] = np.asarray(c, np.int32)
         rl = _ints(refer_lens if refer_lens is not None else [Tr] * B)
         mel = torch.zeros((B, self.cfg["data"]["n_mel_channels"], 4 * nmax), device=self.device, dtype=torch.float32)
+        if g_vq is not None:
+            self._rc(self.lib.dtts_vq_decode_cond(self.h, codes.ctypes.data_as(_lib.c_int_p), nn.ctypes.data_as(_lib.c_int_p), nmax, _ptr(g_vq), B,
+                                                  _ptr(mel), self._stream()))
+            return mel
         self._rc(self.lib.dtts_vq_decode(self.h, codes.ctypes.data_as(_lib.c_int_p), nn.ctypes.data_as(_lib.c_int_p), nmax, _ptr(refer), rl[0], Tr, B,
                                          _ptr(mel), self._stream()))
         return mel
@@ -1322,15 +1390,16 @@ class Runtime:
         return st, info
 
     def gpt_generate_beams(self, refer, refer_lens, texts, num_beams, num_return_sequences=1, max_generate_length=600, length_penalty=1.0,
-                           early_stopping=False, repetition_penalty=2.0, suppress_eos=False, token_wgs=0, prompt_codes=None, processors=None):
+                           early_stopping=False, repetition_penalty=2.0, suppress_eos=False, token_wgs=0, prompt_codes=None, processors=None,
+                           cond=None):
         """Beam search (HF generate(num_beams=K, do_sample=False)) on the device: dtts_gpt_beam_generate.  -> (seqs int32 [B, nrs, G]
         padded with 8193, lens int32 [B, nrs], scores float32 [B, nrs] = HF's sequences_scores), the best nrs <= K finished hypotheses
         of every utterance in score order.  prompt_codes / processors as in gpt_generate; nothing is sampled."""
-        B, _, Tr = refer.shape
+        B, Tr = _speaker_shape(refer, cond)
         text, tl = self._pad_text(texts)
         G, nrs = int(max_generate_length), int(num_return_sequences)
         prompt = self._prompt(prompt_codes, B, tl, G)
-        _check(refer, "refer")
+        _check(refer, "refer"); self._check_cond(cond)
         o = _lib.DttsGptOptions()
         self.lib.dtts_gpt_options_init(C.byref(o))
         K = self._beams(o, num_beams, length_penalty, early_stopping)
@@ -1348,6 +1417,12 @@ class Runtime:
         seqs = np.zeros((B, nrs, G), np.int32)
         lens = np.zeros((B, nrs), np.int32)
         scores = np.zeros((B, nrs), np.float32)
+        if cond is not None:
+            self._rc(self.lib.dtts_gpt_beam_generate_cond(self.h, _ptr(cond), text.ctypes.data_as(_lib.c_int_p), tl.ctypes.data_as(_lib.c_int_p),
+                                                          text.shape[1], B, C.byref(o), nrs, seqs.ctypes.data_as(_lib.c_int_p),
+                                                          lens.ctypes.data_as(_lib.c_int_p), scores.ctypes.data_as(_lib.c_float_p),
+                                                          self._stream()))
+            return seqs, lens, scores
         self._rc(self.lib.dtts_gpt_beam_generate(self.h, _ptr(refer), rl[0], Tr, text.ctypes.data_as(_lib.c_int_p), tl.ctypes.data_as(_lib.c_int_p),
                                                  text.shape[1], B, C.byref(o), nrs, seqs.ctypes.data_as(_lib.c_int_p),
                                                  lens.ctypes.data_as(_lib.c_int_p), scores.ctypes.data_as(_lib.c_float_p), self._stream()))

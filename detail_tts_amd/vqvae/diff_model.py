@@ -25,8 +25,18 @@ class DiffusionTts:
         self.rt.set_option("trunk_fp16", 1 if on else 0)
 
     def get_conditioning(self, conditioning_input, lengths=None):
-        """vqvae/diff_model.py:221-229: mel [B,128,T] -> [B,1536]"""
-        return self.rt.diff_conditioning(conditioning_input.float().contiguous(), lengths)
+        """vqvae/diff_model.py:221-229: mel [B,128,T] -> [B,1536]; n clips per speaker [B,n,128,T] (lengths [B,n]: every clip's valid
+        length, an extension) -> the mean over the n embedder outputs concatenated along time, as the reference takes it: the B n clips
+        run as one batch, then the pool weighted by each clip's embedder length (csrc/voice.hip, voice.embedder_length)."""
+        if conditioning_input.dim() != 4:
+            return self.rt.diff_conditioning(conditioning_input.float().contiguous(), lengths)
+        import numpy as np
+        from ..voice import check_clips, embedder_length
+        S, n, T, lens = check_clips(conditioning_input, None, lengths)
+        d = self.rt.diff_conditioning(conditioning_input.float().reshape(S * n, -1, T).contiguous(), lens)
+        if n == 1:
+            return d
+        return self.rt.voice_pool(d.view(S, n, -1), np.asarray([embedder_length(l) for l in lens], np.float32).reshape(S, n))
 
     def timestep_independent(self, aligned_conditioning, conditioning_latent, expected_seq_len, return_code_pred=False, lengths=None):
         """vqvae/diff_model.py:231-260 (latent branch): [B,n,768] -> [B,768,4n]"""

@@ -24,6 +24,7 @@ from ..gpt.model import UnifiedVoice
 from .. import _lib as _lib_slots
 from ..pipeline import drain_session, group_requests, normalize_request, split_latents, split_session, stage_b, stage_c, stream_stage_a
 from ..runtime import Runtime
+from ..voice import check_clips, check_speaker, make_voice, model_dims
 from .diff_model import DiffusionTts
 from .utils.diffusion import SAMPLERS, SpacedDiffusion, check_timesteps, get_named_beta_schedule, space_timesteps
 
@@ -315,8 +316,15 @@ class SynthesizerTrn:
     def infer(self, text, text_length, refer, refer_lengths, noise_scale=NOISE_SCALE, *, batch=False, seed=None, sample_ids=None,
               forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False, return_lengths=False,
               stream_vocoder=False, vocoder_chunk=256, wait=True, check_range=True, diffusion_steps=None, sampler="p", eta=0.0,
-              trunk_precision=None, num_candidates=1, choose=None, return_candidates=False, prompt_codes=None, decode_options=None):
+              trunk_precision=None, num_candidates=1, choose=None, return_candidates=False, prompt_codes=None, decode_options=None,
+              speaker=None):
         """vqvae/model_24k.py:774-810.  Returns wav [B,1,1024*n_max] (B=1 unless batch=True).
+
+        speaker: a Voice (get_conditioning_latents; voice.py) in the place of the prompt mel - refer and refer_lengths are then None
+        (both given, or neither: ValueError before any launch).  S = 1 serves every row, else S has to be B.  Neither prompt encoder
+        is launched: stage A takes the voice's gpt member (UnifiedVoice.compute_embeddings' cond_latents), stage B its diffusion
+        member.  With a voice made from the same [B,128,Tr] prompt the call returns the `refer` call's bits; every other option
+        composes with it.  None: today's path, untouched.
 
         decode_options: None or a dict of HF generate()'s remaining decode-time keywords, which the reference's inference_speech_*
         would hand to HF (gpt/decode_options.py: no_repeat_ngram_size, min_length, min_new_tokens, exponential_decay_length_penalty,
@@ -361,7 +369,8 @@ class SynthesizerTrn:
         ncand = check_num_candidates(num_candidates, forced_codes)
         check_prompt_args(prompt_codes, forced_codes, ncand)
         processors, beam = beam_request(decode_options, forced_codes=forced_codes, num_candidates=ncand, return_candidates=return_candidates)
-        st = normalize_request(text, text_length, refer, refer_lengths, seed, sample_ids, forced_codes, batch=batch)
+        st = normalize_request(text, text_length, refer, refer_lengths, seed, sample_ids, forced_codes, batch=batch, speaker=speaker,
+                               dims=None if speaker is None else model_dims(self.cfg))
         B, rl, texts, seed, sample_ids, forced_codes = st.B, st.rl, st.texts, st.seed, st.sids, st.forced
         if prompt_codes is not None:       # (ValueError on a bad row count or code: before any launch)
             prompt_codes = prompt_rows(prompt_codes if batch else prompt_codes[:1], B)
@@ -370,7 +379,12 @@ class SynthesizerTrn:
         if return_candidates and not candidates:
             raise ValueError("return_candidates: forced_codes leave no candidates to report")
         cand_ids = expand_sample_ids(sample_ids, ncand) if candidates else None      # (ValueError on colliding streams: before any launch)
-        refer = st.refer = st.refer.to(self.device, torch.float32).contiguous()
+        cond = None                        # the conditioning encoder's output, handed in when the request carries a voice
+        if st.voice is not None:
+            st.voice = st.voice.for_batch(B)
+            refer, cond = None, st.voice.gpt
+        else:
+            refer = st.refer = st.refer.to(self.device, torch.float32).contiguous()
         ev, cand = [], None
 
         def mark(name):
@@ -385,9 +399,9 @@ class SynthesizerTrn:
         if beam:        # HF's beam search on the device; the best hypothesis's latents come from the return_latent pass, as behind a prompt
             seqs, blens, _ = self.rt.gpt_generate_beams(refer, rl, texts, num_return_sequences=1, max_generate_length=max_generate_length,
                                                         repetition_penalty=REPETITION_PENALTY, suppress_eos=suppress_eos,
-                                                        prompt_codes=prompt_codes, processors=processors or None, **beam)
+                                                        prompt_codes=prompt_codes, processors=processors or None, cond=cond, **beam)
             n, = split_session(blens[:, 0], [B])
-            st.lat, st.n = self.rt.gpt_latents(refer, rl, texts, [seqs[b, 0, : n[b]] for b in range(B)]), n
+            st.lat, st.n = self.rt.gpt_latents(refer, rl, texts, [seqs[b, 0, : n[b]] for b in range(B)], cond=cond), n
         elif forced_codes is None:
             kw = dict(max_generate_length=max_generate_length, top_k=top_k, top_p=TOP_P, temperature=TEMPERATURE,
                       repetition_penalty=REPETITION_PENALTY, suppress_eos=suppress_eos)
@@ -396,8 +410,10 @@ class SynthesizerTrn:
             if processors:
                 kw["processors"] = processors
             a_refer, a_rl, a_texts, a_ids = refer, rl, texts, sample_ids
+            if cond is not None:
+                kw["cond"] = cond if not (candidates and ncand > 1) else cond.repeat_interleave(ncand, 0).contiguous()
             if candidates and ncand > 1:                            # HF's num_return_sequences expansion: every row N times
-                a_refer = refer.repeat_interleave(ncand, 0).contiguous()
+                a_refer = None if refer is None else refer.repeat_interleave(ncand, 0).contiguous()
                 a_rl = [v for v in rl for _ in range(ncand)]
                 a_texts = [t for t in texts for _ in range(ncand)]
             if candidates:
@@ -428,10 +444,10 @@ class SynthesizerTrn:
             if prompt_codes is None:
                 split_latents(lat, [st], [n])
             else:       # behind a prompt they are not: the reference's return_latent pass sees the generated codes alone (:796-799)
-                st.lat, st.n = self.rt.gpt_latents(refer, rl, texts, [codes[b, : n[b]] for b in range(B)]), n
+                st.lat, st.n = self.rt.gpt_latents(refer, rl, texts, [codes[b, : n[b]] for b in range(B)], cond=cond), n
         else:
             n = st.n = [len(c) for c in forced_codes]
-            st.lat = self.rt.gpt_latents(refer, rl, texts, forced_codes)
+            st.lat = self.rt.gpt_latents(refer, rl, texts, forced_codes, cond=cond)
         mark("gpt_decode" if session else "gpt")
         # ---- stage B (:802-804)
         mel, lens_t = stage_b(self, st, sampler_id, eta, prec, sched_ts=sched_ts, mark=mark)
@@ -469,7 +485,8 @@ class SynthesizerTrn:
                      trunk_precision=None, decode_options=None):
         """Batch server: `infer(..., batch=True)` over a sequence of request batches, software-pipelined over three HIP streams.
 
-        requests: iterable of dicts with keys text [B,Lt], text_length [B], refer [B,128,Tr], refer_lengths [B] and optionally seed,
+        requests: iterable of dicts with keys text [B,Lt], text_length [B], refer [B,128,Tr], refer_lengths [B] (or, in the place of those
+        two, speaker = a Voice: see infer) and optionally seed,
         sample_ids, forced_codes (per-row code arrays fed through the KV-cache decode instead of sampling: tests / ragged benchmarks;
         <= 16 rows) (any B; up to 16 utterances share one decode session; with pair_stage_a two consecutive requests of <= 8 utterances
         are decoded as ONE session - stage A of requests i + 1 and i + 2 together under stage B of requests i - 1 and i).  Yields (wav [B,1,1024*n_max], lengths) per request, in order; every
@@ -521,11 +538,12 @@ class SynthesizerTrn:
         # library supports exactly this split (include/detail_hip.h, "Threads"); ctypes releases the GIL inside the calls.
         def stage_a(group):
             torch.cuda.set_device(dev)
-            return stream_stage_a(self.rt, sa, group, kw, token_wgs, trace)
+            return stream_stage_a(self.rt, sa, group, kw, token_wgs, trace, dims=model_dims(self.cfg))
 
         def launch_bc(st):
             cur.wait_event(st.a_done)
-            st.refer.record_stream(cur)
+            if st.refer is not None:
+                st.refer.record_stream(cur)
             st.lat.record_stream(cur)
             if st.tr:
                 st.tr["host_b0"] = time.perf_counter()
@@ -593,17 +611,28 @@ class SynthesizerTrn:
 
     def infer_gpt(self, text, text_length, refer, refer_lengths, noise_scale=NOISE_SCALE, *, batch=False, seed=None, sample_ids=None,
                   forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False, prompt_codes=None,
-                  decode_options=None):
+                  decode_options=None, speaker=None):
         """vqvae/model_24k.py:811-847: GPT codes -> quantizer.decode + vq_ref_enc -> vq_dec -> infer_flowvae (no diffusion).
-        prompt_codes (not with forced_codes): line 819 calls UnifiedVoice.inference_speech_valle, see infer.  decode_options: see infer."""
+        prompt_codes (not with forced_codes): line 819 calls UnifiedVoice.inference_speech_valle, see infer.  decode_options: see infer.
+        speaker: a Voice with a vq member in the place of (refer, refer_lengths), see infer: its gpt member conditions the decode, its vq
+        member is g_vq."""
         check_prompt_args(prompt_codes, forced_codes, 1)
         processors, beam = beam_request(decode_options, forced_codes=forced_codes)
-        st = normalize_request(text, text_length, refer, refer_lengths, seed, sample_ids, forced_codes, batch=batch)
+        st = normalize_request(text, text_length, refer, refer_lengths, seed, sample_ids, forced_codes, batch=batch, speaker=speaker,
+                               dims=None if speaker is None else model_dims(self.cfg))
+        if speaker is not None and speaker.vq is None:
+            raise ValueError("infer_gpt: this Voice has no vq member (it was made by a model without VQ weights)")
         B, rl, seed, sample_ids = st.B, st.rl, st.seed, st.sids
         pkw = {} if prompt_codes is None else dict(prompt_codes=prompt_rows(prompt_codes if batch else prompt_codes[:1], B))
         if processors:
             pkw["processors"] = processors
-        refer = st.refer.to(self.device, torch.float32).contiguous()
+        g_vq = None
+        if st.voice is not None:
+            voice = st.voice.for_batch(B)
+            refer, g_vq = None, voice.vq
+            pkw["cond"] = voice.gpt
+        else:
+            refer = st.refer.to(self.device, torch.float32).contiguous()
         if st.forced is None and beam:
             seqs, blens, _ = self.rt.gpt_generate_beams(refer, rl, st.texts, num_return_sequences=1, max_generate_length=max_generate_length,
                                                         repetition_penalty=REPETITION_PENALTY, suppress_eos=suppress_eos, **pkw, **beam)
@@ -618,7 +647,7 @@ class SynthesizerTrn:
         # vqvae/model_24k.py:833-834: the stop token came first -> the reference decodes a ZERO latent of 16 frames (64 mel frames);
         # code -1 is that zero vector in dtts_vq_decode
         code_list = [c if len(c) else np.full(self.EMPTY_CODE_FRAMES, -1, np.int64) for c in code_list]
-        mel = self.rt.vq_decode(code_list, refer, rl)
+        mel = self.rt.vq_decode(code_list, refer, rl, g_vq=g_vq)
         lens_t = [4 * len(c) for c in code_list]
         return self.rt.vocoder(mel, seed, sample_ids, lens=lens_t, noise_scale=noise_scale)
 
@@ -703,16 +732,30 @@ class SynthesizerTrn:
         d.rt = self.rt
         return d
 
-    def _code_embedding(self, codes, text, text_length, refer, refer_lengths):
+    def get_conditioning_latents(self, refer, refer_lengths=None, *, clip_lengths=None):
+        """The speaker of a prompt as a Voice (voice.py): the outputs of gpt.conditioning_encoder, diffusion.contextual_embedder and
+        vq_ref_enc, computed once and handed to infer / infer_gpt / infer_stream / invert_mel / resynthesize as speaker=.
+        refer [S,128,T] (one clip per speaker; refer_lengths [S]) or [S,n,128,T] (n clips per speaker, pooled as the reference's two
+        get_conditioning pool them); clip_lengths [S,n] gives every clip its own valid length (an extension, as lengths are elsewhere)."""
+        checked = check_clips(refer, refer_lengths, clip_lengths)      # (ValueError before any device work)
+        return make_voice(self.rt, refer, *checked)
+
+    def _code_embedding(self, codes, text, text_length, refer, refer_lengths, speaker=None):
         """infer's conditioning of the diffusion (vqvae/model_24k.py:796-803) for given codes [B, n] -> code embedding [B,768,4n]"""
-        refer = torch.as_tensor(refer).to(self.device, torch.float32).contiguous()
+        check_speaker(speaker, refer, refer_lengths, codes.shape[0], None if speaker is None else model_dims(self.cfg))
         n = codes.shape[-1]
         wav_len = torch.tensor([n * 1024] * codes.shape[0])                   # codes.shape[-1] * mel_length_compression (:798)
+        if speaker is not None:
+            voice = speaker.for_batch(codes.shape[0])
+            latent = self.gpt(None, None, text, text_length, codes, wav_len, return_latent=True, clip_inputs=False, cond_latents=voice.gpt)
+            return self.diffusion.timestep_independent(latent, voice.diffusion, 4 * n)
+        refer = torch.as_tensor(refer).to(self.device, torch.float32).contiguous()
         latent = self.gpt(refer, refer_lengths, text, text_length, codes, wav_len, return_latent=True, clip_inputs=False)
         cond = self.diffusion.get_conditioning(refer)
         return self.diffusion.timestep_independent(latent, cond, 4 * n)
 
-    def invert_mel(self, mel, mel_lengths, text, text_length, refer, refer_lengths, *, diffusion_steps=None, depth=None):
+    def invert_mel(self, mel, mel_lengths, text, text_length, refer=None, refer_lengths=None, *, diffusion_steps=None, depth=None,
+                   speaker=None):
         """DDIM inversion of an existing mel under (text, refer): the noise-level-`depth` x that the guided DDIM sampler of
         `diffusion_steps` renders back from.  mel: a raw log-mel [B,128,T], T % 4 == 0 (ValueError otherwise).  forward_diff's
         preparation - normalize_torch_mel, encode, the GPT latents of (refer, text, codes) with return_latent=True, clip_inputs=False
@@ -722,28 +765,32 @@ class SynthesizerTrn:
 
         The round trip is NOT the identity: guidance and the clamp of pred_xstart are not invertible.  On the test weights the
         reference's own inversion + DDIM (eta = 0, 10 steps) misses its input by 0.88 max-abs (normalised mel) from depth 5 and by
-        1.37 from depth 9.  Audio under a trained checkpoint is unmeasured."""
+        1.37 from depth 9.  Audio under a trained checkpoint is unmeasured.  speaker: a Voice in the place of (refer, refer_lengths)."""
+        check_speaker(speaker, refer, refer_lengths, torch.as_tensor(mel).shape[0], None if speaker is None else model_dims(self.cfg))
         mel = torch.as_tensor(mel).to(self.device, torch.float32).contiguous()
         if mel.dim() != 3 or mel.shape[-1] % 4 != 0:
             raise ValueError(f"mel must be [B,128,T] with T a multiple of 4 (the codes' hop), not shape {tuple(mel.shape)}")
         d = self.sampling_diffuser(diffusion_steps)
         depth, _ = d.invert_depth(depth)
         codes, _ = self.encode(mel, mel_lengths)
-        emb = self._code_embedding(codes, text, text_length, refer, refer_lengths)
+        emb = self._code_embedding(codes, text, text_length, refer, refer_lengths, speaker)
         x = d.ddim_reverse_sample_loop(self.diffusion, normalize_torch_mel(mel), {"precomputed_aligned_embeddings": emb}, depth=depth)
         return dict(x=x, depth=depth, diffusion_steps=d.num_timesteps, codes=codes, emb=emb)
 
     def resynthesize(self, inv, text, text_length, *, refer=None, refer_lengths=None, eta=0.0, vocode=True, seed=0, sample_ids=None,
-                     noise_scale=NOISE_SCALE):
+                     noise_scale=NOISE_SCALE, speaker=None):
         """Render an inversion (invert_mel's dict) again: ddim_sample_loop from t_start = inv['depth'] on the same diffuser (a full loop
         with noise = x when depth == diffusion_steps), de-normalised -> mel [B,128,T] (vocode=False) or (wav, mel) through
         infer_flowvae.  refer given: the code embedding is rebuilt from inv['codes'] under THAT prompt (its GPT latents and
         get_conditioning), so the mel is rendered in another voice; else inv['emb'] is reused and text / text_length are not read.
         eta > 0 draws Philox noise keyed by (seed, sample_ids).  Not the identity, and unmeasured on a trained checkpoint: see
-        invert_mel."""
+        invert_mel.  speaker: a Voice in the place of refer (both: ValueError)."""
+        if speaker is not None:
+            check_speaker(speaker, refer, refer_lengths, inv["codes"].shape[0], model_dims(self.cfg))
         d = self.sampling_diffuser(inv["diffusion_steps"])
         depth, t_start = d.invert_depth(inv["depth"])
-        emb = inv["emb"] if refer is None else self._code_embedding(inv["codes"], text, text_length, refer, refer_lengths)
+        emb = inv["emb"] if refer is None and speaker is None else self._code_embedding(inv["codes"], text, text_length, refer, refer_lengths,
+                                                                                        speaker)
         x = inv["x"]
         norm = d.ddim_sample_loop(self.diffusion, tuple(x.shape), noise=x, model_kwargs={"precomputed_aligned_embeddings": emb}, eta=eta,
                                   seed=seed, sample_ids=sample_ids, t_start=t_start)

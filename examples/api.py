@@ -44,7 +44,11 @@ def main():
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--out", default="gen.wav")
     ap.add_argument("--max-generate-length", type=int, default=600)
+    ap.add_argument("--save-voice", metavar="FILE", help="write the prompt's conditioning latents (a Voice, one .npz) and synthesise with them")
+    ap.add_argument("--voice", metavar="FILE", help="synthesise with a stored Voice: no prompt wav is read and no prompt encoder runs")
     a = ap.parse_args()
+    if a.voice and (a.wav or a.save_voice):
+        ap.error("--voice stands in the place of the prompt: not with --wav or --save-voice")
     device = "cuda:0"
     if a.ids:
         ids = [int(v) for v in a.ids.split(",")]
@@ -59,6 +63,15 @@ def main():
         return
     text_tokens = F.pad(torch.IntTensor(ids).unsqueeze(0), (0, 1))                          # api.py:24-25
     vqvae = load_model("vqvae", a.ckpt, None, device)                                       # api.py:33
+    text_lengths = torch.LongTensor([text_tokens.shape[-1]])
+    kw = dict(max_generate_length=a.max_generate_length, seed=a.seed, suppress_eos=a.synthetic or a.ckpt.startswith("synthetic"))
+    if a.voice:
+        from detail_tts_amd.voice import Voice
+        with torch.no_grad():
+            wav = vqvae.infer(text_tokens, text_lengths, None, None, speaker=Voice.load(a.voice, vqvae), **kw)
+        write_wav(a.out, wav.squeeze(0), 24000)
+        print(f"{a.out}: {wav.shape[-1] / 24000:.2f} s of audio in the voice of {a.voice} from {len(ids)} text ids")
+        return
     if a.wav:
         audio, sr = read_wav(a.wav)                                                         # api.py:34-37
     else:
@@ -70,10 +83,13 @@ def main():
     spec = mel_spectrogram_torch(audio, hps.data.filter_length, hps.data.n_mel_channels, hps.data.sampling_rate, hps.data.hop_length,
                                  hps.data.win_length, hps.data.mel_fmin, hps.data.mel_fmax, rt=vqvae.rt)      # api.py:41-47
     spec_lengths = torch.LongTensor([spec.shape[-1]])
-    text_lengths = torch.LongTensor([text_tokens.shape[-1]])
     with torch.no_grad():
-        wav = vqvae.infer(text_tokens, text_lengths, spec, spec_lengths, max_generate_length=a.max_generate_length, seed=a.seed,
-                          suppress_eos=a.synthetic or a.ckpt.startswith("synthetic"))       # api.py:49
+        if a.save_voice:        # the prompt is encoded once, here; --voice FILE reuses it (the same waveform bit for bit)
+            voice = vqvae.get_conditioning_latents(spec, spec_lengths)
+            voice.save(a.save_voice)
+            wav = vqvae.infer(text_tokens, text_lengths, None, None, speaker=voice, **kw)
+        else:
+            wav = vqvae.infer(text_tokens, text_lengths, spec, spec_lengths, **kw)             # api.py:49
     write_wav(a.out, wav.squeeze(0), 24000)                                                  # api.py:50
     print(f"{a.out}: {wav.shape[-1] / 24000:.2f} s of audio from {spec.shape[-1]} prompt frames and {len(ids)} text ids")
 

@@ -244,6 +244,40 @@ int dtts_gpt_forward_losses(dtts_handle* h, const float* refer, const int* refer
                             const int* mel_codes, int n, int B, float* losses_out, float* text_logprob, float* mel_logprob,
                             float* mel_logits, void* stream);
 
+/* ---- voices: the prompt's latents computed once, pooled over clips, handed back in -------------------------------------------------
+ * A speaker is what three encoders make of the prompt mel: gpt.conditioning_encoder ([768]; dtts_op_mel_style), DiffusionTts'
+ * contextual_embedder ([1536]; dtts_diff_conditioning) and vq_ref_enc ([4 inter_channels]; dtts_op_mel_style).  The reference pools n
+ * clips of a speaker in the model code: UnifiedVoice.get_conditioning (gpt/model.py:419-427) takes the mean of the n encoder outputs,
+ * DiffusionTts.get_conditioning (vqvae/diff_model.py:221-229) the mean over the n embedder outputs concatenated along time - the mean
+ * of the per-clip means weighted by each clip's embedder length ((l - 1) / 2 + 1 - 1) / 2 + 1.  Here the S n clips run through an encoder
+ * as ONE ragged batch of S n rows, then dtts_voice_pool.
+ *
+ * dtts_voice_pool: out[s][d] = sum_j w[s][j] v[s][j][d] / sum_j w[s][j].  v DEVICE [S][n][D], weights HOST [S][n] (finite, >= 0, every
+ * row's sum > 0: checked before the launch) or NULL (all 1: the plain mean), out DEVICE [S][D], not aliasing v.  fp32, j ascending, every
+ * product, sum and the quotient rounded on its own (no fma); one thread per (s, d), no atomics: two calls give the same bits.  Clips of
+ * weight 0 are skipped, and a speaker with one live clip (n = 1 above all) is COPIED, not pooled: a one-clip voice is the encoder's
+ * output bit for bit.  Asynchronous on `stream`; nothing is allocated. */
+int dtts_voice_pool(dtts_handle* h, const float* v, const float* weights, int S, int n, int D, float* out, void* stream);
+
+/* The stage-A entries with the conditioning encoder's output handed in (UnifiedVoice.compute_embeddings' cond_latents,
+ * gpt/model.py:492-513): cond DEVICE [B][768] in the place of (refer, refer_lens, Tr); the encoder is not launched and everything
+ * behind it is the launch sequence of the entry without _cond - with cond = the encoder's output on the same batch, the same bits.
+ * dtts_gpt_beam_generate_cond repeats an utterance's cond row for its K beams where dtts_gpt_beam_generate repeats the prompt mel; a
+ * session's replay record (a timed-out token kernel) keeps the cond vector where it keeps the prompt mel. */
+int dtts_gpt_generate_cond(dtts_handle* h, const float* cond, const int* text, const int* text_lens, int Lt_max, int B,
+                           const dtts_gpt_options* opts, int* codes_out, int* ncodes_out, float* latents_cm, int lat_stride, void* stream);
+int dtts_gpt_prefill_cond(dtts_handle* h, const float* cond, const int* text, const int* text_lens, int Lt_max, int B,
+                          const dtts_gpt_options* opts, float* latents_cm, int lat_stride, void* stream);
+int dtts_gpt_beam_generate_cond(dtts_handle* h, const float* cond, const int* text, const int* text_lens, int Lt_max, int B,
+                                const dtts_gpt_options* opts, int nrs, int* seqs_out, int* lens_out, float* scores_out, void* stream);
+int dtts_gpt_latents_cond(dtts_handle* h, const float* cond, const int* text, const int* text_lens, int Lt_max, const int* codes,
+                          const int* ncodes, int n_max, int B, float* latents_cm, int lat_stride, void* stream);
+int dtts_gpt_forward_losses_cond(dtts_handle* h, const float* cond, const int* text_ids, int Lt, const int* mel_codes, int n, int B,
+                                 float* losses_out, float* text_logprob, float* mel_logprob, float* mel_logits, void* stream);
+/* dtts_vq_decode (below) with g_vq DEVICE [B][4 inter_channels] = vq_ref_enc's output in the place of (refer, refer_lens, Tr) */
+int dtts_vq_decode_cond(dtts_handle* h, const int* codes, const int* ncodes, int nmax, const float* g_vq, int B, float* mel_out,
+                        void* stream);
+
 /* ---- stage B: diffusion mel decoder ---------------------------------------------------------- */
 
 /* DiffusionTts.get_conditioning (vqvae/diff_model.py:221-229): refer [B,128,Tmax] -> cond [B,1536] */
