@@ -211,6 +211,18 @@ SIGNATURES = {
                                     C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dtts_op_attention_rel": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dtts_gpt_attentions": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, c_int_p, c_int_p, C.c_int, c_int_p, c_int_p, C.c_int, C.c_int,
+                                      c_int_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "dtts_gpt_attentions_cond": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, c_int_p, c_int_p, C.c_int, C.c_int, c_int_p,
+                                           C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "dtts_gpt_text_alignment": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, c_int_p, c_int_p, C.c_int, c_int_p, c_int_p, C.c_int,
+                                          C.c_int, c_int_p, C.c_int, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dtts_gpt_text_alignment_cond": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, c_int_p, c_int_p, C.c_int, C.c_int,
+                                               c_int_p, C.c_int, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dtts_op_attn_probs": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_int, C.c_float, c_int_p, c_int_p, c_int_p, c_int_p, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int,
+                                     C.c_void_p, C.c_void_p]),
+    "dtts_op_monotone_path": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dtts_op_philox_normal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_ulonglong, c_int_p, C.c_int, C.c_int, C.c_void_p]),
 }
 

@@ -871,6 +871,58 @@ int dtts_op_attention_rel(dtts_handle* h, const float* qkv, const int* lens, int
     DTTS_API_END(h)
 }
 
+// ---- text-to-audio alignment (include/detail_hip.h, "alignment")
+int dtts_gpt_attentions(dtts_handle* h, const float* refer, const int* refer_lens, int Tr, const int* text, const int* text_lens, int Lt_max,
+                        const int* codes, const int* ncodes, int n_max, int B, const int* layers, int n_layers, float* out, int L_out,
+                        void* stream) {
+    DTTS_API_BEGIN
+    h->m->gpt_attentions(refer, refer_lens, Tr, text, text_lens, Lt_max, codes, ncodes, n_max, B, layers, n_layers, out, L_out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_gpt_attentions_cond(dtts_handle* h, const float* cond, const int* text, const int* text_lens, int Lt_max, const int* codes,
+                             const int* ncodes, int n_max, int B, const int* layers, int n_layers, float* out, int L_out, void* stream) {
+    DTTS_API_BEGIN
+    DTTS_REQUIRE(cond, "dtts_gpt_attentions_cond: cond");
+    h->m->gpt_attentions(nullptr, nullptr, 0, text, text_lens, Lt_max, codes, ncodes, n_max, B, layers, n_layers, out, L_out, (hipStream_t)stream, cond);
+    DTTS_API_END(h)
+}
+
+int dtts_gpt_text_alignment(dtts_handle* h, const float* refer, const int* refer_lens, int Tr, const int* text, const int* text_lens, int Lt_max,
+                            const int* codes, const int* ncodes, int n_max, int B, const int* layers, int n_layers, const float* head_weights,
+                            float* attn, float* text_mass, void* stream) {
+    DTTS_API_BEGIN
+    h->m->gpt_text_alignment(refer, refer_lens, Tr, text, text_lens, Lt_max, codes, ncodes, n_max, B, layers, n_layers, head_weights, attn,
+                             text_mass, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_gpt_text_alignment_cond(dtts_handle* h, const float* cond, const int* text, const int* text_lens, int Lt_max, const int* codes,
+                                 const int* ncodes, int n_max, int B, const int* layers, int n_layers, const float* head_weights, float* attn,
+                                 float* text_mass, void* stream) {
+    DTTS_API_BEGIN
+    DTTS_REQUIRE(cond, "dtts_gpt_text_alignment_cond: cond");
+    h->m->gpt_text_alignment(nullptr, nullptr, 0, text, text_lens, Lt_max, codes, ncodes, n_max, B, layers, n_layers, head_weights, attn,
+                             text_mass, (hipStream_t)stream, cond);
+    DTTS_API_END(h)
+}
+
+int dtts_op_attn_probs(dtts_handle* h, const float* qkv, const int* lens, int B, int rows, int cs, int T, int H, int D, int q_off, int k_off,
+                       int head_stride, float scale, const int* q0, const int* nq, const int* k0, const int* nk, int nq_max, int nk_max,
+                       int mode, const float* head_weights, int first, float* out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->op_attn_probs(qkv, lens, B, rows, cs, T, H, D, q_off, k_off, head_stride, scale, q0, nq, k0, nk, nq_max, nk_max, mode, head_weights,
+                        first, out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_op_monotone_path(dtts_handle* h, const float* score, const int* n, const int* m, int B, int n_max, int m_max, int* path,
+                          void* stream) {
+    DTTS_API_BEGIN
+    h->m->op_monotone_path(score, n, m, B, n_max, m_max, path, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
 int dtts_op_philox_normal(dtts_handle* h, float* out, int n, int B, unsigned long long seed, const int* sample_ids, int stage,
                           int step, void* stream) {
     DTTS_API_BEGIN

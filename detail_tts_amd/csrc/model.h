@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "attention.h"
+#include "attn_probs.h"
 #include "common.h"
 #include "conv_gemm.h"
 #include "conv_x3.h"
@@ -332,6 +333,17 @@ public:
     void gpt_forward_losses(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, int Lt, const int* codes_host, int n,
                             int B, float* losses_out, float* text_logprob, float* mel_logprob, float* mel_logits, hipStream_t s,
                             const float* cond_in = nullptr);
+    // ---- text-to-audio alignment (model_align.hip; include/detail_hip.h "alignment")
+    void gpt_attentions(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host, int Lt_max,
+                        const int* codes_host, const int* ncodes_host, int n_max, int B, const int* layers_host, int n_layers, float* out,
+                        int L_out, hipStream_t s, const float* cond_in = nullptr);
+    void gpt_text_alignment(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host, int Lt_max,
+                            const int* codes_host, const int* ncodes_host, int n_max, int B, const int* layers_host, int n_layers,
+                            const float* head_weights_host, float* attn_out, float* text_mass_out, hipStream_t s, const float* cond_in = nullptr);
+    void op_attn_probs(const float* qkv, const int* lens_host, int B, int rows, int cs, int T, int H, int D, int q_off, int k_off, int head_stride,
+                       float scale, const int* q0_host, const int* nq_host, const int* k0_host, const int* nk_host, int nq_max, int nk_max,
+                       int mode, const float* w_host, int first, float* out, hipStream_t s);
+    void op_monotone_path(const float* score, const int* n_host, const int* m_host, int B, int n_max, int m_max, int* path, hipStream_t s);
     // ---- stage C
     void mel_style(const MelStyleW& w, const float* mel, const int* lens_dev, const int* lens_host, int B, int T, float* g_out,
                    hipStream_t s, bool padded_batch = false);
@@ -493,9 +505,28 @@ private:
         int L = 0;
         std::vector<int> tl, ml;         // text positions (ids + 2) and mel positions (codes + 2) of every row
     };
+    // What a teacher-forced pass reads out of its attention (attn_probs.h), per selected layer right behind that layer's qkv conv:
+    //   HEADS  every head's map on the row's whole [lt_b, lt_b]       -> out [n_layers][B][H][L][L]      (nq_max = nk_max = 0: set by the pass)
+    //   MEAN   sum over (layer, head) of w[layer][head] P on the window queries c0_b + j (the columns that PREDICT code j, c0_b = 1 + tl_b
+    //          the start-mel column), keys 1 .. tl_b ([255, text, 0])   -> out [B][nq_max][nk_max], layers accumulating in list order
+    // layers and w ([n_layers][H], MEAN) HOST, checked by the entry; the pass uploads w with the windows, behind its own id checks.
+    struct GptAttnRequest {
+        int mode = 0;
+        const int* layers = nullptr;
+        int n_layers = 0;
+        const float* w = nullptr;
+        float* out = nullptr;
+        int nq_max = 0, nk_max = 0;
+    };
+    // ... and what gpt_prefill_layers gets of it: the windows [B] and the weights as device arrays
+    struct GptAttnCapture {
+        GptAttnRequest req;
+        const int *q0 = nullptr, *nq = nullptr, *k0 = nullptr, *nk = nullptr;
+        const float* w = nullptr;
+    };
     GptForced gpt_teacher_forced(const float* refer, const int* refer_lens_host, int Tr, const int* text_host, const int* text_lens_host,
                                  int Lt_max, const int* codes_host, const int* ncodes_host, int n_max, int B, size_t extra_ws_bytes,
-                                 hipStream_t s, const float* cond_in = nullptr);
+                                 hipStream_t s, const float* cond_in = nullptr, const GptAttnRequest* attn = nullptr);
     // one head through gpt_score.hip over columns of lat [B][C][lat_cs] (targets range-checked by the caller), rows in groups of 16
     void score_head(const PackedConv& head, const float* lat, long long lat_bs, int lat_cs, const int* targets_host, const int* ntargets_host,
                     int n_max, int B, float* logprob_out, float* logits_out, hipStream_t s);
@@ -505,7 +536,8 @@ private:
     void build_vq();
     void build_frontend();
     void gpt_prefill_layers(float* x, const int* lens, int B, int L, float* kv_cache, long long kv_layer_stride, long long kv_bs,
-                            int kv_cs, hipStream_t s);
+                            int kv_cs, hipStream_t s, const GptAttnCapture* capture = nullptr);
+    void gpt_capture_probs(const GptAttnCapture& c, int layer, const float* qkv, const int* lens, int B, int L, hipStream_t s);
     MelStyleW mel_style_w(const std::string& prefix, int n_mel, int hidden, int out) const;
     // the one place a ConvParams is laid out: x [B, cin, Ta] -> y [B, cout, Ta], T live columns, lengths `lens` (device) on both sides
     ConvParams cp(const float* x, int cin, float* y, int cout, int B, int T, int Ta, const int* lens) const;

@@ -122,7 +122,7 @@ bool Model::gpt_use_token_kernel() const {
 
 // HF GPT-2 stack (without ln_f) over x [B, C, L] in place; optionally fills the KV cache.
 void Model::gpt_prefill_layers(float* x, const int* lens, int B, int L, float* kv_cache, long long kv_layer_stride,
-                               long long kv_bs, int kv_cs, hipStream_t s) {
+                               long long kv_bs, int kv_cs, hipStream_t s, const GptAttnCapture* capture) {
     const int C = cfg.gpt_dim, H = cfg.gpt_heads, D = C / H;
     const size_t act = (size_t)B * C * L;
     const size_t mark = ws().mark();
@@ -137,6 +137,7 @@ void Model::gpt_prefill_layers(float* x, const int* lens, int B, int L, float* k
         ConvParams p = cp(h, C, qkv, 3 * C, B, L, L, lens);
         run_conv(w.attn, p, s);
         if (kv_cache) launch_kv_to_cache(qkv, 3 * bs, L, lens, L, B, C, kv_cache + l * kv_layer_stride, kv_bs, kv_cs, s);
+        if (capture) gpt_capture_probs(*capture, (int)l, qkv, lens, B, L, s);
         AttnParams a;
         a.qkv = qkv;
         a.bs = 3 * bs;
@@ -172,6 +173,37 @@ void Model::gpt_prefill_layers(float* x, const int* lens, int B, int L, float* k
         run_conv(w.fc2, p, s);
     }
     ws().rewind(mark);
+}
+
+// The read-out of a selected layer's attention probabilities (attn_probs.hip) from the qkv rows the flash launch is about to consume.
+// HEADS: slot k of the layer list gets its own [B][H][nq_max][nk_max]; MEAN: the layers accumulate into one buffer in list order.
+void Model::gpt_capture_probs(const GptAttnCapture& c, int layer, const float* qkv, const int* lens, int B, int L, hipStream_t s) {
+    const int C = cfg.gpt_dim, H = cfg.gpt_heads, D = C / H;
+    for (int k = 0; k < c.req.n_layers; ++k) {
+        if (c.req.layers[k] != layer) continue;
+        AttnProbsParams a;
+        a.qkv = qkv;
+        a.bs = (long long)3 * C * L;
+        a.cs = L;
+        a.q_off = 0;
+        a.k_off = C;
+        a.head_stride = D;
+        a.lens = lens;
+        a.q0 = c.q0; a.nq = c.nq; a.k0 = c.k0; a.nk = c.nk;
+        a.B = B; a.H = H; a.D = D;
+        a.nq_max = c.req.nq_max;
+        a.nk_max = c.req.nk_max;
+        a.scale = 1.f / std::sqrt((float)D);
+        a.mode = c.req.mode;
+        if (c.req.mode == ATTN_PROBS_HEADS) {
+            a.out = c.req.out + (size_t)k * B * H * a.nq_max * a.nk_max;
+        } else {
+            a.out = c.req.out;
+            a.w = c.w + (size_t)k * H;
+            a.first = k == 0;
+        }
+        launch_attn_probs(a, s);
+    }
 }
 
 static size_t prefill_ws(int B, int C, int L) { return sizeof(float) * (size_t)9 * B * C * L + 16 * 256; }
@@ -1266,7 +1298,7 @@ void Model::op_sample_logits_opts(const float* logits, int R, int V, const dtts_
 // The teacher-forced pass over [cond | 255, text, 0 | 8192, codes, 8193] (gpt/model.py:463-476, 392-403): see model.h
 Model::GptForced Model::gpt_teacher_forced(const float* refer, const int* refer_lens_host, int Tr, const int* text_host,
                                            const int* text_lens_host, int Lt_max, const int* codes_host, const int* ncodes_host, int n_max,
-                                           int B, size_t extra_ws_bytes, hipStream_t s, const float* cond_in) {
+                                           int B, size_t extra_ws_bytes, hipStream_t s, const float* cond_in, const GptAttnRequest* attn) {
     DTTS_REQUIRE(bound_ && has_gpt_, "gpt weights not bound");
     DTTS_REQUIRE(cond_in || (refer && Tr >= 1), "neither a prompt mel nor its conditioning latent");
     if (cond_in) Tr = 0;
@@ -1325,7 +1357,31 @@ Model::GptForced Model::gpt_teacher_forced(const float* refer, const int* refer_
     const int* d_lt = upload_ints(lt.data(), B, s);
     DTTS_CHECK_HIP(hipMemsetAsync(emb, 0, sizeof(float) * (size_t)B * C * L, s));
     launch_build_prefix(cond, d_ids, tl_max, d_tl, text_emb_, text_pos_, mel_emb_, mel_pos_, d_mids, ml_max, d_ml, B, C, L, emb, s);
-    gpt_prefill_layers(emb, d_lt, B, L, nullptr, 0, 0, 0, s);
+    GptAttnCapture cap;
+    if (attn) {
+        // the windows (model.h): HEADS the row's whole [lt_b, lt_b]; MEAN queries c0_b + j = the columns predicting code j, keys 1 .. tl_b
+        cap.req = *attn;
+        std::vector<int> q0(B), nq(B), k0(B), nk(B);
+        for (int b = 0; b < B; ++b) {
+            const bool heads = attn->mode == ATTN_PROBS_HEADS;
+            q0[b] = heads ? 0 : 1 + tl[b];
+            nq[b] = heads ? lt[b] : nn[b];
+            k0[b] = heads ? 0 : 1;
+            nk[b] = heads ? lt[b] : tl[b];
+        }
+        if (attn->mode == ATTN_PROBS_HEADS) {
+            DTTS_REQUIRE(attn->nq_max >= L && attn->nk_max == attn->nq_max, "attention maps: the output's L is smaller than the longest row");
+        } else {
+            DTTS_REQUIRE(attn->nq_max == n_max && attn->nk_max == tl_max, "text alignment: output shape");
+        }
+        cap.q0 = upload_ints(q0.data(), B, s);
+        cap.nq = upload_ints(nq.data(), B, s);
+        cap.k0 = upload_ints(k0.data(), B, s);
+        cap.nk = upload_ints(nk.data(), B, s);
+        static_assert(sizeof(float) == sizeof(int), "the head weights travel through the int upload ring");
+        if (attn->w) cap.w = reinterpret_cast<const float*>(upload_ints(reinterpret_cast<const int*>(attn->w), attn->n_layers * cfg.gpt_heads, s));
+    }
+    gpt_prefill_layers(emb, d_lt, B, L, nullptr, 0, 0, 0, s, attn ? &cap : nullptr);
     const long long bs = (long long)C * L;
     launch_ln_channels(emb, nullptr, bs, L, d_lt, L, B, C, lnf_g_, lnf_b_, 1e-5f, enc, bs, L, s);       // GPT2Model.ln_f
     launch_ln_channels(enc, nullptr, bs, L, d_lt, L, B, C, fin_g_, fin_b_, 1e-5f, emb, bs, L, s);       // final_norm (:403)

@@ -269,4 +269,42 @@ class UnifiedVoice:
         lp = self.rt.gpt_score(lat, codes).cpu().numpy()
         return [lp[b, : len(c)].copy() for b, c in enumerate(codes)]
 
+    @staticmethod
+    def _code_rows(mel_codes):
+        """[B, n] (tensor / array) or a list of B one-dimensional rows -> list of int32 arrays"""
+        if isinstance(mel_codes, (list, tuple)):
+            return [np.asarray(torch.as_tensor(c).cpu().numpy() if not isinstance(c, np.ndarray) else c, np.int32).reshape(-1) for c in mel_codes]
+        c = torch.as_tensor(mel_codes).cpu().numpy().astype(np.int32)
+        return [r for r in (c[None] if c.ndim == 1 else c)]
+
+    def attentions(self, speech_conditioning_latent, cond_lengths, text_inputs, mel_codes, *, text_lengths=None, layers=None,
+                   cond_latents=None):
+        """The GPT's attention maps of the teacher-forced pass over [cond | 255, text, 0 | 8192, codes, 8193]: a tuple of [B, 16, L, L]
+        CUDA tensors, one per selected layer (`layers`: distinct ids, None = all 10) - the value of the reference's
+        get_logits(..., get_attns=True) (gpt/model.py:392-400).  forward(return_attentions=True) keeps refusing: the reference's own
+        unpacks the 10-tuple into two names and fails, so there is no value of it to mirror.  Rows may be ragged (text_lengths, a list
+        of code rows): row b fills its own top-left lt_b x lt_b, lt_b = 1 + (text_b + 2) + (codes_b + 2), the rest is 0.  A result
+        above 1 GiB raises ValueError naming `layers`.  One extra kernel per selected layer (csrc/attn_probs.hip) in the pass that
+        forward(return_latent=True) runs; exact-fp32 scores."""
+        refer, cond = self._speaker(speech_conditioning_latent, cond_lengths, cond_latents)
+        cl = None if cond_lengths is None else torch.as_tensor(cond_lengths).reshape(-1).tolist()
+        out = self.rt.gpt_attentions(refer, cl, self._texts(text_inputs, text_lengths), self._code_rows(mel_codes), layers=layers, cond=cond)
+        return tuple(out[k] for k in range(out.shape[0]))
+
+    def text_alignment(self, speech_conditioning_latent, cond_lengths, text_inputs, text_lengths, mel_codes_list, *, layers=None,
+                       head_weights=None, cond_latents=None):
+        """Which text column every mel code sits on, from the text-audio attention of the teacher-forced pass:
+        dict(attn cuda [B, n_max, tl_max], text_mass cuda [B, n_max], path cuda int32 [B, n_max]).  attn[b, j, i] is the attention of
+        the column that PREDICTS code j (the start-mel column for code 0) to text column i of [255, text, 0], summed over the selected
+        `layers` and the 16 heads with `head_weights` [len(layers), 16] (None: the uniform mean); its softmax ran over ALL keys, so
+        text_mass = attn.sum(-1) says how much sits on the text at all.  path is the monotone path of largest total
+        log(clamp_min(attn, 1e-12)) (csrc/align_path.hip; -1 beyond a row's codes): it may stay on a column or jump ahead.  Which
+        layers and heads carry the alignment of a trained checkpoint is unknown here, and alignment quality is unmeasured."""
+        refer, cond = self._speaker(speech_conditioning_latent, cond_lengths, cond_latents)
+        cl = None if cond_lengths is None else torch.as_tensor(cond_lengths).reshape(-1).tolist()
+        texts, codes = self._texts(text_inputs, text_lengths), self._code_rows(mel_codes_list)
+        attn, mass = self.rt.gpt_text_alignment(refer, cl, texts, codes, layers=layers, head_weights=head_weights, cond=cond)
+        path = self.rt.op_monotone_path(torch.log(attn.clamp_min(1e-12)), [len(c) for c in codes], [len(t) + 2 for t in texts])
+        return dict(attn=attn, text_mass=mass, path=path)
+
     __call__ = forward

@@ -367,6 +367,132 @@ class Runtime:
                                            _ptr(lat), nmax, self._stream()))
         return lat
 
+    # ---- text-to-audio alignment (include/detail_hip.h "alignment"; detail_tts_amd/gpt/alignment.py for what is made of it)
+    ATTENTIONS_MAX_BYTES = 1 << 30
+
+    def _forced_batch(self, refer, refer_lens, texts, codes_list, cond):
+        """the host side the teacher-forced entries share -> (B, Tr, rl, text, tl, codes, nn, nmax)"""
+        B, Tr = _speaker_shape(refer, cond)
+        _check(refer, "refer"); self._check_cond(cond)
+        if len(texts) != B or len(codes_list) != B:
+            raise ValueError(f"{len(texts)} texts and {len(codes_list)} code rows for a batch of {B}")
+        text, tl = self._pad_text(texts)
+        nn = np.array([len(c) for c in codes_list], np.int32)
+        nmax = int(nn.max())
+        codes = np.zeros((B, max(nmax, 1)), np.int32)[:, :nmax]
+        codes = np.ascontiguousarray(codes)
+        for b, c in enumerate(codes_list):
+            codes[b, :len(c)] = np.asarray(c, np.int32)
+        rl = _ints(refer_lens if refer_lens is not None else [Tr] * B)
+        return B, Tr, rl, text, tl, codes, nn, nmax
+
+    def _layers(self, layers):
+        """layers -> int32 array of distinct ids in [0, n_layers) (None: all); ValueError naming `layers` before any launch"""
+        nl = int(self.cfg["gpt"]["layers"])
+        ls = np.arange(nl, dtype=np.int32) if layers is None else np.ascontiguousarray(np.asarray(layers, np.int64).reshape(-1))
+        if ls.size < 1 or ls.min() < 0 or ls.max() >= nl or len(set(ls.tolist())) != ls.size:
+            raise ValueError(f"`layers` have to be distinct ids in [0, {nl}), but are {ls.tolist()}")
+        return ls.astype(np.int32)
+
+    def gpt_attentions(self, refer, refer_lens, texts, codes_list, layers=None, cond=None):
+        """Per-head attention maps of the teacher-forced pass (dtts_gpt_attentions; the reference's get_logits(get_attns=True),
+        gpt/model.py:392-400) -> cuda [n_layers, B, H, L, L], L the longest row's 1 + (text + 2) + (codes + 2); row b fills its own top-left
+        lt_b x lt_b, everything else is 0.  A result above 1 GiB is refused with a ValueError naming `layers`."""
+        B, Tr, rl, text, tl, codes, nn, nmax = self._forced_batch(refer, refer_lens, texts, codes_list, cond)
+        ls = self._layers(layers)
+        H = int(self.cfg["gpt"]["heads"])
+        L = int((1 + tl + 2 + nn + 2).max())
+        nbytes = 4 * ls.size * B * H * L * L
+        if nbytes > self.ATTENTIONS_MAX_BYTES:
+            raise ValueError(f"the attention maps of {ls.size} layers x {B} rows x {H} heads x {L} x {L} take {nbytes / 2**30:.2f} GiB (> 1 GiB): "
+                             "select fewer `layers` (or fewer rows per call)")
+        out = torch.zeros((ls.size, B, H, L, L), device=self.device, dtype=torch.float32)
+        ip = lambda a: a.ctypes.data_as(_lib.c_int_p)
+        if cond is not None:
+            self._rc(self.lib.dtts_gpt_attentions_cond(self.h, _ptr(cond), ip(text), ip(tl), text.shape[1], ip(codes), ip(nn), nmax, B, ip(ls),
+                                                       ls.size, _ptr(out), L, self._stream()))
+        else:
+            self._rc(self.lib.dtts_gpt_attentions(self.h, _ptr(refer), rl[0], Tr, ip(text), ip(tl), text.shape[1], ip(codes), ip(nn), nmax, B,
+                                                  ip(ls), ls.size, _ptr(out), L, self._stream()))
+        return out
+
+    def gpt_text_alignment(self, refer, refer_lens, texts, codes_list, layers=None, head_weights=None, cond=None):
+        """The text-audio attention of the teacher-forced pass (dtts_gpt_text_alignment) -> (attn cuda [B, n_max, Lt_max + 2], text_mass
+        cuda [B, n_max]): attn[b, j, i] = sum over (selected layer, head) of w * P(the column predicting code j -> text column i of
+        [255, text, 0]).  head_weights [n_layers, H] or None (uniform 1 / (n_layers H))."""
+        B, Tr, rl, text, tl, codes, nn, nmax = self._forced_batch(refer, refer_lens, texts, codes_list, cond)
+        ls = self._layers(layers)
+        H = int(self.cfg["gpt"]["heads"])
+        hw = None
+        if head_weights is not None:
+            hw = np.ascontiguousarray(np.asarray(torch.as_tensor(head_weights).detach().cpu().numpy(), np.float32))
+            if hw.shape != (ls.size, H) or not np.isfinite(hw).all():
+                raise ValueError(f"`head_weights` have to be finite and [{ls.size}, {H}] (one row per selected layer), but are {hw.shape}")
+        if nmax < 1:
+            raise ValueError("text_alignment: no row has a code")
+        attn = torch.zeros((B, nmax, text.shape[1] + 2), device=self.device, dtype=torch.float32)
+        mass = torch.zeros((B, nmax), device=self.device, dtype=torch.float32)
+        ip = lambda a: a.ctypes.data_as(_lib.c_int_p)
+        hp = hw.ctypes.data_as(_lib.c_float_p) if hw is not None else None
+        if cond is not None:
+            self._rc(self.lib.dtts_gpt_text_alignment_cond(self.h, _ptr(cond), ip(text), ip(tl), text.shape[1], ip(codes), ip(nn), nmax, B,
+                                                           ip(ls), ls.size, hp, _ptr(attn), _ptr(mass), self._stream()))
+        else:
+            self._rc(self.lib.dtts_gpt_text_alignment(self.h, _ptr(refer), rl[0], Tr, ip(text), ip(tl), text.shape[1], ip(codes), ip(nn), nmax,
+                                                      B, ip(ls), ls.size, hp, _ptr(attn), _ptr(mass), self._stream()))
+        return attn, mass
+
+    def op_attn_probs(self, qkv, heads, dim, q_off, k_off, head_stride, scale, lens, q0, nq, k0, nk, mode="heads", head_weights=None,
+                      first=True, out=None, T=None):
+        """ONE launch of the attention-probabilities kernel (csrc/attn_probs.hip) on the caller's rows qkv [B, rows, cs] (addressed as in
+        op_attention) -> (out, guard).  Element (i, j) of sample b is P_h[q0[b] + i, k0[b] + j], the causal softmax over ALL keys of the
+        row.  mode "heads": out [B, heads, nq_max, nk_max]; "mean": out [B, nq_max, nk_max] = (0 if first else out) + sum_h
+        head_weights[h] P_h - pass the previous call's `out` back in to accumulate.  A fresh out is handed over filled with NaN (the
+        kernel leaves everything outside a sample's window, and rows t >= len, untouched) with one more sample-sized NaN slab, guard,
+        directly behind it.  dim != 48, a window outside [0, T] or wrong shapes raise DttsError before anything is launched."""
+        _check(qkv, "qkv"); _check(out, "out")
+        if qkv.dim() != 3:
+            raise DttsError("op_attn_probs: qkv must be [B, rows, cs]")
+        if mode not in ("heads", "mean"):
+            raise DttsError("op_attn_probs: mode is 'heads' or 'mean'")
+        B, rows, cs = qkv.shape
+        T = cs if T is None else int(T)
+        heads, dim = int(heads), int(dim)
+        arrs = [_ints(a) for a in (lens, q0, nq, k0, nk)]
+        if any(a is None or a[1].size != B for a in arrs):
+            raise DttsError("op_attn_probs: lens, q0, nq, k0, nk hold one value per sample")
+        nq_max, nk_max = max(int(arrs[2][1].max()), 1), max(int(arrs[4][1].max()), 1)
+        shape = (heads, nq_max, nk_max) if mode == "heads" else (nq_max, nk_max)
+        hw = None
+        if mode == "mean":
+            hw = np.ascontiguousarray(np.asarray(head_weights, np.float32).reshape(-1))
+            if hw.size != heads:
+                raise DttsError("op_attn_probs: one head weight per head")
+        guard = None
+        if out is None:
+            out, guard = self._nan_with_guard(B, *shape)
+        elif tuple(out.shape) != (B,) + shape:
+            raise DttsError(f"op_attn_probs: out must be {(B,) + shape}")
+        self._rc(self.lib.dtts_op_attn_probs(self.h, _ptr(qkv), arrs[0][0], B, rows, cs, T, heads, dim, int(q_off), int(k_off), int(head_stride),
+                                             float(scale), arrs[1][0], arrs[2][0], arrs[3][0], arrs[4][0], nq_max, nk_max,
+                                             0 if mode == "heads" else 1, hw.ctypes.data_as(_lib.c_float_p) if hw is not None else None,
+                                             int(bool(first)), _ptr(out), self._stream()))
+        return out, guard
+
+    def op_monotone_path(self, score, n, m):
+        """The monotone path (csrc/align_path.hip): score cuda [B, n_max, m_max], n / m one int per sample -> path cuda int32 [B, n_max],
+        -1 beyond n[b].  dp[0] = score[0]; dp[j][i] = score[j][i] + max_{i' <= i} dp[j-1][i'], ties to the lowest index."""
+        _check(score, "score")
+        if score.dim() != 3 or min(score.shape) < 1:
+            raise DttsError("op_monotone_path: score must be [B, n_max, m_max]")
+        B, n_max, m_max = score.shape
+        ni, mi = _ints(n), _ints(m)
+        if ni[1].size != B or mi[1].size != B:
+            raise DttsError("op_monotone_path: one n and one m per sample")
+        path = torch.full((B, n_max), -1, device=self.device, dtype=torch.int32)
+        self._rc(self.lib.dtts_op_monotone_path(self.h, _ptr(score), ni[0], mi[0], B, n_max, m_max, _ptr(path), self._stream()))
+        return path
+
     def gpt_score(self, lat, codes_list, want_logits=False):
         """log p(codes_list[b][k] | lat[b, :, k]) under the model's unprocessed distribution (dtts_gpt_score): lat cuda [B,768,>= n_max] as
         gpt_generate / gpt_finish / gpt_latents return it, codes_list one int array per row (any lengths, 0 included) ->

@@ -317,8 +317,15 @@ class SynthesizerTrn:
               forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False, return_lengths=False,
               stream_vocoder=False, vocoder_chunk=256, wait=True, check_range=True, diffusion_steps=None, sampler="p", eta=0.0,
               trunk_precision=None, num_candidates=1, choose=None, return_candidates=False, prompt_codes=None, decode_options=None,
-              speaker=None):
+              speaker=None, return_alignment=False, align_options=None):
         """vqvae/model_24k.py:774-810.  Returns wav [B,1,1024*n_max] (B=1 unless batch=True).
+
+        return_alignment: the call also returns, as its LAST value, the text-to-audio alignment of the synthesised codes - one
+        dictionary per row, as align() gives it (per-token and per-word code spans and times, and the coverage / skipped /
+        longest_stay figures that show a decode which skipped or repeated text).  One extra teacher-forced pass over the generated
+        codes alone (what infer already runs behind a prompt or beams) with the attention read-out, enqueued behind stage C; it
+        composes with prompt_codes, num_candidates (the chosen rows), beams, forced_codes and speaker.  align_options: None or a dict of
+        align()'s layers / head_weights / space_id.  False (the default): no extra launch, the same bits.
 
         speaker: a Voice (get_conditioning_latents; voice.py) in the place of the prompt mel - refer and refer_lengths are then None
         (both given, or neither: ValueError before any launch).  S = 1 serves every row, else S has to be B.  Neither prompt encoder
@@ -401,7 +408,8 @@ class SynthesizerTrn:
                                                         repetition_penalty=REPETITION_PENALTY, suppress_eos=suppress_eos,
                                                         prompt_codes=prompt_codes, processors=processors or None, cond=cond, **beam)
             n, = split_session(blens[:, 0], [B])
-            st.lat, st.n = self.rt.gpt_latents(refer, rl, texts, [seqs[b, 0, : n[b]] for b in range(B)], cond=cond), n
+            out_codes = [seqs[b, 0, : n[b]] for b in range(B)]
+            st.lat, st.n = self.rt.gpt_latents(refer, rl, texts, out_codes, cond=cond), n
         elif forced_codes is None:
             kw = dict(max_generate_length=max_generate_length, top_k=top_k, top_p=TOP_P, temperature=TEMPERATURE,
                       repetition_penalty=REPETITION_PENALTY, suppress_eos=suppress_eos)
@@ -445,9 +453,12 @@ class SynthesizerTrn:
                 split_latents(lat, [st], [n])
             else:       # behind a prompt they are not: the reference's return_latent pass sees the generated codes alone (:796-799)
                 st.lat, st.n = self.rt.gpt_latents(refer, rl, texts, [codes[b, : n[b]] for b in range(B)], cond=cond), n
+            if return_alignment:                                        # the chosen rows' codes, stop token cut
+                out_codes = [codes[r, : n[b]] for b, r in enumerate(rows if candidates else range(B))]
         else:
             n = st.n = [len(c) for c in forced_codes]
             st.lat = self.rt.gpt_latents(refer, rl, texts, forced_codes, cond=cond)
+            out_codes = forced_codes
         mark("gpt_decode" if session else "gpt")
         # ---- stage B (:802-804)
         mel, lens_t = stage_b(self, st, sampler_id, eta, prec, sched_ts=sched_ts, mark=mark)
@@ -471,9 +482,10 @@ class SynthesizerTrn:
             torch.cuda.synchronize(self.device)
             for (_, a), (nm, b) in zip(ev[:-1], ev[1:]):
                 self.stage_ms[nm] = self.stage_ms.get(nm, 0.0) + a.elapsed_time(b)
-        if return_lengths:
-            return (wav, [1024 * v for v in n], cand) if return_candidates else (wav, [1024 * v for v in n])
-        return (wav, cand) if return_candidates else wav
+        ret = (wav,) + (([1024 * v for v in n],) if return_lengths else ()) + ((cand,) if return_candidates else ())
+        if return_alignment:
+            ret += (self._alignment_of(texts, out_codes, refer, rl, cond, **(align_options or {})),)
+        return ret if len(ret) > 1 else wav
 
     def check_vocoder(self, ticket=None):
         """raise if the stage-C call `ticket` (default: the last one issued) saturated; the caller has waited for its waveform"""
@@ -611,8 +623,10 @@ class SynthesizerTrn:
 
     def infer_gpt(self, text, text_length, refer, refer_lengths, noise_scale=NOISE_SCALE, *, batch=False, seed=None, sample_ids=None,
                   forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False, prompt_codes=None,
-                  decode_options=None, speaker=None):
+                  decode_options=None, speaker=None, return_alignment=False, align_options=None):
         """vqvae/model_24k.py:811-847: GPT codes -> quantizer.decode + vq_ref_enc -> vq_dec -> infer_flowvae (no diffusion).
+        return_alignment / align_options: as in infer - (wav, alignment) with one dictionary per row; a row whose stop token came first
+        has no codes and an empty path.
         prompt_codes (not with forced_codes): line 819 calls UnifiedVoice.inference_speech_valle, see infer.  decode_options: see infer.
         speaker: a Voice with a vq member in the place of (refer, refer_lengths), see infer: its gpt member conditions the decode, its vq
         member is g_vq."""
@@ -646,10 +660,60 @@ class SynthesizerTrn:
             code_list = [np.asarray(c) for c in st.forced]
         # vqvae/model_24k.py:833-834: the stop token came first -> the reference decodes a ZERO latent of 16 frames (64 mel frames);
         # code -1 is that zero vector in dtts_vq_decode
+        out_codes = code_list
         code_list = [c if len(c) else np.full(self.EMPTY_CODE_FRAMES, -1, np.int64) for c in code_list]
         mel = self.rt.vq_decode(code_list, refer, rl, g_vq=g_vq)
         lens_t = [4 * len(c) for c in code_list]
-        return self.rt.vocoder(mel, seed, sample_ids, lens=lens_t, noise_scale=noise_scale)
+        wav = self.rt.vocoder(mel, seed, sample_ids, lens=lens_t, noise_scale=noise_scale)
+        if not return_alignment:
+            return wav
+        return wav, self._alignment_of(st.texts, out_codes, refer, rl, pkw.get("cond"), **(align_options or {}))
+
+    def _alignment_of(self, texts, code_list, refer, rl, cond, layers=None, head_weights=None, space_id=None):
+        """one teacher-forced pass with the attention read-out over (texts, code_list), the path kernel, then the host bookkeeping of
+        gpt/alignment.py -> a list of per-row dictionaries (describe).  Waits for its own results (the path comes to the host)."""
+        from ..gpt.alignment import describe
+        rows = [np.asarray(c, np.int32).reshape(-1) for c in code_list]
+        spc, sr = self.cfg["gpt"]["mel_length_compression"], self.cfg["data"]["sampling_rate"]
+        if max(len(c) for c in rows) == 0:          # nothing was spoken in any row: no pass to run, every path is empty
+            return [describe([], 0, t, None, spc, sr, space_id) for t in texts]
+        attn, mass = self.rt.gpt_text_alignment(refer, rl, texts, rows, layers=layers, head_weights=head_weights, cond=cond)
+        path = self.rt.op_monotone_path(torch.log(attn.clamp_min(1e-12)), [len(c) for c in rows], [len(t) + 2 for t in texts])
+        path, mass = path.cpu().numpy(), mass.cpu().numpy()
+        return [describe(path[b], len(rows[b]), texts[b], mass[b], spc, sr, space_id) for b in range(len(rows))]
+
+    def align(self, text, text_length, codes, code_lengths=None, refer=None, refer_lengths=None, *, speaker=None, layers=None,
+              head_weights=None, space_id=None):
+        """When did the model speak what: the alignment of mel codes (infer's, encode()'s, anyone's) to the text, from the GPT's
+        text-audio attention.  text [B, Lt] / text_length [B] as in infer (every row counts: there is no `batch` switch); codes [B, n]
+        with code_lengths [B], or a list of B one-dimensional rows, WITHOUT a stop token; refer / refer_lengths or speaker= under
+        infer's rules (both or neither: ValueError before any launch).  Returns one dictionary per row (gpt/alignment.py describe):
+          path        int32 [n]: the text column of every code; columns are those of [255, text ..., 0], so column 1 + k is text id k
+          spans/times per column (first, last) code and (start, end) seconds, None for a column without a code;
+          token_spans / token_times the same per text id; words (with space_id, the tokenizer's [SPACE] id) the ids between spaces merged
+          stats       coverage, skipped (text ids without a code), longest_stay, mean_text_mass - a decode that skipped or repeated
+                      text shows here.
+        Code j covers samples [1024 j, 1024 (j + 1)) (gpt.mel_length_compression at data.sampling_rate).  One teacher-forced pass with
+        one more kernel per selected layer, then the path kernel.  layers / head_weights [len(layers), 16]: which maps count (default:
+        the uniform mean over all 10 x 16 - which heads carry the alignment of a trained checkpoint is unknown here, and alignment
+        quality is unmeasured)."""
+        text = torch.as_tensor(text)
+        B = text.shape[0]
+        st = normalize_request(text, text_length, refer, refer_lengths, 0, None, None, batch=True, speaker=speaker,
+                               dims=None if speaker is None else model_dims(self.cfg))
+        if isinstance(codes, (list, tuple)):
+            rows = [np.asarray(torch.as_tensor(c).cpu().numpy(), np.int32).reshape(-1) for c in codes]
+        else:
+            c = torch.as_tensor(codes).cpu().numpy().astype(np.int32)
+            cl = [c.shape[1]] * c.shape[0] if code_lengths is None else [int(v) for v in torch.as_tensor(code_lengths).reshape(-1).tolist()]
+            rows = [c[b, : cl[b]] for b in range(c.shape[0])]
+        if len(rows) != B:
+            raise ValueError(f"align: {len(rows)} code rows for {B} texts")
+        if st.voice is not None:
+            refer, cond = None, st.voice.for_batch(B).gpt
+        else:
+            refer, cond = st.refer.to(self.device, torch.float32).contiguous(), None
+        return self._alignment_of(st.texts, rows, refer, st.rl, cond, layers, head_weights, space_id)
 
     def encode(self, y, y_lengths=None):
         """vqvae/model_24k.py:877-880 -> (codes [B, T/4] int64, x_vq [B,768,T/4])"""

@@ -46,6 +46,8 @@ def main():
     ap.add_argument("--max-generate-length", type=int, default=600)
     ap.add_argument("--save-voice", metavar="FILE", help="write the prompt's conditioning latents (a Voice, one .npz) and synthesise with them")
     ap.add_argument("--voice", metavar="FILE", help="synthesise with a stored Voice: no prompt wav is read and no prompt encoder runs")
+    ap.add_argument("--timings", metavar="PATH", help="also align the synthesised codes to the text (infer(return_alignment=True)) and write "
+                                                      "the token and word spans and times as JSON; words need --vocab (its [SPACE] id)")
     a = ap.parse_args()
     if a.voice and (a.wav or a.save_voice):
         ap.error("--voice stands in the place of the prompt: not with --wav or --save-voice")
@@ -65,10 +67,30 @@ def main():
     vqvae = load_model("vqvae", a.ckpt, None, device)                                       # api.py:33
     text_lengths = torch.LongTensor([text_tokens.shape[-1]])
     kw = dict(max_generate_length=a.max_generate_length, seed=a.seed, suppress_eos=a.synthetic or a.ckpt.startswith("synthetic"))
+    if a.timings:
+        space = None
+        if a.vocab and not a.ids:
+            space = VoiceBpeTokenizer(a.vocab).tokenizer.token_to_id("[SPACE]")
+        kw.update(return_alignment=True, align_options=dict(space_id=space))
+
+    def finish(result):
+        """the waveform of an infer call; with --timings its alignment goes to the JSON file"""
+        if not a.timings:
+            return result
+        import json
+        wav, (al,) = result
+        doc = dict(ids=[int(v) for v in text_tokens[0].tolist()], sampling_rate=24000, stats=al["stats"],
+                   tokens=[dict(index=k, id=int(text_tokens[0, k]), codes=s, seconds=t) for k, (s, t) in enumerate(zip(al["token_spans"], al["token_times"]))],
+                   words=[dict(tokens=w["tokens"], codes=w["span"], seconds=w["time"]) for w in al.get("words", [])])
+        with open(a.timings, "w") as f:
+            json.dump(doc, f, indent=1)
+        print(f"{a.timings}: {len(doc['tokens'])} tokens, {len(doc['words'])} words, coverage {al['stats']['coverage']:.2f} "
+              "(alignment quality is unmeasured: no trained checkpoint)")
+        return wav
     if a.voice:
         from detail_tts_amd.voice import Voice
         with torch.no_grad():
-            wav = vqvae.infer(text_tokens, text_lengths, None, None, speaker=Voice.load(a.voice, vqvae), **kw)
+            wav = finish(vqvae.infer(text_tokens, text_lengths, None, None, speaker=Voice.load(a.voice, vqvae), **kw))
         write_wav(a.out, wav.squeeze(0), 24000)
         print(f"{a.out}: {wav.shape[-1] / 24000:.2f} s of audio in the voice of {a.voice} from {len(ids)} text ids")
         return
@@ -87,9 +109,9 @@ def main():
         if a.save_voice:        # the prompt is encoded once, here; --voice FILE reuses it (the same waveform bit for bit)
             voice = vqvae.get_conditioning_latents(spec, spec_lengths)
             voice.save(a.save_voice)
-            wav = vqvae.infer(text_tokens, text_lengths, None, None, speaker=voice, **kw)
+            wav = finish(vqvae.infer(text_tokens, text_lengths, None, None, speaker=voice, **kw))
         else:
-            wav = vqvae.infer(text_tokens, text_lengths, spec, spec_lengths, **kw)             # api.py:49
+            wav = finish(vqvae.infer(text_tokens, text_lengths, spec, spec_lengths, **kw))     # api.py:49
     write_wav(a.out, wav.squeeze(0), 24000)                                                  # api.py:50
     print(f"{a.out}: {wav.shape[-1] / 24000:.2f} s of audio from {spec.shape[-1]} prompt frames and {len(ids)} text ids")
 

@@ -278,6 +278,36 @@ int dtts_gpt_forward_losses_cond(dtts_handle* h, const float* cond, const int* t
 int dtts_vq_decode_cond(dtts_handle* h, const int* codes, const int* ncodes, int nmax, const float* g_vq, int B, float* mel_out,
                         void* stream);
 
+/* ---- alignment: when did the model speak what --------------------------------------------------------------------------------------
+ * Code position j attends to the text it is pronouncing; the GPT's text-audio attention therefore carries the timing.  The reference
+ * exposes the maps through get_logits(..., get_attns=True) (gpt/model.py:392-400: GPT2Model(output_attentions=True).attentions, one
+ * [B, H, L, L] per layer; its forward(return_attentions=True) unpacks that 10-tuple into two names and cannot run).  The flash kernel
+ * of the prefill keeps P in registers, so these entries run the teacher-forced pass of dtts_gpt_latents - same arguments, same checks,
+ * HOST ids range-checked before any launch - with one more kernel (csrc/attn_probs.hip) behind the qkv conv of every selected layer:
+ * exact-fp32 MFMA scores, softmax over ALL of a row's keys s <= t, only the wanted window written.  layers HOST [n_layers]: distinct
+ * ids in [0, gpt_layers).  Asynchronous on `stream`; no atomics: two calls give the same bits, and a row does not depend on the batch.
+ *
+ * dtts_gpt_attentions: out DEVICE [n_layers][B][H][L_out][L_out], handed over ZEROED; row b fills its own top-left lt_b x lt_b,
+ * lt_b = 1 + (text_lens[b] + 2) + (ncodes[b] + 2) <= L_out (columns: cond | 255, text, 0 | 8192, codes, 8193); keys s > t hold 0.
+ *
+ * dtts_gpt_text_alignment: attn[b][j][i] = sum over (selected layer k, head h) of w[k][h] * P_{k,h}[c0_b + j][1 + i], with c0_b =
+ * 1 + text_lens[b] + 2 the start-mel column - column c0_b + j is the one that PREDICTS code j - and i = 0 .. text_lens[b] + 1 the row's
+ * text span [255, text, 0].  head_weights HOST [n_layers][H] (finite) or NULL: uniform 1 / (n_layers H).  Heads are added in ascending
+ * order, layers in list order, fp32, one owner per element.  attn DEVICE [B][n_max][Lt_max + 2] and text_mass DEVICE [B][n_max] (the
+ * row sums: how much of the probability sits on the text at all) are handed over ZEROED; Lt_max is the longest row's text length.
+ * Which layers and heads carry the alignment of a trained checkpoint is not known here: the default is the plain mean. */
+int dtts_gpt_attentions(dtts_handle* h, const float* refer, const int* refer_lens, int Tr, const int* text, const int* text_lens,
+                        int Lt_max, const int* codes, const int* ncodes, int n_max, int B, const int* layers, int n_layers, float* out,
+                        int L_out, void* stream);
+int dtts_gpt_attentions_cond(dtts_handle* h, const float* cond, const int* text, const int* text_lens, int Lt_max, const int* codes,
+                             const int* ncodes, int n_max, int B, const int* layers, int n_layers, float* out, int L_out, void* stream);
+int dtts_gpt_text_alignment(dtts_handle* h, const float* refer, const int* refer_lens, int Tr, const int* text, const int* text_lens,
+                            int Lt_max, const int* codes, const int* ncodes, int n_max, int B, const int* layers, int n_layers,
+                            const float* head_weights, float* attn, float* text_mass, void* stream);
+int dtts_gpt_text_alignment_cond(dtts_handle* h, const float* cond, const int* text, const int* text_lens, int Lt_max, const int* codes,
+                                 const int* ncodes, int n_max, int B, const int* layers, int n_layers, const float* head_weights,
+                                 float* attn, float* text_mass, void* stream);
+
 /* ---- stage B: diffusion mel decoder ---------------------------------------------------------- */
 
 /* DiffusionTts.get_conditioning (vqvae/diff_model.py:221-229): refer [B,128,Tmax] -> cond [B,1536] */
@@ -831,6 +861,25 @@ int dtts_op_attention(dtts_handle* h, const float* qkv, const int* lens, int B, 
  * y DEVICE [B][H D][T], relk DEVICE [B][H][T][2 window + 1], ml DEVICE [B][H][T][2]: written at t < len only. */
 int dtts_op_attention_rel(dtts_handle* h, const float* qkv, const int* lens, int B, int T, int H, int D, const float* ek,
                           const float* ev, int window, float scale, float* y, float* relk, float* ml, void* stream);
+/* ONE launch of the attention-probabilities kernel (csrc/attn_probs.hip) on the caller's rows - the read-out behind
+ * dtts_gpt_attentions / dtts_gpt_text_alignment (the attentions of gpt/model.py:392-400, get_attns=True):
+ *   P_h[t][s] = softmax_s(scale q_t . k_s) over ALL keys s <= t, s < len_b;   element (i, j) of sample b <-> t = q0[b] + i, s = k0[b] + j
+ * qkv DEVICE [B][rows][cs] addressed as in dtts_op_attention (no v rows are read); D = 48 only.  lens, q0, nq, k0, nk HOST [B], windows
+ * inside [0, T], nq[b] <= nq_max, nk[b] <= nk_max.  mode 0: out DEVICE [B][H][nq_max][nk_max] = P_h.  mode 1: out DEVICE
+ * [B][nq_max][nk_max] = (first ? 0 : out) + sum_h head_weights[h] P_h, h ascending in fp32 (head_weights HOST [H]).  A key s > t inside
+ * the window is written as exactly 0; elements outside nq[b] x nk[b] and rows t >= len_b are never touched.  Anything else is refused
+ * before a launch. */
+int dtts_op_attn_probs(dtts_handle* h, const float* qkv, const int* lens, int B, int rows, int cs, int T, int H, int D, int q_off, int k_off,
+                       int head_stride, float scale, const int* q0, const int* nq, const int* k0, const int* nk, int nq_max, int nk_max,
+                       int mode, const float* head_weights, int first, float* out, void* stream);
+/* The monotone path through a score matrix (csrc/align_path.hip) - the decoding step of the alignment, no line of the reference:
+ *   dp[0][i] = score[0][i];  dp[j][i] = score[j][i] + max_{i' <= i} dp[j-1][i'];  the prefix argmax and the path's end (the argmax of
+ * row n - 1) take the LOWEST index among equal maxima; path[j] = the column of row j.  score DEVICE [B][n_max][m_max] fp32, n / m HOST
+ * [B] (m[b] >= 1 where n[b] >= 1), path DEVICE int32 [B][n_max], -1 at j >= n[b].  n_max <= gpt_max_mel_pos, m_max <=
+ * gpt_max_text_pos + 1.  One fp32 add and compares per cell: equal, bit for bit, to the same recurrence in fp32 anywhere.  The path may
+ * stay on a column or jump ahead; it need not reach the last column. */
+int dtts_op_monotone_path(dtts_handle* h, const float* score, const int* n, const int* m, int B, int n_max, int m_max, int* path,
+                          void* stream);
 /* The device sampler on given logits rows: HF RepetitionPenalty / Temperature / TopK / TopP processors as the reference's
  * generate() applies them (vqvae/model_24k.py:786-792) + the inverse-CDF draw on uniforms[r].  logits DEVICE [R][V] (R <= 16),
  * history HOST [R][hist_len] ids present in the row's input_ids, uniforms DEVICE [R] -> tokens HOST [R].  Synchronises. */
