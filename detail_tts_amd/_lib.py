@@ -53,6 +53,10 @@ class DttsAttnX3Info(C.Structure):
     _fields_ = [("conv", DttsConvX3Info), ("attn_ksplit", C.c_int), ("attn_p1", C.c_int), ("attn_workgroups", C.c_int)]
 
 
+class DttsGemvInfo(C.Structure):
+    _fields_ = [("slices", C.c_int), ("vec", C.c_int), ("rpw", C.c_int), ("nb", C.c_int)]
+
+
 class DttsKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("launches", C.c_longlong), ("total_ms", C.c_double), ("union_ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -224,6 +228,17 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p]),
     "dtts_op_monotone_path": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dtts_op_philox_normal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_ulonglong, c_int_p, C.c_int, C.c_int, C.c_void_p]),
+    "dtts_op_gemv_block": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DttsGemvInfo), C.c_void_p]),
+    "dtts_op_decode_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_longlong, C.c_int, c_int_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                           C.c_void_p, C.c_void_p]),
+    "dtts_op_gpt_final_ln": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_int_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "dtts_op_ln_fold_vectors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "dtts_op_kv_to_cache": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
 }
 
 _lib = None

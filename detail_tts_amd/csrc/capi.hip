@@ -923,6 +923,54 @@ int dtts_op_monotone_path(dtts_handle* h, const float* score, const int* n, cons
     DTTS_API_END(h)
 }
 
+// ---- the decode chain's kernels, one launch each (include/detail_hip.h)
+int dtts_op_gemv_block(dtts_handle* h, int pro, const float* W, int K, int CoutP, int B, const float* x, int x_stride, const float* parts,
+                       int in_slices, int in_stride, int in_act, const float* in_bias, const float* gamma, float* y_out, float* stats_out,
+                       const float* stats_in, int stats_slices, int K_ln, const float* fold_c, const float* fold_d, float* part,
+                       dtts_gemv_info* info, void* stream) {
+    DTTS_API_BEGIN
+    dtts::GemvIn in;
+    in.x = x; in.x_stride = x_stride; in.parts = parts; in.in_slices = in_slices; in.in_stride = in_stride; in.in_act = in_act;
+    in.in_bias = in_bias; in.gamma = gamma; in.y_out = y_out; in.stats_out = stats_out; in.stats_in = stats_in;
+    in.stats_slices = stats_slices; in.K_ln = K_ln; in.fold_c = fold_c; in.fold_d = fold_d;
+    dtts::GemvShape g{0, 0, 0};
+    int slices = 0;
+    h->m->op_gemv_block(pro, W, K, CoutP, in, B, part, &g, &slices, (hipStream_t)stream);
+    if (info) { info->slices = slices; info->vec = g.vec; info->rpw = g.rpw; info->nb = g.nb; }
+    DTTS_API_END(h)
+}
+
+int dtts_op_decode_attention(dtts_handle* h, const float* part, int slices, int CoutP, const float* stats, int stats_slices,
+                             const float* fold_c, const float* fold_d, float* cache, long long cache_bs, int cap, const int* lp,
+                             const int* step, int B, int H, int D, int ksplit, const float* wproj, int wpCoutP, float* out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->op_decode_attention(part, slices, CoutP, stats, stats_slices, fold_c, fold_d, cache, cache_bs, cap, lp, step, B, H, D, ksplit, wproj,
+                              wpCoutP, out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_op_gpt_final_ln(dtts_handle* h, const float* res, const float* bias, const float* parts, int in_slices, int in_stride, int B,
+                         const float* g1, const float* b1, const float* g2, const float* b2, float* y, int C, const int* step,
+                         int max_steps, float* latents, int lat_cs, void* stream) {
+    DTTS_API_BEGIN
+    h->m->op_gpt_final_ln(res, bias, parts, in_slices, in_stride, B, g1, b1, g2, b2, y, C, step, max_steps, latents, lat_cs, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_op_ln_fold_vectors(dtts_handle* h, const float* W, int K, int CoutP, const float* gamma, const float* beta, const float* bias,
+                            float* c, float* d, void* stream) {
+    DTTS_API_BEGIN
+    h->m->op_ln_fold_vectors(W, K, CoutP, gamma, beta, bias, c, d, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_op_kv_to_cache(dtts_handle* h, const float* qkv, const int* lens, int B, int C, int L, float* cache, long long cache_bs, int cap,
+                        void* stream) {
+    DTTS_API_BEGIN
+    h->m->op_kv_to_cache(qkv, lens, B, C, L, cache, cache_bs, cap, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
 int dtts_op_philox_normal(dtts_handle* h, float* out, int n, int B, unsigned long long seed, const int* sample_ids, int stage,
                           int step, void* stream) {
     DTTS_API_BEGIN

@@ -77,6 +77,9 @@ struct GemvIn {
     const float* fold_d = nullptr;
 };
 int gemv_block_slices(int K, int CoutP);
+// the instantiation launch_gemv_block takes for (K, CoutP, B): VEC columns per lane, RPW weight rows per wave, NB batch rows
+struct GemvShape { int vec, rpw, nb; };
+GemvShape gemv_block_shape(int K, int CoutP, int B);
 void launch_gemv_block(int pro, const float* W, int K, int CoutP, const GemvIn& in, int B, float* part, hipStream_t s);
 
 // single-query attention with c_attn's LN-algebra finish folded in (sums the qkv partials of its head, appends k/v to the cache at
@@ -84,9 +87,12 @@ void launch_gemv_block(int pro, const float* W, int K, int CoutP, const GemvIn& 
 int decode_attention_splits();
 void launch_decode_attention_qkv(const float* part, int slices, int CoutP, const float* stats, int stats_slices, const float* fold_c,
                                  const float* fold_d, float* cache, long long cache_bs, int cache_cs, const GptCtl* ctl, int B, int H, int D,
-                                 float* out, hipStream_t s, const float* wproj = nullptr, int wpCoutP = 0);
+                                 float* out, hipStream_t s, const float* wproj = nullptr, int wpCoutP = 0, int ksplit = 0);
 // wproj (K-major packed [C][wpCoutP] weight of the attention's output projection) given: the projection is applied in the same
 // kernel; out = per-head partials [H][B][wpCoutP] for a GP_RESSUM GEMV with in_slices = H (no key split, no GP_ATTN GEMV)
+// ksplit (split form only): key splits of this launch, 1 .. 8; 0 = decode_attention_splits()
+// LDS the kernel needs for a cache of cache_cs columns (the dynamic score buffer + its static arrays), against the 64 KiB of a workgroup
+bool decode_attention_fits(int cache_cs, bool fused);
 
 // copy k,v rows of a prefill qkv buffer [B, 3C, L] into the cache (columns 0..len-1)
 void launch_kv_to_cache(const float* qkv, long long bs, int cs, const int* lens, int L, int B, int C, float* cache, long long cache_bs,

@@ -395,12 +395,19 @@ static bool gemv_wide(int K, int CoutP) {
 
 int gemv_block_slices(int K, int CoutP) { return gemv_wide(K, CoutP) ? K / 128 : K / gemv_rows(K, CoutP); }
 
+GemvShape gemv_block_shape(int K, int CoutP, int B) {
+    const int nb = B <= 8 ? 8 : 16;
+    if (gemv_wide(K, CoutP)) return {4, 16, nb};
+    return {1, gemv_rows(K, CoutP) == 64 ? 8 : 16, nb};
+}
+
 void launch_gemv_block(int pro, const float* W, int K, int CoutP, const GemvIn& in, int B, float* part, hipStream_t s) {
     DTTS_REQUIRE(B >= 1 && B <= GEMV_MAXB && K % 128 == 0 && CoutP % 4 == 0, "gemv_block shape");
     const int rows = gemv_rows(K, CoutP);
     DTTS_REQUIRE((long long)(K / rows) * CoutP <= (long long)GEMV_PART_FLOATS, "gemv partial scratch (per batch row)");
-    if (gemv_wide(K, CoutP)) gemv_block_launch_v<4, 16>(pro, W, K, CoutP, in, B, part, s);
-    else if (rows == 64) gemv_block_launch_v<1, 8>(pro, W, K, CoutP, in, B, part, s);
+    const GemvShape g = gemv_block_shape(K, CoutP, B);
+    if (g.vec == 4) gemv_block_launch_v<4, 16>(pro, W, K, CoutP, in, B, part, s);
+    else if (g.rpw == 8) gemv_block_launch_v<1, 8>(pro, W, K, CoutP, in, B, part, s);
     else gemv_block_launch_v<1, 16>(pro, W, K, CoutP, in, B, part, s);
     DTTS_CHECK_HIP(hipGetLastError());
 }
@@ -576,21 +583,26 @@ int decode_attention_splits() {
     return n;
 }
 
+bool decode_attention_fits(int cache_cs, bool fused) {
+    return cache_cs >= 0 && sizeof(float) * (size_t)cache_cs + 5376 + (fused ? 256 : 0) <= 64 * 1024;
+}
+
 void launch_decode_attention_qkv(const float* part, int slices, int CoutP, const float* stats, int stats_slices, const float* fold_c,
                                  const float* fold_d, float* cache, long long cache_bs, int cache_cs, const GptCtl* ctl, int B, int H, int D,
-                                 float* out, hipStream_t s, const float* wproj, int wpCoutP) {
+                                 float* out, hipStream_t s, const float* wproj, int wpCoutP, int ksplit) {
     DTTS_REQUIRE(D == 48, "decode attention head dim");
+    DTTS_REQUIRE(ksplit >= 0 && ksplit <= 8, "decode attention: key splits 1 .. 8 (0: the process default)");
     if (wproj) {             // attention + output projection: one (head, row) workgroup, no key split; out = per-head partials [H][B][wpCoutP]
         DTTS_REQUIRE(wpCoutP == 3 * 256 && H * D <= wpCoutP, "fused attention projection: 768 output columns");
-        DTTS_REQUIRE(sizeof(float) * (size_t)cache_cs + 5376 + 256 <= 64 * 1024, "decode attention: KV cache too long for the LDS score buffer");
+        DTTS_REQUIRE(decode_attention_fits(cache_cs, true), "decode attention: KV cache too long for the LDS score buffer");
         hipLaunchKernelGGL((decode_attention_qkv_kernel<48, true>), dim3(H, B, 1), dim3(256), sizeof(float) * cache_cs, s, part, slices, B, CoutP,
                            stats, stats_slices, fold_c, fold_d, cache, cache_bs, cache_cs, ctl, H, out, wproj, wpCoutP);
         DTTS_CHECK_HIP(hipGetLastError());
         return;
     }
     // 64 KiB of LDS per workgroup by default: the dynamic score buffer + 5.1 KiB of static arrays (pvs 4 032 B, qkv_s 576 B, red)
-    DTTS_REQUIRE(sizeof(float) * (size_t)cache_cs + 5376 <= 64 * 1024, "decode attention: KV cache too long for the LDS score buffer");
-    hipLaunchKernelGGL((decode_attention_qkv_kernel<48, false>), dim3(H, B, decode_attention_splits()), dim3(256), sizeof(float) * cache_cs, s, part,
+    DTTS_REQUIRE(decode_attention_fits(cache_cs, false), "decode attention: KV cache too long for the LDS score buffer");
+    hipLaunchKernelGGL((decode_attention_qkv_kernel<48, false>), dim3(H, B, ksplit ? ksplit : decode_attention_splits()), dim3(256), sizeof(float) * cache_cs, s, part,
                        slices, B, CoutP, stats, stats_slices, fold_c, fold_d, cache, cache_bs, cache_cs, ctl, H, out, nullptr, 0);
     DTTS_CHECK_HIP(hipGetLastError());
 }

@@ -139,6 +139,7 @@ struct GptSession {
     int* tok_err = nullptr;
     unsigned* tok_epoch = nullptr;
     int tok_wgs = 128;                 // workgroups of the token kernel for this session (dtts_gpt_options.token_wgs, else option gpt_token_wgs)
+    bool fuse_proj = true;             // the chain's attention applies its output projection itself (option gpt_fuse_proj, latched at prefill)
     // beam search (gpt_beam.hip): beam_K > 1 = the rows are B / beam_K utterances x beam_K beams and the beam kernels take the sampler's
     // place.  The buffers are laid out for every session (their addresses do not depend on K); graphs are dropped when K changes.
     int beam_K = 0, beam_es = 0;
@@ -344,6 +345,25 @@ public:
                        float scale, const int* q0_host, const int* nq_host, const int* k0_host, const int* nk_host, int nq_max, int nk_max,
                        int mode, const float* w_host, int first, float* out, hipStream_t s);
     void op_monotone_path(const float* score, const int* n_host, const int* m_host, int B, int n_max, int m_max, int* path, hipStream_t s);
+    // ---- the decode chain's kernels (gpt_kernels.h), ONE launch each on the caller's buffers (model_gpt.hip; weightless handles serve them).
+    // Every argument the launcher or the kernel cannot take is refused before anything is launched or uploaded.
+    // op_gemv_block: launch_gemv_block(pro, W [K][CoutP], in, B) -> part [slices][B][CoutP]; `in` carries the caller's DEVICE pointers
+    // (the fields the prologue does not read may be null); shape / slices: what the launcher chose.
+    void op_gemv_block(int pro, const float* W, int K, int CoutP, const GemvIn& in, int B, float* part, GemvShape* shape, int* slices,
+                       hipStream_t s);
+    // op_decode_attention: launch_decode_attention_qkv with a control block built from lp / step (HOST [B]); cache DEVICE [B][cache_bs]
+    // (K [C][cap] | V [cap][C]), updated in place; out = records [B][H][KS][ATT_REC], or with wproj [H D][768] partials [H][B][768]
+    void op_decode_attention(const float* part, int slices, int CoutP, const float* stats, int stats_slices, const float* fold_c,
+                             const float* fold_d, float* cache, long long cache_bs, int cap, const int* lp_host, const int* step_host,
+                             int B, int H, int D, int ksplit, const float* wproj, int wpCoutP, float* out, hipStream_t s);
+    // op_gpt_final_ln: launch_gpt_final_ln; step_host [B] / max_steps / latents [B][C][lat_cs] (may be null) make the control block
+    void op_gpt_final_ln(const float* res, const float* bias, const float* parts, int in_slices, int in_stride, int B, const float* g1,
+                         const float* b1, const float* g2, const float* b2, float* y, int C, const int* step_host, int max_steps,
+                         float* latents, int lat_cs, hipStream_t s);
+    void op_ln_fold_vectors(const float* W, int K, int CoutP, const float* gamma, const float* beta, const float* bias, float* c, float* d,
+                            hipStream_t s);
+    // op_kv_to_cache: launch_kv_to_cache on qkv [B][3 C][L], lens HOST [B] in [0, min(L, cap)] -> cache [B][cache_bs >= 2 C cap]
+    void op_kv_to_cache(const float* qkv, const int* lens_host, int B, int C, int L, float* cache, long long cache_bs, int cap, hipStream_t s);
     // ---- stage C
     void mel_style(const MelStyleW& w, const float* mel, const int* lens_dev, const int* lens_host, int B, int T, float* g_out,
                    hipStream_t s, bool padded_batch = false);
@@ -440,6 +460,9 @@ public:
         else if (key == "gpt_graph") opt_gpt_graph_ = value != 0;
         else if (key == "x3_range_check") opt_range_check_ = value != 0;
         else if (key == "gpt_token_kernel") { opt_gpt_token_ = value != 0; if (value != 0) tok_failed_ = false; gpt_drop_graphs(); }
+        // 0: the chain's attention leaves key-split records and a GP_ATTN GEMV projects them (the form of any model that is not 16 x 48
+        // with a 768-column projection); latched per session at prefill.  DTTS_GPT_FUSE_PROJ, when set, wins
+        else if (key == "gpt_fuse_proj") { DTTS_REQUIRE(value == 0 || value == 1, "gpt_fuse_proj: 0 or 1"); opt_gpt_fuse_proj_ = value != 0; gpt_drop_graphs(); }
         else if (key == "gpt_token_exclusive_cu") { opt_tok_exclusive_ = value != 0; gpt_drop_graphs(); }
         else if (key == "gpt_token_min_rows") { DTTS_REQUIRE(value == 1 || value == 4 || value == 8, "gpt_token_min_rows: 1, 4 or 8"); opt_tok_min_rows_ = value; gpt_drop_graphs(); }
         else if (key == "gpt_token_wgs") { DTTS_REQUIRE(value == 128 || value == 64 || value == 32, "gpt_token_wgs: 128, 64 or 32"); opt_tok_wgs_ = value; gpt_drop_graphs(); }
@@ -467,6 +490,7 @@ public:
     int get_option(const std::string& key) const {      // the options a caller restores after a per-call override
         if (key == "conv_x3") return use_x3() ? 1 : 0;
         if (key == "trunk_fp16") return opt_trunk_fp16_ ? 1 : 0;
+        if (key == "gpt_fuse_proj") return opt_gpt_fuse_proj_ ? 1 : 0;
         throw Error(-1, "option '" + key + "' cannot be read back");
     }
     std::string last_error;
@@ -660,6 +684,7 @@ private:
     GptTokenParams tokp_;                 // its launch parameters (weight side filled at bind time, session side at prefill)
     bool tok_ok_ = false;                 // the model has the shape the token kernel is written for
     bool opt_gpt_token_ = true;           // option "gpt_token_kernel"
+    bool opt_gpt_fuse_proj_ = true;       // option "gpt_fuse_proj"
     bool opt_tok_exclusive_ = false;      // option "gpt_token_exclusive_cu": 1 = the token kernel asks for whole CUs (a CU's whole LDS).  Default 0 since round 6:
                                           // 2 x 500 headline requests through infer_stream, one run per setting, every waveform bit-identical to its
                                           // blocking infer() (profiles/r06_soak.txt), and sharing is 0.4 - 0.55 % faster

@@ -491,6 +491,10 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
         const int wgs = o.token_wgs ? o.token_wgs : opt_tok_wgs_;      // latched: a later set_option does not change a running session's kernel
         if (wgs != gs_.tok_wgs) gpt_drop_graphs();                      // (captured decode graphs hold the previous session's kernel choice)
         gs_.tok_wgs = wgs;
+        static const int env_fuse = env_tri("DTTS_GPT_FUSE_PROJ");       // the env value wins when set, as the token kernel's switches do
+        const bool fuse = env_fuse >= 0 ? env_fuse != 0 : opt_gpt_fuse_proj_;
+        if (fuse != gs_.fuse_proj) gpt_drop_graphs();                   // (the captured chain holds K2 + K3 in one form or the other)
+        gs_.fuse_proj = fuse;
     }
     c.top_k = o.top_k;
     c.suppress_eos = o.suppress_eos;
@@ -726,8 +730,7 @@ void Model::gpt_step_launches(hipStream_t s) {
         a.y_out = gs_.x;
         a.stats_out = gs_.st1;
         launch_gemv_block(GP_RESSUM, w.attn.w, C, w.attn.CoutP, a, B, gs_.part, s);
-        static const bool fuse_proj = env_on("DTTS_GPT_FUSE_PROJ");
-        const bool fp = fuse_proj && w.proj.CoutP == 768 && H == 16;
+        const bool fp = gs_.fuse_proj && w.proj.CoutP == 768 && H == 16;
         if (fp) {                                        // K2 + K3: attention and its output projection, per-head partials in part2
             launch_decode_attention_qkv(gs_.part, sq, w.attn.CoutP, gs_.st1, st_sl, w.attn_c, w.attn_d, cache, gs_.kv_bs, gs_.cap, gs_.ctl, B, H,
                                         D, gs_.part2, s, w.proj.w, w.proj.CoutP);
@@ -1497,6 +1500,116 @@ void Model::gpt_forward_losses(const float* refer, const int* refer_lens_host, i
     score_head(text_head_, f.enc + 1, bs, f.L, tt.data(), ntt.data(), nt, B, text_logprob, nullptr, s);
     score_head(mel_head_, f.enc + (f.L - nm), bs, f.L, tm.data(), ntm.data(), nm, B, mel_logprob, mel_logits, s);
     launch_gpt_loss_means(text_logprob, B * nt, mel_logprob, B * nm, losses_out, s);
+}
+
+// ------------------------------------------------------------------------------------------ unit entries of the decode chain
+// One launch each of the kernels gpt_step_launches strings together, on the caller's buffers (tests/test_gpu_gpt_decode.py).  The sizes
+// of the buffers are the caller's (Runtime checks the tensors); what is checked here is every relation the launcher and the kernel
+// rely on.  Nothing is uploaded or launched before the last check.  The launches are bracketed for the profiler (level 2).
+void Model::op_gemv_block(int pro, const float* W, int K, int CoutP, const GemvIn& in, int B, float* part, GemvShape* shape, int* slices,
+                          hipStream_t s) {
+    DTTS_REQUIRE(pro == GP_PLAIN || pro == GP_RESSUM || pro == GP_LNPARTS || pro == GP_ATTN, "op_gemv_block: prologue 0 .. 3");
+    DTTS_REQUIRE(W && part, "op_gemv_block: null argument");
+    DTTS_REQUIRE(B >= 1 && B <= GEMV_MAXB, "op_gemv_block: 1 .. 16 batch rows");
+    DTTS_REQUIRE(K >= 128 && K <= (1 << 16) && K % 128 == 0, "op_gemv_block: K must be a multiple of 128");
+    DTTS_REQUIRE(CoutP >= 4 && CoutP <= (1 << 20) && CoutP % 4 == 0, "op_gemv_block: CoutP must be a multiple of 4");
+    DTTS_REQUIRE((long long)gemv_block_slices(K, CoutP) * CoutP <= (long long)GEMV_PART_FLOATS, "op_gemv_block: partials beyond the per-row scratch");
+    if (pro == GP_PLAIN || pro == GP_RESSUM) DTTS_REQUIRE(in.x && in.x_stride >= K, "op_gemv_block: x rows [B][x_stride >= K]");
+    if (pro == GP_RESSUM) {
+        DTTS_REQUIRE(in.gamma && in.y_out && in.stats_out, "op_gemv_block: the residual prologue needs gamma, y_out and stats_out");
+        DTTS_REQUIRE(in.in_slices >= 0 && in.in_slices <= 64, "op_gemv_block: in_slices 0 .. 64");
+        DTTS_REQUIRE(in.in_slices == 0 || (in.parts && in.in_stride >= K), "op_gemv_block: partials [in_slices][B][in_stride >= K]");
+    }
+    if (pro == GP_LNPARTS) {
+        DTTS_REQUIRE(in.parts && in.stats_in && in.fold_c && in.fold_d, "op_gemv_block: the LayerNorm prologue needs parts, stats_in, fold_c and fold_d");
+        DTTS_REQUIRE(in.in_slices >= 1 && in.in_slices <= 64 && in.in_stride >= K, "op_gemv_block: partials [in_slices in 1 .. 64][B][in_stride >= K]");
+        DTTS_REQUIRE(in.stats_slices >= 1 && in.stats_slices <= 64 && in.K_ln >= 1, "op_gemv_block: statistics [stats_slices in 1 .. 64][B][2] over K_ln >= 1 values");
+        DTTS_REQUIRE(in.in_act == ACT_NONE || in.in_act == ACT_GELU_NEW, "op_gemv_block: in_act is 0 or gelu_new");
+    }
+    if (pro == GP_ATTN) {
+        DTTS_REQUIRE(in.parts && in.in_stride >= 1 && in.in_stride <= ATT_REC - 2 && K % in.in_stride == 0, "op_gemv_block: records of head dim in_stride, K = H in_stride");
+        DTTS_REQUIRE(in.in_slices >= 1 && in.in_slices <= 8, "op_gemv_block: 1 .. 8 key splits");
+    }
+    // ---- nothing has been launched up to here
+    const GemvShape g = gemv_block_shape(K, CoutP, B);
+    if (shape) *shape = g;
+    if (slices) *slices = gemv_block_slices(K, CoutP);
+    static const char* tags[3][2] = {{"gemv_block_kernel<1,8,8>", "gemv_block_kernel<1,8,16>"},
+                                     {"gemv_block_kernel<1,16,8>", "gemv_block_kernel<1,16,16>"},
+                                     {"gemv_block_kernel<4,16,8>", "gemv_block_kernel<4,16,16>"}};
+    ProfScope ps(tags[g.vec == 4 ? 2 : (g.rpw == 16 ? 1 : 0)][g.nb == 16 ? 1 : 0], 0.0, 4.0 * K * CoutP, s);
+    launch_gemv_block(pro, W, K, CoutP, in, B, part, s);
+}
+
+void Model::op_decode_attention(const float* part, int slices, int CoutP, const float* stats, int stats_slices, const float* fold_c,
+                                const float* fold_d, float* cache, long long cache_bs, int cap, const int* lp_host, const int* step_host,
+                                int B, int H, int D, int ksplit, const float* wproj, int wpCoutP, float* out, hipStream_t s) {
+    DTTS_REQUIRE(part && stats && fold_c && fold_d && cache && lp_host && step_host && out, "op_decode_attention: null argument");
+    DTTS_REQUIRE(D == 48, "op_decode_attention: head dim 48 is the only instantiation");
+    DTTS_REQUIRE(B >= 1 && B <= GEMV_MAXB && H >= 1 && H <= 64, "op_decode_attention: 1 .. 16 rows, 1 .. 64 heads");
+    DTTS_REQUIRE(slices >= 1 && slices <= 64 && stats_slices >= 1 && stats_slices <= 64, "op_decode_attention: slice counts 1 .. 64");
+    DTTS_REQUIRE(CoutP >= 3 * H * D && CoutP <= (1 << 20), "op_decode_attention: the qkv partials need 3 H D columns");
+    DTTS_REQUIRE(ksplit >= 0 && ksplit <= 8, "op_decode_attention: key splits 1 .. 8 (0: the process default)");
+    DTTS_REQUIRE(cap >= 1 && decode_attention_fits(cap, wproj != nullptr), "op_decode_attention: cap beyond the LDS score buffer");
+    DTTS_REQUIRE(cache_bs >= (long long)2 * H * D * cap, "op_decode_attention: a row's cache is K [C][cap] | V [cap][C]");
+    if (wproj) DTTS_REQUIRE(wpCoutP == 768 && H * D <= 768 && ksplit == 0, "op_decode_attention: the fused projection is 768 columns wide and takes no key split");
+    for (int b = 0; b < B; ++b)
+        DTTS_REQUIRE(lp_host[b] >= 0 && step_host[b] >= 0 && lp_host[b] + step_host[b] >= 1 && (long long)lp_host[b] + step_host[b] <= cap,
+                     "op_decode_attention: 1 <= lp + step <= cap for every row");
+    // ---- nothing has been launched or uploaded up to here
+    GptCtl c;
+    std::memset(&c, 0, sizeof(c));
+    for (int b = 0; b < B; ++b) { c.lp[b] = lp_host[b]; c.step[b] = step_host[b]; }
+    static_assert(sizeof(GptCtl) % sizeof(int) == 0, "the control block travels through the int upload ring");
+    const GptCtl* ctl = reinterpret_cast<const GptCtl*>(upload_ints(reinterpret_cast<const int*>(&c), (int)(sizeof(GptCtl) / sizeof(int)), s));
+    ProfScope ps(wproj ? "decode_attention_qkv_kernel<48,proj>" : "decode_attention_qkv_kernel<48,split>", 0.0, 8.0 * B * H * D * cap, s);
+    launch_decode_attention_qkv(part, slices, CoutP, stats, stats_slices, fold_c, fold_d, cache, cache_bs, cap, ctl, B, H, D, out, s, wproj,
+                                wpCoutP, ksplit);
+}
+
+void Model::op_gpt_final_ln(const float* res, const float* bias, const float* parts, int in_slices, int in_stride, int B, const float* g1,
+                            const float* b1, const float* g2, const float* b2, float* y, int C, const int* step_host, int max_steps,
+                            float* latents, int lat_cs, hipStream_t s) {
+    DTTS_REQUIRE(res && g1 && b1 && g2 && b2 && y && step_host, "op_gpt_final_ln: null argument");
+    DTTS_REQUIRE(C >= 1 && C <= 1024, "op_gpt_final_ln: width 1 .. 1024");
+    DTTS_REQUIRE(B >= 1 && B <= GEMV_MAXB, "op_gpt_final_ln: 1 .. 16 rows");
+    DTTS_REQUIRE(in_slices >= 0 && in_slices <= 64, "op_gpt_final_ln: in_slices 0 .. 64");
+    DTTS_REQUIRE(in_slices == 0 || (parts && in_stride >= C), "op_gpt_final_ln: partials [in_slices][B][in_stride >= C]");
+    DTTS_REQUIRE(!latents || lat_cs >= 1, "op_gpt_final_ln: latents [B][C][lat_cs]");
+    for (int b = 0; b < B; ++b)
+        DTTS_REQUIRE(step_host[b] >= 0 && (!latents || step_host[b] >= max_steps || step_host[b] < lat_cs),
+                     "op_gpt_final_ln: a step below max_steps must be a column of latents");
+    // ---- nothing has been launched or uploaded up to here
+    GptCtl c;
+    std::memset(&c, 0, sizeof(c));
+    for (int b = 0; b < B; ++b) c.step[b] = step_host[b];
+    c.max_steps = max_steps;
+    c.latents = latents;
+    c.lat_bs = (long long)C * lat_cs;
+    c.lat_cs = lat_cs;
+    const GptCtl* ctl = reinterpret_cast<const GptCtl*>(upload_ints(reinterpret_cast<const int*>(&c), (int)(sizeof(GptCtl) / sizeof(int)), s));
+    ProfScope ps("gpt_final_ln_kernel", 0.0, 8.0 * B * C, s);
+    launch_gpt_final_ln(res, bias, parts, in_slices, in_stride, B, g1, b1, g2, b2, y, C, ctl, s);
+}
+
+void Model::op_ln_fold_vectors(const float* W, int K, int CoutP, const float* gamma, const float* beta, const float* bias, float* c, float* d,
+                               hipStream_t s) {
+    DTTS_REQUIRE(W && gamma && beta && c && d, "op_ln_fold_vectors: null argument");
+    DTTS_REQUIRE(K >= 1 && K <= (1 << 16) && CoutP >= 1 && CoutP <= (1 << 20), "op_ln_fold_vectors: sizes");
+    ProfScope ps("ln_fold_vectors_kernel", 0.0, 4.0 * K * CoutP, s);
+    launch_ln_fold_vectors(W, K, CoutP, gamma, beta, bias, c, d, s);
+}
+
+void Model::op_kv_to_cache(const float* qkv, const int* lens_host, int B, int C, int L, float* cache, long long cache_bs, int cap,
+                           hipStream_t s) {
+    DTTS_REQUIRE(qkv && lens_host && cache, "op_kv_to_cache: null argument");
+    DTTS_REQUIRE(B >= 1 && B <= 65535 && C >= 1 && 2 * C <= 65535 && L >= 1 && L <= (1 << 20) && cap >= 1 && cap <= (1 << 20), "op_kv_to_cache: sizes");
+    DTTS_REQUIRE(cache_bs >= (long long)2 * C * cap, "op_kv_to_cache: a row's cache is K [C][cap] | V [cap][C]");
+    for (int b = 0; b < B; ++b) DTTS_REQUIRE(lens_host[b] >= 0 && lens_host[b] <= L && lens_host[b] <= cap, "op_kv_to_cache: lengths must lie in [0, min(L, cap)]");
+    // ---- nothing has been launched or uploaded up to here
+    const int* dl = upload_ints(lens_host, B, s);
+    ProfScope ps("kv_to_cache_kernel", 0.0, 16.0 * B * C * L, s);
+    launch_kv_to_cache(qkv, (long long)3 * C * L, L, dl, L, B, C, cache, cache_bs, cap, s);
 }
 
 }  // namespace dtts

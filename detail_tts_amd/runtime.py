@@ -122,7 +122,7 @@ class Runtime:
         self._rc(self.lib.dtts_set_option(self.h, key.encode(), int(value)))
 
     def get_option(self, key):
-        """"conv_x3" / "trunk_fp16" as the library holds them"""
+        """"conv_x3" / "trunk_fp16" / "gpt_fuse_proj" as the library holds them"""
         v = C.c_int(0)
         self._rc(self.lib.dtts_get_option(self.h, key.encode(), C.byref(v)))
         return int(v.value)
@@ -1424,6 +1424,179 @@ class Runtime:
         self._rc(self.lib.dtts_op_attention_rel(self.h, _ptr(qkv), li[0] if li else None, B, T, heads, dim, _ptr(ek), _ptr(ev), window,
                                                 float(scale), _ptr(y), _ptr(relk), _ptr(ml), self._stream()))
         return (y, relk, guard, ml) if want_ml else (y, relk, guard)
+
+    # ---- the GPT decode chain's kernels (csrc/gpt_kernels.hip), ONE launch each on the caller's tensors.  No weights are read: a
+    # handle made with parts=() serves them.  Every output is handed over inside a NaN-filled allocation with a guard slab behind it.
+    GEMV_PROLOGUES = {"plain": 0, "ressum": 1, "lnparts": 2, "attn": 3}
+
+    def _nan(self, *shape):
+        return torch.full(tuple(shape), float("nan"), device=self.device, dtype=torch.float32)
+
+    def op_gemv_block(self, pro, W, B, x=None, parts=None, in_slices=0, in_act=0, in_bias=None, gamma=None, stats_in=None, stats_slices=0,
+                      K_ln=0, fold_c=None, fold_d=None, head_dim=0):
+        """ONE launch_gemv_block: part[slice, b, col] = sum_{k in slice} v(b, k) W[k, col] over W [K, CoutP], with v by prologue
+        pro = "plain" (x [>= B, x_stride >= K]), "ressum" (v = x + in_bias + sum of the first in_slices slices of parts
+        [>= in_slices, B, in_stride >= K]; the GEMV input is gamma v; also returns y_out [B, K] = v and stats_out [slices, B, 2] =
+        (sum v, sum v^2) per slice), "lnparts" (v = act(r (sum parts - mu fold_c) + fold_d), (mu, r) from stats_in
+        [>= stats_slices, B, 2] over K_ln values, in_act 0 or 4 = gelu_new) or "attn" (parts = records [B, K / head_dim, in_slices, 64]
+        of op_decode_attention).  -> dict(part [slices, B, CoutP], guard (every slab of the allocation behind part), y_out, y_guard,
+        stats_out, stats_guard (ressum; else None), slices, shape = (VEC, RPW, NB) the launcher chose).  Whatever the launcher cannot
+        take raises DttsError before anything is launched."""
+        if pro not in self.GEMV_PROLOGUES:
+            raise DttsError("op_gemv_block: pro is 'plain', 'ressum', 'lnparts' or 'attn'")
+        for t, n in ((W, "W"), (x, "x"), (parts, "parts"), (in_bias, "in_bias"), (gamma, "gamma"), (stats_in, "stats_in"), (fold_c, "fold_c"),
+                     (fold_d, "fold_d")):
+            _check(t, n)
+        if W is None or W.dim() != 2:
+            raise DttsError("op_gemv_block: W must be [K, CoutP]")
+        K, CoutP = W.shape
+        B, in_slices, stats_slices, K_ln, head_dim = int(B), int(in_slices), int(stats_slices), int(K_ln), int(head_dim)
+        if B < 1 or K < 1:
+            raise DttsError("op_gemv_block: empty GEMV")
+        x_stride = in_stride = 0
+        if pro in ("plain", "ressum"):
+            if x is None or x.dim() != 2 or x.shape[0] < B:
+                raise DttsError("op_gemv_block: x must be [>= B, x_stride]")
+            x_stride = x.shape[1]
+        if pro in ("ressum", "lnparts") and (in_slices or pro == "lnparts"):
+            if parts is None or parts.dim() != 3 or parts.shape[0] < in_slices or parts.shape[1] != B:
+                raise DttsError("op_gemv_block: parts must be [>= in_slices, B, in_stride]")
+            in_stride = parts.shape[2]
+        if pro == "ressum" and (gamma is None or gamma.numel() != K or (in_bias is not None and in_bias.numel() != K)):
+            raise DttsError("op_gemv_block: gamma and in_bias hold K values")
+        if pro == "lnparts":
+            if stats_in is None or stats_in.dim() != 3 or stats_in.shape[0] < stats_slices or tuple(stats_in.shape[1:]) != (B, 2):
+                raise DttsError("op_gemv_block: stats_in must be [>= stats_slices, B, 2]")
+            if fold_c is None or fold_d is None or fold_c.numel() != K or fold_d.numel() != K:
+                raise DttsError("op_gemv_block: fold_c and fold_d hold K values")
+        if pro == "attn":
+            if head_dim < 1 or K % head_dim or parts is None or tuple(parts.shape) != (B, K // head_dim, in_slices, 64):
+                raise DttsError("op_gemv_block: parts must be the records [B, K / head_dim, in_slices, 64]")
+            in_stride = head_dim
+        smax = max(K // 64, 1)
+        buf = self._nan(smax + 1, B, CoutP)
+        y_out, y_guard = self._nan_with_guard(B, K) if pro == "ressum" else (None, None)
+        sbuf = self._nan(smax + 1, B, 2) if pro == "ressum" else None
+        info = _lib.DttsGemvInfo()
+        self._rc(self.lib.dtts_op_gemv_block(self.h, self.GEMV_PROLOGUES[pro], _ptr(W), K, CoutP, B, _ptr(x), x_stride, _ptr(parts), in_slices,
+                                             in_stride, int(in_act), _ptr(in_bias), _ptr(gamma), _ptr(y_out), _ptr(sbuf), _ptr(stats_in),
+                                             stats_slices, K_ln, _ptr(fold_c), _ptr(fold_d), _ptr(buf), C.byref(info), self._stream()))
+        n = int(info.slices)
+        return dict(part=buf[:n], guard=buf[n:], y_out=y_out, y_guard=y_guard, stats_out=None if sbuf is None else sbuf[:n],
+                    stats_guard=None if sbuf is None else sbuf[n:], slices=n, shape=(int(info.vec), int(info.rpw), int(info.nb)))
+
+    @staticmethod
+    def decode_attention_splits():
+        """the key splits of a decode attention launched with ksplit = 0 (DTTS_GPT_KSPLIT, 1 .. 8, default 2; read once per process)"""
+        import os
+        try:
+            k = int(os.environ.get("DTTS_GPT_KSPLIT", "") or 2)
+        except ValueError:
+            k = 2
+        return min(max(k, 1), 8)
+
+    def op_decode_attention(self, part, slices, stats, stats_slices, fold_c, fold_d, cache, lp, step, B, H, ksplit=0, wproj=None, dim=48,
+                            cap=None):
+        """ONE launch_decode_attention_qkv for the token at step[b] of rows whose prefix holds lp[b] positions: q / k / v of head h =
+        r_b (sum of the first `slices` slices of part [>= slices, B, CoutP] - mu_b fold_c) + fold_d at columns {0, C, 2 C} + dim h
+        (C = H dim; (mu_b, r_b) from stats [>= stats_slices, B, 2] over C values); k and v are written into cache [B, cache_bs] (K
+        [C, cap] then V [cap, C]; cap defaults to cache_bs // 2 C) at column pos = lp + step - 1 IN PLACE, and the new token attends to
+        columns 0 .. pos.  -> (out, guard): the records [B, H, KS, 64] = (max, denominator, 48 unnormalised sums, 14 floats never
+        written) of KS = ksplit key ranges (0: decode_attention_splits()), or with wproj [C, 768] the per-head partials [H, B, 768]
+        of the output projection.  guard: one more slab of the leading dimension, directly behind out."""
+        for t, n in ((part, "part"), (stats, "stats"), (fold_c, "fold_c"), (fold_d, "fold_d"), (cache, "cache"), (wproj, "wproj")):
+            _check(t, n)
+        B, H, dim, slices, stats_slices, ksplit = int(B), int(H), int(dim), int(slices), int(stats_slices), int(ksplit)
+        if min(B, H, dim) < 1:
+            raise DttsError("op_decode_attention: empty attention")
+        Cw = H * dim
+        if part is None or part.dim() != 3 or part.shape[0] < slices or part.shape[1] != B:
+            raise DttsError("op_decode_attention: part must be [>= slices, B, CoutP]")
+        CoutP = part.shape[2]
+        if stats is None or stats.dim() != 3 or stats.shape[0] < stats_slices or tuple(stats.shape[1:]) != (B, 2):
+            raise DttsError("op_decode_attention: stats must be [>= stats_slices, B, 2]")
+        if fold_c is None or fold_d is None or fold_c.numel() != CoutP or fold_d.numel() != CoutP:
+            raise DttsError("op_decode_attention: fold_c and fold_d hold CoutP values")
+        if cache is None or cache.dim() != 2 or cache.shape[0] != B:
+            raise DttsError("op_decode_attention: cache must be [B, cache_bs]")
+        cap = cache.shape[1] // (2 * Cw) if cap is None else int(cap)
+        li, si = _ints(lp), _ints(step)
+        if li[1].size != B or si[1].size != B:
+            raise DttsError("op_decode_attention: one lp and one step per row")
+        wpCoutP = 0
+        if wproj is not None:
+            if wproj.dim() != 2 or wproj.shape[0] != Cw:
+                raise DttsError("op_decode_attention: wproj must be [H dim, columns]")
+            wpCoutP = wproj.shape[1]
+            out, guard = self._nan_with_guard(H, B, wpCoutP)
+        else:
+            if not 0 <= ksplit <= 8:
+                raise DttsError("op_decode_attention: ksplit 0 .. 8")
+            ksplit = ksplit or self.decode_attention_splits()          # resolved here: the records are laid out for the count the kernel runs
+            out, guard = self._nan_with_guard(B, H, ksplit, 64)
+        self._rc(self.lib.dtts_op_decode_attention(self.h, _ptr(part), slices, CoutP, _ptr(stats), stats_slices, _ptr(fold_c), _ptr(fold_d),
+                                                   _ptr(cache), cache.shape[1], cap, li[0], si[0], B, H, dim, ksplit, _ptr(wproj), wpCoutP,
+                                                   _ptr(out), self._stream()))
+        return out, guard
+
+    def op_gpt_final_ln(self, res, g1, b1, g2, b2, bias=None, parts=None, in_slices=0, step=None, max_steps=0, latents=None):
+        """ONE launch_gpt_final_ln: y [B, C] = LN(LN(res + bias + sum of the first in_slices slices of parts [>= in_slices, B,
+        in_stride >= C]; g1, b1); g2, b2), C <= 1024 -> (y, guard).  latents [B, C, lat_cs] (optional, modified IN PLACE): column
+        step[b] of row b receives y[b] when step[b] < max_steps."""
+        for t, n in ((res, "res"), (g1, "g1"), (b1, "b1"), (g2, "g2"), (b2, "b2"), (bias, "bias"), (parts, "parts"), (latents, "latents")):
+            _check(t, n)
+        if res is None or res.dim() != 2 or min(res.shape) < 1:
+            raise DttsError("op_gpt_final_ln: res must be [B, C]")
+        B, Cw = res.shape
+        in_slices, in_stride = int(in_slices), 0
+        if any(t is None or t.numel() != Cw for t in (g1, b1, g2, b2)) or (bias is not None and bias.numel() != Cw):
+            raise DttsError("op_gpt_final_ln: the LayerNorm vectors and the bias hold C values")
+        if in_slices:
+            if parts is None or parts.dim() != 3 or parts.shape[0] < in_slices or parts.shape[1] != B:
+                raise DttsError("op_gpt_final_ln: parts must be [>= in_slices, B, in_stride]")
+            in_stride = parts.shape[2]
+        lat_cs = 0
+        if latents is not None:
+            if latents.dim() != 3 or tuple(latents.shape[:2]) != (B, Cw):
+                raise DttsError("op_gpt_final_ln: latents must be [B, C, lat_cs]")
+            lat_cs = latents.shape[2]
+        si = _ints([0] * B if step is None else step)
+        if si[1].size != B:
+            raise DttsError("op_gpt_final_ln: one step per row")
+        y, guard = self._nan_with_guard(B, Cw)
+        self._rc(self.lib.dtts_op_gpt_final_ln(self.h, _ptr(res), _ptr(bias), _ptr(parts), in_slices, in_stride, B, _ptr(g1), _ptr(b1), _ptr(g2),
+                                               _ptr(b2), _ptr(y), Cw, si[0], int(max_steps), _ptr(latents), lat_cs, self._stream()))
+        return y, guard
+
+    def op_ln_fold_vectors(self, W, gamma, beta, bias=None):
+        """ONE launch_ln_fold_vectors on W [K, CoutP]: c[n] = sum_k gamma[k] W[k, n], d[n] = sum_k beta[k] W[k, n] + bias[n]
+        -> (c, d, guard), three rows of one NaN-filled allocation"""
+        for t, n in ((W, "W"), (gamma, "gamma"), (beta, "beta"), (bias, "bias")):
+            _check(t, n)
+        if W is None or W.dim() != 2 or min(W.shape) < 1:
+            raise DttsError("op_ln_fold_vectors: W must be [K, CoutP]")
+        K, CoutP = W.shape
+        if gamma is None or beta is None or gamma.numel() != K or beta.numel() != K or (bias is not None and bias.numel() != CoutP):
+            raise DttsError("op_ln_fold_vectors: gamma and beta hold K values, bias CoutP")
+        buf = self._nan(3, CoutP)
+        self._rc(self.lib.dtts_op_ln_fold_vectors(self.h, _ptr(W), K, CoutP, _ptr(gamma), _ptr(beta), _ptr(bias), _ptr(buf[0]), _ptr(buf[1]),
+                                                  self._stream()))
+        return buf[0], buf[1], buf[2]
+
+    def op_kv_to_cache(self, qkv, lens, cap):
+        """ONE launch_kv_to_cache: rows [C, 3 C) of the prefill's qkv [B, 3 C, L], columns < lens[b] -> (cache, guard): cache
+        [B, 2 C cap] = K [C, cap] then V [cap, C] (token-major) of every row, NaN wherever the kernel does not write"""
+        _check(qkv, "qkv")
+        if qkv is None or qkv.dim() != 3 or qkv.shape[1] % 3 or min(qkv.shape) < 1:
+            raise DttsError("op_kv_to_cache: qkv must be [B, 3 C, L]")
+        B, C3, L = qkv.shape
+        li = _ints(lens)
+        if li[1].size != B or int(cap) < 1:
+            raise DttsError("op_kv_to_cache: one length per row, cap >= 1")
+        bs = 2 * (C3 // 3) * int(cap)
+        cache, guard = self._nan_with_guard(B, bs)
+        self._rc(self.lib.dtts_op_kv_to_cache(self.h, _ptr(qkv), li[0], B, C3 // 3, L, _ptr(cache), bs, int(cap), self._stream()))
+        return cache, guard
 
     def diff_p_sample(self, x, code_emb, step, seed, sample_ids, lens=None, noise=None, return_x0=False):
         """one GaussianDiffusion.p_sample at sampling step `step` (49 = first): returns the new x (and pred_xstart)"""

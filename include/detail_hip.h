@@ -716,6 +716,11 @@ int dtts_spectrogram(dtts_handle* h, const float* wav, const int* lens, int B, i
  *                 tiles, fused column GEMVs, weights streamed through a register window): codes and latents bit-identical, 105 / 205 ms per
  *                 234 tokens alone instead of 80, but half / a quarter of the CUs - next to a diffusion 64 is 5 - 7 ms per request
  *                 faster than 128 and 32 slower (profiles/r06_token_wgs.txt); env DTTS_GPT_TOKEN_WGS overrides both;
+ *   "gpt_fuse_proj" (default 1): the launch-per-GEMV decode chain (token kernel off, or sessions of more than 16 rows) applies the
+ *                 attention's output projection inside the attention kernel (16 heads x 48, 768 columns).  0 = the key-split attention
+ *                 (flash-decoding records) followed by the projection GEMV that merges them - the form every other model shape takes.
+ *                 Latched per session at prefill; a change drops the captured decode graphs.  env DTTS_GPT_FUSE_PROJ, when set, wins;
+ *                 readable with dtts_get_option;
  *   "gpt_token_min_rows" (default 1): the smallest instantiation of the token kernel a session may take: 1-row sessions run the
  *                 1-row kernel, sessions of <= 4 rows the 4-row one (round 5: the batch-1 latency case; per row bit-identical to the
  *                 8-row one); 4 / 8 = the smallest allowed is the 4- / 8-row kernel; env DTTS_GPT_TOKEN_MIN_ROWS;
@@ -759,7 +764,7 @@ int dtts_spectrogram(dtts_handle* h, const float* wav, const int* lens, int B, i
  * Any other key fails with -1 "unknown option" - also the keys of the two experiments that earlier versions carried and that were
  * removed with their code: the fused-GroupNorm conv epilogue and the pipelined integrator chunks (DESIGN_APPENDIX.md 4.3, 4.5). */
 int dtts_set_option(dtts_handle* h, const char* key, int value);
-/* Reads back "conv_x3" (1 only if DTTS_CONV_X3 does not disable it) or "trunk_fp16": what a caller needs to restore after a per-call override. */
+/* Reads back "conv_x3" (1 only if DTTS_CONV_X3 does not disable it), "trunk_fp16" or "gpt_fuse_proj": what a caller needs to restore after a per-call override. */
 int dtts_get_option(dtts_handle* h, const char* key, int* value);
 
 /* ---- measurement ---------------------------------------------------------------------------------------------- */
@@ -880,6 +885,47 @@ int dtts_op_attn_probs(dtts_handle* h, const float* qkv, const int* lens, int B,
  * stay on a column or jump ahead; it need not reach the last column. */
 int dtts_op_monotone_path(dtts_handle* h, const float* score, const int* n, const int* m, int B, int n_max, int m_max, int* path,
                           void* stream);
+/* ---- the GPT decode chain's kernels (csrc/gpt_kernels.hip), ONE launch each on the caller's DEVICE buffers; a handle without weights
+ * serves them.  Whatever the launcher or the kernel cannot take is refused before a launch.
+ * dtts_op_gemv_block: part[slice][b][col] = sum_{k in slice} v(b, k) W[k][col] over W [K][CoutP] (K % 128 == 0, CoutP % 4 == 0, B <= 16),
+ * v by prologue `pro`:
+ *   0 plain    v = x[b][k]                                            (x [B][x_stride >= K])
+ *   1 residual v = x + in_bias + sum of the in_slices partials parts [in_slices][B][in_stride >= K]; y_out [B][K] = v, stats_out
+ *              [slices][B][2] = (sum v, sum v^2) over the slice's K range; the GEMV input is gamma[k] v.  in_slices 0: x + in_bias
+ *   2 LN       v = act(r_b (sum of partials - mu_b fold_c[k]) + fold_d[k]), (mu_b, r_b) from stats_in [stats_slices][B][2] over K_ln values;
+ *              in_act 0 or 4 (gelu_new)
+ *   3 attn     v = the merged key-split records parts [B][K / in_stride][in_slices][64] of dtts_op_decode_attention, head dim in_stride
+ * Pointers the prologue does not read may be null.  info (may be null): the slice count and the instantiation the launcher chose. */
+typedef struct dtts_gemv_info {
+    int slices;      /* split-K slices written: part is [slices][B][CoutP] */
+    int vec;         /* columns per lane: 4 (256-column workgroups) or 1 (64-column) */
+    int rpw;         /* weight rows per wave: 16 (128 input rows per workgroup) or 8 (64) */
+    int nb;          /* batch rows of the instantiation: 8 or 16 */
+} dtts_gemv_info;
+int dtts_op_gemv_block(dtts_handle* h, int pro, const float* W, int K, int CoutP, int B, const float* x, int x_stride, const float* parts,
+                       int in_slices, int in_stride, int in_act, const float* in_bias, const float* gamma, float* y_out, float* stats_out,
+                       const float* stats_in, int stats_slices, int K_ln, const float* fold_c, const float* fold_d, float* part,
+                       dtts_gemv_info* info, void* stream);
+/* The decode attention of one token: q / k / v of head h = r_b (sum of the `slices` partials part [slices][B][CoutP] - mu_b fold_c) + fold_d
+ * at columns {0, C, 2 C} + 48 h (C = 48 H; statistics stats [stats_slices][B][2] over C values), k / v appended to cache [B][cache_bs]
+ * (K [C][cap] then V [cap][C]) at column pos = lp[b] + step[b] - 1, softmax(q . k / sqrt(48)) v over columns 0 .. pos.  lp, step HOST [B],
+ * 1 <= lp + step <= cap.  wproj null: out [B][H][KS][64] records (max, denominator, 48 unnormalised sums) of KS = ksplit key ranges
+ * (ksplit 0 = the process default DTTS_GPT_KSPLIT, 1 .. 8).  wproj DEVICE [C][768] (H D <= 768): out [H][B][768] per-head partials of
+ * the projection, ksplit 0.  D == 48 only. */
+int dtts_op_decode_attention(dtts_handle* h, const float* part, int slices, int CoutP, const float* stats, int stats_slices,
+                             const float* fold_c, const float* fold_d, float* cache, long long cache_bs, int cap, const int* lp,
+                             const int* step, int B, int H, int D, int ksplit, const float* wproj, int wpCoutP, float* out, void* stream);
+/* y [B][C] = LN(LN(res + bias + sum of in_slices partials parts [in_slices][B][in_stride]; g1, b1); g2, b2), C <= 1024, and when latents
+ * DEVICE [B][C][lat_cs] is given and step[b] < max_steps also latents[b][:, step[b]].  step HOST [B]; bias, parts, latents may be null. */
+int dtts_op_gpt_final_ln(dtts_handle* h, const float* res, const float* bias, const float* parts, int in_slices, int in_stride, int B,
+                         const float* g1, const float* b1, const float* g2, const float* b2, float* y, int C, const int* step,
+                         int max_steps, float* latents, int lat_cs, void* stream);
+/* c[n] = sum_k gamma[k] W[k][n], d[n] = sum_k beta[k] W[k][n] + bias[n] over W [K][CoutP] (bias may be null) */
+int dtts_op_ln_fold_vectors(dtts_handle* h, const float* W, int K, int CoutP, const float* gamma, const float* beta, const float* bias,
+                            float* c, float* d, void* stream);
+/* rows [C, 3 C) of qkv [B][3 C][L], columns < lens[b] (HOST, in [0, min(L, cap)]) -> cache [B][cache_bs >= 2 C cap]: K [C][cap], V [cap][C] */
+int dtts_op_kv_to_cache(dtts_handle* h, const float* qkv, const int* lens, int B, int C, int L, float* cache, long long cache_bs, int cap,
+                        void* stream);
 /* The device sampler on given logits rows: HF RepetitionPenalty / Temperature / TopK / TopP processors as the reference's
  * generate() applies them (vqvae/model_24k.py:786-792) + the inverse-CDF draw on uniforms[r].  logits DEVICE [R][V] (R <= 16),
  * history HOST [R][hist_len] ids present in the row's input_ids, uniforms DEVICE [R] -> tokens HOST [R].  Synchronises. */
