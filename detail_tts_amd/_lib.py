@@ -139,6 +139,12 @@ SIGNATURES = {
                                    C.c_void_p, C.c_void_p]),
     "dtts_diff_sample_from": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, c_int_p, C.c_int, C.c_int,
                                         C.c_ulonglong, c_int_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "dtts_diff_inpaint": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, c_int_p, C.c_int, C.c_int,
+                                    C.c_ulonglong, c_int_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dtts_op_inpaint_blend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, c_float_p,
+                                        C.c_int, C.c_int, C.c_ulonglong, c_int_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dtts_inpaint_table": (C.c_int, [c_int_p, C.c_int, C.c_int, c_float_p, C.c_int, c_int_p]),
     "dtts_diff_reverse_step": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          C.c_void_p]),
     "dtts_diff_mean_variance": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_void_p,

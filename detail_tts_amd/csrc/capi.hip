@@ -629,6 +629,47 @@ int dtts_diff_sample_from(dtts_handle* h, int id, int sampler, float eta, int fi
     DTTS_API_END(h)
 }
 
+int dtts_diff_inpaint(dtts_handle* h, int id, int sampler, float eta, int first_step, int resample, const float* code_emb, const int* lens,
+                      int B, int T, unsigned long long seed, const int* sample_ids, const float* x_init, const float* known,
+                      const unsigned char* keep, const float* step_noise, const float* known_noise, const float* renoise, float* x_out,
+                      float* x_traj, void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_inpaint(id, sampler, eta, first_step, resample, code_emb, lens, B, T, seed, sample_ids, x_init, known, keep, step_noise,
+                       known_noise, renoise, x_out, x_traj, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_op_inpaint_blend(dtts_handle* h, float* x, const float* known, const unsigned char* keep, const int* lens, int B, int C, int T,
+                          const float* coefs, int step0, int renoise, unsigned long long seed, const int* sample_ids, int philox_step,
+                          const float* known_noise, const float* renoise_noise, void* stream) {
+    DTTS_API_BEGIN
+    DTTS_REQUIRE(coefs, "coefs");
+    const dtts::InpaintCoefs k = {coefs[0], coefs[1], coefs[2], coefs[3]};
+    h->m->op_inpaint_blend(x, known, keep, lens, B, C, T, k, step0, renoise, seed, sample_ids, philox_step, known_noise, renoise_noise,
+                           (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_inpaint_table(const int* timesteps, int n, int trained_steps, float* coefs, int cap, int* n_out) {
+    DTTS_API_BEGIN
+    DTTS_REQUIRE(timesteps && n >= 1 && trained_steps >= 1, "timesteps, n >= 1, trained_steps >= 1");
+    std::vector<int> tmap(timesteps, timesteps + n);
+    for (int t : tmap) DTTS_REQUIRE(t >= 0 && t < trained_steps, "timestep out of [0, trained_steps)");
+    std::sort(tmap.begin(), tmap.end());
+    tmap.erase(std::unique(tmap.begin(), tmap.end()), tmap.end());
+    dtts::ScheduleTables sc;
+    dtts::make_schedule(trained_steps, tmap, 0.f, sc);
+    if (n_out) *n_out = sc.n;
+    DTTS_REQUIRE(!coefs || cap >= sc.n, "cap < n");
+    if (coefs)
+        for (int i = 0; i < sc.n; ++i) {
+            const dtts::InpaintCoefs k = sc.inpaint(i);
+            const float v[4] = {k.known_a, k.known_b, k.renoise_a, k.renoise_b};
+            std::memcpy(coefs + (size_t)4 * i, v, sizeof(v));
+        }
+    DTTS_API_END(nullptr)
+}
+
 int dtts_diff_reverse_step(dtts_handle* h, int id, float* x, const float* code_emb, const int* lens, int B, int T, int step, float* x0_out,
                            void* stream) {
     DTTS_API_BEGIN

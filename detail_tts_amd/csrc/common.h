@@ -58,7 +58,9 @@ static inline int env_tri(const char* name) {          // -1 = not set (the call
 enum NoiseStage : int { STAGE_GPT_SAMPLE = 1, STAGE_DIFF_INIT = 2, STAGE_DIFF_STEP = 3, STAGE_FLOW_PRIOR = 4,
                         STAGE_DIFF_QSAMPLE = 5,     // 5: the forward process' noise (q_sample of the evaluation loss, diff_loss.h), step 0
                         STAGE_POSTERIOR = 6,        // 6: enc_q's posterior sample (forward_flowvae, flowvae_fwd.h), step 0
-                        STAGE_DIFF_BPD = 7 };       // 7: the forward process' noise of calc_bpd_loop (diff_bpd.h), step = timestep t
+                        STAGE_DIFF_BPD = 7,         // 7: the forward process' noise of calc_bpd_loop (diff_bpd.h), step = timestep t
+                        STAGE_DIFF_KNOWN = 8,       // 8: inpainting, the noise of the known frames (diff_inpaint.h), step = i + r * N
+                        STAGE_DIFF_RENOISE = 9 };   // 9: inpainting, the forward step of a repeat, step = i + r * N
 
 // activation ids shared by prologues / epilogues
 enum Act : int {

@@ -2,6 +2,7 @@
 #pragma once
 #include <vector>
 
+#include "diff_inpaint.h"
 #include "ops.h"
 
 namespace dtts {
@@ -21,10 +22,12 @@ struct ScheduleTables {
     std::vector<float> sqrt_ac, sqrt_1m_ac;   // kind 0: fp32 sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod (q_sample, :243-260)
     std::vector<float> log_1m_ac;         // kind 0: fp32 log_one_minus_alphas_cumprod (q_mean_variance, :230-241: _prior_bpd)
     std::vector<DpmStepCoefs> dpm;        // kind 1: the update of column i
+    std::vector<double> ac64;             // kind 0: float64 alphas_cumprod (inpaint: every scalar is rounded once, from these)
     float cfk_k = 0.f;
     int n = 0;
     DdimStepCoefs ddim(int i, float eta) const;
     DdimReverseCoefs ddim_reverse(int i) const;
+    InpaintCoefs inpaint(int i) const;
     bool same_key(const ScheduleTables& o) const { return kind == o.kind && tmap == o.tmap && ftimes == o.ftimes; }
 };
 

@@ -56,6 +56,7 @@ void make_schedule(int trained, const std::vector<int>& tmap, float cfk_k, Sched
     sc.sqrt_ac.resize(n);
     sc.sqrt_1m_ac.resize(n);
     sc.log_1m_ac.resize(n);
+    sc.ac64 = acp;
     for (int i = 0; i < n; ++i) {
         DiffStepCoefs k;
         k.sqrt_recip_ac = (float)std::sqrt(1.0 / acp[i]);
@@ -101,6 +102,18 @@ DdimReverseCoefs ScheduleTables::ddim_reverse(int i) const {
     const float an = ac_next[i];
     k.sqrt_ac_next = std::sqrt(an);
     k.sqrt_1m_ac_next = std::sqrt(1.f - an);
+    return k;
+}
+
+// The inpainting step's scalars (diff_inpaint.h): the known frames at level i - 1 are q_sample at alphas_cumprod_prev[i], and a repeat
+// goes back up by one forward step of beta_i = 1 - ac[i] / acp[i].  Double throughout, one rounding to fp32 each.
+InpaintCoefs ScheduleTables::inpaint(int i) const {
+    const double a = ac64[i], ap = i > 0 ? ac64[i - 1] : 1.0;
+    InpaintCoefs k;
+    k.known_a = (float)std::sqrt(ap);
+    k.known_b = (float)std::sqrt(1.0 - ap);
+    k.renoise_a = (float)std::sqrt(a / ap);
+    k.renoise_b = (float)std::sqrt(1.0 - a / ap);
     return k;
 }
 

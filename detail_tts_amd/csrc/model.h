@@ -241,6 +241,19 @@ public:
     void diff_sample_from(int sched_id, int sampler, float eta, int first_step, const float* code_emb, const int* lens_host, int B, int T,
                           unsigned long long seed, const int* sample_ids_host, const float* x_init, const float* step_noise, float* mel_out,
                           int denorm, hipStream_t s);
+    // diff_sample_from with inpainting (RePaint): after every sampler update the frames with keep[b][t] != 0 are overwritten with
+    // `known` noised to the level just reached, and every step above 0 is evaluated `resample` times with one forward step in between
+    // (diff_inpaint.h).  x_init NULL: first_step = n - 1 and x_T is diff_sample_ex's draw.  x_out: the normalised x_0.  The three
+    // optional noise arrays are [first_step * resample + 1][B,128,T] in evaluation order; x_traj (optional), the same shape: x after
+    // every evaluation's blend.
+    void diff_inpaint(int sched_id, int sampler, float eta, int first_step, int resample, const float* code_emb, const int* lens_host,
+                      int B, int T, unsigned long long seed, const int* sample_ids_host, const float* x_init, const float* known,
+                      const unsigned char* keep, const float* step_noise, const float* known_noise, const float* renoise, float* x_out,
+                      float* x_traj, hipStream_t s);
+    // one launch of the inpainting blend on caller-supplied x (= u, in place) [B,C,T] (unit entry of the kernel's tests)
+    void op_inpaint_blend(float* x, const float* known, const unsigned char* keep, const int* lens_host, int B, int C, int T,
+                          InpaintCoefs k, int step0, int renoise, unsigned long long seed, const int* sample_ids_host, int pstep,
+                          const float* known_noise, const float* renoise_noise, hipStream_t s);
     // one ddim_reverse_sample at spaced step `step`, x in place (diff_invert's step: the same bits)
     void diff_reverse_step(int sched_id, float* x, const float* code_emb, const int* lens_host, int B, int T, int step, float* x0_out,
                            hipStream_t s);

@@ -1056,6 +1056,97 @@ void Model::diff_sample_from(int sched_id, int sampler, float eta, int first_ste
     if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
 }
 
+// ---- mel inpainting (RePaint, Lugmayr et al. 2022): diff_sample_from with the kept frames overwritten after every update
+// Step i, repeat r of U: the unchanged sampler update takes x from level i to i - 1, the blend (diff_inpaint.h) overwrites the kept
+// frames with `known` at level i - 1 and, for r < U - 1, takes x one forward step back up to level i.  Step 0 runs once.  All three
+// noise streams carry the Philox step field i + r * N: the update kernels' `step` argument feeds only the key, so repeat 0 of
+// STAGE_DIFF_STEP is the plain loop's key and a call with nothing kept and U = 1 is diff_sample_from bit for bit.  The code-path
+// table is the whole loop's (as in diff_sample_from) and is read again by every repeat of a step.
+void Model::diff_inpaint(int sched_id, int sampler, float eta, int first_step, int resample, const float* code_emb, const int* lens_host,
+                         int B, int T, unsigned long long seed, const int* sample_ids_host, const float* x_init, const float* known,
+                         const unsigned char* keep, const float* step_noise, const float* known_noise, const float* renoise, float* x_out,
+                         float* x_traj, hipStream_t s) {
+    DTTS_REQUIRE(bound_, "weights not bound");
+    DTTS_REQUIRE(sampler == 0 || sampler == 1, "diff_inpaint: sampler 0 (p) or 1 (ddim); a multistep solver's history does not survive the overwrite");
+    DTTS_REQUIRE(eta >= 0.f, "eta must be >= 0");
+    DTTS_REQUIRE(resample >= 1 && resample <= 32, "diff_inpaint: resample out of [1, 32]");
+    DTTS_REQUIRE(known && keep, "diff_inpaint: known and keep");
+    DTTS_REQUIRE(code_emb && x_out && sample_ids_host && B >= 1 && T >= 1, "diff_inpaint: code_emb, x_out, sample_ids");
+    Schedule& sc = schedule(sched_id);
+    DTTS_REQUIRE(sc.kind == 0, "diff_inpaint runs on an integer-timestep schedule (dtts_diff_schedule)");
+    DTTS_REQUIRE(first_step >= 0 && first_step < sc.n, "diff_inpaint: first_step out of [0, steps of the schedule)");
+    DTTS_REQUIRE(x_init || first_step == sc.n - 1, "diff_inpaint: x_init is required below the top of the schedule");
+    check_lens(lens_host, B, T);
+    const int C = cfg.diff_channels, OC = cfg.diff_out_channels, MC = cfg.mel_channels;
+    const bool table = integ_table_fits(sc.n, B, C, T);                  // the whole loop's decision
+    const PairCall pc = begin_pair(code_emb, lens_host, sample_ids_host, B, T, s, table ? integ_call_bytes(sc.n, B, C, T) : 0);
+    const PairPlan& pl = pc.pl;
+    float* x = x_out;
+    const long long xbs = (long long)MC * T;
+    const size_t plane = (size_t)B * MC * T;
+    if (x_init) {
+        if (x != x_init) DTTS_CHECK_HIP(hipMemcpyAsync(x, x_init, sizeof(float) * plane, hipMemcpyDeviceToDevice, s));
+    } else {                                                             // x_T as diff_sample_ex draws it
+        DTTS_CHECK_HIP(hipMemsetAsync(x, 0, sizeof(float) * plane, s));
+        for (int b = 0; b < B; ++b) {
+            const int len = lens_host ? lens_host[b] : T;
+            if (len == T) {
+                launch_philox_normal(x + (size_t)b * xbs, xbs, MC * T, 1, seed, pc.sids + b, STAGE_DIFF_INIT, 0, 1.f, s);
+            } else {
+                float* tmp = pc.out2;                                    // free until the first forward
+                launch_philox_normal(tmp, 0, MC * len, 1, seed, pc.sids + b, STAGE_DIFF_INIT, 0, 1.f, s);
+                DTTS_CHECK_HIP(hipMemcpy2DAsync(x + (size_t)b * xbs, sizeof(float) * T, tmp, sizeof(float) * len, sizeof(float) * len, MC,
+                                                hipMemcpyDeviceToDevice, s));
+            }
+        }
+    }
+    const int Bi = B + pl.Nu, k_first = sc.n - 1 - first_step;           // loop position of first_step
+    float* integ_all = nullptr;
+    int k_table = k_first;
+    if (table) {
+        k_table = k_first / integ_chunk(Bi) * integ_chunk(Bi);           // the whole loop's launch that holds first_step starts here
+        std::vector<int> steps(sc.n - k_table), li(Bi);
+        for (int k = k_table; k < sc.n; ++k) steps[k - k_table] = sc.n - 1 - k;
+        for (int b = 0; b < B; ++b) li[b] = lens_host ? lens_host[b] : T;
+        for (int u = 0; u < pl.Nu; ++u) li[B + u] = pl.ulen[u];
+        integ_all = ws().f32(steps.size() * (size_t)Bi * C * T);
+        precompute_integrator(sc, pc.cbuf0, pl.lens_i, li.data(), B, pl.Nu, T, steps, integ_all, s);
+    }
+    const size_t mark = ws().mark();
+    size_t e = 0;                                                        // evaluation index: the override arrays' leading axis
+    for (int k = k_first; k < sc.n; ++k) {
+        const int i = sc.n - 1 - k;
+        const InpaintCoefs kc = sc.inpaint(i);
+        const int reps = i == 0 ? 1 : resample;
+        for (int r = 0; r < reps; ++r, ++e) {
+            Profiler::gate() = (e % Profiler::get().step_every) == 0;
+            ws().rewind(mark);
+            diff_forward_pair(sc, x, pc.cbuf0, pl, B, T, i, pc.out2, s, integ_all ? integ_all + (size_t)(k - k_table) * Bi * C * T : nullptr);
+            const int pstep = i + r * sc.n;
+            const float* nz = step_noise ? step_noise + e * plane : nullptr;
+            if (sampler == 1)
+                launch_ddim_update(x, xbs, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.ddim(i, eta), seed, pc.sids, pstep, nz, 0, s);
+            else
+                launch_diff_update(x, xbs, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.p[i], seed, pc.sids, pstep, nz, 0, s);
+            launch_inpaint_blend(x, known, keep, pl.lens2, T, B, MC, kc, i == 0 ? 1 : 0, r < reps - 1 ? 1 : 0, seed, pc.sids, pstep,
+                                 known_noise ? known_noise + e * plane : nullptr, renoise ? renoise + e * plane : nullptr, s);
+            if (x_traj) DTTS_CHECK_HIP(hipMemcpyAsync(x_traj + e * plane, x, sizeof(float) * plane, hipMemcpyDeviceToDevice, s));
+        }
+    }
+    Profiler::gate() = true;
+    if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
+}
+
+void Model::op_inpaint_blend(float* x, const float* known, const unsigned char* keep, const int* lens_host, int B, int C, int T,
+                             InpaintCoefs k, int step0, int renoise, unsigned long long seed, const int* sample_ids_host, int pstep,
+                             const float* known_noise, const float* renoise_noise, hipStream_t s) {
+    DTTS_REQUIRE(x && known && keep && B >= 1 && C >= 1 && T >= 1, "op_inpaint_blend: x, known, keep");
+    check_lens(lens_host, B, T);
+    const int* dl = lens_host ? upload_ints(lens_host, B, s) : nullptr;
+    const int* sids = sample_ids_host ? upload_ints(sample_ids_host, B, s) : nullptr;
+    launch_inpaint_blend(x, known, keep, dl, T, B, C, k, step0, renoise, seed, sids, pstep, known_noise, renoise_noise, s);
+}
+
 // one DPM-Solver++(2M) step (vqvae/utils/dpm_solver.py:1176-1208 per step) of DPM schedule `sched_id` at step index `step`, x in place
 void Model::diff_step_dpm(int sched_id, float* x, float* x0_hist, const float* code_emb, const int* lens_host, int B, int T, int step,
                           float* x0_out, hipStream_t s) {

@@ -26,6 +26,7 @@ from ..pipeline import drain_session, group_requests, normalize_request, split_l
 from ..runtime import Runtime
 from ..voice import check_clips, check_speaker, make_voice, model_dims
 from .diff_model import DiffusionTts
+from .inpaint import check_inpaint_args, splice_codes  # noqa: F401  (splice_codes: the host helper beside inpaint_mel)
 from .utils.diffusion import SAMPLERS, SpacedDiffusion, check_timesteps, get_named_beta_schedule, space_timesteps
 
 
@@ -863,6 +864,60 @@ class SynthesizerTrn:
             return mel
         B, T = mel.shape[0], mel.shape[-1]
         return self.infer_flowvae(mel, [T] * B, None, noise_scale, batch=True, seed=seed, sample_ids=sample_ids), mel
+
+    def inpaint_mel(self, mel, mel_lengths, text, text_length, refer=None, refer_lengths=None, *, spans=None, keep=None, codes=None,
+                    diffusion_steps=None, sampler="ddim", eta=0.0, resample=1, t_start=None, seed=0, sample_ids=None, vocode=True,
+                    noise_scale=NOISE_SCALE, speaker=None):
+        """Render a stretch of an existing utterance again and leave the rest untouched (RePaint, Lugmayr et al. 2022, on the diffusion
+        decoder).  mel: a raw log-mel [B,128,T], T % 4 == 0.  Exactly one of
+          spans  per row a list of inclusive code spans (first, last) - what align / return_alignment hand out under "spans",
+                 "token_spans" and each word's "span" (None entries are skipped); frames 4 first .. 4 last + 3 are regenerated
+          keep   a bool frame mask [B,T] (or [T] for all rows), False where the mel is to be regenerated.
+        codes [B, T/4]: what the result is to speak (None: encode(mel), the same content in a fresh rendering; another length:
+        splice_codes).  The code embedding is _code_embedding(codes, text, ...) over the WHOLE sequence, known =
+        normalize_torch_mel(mel), and the sampling loop of `diffusion_steps` (sampler "ddim" with eta, or "p") runs with known= / keep=
+        / resample= (SpacedDiffusion.p_sample_loop): after every step the kept frames are overwritten with the known mel noised to
+        that level, so the new frames are generated in the context of the old ones at every noise level; resample = U in [1, 32]
+        repeats every step U times so that the seam harmonises (U times the cost).  t_start = s starts from q_sample(known, s) (Philox
+        stage 5, keyed by seed / sample_ids) in the place of pure noise and keeps the span's coarse shape.
+        -> mel' [B,128,T] (vocode=False) or (wav, mel') through infer_flowvae, as resynthesize.  The kept frames of mel' are the
+        caller's mel BITS (torch.where on the caller's tensor, no normalise / de-normalise round trip); the values of mel inside the
+        regenerated frames are read only by encode (codes=None) and by q_sample (t_start).
+
+        ValueError before any launch: T % 4 != 0; both or neither of spans / keep; a mask of another shape or dtype; a span outside
+        [0, T/4), reversed or overlapping; every frame kept (nothing to do); resample not an int in [1, 32]; sampler "dpmsolver++" (a
+        multistep history does not survive the overwrite); eta < 0; codes of another length; t_start outside the schedule.  Nothing
+        kept with t_start=None is allowed: it is the plain sampling loop under these codes.  speaker: a Voice in the place of (refer,
+        refer_lengths).  Audio and seam quality under a trained checkpoint are unmeasured."""
+        shape = tuple(torch.as_tensor(mel).shape)
+        key, _, eta = sampling_args(diffusion_steps, sampler, eta)
+        kmask = check_inpaint_args(shape, spans, keep, codes, resample, sampler, eta, t_start, len(key) if isinstance(key, list) else key)
+        check_speaker(speaker, refer, refer_lengths, shape[0], None if speaker is None else model_dims(self.cfg))
+        mel = torch.as_tensor(mel).to(self.device, torch.float32).contiguous()
+        B, _, T = shape
+        if codes is None:
+            codes, _ = self.encode(mel, mel_lengths)
+        else:
+            codes = torch.as_tensor(codes).to(self.device).long()
+        emb = self._code_embedding(codes, text, text_length, refer, refer_lengths, speaker)
+        d = SpacedDiffusion(key, betas=get_named_beta_schedule("linear", TRAINED_DIFFUSION_STEPS), conditioning_free=True,
+                            conditioning_free_k=COND_FREE_K, sampler=sampler)
+        d.rt = self.rt
+        known = normalize_torch_mel(mel).contiguous()
+        ids = list(range(B)) if sample_ids is None else list(sample_ids)
+        noise = None
+        if t_start is not None:
+            noise = d.q_sample(known, [int(t_start)] * B, seed=seed, sample_ids=ids)[0]
+        kdev = kmask.to(self.device)
+        args = dict(noise=noise, model_kwargs={"precomputed_aligned_embeddings": emb}, seed=seed, sample_ids=ids, t_start=t_start,
+                    known=known, keep=kdev, resample=int(resample))
+        if sampler == "ddim":
+            args["eta"] = eta
+        norm = (d.ddim_sample_loop if sampler == "ddim" else d.p_sample_loop)(self.diffusion, (B, 128, T), **args)
+        out = torch.where(kdev[:, None, :], mel, denormalize_torch_mel(norm))
+        if not vocode:
+            return out
+        return self.infer_flowvae(out, [T] * B, None, noise_scale, batch=True, seed=seed, sample_ids=sample_ids), out
 
     def forward_vq(self, y, y_lengths, data=None):
         """vqvae/model_24k.py:654-666, the VQ stage's validation loss -> a 0-d fp32 CUDA tensor: L1(vq_dec(quantizer(vq_enc(y)) +

@@ -51,6 +51,19 @@ def check_timesteps(t, batch, num_timesteps):
     return [int(v) for v in a]
 
 
+def check_keep(keep, B, T):
+    """a frame mask of an inpainting call: bool [B,T], or [T] for all rows -> bool [B,T] (ValueError otherwise; host only)"""
+    import torch
+    k = torch.as_tensor(keep)
+    if k.dtype != torch.bool:
+        raise ValueError(f"keep must be a bool mask, not {k.dtype}")
+    if k.dim() == 1 and k.shape[0] == T:
+        k = k.unsqueeze(0).expand(B, T)
+    if tuple(k.shape) != (B, T):
+        raise ValueError(f"keep must be [{B}, {T}] or [{T}], not {tuple(k.shape)}")
+    return k.contiguous()
+
+
 def get_named_beta_schedule(name, n):
     if name != "linear":
         raise NotImplementedError(name)
@@ -370,32 +383,97 @@ class SpacedDiffusion:
         return rt.diff_sample_ex(emb, seed, sample_ids, sched=sched, sampler=SAMPLERS[sampler], eta=eta, lens=lens, x_init=noise,
                                  denorm=denorm)
 
+    def _inpaint_args(self, known, keep, resample, shape):
+        """known= / keep= / resample= of the sampling loops, checked on the host -> None (none given: today's path) or
+        (known, keep [B,T] bool, U).  ValueError: one of known / keep without the other, resample without them, a mask of another
+        shape or dtype, resample not an int in [1, 32]."""
+        if known is None and keep is None:
+            if resample != 1:
+                raise ValueError("resample repeats the steps of an inpainting call: it needs known= and keep=")
+            return None
+        if self.sampler == "dpmsolver++":
+            raise ValueError("inpainting is not available on a dpmsolver++ diffuser (a multistep history does not survive the overwrite)")
+        if known is None or keep is None:
+            raise ValueError("inpainting needs both known= (the normalised mel) and keep= (the frame mask), or neither")
+        if isinstance(resample, bool) or not isinstance(resample, (int, np.integer)) or not 1 <= resample <= 32:
+            raise ValueError(f"resample must be an integer in [1, 32], not {resample!r}")
+        B, _, T = shape
+        if tuple(known.shape) != tuple(shape):
+            raise ValueError(f"known must be {tuple(shape)}, not {tuple(known.shape)}")
+        return known, check_keep(keep, B, T), int(resample)
+
+    def _inpaint_loop(self, sampler, model, shape, noise, model_kwargs, seed, sample_ids, lens, eta, t_start, inp, step_noise=None,
+                      known_noise=None, renoise=None, return_trajectory=False):
+        """a sampling loop with the kept frames overwritten after every step (dtts_diff_inpaint); `noise` is x_T, or x at t_start"""
+        self._check(sampler)
+        if sampler == "dpmsolver++":
+            raise ValueError("inpainting is not available with dpmsolver++ (a multistep history does not survive the overwrite)")
+        if eta < 0:
+            raise ValueError("eta must be >= 0")
+        if t_start is not None:
+            if isinstance(t_start, bool) or not isinstance(t_start, (int, np.integer)) or not 0 <= t_start < self.num_timesteps:
+                raise ValueError(f"t_start must be an integer in [0, {self.num_timesteps}), not {t_start!r}")
+            if noise is None:
+                raise ValueError("t_start needs `noise`: x at the level of step t_start")
+        emb = (model_kwargs or {}).get("precomputed_aligned_embeddings")
+        if emb is None:
+            raise ValueError("precomputed_aligned_embeddings is required (as in do_spectrogram_diffusion)")
+        known, keep, U = inp
+        sample_ids = list(range(shape[0])) if sample_ids is None else sample_ids
+        rt = model.rt
+        return rt.diff_inpaint(known.float().contiguous(), keep, emb, seed, sample_ids, sched=rt.diff_schedule(self.timestep_map),
+                               sampler=SAMPLERS[sampler], eta=eta, resample=U, first_step=None if t_start is None else int(t_start),
+                               x_init=None if noise is None else noise.float().contiguous(), lens=lens, step_noise=step_noise,
+                               known_noise=known_noise, renoise=renoise, return_trajectory=return_trajectory)
+
     def p_sample_loop(self, model, shape, noise=None, model_kwargs=None, progress=False, seed=0, sample_ids=None, lens=None, t_start=None,
+                      known=None, keep=None, resample=1, step_noise=None, known_noise=None, renoise=None, return_trajectory=False,
                       **_):
         """model: a detail_tts_amd DiffusionTts; returns x_0 (normalised mel) [B,128,T] of THIS diffuser's schedule.  t_start = s: `noise`
         (required then) is x at the level of step s and steps s .. 0 run, with the Philox noise the whole loop draws at those steps;
-        t_start = num_timesteps - 1 is the whole loop from x_T = noise.  None: the whole loop."""
+        t_start = num_timesteps - 1 is the whole loop from x_T = noise.  None: the whole loop.
+
+        Inpainting (RePaint): known [B,128,T] (a normalised mel) and keep (bool [B,T], or [T] for all rows) - both or neither - hold
+        the frames with keep set to `known`: after every step they are overwritten with known noised to the level just reached, so the
+        other frames are generated in their context at every noise level; resample = U runs every step above 0 U times with one
+        forward step in between.  The kept frames of the result are known's bits (a select); known is never read elsewhere.  Nothing
+        kept with U = 1 is the plain loop bit for bit.  step_noise / known_noise / renoise [t * U + 1, B,128,T] (t = t_start or
+        num_timesteps - 1) replace the three Philox streams, and return_trajectory=True returns (x_0, x after every evaluation, the
+        same leading axis) - both for parity tests, and only on the inpainting path."""
+        inp = self._inpaint_args(known, keep, resample, shape)
+        if inp is not None:
+            return self._inpaint_loop("p", model, shape, noise, model_kwargs, seed, sample_ids, lens, 0.0, t_start, inp, step_noise,
+                                      known_noise, renoise, return_trajectory)
         if t_start is not None:
             return self._loop_from("p", model, shape, noise, model_kwargs, seed, sample_ids, lens, 0.0, t_start)
         return self._loop("p", model, shape, noise, model_kwargs, seed, sample_ids, lens, 0.0)
 
     def ddim_sample_loop(self, model, shape, noise=None, model_kwargs=None, progress=False, eta=0.0, seed=0, sample_ids=None, lens=None,
-                         t_start=None, **_):
+                         t_start=None, known=None, keep=None, resample=1, step_noise=None, known_noise=None, renoise=None,
+                         return_trajectory=False, **_):
         """vqvae/utils/diffusion.py:819-851 (ddim_sample :744-783 per step, Philox noise when eta > 0).  t_start = s: `noise` (required
         then) is x at the level of step s and steps s .. 0 run - what ddim_reverse_sample_loop(depth=s) yields, for s <= num_timesteps
-        - 1; an inversion to depth num_timesteps is pure eps' and feeds the whole loop (t_start None) as `noise`."""
+        - 1; an inversion to depth num_timesteps is pure eps' and feeds the whole loop (t_start None) as `noise`.
+        known / keep / resample: inpainting, as in p_sample_loop."""
+        inp = self._inpaint_args(known, keep, resample, shape)
+        if inp is not None:
+            return self._inpaint_loop("ddim", model, shape, noise, model_kwargs, seed, sample_ids, lens, float(eta), t_start, inp,
+                                      step_noise, known_noise, renoise, return_trajectory)
         if t_start is not None:
             return self._loop_from("ddim", model, shape, noise, model_kwargs, seed, sample_ids, lens, float(eta), t_start)
         return self._loop("ddim", model, shape, noise, model_kwargs, seed, sample_ids, lens, float(eta))
 
     def k_diffusion_sample_loop(self, k_sampler, pbar, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                                device=None, model_kwargs=None, progress=False, seed=0, sample_ids=None, lens=None, t_start=None, **_):
+                                device=None, model_kwargs=None, progress=False, seed=0, sample_ids=None, lens=None, t_start=None,
+                                known=None, keep=None, resample=1, **_):
         """vqvae/utils/diffusion.py:487-581: DPM-Solver++(2M) over num_timesteps steps (vqvae/utils/dpm_solver.py, time_uniform,
         multistep, order 2) with constant guidance cond_free_k; as in the reference, `k_sampler` is ignored.  x_T = `noise` (None: the
         Philox STAGE_DIFF_INIT draw); no noise after it, no clamp.  `pbar` (may be None) is advanced by the num_timesteps model
         evaluations once the loop is enqueued."""
         if t_start is not None:
             raise ValueError("t_start is not available with dpmsolver++ (a multistep solver has no state below its first step)")
+        if known is not None or keep is not None or resample != 1:
+            raise ValueError("inpainting is not available with dpmsolver++ (a multistep history does not survive the overwrite)")
         if not isinstance(model_kwargs, dict):
             raise ValueError("model_kwargs must be a dict (the reference asserts it)")
         x = self._loop("dpmsolver++", model, shape, noise, model_kwargs, seed, sample_ids, lens, 0.0)
@@ -407,6 +485,8 @@ class SpacedDiffusion:
         """vqvae/utils/diffusion.py:640-652: dispatch on self.sampler ("dpmsolver++": k_diffusion_sample_loop)"""
         self._check(self.sampler)
         if self.sampler == "dpmsolver++":
+            if kwargs.get("known") is not None or kwargs.get("keep") is not None or kwargs.get("resample", 1) != 1:
+                raise ValueError("inpainting is not available with dpmsolver++ (a multistep history does not survive the overwrite)")
             return self.k_diffusion_sample_loop(None, None, *args, **kwargs)
         if self.sampler == "ddim":
             return self.ddim_sample_loop(*args, **kwargs)
