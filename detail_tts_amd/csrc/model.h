@@ -237,13 +237,13 @@ public:
     void diff_invert(int sched_id, const float* code_emb, const int* lens_host, int B, int T, const float* x_start, int depth, float* x_out,
                      float* x_traj, float* x0_traj, hipStream_t s);
     // diff_sample_ex from below the top of the schedule: x_init is x at the level of step `first_step`, steps first_step .. 0 run
-    // (samplers 0 and 1).  The code-path table is evaluated in the launches the whole loop would make, so the result is the whole loop's.
+    // (samplers 0 and 1).  Both are sample_loop, whose code-path table is evaluated in the launches the whole loop makes.
     void diff_sample_from(int sched_id, int sampler, float eta, int first_step, const float* code_emb, const int* lens_host, int B, int T,
                           unsigned long long seed, const int* sample_ids_host, const float* x_init, const float* step_noise, float* mel_out,
                           int denorm, hipStream_t s);
     // diff_sample_from with inpainting (RePaint): after every sampler update the frames with keep[b][t] != 0 are overwritten with
     // `known` noised to the level just reached, and every step above 0 is evaluated `resample` times with one forward step in between
-    // (diff_inpaint.h).  x_init NULL: first_step = n - 1 and x_T is diff_sample_ex's draw.  x_out: the normalised x_0.  The three
+    // (diff_inpaint.h).  x_init NULL: first_step = n - 1 and x_T is drawn (draw_x_T).  x_out: the normalised x_0.  The three
     // optional noise arrays are [first_step * resample + 1][B,128,T] in evaluation order; x_traj (optional), the same shape: x after
     // every evaluation's blend.
     void diff_inpaint(int sched_id, int sampler, float eta, int first_step, int resample, const float* code_emb, const int* lens_host,
@@ -615,7 +615,8 @@ private:
     void code_half(const float* in, float* P, const TrunkIo& io);   // P = W_integ2 . in: the code half of integrating_conv
     bool use_x3() const;
     // lens2 [2B]: the stack's lengths; lens_i [B + Nu]: the integrator batch's; umap [2B]: integrator sample of stack sample b; xmap [2B]: b % B
-    struct PairPlan { const int *lens2, *lens_i, *umap, *xmap; int Nu; std::vector<int> ulen; };
+    // lens_i_host: lens_i on the host (the B row lengths, then the Nu distinct ones)
+    struct PairPlan { const int *lens2, *lens_i, *umap, *xmap; int Nu; std::vector<int> lens_i_host; };
     PairPlan plan_pair(const int* lens_host, int B, int T, hipStream_t s);
     // cbuf0: [B + Nu, C, T] = B conditional code embeddings followed by Nu unconditional inputs (one per distinct length)
     // integ (optional): [B + Nu, C, T] code-path terms P = W_integ2 . conditioning_timestep_integrator(cbuf0) of this step (precompute_integrator)
@@ -628,10 +629,45 @@ private:
                                const std::vector<int>& steps, float* integ_all, hipStream_t s);
     // what the entry points around one diff_forward_pair share: the workspace sized for the call (+ extra_bytes, + hist_floats), the plan,
     // the sample ids (optional), cbuf0 = (code_emb, or the unconditioned embedding when null | unconditional inputs), out2 [2B, OC, T]
-    // and the DPM-Solver++ history [hist_floats]
+    // and the DPM-Solver++ history [hist_floats].  On top of it the sampling entries share, each written once (model_diffusion.hip):
+    // draw_x_T, code_path_table (the table's launch rule), sampler_update (the ten strided-tensor arguments of every update kernel),
+    // sample_loop (the descending loop of diff_sample_ex / diff_sample_from / diff_inpaint) and single_step (diff_step, diff_step_dpm,
+    // diff_reverse_step, diff_mean_variance); diff_invert keeps its own short ascending loop on the same pieces.
     struct PairCall { PairPlan pl; const int* sids; float *cbuf0, *out2, *hist; };
     PairCall begin_pair(const float* code_emb, const int* lens_host, const int* sample_ids_host, int B, int T, hipStream_t s,
                         size_t extra_bytes = 0, size_t hist_floats = 0);
+    // x_T into x [B,128,T]: Philox normals per row over its own [128, len] (pc.out2 is the compact scratch of a short row)
+    void draw_x_T(float* x, const PairCall& pc, const int* lens_host, int B, int T, unsigned long long seed, hipStream_t s);
+    // precompute_integrator's output for loop positions k0 .. : at(k) = position k's [B + Nu, C, T] terms (null without a table)
+    struct CodePathTable {
+        float* base = nullptr;
+        int k0 = 0;
+        size_t stride = 0;
+        const float* at(int k) const { return base ? base + (size_t)(k - k0) * stride : nullptr; }
+    };
+    CodePathTable code_path_table(const Schedule& sc, const PairCall& pc, int B, int T, int k_first, int k_end, bool descending, bool pinned,
+                                  hipStream_t s);
+    enum { SAMPLER_DDIM_REVERSE = 3 };           // sampler_update's fourth kind, behind diff_invert / diff_reverse_step only
+    void sampler_update(const Schedule& sc, const PairCall& pc, float* x, int B, int T, int sampler, float eta, int step,
+                        unsigned long long seed, int pstep, const float* noise, int denorm, hipStream_t s, float* x0_out = nullptr,
+                        float* x0_hist = nullptr);
+    struct SampleLoop {
+        int sampler = 0;                         // 0 (p), 1 (ddim), 2 (dpmsolver++: the history is the call's own)
+        float eta = 0.f;
+        int k_first = 0, k_end = 0;              // loop positions [k_first, k_end): position k runs step n - 1 - k
+        int resample = 1;                        // evaluations of every step above 0
+        const float* known = nullptr;            // inpainting blend after every update (null: none): known, keep and its two noise arrays
+        const unsigned char* keep = nullptr;
+        const float *known_noise = nullptr, *renoise = nullptr;
+        const float* step_noise = nullptr;       // per evaluation, in place of the Philox draw
+        float* x_traj = nullptr;                 // x after every evaluation
+        int denorm = 0;                          // the last position's update writes the raw log-mel
+    };
+    void sample_loop(Schedule& sc, const SampleLoop& c, const float* code_emb, const int* lens_host, int B, int T, unsigned long long seed,
+                     const int* sample_ids_host, const float* x_init, float* x, hipStream_t s);
+    template <class Update>
+    void single_step(Schedule& sc, const float* x, const float* code_emb, const int* lens_host, const int* sample_ids_host, int B, int T,
+                     int step, bool pinned_table, hipStream_t s, Update&& update);
     void ensure_fork_events();
     // the per-row driver behind diff_forward_rows / diff_training_losses: carves rows_ws_bytes(B, C, T) of ws(), which the caller has sized
     void diff_forward_rows_s(const Schedule& sc, const float* x, const float* code_emb, const int* lens_host, int B, int T, const int* step_of_row,

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <optional>
 #include "prof.h"
 
 namespace dtts {
@@ -400,8 +401,8 @@ Model::PairPlan Model::plan_pair(const int* lens_host, int B, int T, hipStream_t
     }
     for (int v : ul) li.push_back(v);
     PairPlan pl;
+    pl.lens_i_host = li;
     pl.Nu = (int)ul.size();
-    pl.ulen = ul;
     pl.lens2 = upload_ints(l2.data(), 2 * B, s);
     pl.lens_i = upload_ints(li.data(), (int)li.size(), s);
     pl.umap = upload_ints(um.data(), 4 * B, s);
@@ -734,6 +735,130 @@ Model::PairCall Model::begin_pair(const float* code_emb, const int* lens_host, c
     return pc;
 }
 
+// ------------------------------------------------------------------------------ what the sampling entries share
+static void check_lens(const int* lens_host, int B, int T) {
+    for (int b = 0; lens_host && b < B; ++b) DTTS_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= T, "lens: every length in [1, T]");
+}
+// May the code-path table of `nst` steps be built?  The terms of all steps are evaluated up front (opt-out: DTTS_INTEG_PRECOMPUTE=0) and
+// cost nst * 2B * C * T floats (3 GB at batch 8 x 10 s, 11 GB at batch 4 x 60 s): beyond DTTS_INTEG_MAX_GB (default 24) the integrator
+// and the code half run inside every step instead (same values, no table).
+static bool integ_table_fits(int nst, int B, int C, int T) {
+    static const bool env_pre_on = env_on("DTTS_INTEG_PRECOMPUTE");
+    static const double max_gb = []() { const char* v = env_str("DTTS_INTEG_MAX_GB"); return v ? atof(v) : 24.0; }();
+    return env_pre_on && (double)(sizeof(float) * (size_t)nst * 2 * B * C * T) <= max_gb * 1073741824.0;
+}
+static size_t integ_call_bytes(int nst, int B, int C, int T) {        // the table of nst steps + precompute_integrator's scratch (Nu <= B)
+    return sizeof(float) * (size_t)nst * 2 * B * C * T + integ_ws_bytes(2 * B, integ_chunk(B + 1) * 2 * B, C, T);
+}
+
+// x_T (vqvae/model_24k.py:488): per-sample noise indexed over the sample's own [128, len], so that element order == reference tensor order
+void Model::draw_x_T(float* x, const PairCall& pc, const int* lens_host, int B, int T, unsigned long long seed, hipStream_t s) {
+    const int MC = cfg.mel_channels;
+    const long long xbs = (long long)MC * T;
+    DTTS_CHECK_HIP(hipMemsetAsync(x, 0, sizeof(float) * (size_t)B * MC * T, s));
+    for (int b = 0; b < B; ++b) {
+        const int len = lens_host ? lens_host[b] : T;
+        if (len == T) {
+            launch_philox_normal(x + (size_t)b * xbs, xbs, MC * T, 1, seed, pc.sids + b, STAGE_DIFF_INIT, 0, 1.f, s);
+        } else {
+            // compact [128, len] then scatter rows into the padded buffer
+            float* tmp = pc.out2;   // free until the first forward
+            launch_philox_normal(tmp, 0, MC * len, 1, seed, pc.sids + b, STAGE_DIFF_INIT, 0, 1.f, s);
+            DTTS_CHECK_HIP(hipMemcpy2DAsync(x + (size_t)b * xbs, sizeof(float) * T, tmp, sizeof(float) * len, sizeof(float) * len, MC,
+                                            hipMemcpyDeviceToDevice, s));
+        }
+    }
+}
+
+// The code-path terms of loop positions [k_first, k_end), carved from ws() and evaluated here: position k is step k of an ascending loop,
+// step n - 1 - k of a descending one.  Unpinned, a row's bits follow the width of the launch that made it (split-K), and the whole loop
+// evaluates J = integ_chunk steps per launch from position 0: the table then starts at the launch that holds k_first, unneeded steps
+// included (at most J - 1), so a loop entered anywhere reads the bits the whole loop reads.  Pinned (RowInvariantLaunches), a row is the
+// same bits whatever shares its launch, and the table starts at k_first.
+Model::CodePathTable Model::code_path_table(const Schedule& sc, const PairCall& pc, int B, int T, int k_first, int k_end, bool descending,
+                                            bool pinned, hipStream_t s) {
+    const PairPlan& pl = pc.pl;
+    const int Bi = B + pl.Nu, J = integ_chunk(Bi);
+    CodePathTable t;
+    t.k0 = pinned ? k_first : k_first / J * J;
+    t.stride = (size_t)Bi * cfg.diff_channels * T;
+    std::vector<int> steps(k_end - t.k0);
+    for (int k = t.k0; k < k_end; ++k) steps[k - t.k0] = descending ? sc.n - 1 - k : k;
+    t.base = ws().f32(steps.size() * t.stride);
+    std::optional<RowInvariantLaunches> pin;
+    if (pinned) pin.emplace();
+    precompute_integrator(sc, pc.cbuf0, pl.lens_i, pl.lens_i_host.data(), B, pl.Nu, T, steps, t.base, s);
+    return t;
+}
+
+// one sampler update on the forward's output pc.out2, x in place: p_sample (0), ddim_sample (1), DPM-Solver++(2M) (2: x0_hist) or
+// ddim_reverse_sample (SAMPLER_DDIM_REVERSE: the entries' own, no noise) of step `step`.  pstep: the Philox step field of the noise
+// drawn when `noise` is null.
+void Model::sampler_update(const Schedule& sc, const PairCall& pc, float* x, int B, int T, int sampler, float eta, int step,
+                           unsigned long long seed, int pstep, const float* noise, int denorm, hipStream_t s, float* x0_out, float* x0_hist) {
+    const int OC = cfg.diff_out_channels, MC = cfg.mel_channels;
+    const long long xbs = (long long)MC * T, obs = (long long)OC * T;
+    const int* lens2 = pc.pl.lens2;
+    if (sampler == SAMPLER_DDIM_REVERSE)
+        launch_ddim_reverse_update(x, xbs, T, pc.out2, obs, T, lens2, T, B, MC, sc.ddim_reverse(step), s, x0_out);
+    else if (sampler == 2)
+        launch_dpm_update(x, xbs, T, pc.out2, obs, T, lens2, T, B, MC, sc.dpm[step], x0_hist, denorm, s, x0_out);
+    else if (sampler == 1)
+        launch_ddim_update(x, xbs, T, pc.out2, obs, T, lens2, T, B, MC, sc.ddim(step, eta), seed, pc.sids, pstep, noise, denorm, s, x0_out);
+    else
+        launch_diff_update(x, xbs, T, pc.out2, obs, T, lens2, T, B, MC, sc.p[step], seed, pc.sids, pstep, noise, denorm, s, x0_out);
+}
+
+// The descending sampling loop behind diff_sample_ex, diff_sample_from and diff_inpaint: positions [k_first, k_end), position k at step
+// i = n - 1 - k, every step above 0 run `resample` times.  x_init null: x_T is drawn.  The fit decision, the workspace and the table's
+// launches are those of a loop over [0, k_end) (code_path_table), so a loop cut in two equals the loop run through; a loop cut short
+// (k_end < n) keeps its narrower last launch.  Evaluation e (counted from k_first) indexes the noise and trajectory arrays and the
+// profiler's sampling; repeat r of step i draws on the Philox step field i + r * n, so repeat 0 is the plain loop's key.
+void Model::sample_loop(Schedule& sc, const SampleLoop& c, const float* code_emb, const int* lens_host, int B, int T, unsigned long long seed,
+                        const int* sample_ids_host, const float* x_init, float* x, hipStream_t s) {
+    const int C = cfg.diff_channels, MC = cfg.mel_channels;
+    const size_t plane = (size_t)B * MC * T;
+    const bool fits = integ_table_fits(c.k_end, B, C, T);
+    const PairCall pc = begin_pair(code_emb, lens_host, sample_ids_host, B, T, s, fits ? integ_call_bytes(c.k_end, B, C, T) : 0,
+                                   c.sampler == 2 ? plane : 0);               // DPM-Solver++(2M): the previous step's x0
+    if (!x_init)
+        draw_x_T(x, pc, lens_host, B, T, seed, s);
+    else if (x != x_init)
+        DTTS_CHECK_HIP(hipMemcpyAsync(x, x_init, sizeof(float) * plane, hipMemcpyDeviceToDevice, s));
+    const CodePathTable tab = fits ? code_path_table(sc, pc, B, T, c.k_first, c.k_end, true, false, s) : CodePathTable{};
+    const size_t mark = ws().mark();
+    size_t e = 0;
+    for (int k = c.k_first; k < c.k_end; ++k) {
+        const int i = sc.n - 1 - k, reps = i == 0 ? 1 : c.resample;
+        for (int r = 0; r < reps; ++r, ++e) {
+            Profiler::gate() = (e % Profiler::get().step_every) == 0;
+            ws().rewind(mark);                              // the forward's scratch is re-carved every evaluation
+            diff_forward_pair(sc, x, pc.cbuf0, pc.pl, B, T, i, pc.out2, s, tab.at(k));
+            const int pstep = i + r * sc.n;
+            sampler_update(sc, pc, x, B, T, c.sampler, c.eta, i, seed, pstep, c.step_noise ? c.step_noise + e * plane : nullptr,
+                           (c.denorm && k == c.k_end - 1) ? 1 : 0, s, nullptr, pc.hist);
+            if (c.known)    // the kept frames back at level i - 1 and, before another repeat, x one forward step up again (diff_inpaint.h)
+                launch_inpaint_blend(x, c.known, c.keep, pc.pl.lens2, T, B, MC, sc.inpaint(i), i == 0 ? 1 : 0, r < reps - 1 ? 1 : 0, seed, pc.sids,
+                                     pstep, c.known_noise ? c.known_noise + e * plane : nullptr, c.renoise ? c.renoise + e * plane : nullptr, s);
+            if (c.x_traj) DTTS_CHECK_HIP(hipMemcpyAsync(c.x_traj + e * plane, x, sizeof(float) * plane, hipMemcpyDeviceToDevice, s));
+        }
+    }
+    Profiler::gate() = true;
+    if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
+}
+
+// What the single-step entries share: the call's set-up, the forward at `step` - with pinned_table behind a one-step code-path table
+// under RowInvariantLaunches, which is diff_invert's step bit for bit - then the caller's update on pc.out2
+template <class Update>
+void Model::single_step(Schedule& sc, const float* x, const float* code_emb, const int* lens_host, const int* sample_ids_host, int B, int T,
+                        int step, bool pinned_table, hipStream_t s, Update&& update) {
+    const PairCall pc = begin_pair(code_emb, lens_host, sample_ids_host, B, T, s, pinned_table ? integ_call_bytes(1, B, cfg.diff_channels, T) : 0);
+    const CodePathTable tab = pinned_table ? code_path_table(sc, pc, B, T, step, step + 1, false, true, s) : CodePathTable{};
+    diff_forward_pair(sc, x, pc.cbuf0, pc.pl, B, T, step, pc.out2, s, tab.at(step));
+    update(pc);
+    if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
+}
+
 // ------------------------------------------------------------------------------ stage entry points
 void Model::diff_forward(const float* x, const float* code_emb, const int* lens_host, int B, int T, int step, int cond_free,
                          float* out, hipStream_t s) {
@@ -790,6 +915,7 @@ void Model::diff_sample(const float* code_emb, const int* lens_host, int B, int 
     diff_sample_ex(0, 0, 0.f, code_emb, lens_host, B, T, seed, sample_ids_host, n_steps, x_init, step_noise, mel_out, denorm, s);
 }
 
+// the first n_steps steps of the schedule from x_init, or from a drawn x_T: sample_loop over positions [0, n_steps)
 void Model::diff_sample_ex(int sched_id, int sampler, float eta, const float* code_emb, const int* lens_host, int B, int T,
                            unsigned long long seed, const int* sample_ids_host, int n_steps, const float* x_init, const float* step_noise,
                            float* mel_out, int denorm, hipStream_t s) {
@@ -801,71 +927,13 @@ void Model::diff_sample_ex(int sched_id, int sampler, float eta, const float* co
     DTTS_REQUIRE(dpm == (sc.kind == 1), dpm ? "sampler 2 (dpmsolver++) runs on a DPM schedule (dtts_diff_schedule_dpm)"
                                             : "samplers 0 / 1 run on an integer-timestep schedule (dtts_diff_schedule)");
     DTTS_REQUIRE(!dpm || (eta == 0.f && !step_noise), "dpmsolver++ draws no noise: eta must be 0 and step_noise NULL");
-    const int C = cfg.diff_channels, OC = cfg.diff_out_channels, MC = cfg.mel_channels;
-    if (n_steps <= 0 || n_steps > sc.n) n_steps = sc.n;
-    // the code-path terms of all steps (the integrator's outputs through the code half of integrating_conv) are evaluated up front
-    // (opt-out: DTTS_INTEG_PRECOMPUTE=0); Nu <= B distinct lengths
-    static const bool env_pre_on = env_on("DTTS_INTEG_PRECOMPUTE");
-    // the precomputed terms of all steps cost n_steps * 2B * C * T floats (3 GB at batch 8 x 10 s, 11 GB at batch 4 x 60 s):
-    // beyond DTTS_INTEG_MAX_GB (default 24) the integrator and the code half run inside every step instead (same values, no table)
-    static const double max_gb = []() { const char* v = env_str("DTTS_INTEG_MAX_GB"); return v ? atof(v) : 24.0; }();
-    const size_t integ_table = sizeof(float) * (size_t)n_steps * 2 * B * C * T;
-    const bool env_pre = env_pre_on && (double)integ_table <= max_gb * 1073741824.0;
-    const size_t integ_bytes = env_pre ? integ_table + integ_ws_bytes(2 * B, integ_chunk(B + 1) * 2 * B, C, T) : 0;
-    const size_t hist_floats = dpm ? (size_t)B * MC * T : 0;          // DPM-Solver++(2M): the previous step's x0
-    const PairCall pc = begin_pair(code_emb, lens_host, sample_ids_host, B, T, s, integ_bytes, hist_floats);
-    const PairPlan& pl = pc.pl;
-    const int *lens2 = pl.lens2, *sids = pc.sids;
-    float *cbuf0 = pc.cbuf0, *out2 = pc.out2, *x0_hist = pc.hist;
-    // x_T  (vqvae/model_24k.py:488); per-sample noise is indexed over the sample's own [128, len]
-    float* x = mel_out;
-    const long long xbs = (long long)MC * T;
-    if (x_init) {
-        DTTS_CHECK_HIP(hipMemcpyAsync(x, x_init, sizeof(float) * (size_t)B * MC * T, hipMemcpyDeviceToDevice, s));
-    } else {
-        DTTS_CHECK_HIP(hipMemsetAsync(x, 0, sizeof(float) * (size_t)B * MC * T, s));
-        // generate per sample with its own length so that element order == reference tensor order
-        for (int b = 0; b < B; ++b) {
-            const int len = lens_host ? lens_host[b] : T;
-            if (len == T) {
-                launch_philox_normal(x + (size_t)b * xbs, xbs, MC * T, 1, seed, sids + b, STAGE_DIFF_INIT, 0, 1.f, s);
-            } else {
-                // compact [128, len] then scatter rows into the padded buffer
-                float* tmp = out2;   // free until the first forward
-                launch_philox_normal(tmp, 0, MC * len, 1, seed, sids + b, STAGE_DIFF_INIT, 0, 1.f, s);
-                DTTS_CHECK_HIP(hipMemcpy2DAsync(x + (size_t)b * xbs, sizeof(float) * T, tmp, sizeof(float) * len,
-                                                sizeof(float) * len, MC, hipMemcpyDeviceToDevice, s));
-            }
-        }
-    }
-    float* integ_all = nullptr;
-    const int Bi = B + pl.Nu;
-    if (env_pre) {
-        std::vector<int> steps(n_steps), li(Bi);
-        for (int k = 0; k < n_steps; ++k) steps[k] = sc.n - 1 - k;
-        for (int b = 0; b < B; ++b) li[b] = lens_host ? lens_host[b] : T;
-        for (int u = 0; u < pl.Nu; ++u) li[B + u] = pl.ulen[u];
-        integ_all = ws().f32((size_t)n_steps * Bi * C * T);
-        precompute_integrator(sc, cbuf0, pl.lens_i, li.data(), B, pl.Nu, T, steps, integ_all, s);
-    }
-    const size_t mark = ws().mark();
-    for (int k = 0; k < n_steps; ++k) {
-        const int i = sc.n - 1 - k;
-        Profiler::gate() = (k % Profiler::get().step_every) == 0;
-        ws().rewind(mark);                              // the forward's scratch is re-carved every step
-        diff_forward_pair(sc, x, cbuf0, pl, B, T, i, out2, s, integ_all ? integ_all + (size_t)k * Bi * C * T : nullptr);
-        const bool last = (k == n_steps - 1);
-        const float* nz = step_noise ? step_noise + (size_t)k * B * MC * T : nullptr;
-        if (dpm)
-            launch_dpm_update(x, xbs, T, out2, (long long)OC * T, T, lens2, T, B, MC, sc.dpm[i], x0_hist, (denorm && last) ? 1 : 0, s);
-        else if (sampler == 1)
-            launch_ddim_update(x, xbs, T, out2, (long long)OC * T, T, lens2, T, B, MC, sc.ddim(i, eta), seed, sids, i, nz,
-                               (denorm && last) ? 1 : 0, s);
-        else
-            launch_diff_update(x, xbs, T, out2, (long long)OC * T, T, lens2, T, B, MC, sc.p[i], seed, sids, i, nz, (denorm && last) ? 1 : 0, s);
-    }
-    Profiler::gate() = true;
-    if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
+    SampleLoop c;
+    c.sampler = sampler;
+    c.eta = eta;
+    c.k_end = (n_steps <= 0 || n_steps > sc.n) ? sc.n : n_steps;
+    c.step_noise = step_noise;
+    c.denorm = denorm;
+    sample_loop(sc, c, code_emb, lens_host, B, T, seed, sample_ids_host, x_init, mel_out, s);
 }
 
 // GaussianDiffusion.p_sample (vqvae/utils/diffusion.py:445-485) at one sampling step, x in place
@@ -884,37 +952,15 @@ void Model::diff_step(int sched_id, int sampler, float eta, float* x, const floa
     DTTS_REQUIRE(sc.kind == 0, "diff_step runs on an integer-timestep schedule (DPM-Solver++: diff_step_dpm)");
     DTTS_REQUIRE(step >= 0 && step < sc.n, "step out of range");
     DTTS_REQUIRE(sample_ids_host, "sample_ids");
-    const int OC = cfg.diff_out_channels, MC = cfg.mel_channels;
-    const PairCall pc = begin_pair(code_emb, lens_host, sample_ids_host, B, T, s);
-    const PairPlan& pl = pc.pl;
-    diff_forward_pair(sc, x, pc.cbuf0, pl, B, T, step, pc.out2, s);
-    if (sampler == 1)
-        launch_ddim_update(x, (long long)MC * T, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.ddim(step, eta), seed, pc.sids, step,
-                           noise, 0, s, x0_out);
-    else
-        launch_diff_update(x, (long long)MC * T, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.p[step], seed, pc.sids, step, noise, 0,
-                           s, x0_out);
-    if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
+    single_step(sc, x, code_emb, lens_host, sample_ids_host, B, T, step, false, s, [&](const PairCall& pc) {
+        sampler_update(sc, pc, x, B, T, sampler, eta, step, seed, step, noise, 0, s, x0_out);
+    });
 }
 
 // ---- DDIM inversion, partial-depth sampling, p_mean_variance
-static void check_lens(const int* lens_host, int B, int T) {
-    for (int b = 0; lens_host && b < B; ++b) DTTS_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= T, "lens: every length in [1, T]");
-}
-// may the code-path table of `nst` steps be built (diff_sample_ex's rule: DTTS_INTEG_PRECOMPUTE, DTTS_INTEG_MAX_GB)
-static bool integ_table_fits(int nst, int B, int C, int T) {
-    static const bool env_pre_on = env_on("DTTS_INTEG_PRECOMPUTE");
-    static const double max_gb = []() { const char* v = env_str("DTTS_INTEG_MAX_GB"); return v ? atof(v) : 24.0; }();
-    return env_pre_on && (double)(sizeof(float) * (size_t)nst * 2 * B * C * T) <= max_gb * 1073741824.0;
-}
-static size_t integ_call_bytes(int nst, int B, int C, int T) {        // the table of nst steps + precompute_integrator's scratch
-    return sizeof(float) * (size_t)nst * 2 * B * C * T + integ_ws_bytes(2 * B, integ_chunk(B + 1) * 2 * B, C, T);
-}
-
 // GaussianDiffusion.ddim_reverse_sample (vqvae/utils/diffusion.py:785-817) for t = 0 .. depth - 1.  The code-path terms are evaluated for
-// exactly those steps, in that order, under RowInvariantLaunches: a row of the table is then the same bits whatever shares its launch, so
-// diff_reverse_step - a table of one step - computes this loop's step bit for bit.  A table beyond DTTS_INTEG_MAX_GB is built one step at
-// a time inside the loop (same values).
+// exactly those steps, in that order, under RowInvariantLaunches (code_path_table, pinned), so diff_reverse_step - a table of one step -
+// computes this loop's step bit for bit.  A table beyond DTTS_INTEG_MAX_GB is built one step at a time inside the loop (same values).
 void Model::diff_invert(int sched_id, const float* code_emb, const int* lens_host, int B, int T, const float* x_start, int depth,
                         float* x_out, float* x_traj, float* x0_traj, hipStream_t s) {
     DTTS_REQUIRE(bound_, "weights not bound");
@@ -923,37 +969,26 @@ void Model::diff_invert(int sched_id, const float* code_emb, const int* lens_hos
     DTTS_REQUIRE(sc.kind == 0, "diff_invert runs on an integer-timestep schedule (dtts_diff_schedule)");
     DTTS_REQUIRE(depth >= 1 && depth <= sc.n, "diff_invert: depth out of [1, steps of the schedule]");
     check_lens(lens_host, B, T);
-    const int C = cfg.diff_channels, OC = cfg.diff_out_channels, MC = cfg.mel_channels;
-    const bool table = integ_table_fits(depth, B, C, T);
-    const int nst = table ? depth : 1;
-    const PairCall pc = begin_pair(code_emb, lens_host, nullptr, B, T, s, integ_call_bytes(nst, B, C, T));
+    const int C = cfg.diff_channels, MC = cfg.mel_channels;
+    const bool fits = integ_table_fits(depth, B, C, T);
+    const PairCall pc = begin_pair(code_emb, lens_host, nullptr, B, T, s, integ_call_bytes(fits ? depth : 1, B, C, T));
     const PairPlan& pl = pc.pl;
     const size_t plane = (size_t)B * MC * T;
     float* x = x_out;
-    const long long xbs = (long long)MC * T;
     if (x != x_start) DTTS_CHECK_HIP(hipMemcpyAsync(x, x_start, sizeof(float) * plane, hipMemcpyDeviceToDevice, s));
-    const int Bi = B + pl.Nu;
-    std::vector<int> li(Bi);
-    for (int b = 0; b < B; ++b) li[b] = lens_host ? lens_host[b] : T;
-    for (int u = 0; u < pl.Nu; ++u) li[B + u] = pl.ulen[u];
-    float* integ_all = ws().f32((size_t)nst * Bi * C * T);
-    if (table) {
-        std::vector<int> steps(depth);
-        for (int k = 0; k < depth; ++k) steps[k] = k;
-        RowInvariantLaunches pin;
-        precompute_integrator(sc, pc.cbuf0, pl.lens_i, li.data(), B, pl.Nu, T, steps, integ_all, s);
-    }
+    // without the table: one slot (stride 0), refilled in front of every step
+    const CodePathTable tab = fits ? code_path_table(sc, pc, B, T, 0, depth, false, true, s)
+                                   : CodePathTable{ws().f32((size_t)(B + pl.Nu) * C * T), 0, 0};
     const size_t mark = ws().mark();
     for (int i = 0; i < depth; ++i) {
         Profiler::gate() = (i % Profiler::get().step_every) == 0;
         ws().rewind(mark);
-        if (!table) {
+        if (!fits) {
             RowInvariantLaunches pin;
-            precompute_integrator(sc, pc.cbuf0, pl.lens_i, li.data(), B, pl.Nu, T, std::vector<int>{i}, integ_all, s);
+            precompute_integrator(sc, pc.cbuf0, pl.lens_i, pl.lens_i_host.data(), B, pl.Nu, T, std::vector<int>{i}, tab.base, s);
         }
-        diff_forward_pair(sc, x, pc.cbuf0, pl, B, T, i, pc.out2, s, integ_all + (table ? (size_t)i * Bi * C * T : 0));
-        launch_ddim_reverse_update(x, xbs, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.ddim_reverse(i), s,
-                                   x0_traj ? x0_traj + (size_t)i * plane : nullptr);
+        diff_forward_pair(sc, x, pc.cbuf0, pl, B, T, i, pc.out2, s, tab.at(i));
+        sampler_update(sc, pc, x, B, T, SAMPLER_DDIM_REVERSE, 0.f, i, 0, i, nullptr, 0, s, x0_traj ? x0_traj + (size_t)i * plane : nullptr);
         if (x_traj) DTTS_CHECK_HIP(hipMemcpyAsync(x_traj + (size_t)i * plane, x, sizeof(float) * plane, hipMemcpyDeviceToDevice, s));
     }
     Profiler::gate() = true;
@@ -969,21 +1004,9 @@ void Model::diff_reverse_step(int sched_id, float* x, const float* code_emb, con
     DTTS_REQUIRE(sc.kind == 0, "diff_reverse_step runs on an integer-timestep schedule (dtts_diff_schedule)");
     DTTS_REQUIRE(step >= 0 && step < sc.n, "step out of range");
     check_lens(lens_host, B, T);
-    const int C = cfg.diff_channels, OC = cfg.diff_out_channels, MC = cfg.mel_channels;
-    const PairCall pc = begin_pair(code_emb, lens_host, nullptr, B, T, s, integ_call_bytes(1, B, C, T));
-    const PairPlan& pl = pc.pl;
-    const int Bi = B + pl.Nu;
-    std::vector<int> li(Bi);
-    for (int b = 0; b < B; ++b) li[b] = lens_host ? lens_host[b] : T;
-    for (int u = 0; u < pl.Nu; ++u) li[B + u] = pl.ulen[u];
-    float* integ = ws().f32((size_t)Bi * C * T);
-    {
-        RowInvariantLaunches pin;
-        precompute_integrator(sc, pc.cbuf0, pl.lens_i, li.data(), B, pl.Nu, T, std::vector<int>{step}, integ, s);
-    }
-    diff_forward_pair(sc, x, pc.cbuf0, pl, B, T, step, pc.out2, s, integ);
-    launch_ddim_reverse_update(x, (long long)MC * T, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.ddim_reverse(step), s, x0_out);
-    if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
+    single_step(sc, x, code_emb, lens_host, nullptr, B, T, step, true, s, [&](const PairCall& pc) {
+        sampler_update(sc, pc, x, B, T, SAMPLER_DDIM_REVERSE, 0.f, step, 0, step, nullptr, 0, s, x0_out);
+    });
 }
 
 // GaussianDiffusion.p_mean_variance (vqvae/utils/diffusion.py:284-386) at spaced step `step`: diff_step's forward, nothing sampled
@@ -997,18 +1020,14 @@ void Model::diff_mean_variance(int sched_id, const float* x, const float* code_e
     DTTS_REQUIRE(step >= 0 && step < sc.n, "step out of range");
     check_lens(lens_host, B, T);
     const int OC = cfg.diff_out_channels, MC = cfg.mel_channels;
-    const PairCall pc = begin_pair(code_emb, lens_host, nullptr, B, T, s);
-    const PairPlan& pl = pc.pl;
-    diff_forward_pair(sc, x, pc.cbuf0, pl, B, T, step, pc.out2, s);
-    launch_diff_mean_variance(x, (long long)MC * T, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.p[step], mean, variance,
-                              log_variance, pred_xstart, s);
-    if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
+    single_step(sc, x, code_emb, lens_host, nullptr, B, T, step, false, s, [&](const PairCall& pc) {
+        launch_diff_mean_variance(x, (long long)MC * T, T, pc.out2, (long long)OC * T, T, pc.pl.lens2, T, B, MC, sc.p[step], mean, variance,
+                                  log_variance, pred_xstart, s);
+    });
 }
 
 // diff_sample_ex entered at step `first_step`: x_init is x at that level, steps first_step .. 0 run, Philox noise keyed by the step index
-// as in the whole loop.  The whole loop evaluates its code-path table J steps per launch from step n - 1 down, and a launch's split-K
-// follows its width; here the launches that hold a needed step are made whole, unneeded steps included (at most J - 1 of them), so every
-// step reads the bits the whole loop reads and a loop cut in two equals the loop run through.
+// as in the whole loop: sample_loop over positions [n - 1 - first_step, n), whose table makes a loop cut in two equal the loop run through
 void Model::diff_sample_from(int sched_id, int sampler, float eta, int first_step, const float* code_emb, const int* lens_host, int B, int T,
                              unsigned long long seed, const int* sample_ids_host, const float* x_init, const float* step_noise,
                              float* mel_out, int denorm, hipStream_t s) {
@@ -1020,48 +1039,22 @@ void Model::diff_sample_from(int sched_id, int sampler, float eta, int first_ste
     DTTS_REQUIRE(sc.kind == 0, "diff_sample_from runs on an integer-timestep schedule (dtts_diff_schedule)");
     DTTS_REQUIRE(first_step >= 0 && first_step < sc.n, "diff_sample_from: first_step out of [0, steps of the schedule)");
     check_lens(lens_host, B, T);
-    const int C = cfg.diff_channels, OC = cfg.diff_out_channels, MC = cfg.mel_channels;
-    const bool table = integ_table_fits(sc.n, B, C, T);                  // the whole loop's decision
-    const PairCall pc = begin_pair(code_emb, lens_host, sample_ids_host, B, T, s, table ? integ_call_bytes(sc.n, B, C, T) : 0);
-    const PairPlan& pl = pc.pl;
-    float* x = mel_out;
-    const long long xbs = (long long)MC * T;
-    if (x != x_init) DTTS_CHECK_HIP(hipMemcpyAsync(x, x_init, sizeof(float) * (size_t)B * MC * T, hipMemcpyDeviceToDevice, s));
-    const int Bi = B + pl.Nu, k_first = sc.n - 1 - first_step;           // loop position of first_step
-    float* integ_all = nullptr;
-    int k_table = k_first;
-    if (table) {
-        k_table = k_first / integ_chunk(Bi) * integ_chunk(Bi);           // the whole loop's launch that holds first_step starts here
-        std::vector<int> steps(sc.n - k_table), li(Bi);
-        for (int k = k_table; k < sc.n; ++k) steps[k - k_table] = sc.n - 1 - k;
-        for (int b = 0; b < B; ++b) li[b] = lens_host ? lens_host[b] : T;
-        for (int u = 0; u < pl.Nu; ++u) li[B + u] = pl.ulen[u];
-        integ_all = ws().f32(steps.size() * (size_t)Bi * C * T);
-        precompute_integrator(sc, pc.cbuf0, pl.lens_i, li.data(), B, pl.Nu, T, steps, integ_all, s);
-    }
-    const size_t mark = ws().mark();
-    for (int k = k_first; k < sc.n; ++k) {
-        const int i = sc.n - 1 - k;
-        Profiler::gate() = ((k - k_first) % Profiler::get().step_every) == 0;
-        ws().rewind(mark);
-        diff_forward_pair(sc, x, pc.cbuf0, pl, B, T, i, pc.out2, s, integ_all ? integ_all + (size_t)(k - k_table) * Bi * C * T : nullptr);
-        const int dn = (denorm && i == 0) ? 1 : 0;
-        const float* nz = step_noise ? step_noise + (size_t)(k - k_first) * B * MC * T : nullptr;
-        if (sampler == 1)
-            launch_ddim_update(x, xbs, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.ddim(i, eta), seed, pc.sids, i, nz, dn, s);
-        else
-            launch_diff_update(x, xbs, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.p[i], seed, pc.sids, i, nz, dn, s);
-    }
-    Profiler::gate() = true;
-    if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
+    SampleLoop c;
+    c.sampler = sampler;
+    c.eta = eta;
+    c.k_first = sc.n - 1 - first_step;
+    c.k_end = sc.n;
+    c.step_noise = step_noise;
+    c.denorm = denorm;
+    sample_loop(sc, c, code_emb, lens_host, B, T, seed, sample_ids_host, x_init, mel_out, s);
 }
 
 // ---- mel inpainting (RePaint, Lugmayr et al. 2022): diff_sample_from with the kept frames overwritten after every update
 // Step i, repeat r of U: the unchanged sampler update takes x from level i to i - 1, the blend (diff_inpaint.h) overwrites the kept
 // frames with `known` at level i - 1 and, for r < U - 1, takes x one forward step back up to level i.  Step 0 runs once.  All three
 // noise streams carry the Philox step field i + r * N: the update kernels' `step` argument feeds only the key, so repeat 0 of
-// STAGE_DIFF_STEP is the plain loop's key and a call with nothing kept and U = 1 is diff_sample_from bit for bit.  The code-path
-// table is the whole loop's (as in diff_sample_from) and is read again by every repeat of a step.
+// STAGE_DIFF_STEP is the plain loop's key and a call with nothing kept and U = 1 is diff_sample_from bit for bit: both are sample_loop,
+// whose table every repeat of a step reads again.
 void Model::diff_inpaint(int sched_id, int sampler, float eta, int first_step, int resample, const float* code_emb, const int* lens_host,
                          int B, int T, unsigned long long seed, const int* sample_ids_host, const float* x_init, const float* known,
                          const unsigned char* keep, const float* step_noise, const float* known_noise, const float* renoise, float* x_out,
@@ -1077,64 +1070,19 @@ void Model::diff_inpaint(int sched_id, int sampler, float eta, int first_step, i
     DTTS_REQUIRE(first_step >= 0 && first_step < sc.n, "diff_inpaint: first_step out of [0, steps of the schedule)");
     DTTS_REQUIRE(x_init || first_step == sc.n - 1, "diff_inpaint: x_init is required below the top of the schedule");
     check_lens(lens_host, B, T);
-    const int C = cfg.diff_channels, OC = cfg.diff_out_channels, MC = cfg.mel_channels;
-    const bool table = integ_table_fits(sc.n, B, C, T);                  // the whole loop's decision
-    const PairCall pc = begin_pair(code_emb, lens_host, sample_ids_host, B, T, s, table ? integ_call_bytes(sc.n, B, C, T) : 0);
-    const PairPlan& pl = pc.pl;
-    float* x = x_out;
-    const long long xbs = (long long)MC * T;
-    const size_t plane = (size_t)B * MC * T;
-    if (x_init) {
-        if (x != x_init) DTTS_CHECK_HIP(hipMemcpyAsync(x, x_init, sizeof(float) * plane, hipMemcpyDeviceToDevice, s));
-    } else {                                                             // x_T as diff_sample_ex draws it
-        DTTS_CHECK_HIP(hipMemsetAsync(x, 0, sizeof(float) * plane, s));
-        for (int b = 0; b < B; ++b) {
-            const int len = lens_host ? lens_host[b] : T;
-            if (len == T) {
-                launch_philox_normal(x + (size_t)b * xbs, xbs, MC * T, 1, seed, pc.sids + b, STAGE_DIFF_INIT, 0, 1.f, s);
-            } else {
-                float* tmp = pc.out2;                                    // free until the first forward
-                launch_philox_normal(tmp, 0, MC * len, 1, seed, pc.sids + b, STAGE_DIFF_INIT, 0, 1.f, s);
-                DTTS_CHECK_HIP(hipMemcpy2DAsync(x + (size_t)b * xbs, sizeof(float) * T, tmp, sizeof(float) * len, sizeof(float) * len, MC,
-                                                hipMemcpyDeviceToDevice, s));
-            }
-        }
-    }
-    const int Bi = B + pl.Nu, k_first = sc.n - 1 - first_step;           // loop position of first_step
-    float* integ_all = nullptr;
-    int k_table = k_first;
-    if (table) {
-        k_table = k_first / integ_chunk(Bi) * integ_chunk(Bi);           // the whole loop's launch that holds first_step starts here
-        std::vector<int> steps(sc.n - k_table), li(Bi);
-        for (int k = k_table; k < sc.n; ++k) steps[k - k_table] = sc.n - 1 - k;
-        for (int b = 0; b < B; ++b) li[b] = lens_host ? lens_host[b] : T;
-        for (int u = 0; u < pl.Nu; ++u) li[B + u] = pl.ulen[u];
-        integ_all = ws().f32(steps.size() * (size_t)Bi * C * T);
-        precompute_integrator(sc, pc.cbuf0, pl.lens_i, li.data(), B, pl.Nu, T, steps, integ_all, s);
-    }
-    const size_t mark = ws().mark();
-    size_t e = 0;                                                        // evaluation index: the override arrays' leading axis
-    for (int k = k_first; k < sc.n; ++k) {
-        const int i = sc.n - 1 - k;
-        const InpaintCoefs kc = sc.inpaint(i);
-        const int reps = i == 0 ? 1 : resample;
-        for (int r = 0; r < reps; ++r, ++e) {
-            Profiler::gate() = (e % Profiler::get().step_every) == 0;
-            ws().rewind(mark);
-            diff_forward_pair(sc, x, pc.cbuf0, pl, B, T, i, pc.out2, s, integ_all ? integ_all + (size_t)(k - k_table) * Bi * C * T : nullptr);
-            const int pstep = i + r * sc.n;
-            const float* nz = step_noise ? step_noise + e * plane : nullptr;
-            if (sampler == 1)
-                launch_ddim_update(x, xbs, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.ddim(i, eta), seed, pc.sids, pstep, nz, 0, s);
-            else
-                launch_diff_update(x, xbs, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.p[i], seed, pc.sids, pstep, nz, 0, s);
-            launch_inpaint_blend(x, known, keep, pl.lens2, T, B, MC, kc, i == 0 ? 1 : 0, r < reps - 1 ? 1 : 0, seed, pc.sids, pstep,
-                                 known_noise ? known_noise + e * plane : nullptr, renoise ? renoise + e * plane : nullptr, s);
-            if (x_traj) DTTS_CHECK_HIP(hipMemcpyAsync(x_traj + e * plane, x, sizeof(float) * plane, hipMemcpyDeviceToDevice, s));
-        }
-    }
-    Profiler::gate() = true;
-    if (sc.used) DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
+    SampleLoop c;
+    c.sampler = sampler;
+    c.eta = eta;
+    c.k_first = sc.n - 1 - first_step;
+    c.k_end = sc.n;
+    c.resample = resample;
+    c.known = known;
+    c.keep = keep;
+    c.known_noise = known_noise;
+    c.renoise = renoise;
+    c.step_noise = step_noise;
+    c.x_traj = x_traj;
+    sample_loop(sc, c, code_emb, lens_host, B, T, seed, sample_ids_host, x_init, x_out, s);
 }
 
 void Model::op_inpaint_blend(float* x, const float* known, const unsigned char* keep, const int* lens_host, int B, int C, int T,
@@ -1155,12 +1103,9 @@ void Model::diff_step_dpm(int sched_id, float* x, float* x0_hist, const float* c
     DTTS_REQUIRE(sc.kind == 1, "diff_step_dpm runs on a DPM schedule (dtts_diff_schedule_dpm)");
     DTTS_REQUIRE(step >= 0 && step < sc.n, "step out of range");
     DTTS_REQUIRE(x && x0_hist && code_emb, "x, x0_hist, code_emb");
-    const int OC = cfg.diff_out_channels, MC = cfg.mel_channels;
-    const PairCall pc = begin_pair(code_emb, lens_host, nullptr, B, T, s);
-    const PairPlan& pl = pc.pl;
-    diff_forward_pair(sc, x, pc.cbuf0, pl, B, T, step, pc.out2, s);
-    launch_dpm_update(x, (long long)MC * T, T, pc.out2, (long long)OC * T, T, pl.lens2, T, B, MC, sc.dpm[step], x0_hist, 0, s, x0_out);
-    DTTS_CHECK_HIP(hipEventRecord(sc.used, s));
+    single_step(sc, x, code_emb, lens_host, nullptr, B, T, step, false, s, [&](const PairCall& pc) {
+        sampler_update(sc, pc, x, B, T, 2, 0.f, step, 0, step, nullptr, 0, s, x0_out, x0_hist);
+    });
 }
 
 void Model::diff_conditioning(const float* refer, const int* lens_host, int B, int Tmax, float* cond_out, hipStream_t s) {

@@ -175,6 +175,24 @@ def test_nothing_kept_is_the_plain_loop(synth, S, kw, name, eta):
         assert bool(torch.isfinite(plain).all()) and torch.equal(got, plain), (extra.keys(), maxabs(host(got), host(plain)))
 
 
+@pytest.mark.parametrize("sampler,eta", [(0, 0.0), (1, 0.5)])
+def test_nothing_kept_from_a_drawn_x_T_is_diff_sample_ex(synth, sampler, eta):
+    """the entries themselves on a ragged batch, lens (48, 20, 33): dtts_diff_inpaint with keep all False, U = 1, from the top with no
+    x_init equals dtts_diff_sample_ex (no x_init, denorm off) bit for bit - both draw x_T, the short rows through the
+    compact-then-scatter route, and run the same loop"""
+    from detail_tts_amd.vqvae.utils.diffusion import space_timesteps
+    rt = synth.rt
+    lens, sids, seed = [48, 20, 33], [3, 11, 4], 7
+    rs = np.random.RandomState(21)
+    ce, known = dev(rs.randn(3, 768, T) * 0.5), dev(np.clip(rs.randn(3, 128, T) * 0.5, -1, 1))
+    sched = rt.diff_schedule(sorted(space_timesteps(4000, [N])))
+    plain = rt.diff_sample_ex(ce, seed, sids, sched=sched, sampler=sampler, eta=eta, lens=lens, x_init=None, denorm=False)
+    got = rt.diff_inpaint(known, torch.zeros((3, T), dtype=torch.bool), ce, seed, sids, sched=sched, sampler=sampler, eta=eta, resample=1,
+                          first_step=None, x_init=None, lens=lens)
+    assert bool(torch.isfinite(plain).all()) and float(plain.abs().max()) > 0.1
+    assert torch.equal(got, plain), maxabs(host(got), host(plain))
+
+
 @pytest.mark.parametrize("name,U", PI.CHAINS)
 def test_mixed_mask_keeps_known_and_changes_the_span(synth, S, kw, name, U):
     """kept frames are known's bits, the span differs from the plain loop's and from known, two calls give the same bits, a NaN in the
