@@ -78,6 +78,7 @@ SIGNATURES = {
     "dtts_spectrogram": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "dtts_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "dtts_get_option": (C.c_int, [C.c_void_p, C.c_char_p, c_int_p]),
+    "dtts_uncond_cache_stats": (C.c_int, [C.c_void_p, c_u64_p]),
     "dtts_profile_enable": (C.c_int, [C.c_int]),
     "dtts_profile_sampling": (C.c_int, [C.c_int]),
     "dtts_profile_report": (C.c_int, [C.POINTER(DttsKernelStat), C.c_int]),

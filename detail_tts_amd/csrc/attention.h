@@ -68,6 +68,9 @@ void launch_flash_attention_x3b(const AttnParams& p, hipStream_t stream, AttnX3L
 void set_attn_ksplit(int n);      // key ranges per (sample, head, query block) of attention_x3b launches of <= 2 samples that do not fill the CUs: 1 = off, 2 .. 4 (default: up to 4); process-wide
 void set_attn_ksplit_cus(int n);  // ... split only while workgroups x S <= n (default 256)
 int attn_ksplit();
+// the split-precision launcher's key-split rule (host): the key ranges per (sample, head, query block) of a launch of B samples
+// (1: no split); ksplit_max > 0 caps it.  For callers that must know it before launching (Model::integ_unsplit).
+int attn_x3b_ksplit(int T, int H, int B, int ksplit_max = 0);
 
 // VITS relative-position helpers (vqvae/modules/attentions.py:198-239), W = window (4)
 //   relk[b,h,t,r] = scale * sum_c q[c,t] * Ek[r][c]

@@ -589,26 +589,34 @@ int attn_ksplit() {
     return v;
 }
 
-// operands = AttnPlanes images (p.planes).  Two workgroups per CU: 218 registers; the 1024 workgroups of the headline launch are two
-// full rounds of 512 (three per CU spilled).
-void launch_flash_attention_x3b(const AttnParams& p, hipStream_t stream, AttnX3Launch* chosen) {
-    DTTS_REQUIRE(p.D == 48 && p.bias_tab && !p.causal && !p.band && !p.ml_out && p.planes, "attention_x3b covers head dim 48 with the T5 bias on operand images");
-    constexpr int NW = 4;
-    const int base = cdiv(p.T, NW * QPW) * p.H * p.B;
-    // Key split (round 6): a launch of <= 2 samples (the batch-1 CFG pair, single-sample unit calls) whose (head, sample, 128-query)
-    // workgroups do not even fill the CUs cuts the keys into S ranges, one workgroup each, merged by the last wave to arrive - but only
-    // while base x S workgroups still find a CU each: at T = 936 the pair's 256 workgroups already occupy every CU and a split buys
-    // nothing (measured: batch-1 diffusion 122.8 ms without, 123.4 / 125.9 / 126.8 ms with S = 2 / 3 / 4, profiles/r06_batch1.txt), so
-    // the headline shapes run exactly round 5's launch.  DTTS_ATTN_KSPLIT = the largest S tried (default 4; 1 = off).
+// Key split (round 6): a launch of <= 2 samples (the batch-1 CFG pair, single-sample unit calls) whose (head, sample, 128-query)
+// workgroups do not even fill the CUs cuts the keys into S ranges, one workgroup each, merged by the last wave to arrive - but only
+// while base x S workgroups still find a CU each: at T = 936 the pair's 256 workgroups already occupy every CU and a split buys
+// nothing (measured: batch-1 diffusion 122.8 ms without, 123.4 / 125.9 / 126.8 ms with S = 2 / 3 / 4, profiles/r06_batch1.txt), so
+// the headline shapes run exactly round 5's launch.  DTTS_ATTN_KSPLIT = the largest S tried (default 4; 1 = off).
+constexpr int X3B_NW = 4;            // waves per workgroup
+int attn_x3b_ksplit(int T, int H, int B, int ksplit_max) {
+    constexpr int NW = X3B_NW;
+    const int base = cdiv(T, NW * QPW) * H * B;
     const int ks_env = attn_ksplit();
     static const int ks_maxb = env_int("DTTS_ATTN_KSPLIT_MAXB", 2);
     const int ks_cus = attn_ksplit_cus();
     int S = 1;
-    if (p.B <= ks_maxb && ks_env > 1) {
+    if (B <= ks_maxb && ks_env > 1) {
         S = ks_env;
-        while (S > 1 && ((long long)base * S > ks_cus || AttnPlanes::nt64(p.T) < 2 * S || (size_t)base * S > X3_MAX_SLABS || (size_t)base * NW > X3_SPLIT_COUNTERS)) --S;
+        while (S > 1 && ((long long)base * S > ks_cus || AttnPlanes::nt64(T) < 2 * S || (size_t)base * S > X3_MAX_SLABS || (size_t)base * NW > X3_SPLIT_COUNTERS)) --S;
     }
-    if (p.ksplit_max > 0) S = std::min(S, p.ksplit_max);
+    if (ksplit_max > 0) S = std::min(S, ksplit_max);
+    return S;
+}
+
+// operands = AttnPlanes images (p.planes).  Two workgroups per CU: 218 registers; the 1024 workgroups of the headline launch are two
+// full rounds of 512 (three per CU spilled).
+void launch_flash_attention_x3b(const AttnParams& p, hipStream_t stream, AttnX3Launch* chosen) {
+    DTTS_REQUIRE(p.D == 48 && p.bias_tab && !p.causal && !p.band && !p.ml_out && p.planes, "attention_x3b covers head dim 48 with the T5 bias on operand images");
+    constexpr int NW = X3B_NW;
+    const int base = cdiv(p.T, NW * QPW) * p.H * p.B;
+    const int S = attn_x3b_ksplit(p.T, p.H, p.B, p.ksplit_max);
     AttnParams q = p;
     if (S > 1) {
         q.ksplit = S;

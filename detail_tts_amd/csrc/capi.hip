@@ -209,6 +209,14 @@ int dtts_set_option(dtts_handle* h, const char* key, int value) {
     DTTS_API_END(h)
 }
 
+int dtts_uncond_cache_stats(dtts_handle* h, unsigned long long* out) {
+    DTTS_API_BEGIN
+    if (!out) throw dtts::Error(-2, "dtts_uncond_cache_stats: out is null");
+    const dtts::UncondCacheStats st = h->m->uncond_cache_stats();
+    out[0] = st.entries; out[1] = st.bytes; out[2] = st.hits; out[3] = st.misses; out[4] = st.bypasses; out[5] = st.evictions;
+    DTTS_API_END(h)
+}
+
 int dtts_get_option(dtts_handle* h, const char* key, int* value) {
     DTTS_API_BEGIN
     if (!value) throw dtts::Error(-2, "dtts_get_option: value is null");

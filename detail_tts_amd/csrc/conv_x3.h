@@ -48,6 +48,10 @@ struct ConvX3Launch {
     int epi = -1, kw3 = 0, stages = 0, ksplit = 0, p1 = 0, epi_vec = 0, cols = 0, workgroups = 0;
 };
 void launch_conv_x3(const ConvParams& p, hipStream_t s, ConvX3Launch* chosen = nullptr);
+// the launcher's split-K rule (host): the workgroups per output tile of a launch of B samples x Nout columns (1: no split), decided on
+// the padded tile count; ksplit_max > 0 caps it.  For callers that must know before launching whether a launch's width picks its
+// summation order (Model::integ_unsplit).
+int conv_x3_ksplit(int CoutP, int Cin, int KW, int Nout, int B, int ksplit_max = 0);
 // option "conv_stages" (process-wide): 2 / 3 / 4 forces that many LDS stages, 0 = by launch size (the launcher's rule), n < 0 = back to
 // the initial value (DTTS_CONV_STAGES, else 0)
 void set_conv_stages(int n);

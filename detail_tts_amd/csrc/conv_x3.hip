@@ -1003,6 +1003,21 @@ static long long split_tiles_max() {
     return v;
 }
 
+// split-K: launches of at most 128 tiles (half the CUs: batch 1) divide the channel blocks among up to 4 workgroups per tile
+int conv_x3_ksplit(int CoutP, int Cin, int KW, int Nout, int B, int ksplit_max) {
+    static const int max_split = []() { const int n = env_int("DTTS_CONV_KSPLIT", 4); return n < 1 ? 1 : (n > 8 ? 8 : n); }();
+    int S = 1;
+    // (k = 3: 144 K-steps per tile; the 48 steps of a 1x1 conv barely pay for the exchange: at most 2 there)
+    const long long split_tiles = split_tiles_max();
+    static const long long split_wgs = env_int("DTTS_CONV_KSPLIT_WGS", 256);
+    // (decided on the PADDED tile count: a column table must not change the summation order of a launch)
+    const long long ntile_pad = (long long)(CoutP / BM) * cdiv(Nout, BN) * B;
+    static const int max_split_k1 = env_int("DTTS_CONV_KSPLIT_K1", 2);
+    if (ntile_pad <= split_tiles) S = (int)std::min<long long>(std::min<long long>(KW == 3 ? max_split : std::min(max_split, max_split_k1), split_wgs / ntile_pad), (Cin >> 4) / 8);
+    if (ksplit_max > 0) S = std::min(S, ksplit_max);
+    return S < 1 ? 1 : S;
+}
+
 // option "conv_stages" / DTTS_CONV_STAGES (process-wide, like conv_small_tiles): the number of LDS stages of every conv_x3 launch
 static int conv_stages_default() {
     static const int v = []() { const int n = (int)env_int("DTTS_CONV_STAGES", 0); return n >= 2 && n <= 4 ? n : 0; }();
@@ -1039,18 +1054,7 @@ void launch_conv_x3(const ConvParams& p_in, hipStream_t s, ConvX3Launch* chosen)
     static const long long max4 = env_int("DTTS_CONV_STAGES4_MAXWG", 128);
     DTTS_REQUIRE(!p.cols || (p.ncols > 0 && p.ncols <= cdiv(p.Nout, BN) * p.B && cdiv(p.Nout, BN) < 256), "conv_x3: column table");
     const long long ntile = (long long)(p.CoutP / BM) * (p.cols ? p.ncols : cdiv(p.Nout, BN) * p.B);
-    // split-K: launches of at most 128 tiles (half the CUs: batch 1) divide the channel blocks among up to 4 workgroups per tile
-    static const int max_split = []() { const int n = env_int("DTTS_CONV_KSPLIT", 4); return n < 1 ? 1 : (n > 8 ? 8 : n); }();
-    int S = 1;
-    // (k = 3: 144 K-steps per tile; the 48 steps of a 1x1 conv barely pay for the exchange: at most 2 there)
-    const long long split_tiles = split_tiles_max();
-    static const long long split_wgs = env_int("DTTS_CONV_KSPLIT_WGS", 256);
-    // (decided on the PADDED tile count: a column table must not change the summation order of a launch)
-    const long long ntile_pad = (long long)(p.CoutP / BM) * cdiv(p.Nout, BN) * p.B;
-    static const int max_split_k1 = env_int("DTTS_CONV_KSPLIT_K1", 2);
-    if (ntile_pad <= split_tiles) S = (int)std::min<long long>(std::min<long long>(p.KW == 3 ? max_split : std::min(max_split, max_split_k1), split_wgs / ntile_pad), (p.Cin >> 4) / 8);
-    if (p.ksplit_max > 0) S = std::min(S, p.ksplit_max);
-    if (S < 1) S = 1;
+    const int S = conv_x3_ksplit(p.CoutP, p.Cin, p.KW, p.Nout, p.B, p.ksplit_max);
     p.ksplit = S;
     static const bool epi_vec_on = env_on("DTTS_X3_EPI_VEC");
     auto al16 = [](const void* q, long long bs, int cs) { return (reinterpret_cast<unsigned long long>(q) & 15ull) == 0 && (bs & 3) == 0 && (cs & 3) == 0; };

@@ -2,6 +2,7 @@
 // Everything here enqueues work on the caller's HIP stream; no hidden synchronisation except
 // workspace growth (hipMalloc) which only happens when a call needs more memory than any before it, and the schedule cache
 // (diff_schedule: hipMalloc of a new schedule's tables; an eviction waits for the last launch that read the evicted tables).
+// The unconditional code-path cache (option uncond_cache_mb) allocates its one block at the first sampling call that can use it.
 #pragma once
 #include <map>
 #include <memory>
@@ -25,6 +26,7 @@
 #include "flowvae_fwd.h"
 #include "gpt_kernels.h"
 #include "ops.h"
+#include "uncond_cache.h"
 #include "../../include/detail_hip.h"
 
 namespace dtts {
@@ -488,6 +490,7 @@ public:
         else if (key == "gpt_beam_skip_reorder") { opt_beam_skip_reorder_ = value != 0; gpt_drop_graphs(); }
         else if (key == "cfg_streams") opt_cfg_streams_ = value < 0 ? 0 : value;
         else if (key == "conv_cols") opt_conv_cols_ = value != 0;
+        else if (key == "uncond_cache_mb") set_uncond_cache_mb(value);      // budget of the unconditional code-path cache; 0 = off, its block freed
         else if (key == "voc_chain_planes") opt_voc_chain_ = value != 0;
         else if (key == "voc_x3") opt_voc_x3_ = value != 0;                 // 0: stage C on the exact fp32 kernels only (the trunk keeps conv_x3's choice)
         else if (key == "x3_fault") opt_x3_fault_ = value;                  // test hook: the n-th stage-C ticket from now on is raised as saturated
@@ -620,30 +623,39 @@ private:
     PairPlan plan_pair(const int* lens_host, int B, int T, hipStream_t s);
     // cbuf0: [B + Nu, C, T] = B conditional code embeddings followed by Nu unconditional inputs (one per distinct length)
     // integ (optional): [B + Nu, C, T] code-path terms P = W_integ2 . conditioning_timestep_integrator(cbuf0) of this step (precompute_integrator)
+    // umap (optional, with integ): this step's [2B] code-path sample indices in place of pl.umap (CodePathTable::umap_at)
     void diff_forward_pair(const Schedule& sc, const float* x, const float* cbuf0, const PairPlan& pl, int B, int T, int step, float* out2,
-                           hipStream_t s, const float* integ = nullptr);
+                           hipStream_t s, const float* integ = nullptr, const int* umap = nullptr);
     // The integrator sees (code embedding | unconditioned embedding, timestep) only - never x_t - so its output for every sampling
     // step, and the code half of integrating_conv on it, is known before the loop starts: steps are evaluated J at a time as one batch of
     // J*(B+Nu) samples, each at its own step; the step-invariant front of its first ResBlock once.  lens_i: plan_pair's (device).
+    // J (0: integ_chunk(B + Nu)): the steps per launch, for a caller that evaluates fewer unconditional rows than the call has lengths
+    // and keeps the call's launch boundaries (code_path_table)
     void precompute_integrator(const Schedule& sc, const float* cbuf0, const int* lens_i, const int* lens_i_host, int B, int Nu, int T,
-                               const std::vector<int>& steps, float* integ_all, hipStream_t s);
+                               const std::vector<int>& steps, float* integ_all, hipStream_t s, int J = 0);
     // what the entry points around one diff_forward_pair share: the workspace sized for the call (+ extra_bytes, + hist_floats), the plan,
     // the sample ids (optional), cbuf0 = (code_emb, or the unconditioned embedding when null | unconditional inputs), out2 [2B, OC, T]
     // and the DPM-Solver++ history [hist_floats].  On top of it the sampling entries share, each written once (model_diffusion.hip):
     // draw_x_T, code_path_table (the table's launch rule), sampler_update (the ten strided-tensor arguments of every update kernel),
     // sample_loop (the descending loop of diff_sample_ex / diff_sample_from / diff_inpaint) and single_step (diff_step, diff_step_dpm,
     // diff_reverse_step, diff_mean_variance); diff_invert keeps its own short ascending loop on the same pieces.
-    struct PairCall { PairPlan pl; const int* sids; float *cbuf0, *out2, *hist; };
+    // defer_uncond: the unconditional inputs are left to code_path_table, which fills only the rows it evaluates
+    struct PairCall { PairPlan pl; const int* sids; float *cbuf0, *out2, *hist; bool uncond_deferred; };
     PairCall begin_pair(const float* code_emb, const int* lens_host, const int* sample_ids_host, int B, int T, hipStream_t s,
-                        size_t extra_bytes = 0, size_t hist_floats = 0);
+                        size_t extra_bytes = 0, size_t hist_floats = 0, bool defer_uncond = false);
     // x_T into x [B,128,T]: Philox normals per row over its own [128, len] (pc.out2 is the compact scratch of a short row)
     void draw_x_T(float* x, const PairCall& pc, const int* lens_host, int B, int T, unsigned long long seed, hipStream_t s);
     // precompute_integrator's output for loop positions k0 .. : at(k) = position k's [B + Nu, C, T] terms (null without a table)
+    // With rows served by the unconditional cache the block is [n][B + Nm] evaluated rows followed by one [n] slab per served length,
+    // and umap [n][2B] holds every position's sample indices relative to at(k) (null: pl.umap, every row evaluated).
     struct CodePathTable {
         float* base = nullptr;
         int k0 = 0;
         size_t stride = 0;
+        const int* umap = nullptr;
+        int umap_stride = 0;
         const float* at(int k) const { return base ? base + (size_t)(k - k0) * stride : nullptr; }
+        const int* umap_at(int k) const { return umap ? umap + (size_t)(k - k0) * umap_stride : nullptr; }
     };
     CodePathTable code_path_table(const Schedule& sc, const PairCall& pc, int B, int T, int k_first, int k_end, bool descending, bool pinned,
                                   hipStream_t s);
@@ -771,6 +783,26 @@ private:
                                           // same launches issued eagerly on ROCm 7.2 / MI355X: DESIGN.md section 4)
 
     bool opt_two_streams_ = true;
+    // The unconditional code-path cache (uncond_cache.h): slabs P[n][C][T] of one (binding, schedule, length, width) in
+    // one device block, produced on one call's stream and read on another's - `ready` is recorded behind the copy that fills a slot,
+    // `read` behind every copy out of it; a slot is reused only once both have completed (queried, never waited for on the host).
+    struct UcacheEvents { hipEvent_t ready = nullptr, read = nullptr; };
+    std::mutex ucache_mu_;
+    UncondCacheBook ucache_;             // its budget is set when the block is allocated, at first use
+    char* ucache_mem_ = nullptr;
+    std::vector<UcacheEvents> ucache_ev_;   // by slot
+    size_t ucache_want_ = 0;             // option "uncond_cache_mb" in bytes (constructor: DTTS_UNCOND_CACHE_MB, default 4096)
+    unsigned long long bind_gen_ = 0;    // bind_weights calls so far
+    void set_uncond_cache_mb(int mb);
+    void ucache_release();               // waits for the slots' events, frees the block, empties the book
+    bool ucache_slot_busy(int slot);
+    // May the cache serve / keep rows of this pre-pass?  Only where NO launch of it - with every unconditional row present (Bi_hi
+    // samples per step) and with none (Bi_lo) - takes conv split-K or the attention's key split: there alone a row's bits do not depend
+    // on what shares its launch.  n_pos steps in launches of J.
+    bool integ_unsplit(int Bi_lo, int Bi_hi, int T, int n_pos, int J) const;
+public:
+    UncondCacheStats uncond_cache_stats();
+private:
     int prof_rot_ = 0;               // precompute_integrator calls so far: rotates the chunk pairs the profiler brackets
     bool opt_voc_x3_ = true;         // stage C's split-precision kernels (ResBlock1 convs, WaveNet in_layers); 0 = exact fp32 (cannot saturate)
     int opt_x3_fault_ = 0;           // test hook (option x3_fault)

@@ -43,10 +43,15 @@ void* Arena::raw(size_t bytes) {
 
 // ------------------------------------------------------------------------------------------ Model
 static constexpr size_t INT_RING_BYTES = 1u << 20;      // per issuing thread
-Model::Model(const dtts_config& c, int dev) : cfg(c), device(dev) { DTTS_CHECK_HIP(hipSetDevice(dev)); }
+Model::Model(const dtts_config& c, int dev) : cfg(c), device(dev) {
+    DTTS_CHECK_HIP(hipSetDevice(dev));
+    const long long mb = env_int("DTTS_UNCOND_CACHE_MB", 4096);
+    ucache_want_ = (size_t)(mb < 0 ? 0 : mb) << 20;
+}
 
 Model::~Model() {
     gpt_drop_graphs();
+    try { ucache_release(); } catch (...) {}
     if (x3_sat_) (void)hipHostFree(x3_sat_);
     for (auto& kv : int_rings_) {
         IntRing& r = *kv.second;
@@ -247,6 +252,11 @@ void Model::bind_weights(const void* blob, size_t nbytes, const char* const* nam
                          const unsigned long long* numels, int n, hipStream_t stream) {
     weights_.clear();
     bound_ = false;
+    {   // a new generation of weights: nothing cached under the old one is served again (uncond_cache.h)
+        std::lock_guard<std::mutex> lk(ucache_mu_);
+        ++bind_gen_;
+        ucache_.invalidate_all();
+    }
     for (int i = 0; i < n; ++i) {
         DTTS_REQUIRE((offsets[i] + numels[i]) * sizeof(float) <= nbytes, "weight table entry outside the blob");
         DTTS_REQUIRE(offsets[i] % 4 == 0, "weight offsets must be 16-byte aligned");

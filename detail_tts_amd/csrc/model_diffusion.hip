@@ -422,8 +422,9 @@ Model::PairPlan Model::plan_pair(const int* lens_host, int B, int T, hipStream_t
 // table; without it (diff_step, diff_forward*, a table beyond DTTS_INTEG_MAX_GB) the integrator and one integ2_ launch over its
 // B + Nu outputs run here first.
 void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* cbuf0, const PairPlan& pl, int B, int T, int step, float* out2,
-                              hipStream_t s, const float* integ) {
+                              hipStream_t s, const float* integ, const int* umap) {
     const int C = cfg.diff_channels, Ta = T, OC = cfg.diff_out_channels, MC = cfg.mel_channels, Nu = pl.Nu;
+    if (!umap || !integ) umap = pl.umap;
     const int *lens2 = pl.lens2, *lens_i = pl.lens_i;
     const long long bs = (long long)C * Ta;
     static const bool env_two = env_on("DTTS_TWO_STREAMS");
@@ -495,7 +496,7 @@ void Model::diff_forward_pair(const Schedule& sc, const float* x, const float* c
         r.pad = 1;
         r.x_bidx = pl.xmap + b0;                       // x_t of stack sample b: (b0 + b) % B
         with_res(r, P, bs, Ta);
-        r.res_bidx = pl.umap + b0;                     // code-path sample of stack sample b (uncond samples share one per length)
+        r.res_bidx = umap + b0;                        // code-path sample of stack sample b (uncond samples share one per length)
         if (x3) with_planes(r, xs0, T);
         run_conv(xpath_, r, st);
         // main stack (:299-309)
@@ -634,8 +635,8 @@ static int integ_chunk(int Bi) {     // steps per batched evaluation (~36 sample
 }
 
 void Model::precompute_integrator(const Schedule& sc, const float* cbuf0, const int* lens_i, const int* lens_i_host, int B, int Nu, int T,
-                                  const std::vector<int>& steps, float* integ_all, hipStream_t s) {
-    const int C = cfg.diff_channels, Bi = B + Nu, J = integ_chunk(Bi), NS = (int)steps.size();
+                                  const std::vector<int>& steps, float* integ_all, hipStream_t s, int J_call) {
+    const int C = cfg.diff_channels, Bi = B + Nu, J = J_call > 0 ? J_call : integ_chunk(Bi), NS = (int)steps.size();
     const size_t ct = (size_t)C * T, mark = ws().mark();
     const int Bv = J * Bi;
     const bool x3 = use_x3();
@@ -719,7 +720,7 @@ static size_t pair_ws_bytes(int B, int C, int MC, int T) {
 }
 
 Model::PairCall Model::begin_pair(const float* code_emb, const int* lens_host, const int* sample_ids_host, int B, int T, hipStream_t s,
-                                  size_t extra_bytes, size_t hist_floats) {
+                                  size_t extra_bytes, size_t hist_floats, bool defer_uncond) {
     const int C = cfg.diff_channels, OC = cfg.diff_out_channels;
     const size_t half = (size_t)B * C * T;
     ws().ensure(pair_ws_bytes(B, C, cfg.mel_channels, T) + extra_bytes + sizeof(float) * (2 * half + (size_t)2 * B * OC * T + hist_floats) + 8192);
@@ -730,7 +731,8 @@ Model::PairCall Model::begin_pair(const float* code_emb, const int* lens_host, c
     pc.out2 = ws().f32((size_t)2 * B * OC * T);
     pc.hist = hist_floats ? ws().f32(hist_floats) : nullptr;
     if (code_emb) DTTS_CHECK_HIP(hipMemcpyAsync(pc.cbuf0, code_emb, sizeof(float) * half, hipMemcpyDeviceToDevice, s));
-    for (int h = code_emb ? 1 : 0; h < 2; ++h)          // the unconditional inputs; without a code embedding the conditional half too
+    pc.uncond_deferred = defer_uncond;
+    for (int h = code_emb ? 1 : 0; h < (defer_uncond ? 1 : 2); ++h)   // the unconditional inputs; without a code embedding the conditional half too
         launch_broadcast_channels(uncond_, h ? pc.pl.Nu : B, C, T, pc.cbuf0 + h * half, (long long)C * T, T, s);
     return pc;
 }
@@ -775,6 +777,8 @@ void Model::draw_x_T(float* x, const PairCall& pc, const int* lens_host, int B, 
 // evaluates J = integ_chunk steps per launch from position 0: the table then starts at the launch that holds k_first, unneeded steps
 // included (at most J - 1), so a loop entered anywhere reads the bits the whole loop reads.  Pinned (RowInvariantLaunches), a row is the
 // same bits whatever shares its launch, and the table starts at k_first.
+// Unpinned and outside every split regime the unconditional rows come from the per-Model cache where it holds them (DESIGN.md 4.5
+// item 4): only the others are evaluated, in the launches the uncached call makes.
 Model::CodePathTable Model::code_path_table(const Schedule& sc, const PairCall& pc, int B, int T, int k_first, int k_end, bool descending,
                                             bool pinned, hipStream_t s) {
     const PairPlan& pl = pc.pl;
@@ -787,8 +791,180 @@ Model::CodePathTable Model::code_path_table(const Schedule& sc, const PairCall& 
     t.base = ws().f32(steps.size() * t.stride);
     std::optional<RowInvariantLaunches> pin;
     if (pinned) pin.emplace();
-    precompute_integrator(sc, pc.cbuf0, pl.lens_i, pl.lens_i_host.data(), B, pl.Nu, T, steps, t.base, s);
+    const int C = cfg.diff_channels, Nu = pl.Nu, n = (int)steps.size();
+    const size_t ct = (size_t)C * T, slab = sizeof(float) * n * ct;
+    auto fill_uncond = [&](int rows) {                                    // begin_pair left the unconditional inputs to this call
+        if (pc.uncond_deferred && rows > 0) launch_broadcast_channels(uncond_, rows, C, T, pc.cbuf0 + (size_t)B * ct, (long long)ct, T, s);
+    };
+    // ---- the unconditional rows from the cache (uncond_cache.h).  Off (budget 0): every row evaluated, nothing counted.  It stands
+    // aside - counted - on the exact fp32 kernels, under RowInvariantLaunches (pinned entries neither read nor write it), for a table
+    // that does not start at position 0 of a descending loop, and wherever a launch's width picks a summation order (integ_unsplit):
+    // a hit must be the miss's bits.  (n * 2B: the per-position index table must fit one upload.)
+    bool use = false;
+    if (ucache_want_ > 0) {
+        use = use_x3() && !pinned && !RowInvariantLaunches::on() && descending && t.k0 == 0 && (size_t)n * 2 * B <= 32768 &&
+              integ_unsplit(B, Bi, T, n, J);
+        std::lock_guard<std::mutex> lk(ucache_mu_);
+        if (use && !ucache_mem_) {                                        // first use: the one allocation
+            if (hipMalloc(reinterpret_cast<void**>(&ucache_mem_), ucache_want_) == hipSuccess) {
+                ucache_.set_budget(ucache_want_);
+            } else {                                                      // no room for the budget: the cache stays off, the call goes on
+                (void)hipGetLastError();
+                ucache_mem_ = nullptr;
+                ucache_want_ = 0;
+                use = false;
+            }
+        }
+        if (!use) ucache_.count_bypass();
+    }
+    if (!use) {
+        fill_uncond(Nu);
+        precompute_integrator(sc, pc.cbuf0, pl.lens_i, pl.lens_i_host.data(), B, Nu, T, steps, t.base, s);
+        return t;
+    }
+    // (trunk_fp16 is not in the key: the integrator always takes three products)
+    UncondKey key;
+    key.sched_id = sc.id;
+    key.kind = sc.kind;
+    key.tmap = sc.tmap;
+    key.ftimes = sc.ftimes;
+    key.n_pos = n;
+    key.T = T;
+    const int* ulen = pl.lens_i_host.data() + B;                          // the Nu distinct lengths
+    std::vector<int> miss, slot_of(Nu, -1), served_of(Nu, -1), row_of(Nu, -1);   // g -> its slot | its slab behind the evaluated rows | its evaluated row
+    std::vector<size_t> off_of(Nu, 0);
+    int Nh = 0;
+    {
+        std::lock_guard<std::mutex> lk(ucache_mu_);
+        key.bind_gen = bind_gen_;
+        for (int g = 0; g < Nu; ++g) {
+            key.len = ulen[g];
+            if (const UncondCacheBook::Entry* e = ucache_.lookup(key)) { slot_of[g] = e->slot; off_of[g] = e->off; ++Nh; }
+            else { row_of[g] = B + (int)miss.size(); miss.push_back(g); }
+        }
+        // the served slabs into the block, behind the rows this call evaluates: [n][B + Nm][C][T] | Nh x [n][C][T].  Enqueued under the
+        // lock, so no insert can take a slot between its lookup and the `read` record that marks it busy.  A reader first waits for
+        // the reader before it: `read`, re-recorded by every reader, then completes only when all of them have.
+        const int Bc = B + (int)miss.size();
+        float* served = t.base + (size_t)n * Bc * ct;
+        for (int g = 0, h = 0; g < Nu; ++g) {
+            if (slot_of[g] < 0) continue;
+            const UcacheEvents& ev = ucache_ev_[(size_t)slot_of[g]];
+            DTTS_CHECK_HIP(hipStreamWaitEvent(s, ev.ready, 0));
+            DTTS_CHECK_HIP(hipStreamWaitEvent(s, ev.read, 0));
+            DTTS_CHECK_HIP(hipMemcpyAsync(served + (size_t)h * n * ct, ucache_mem_ + off_of[g], slab, hipMemcpyDeviceToDevice, s));
+            DTTS_CHECK_HIP(hipEventRecord(ev.read, s));
+            served_of[g] = h++;
+        }
+    }
+    const int Nm = (int)miss.size(), Bc = B + Nm;
+    if (Nh > 0) {
+        // position k reads its rows relative to at(k) = base + k Bc ct: evaluated row r at r, served slab h's row at n Bc + h n + k - k Bc
+        t.stride = (size_t)Bc * ct;
+        std::vector<int> um((size_t)n * 2 * B);
+        for (int k = 0; k < n; ++k)
+            for (int b = 0; b < B; ++b) {
+                const int g = (int)(std::find(ulen, ulen + Nu, pl.lens_i_host[(size_t)b]) - ulen);    // row b's length among the distinct ones
+                um[(size_t)k * 2 * B + b] = b;
+                um[(size_t)k * 2 * B + B + b] = row_of[g] >= 0 ? row_of[g] : n * Bc + served_of[g] * n + k - k * Bc;
+            }
+        t.umap = upload_ints(um.data(), (int)um.size(), s);
+        t.umap_stride = 2 * B;
+    }
+    // the rows left to evaluate: the B conditional ones and the Nm missing lengths, in launches of the CALL's J steps - launch count,
+    // chunk boundaries and lane alternation stay those of the uncached call; launches only cover fewer samples
+    fill_uncond(Nm);
+    if (Nm == Nu) {
+        precompute_integrator(sc, pc.cbuf0, pl.lens_i, pl.lens_i_host.data(), B, Nu, T, steps, t.base, s, J);
+    } else {
+        std::vector<int> li(pl.lens_i_host.begin(), pl.lens_i_host.begin() + B);
+        for (int g : miss) li.push_back(ulen[g]);
+        const int* dli = upload_ints(li.data(), Bc, s);
+        register_cols(dli, li.data(), Bc, T, s);
+        precompute_integrator(sc, pc.cbuf0, dli, li.data(), B, Nm, T, steps, t.base, s, J);
+        register_cols(dli, nullptr, 0, T, s);
+    }
+    // after a miss: the new slabs into the cache on this call's stream (rows B + m of every position), `ready` behind each copy
+    if (Nm > 0) {
+        std::lock_guard<std::mutex> lk(ucache_mu_);
+        if (ucache_mem_ && key.bind_gen == bind_gen_)
+            for (int m = 0; m < Nm; ++m) {
+                key.len = ulen[miss[(size_t)m]];
+                const UncondCacheBook::Entry* e = ucache_.insert(key, slab, [this](int slot) { return ucache_slot_busy(slot); });
+                if (!e) continue;                                         // larger than the budget, or every candidate slot still busy
+                if ((size_t)e->slot >= ucache_ev_.size()) ucache_ev_.resize((size_t)e->slot + 1);
+                UcacheEvents& ev = ucache_ev_[(size_t)e->slot];
+                if (!ev.ready) {
+                    DTTS_CHECK_HIP(hipEventCreateWithFlags(&ev.ready, hipEventDisableTiming));
+                    DTTS_CHECK_HIP(hipEventCreateWithFlags(&ev.read, hipEventDisableTiming));
+                }
+                for (int k = 0; k < n; ++k)
+                    DTTS_CHECK_HIP(hipMemcpyAsync(ucache_mem_ + e->off + sizeof(float) * k * ct, t.base + ((size_t)k * Bc + B + m) * ct,
+                                                  sizeof(float) * ct, hipMemcpyDeviceToDevice, s));
+                DTTS_CHECK_HIP(hipEventRecord(ev.ready, s));
+            }
+    }
     return t;
+}
+
+bool Model::integ_unsplit(int Bi_lo, int Bi_hi, int T, int n_pos, int J) const {
+    const bool planes = integ_[0].at.C / integ_[0].at.H == AttnPlanes::D;   // else the fp32 attention, which never splits its keys
+    auto conv1 = [&](const PackedConv& c, int nb) { return conv_x3_ksplit(c.CoutP, c.Cin, c.KW, T, nb) == 1; };
+    for (int Bi : {Bi_lo, Bi_hi}) {
+        if (!conv1(integ_[0].rb.c1, Bi)) return false;                        // layer 0's front: once, on the Bi inputs
+        for (int jn : {std::min(J, n_pos), n_pos % J}) {                      // the full launches | the narrower last one
+            if (jn == 0) continue;
+            const int nb = jn * Bi;
+            for (size_t l = 0; l < integ_.size(); ++l) {
+                const DiffLayerW& L = integ_[l];
+                if (l > 0 && !conv1(L.rb.c1, nb)) return false;
+                if (!conv1(L.rb.c2, nb) || !conv1(L.at.qkv, nb) || !conv1(L.at.proj, nb)) return false;
+                if (planes && attn_x3b_ksplit(T, L.at.H, nb) != 1) return false;
+            }
+            if (!conv1(integ2_, nb)) return false;
+        }
+    }
+    return true;
+}
+
+bool Model::ucache_slot_busy(int slot) {
+    if ((size_t)slot >= ucache_ev_.size() || !ucache_ev_[(size_t)slot].ready) return false;
+    for (hipEvent_t e : {ucache_ev_[(size_t)slot].ready, ucache_ev_[(size_t)slot].read}) {
+        const hipError_t r = hipEventQuery(e);
+        if (r == hipErrorNotReady) return true;
+        DTTS_CHECK_HIP(r);
+    }
+    return false;
+}
+
+void Model::ucache_release() {
+    std::lock_guard<std::mutex> lk(ucache_mu_);
+    for (UcacheEvents& ev : ucache_ev_)
+        for (hipEvent_t* e : {&ev.ready, &ev.read})
+            if (*e) {
+                (void)hipEventSynchronize(*e);
+                (void)hipEventDestroy(*e);
+                *e = nullptr;
+            }
+    ucache_ev_.clear();
+    if (ucache_mem_) (void)hipFree(ucache_mem_);
+    ucache_mem_ = nullptr;
+    ucache_.set_budget(0);                                                // (drops the entries; the counters live on)
+}
+
+// option "uncond_cache_mb": not a launch path - a change waits for the copies in flight, frees the block, and the next call that can
+// use the cache allocates the new budget.  0 = off.
+void Model::set_uncond_cache_mb(int mb) {
+    DTTS_REQUIRE(mb >= 0, "uncond_cache_mb: megabytes >= 0");
+    const size_t want = (size_t)mb << 20;
+    if (want == ucache_want_ && (!ucache_mem_ || ucache_.budget() == want)) return;
+    ucache_release();
+    ucache_want_ = want;
+}
+
+UncondCacheStats Model::uncond_cache_stats() {
+    std::lock_guard<std::mutex> lk(ucache_mu_);
+    return ucache_.stats();
 }
 
 // one sampler update on the forward's output pc.out2, x in place: p_sample (0), ddim_sample (1), DPM-Solver++(2M) (2: x0_hist) or
@@ -819,8 +995,10 @@ void Model::sample_loop(Schedule& sc, const SampleLoop& c, const float* code_emb
     const int C = cfg.diff_channels, MC = cfg.mel_channels;
     const size_t plane = (size_t)B * MC * T;
     const bool fits = integ_table_fits(c.k_end, B, C, T);
+    // (with a table and the unconditional cache on, code_path_table fills the unconditional inputs: only the rows it evaluates)
     const PairCall pc = begin_pair(code_emb, lens_host, sample_ids_host, B, T, s, fits ? integ_call_bytes(c.k_end, B, C, T) : 0,
-                                   c.sampler == 2 ? plane : 0);               // DPM-Solver++(2M): the previous step's x0
+                                   c.sampler == 2 ? plane : 0,                // DPM-Solver++(2M): the previous step's x0
+                                   fits && ucache_want_ > 0 && use_x3() && !RowInvariantLaunches::on());
     if (!x_init)
         draw_x_T(x, pc, lens_host, B, T, seed, s);
     else if (x != x_init)
@@ -833,7 +1011,7 @@ void Model::sample_loop(Schedule& sc, const SampleLoop& c, const float* code_emb
         for (int r = 0; r < reps; ++r, ++e) {
             Profiler::gate() = (e % Profiler::get().step_every) == 0;
             ws().rewind(mark);                              // the forward's scratch is re-carved every evaluation
-            diff_forward_pair(sc, x, pc.cbuf0, pc.pl, B, T, i, pc.out2, s, tab.at(k));
+            diff_forward_pair(sc, x, pc.cbuf0, pc.pl, B, T, i, pc.out2, s, tab.at(k), tab.umap_at(k));
             const int pstep = i + r * sc.n;
             sampler_update(sc, pc, x, B, T, c.sampler, c.eta, i, seed, pstep, c.step_noise ? c.step_noise + e * plane : nullptr,
                            (c.denorm && k == c.k_end - 1) ? 1 : 0, s, nullptr, pc.hist);

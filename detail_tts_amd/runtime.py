@@ -127,6 +127,12 @@ class Runtime:
         self._rc(self.lib.dtts_get_option(self.h, key.encode(), C.byref(v)))
         return int(v.value)
 
+    def uncond_cache_stats(self):
+        """the unconditional code-path cache (option "uncond_cache_mb"): entries, bytes, hits, misses, bypasses, evictions"""
+        out = np.zeros(6, np.uint64)
+        self._rc(self.lib.dtts_uncond_cache_stats(self.h, out.ctypes.data_as(_lib.c_u64_p)))
+        return dict(zip(("entries", "bytes", "hits", "misses", "bypasses", "evictions"), (int(v) for v in out)))
+
     def profile_enable(self, on=True):
         """True / 1: MFMA kernels; 2: also the bandwidth-only helper kernels; False: off"""
         self.lib.dtts_profile_enable(int(on))

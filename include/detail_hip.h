@@ -794,12 +794,25 @@ int dtts_spectrogram(dtts_handle* h, const float* wav, const int* lens, int B, i
  *                 embedding / AdaGN tables and the out conv keep the three-product kernels; GroupNorm,
  *                 softmax, residual adds and every activation between kernels stay fp32.  All samplers, any step count.  Refused with
  *                 conv_x3 = 0 (the exact fp32 kernels have no such mode), and conv_x3 = 0 is refused while it is 1.  A launch-time
- *                 kernel choice: the captured graphs (stage A's decode graphs) hold no trunk launch, none is dropped.
+ *                 kernel choice: the captured graphs (stage A's decode graphs) hold no trunk launch, none is dropped;
+ *   "uncond_cache_mb" (default 4096; env DTTS_UNCOND_CACHE_MB): byte budget, in MiB, of the unconditional code-path cache.  The
+ *                 unconditional rows of the code-path table of a sampling loop depend on the bound weights, the schedule and the
+ *                 length only - on nothing of the request - so their [steps][768][T] slab is kept on the device per (binding, schedule,
+ *                 steps, length, padded width T) and the next call with that length evaluates only its conditional rows.  ONE device
+ *                 allocation of the whole budget at the first call that can use it (none if that fails: the cache stays off); a slab
+ *                 is 4 steps 768 T bytes (144 MB at 50 steps x 10 s), least recently used slabs make room, a slab larger than the
+ *                 budget is not kept.  A served call is bit-identical to an unserved one: the cache stands aside (counted as a bypass)
+ *                 wherever a launch's width chooses a summation order (conv split-K, attention key split: small batches x short
+ *                 rows), on conv_x3 = 0, in dtts_diff_invert / _reverse_step / _calc_bpd, and for dtts_diff_sample_from entered below
+ *                 the first launch.  A change waits for the copies in flight and frees the block; 0 = off.
  * Any other key fails with -1 "unknown option" - also the keys of the two experiments that earlier versions carried and that were
  * removed with their code: the fused-GroupNorm conv epilogue and the pipelined integrator chunks (DESIGN_APPENDIX.md 4.3, 4.5). */
 int dtts_set_option(dtts_handle* h, const char* key, int value);
 /* Reads back "conv_x3" (1 only if DTTS_CONV_X3 does not disable it), "trunk_fp16" or "gpt_fuse_proj": what a caller needs to restore after a per-call override. */
 int dtts_get_option(dtts_handle* h, const char* key, int* value);
+/* The unconditional code-path cache (option "uncond_cache_mb") since the handle was created: out[6] = live entries, their bytes, rows
+ * served (hits), rows evaluated and offered to the cache (misses), calls that stood aside (bypasses), entries given up (evictions). */
+int dtts_uncond_cache_stats(dtts_handle* h, unsigned long long* out);
 
 /* ---- measurement ---------------------------------------------------------------------------------------------- */
 /* Per-launch hipEvent profiling of the MFMA kernels (conv GEMM, flash attention), recorded on the launch stream.
