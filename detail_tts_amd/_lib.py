@@ -114,6 +114,9 @@ SIGNATURES = {
     "dtts_gpt_forward_losses": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, c_int_p, C.c_int, c_int_p, C.c_int, C.c_int, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dtts_voice_pool": (C.c_int, [C.c_void_p, C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dtts_wav_edges": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    "dtts_wav_join": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, C.c_longlong, C.c_int, C.c_void_p,
+                                C.c_void_p]),
     "dtts_gpt_generate_cond": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, C.c_int, C.POINTER(DttsGptOptions), c_int_p, c_int_p,
                                          C.c_void_p, C.c_int, C.c_void_p]),
     "dtts_gpt_prefill_cond": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, c_int_p, C.c_int, C.c_int, C.POINTER(DttsGptOptions), C.c_void_p,

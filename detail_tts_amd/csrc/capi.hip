@@ -563,6 +563,20 @@ int dtts_voice_pool(dtts_handle* h, const float* v, const float* weights, int S,
     DTTS_API_END(h)
 }
 
+int dtts_wav_edges(dtts_handle* h, const float* wav, const int* lens, int B, int stride, int frame, float threshold, int keep, int* edges,
+                   void* stream) {
+    DTTS_API_BEGIN
+    h->m->wav_edges(wav, lens, B, stride, frame, threshold, keep, edges, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_wav_join(dtts_handle* h, const float* wav, int B, int stride, const int* begins, const int* counts, const int* offsets,
+                  long long total, int fade, float* out, void* stream) {
+    DTTS_API_BEGIN
+    h->m->wav_join(wav, B, stride, begins, counts, offsets, total, fade, out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
 int dtts_diff_conditioning(dtts_handle* h, const float* refer, const int* lens, int B, int Tmax, float* cond_out, void* stream) {
     DTTS_API_BEGIN
     h->m->diff_conditioning(refer, lens, B, Tmax, cond_out, (hipStream_t)stream);

@@ -309,6 +309,10 @@ public:
                        const int* sample_ids_host, const float* noise, float* x0_out, hipStream_t s);
     // ---- voices (voice.hip): out [S, D] = sum_j w[s][j] v[s, j, :] / sum_j w[s][j] over the n clips of speaker s; w_host nullptr = all 1
     void voice_pool(const float* v, const float* w_host, int S, int n, int D, float* out, hipStream_t s);
+    // ---- long form (wav_join.hip): the loud span of every row of a padded waveform batch, and the rows' spans laid end to end
+    void wav_edges(const float* wav, const int* lens_host, int B, int stride, int frame, float threshold, int keep, int* edges, hipStream_t s);
+    void wav_join(const float* wav, int B, int stride, const int* begins, const int* counts, const int* offsets, long long total, int fade,
+                  float* out, hipStream_t s);
     // ---- stage A
     // Every stage-A entry that takes the prompt mel `refer` also takes cond_in [B, gpt_dim] (device): the conditioning encoder's output,
     // computed earlier (a voice, voice.hip).  With cond_in the encoder is not launched and refer / refer_lens_host / Tr are not read.

@@ -561,6 +561,42 @@ class Runtime:
                                           self._stream()))
         return out
 
+    # ------------------------------------------------------------------ long form
+    @staticmethod
+    def _wav_rows(wav, who):
+        """a padded waveform batch, [B, stride] or stage C's [B, 1, stride] -> (its [B, stride] view, B, stride)"""
+        _check(wav, "wav")
+        if wav.dim() == 3 and wav.shape[1] == 1:
+            wav = wav.view(wav.shape[0], wav.shape[2])
+        if wav.dim() != 2 or min(wav.shape) < 1:
+            raise ValueError(f"{who}: wav has to be [B, stride] or [B, 1, stride], but is {tuple(wav.shape)}")
+        return wav, wav.shape[0], wav.shape[1]
+
+    def wav_edges(self, wav, lens, *, frame=256, threshold, keep=0):
+        """where every row of a padded waveform batch is loud (dtts_wav_edges): wav cuda [B, stride], lens [B] in 0 .. stride -> HOST int32
+        [B, 2] = (begin, end).  A frame of `frame` samples is loud when sum(x^2) >= threshold^2 count; begin = max(0, first loud frame's
+        start - keep), end = min(len, last loud frame's end + keep); no loud frame: (0, 0).  Waits for its own result (the read-back)."""
+        from .longform import check_edges
+        wav, B, stride = self._wav_rows(wav, "wav_edges")
+        lens, frame, threshold, keep = check_edges(lens, B, stride, frame, threshold, keep)
+        edges = torch.empty((B, 2), device=self.device, dtype=torch.int32)
+        self._rc(self.lib.dtts_wav_edges(self.h, _ptr(wav), lens.ctypes.data_as(_lib.c_int_p), B, stride, frame, threshold, keep, _ptr(edges),
+                                         self._stream()))
+        return edges.cpu().numpy()
+
+    def wav_join(self, wav, begins, counts, offsets, total, *, fade):
+        """the rows' spans laid end to end (dtts_wav_join): out[offsets[b] + i] = wav[b, begins[b] + i] w_b(i), i < counts[b], every other
+        sample +0.0; w_b a linear fade over min(fade, counts[b] // 2) samples at either end -> cuda fp32 [total].  ValueError before the
+        launch on overlapping or descending spans, begins + counts > stride, total >= 2**31 or B > 16.  Asynchronous."""
+        from .longform import check_join
+        wav, B, stride = self._wav_rows(wav, "wav_join")
+        begins, counts, offsets, total, fade = check_join(begins, counts, offsets, total, fade, B, stride)
+        out = torch.empty((total,), device=self.device, dtype=torch.float32)
+        if total:
+            self._rc(self.lib.dtts_wav_join(self.h, _ptr(wav), B, stride, *(a.ctypes.data_as(_lib.c_int_p) for a in (begins, counts, offsets)),
+                                            total, fade, _ptr(out), self._stream()))
+        return out
+
     # ------------------------------------------------------------------ stage B
     def diff_conditioning(self, refer, lens=None):
         _check(refer, "refer")

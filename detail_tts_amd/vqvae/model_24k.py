@@ -620,6 +620,69 @@ class SynthesizerTrn:
             if launched is not None:
                 launched[2].synchronize()
 
+    # ------------------------------------------------------------------------------------------------------------
+    def infer_long(self, text, refer=None, refer_lengths=None, *, speaker=None, tokenizer=None, sentence_ids=None, clause_ids=(),
+                   space_id=None, max_len=160, min_len=0, rows_per_call=8, seed=None, pauses_ms=None, trim_db=-40.0, keep_ms=20,
+                   fade_ms=5, stream=False, return_chunks=False, forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50,
+                   suppress_eos=False, diffusion_steps=None, sampler="p", eta=0.0, trunk_precision=None, decode_options=None,
+                   noise_scale=NOISE_SCALE):
+        """A text of any length in one voice -> one waveform [1,1,N] (longform.py; the reference has no long-form path).
+
+        The text is cut into chunks at sentence ends (longform.split_units: a sentence of more than `max_len` units again after a
+        clause mark, a space, or at max_len; sentences shorter than `min_len` merged), every chunk is a complete utterance - a row of
+        infer(batch=True), through the stages exactly as they are - and each group of `rows_per_call` (1 .. 16) chunks goes through
+        infer_stream as one request: group i + 1 decodes under group i's diffusion.  A group's waveforms are then joined on the device
+        (csrc/wav_join.hip): every row cut to its loud span (frames of 256 samples whose RMS reaches `trim_db` dB re full scale, `keep_ms`
+        kept around them; trim_db=None: nothing is cut), faded in and out linearly over `fade_ms`, and followed by pauses_ms[kind] of
+        exact zeros, kind = how the chunk ended ("sentence", "clause", "word", "hard"; the text's last chunk, "end", has no pause;
+        None: 400 / 200 / 60 / 0 ms).  A chunk that trimmed to nothing contributes no samples and keeps its pause.
+
+        text: a pinyin string (split at 。！？!?. / ，,；;、：: / spaces; needs `tokenizer`, an object with .encode; a chunk is framed as the
+        reference's api.py frames a text: " " + chunk + " ", encoded, one trailing 0), or a 1-D array of text ids (needs `sentence_ids`;
+        `clause_ids` and `space_id` as the vocabulary has them; framed as [space_id] + ids + [space_id, 0], or ids + [0]).  A framed chunk
+        of more than gpt.max_text_tokens ids is a ValueError naming its span.  The speaker: `speaker`, a Voice of S = 1, or a prompt mel
+        `refer` [1,128,Tr] (+ refer_lengths), whose latents are computed ONCE (get_conditioning_latents) - both given, or neither:
+        ValueError.  Every check is made before anything runs.
+
+        Chunk k is row k % rows_per_call of request k // rows_per_call, every request carries the call's `seed` (None: drawn once) and
+        chunk k has sample id k: a chunk's random streams do not depend on rows_per_call (its waveform is promised bit for bit only
+        for the same grouping).  forced_codes: a list of one code array per chunk (tests, ragged benchmarks); such a call runs its groups
+        as a loop of blocking infer(batch=True) calls and returns their bits - infer_stream decodes forced codes through the KV cache,
+        which moves the last bits of the latents, and nothing is decoded that the next group could overlap
+        (longform.group_waveforms).  Beams are refused as infer_stream refuses them; the remaining keywords are infer_stream's.
+
+        stream=True: a generator of the groups' pieces [1,1,n_i], in order, each as its group completes - the first audio arrives after
+        the first group.  stream=False: the same pieces concatenated (the same code, the same bits).  return_chunks: also one dict per
+        chunk - with stream=True each piece comes with the dicts of its own chunks - of span (in the caller's text), kind, codes (the
+        number of codes; max_generate_length - 1, the most a decode returns in front of its stop token, means the chunk ran into the limit
+        and was cut short), samples (before trimming), begin,
+        end, offset (in the whole output) and pause (samples).  The only host wait the call adds to infer_stream's is the read-back of
+        a group's edges, when its waveform is being handed out anyway.
+
+        The defaults - max_len, pauses, threshold, margin, fade - are the maintainer's choice and UNMEASURED: without a trained
+        checkpoint nothing is known about seam and pause quality, the right trim level or the codes a chunk of max_len units needs."""
+        from .. import longform
+        sampling_args(diffusion_steps, sampler, eta)
+        SynthesizerTrn._check_trunk_precision(self, trunk_precision)
+        plan = longform.prepare(self, text, refer, refer_lengths, speaker=speaker, tokenizer=tokenizer, sentence_ids=sentence_ids,
+                                clause_ids=clause_ids, space_id=space_id, max_len=max_len, min_len=min_len, rows_per_call=rows_per_call,
+                                seed=seed, pauses_ms=pauses_ms, trim_db=trim_db, keep_ms=keep_ms, fade_ms=fade_ms, forced_codes=forced_codes,
+                                decode_options=decode_options)
+        pieces = longform.run(self, plan, dict(noise_scale=noise_scale, max_generate_length=max_generate_length, top_k=top_k,
+                                               suppress_eos=suppress_eos, diffusion_steps=diffusion_steps, sampler=sampler, eta=eta,
+                                               trunk_precision=trunk_precision, decode_options=decode_options),
+                             pipelined=forced_codes is None)
+        if stream:
+            return pieces if return_chunks else (p for p, _ in pieces)
+        got = list(pieces)
+        wav = torch.cat([p for p, _ in got], 2)
+        return (wav, [c for _, cs in got for c in cs]) if return_chunks else wav
+
+    def join_group(self, wav, lens, kinds, plan, base=0, complete=True):
+        """one group of infer_long: its waveform batch cut and joined on the device (longform.join_group) -> (piece [n], chunk dicts)"""
+        from .. import longform
+        return longform.join_group(self, wav, lens, kinds, plan, base, complete)
+
     EMPTY_CODE_FRAMES = 16
 
     def infer_gpt(self, text, text_length, refer, refer_lengths, noise_scale=NOISE_SCALE, *, batch=False, seed=None, sample_ids=None,

@@ -5,6 +5,7 @@ vocoder -> gen.wav.  Everything after reading the file runs in libdetail_hip.so.
     python examples/api.py --ckpt /path/model-480.pt --vocab /path/bpe_tokenizers/zh_tokenizer.json --wav 1.wav \\
         --text "da4 jia1 hao3 ， jin1 tian1 lai2 dian3 da4 jia1 xiang3 kan4 de5 dong1 xi1 。"
     python examples/api.py --synthetic            # no checkpoint / vocabulary: seed-0 random weights, random ids, a synthetic prompt
+    python examples/api.py --ckpt ... --vocab ... --wav 1.wav --text-file chapter.txt     # a long pinyin text: infer_long, one wav
 """
 import argparse
 import os
@@ -48,9 +49,21 @@ def main():
     ap.add_argument("--voice", metavar="FILE", help="synthesise with a stored Voice: no prompt wav is read and no prompt encoder runs")
     ap.add_argument("--timings", metavar="PATH", help="also align the synthesised codes to the text (infer(return_alignment=True)) and write "
                                                       "the token and word spans and times as JSON; words need --vocab (its [SPACE] id)")
+    ap.add_argument("--text-file", metavar="PATH", help="a text of any length AS PINYIN: split at sentence ends, synthesised chunk by chunk "
+                                                        "and joined into one wav (infer_long); without --vocab a character stands for an id")
+    ap.add_argument("--pause-ms", type=float, nargs=4, metavar=("SENTENCE", "CLAUSE", "WORD", "HARD"),
+                    help="with --text-file: the silence behind a chunk by how it ended (default 400 200 60 0; unmeasured under a trained checkpoint)")
+    ap.add_argument("--max-len", type=int, default=160, help="with --text-file: the most characters of a chunk")
     a = ap.parse_args()
     if a.voice and (a.wav or a.save_voice):
         ap.error("--voice stands in the place of the prompt: not with --wav or --save-voice")
+    if a.text_file and a.timings:
+        ap.error("--timings is not available with --text-file: word timings across chunks are not implemented "
+                 "(infer_long(return_chunks=True) gives every chunk's offset)")
+    if a.text_file and (a.ids or a.print_ids):
+        ap.error("--text-file takes the text from the file: not with --ids or --print-ids")
+    if (a.pause_ms or a.max_len != 160) and not a.text_file:
+        ap.error("--pause-ms and --max-len belong to --text-file")
     device = "cuda:0"
     if a.ids:
         ids = [int(v) for v in a.ids.split(",")]
@@ -87,8 +100,29 @@ def main():
         print(f"{a.timings}: {len(doc['tokens'])} tokens, {len(doc['words'])} words, coverage {al['stats']['coverage']:.2f} "
               "(alignment quality is unmeasured: no trained checkpoint)")
         return wav
+    if a.text_file:
+        a.long = dict(text=open(a.text_file, encoding="utf-8").read(), max_len=a.max_len, seed=a.seed, suppress_eos=kw["suppress_eos"],
+                      max_generate_length=a.max_generate_length)
+        if a.pause_ms:
+            a.long["pauses_ms"] = dict(zip(("sentence", "clause", "word", "hard"), a.pause_ms))
+        if a.vocab:
+            a.long["tokenizer"] = VoiceBpeTokenizer(a.vocab)
+        else:       # no vocabulary: a character stands for an id (synthetic weights only - the ids mean nothing)
+            a.long["tokenizer"] = type("CharIds", (), dict(encode=staticmethod(lambda t: [3 + ord(c) % 250 for c in t])))()
+
+    def long_form(**speaker):
+        """--text-file: the whole text through infer_long in the prompt's voice -> the wav file"""
+        with torch.no_grad():
+            wav, chunks = vqvae.infer_long(a.long.pop("text"), return_chunks=True, **speaker, **a.long)
+        write_wav(a.out, wav.squeeze(0), 24000)
+        cut = sum(c["codes"] >= a.max_generate_length - 1 for c in chunks)
+        print(f"{a.out}: {wav.shape[-1] / 24000:.2f} s of audio from {len(chunks)} chunks of {a.text_file}"
+              + (f"; {cut} chunks ran into --max-generate-length and were cut short" if cut and not kw["suppress_eos"] else ""))
+
     if a.voice:
         from detail_tts_amd.voice import Voice
+        if a.text_file:
+            return long_form(speaker=Voice.load(a.voice, vqvae))
         with torch.no_grad():
             wav = finish(vqvae.infer(text_tokens, text_lengths, None, None, speaker=Voice.load(a.voice, vqvae), **kw))
         write_wav(a.out, wav.squeeze(0), 24000)
@@ -105,6 +139,12 @@ def main():
     spec = mel_spectrogram_torch(audio, hps.data.filter_length, hps.data.n_mel_channels, hps.data.sampling_rate, hps.data.hop_length,
                                  hps.data.win_length, hps.data.mel_fmin, hps.data.mel_fmax, rt=vqvae.rt)      # api.py:41-47
     spec_lengths = torch.LongTensor([spec.shape[-1]])
+    if a.text_file:
+        with torch.no_grad():
+            voice = vqvae.get_conditioning_latents(spec, spec_lengths)
+        if a.save_voice:
+            voice.save(a.save_voice)
+        return long_form(speaker=voice)
     with torch.no_grad():
         if a.save_voice:        # the prompt is encoded once, here; --voice FILE reuses it (the same waveform bit for bit)
             voice = vqvae.get_conditioning_latents(spec, spec_lengths)

@@ -278,6 +278,28 @@ int dtts_gpt_forward_losses_cond(dtts_handle* h, const float* cond, const int* t
 int dtts_vq_decode_cond(dtts_handle* h, const int* codes, const int* ncodes, int nmax, const float* g_vq, int B, float* mel_out,
                         void* stream);
 
+/* ---- long form: the waveforms of a group of chunks cut at their loud edges and laid end to end -----------------------------------
+ * A text longer than one utterance is synthesised chunk by chunk (detail_tts_amd/longform.py), every chunk a complete utterance and a
+ * row of the padded [B][stride] waveform batch stage C returns.  These two entries touch waveforms only.  Both asynchronous on
+ * `stream`, no atomics on global memory, nothing allocated: two calls give the same bits.  The reference has no long-form path; the
+ * defaults the Python side hands in (threshold, keep, fade, pauses) are unmeasured under a trained checkpoint.
+ *
+ * dtts_wav_edges: wav DEVICE [B][stride], lens HOST [B] (any value in 0 .. stride), edges DEVICE int [B][2] = (begin, end).  A frame
+ * is `frame` consecutive samples of a row (the last one may be partial) and is loud when sum(x^2) >= threshold^2 count, count its own
+ * sample count, the sum in fp32 in a fixed order.  With first / last the row's first and last loud frames, begin = max(0, first frame
+ * - keep) and end = min(lens[b], (last + 1) frame + keep); a row with no loud frame (lens[b] = 0 among them) gives (0, 0).  Samples at
+ * or beyond lens[b] are never read.  One workgroup per row.
+ *
+ * dtts_wav_join: out[offsets[b] + i] = wav[b][begins[b] + i] w_b(i) for i < counts[b], every other sample of out [total] is +0.0 (the
+ * pauses).  begins / counts / offsets HOST [B], B <= 16; checked before the launch: begins[b] + counts[b] <= stride, the spans
+ * [offsets[b], offsets[b] + counts[b]) ascending, disjoint and inside total, total < 2^31.  w_b fades in linearly over the first n_b =
+ * min(fade, counts[b] / 2) samples - (2 i + 1) / (2 n_b), ONE correctly rounded fp32 division of two exact integers - fades out as the
+ * mirror image over the last n_b and is 1 (the sample's own bits) in between; fade = 0 is a plain copy.  out must not alias wav. */
+int dtts_wav_edges(dtts_handle* h, const float* wav, const int* lens, int B, int stride, int frame, float threshold, int keep, int* edges,
+                   void* stream);
+int dtts_wav_join(dtts_handle* h, const float* wav, int B, int stride, const int* begins, const int* counts, const int* offsets,
+                  long long total, int fade, float* out, void* stream);
+
 /* ---- alignment: when did the model speak what --------------------------------------------------------------------------------------
  * Code position j attends to the text it is pronouncing; the GPT's text-audio attention therefore carries the timing.  The reference
  * exposes the maps through get_logits(..., get_attns=True) (gpt/model.py:392-400: GPT2Model(output_attentions=True).attentions, one
