@@ -130,6 +130,9 @@ SIGNATURES = {
     "dtts_vq_decode_cond": (C.c_int, [C.c_void_p, c_int_p, c_int_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "dtts_diff_conditioning": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dtts_diff_timestep_independent": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dtts_diff_timestep_independent_ex": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_void_p, c_int_p, c_int_p, C.c_int,
+                                                    C.c_void_p, C.c_void_p]),
+    "dtts_op_frame_map": (C.c_int, [C.c_void_p, c_int_p, c_int_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dtts_diff_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dtts_diff_sample": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, C.c_int, C.c_ulonglong, c_int_p, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

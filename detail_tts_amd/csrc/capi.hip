@@ -590,6 +590,20 @@ int dtts_diff_timestep_independent(dtts_handle* h, const float* latent_cm, const
     DTTS_API_END(h)
 }
 
+int dtts_diff_timestep_independent_ex(dtts_handle* h, const float* latent_cm, const int* lens_n, int B, int nmax, const float* cond,
+                                      const int* frames, const int* durations, int Tmax, float* code_emb, void* stream) {
+    DTTS_API_BEGIN
+    h->m->diff_timestep_independent_ex(latent_cm, lens_n, B, nmax, cond, frames, durations, Tmax, code_emb, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_op_frame_map(dtts_handle* h, const int* lens_n, const int* frames, const int* durations, int B, int nmax, int Tmax, int* map_out,
+                      void* stream) {
+    DTTS_API_BEGIN
+    h->m->op_frame_map(lens_n, frames, durations, B, nmax, Tmax, map_out, (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
 int dtts_diff_forward(dtts_handle* h, const float* x, const float* code_emb, const int* lens, int B, int T, int step,
                       int cond_free, float* out, void* stream) {
     DTTS_API_BEGIN

@@ -222,6 +222,17 @@ public:
     void diff_conditioning(const float* refer, const int* lens_host, int B, int Tmax, float* cond_out, hipStream_t s);
     void diff_timestep_independent(const float* latent_cm, const int* lens_n_host, int B, int nmax, const float* cond,
                                    float* code_emb, hipStream_t s);
+    // ... expanded to a frame plan (frame_map.hip): row b to frames_host[b] frames, uniformly (F.interpolate's nearest rule) or by
+    // durations_host [B, nmax]; code_emb [B,768,Tmax].  frames_host == nullptr: the entry above, the same launches.
+    void diff_timestep_independent_ex(const float* latent_cm, const int* lens_n_host, int B, int nmax, const float* cond,
+                                      const int* frames_host, const int* durations_host, int Tmax, float* code_emb, hipStream_t s);
+    void op_frame_map(const int* lens_n_host, const int* frames_host, const int* durations_host, int B, int nmax, int Tmax, int* map_out,
+                      hipStream_t s);
+    void check_frames(const int* lens_n_host, const int* frames_host, const int* durations_host, int B, int nmax, int Tmax);
+    void frame_map_device(const int* d_lens_n, const int* d_frames, const int* durations_host, int B, int nmax, int Tmax, int* map,
+                          hipStream_t s);
+    void affine_gather(const float* x, long long x_bs, int x_cs, const float* ab, const int* d_frames, const int* map, int Tmax, int B, int C,
+                       float* y, hipStream_t s);
     void diff_forward(const float* x, const float* code_emb, const int* lens_host, int B, int T, int step, int cond_free,
                       float* out, hipStream_t s);
     void diff_sample(const float* code_emb, const int* lens_host, int B, int T, unsigned long long seed, const int* sample_ids_host,

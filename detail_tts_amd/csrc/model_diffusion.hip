@@ -1328,11 +1328,19 @@ void Model::diff_conditioning(const float* refer, const int* lens_host, int B, i
 
 void Model::diff_timestep_independent(const float* latent_cm, const int* lens_n_host, int B, int nmax, const float* cond,
                                       float* code_emb, hipStream_t s) {
+    diff_timestep_independent_ex(latent_cm, lens_n_host, B, nmax, cond, nullptr, nullptr, 0, code_emb, s);
+}
+
+void Model::diff_timestep_independent_ex(const float* latent_cm, const int* lens_n_host, int B, int nmax, const float* cond,
+                                         const int* frames_host, const int* durations_host, int Tmax, float* code_emb, hipStream_t s) {
     DTTS_REQUIRE(bound_, "weights not bound");
+    DTTS_REQUIRE(frames_host || !durations_host, "durations need frames");
+    if (frames_host) check_frames(lens_n_host, frames_host, durations_host, B, nmax, Tmax);      // refusals before any launch
     const int C = cfg.diff_channels;
     const size_t act = (size_t)B * C * nmax;
     const bool x3l = use_x3() && !latcond_.empty() && latcond_[0].qkv.w3;
-    ws().ensure(sizeof(float) * (3 * act + qkv_floats(B, C, nmax) + (size_t)2 * B * C) + (x3l ? x3_bytes(B, C, nmax) : 0) + 8192);
+    ws().ensure(sizeof(float) * (3 * act + qkv_floats(B, C, nmax) + (size_t)2 * B * C) + (x3l ? x3_bytes(B, C, nmax) : 0) + 8192 +
+                (frames_host ? sizeof(int) * (size_t)B * Tmax + 256 : 0));
     std::vector<int> ln(B);
     for (int b = 0; b < B; ++b) ln[b] = lens_n_host ? lens_n_host[b] : nmax;
     const int* dl = upload_ints(ln.data(), B, s);
@@ -1354,7 +1362,15 @@ void Model::diff_timestep_independent(const float* latent_cm, const int* lens_n_
     }
     // code_norm(code_emb) * (1 + cond_scale) + cond_shift  (vqvae/diff_model.py:236, 242), then nearest x4 (:252)
     launch_gn_coeffs(cur, bs, nmax, dl, nmax, B, C, gn_groups(C), code_gn_g_, code_gn_b_, 1e-5f, cond, 1, 2 * C, io.ab, s);
-    launch_affine_apply(cur, bs, nmax, io.ab, dl, nmax, B, C, 4, ACT_NONE, code_emb, (long long)C * 4 * nmax, 4 * nmax, s);
+    if (!frames_host) {
+        launch_affine_apply(cur, bs, nmax, io.ab, dl, nmax, B, C, 4, ACT_NONE, code_emb, (long long)C * 4 * nmax, 4 * nmax, s);
+        return;
+    }
+    // ... or F.interpolate(size=T_b, mode='nearest') / repeat_interleave of the plan, through the row maps (frame_map.hip)
+    const int* df = upload_ints(frames_host, B, s);
+    int* map = ws().i32((size_t)B * Tmax);
+    frame_map_device(dl, df, durations_host, B, nmax, Tmax, map, s);
+    affine_gather(cur, bs, nmax, io.ab, df, map, Tmax, B, C, code_emb, s);
 }
 
 void Model::op_attention_block(const char* prefix, const float* x, const int* lens_host, int B, int C, int T, float* y,

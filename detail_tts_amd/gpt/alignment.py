@@ -36,6 +36,14 @@ def token_times(spans, samples_per_code, sampling_rate):
     return [None if s is None else (s[0] * k, (s[1] + 1) * k) for s in spans]
 
 
+def token_times_frames(spans, bounds, samples_per_frame, sampling_rate):
+    """token_times under a frame plan (duration.py: speed / durations / span_rates): code j covers mel frames
+    [bounds[j], bounds[j + 1]) - bounds[j] the first frame whose code is >= j - each frame samples_per_frame samples; a span whose codes
+    own no frame gets an empty interval (start == end)"""
+    k = float(samples_per_frame) / float(sampling_rate)
+    return [None if s is None else (int(bounds[s[0]]) * k, int(bounds[s[1] + 1]) * k) for s in spans]
+
+
 def group_words(ids, spans, space_id):
     """The caller's text ids and THEIR spans (spans_from_path(...)[1:1 + len(ids)]) -> a list of words: the runs of tokens between
     `space_id` ids, each dict(tokens=[indices into ids], span=(first, last) over its tokens that own a code, or None).  The space
@@ -75,18 +83,22 @@ def alignment_stats(path, n, n_text, text_mass=None):
     return dict(coverage=1.0 if n_text == 0 else (n_text - len(skipped)) / n_text, skipped=skipped, longest_stay=int(stay), mean_text_mass=mass)
 
 
-def describe(path, n, ids, text_mass, samples_per_code, sampling_rate, space_id=None):
+def describe(path, n, ids, text_mass, samples_per_code, sampling_rate, space_id=None, frame_bounds=None):
     """One utterance's alignment as SynthesizerTrn.align returns it: dict(path, spans, times (per column), token_spans / token_times
-    (per caller's id), words (with `space_id`; each with its time), stats)."""
+    (per caller's id), words (with `space_id`; each with its time), stats).  frame_bounds (a planned infer: FramePlan.code_bounds, with
+    samples_per_code / 4 samples per frame): every time follows the plan's map (token_times_frames); None: the fixed 4 frames per code."""
     ids = np.asarray(ids).reshape(-1)
     p = np.asarray(path, np.int64).reshape(-1)[: int(n)]
     spans = spans_from_path(p, n, ids.size + 2)
     tok = spans[1:1 + ids.size]
-    out = dict(path=p.astype(np.int32), spans=spans, times=token_times(spans, samples_per_code, sampling_rate), token_spans=tok,
-               token_times=token_times(tok, samples_per_code, sampling_rate), stats=alignment_stats(p, n, ids.size, text_mass))
+    times_of = lambda sp: token_times(sp, samples_per_code, sampling_rate)  # noqa: E731
+    if frame_bounds is not None:
+        times_of = lambda sp: token_times_frames(sp, frame_bounds, samples_per_code // 4, sampling_rate)  # noqa: E731
+    out = dict(path=p.astype(np.int32), spans=spans, times=times_of(spans), token_spans=tok,
+               token_times=times_of(tok), stats=alignment_stats(p, n, ids.size, text_mass))
     if space_id is not None:
         words = group_words(ids, tok, space_id)
-        for w, t in zip(words, token_times([w["span"] for w in words], samples_per_code, sampling_rate)):
+        for w, t in zip(words, times_of([w["span"] for w in words])):
             w["time"] = t
         out["words"] = words
     return out

@@ -184,7 +184,7 @@ def check_forced(forced_codes, nchunks):
     return forced
 
 
-def plan_requests(chunks, rows_per_call, seed, speaker, forced_codes=None):
+def plan_requests(chunks, rows_per_call, seed, speaker, forced_codes=None, speed=None):
     """chunk k is row k % rows_per_call of request k // rows_per_call, with sample id k - its random streams do not depend on
     rows_per_call - and every request carries the call's one seed -> the request dicts of infer_stream"""
     import torch
@@ -199,6 +199,8 @@ def plan_requests(chunks, rows_per_call, seed, speaker, forced_codes=None):
                    sample_ids=list(range(r0, r0 + len(rows))))
         if forced_codes is not None:
             req["forced_codes"] = forced_codes[r0: r0 + len(rows)]
+        if speed is not None:
+            req["speed"] = speed
         reqs.append(req)
     return reqs
 
@@ -269,7 +271,7 @@ def check_join(begins, counts, offsets, total, fade, B, stride):
 # ---------------------------------------------------------------------------------------------------------------- the driver
 def prepare(model, text, refer=None, refer_lengths=None, *, speaker=None, tokenizer=None, sentence_ids=None, clause_ids=(),
             space_id=None, max_len=160, min_len=0, rows_per_call=8, seed=None, pauses_ms=None, trim_db=-40.0, keep_ms=20, fade_ms=5,
-            forced_codes=None, decode_options=None):
+            forced_codes=None, decode_options=None, speed=None):
     """every check and all the planning of infer_long, before anything runs on the device but the prompt's encoders (once) ->
     dict(chunks, requests, pauses, threshold, keep, fade)"""
     import torch
@@ -280,6 +282,11 @@ def prepare(model, text, refer=None, refer_lengths=None, *, speaker=None, tokeni
     rows_per_call = check_rows_per_call(rows_per_call)
     pauses_ms = check_pauses(PAUSES_MS if pauses_ms is None else pauses_ms)
     beam_request(decode_options, stream=True)                # beams are refused as infer_stream refuses them
+    if speed is not None:                                     # one rate for all chunks (duration.py); 1.0 is no plan at all
+        from .duration import check_speed
+        if isinstance(speed, (list, tuple, np.ndarray)):
+            raise ValueError("infer_long takes ONE speed for all chunks")
+        speed = None if check_speed(speed, 1) is None else float(speed)
     if trim_db is not None and not (math.isfinite(float(trim_db)) and float(trim_db) <= 0):
         raise ValueError(f"trim_db has to be None (no trimming) or a level <= 0 dB relative to full scale, but is {trim_db}")
     if not (math.isfinite(float(keep_ms)) and keep_ms >= 0 and math.isfinite(float(fade_ms)) and fade_ms >= 0):
@@ -303,7 +310,7 @@ def prepare(model, text, refer=None, refer_lengths=None, *, speaker=None, tokeni
     if speaker is None:                                       # the prompt's latents, once: no prompt encoder runs per group
         speaker = model.get_conditioning_latents(refer, refer_lengths)
     sr = cfg["data"]["sampling_rate"]
-    return dict(chunks=chunks, requests=plan_requests(chunks, rows_per_call, int(seed), speaker, forced),
+    return dict(chunks=chunks, requests=plan_requests(chunks, rows_per_call, int(seed), speaker, forced, speed), speed=speed,
                 pauses={k: ms_to_samples(v, sr) for k, v in pauses_ms.items()},
                 threshold=None if trim_db is None else 10.0 ** (float(trim_db) / 20.0),
                 keep=ms_to_samples(keep_ms, sr), fade=ms_to_samples(fade_ms, sr))
@@ -352,8 +359,9 @@ def group_waveforms(model, plan, stream_kw, pipelined=True):
     kw = dict(stream_kw)
     noise_scale = kw.pop("noise_scale")
     for r in plan["requests"]:
+        rate = {} if r.get("speed") is None else dict(speed=r["speed"])
         yield model.infer(r["text"], r["text_length"], None, None, noise_scale, batch=True, speaker=r["speaker"], seed=r["seed"],
-                          sample_ids=r["sample_ids"], forced_codes=r.get("forced_codes"), return_lengths=True, **kw)
+                          sample_ids=r["sample_ids"], forced_codes=r.get("forced_codes"), return_lengths=True, **rate, **kw)
 
 
 def run(model, plan, stream_kw, pipelined=True):
@@ -365,6 +373,8 @@ def run(model, plan, stream_kw, pipelined=True):
         piece, infos = model.join_group(wav, lens, [c["kind"] for c in rows], plan, base, complete=pipelined)
         for c, info in zip(rows, infos):
             info.update(span=c["span"], kind=c["kind"], codes=info["samples"] // 1024)
+            if plan.get("speed") is not None:             # under a rate the samples no longer count the codes
+                info.update(codes=None, frames=info["samples"] // 256)
         base += piece.numel()
         k += len(lens)
         yield piece.view(1, 1, -1), infos

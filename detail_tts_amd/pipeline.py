@@ -32,15 +32,19 @@ class Request:
     a_done: object = None
     tr: dict = None             # this request's entry of SynthesizerTrn.stream_trace
     voice: object = None        # the request's speaker as a Voice (voice.py) in the place of refer: S = 1 or B until stage A expands it
+    rate: dict = None           # the request's speed / durations / span_rates, checked (duration.check_request); None: no frame plan
+    plan: object = None         # stage B: the FramePlan it ran under (duration.py), None on the x4 path
 
 
 def normalize_request(text, text_length, refer, refer_lengths, seed=None, sample_ids=None, forced_codes=None, *, batch=True,
-                      speaker=None, dims=None):
+                      speaker=None, dims=None, speed=None, durations=None, span_rates=None):
     """the arguments of infer() / one request dict of infer_stream() -> Request: B, integer rl, a drawn seed when none is given,
     default sample ids range(B), per-row int32 text arrays cut at their own lengths.  batch=False keeps the first row only (the
     reference: text = text[0].unsqueeze(0) ..., vqvae/model_24k.py:775-778).  No device transfer: refer stays where it is.
     speaker: a Voice in the place of (refer, refer_lengths), which are then None (voice.check_speaker: ValueError otherwise, and on
-    S not in {1, B} or widths other than the model's `dims`); the Request carries it as `voice`, refer = None and rl = zeros."""
+    S not in {1, B} or widths other than the model's `dims`); the Request carries it as `voice`, refer = None and rl = zeros.
+    speed / durations / span_rates: the speaking-rate keywords (duration.check_request: at most one, the last two with forced_codes;
+    ValueError here, before any launch); the Request carries them as `rate`, None when they ask for nothing (speed None or 1.0)."""
     text = torch.as_tensor(text)
     tl = torch.as_tensor(text_length).reshape(-1).tolist()
     if speaker is not None or refer is None:
@@ -54,12 +58,20 @@ def normalize_request(text, text_length, refer, refer_lengths, seed=None, sample
         text, refer, tl, rl = text[:1], None if refer is None else refer[:1], tl[:1], rl[:1]
         if forced_codes is not None:
             forced_codes = forced_codes[:1]
+        durations = None if durations is None else durations[:1]
+        span_rates = None if span_rates is None else span_rates[:1]
+        if isinstance(speed, (list, tuple, np.ndarray)) or (hasattr(speed, "dim") and speed.dim() > 0):
+            speed = speed[:1]
     B = text.shape[0]
+    rate = None
+    if speed is not None or durations is not None or span_rates is not None:
+        from .duration import check_request
+        rate = check_request(speed, durations, span_rates, forced_codes, B)
     if seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     sids = list(range(B)) if sample_ids is None else list(sample_ids)
     texts = [text[b, : int(tl[b])].cpu().numpy().astype(np.int32) for b in range(B)]
-    return Request(B=B, rl=rl, seed=seed, sids=sids, texts=texts, refer=refer, forced=forced_codes, voice=speaker)
+    return Request(B=B, rl=rl, seed=seed, sids=sids, texts=texts, refer=refer, forced=forced_codes, voice=speaker, rate=rate)
 
 
 def group_requests(requests, pair=False):
@@ -139,12 +151,20 @@ def drain_session(rt, max_generate_length, suppress_eos):
 
 def stage_b(model, st, sampler_id, eta, prec, *, sched=None, sched_ts=None, mark=lambda name: None):
     """stage B of one request on the current stream (vqvae/model_24k.py:802-804) -> (mel, lens_t).  sched None: the schedule of
-    `sched_ts` is looked up (built on first use) between the embedding and the sampling launches."""
+    `sched_ts` is looked up (built on first use) between the embedding and the sampling launches.  A request with a rate (speed /
+    durations / span_rates) runs under its frame plan (duration.make_plan, kept as st.plan): the embedding through the plan's maps,
+    lens_t the plan's frame counts; without one, the x4 launch and 4 frames per code."""
     rt = model.rt
     cond = st.voice.diffusion if st.voice is not None else rt.diff_conditioning(st.refer, st.rl)
-    code_emb = rt.diff_timestep_independent(st.lat, cond, st.n)
+    if st.rate is None:
+        code_emb = rt.diff_timestep_independent(st.lat, cond, st.n)
+        lens_t = [4 * v for v in st.n]
+    else:
+        from .duration import make_plan
+        st.plan = make_plan(st.n, st.rate)
+        code_emb = rt.diff_timestep_independent(st.lat, cond, st.n, frames=st.plan.frames, durations=st.plan.durations)
+        lens_t = list(st.plan.frames)
     mark("diff_cond")
-    lens_t = [4 * v for v in st.n]
     if sched is None:
         sched = rt.sampler_schedule(sched_ts, sampler_id)
     with model._trunk_precision(prec):
@@ -183,7 +203,8 @@ def stream_stage_a(rt, sa, group, kw, token_wgs, trace=None, dims=None):
     rows is decoded session after session (gpt_generate).  `kw`: the sampling arguments; next(token_wgs): a session's token-kernel width."""
     dev = rt.device
     sts = [normalize_request(r["text"], r["text_length"], r.get("refer"), r.get("refer_lengths"), r.get("seed"), r.get("sample_ids"),
-                             r.get("forced_codes"), speaker=r.get("speaker"), dims=dims) for r in group]
+                             r.get("forced_codes"), speaker=r.get("speaker"), dims=dims, speed=r.get("speed"),
+                             durations=r.get("durations"), span_rates=r.get("span_rates")) for r in group]
     tr = None
     if trace is not None:
         tr = dict(host_a0=time.perf_counter(), ev_a0=torch.cuda.Event(enable_timing=True), ev_a1=torch.cuda.Event(enable_timing=True))

@@ -606,13 +606,62 @@ class Runtime:
         self._rc(self.lib.dtts_diff_conditioning(self.h, _ptr(refer), li[0] if li else None, B, T, _ptr(out), self._stream()))
         return out
 
-    def diff_timestep_independent(self, latent_cm, cond, lens_n=None):
+    @staticmethod
+    def _frame_plan(B, n, lens_n, frames, durations, Tmax=None):
+        """the host arrays of a frame plan (duration.py) -> (frames int32 [B], durations int32 [B, n] or None, Tmax).  frames: one frame
+        count per row; durations: None (the uniform map), an array [B, n] or a list of B rows (zero-padded to n here).  The library
+        refuses what is left: a count outside 1 .. Tmax, a row's durations that do not sum to its count, Tmax % 4 != 0."""
+        fr = np.ascontiguousarray(np.asarray(frames, dtype=np.int32).reshape(-1))
+        if fr.size != B:
+            raise ValueError(f"frames holds {fr.size} counts for B = {B} rows")
+        if lens_n is not None and len(lens_n) != B:
+            raise ValueError(f"lens_n holds {len(lens_n)} counts for B = {B} rows")
+        dur = None
+        if durations is not None:
+            dur = np.zeros((B, n), np.int32)
+            if len(durations) != B:
+                raise ValueError(f"durations holds {len(durations)} rows for B = {B}")
+            for b, d in enumerate(durations):
+                d = np.asarray(d, np.int32).reshape(-1)
+                if d.size > n:
+                    raise ValueError(f"durations[{b}] holds {d.size} entries for rows of at most {n} codes")
+                dur[b, : d.size] = d
+        return fr, dur, int(fr.max()) if Tmax is None else int(Tmax)
+
+    def diff_timestep_independent(self, latent_cm, cond, lens_n=None, *, frames=None, durations=None):
+        """DiffusionTts.timestep_independent, latent branch: latent_cm [B,768,n] -> the code embedding [B,768,4 n]; with `frames` (one
+        frame count per row, each a multiple of 4 as the vocoder needs it) [B,768,max(frames)], row b expanded to frames[b] columns by
+        F.interpolate's nearest rule or, with `durations` (per row the frames of every code, summing to frames[b]), by
+        repeat_interleave (dtts_diff_timestep_independent_ex, csrc/frame_map.hip); columns beyond a row's count are zero."""
         _check(latent_cm, "latent_cm"); _check(cond, "cond")
         B, Cc, n = latent_cm.shape
-        out = torch.zeros((B, Cc, 4 * n), device=self.device, dtype=torch.float32)
         li = _ints(lens_n)
-        self._rc(self.lib.dtts_diff_timestep_independent(self.h, _ptr(latent_cm), li[0] if li else None, B, n, _ptr(cond),
-                                                         _ptr(out), self._stream()))
+        if frames is None:
+            if durations is not None:
+                raise ValueError("durations need frames (the rows' frame counts)")
+            out = torch.zeros((B, Cc, 4 * n), device=self.device, dtype=torch.float32)
+            self._rc(self.lib.dtts_diff_timestep_independent(self.h, _ptr(latent_cm), li[0] if li else None, B, n, _ptr(cond),
+                                                             _ptr(out), self._stream()))
+            return out
+        fr, dur, Tmax = self._frame_plan(B, n, lens_n, frames, durations)
+        out = torch.zeros((B, Cc, max(Tmax, 1)), device=self.device, dtype=torch.float32)
+        self._rc(self.lib.dtts_diff_timestep_independent_ex(self.h, _ptr(latent_cm), li[0] if li else None, B, n, _ptr(cond),
+                                                            fr.ctypes.data_as(_lib.c_int_p),
+                                                            dur.ctypes.data_as(_lib.c_int_p) if dur is not None else None, Tmax,
+                                                            _ptr(out), self._stream()))
+        return out
+
+    def op_frame_map(self, lens_n, frames, durations=None, *, nmax=None, Tmax=None):
+        """the frame -> code maps of a frame plan, as the device builds them (dtts_op_frame_map: the unit entry of the two map kernels)
+        -> cuda int32 [B, Tmax], -1 at and beyond a row's frame count.  lens_n [B] code counts, frames [B], durations None / rows."""
+        B = len(lens_n)
+        n = int(max(lens_n)) if nmax is None else int(nmax)
+        fr, dur, Tmax = self._frame_plan(B, n, lens_n, frames, durations, Tmax)
+        li = _ints(lens_n)
+        out = torch.empty((B, max(Tmax, 1)), device=self.device, dtype=torch.int32)
+        self._rc(self.lib.dtts_op_frame_map(self.h, li[0], fr.ctypes.data_as(_lib.c_int_p),
+                                            dur.ctypes.data_as(_lib.c_int_p) if dur is not None else None, B, n, Tmax, _ptr(out),
+                                            self._stream()))
         return out
 
     def diff_forward(self, x, step, code_emb=None, cond_free=False, lens=None):

@@ -38,16 +38,37 @@ class DiffusionTts:
             return d
         return self.rt.voice_pool(d.view(S, n, -1), np.asarray([embedder_length(l) for l in lens], np.float32).reshape(S, n))
 
-    def timestep_independent(self, aligned_conditioning, conditioning_latent, expected_seq_len, return_code_pred=False, lengths=None):
-        """vqvae/diff_model.py:231-260 (latent branch): [B,n,768] -> [B,768,4n]"""
+    def timestep_independent(self, aligned_conditioning, conditioning_latent, expected_seq_len, return_code_pred=False, lengths=None,
+                             *, frames=None, durations=None):
+        """vqvae/diff_model.py:231-260 (latent branch): [B,n,768] -> [B,768,expected_seq_len].  expected_seq_len = 4 n is the
+        inference path's x4 launch.  Any other positive multiple of 4 (the vocoder's granule) with lengths=None is the reference's
+        F.interpolate(size=expected_seq_len, mode='nearest') of every row, torch's float32 index rule bit for bit (duration.py).  A
+        ragged batch (lengths: the rows' code counts, an extension) at other rates says so per row: frames= (one frame count per row,
+        expected_seq_len >= their largest) and optionally durations= (Runtime.diff_timestep_independent)."""
         if return_code_pred:
             raise NotImplementedError("return_code_pred is a training-only branch")
         if aligned_conditioning.dtype != torch.float32:
             raise NotImplementedError("token (code_converter) conditioning is not on the inference path")
+        B, n = aligned_conditioning.shape[0], aligned_conditioning.shape[1]
+        T = int(expected_seq_len)
+        if frames is None:
+            if durations is not None:
+                raise ValueError("durations= needs frames= (the rows' frame counts)")
+            if T != 4 * n:
+                if lengths is not None:
+                    raise ValueError("expected_seq_len must be 4 * n for a ragged batch (lengths=): give the rows' frame counts with "
+                                     "the keyword frames= (one per row, each a multiple of 4) instead")
+                if T < 4 or T % 4:
+                    raise ValueError(f"expected_seq_len must be a positive multiple of 4, but is {expected_seq_len}")
+                frames = [T] * B
+        elif T % 4 or T < max(int(f) for f in frames):
+            raise ValueError(f"expected_seq_len = {expected_seq_len} must be a multiple of 4 that holds every row of frames= {list(frames)}")
         lat_cm = aligned_conditioning.permute(0, 2, 1).contiguous()
-        out = self.rt.diff_timestep_independent(lat_cm, conditioning_latent.contiguous(), lengths)
-        if expected_seq_len != out.shape[-1]:
-            raise ValueError("expected_seq_len must be 4 * n (F.interpolate nearest x4 on the inference path)")
+        if frames is None:
+            return self.rt.diff_timestep_independent(lat_cm, conditioning_latent.contiguous(), lengths)
+        out = self.rt.diff_timestep_independent(lat_cm, conditioning_latent.contiguous(), lengths, frames=frames, durations=durations)
+        if out.shape[-1] < T:                                       # every row shorter than expected_seq_len: zero columns behind them
+            out = torch.nn.functional.pad(out, (0, T - out.shape[-1]))
         return out
 
     def forward(self, x, timesteps, aligned_conditioning=None, conditioning_latent=None, precomputed_aligned_embeddings=None,

@@ -318,8 +318,19 @@ class SynthesizerTrn:
               forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False, return_lengths=False,
               stream_vocoder=False, vocoder_chunk=256, wait=True, check_range=True, diffusion_steps=None, sampler="p", eta=0.0,
               trunk_precision=None, num_candidates=1, choose=None, return_candidates=False, prompt_codes=None, decode_options=None,
-              speaker=None, return_alignment=False, align_options=None):
+              speaker=None, return_alignment=False, align_options=None, speed=None, durations=None, span_rates=None):
         """vqvae/model_24k.py:774-810.  Returns wav [B,1,1024*n_max] (B=1 unless batch=True).
+
+        speed / durations / span_rates (at most one; duration.py): how fast the voice speaks.  The reference's
+        DiffusionTts.timestep_independent expands the code embedding to any frame count (F.interpolate nearest,
+        vqvae/diff_model.py:252) and only do_spectrogram_diffusion fixes 4 frames per code; here row b gets T_b frames, a multiple of 4:
+        speed (a rate, or one per row, in [0.25, 4]) -> T_b = max(4, 4 int(n_b / speed_b + 0.5)) under torch's own nearest map;
+        durations (per row the frames of every code, >= 0; a sum off a multiple of 4 extends the last speaking code) and span_rates
+        (per row (first_code, last_code, rate) spans, inclusive as return_alignment hands them out; a code outside every span keeps its
+        4 frames) need forced_codes - re-render the codes of an earlier call with one word held longer.  Checked on the host before
+        any launch.  Under a plan the waveform is [B,1,256*max(T_b)], the returned lengths are 256 T_b and return_alignment's times
+        follow the map; it composes with every other keyword (num_candidates: the plan applies to the winners).  speed None, or 1.0
+        with the other two absent: today's launches and bits.  Audio quality at other rates is unmeasured (no trained checkpoint).
 
         return_alignment: the call also returns, as its LAST value, the text-to-audio alignment of the synthesised codes - one
         dictionary per row, as align() gives it (per-token and per-word code spans and times, and the coverage / skipped /
@@ -378,7 +389,8 @@ class SynthesizerTrn:
         check_prompt_args(prompt_codes, forced_codes, ncand)
         processors, beam = beam_request(decode_options, forced_codes=forced_codes, num_candidates=ncand, return_candidates=return_candidates)
         st = normalize_request(text, text_length, refer, refer_lengths, seed, sample_ids, forced_codes, batch=batch, speaker=speaker,
-                               dims=None if speaker is None else model_dims(self.cfg))
+                               dims=None if speaker is None else model_dims(self.cfg), speed=speed, durations=durations,
+                               span_rates=span_rates)
         B, rl, texts, seed, sample_ids, forced_codes = st.B, st.rl, st.texts, st.seed, st.sids, st.forced
         if prompt_codes is not None:       # (ValueError on a bad row count or code: before any launch)
             prompt_codes = prompt_rows(prompt_codes if batch else prompt_codes[:1], B)
@@ -483,9 +495,9 @@ class SynthesizerTrn:
             torch.cuda.synchronize(self.device)
             for (_, a), (nm, b) in zip(ev[:-1], ev[1:]):
                 self.stage_ms[nm] = self.stage_ms.get(nm, 0.0) + a.elapsed_time(b)
-        ret = (wav,) + (([1024 * v for v in n],) if return_lengths else ()) + ((cand,) if return_candidates else ())
+        ret = (wav,) + (([256 * t for t in lens_t],) if return_lengths else ()) + ((cand,) if return_candidates else ())
         if return_alignment:
-            ret += (self._alignment_of(texts, out_codes, refer, rl, cond, **(align_options or {})),)
+            ret += (self._alignment_of(texts, out_codes, refer, rl, cond, **(align_options or {}), plan=st.plan),)
         return ret if len(ret) > 1 else wav
 
     def check_vocoder(self, ticket=None):
@@ -499,7 +511,8 @@ class SynthesizerTrn:
         """Batch server: `infer(..., batch=True)` over a sequence of request batches, software-pipelined over three HIP streams.
 
         requests: iterable of dicts with keys text [B,Lt], text_length [B], refer [B,128,Tr], refer_lengths [B] (or, in the place of those
-        two, speaker = a Voice: see infer) and optionally seed,
+        two, speaker = a Voice: see infer) and optionally seed, speed / durations / span_rates (see infer: the request's speaking rate; its
+        yielded lengths are then 256 T_b),
         sample_ids, forced_codes (per-row code arrays fed through the KV-cache decode instead of sampling: tests / ragged benchmarks;
         <= 16 rows) (any B; up to 16 utterances share one decode session; with pair_stage_a two consecutive requests of <= 8 utterances
         are decoded as ONE session - stage A of requests i + 1 and i + 2 together under stage B of requests i - 1 and i).  Yields (wav [B,1,1024*n_max], lengths) per request, in order; every
@@ -563,7 +576,7 @@ class SynthesizerTrn:
                 st.tr["ev_b0"].record(cur)
             mel, lens_t = stage_b(self, st, sampler_id, eta, prec, sched=sched)
             wav, self.vocoder_done, self.vocoder_ticket = stage_c(self.rt, sc, cur, mel, st, lens_t, noise_scale, vocoder_chunk, tr=st.tr)
-            return wav, [1024 * v for v in st.n], self.vocoder_done, self.vocoder_ticket, (mel, st, lens_t)
+            return wav, [256 * t for t in lens_t], self.vocoder_done, self.vocoder_ticket, (mel, st, lens_t)
 
         def hand_out(out):
             """wait for this request's waveform; a saturated stage C is re-run on the exact fp32 kernels (this thread issues every stage-C
@@ -625,8 +638,11 @@ class SynthesizerTrn:
                    space_id=None, max_len=160, min_len=0, rows_per_call=8, seed=None, pauses_ms=None, trim_db=-40.0, keep_ms=20,
                    fade_ms=5, stream=False, return_chunks=False, forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50,
                    suppress_eos=False, diffusion_steps=None, sampler="p", eta=0.0, trunk_precision=None, decode_options=None,
-                   noise_scale=NOISE_SCALE):
+                   noise_scale=NOISE_SCALE, speed=None):
         """A text of any length in one voice -> one waveform [1,1,N] (longform.py; the reference has no long-form path).
+
+        speed: one speaking rate in [0.25, 4] for every chunk (see infer; None or 1.0: today's path).  The join and the pauses are
+        untouched; a chunk's dict then reports `frames` (its mel frames, samples // 256) and `codes` = None (the rate hides them).
 
         The text is cut into chunks at sentence ends (longform.split_units: a sentence of more than `max_len` units again after a
         clause mark, a space, or at max_len; sentences shorter than `min_len` merged), every chunk is a complete utterance - a row of
@@ -667,7 +683,7 @@ class SynthesizerTrn:
         plan = longform.prepare(self, text, refer, refer_lengths, speaker=speaker, tokenizer=tokenizer, sentence_ids=sentence_ids,
                                 clause_ids=clause_ids, space_id=space_id, max_len=max_len, min_len=min_len, rows_per_call=rows_per_call,
                                 seed=seed, pauses_ms=pauses_ms, trim_db=trim_db, keep_ms=keep_ms, fade_ms=fade_ms, forced_codes=forced_codes,
-                                decode_options=decode_options)
+                                decode_options=decode_options, speed=speed)
         pieces = longform.run(self, plan, dict(noise_scale=noise_scale, max_generate_length=max_generate_length, top_k=top_k,
                                                suppress_eos=suppress_eos, diffusion_steps=diffusion_steps, sampler=sampler, eta=eta,
                                                trunk_precision=trunk_precision, decode_options=decode_options),
@@ -733,9 +749,10 @@ class SynthesizerTrn:
             return wav
         return wav, self._alignment_of(st.texts, out_codes, refer, rl, pkw.get("cond"), **(align_options or {}))
 
-    def _alignment_of(self, texts, code_list, refer, rl, cond, layers=None, head_weights=None, space_id=None):
+    def _alignment_of(self, texts, code_list, refer, rl, cond, layers=None, head_weights=None, space_id=None, plan=None):
         """one teacher-forced pass with the attention read-out over (texts, code_list), the path kernel, then the host bookkeeping of
-        gpt/alignment.py -> a list of per-row dictionaries (describe).  Waits for its own results (the path comes to the host)."""
+        gpt/alignment.py -> a list of per-row dictionaries (describe).  Waits for its own results (the path comes to the host).
+        plan: the FramePlan stage B ran under (duration.py) - every time then follows its frame -> code map."""
         from ..gpt.alignment import describe
         rows = [np.asarray(c, np.int32).reshape(-1) for c in code_list]
         spc, sr = self.cfg["gpt"]["mel_length_compression"], self.cfg["data"]["sampling_rate"]
@@ -744,7 +761,8 @@ class SynthesizerTrn:
         attn, mass = self.rt.gpt_text_alignment(refer, rl, texts, rows, layers=layers, head_weights=head_weights, cond=cond)
         path = self.rt.op_monotone_path(torch.log(attn.clamp_min(1e-12)), [len(c) for c in rows], [len(t) + 2 for t in texts])
         path, mass = path.cpu().numpy(), mass.cpu().numpy()
-        return [describe(path[b], len(rows[b]), texts[b], mass[b], spc, sr, space_id) for b in range(len(rows))]
+        bounds = [None if plan is None else plan.code_bounds(b) for b in range(len(rows))]
+        return [describe(path[b], len(rows[b]), texts[b], mass[b], spc, sr, space_id, frame_bounds=bounds[b]) for b in range(len(rows))]
 
     def align(self, text, text_length, codes, code_lengths=None, refer=None, refer_lengths=None, *, speaker=None, layers=None,
               head_weights=None, space_id=None):

@@ -54,6 +54,8 @@ def main():
     ap.add_argument("--pause-ms", type=float, nargs=4, metavar=("SENTENCE", "CLAUSE", "WORD", "HARD"),
                     help="with --text-file: the silence behind a chunk by how it ended (default 400 200 60 0; unmeasured under a trained checkpoint)")
     ap.add_argument("--max-len", type=int, default=160, help="with --text-file: the most characters of a chunk")
+    ap.add_argument("--speed", type=float, help="the speaking rate, 0.25 .. 4.0 (infer(speed=) / infer_long(speed=): 0.8 is slower, 1.25 faster; "
+                                                "audio quality at other rates is unmeasured under a trained checkpoint)")
     a = ap.parse_args()
     if a.voice and (a.wav or a.save_voice):
         ap.error("--voice stands in the place of the prompt: not with --wav or --save-voice")
@@ -80,6 +82,8 @@ def main():
     vqvae = load_model("vqvae", a.ckpt, None, device)                                       # api.py:33
     text_lengths = torch.LongTensor([text_tokens.shape[-1]])
     kw = dict(max_generate_length=a.max_generate_length, seed=a.seed, suppress_eos=a.synthetic or a.ckpt.startswith("synthetic"))
+    if a.speed is not None:
+        kw.update(speed=a.speed)
     if a.timings:
         space = None
         if a.vocab and not a.ids:
@@ -102,7 +106,7 @@ def main():
         return wav
     if a.text_file:
         a.long = dict(text=open(a.text_file, encoding="utf-8").read(), max_len=a.max_len, seed=a.seed, suppress_eos=kw["suppress_eos"],
-                      max_generate_length=a.max_generate_length)
+                      max_generate_length=a.max_generate_length, speed=a.speed)
         if a.pause_ms:
             a.long["pauses_ms"] = dict(zip(("sentence", "clause", "word", "hard"), a.pause_ms))
         if a.vocab:
@@ -115,7 +119,7 @@ def main():
         with torch.no_grad():
             wav, chunks = vqvae.infer_long(a.long.pop("text"), return_chunks=True, **speaker, **a.long)
         write_wav(a.out, wav.squeeze(0), 24000)
-        cut = sum(c["codes"] >= a.max_generate_length - 1 for c in chunks)
+        cut = sum(c["codes"] is not None and c["codes"] >= a.max_generate_length - 1 for c in chunks)      # (None under --speed)
         print(f"{a.out}: {wav.shape[-1] / 24000:.2f} s of audio from {len(chunks)} chunks of {a.text_file}"
               + (f"; {cut} chunks ran into --max-generate-length and were cut short" if cut and not kw["suppress_eos"] else ""))
 

@@ -340,6 +340,22 @@ int dtts_diff_conditioning(dtts_handle* h, const float* refer, const int* lens, 
 int dtts_diff_timestep_independent(dtts_handle* h, const float* latent_cm, const int* lens_n, int B, int nmax,
                                    const float* cond, float* code_emb, void* stream);
 
+/* The same expanded to a frame plan - the reference's hook for any expected_seq_len, F.interpolate(code_emb, size=expected_seq_len,
+ * mode='nearest') (vqvae/diff_model.py:252), which do_spectrogram_diffusion fixes to 4 n.  frames HOST [B]: row b's frame count T_b in
+ * 1 .. Tmax; durations HOST [B*nmax] or NULL: NULL = the uniform map, F.interpolate's own float32 rule
+ * m[t] = min((int)floorf(float(t) * (float(n_b) / float(T_b))), n_b - 1), each operation rounded once; else row b's code j owns
+ * durations[b*nmax + j] >= 0 consecutive frames (repeat_interleave), the row's sum == frames[b].  code_emb DEVICE [B,768,Tmax], columns
+ * at and beyond T_b left as the caller's.  frames == NULL is dtts_diff_timestep_independent (Tmax ignored): the same launches.  Refused
+ * with a message, before any launch: a frame count outside 1 .. Tmax, a duration sum other than frames[b], Tmax % 4 != 0. */
+int dtts_diff_timestep_independent_ex(dtts_handle* h, const float* latent_cm, const int* lens_n, int B, int nmax, const float* cond,
+                                      const int* frames, const int* durations, int Tmax, float* code_emb, void* stream);
+
+/* Unit entry of the two frame-map kernels behind dtts_diff_timestep_independent_ex (the index rule of F.interpolate nearest,
+ * vqvae/diff_model.py:252, and repeat_interleave): lens_n / frames / durations HOST as above -> map_out DEVICE int [B,Tmax], row b's
+ * frame -> code map; columns at and beyond frames[b] are written as -1.  The same refusals. */
+int dtts_op_frame_map(dtts_handle* h, const int* lens_n, const int* frames, const int* durations, int B, int nmax, int Tmax, int* map_out,
+                      void* stream);
+
 /* DiffusionTts.forward with precomputed_aligned_embeddings (vqvae/diff_model.py:262-322) at sampling
  * step `step` (0..diff_steps-1; the model sees timestep_map[step]).  x [B,128,T], code_emb [B,768,T]
  * (ignored when cond_free) -> out [B,256,T]. */
