@@ -33,10 +33,20 @@ class DttsConfig(C.Structure):
     ]
 
 
+class DttsGptRowOptions(C.Structure):
+    """dtts_gpt_row_options: the sampling settings of one row of a decode session"""
+    _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("repetition_penalty", C.c_float), ("typical_mass", C.c_float),
+                ("min_p", C.c_float), ("epsilon_cutoff", C.c_float), ("top_k", C.c_int), ("max_generate_length", C.c_int),
+                ("no_repeat_ngram_size", C.c_int), ("min_length", C.c_int), ("min_new_tokens", C.c_int), ("exp_decay_start", C.c_int),
+                ("exp_decay_factor", C.c_double), ("suppress_tokens", c_int_p), ("n_suppress_tokens", C.c_int),
+                ("begin_suppress_tokens", c_int_p), ("n_begin_suppress_tokens", C.c_int)]
+
+
 class DttsGptOptions(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("seed", C.c_ulonglong), ("sample_ids", c_int_p), ("max_generate_length", C.c_int), ("top_k", C.c_int),
                 ("top_p", C.c_float), ("temperature", C.c_float), ("repetition_penalty", C.c_float), ("suppress_eos", C.c_int),
-                ("forced_uniforms", C.c_void_p), ("forced_codes", c_int_p), ("row_seeds", c_u64_p), ("typical_mass", C.c_float),
+                ("forced_uniforms", C.c_void_p), ("forced_codes", c_int_p), ("row_seeds", c_u64_p),
+                ("row_options", C.POINTER(DttsGptRowOptions)), ("typical_mass", C.c_float),
                 ("no_repeat_ngram_size", C.c_int), ("min_length", C.c_int), ("min_new_tokens", C.c_int), ("exp_decay_start", C.c_int),
                 ("exp_decay_factor", C.c_double), ("suppress_tokens", c_int_p), ("n_suppress_tokens", C.c_int),
                 ("begin_suppress_tokens", c_int_p), ("n_begin_suppress_tokens", C.c_int), ("min_p", C.c_float), ("epsilon_cutoff", C.c_float),
@@ -97,6 +107,8 @@ SIGNATURES = {
                                            C.c_float, C.c_float, C.c_float, C.c_int, c_int_p, C.c_void_p]),
     "dtts_op_sample_logits_opts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DttsGptOptions), c_int_p, C.c_int, c_int_p,
                                              c_int_p, c_int_p, C.c_void_p, c_int_p, C.c_void_p]),
+    "dtts_op_sample_logits_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DttsGptOptions), C.POINTER(DttsGptRowOptions),
+                                             c_int_p, C.c_int, c_int_p, c_int_p, c_int_p, C.c_void_p, c_int_p, C.c_void_p]),
     "dtts_gpt_beam_generate": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p, C.c_int, c_int_p, c_int_p, C.c_int, C.c_int,
                                          C.POINTER(DttsGptOptions), C.c_int, c_int_p, c_int_p, c_float_p, C.c_void_p]),
     "dtts_gpt_beam_finish": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p, c_float_p, C.c_void_p]),

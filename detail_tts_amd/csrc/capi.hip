@@ -332,18 +332,51 @@ static void check_gpt_beams(const dtts_gpt_options* o) {
     }
 }
 
-static void check_gpt_options(const dtts_gpt_options* o) {
+// the sampling fields every row of a session has: the scalar fields of a uniform session, or one row's record written into them
+static void check_gpt_sampling(const dtts_gpt_options* o, int V) {
+    DTTS_REQUIRE(o->typical_mass >= 0.f && o->typical_mass <= 1.f, "options: typical_mass outside [0, 1] (0 = off)");      // NaN fails both
+    DTTS_REQUIRE(o->temperature > 0.f && o->temperature < INFINITY && o->top_p >= 0.f && o->top_p <= 1.f && o->repetition_penalty > 0.f &&
+                     o->repetition_penalty < INFINITY, "options: temperature / top_p / repetition_penalty out of range");
+    check_gpt_processors(o, V);
+}
+
+// dtts_gpt_options.row_options: every row passes the checks the scalar fields get, before any launch; the error names the row
+static void check_gpt_rows(const dtts_gpt_options* o, int B, int V, bool caps) {
+    DTTS_REQUIRE(B >= 1, "options: row_options needs the row count");
+    DTTS_REQUIRE(o->num_beams <= 1, "options: row_options with num_beams > 1 (a beam session is uniform)");
+    int cap_max = 0;
+    for (int b = 0; b < B; ++b) {
+        const dtts_gpt_row_options& r = o->row_options[b];
+        dtts_gpt_options t = *o;
+        t.temperature = r.temperature; t.top_p = r.top_p; t.repetition_penalty = r.repetition_penalty; t.typical_mass = r.typical_mass;
+        t.min_p = r.min_p; t.epsilon_cutoff = r.epsilon_cutoff; t.top_k = r.top_k;
+        t.no_repeat_ngram_size = r.no_repeat_ngram_size; t.min_length = r.min_length; t.min_new_tokens = r.min_new_tokens;
+        t.exp_decay_start = r.exp_decay_start; t.exp_decay_factor = r.exp_decay_factor;
+        t.suppress_tokens = r.suppress_tokens; t.n_suppress_tokens = r.n_suppress_tokens;
+        t.begin_suppress_tokens = r.begin_suppress_tokens; t.n_begin_suppress_tokens = r.n_begin_suppress_tokens;
+        try {
+            check_gpt_sampling(&t, V);
+            if (caps)
+                DTTS_REQUIRE(r.max_generate_length >= 1 && r.max_generate_length <= o->max_generate_length,
+                             "row_options: max_generate_length outside 1 .. the call's max_generate_length");
+        } catch (const dtts::Error& e) {
+            throw dtts::Error(e.code, "row_options[" + std::to_string(b) + "]: " + e.what());
+        }
+        cap_max = std::max(cap_max, r.max_generate_length);
+    }
+    if (caps) DTTS_REQUIRE(cap_max == o->max_generate_length, "options: max_generate_length has to equal the largest row_options[].max_generate_length");
+}
+
+static void check_gpt_options(const dtts_gpt_options* o, int B) {
     DTTS_REQUIRE(o, "options");
     DTTS_REQUIRE(o->struct_size == sizeof(dtts_gpt_options),
                  "dtts_gpt_options.struct_size does not match this library's layout: start from dtts_gpt_options_init() (built against another include/detail_hip.h?)");
     DTTS_REQUIRE(o->sample_ids, "options: sample_ids");
-    DTTS_REQUIRE(o->typical_mass >= 0.f && o->typical_mass <= 1.f, "options: typical_mass outside [0, 1] (0 = off)");      // NaN fails both
     DTTS_REQUIRE(o->token_wgs == 0 || o->token_wgs == 128 || o->token_wgs == 64 || o->token_wgs == 32, "options: token_wgs is 0 (the handle's option), 128, 64 or 32");
     DTTS_REQUIRE(o->prompt_codes || !o->prompt_lens, "options: prompt_lens without prompt_codes");
     DTTS_REQUIRE(!o->prompt_codes || (o->prompt_lens && o->prompt_stride >= 0), "options: prompt_codes needs prompt_lens and prompt_stride >= 0");
-    DTTS_REQUIRE(o->temperature > 0.f && o->temperature < INFINITY && o->top_p >= 0.f && o->top_p <= 1.f && o->repetition_penalty > 0.f &&
-                     o->repetition_penalty < INFINITY, "options: temperature / top_p / repetition_penalty out of range");
-    check_gpt_processors(o, 8194);
+    if (o->row_options) check_gpt_rows(o, B, 8194, true);
+    else check_gpt_sampling(o, 8194);
     check_gpt_beams(o);
 }
 
@@ -351,7 +384,7 @@ int dtts_gpt_generate(dtts_handle* h, const float* refer, const int* refer_lens,
                       int Lt_max, int B, const dtts_gpt_options* opts, int* codes_out, int* ncodes_out, float* latents_cm,
                       int lat_stride, void* stream) {
     DTTS_API_BEGIN
-    check_gpt_options(opts);
+    check_gpt_options(opts, B);
     h->m->gpt_generate(refer, refer_lens, Tr, text, text_lens, Lt_max, B, *opts, codes_out, ncodes_out, latents_cm, lat_stride,
                        (hipStream_t)stream);
     DTTS_API_END(h)
@@ -360,7 +393,7 @@ int dtts_gpt_generate(dtts_handle* h, const float* refer, const int* refer_lens,
 int dtts_gpt_prefill(dtts_handle* h, const float* refer, const int* refer_lens, int Tr, const int* text, const int* text_lens,
                      int Lt_max, int B, const dtts_gpt_options* opts, float* latents_cm, int lat_stride, void* stream) {
     DTTS_API_BEGIN
-    check_gpt_options(opts);
+    check_gpt_options(opts, B);
     h->m->gpt_prefill(refer, refer_lens, Tr, text, text_lens, Lt_max, B, *opts, latents_cm, lat_stride, (hipStream_t)stream);
     DTTS_API_END(h)
 }
@@ -369,7 +402,7 @@ int dtts_gpt_beam_generate(dtts_handle* h, const float* refer, const int* refer_
                            int Lt_max, int B, const dtts_gpt_options* opts, int nrs, int* seqs_out, int* lens_out, float* scores_out,
                            void* stream) {
     DTTS_API_BEGIN
-    check_gpt_options(opts);
+    check_gpt_options(opts, B);
     DTTS_REQUIRE(opts->num_beams > 1, "dtts_gpt_beam_generate: options.num_beams has to be 2 .. 16");
     DTTS_REQUIRE(nrs >= 1 && nrs <= opts->num_beams, "dtts_gpt_beam_generate: num_return_sequences outside 1 .. num_beams");
     DTTS_REQUIRE(seqs_out && lens_out && scores_out, "dtts_gpt_beam_generate: null output");
@@ -396,6 +429,7 @@ int dtts_op_beam_step(dtts_handle* h, const float* logits, int U, int V, const d
     check_gpt_processors(opts, V);
     check_gpt_beams(opts);
     DTTS_REQUIRE(opts->num_beams >= 1, "op_beam_step: options.num_beams has to be 1 .. 16");
+    DTTS_REQUIRE(!opts->row_options, "op_beam_step: row_options (a beam session is uniform)");
     h->m->op_beam_step(logits, U, V, *opts, step, prompt, prompt_len, run_seq, run_score, fin_seq, fin_score, fin_flag, fin_len, unsat, done,
                        parents, tokens, cand_score, cand_beam, cand_tok, (hipStream_t)stream);
     DTTS_API_END(h)
@@ -456,8 +490,29 @@ int dtts_op_sample_logits_opts(dtts_handle* h, const float* logits, int R, int V
     DTTS_REQUIRE(opts->temperature > 0.f && opts->temperature < INFINITY && opts->top_p >= 0.f && opts->top_p <= 1.f &&
                      opts->repetition_penalty > 0.f && opts->repetition_penalty < INFINITY, "options: temperature / top_p / repetition_penalty out of range");
     check_gpt_processors(opts, V);
+    if (opts->row_options) {                         // (the scalar fields are then not read: every row gets the checks they get)
+        DTTS_REQUIRE(R >= 1 && R <= dtts::GEMV_MAXB, "op_sample_logits_opts: rows 1..16");
+        DTTS_REQUIRE(opts->num_beams <= 1, "op_sample_logits_opts: row_options with num_beams > 1");
+        check_gpt_rows(opts, R, V, false);
+    }
     h->m->op_sample_logits_opts(logits, R, V, *opts, history, hist_stride, hist_lens, fills, prompt_lens, uniforms, tokens_out,
                                 (hipStream_t)stream);
+    DTTS_API_END(h)
+}
+
+int dtts_op_sample_logits_rows(dtts_handle* h, const float* logits, int R, int V, const dtts_gpt_options* opts,
+                               const dtts_gpt_row_options* rows, const int* history, int hist_stride, const int* hist_lens, const int* fills,
+                               const int* prompt_lens, const float* uniforms, int* tokens_out, void* stream) {
+    DTTS_API_BEGIN
+    DTTS_REQUIRE(opts && rows, "op_sample_logits_rows: options / rows");
+    DTTS_REQUIRE(opts->struct_size == sizeof(dtts_gpt_options),
+                 "dtts_gpt_options.struct_size does not match this library's layout: start from dtts_gpt_options_init()");
+    DTTS_REQUIRE(R >= 1 && R <= dtts::GEMV_MAXB, "op_sample_logits_rows: rows 1..16");
+    dtts_gpt_options o = *opts;
+    o.row_options = rows;
+    o.num_beams = 0;
+    check_gpt_rows(&o, R, V, false);
+    h->m->op_sample_logits_opts(logits, R, V, o, history, hist_stride, hist_lens, fills, prompt_lens, uniforms, tokens_out, (hipStream_t)stream);
     DTTS_API_END(h)
 }
 
@@ -506,7 +561,7 @@ int dtts_gpt_forward_losses(dtts_handle* h, const float* refer, const int* refer
 int dtts_gpt_generate_cond(dtts_handle* h, const float* cond, const int* text, const int* text_lens, int Lt_max, int B,
                            const dtts_gpt_options* opts, int* codes_out, int* ncodes_out, float* latents_cm, int lat_stride, void* stream) {
     DTTS_API_BEGIN
-    check_gpt_options(opts);
+    check_gpt_options(opts, B);
     DTTS_REQUIRE(cond, "dtts_gpt_generate_cond: cond");
     h->m->gpt_generate(nullptr, nullptr, 0, text, text_lens, Lt_max, B, *opts, codes_out, ncodes_out, latents_cm, lat_stride, (hipStream_t)stream, cond);
     DTTS_API_END(h)
@@ -515,7 +570,7 @@ int dtts_gpt_generate_cond(dtts_handle* h, const float* cond, const int* text, c
 int dtts_gpt_prefill_cond(dtts_handle* h, const float* cond, const int* text, const int* text_lens, int Lt_max, int B,
                           const dtts_gpt_options* opts, float* latents_cm, int lat_stride, void* stream) {
     DTTS_API_BEGIN
-    check_gpt_options(opts);
+    check_gpt_options(opts, B);
     DTTS_REQUIRE(cond, "dtts_gpt_prefill_cond: cond");
     h->m->gpt_prefill(nullptr, nullptr, 0, text, text_lens, Lt_max, B, *opts, latents_cm, lat_stride, (hipStream_t)stream, cond);
     DTTS_API_END(h)
@@ -524,7 +579,7 @@ int dtts_gpt_prefill_cond(dtts_handle* h, const float* cond, const int* text, co
 int dtts_gpt_beam_generate_cond(dtts_handle* h, const float* cond, const int* text, const int* text_lens, int Lt_max, int B,
                                 const dtts_gpt_options* opts, int nrs, int* seqs_out, int* lens_out, float* scores_out, void* stream) {
     DTTS_API_BEGIN
-    check_gpt_options(opts);
+    check_gpt_options(opts, B);
     DTTS_REQUIRE(cond, "dtts_gpt_beam_generate_cond: cond");
     DTTS_REQUIRE(opts->num_beams > 1, "dtts_gpt_beam_generate: options.num_beams has to be 2 .. 16");
     DTTS_REQUIRE(nrs >= 1 && nrs <= opts->num_beams, "dtts_gpt_beam_generate: num_return_sequences outside 1 .. num_beams");

@@ -72,9 +72,12 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_step_kernel(const BeamParam
         return;
     }
     const int n_row = min(2 * K, V);                     // candidates a row can contribute
-    const float rp = ctl->repetition_penalty;
+    // (a beam session is always uniform - per-row settings are refused on the host - so the utterance's first row speaks for all)
+    const float rp = ctl->repetition_penalty[row0];
     const unsigned char* const tok_mask = ctl->tok_mask;
-    const int ngram = ctl->ngram;
+    const int ngram = ctl->ngram[row0];
+    const float* const decay_row = ctl->decay_mul + ctl->decay_tab[row0];
+    const int decay_n = ctl->decay_n[row0];
     int* const hist = ctl->hist;
 
     for (int k = 0; k < K; ++k) {
@@ -111,9 +114,9 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_step_kernel(const BeamParam
         const int eos_off = (ctl->suppress_eos || step < ctl->stop_from[row]) ? p.eos : -1;
         int eos_dec = -1;
         float dmul = 0.f;
-        if (ctl->decay_mul && eos_off < 0) {
+        if (decay_n > 0 && eos_off < 0) {
             const int i = step - ctl->decay_off[row];
-            if (i > 0) { dmul = ctl->decay_mul[i < ctl->decay_n ? i : ctl->decay_n - 1]; eos_dec = p.eos; }
+            if (i > 0) { dmul = decay_row[i < decay_n ? i : decay_n - 1]; eos_dec = p.eos; }
         }
         const float base = p.run_score[row];
 #pragma unroll

@@ -16,11 +16,15 @@ struct GptCtl {
     int lp[GEMV_MAXB];            // prefix length of the row: cond (1) + text positions + start_mel (1)
     int sample_id[GEMV_MAXB];     // Philox stream id of the row
     unsigned long long seed[GEMV_MAXB];     // Philox seed of the row (rows of two requests may share a session)
-    float repetition_penalty, temperature, top_p;
-    int top_k;                    // <= 0: disabled
-    float typical_mass;           // TypicalLogitsWarper mass (HF: between the repetition penalty and the temperature); <= 0 or >= 1: off
+    // ---- the sampling settings are the ROW's own (rows of different requests share a session); a uniform session holds its one value
+    // in every slot.  The sampler runs one workgroup per row and reads slot blockIdx.x, so every value stays uniform over the workgroup.
+    float repetition_penalty[GEMV_MAXB], temperature[GEMV_MAXB], top_p[GEMV_MAXB];
+    int top_k[GEMV_MAXB];         // <= 0: disabled
+    float typical_mass[GEMV_MAXB];      // TypicalLogitsWarper mass (HF: between the repetition penalty and the temperature); <= 0 or >= 1: off
     int suppress_eos;
     int max_steps;                // tokens to generate at most: steps >= max_steps are no-ops (a replayed graph may over-run)
+    int row_max_steps[GEMV_MAXB]; // the row's own cap, 1 .. max_steps: a row whose cap is BELOW max_steps is latched finished by the step that
+                                  // writes its last code (the session then ends with its slowest live row, not at the largest cap)
     const float* forced_u;        // optional [B][u_stride] uniforms replacing the Philox draw (tests)
     int u_stride;
     const int* forced_tokens;     // optional [B][f_stride] teacher-forced tokens (no sampling, still recorded)
@@ -32,19 +36,21 @@ struct GptCtl {
                                   // [1, 8192, c_1 .. c_m]; the input embedding of generated token `step` sits at mel position step + pos_off
     // ---- HF's remaining decode-time logits processors (generation/logits_process.py), each behind a field that is uniform over the
     // workgroup; all zero / null = off (the sampler then does what it did without them).  "Step" is the row's ctl->step.
-    int ngram;                    // NoRepeatNGramLogitsProcessor(n), 1 .. SAMP_NGRAM_MAX; 0: off.  Needs hist
+    int ngram[GEMV_MAXB];         // NoRepeatNGramLogitsProcessor(n), 1 .. SAMP_NGRAM_MAX; 0: off.  Needs hist (kept when ANY row's n > 0)
     int* hist;                    // [B][hist_stride] the row's ORDERED input_ids without the fill-id-1 prefix columns: hist_n0[b] ids seeded
     int hist_stride;              // at prefill (8192, an acoustic prompt's codes), then one token per step appended by the sampler
     int hist_n0[GEMV_MAXB];
     int nfill[GEMV_MAXB];         // min(n, fill ids in front of hist): the only fill ids an n-gram can reach (the prefix is not materialised)
     int stop_from[GEMV_MAXB];     // MinLength + MinNewTokensLength folded: the first step at which the stop token may be drawn
-    const float* decay_mul;       // ExponentialDecayLengthPenalty: [decay_n] float(factor^i - 1), i = step - decay_off[b] > 0; null: off
-    int decay_n;
+    const float* decay_mul;       // ExponentialDecayLengthPenalty: one table of float(factor^i - 1); row b owns the slice [decay_tab[b],
+    int decay_tab[GEMV_MAXB];     // decay_tab[b] + decay_n[b]), indexed by i = step - decay_off[b] > 0 (clamped to the slice's last entry);
+    int decay_n[GEMV_MAXB];       // decay_n[b] = 0: the row's penalty is off
     int decay_off[GEMV_MAXB];
     const unsigned char* tok_mask;      // [V] bit 0: SuppressTokens (always -inf), bit 1: SuppressTokensAtBegin (at step begin_step[b]); null: off
+    int mask_stride;              // 0: one mask for the session; V: row b's mask starts at tok_mask + b * V
     int begin_step[GEMV_MAXB];
-    float min_p;                  // MinPLogitsWarper (after top-k / top-p); <= 0: off
-    float eps_cutoff;             // EpsilonLogitsWarper (after min_p); <= 0: off
+    float min_p[GEMV_MAXB];       // MinPLogitsWarper (after top-k / top-p); <= 0: off
+    float eps_cutoff[GEMV_MAXB];  // EpsilonLogitsWarper (after min_p); <= 0: off
 };
 constexpr int SAMP_NGRAM_MAX = 16;
 

@@ -819,14 +819,20 @@ __global__ __launch_bounds__(SAMP_THREADS) void sampler_kernel(const SamplerPara
     const bool pos_pf = p.x_next && p.C <= SAMP_THREADS;
     const int pos_row = step + ctl->pos_off[b];           // pos_off = 1 (start_mel alone) or m + 2 behind an acoustic prompt
     if (pos_pf && tid < p.C) pos_next = p.mel_pos[(long long)pos_row * p.C + tid];
-    const int top_k = ctl->top_k;
-    const float top_p = ctl->top_p;
+    // (the sampling settings are the row's own slot of the control block: indexed by the block alone, so every lane loads from one
+    // address and every branch on them is uniform over the workgroup)
+    const int top_k = ctl->top_k[b];
+    const float top_p = ctl->top_p[b];
+    const float rp = ctl->repetition_penalty[b], temp = ctl->temperature[b], typical_mass = ctl->typical_mass[b];
+    const int row_cap = ctl->row_max_steps[b], max_steps = ctl->max_steps;
     // (the switches of HF's remaining processors are requested here, with the fields above, so that no phase behind a barrier starts
     // with a load of its own)
     int* const hist = ctl->hist;                          // null unless the n-gram processor runs: the row's ordered token history
-    const int ngram = ctl->ngram;
-    const unsigned char* const tok_mask = ctl->tok_mask;
-    const float min_p = ctl->min_p, eps_cutoff = ctl->eps_cutoff;
+    const int ngram = ctl->ngram[b];
+    const unsigned char* const tok_mask = ctl->tok_mask ? ctl->tok_mask + (long long)b * ctl->mask_stride : nullptr;
+    const float min_p = ctl->min_p[b], eps_cutoff = ctl->eps_cutoff[b];
+    const float* const decay_row = ctl->decay_mul + ctl->decay_tab[b];      // (not dereferenced while decay_n is 0)
+    const int decay_n = ctl->decay_n[b];
     int token;
     // forced token of this (row, step), or -1: sample.  A row may be forced for a prefix only (UnifiedVoice.inference_speech_tortoise's
     // input_tokens, gpt/model.py:533-537) - the choice is uniform over the workgroup (one row per workgroup)
@@ -836,21 +842,20 @@ __global__ __launch_bounds__(SAMP_THREADS) void sampler_kernel(const SamplerPara
     } else {
         // 1. logits = head GEMV partials + bias (its finish), repetition penalty over every id in the row's input_ids, temperature
         const unsigned char* seen = p.seen + (long long)b * V;
-        const float rp = ctl->repetition_penalty, temp = ctl->temperature;
         // MinLength / MinNewTokensLength (HF runs them behind the penalty: -inf either way) share suppress_eos' compare
         const int eos_off = (ctl->suppress_eos || step < ctl->stop_from[b]) ? p.eos : -1;
         // ExponentialDecayLengthPenalty: stop score += |stop score| * float(factor^i - 1), behind the penalty and in front of the
         // temperature; two rounded float operations as torch does them (no contraction).  A stop score that is -inf stays -inf.
         int eos_dec = -1;
         float dmul = 0.f;
-        if (ctl->decay_mul && eos_off < 0) {
+        if (decay_n > 0 && eos_off < 0) {
             const int i = step - ctl->decay_off[b];
             if (i > 0) {
-                dmul = ctl->decay_mul[i < ctl->decay_n ? i : ctl->decay_n - 1];
+                dmul = decay_row[i < decay_n ? i : decay_n - 1];
                 eos_dec = p.eos;
             }
         }
-        const bool typical = ctl->typical_mass > 0.f && ctl->typical_mass < 1.f;
+        const bool typical = typical_mass > 0.f && typical_mass < 1.f;
         // (the maximum of the processed scores rides along: top-k keeps it, so it is the softmax maximum of step 3 unless the typical
         // warper - which may drop the most probable token - runs; a maximum does not depend on the order it is taken in)
         float tmax = -INFINITY;
@@ -966,7 +971,7 @@ __global__ __launch_bounds__(SAMP_THREADS) void sampler_kernel(const SamplerPara
             int cnt = 0;
             for (int i = i0; i < i0 + per && i < V; ++i) {
                 run += expf(sv[sidx[i]] - lse);
-                cnt += run < ctl->typical_mass ? 1 : 0;
+                cnt += run < typical_mass ? 1 : 0;
             }
             if (tid == 0) sh_i[0] = 0;
             __syncthreads();
@@ -1209,7 +1214,9 @@ __global__ __launch_bounds__(SAMP_THREADS) void sampler_kernel(const SamplerPara
     if (tid == 0) {
         p.codes[(long long)b * p.codes_stride + step] = token;
         p.seen[(long long)b * V + token] = 1;
-        if (token == p.eos) p.finished[b] = 1;
+        // a row that has written the last code of its OWN cap is finished (only where that cap is below the session's: a uniform
+        // session's flags are what its stop tokens make them)
+        if (token == p.eos || (row_cap < max_steps && step + 1 >= row_cap)) p.finished[b] = 1;
         if (hist) hist[(long long)b * ctl->hist_stride + ctl->hist_n0[b] + step] = token;      // (step < max_steps: inside the row)
         ctl->step[b] = step + 1;                 // only this workgroup reads or writes step[b] inside this launch
     }

@@ -132,8 +132,8 @@ struct GptSession {
     unsigned char* seen = nullptr;
     int *finished = nullptr, *codes = nullptr, *forced = nullptr;
     int* hist = nullptr;               // [B][cap] ordered token history (no_repeat_ngram_size)
-    unsigned char* tok_mask = nullptr; // [V] suppress_tokens / begin_suppress_tokens bits
-    float* decay_mul = nullptr;        // [G + 1] exponential_decay_length_penalty multipliers
+    unsigned char* tok_mask = nullptr; // [V] suppress_tokens / begin_suppress_tokens bits ([B][V] under row_options)
+    float* decay_mul = nullptr;        // [<= B][G + 1] exponential_decay_length_penalty multipliers, one slice per distinct factor
     GptCtl* ctl = nullptr;
     // persistent token kernel (gpt_token.hip): exchange arena, logits rows, error flag, launch counter
     unsigned long long* xch = nullptr;
@@ -782,6 +782,8 @@ private:
         bool has_cond = false;            // the session was given cond [B, C] instead of a prompt mel: gpt_replay_ holds that vector
         std::vector<int> refer_lens, text, text_lens, sample_ids, forced_codes, prompt_codes, prompt_lens, suppress, begin_suppress;
         std::vector<unsigned long long> row_seeds;
+        std::vector<dtts_gpt_row_options> rows;         // dtts_gpt_options.row_options, and per row its two id lists ([2b], [2b + 1])
+        std::vector<std::vector<int>> row_ids;
         dtts_gpt_options o;
         float* latents_cm = nullptr;
     } replay_;

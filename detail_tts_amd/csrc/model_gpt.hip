@@ -310,11 +310,6 @@ void gpt_decay_multipliers(double factor, int n, float* out) {
         out[i] = (float)(m < DECAY_MUL_MAX ? m : DECAY_MUL_MAX);
     }
 }
-static std::vector<float> processor_decay_table(double factor, int n) {
-    std::vector<float> t(n, 0.f);
-    gpt_decay_multipliers(factor, n, t.data());
-    return t;
-}
 // MinLength and MinNewTokensLength folded: the first decode step at which the stop token may be drawn.  At step j HF sees
 // input_len + j ids, j - forced_prefix of them behind its prompt: the stop is -inf while input_len + j < min_length or
 // j - forced_prefix < min_new_tokens.  (forced_prefix < 0: the unit entry's rows, which are already some tokens behind the prompt.)
@@ -322,6 +317,80 @@ int gpt_first_stop_step(int input_len, int forced_prefix, int min_length, int mi
     return std::max(0, std::max(min_length - input_len, min_new_tokens > 0 ? forced_prefix + min_new_tokens : 0));
 }
 static bool processors_mask_on(const dtts_gpt_options& o) { return o.n_suppress_tokens > 0 || o.n_begin_suppress_tokens > 0; }
+
+// ---- per-row sampling settings: ONE way into the control block.  Row b's settings are its own record (dtts_gpt_options.row_options) or
+// the session's scalar fields; a uniform session writes its one value into every slot and the sampler reads slot blockIdx.x either way.
+static dtts_gpt_row_options gpt_row_settings(const dtts_gpt_options& o, int b) {
+    if (o.row_options) return o.row_options[b];
+    dtts_gpt_row_options r{};
+    r.temperature = o.temperature; r.top_p = o.top_p; r.repetition_penalty = o.repetition_penalty; r.typical_mass = o.typical_mass;
+    r.min_p = o.min_p; r.epsilon_cutoff = o.epsilon_cutoff; r.top_k = o.top_k; r.max_generate_length = o.max_generate_length;
+    r.no_repeat_ngram_size = o.no_repeat_ngram_size; r.min_length = o.min_length; r.min_new_tokens = o.min_new_tokens;
+    r.exp_decay_start = o.exp_decay_start; r.exp_decay_factor = o.exp_decay_factor;
+    r.suppress_tokens = o.suppress_tokens; r.n_suppress_tokens = o.n_suppress_tokens;
+    r.begin_suppress_tokens = o.begin_suppress_tokens; r.n_begin_suppress_tokens = o.n_begin_suppress_tokens;
+    return r;
+}
+static dtts_gpt_options gpt_row_as_options(const dtts_gpt_options& o, const dtts_gpt_row_options& r) {
+    dtts_gpt_options t = o;
+    t.suppress_tokens = r.suppress_tokens; t.n_suppress_tokens = r.n_suppress_tokens;
+    t.begin_suppress_tokens = r.begin_suppress_tokens; t.n_begin_suppress_tokens = r.n_begin_suppress_tokens;
+    return t;
+}
+// What the host hands the sampler besides the scalars: the token masks ([V] for a uniform session, [B][V] under row_options) and ONE
+// decay table in which rows of the same factor share a slice of decay_n entries.  Fills the control block's slots of rows 0 .. B-1
+// (max_steps = G is the caller's); the caller uploads the two tables and points tok_mask / decay_mul at them when they are not empty.
+struct GptRowTables {
+    std::vector<unsigned char> mask;
+    std::vector<float> decay;
+    int ngram_max = 0;
+};
+static GptRowTables gpt_ctl_rows(GptCtl& c, const dtts_gpt_options& o, int B, int V, int G, int decay_n) {
+    GptRowTables t;
+    std::vector<double> factors;
+    bool any_mask = false;
+    for (int b = 0; b < B; ++b) {
+        const dtts_gpt_row_options r = gpt_row_settings(o, b);
+        DTTS_REQUIRE(r.no_repeat_ngram_size >= 0 && r.no_repeat_ngram_size <= SAMP_NGRAM_MAX, "no_repeat_ngram_size outside 0 .. 16");
+        c.repetition_penalty[b] = r.repetition_penalty;
+        c.temperature[b] = r.temperature;
+        c.top_p[b] = r.top_p;
+        c.top_k[b] = r.top_k;
+        c.typical_mass[b] = r.typical_mass;
+        c.row_max_steps[b] = o.row_options ? std::min(std::max(r.max_generate_length, 1), G) : G;
+        c.ngram[b] = r.no_repeat_ngram_size;
+        c.min_p[b] = r.min_p;
+        c.eps_cutoff[b] = r.epsilon_cutoff;
+        t.ngram_max = std::max(t.ngram_max, r.no_repeat_ngram_size);
+        any_mask = any_mask || r.n_suppress_tokens > 0 || r.n_begin_suppress_tokens > 0;
+        c.decay_tab[b] = 0;
+        c.decay_n[b] = 0;
+        if (r.exp_decay_factor > 0.0) {
+            size_t k = 0;
+            while (k < factors.size() && factors[k] != r.exp_decay_factor) ++k;
+            if (k == factors.size()) {
+                factors.push_back(r.exp_decay_factor);
+                t.decay.resize((k + 1) * (size_t)decay_n);
+                gpt_decay_multipliers(r.exp_decay_factor, decay_n, t.decay.data() + k * (size_t)decay_n);
+            }
+            c.decay_tab[b] = (int)k * decay_n;
+            c.decay_n[b] = decay_n;
+        }
+    }
+    c.mask_stride = 0;
+    if (any_mask) {
+        if (!o.row_options) t.mask = processor_token_mask(o, V);
+        else {
+            c.mask_stride = V;
+            t.mask.reserve((size_t)B * V);
+            for (int b = 0; b < B; ++b) {
+                const std::vector<unsigned char> m = processor_token_mask(gpt_row_as_options(o, o.row_options[b]), V);
+                t.mask.insert(t.mask.end(), m.begin(), m.end());
+            }
+        }
+    }
+    return t;
+}
 
 // ---- decode session ------------------------------------------------------------------------------------------------------------
 // dtts_gpt_prefill: conditioning encoder + [cond | text | start_mel] prefill (KV cache filled) + the first sampled token; with
@@ -361,6 +430,16 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
             r.has_text_lens = text_lens_host != nullptr;
             r.refer_lens.clear(); r.text_lens.clear(); r.forced_codes.clear(); r.row_seeds.clear();      // nothing of an earlier session survives
             r.prompt_codes.clear(); r.prompt_lens.clear(); r.suppress.clear(); r.begin_suppress.clear();
+            r.rows.clear(); r.row_ids.clear();
+            if (o.row_options) {                     // the rows' settings and their id lists are the session's: kept with it
+                r.rows.assign(o.row_options, o.row_options + B);
+                r.row_ids.resize((size_t)2 * B);
+                for (int b = 0; b < B; ++b) {
+                    const dtts_gpt_row_options& q = o.row_options[b];
+                    if (q.n_suppress_tokens > 0) r.row_ids[2 * b].assign(q.suppress_tokens, q.suppress_tokens + q.n_suppress_tokens);
+                    if (q.n_begin_suppress_tokens > 0) r.row_ids[2 * b + 1].assign(q.begin_suppress_tokens, q.begin_suppress_tokens + q.n_begin_suppress_tokens);
+                }
+            }
             if (o.n_suppress_tokens > 0) r.suppress.assign(o.suppress_tokens, o.suppress_tokens + o.n_suppress_tokens);
             if (o.n_begin_suppress_tokens > 0) r.begin_suppress.assign(o.begin_suppress_tokens, o.begin_suppress_tokens + o.n_begin_suppress_tokens);
             if (refer_lens_host) r.refer_lens.assign(refer_lens_host, refer_lens_host + B);
@@ -400,7 +479,7 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
     const long long kv_bs = (long long)2 * C * cap, kv_layer = kv_bs * B;
     const size_t need = sizeof(float) * ((size_t)NL * kv_layer + (size_t)B * (4 * C + cfg.gpt_heads * 8 * ATT_REC) + (size_t)2 * B * GEMV_PART_FLOATS + 2 * 64 * GEMV_MAXB * 2) +
                         (size_t)B * V + sizeof(int) * ((size_t)2 * B * G + 64) + sizeof(GptCtl) + 64 * 256 +
-                        sizeof(int) * (size_t)B * cap + (size_t)V + sizeof(float) * ((size_t)G + 1) + 4 * 256 +
+                        sizeof(int) * (size_t)B * cap + (size_t)B * V + sizeof(float) * (size_t)B * ((size_t)G + 1) + 4 * 256 +
                         sizeof(int) * ((size_t)2 * B * G + 8 * GEMV_MAXB) + sizeof(float) * ((size_t)G + 1 + 2 * GEMV_MAXB) + 16 * 256 +
                         (tok_ok_ && B <= GPT_TOKEN_ROWS ? sizeof(unsigned long long) * GPT_TOKEN_XCH_WORDS + sizeof(float) * GPT_TOKEN_ROWS * GPT_TOKEN_VS + 1024 : 0);
     if (need > gpt_state_.capacity() || gs_.B != B || gs_.cap != cap || gs_.G != G) {
@@ -424,8 +503,8 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
         n.codes = gpt_state_.i32((size_t)B * G);
         n.forced = gpt_state_.i32((size_t)B * G);
         n.hist = gpt_state_.i32((size_t)B * cap);
-        n.tok_mask = static_cast<unsigned char*>(gpt_state_.raw((size_t)V));
-        n.decay_mul = gpt_state_.f32((size_t)G + 1);
+        n.tok_mask = static_cast<unsigned char*>(gpt_state_.raw((size_t)B * V));      // a mask and a decay slice per row at the most
+        n.decay_mul = gpt_state_.f32((size_t)B * ((size_t)G + 1));
         n.ctl = static_cast<GptCtl*>(gpt_state_.raw(sizeof(GptCtl)));
         if (tok_ok_ && B <= GPT_TOKEN_ROWS) {
             n.xch = static_cast<unsigned long long*>(gpt_state_.raw(sizeof(unsigned long long) * GPT_TOKEN_XCH_WORDS));
@@ -483,10 +562,6 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
     GptCtl& c = ctl_host_;
     std::memset(&c, 0, sizeof(c));
     for (int b = 0; b < B; ++b) { c.lp[b] = lp[b]; c.pos_off[b] = ml[b]; c.sample_id[b] = o.sample_ids[b]; c.seed[b] = o.row_seeds ? o.row_seeds[b] : o.seed; }
-    c.repetition_penalty = o.repetition_penalty;
-    c.temperature = o.temperature;
-    c.top_p = o.top_p;
-    c.typical_mass = o.typical_mass;
     {
         const int wgs = o.token_wgs ? o.token_wgs : opt_tok_wgs_;      // latched: a later set_option does not change a running session's kernel
         if (wgs != gs_.tok_wgs) gpt_drop_graphs();                      // (captured decode graphs hold the previous session's kernel choice)
@@ -496,7 +571,6 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
         if (fuse != gs_.fuse_proj) gpt_drop_graphs();                   // (the captured chain holds K2 + K3 in one form or the other)
         gs_.fuse_proj = fuse;
     }
-    c.top_k = o.top_k;
     c.suppress_eos = o.suppress_eos;
     c.max_steps = G;
     c.forced_u = o.forced_uniforms;
@@ -510,12 +584,10 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
     // ordered ids [8192, prompt codes] (the prompt's own leading 1 is a fill id), then j tokens.  HF's prompt ends behind the forced
     // prefix (input_tokens): k = the leading forced codes >= 0.
     std::vector<int> hist0;
-    std::vector<unsigned char> mask0;
-    std::vector<float> decay0;
+    DTTS_REQUIRE(!o.row_options || !beamK, "row_options with num_beams > 1 (a beam session is uniform)");
+    const GptRowTables tabs = gpt_ctl_rows(c, o, B, V, G, G + 1);
     {
-        const int n = o.no_repeat_ngram_size;
-        DTTS_REQUIRE(n >= 0 && n <= SAMP_NGRAM_MAX, "no_repeat_ngram_size outside 0 .. 16");
-        c.ngram = n;
+        const int n = tabs.ngram_max;                  // (the history is kept when ANY row bans n-grams)
         c.hist = n > 0 ? gs_.hist : nullptr;
         c.hist_stride = cap;
         if (n > 0) hist0.assign((size_t)B * cap, 0);
@@ -524,27 +596,23 @@ void Model::gpt_prefill(const float* refer, const int* refer_lens_host, int Tr, 
             int k = 0;
             if (o.forced_codes)
                 while (k < G && o.forced_codes[(size_t)b * G + k] >= 0) ++k;
+            const dtts_gpt_row_options rw = gpt_row_settings(o, b);
             c.hist_n0[b] = nn;
-            c.nfill[b] = std::min(n, lp[b] - nn);
+            c.nfill[b] = std::min(c.ngram[b], lp[b] - nn);
             if (n > 0) std::copy(mel0.data() + (size_t)b * np_max + lead, mel0.data() + (size_t)b * np_max + ml[b], hist0.data() + (size_t)b * cap);
-            c.stop_from[b] = gpt_first_stop_step(lp[b], k, o.min_length, o.min_new_tokens);
-            c.decay_off[b] = k + o.exp_decay_start;
+            c.stop_from[b] = gpt_first_stop_step(lp[b], k, rw.min_length, rw.min_new_tokens);
+            c.decay_off[b] = k + rw.exp_decay_start;
             c.begin_step[b] = k;
         }
-        if (processors_mask_on(o)) {
-            mask0 = processor_token_mask(o, V);
+        if (!tabs.mask.empty()) {
             c.tok_mask = gs_.tok_mask;
-            DTTS_CHECK_HIP(hipMemcpyAsync(gs_.tok_mask, mask0.data(), mask0.size(), hipMemcpyHostToDevice, s));
+            DTTS_CHECK_HIP(hipMemcpyAsync(gs_.tok_mask, tabs.mask.data(), tabs.mask.size(), hipMemcpyHostToDevice, s));
         }
-        if (o.exp_decay_factor > 0.0) {
-            decay0 = processor_decay_table(o.exp_decay_factor, G + 1);
+        if (!tabs.decay.empty()) {
             c.decay_mul = gs_.decay_mul;
-            c.decay_n = G + 1;
-            DTTS_CHECK_HIP(hipMemcpyAsync(gs_.decay_mul, decay0.data(), sizeof(float) * decay0.size(), hipMemcpyHostToDevice, s));
+            DTTS_CHECK_HIP(hipMemcpyAsync(gs_.decay_mul, tabs.decay.data(), sizeof(float) * tabs.decay.size(), hipMemcpyHostToDevice, s));
         }
         if (n > 0) DTTS_CHECK_HIP(hipMemcpyAsync(gs_.hist, hist0.data(), sizeof(int) * hist0.size(), hipMemcpyHostToDevice, s));
-        c.min_p = o.min_p;
-        c.eps_cutoff = o.epsilon_cutoff;
     }
     DTTS_CHECK_HIP(hipMemcpyAsync(gs_.ctl, &c, sizeof(c), hipMemcpyHostToDevice, s));
     if (o.forced_codes) DTTS_CHECK_HIP(hipMemcpyAsync(gs_.forced, o.forced_codes, sizeof(int) * (size_t)B * G, hipMemcpyHostToDevice, s));
@@ -881,6 +949,13 @@ bool Model::gpt_replay_failed(const GptCtl& hctl, hipStream_t s) {
     o.sample_ids = r.sample_ids.data();
     o.forced_codes = r.forced_codes.empty() ? nullptr : r.forced_codes.data();
     o.row_seeds = r.row_seeds.empty() ? nullptr : r.row_seeds.data();
+    if (!r.rows.empty()) {
+        for (size_t b = 0; b < r.rows.size(); ++b) {
+            r.rows[b].suppress_tokens = r.row_ids[2 * b].empty() ? nullptr : r.row_ids[2 * b].data();
+            r.rows[b].begin_suppress_tokens = r.row_ids[2 * b + 1].empty() ? nullptr : r.row_ids[2 * b + 1].data();
+        }
+        o.row_options = r.rows.data();
+    } else o.row_options = nullptr;
     if (o.prompt_codes) { o.prompt_codes = r.prompt_codes.data(); o.prompt_lens = r.prompt_lens.data(); }
     o.suppress_tokens = r.suppress.empty() ? nullptr : r.suppress.data();
     o.begin_suppress_tokens = r.begin_suppress.empty() ? nullptr : r.begin_suppress.data();
@@ -926,7 +1001,8 @@ void Model::gpt_finish(int* codes_host, int* ncodes_host, hipStream_t s) {
         DTTS_CHECK_HIP(hipStreamSynchronize(s));
     }
     for (int b = 0; b < B; ++b) {
-        const int done = std::max(0, std::min(hctl.step[b], G));
+        // (a row's own cap: what lies behind it is the latched row's padding; row_max_steps = G in a uniform session)
+        const int done = std::max(0, std::min(std::min(hctl.step[b], G), hctl.row_max_steps[b]));
         int n = done;
         for (int t = 0; t < done; ++t)
             if (hc[(size_t)b * Ga + t] == 8193) { n = t + 1; break; }
@@ -954,6 +1030,7 @@ void Model::gpt_generate(const float* refer, const int* refer_lens_host, int Tr,
         if (o.forced_uniforms) og.forced_uniforms = o.forced_uniforms + (size_t)g0 * G;
         if (o.forced_codes) og.forced_codes = o.forced_codes + (size_t)g0 * G;
         if (o.row_seeds) og.row_seeds = o.row_seeds + g0;
+        if (o.row_options) og.row_options = o.row_options + g0;
         if (o.prompt_codes) og.prompt_codes = o.prompt_codes + (size_t)g0 * o.prompt_stride;
         if (o.prompt_lens) og.prompt_lens = o.prompt_lens + g0;
         gpt_prefill(cond_in ? nullptr : refer + (size_t)g0 * cfg.mel_channels * Tr, refer_lens_host ? refer_lens_host + g0 : nullptr, Tr,
@@ -1033,6 +1110,7 @@ void Model::gpt_beam_generate(const float* refer, const int* refer_lens_host, in
         dtts_gpt_options og = o;
         og.sample_ids = sid.data();
         og.row_seeds = nullptr;
+        DTTS_REQUIRE(!o.row_options, "gpt_beam_generate: row_options (a beam session is uniform)");
         if (o.prompt_codes) { og.prompt_codes = pc.data(); og.prompt_lens = pl.data(); }
         gpt_prefill(cond_in ? nullptr : rf, rl.data(), Tr, tx.data(), tl.data(), Lt_max, R, og, nullptr, 0, s, cond_in ? rf : nullptr);
         while (gs_.steps < G) {
@@ -1073,8 +1151,7 @@ void Model::op_beam_step(const float* logits, int U, int V, const dtts_gpt_optio
     }
     std::vector<float> ld((size_t)G + 1);
     for (int i = 0; i <= G; ++i) ld[i] = (float)std::pow((double)i, (double)o.length_penalty);
-    std::vector<unsigned char> mask0;
-    std::vector<float> decay0;
+    const GptRowTables tabs = gpt_ctl_rows(c, o, R, V, G, G + 1);
     const size_t ni = (size_t)2 * R * G + (size_t)R * hs + 8 * GEMV_MAXB + 2 * GEMV_MAXB * 2, nf = (size_t)G + 1 + 2 * GEMV_MAXB + 2 * GEMV_MAXB + G + 1;
     ws().ensure((size_t)R * V + (size_t)V + sizeof(int) * ni + sizeof(float) * nf + sizeof(GptCtl) + 40 * 256);
     unsigned char* d_seen = static_cast<unsigned char*>(ws().raw((size_t)R * V));
@@ -1087,22 +1164,17 @@ void Model::op_beam_step(const float* logits, int U, int V, const dtts_gpt_optio
     float *d_rsc = ws().f32(GEMV_MAXB), *d_fsc = ws().f32(GEMV_MAXB), *d_ld = ws().f32((size_t)G + 1), *d_cs = ws().f32(2 * GEMV_MAXB);
     float* d_decay = ws().f32((size_t)G + 1);
     GptCtl* dctl = static_cast<GptCtl*>(ws().raw(sizeof(GptCtl)));
-    c.repetition_penalty = o.repetition_penalty;
     c.suppress_eos = o.suppress_eos;
     c.max_steps = G;
-    c.ngram = n;
     c.hist = n > 0 ? d_hist : nullptr;
     c.hist_stride = hs;
-    if (processors_mask_on(o)) {
-        mask0 = processor_token_mask(o, V);
+    if (!tabs.mask.empty()) {
         c.tok_mask = d_mask;
-        DTTS_CHECK_HIP(hipMemcpyAsync(d_mask, mask0.data(), mask0.size(), hipMemcpyHostToDevice, s));
+        DTTS_CHECK_HIP(hipMemcpyAsync(d_mask, tabs.mask.data(), tabs.mask.size(), hipMemcpyHostToDevice, s));
     }
-    if (o.exp_decay_factor > 0.0) {
-        decay0 = processor_decay_table(o.exp_decay_factor, G + 1);
+    if (!tabs.decay.empty()) {
         c.decay_mul = d_decay;
-        c.decay_n = G + 1;
-        DTTS_CHECK_HIP(hipMemcpyAsync(d_decay, decay0.data(), sizeof(float) * decay0.size(), hipMemcpyHostToDevice, s));
+        DTTS_CHECK_HIP(hipMemcpyAsync(d_decay, tabs.decay.data(), sizeof(float) * tabs.decay.size(), hipMemcpyHostToDevice, s));
     }
     auto up = [&](void* d, const void* h, size_t bytes) { DTTS_CHECK_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s)); };
     auto down = [&](void* h, const void* d, size_t bytes) { DTTS_CHECK_HIP(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s)); };
@@ -1167,11 +1239,14 @@ void Model::op_sample_logits(const float* logits, int R, int V, const int* histo
         }
     GptCtl c;
     std::memset(&c, 0, sizeof(c));
-    c.repetition_penalty = repetition_penalty;
-    c.temperature = temperature;
-    c.top_p = top_p;
-    c.top_k = top_k;
-    c.typical_mass = typical_mass;
+    for (int r = 0; r < R; ++r) {
+        c.repetition_penalty[r] = repetition_penalty;
+        c.temperature[r] = temperature;
+        c.top_p[r] = top_p;
+        c.top_k[r] = top_k;
+        c.typical_mass[r] = typical_mass;
+        c.row_max_steps[r] = 1;
+    }
     c.suppress_eos = suppress_eos;
     c.max_steps = 1;
     c.forced_u = uniforms;
@@ -1208,8 +1283,6 @@ void Model::op_sample_logits_opts(const float* logits, int R, int V, const dtts_
     DTTS_REQUIRE(R >= 1 && R <= GEMV_MAXB, "op_sample_logits_opts: rows 1..16");
     DTTS_REQUIRE(V >= 2 && V <= sampler_max_vocab(), "op_sample_logits_opts: vocabulary outside 2 .. the LDS sampler's maximum");
     DTTS_REQUIRE(logits && uniforms && tokens_host && hist_lens && fills && prompt_lens && hist_stride >= 0, "op_sample_logits_opts: operands");
-    const int n = o.no_repeat_ngram_size;
-    DTTS_REQUIRE(n >= 0 && n <= SAMP_NGRAM_MAX, "no_repeat_ngram_size outside 0 .. 16");
     const int hs = hist_stride + 1;                       // the sampler appends the drawn token behind the row's history
     std::vector<unsigned char> seen((size_t)R * V, 0);
     std::vector<int> hist((size_t)R * hs, 0);
@@ -1228,49 +1301,39 @@ void Model::op_sample_logits_opts(const float* logits, int R, int V, const dtts_
             seen[(size_t)r * V + id] = 1;
             hist[(size_t)r * hs + j] = id;
         }
+        const dtts_gpt_row_options rw = gpt_row_settings(o, r);      // (dtts_op_sample_logits_rows: the row's own record)
         c.hist_n0[r] = hist_lens[r];
-        c.nfill[r] = std::min(n, fills[r]);
+        c.nfill[r] = std::min(rw.no_repeat_ngram_size, fills[r]);
         const int fresh = cur - prompt_lens[r];           // tokens behind HF's prompt
-        c.stop_from[r] = gpt_first_stop_step(cur, -fresh, o.min_length, o.min_new_tokens);      // > 0: the sampler's step 0 is in front of it
-        const int i = fresh - o.exp_decay_start;          // the sampler's step is 0: i = step - decay_off
+        c.stop_from[r] = gpt_first_stop_step(cur, -fresh, rw.min_length, rw.min_new_tokens);      // > 0: the sampler's step 0 is in front of it
+        const int i = fresh - rw.exp_decay_start;         // the sampler's step is 0: i = step - decay_off
         c.decay_off[r] = -i;
         decay_n = std::max(decay_n, i + 1);
         c.begin_step[r] = fresh == 0 ? 0 : -1;
     }
-    ws().ensure((size_t)R * V + sizeof(int) * ((size_t)R * hs + 4 * R) + sizeof(GptCtl) + (size_t)V + sizeof(float) * decay_n + 16 * 256);
+    const GptRowTables tabs = gpt_ctl_rows(c, o, R, V, 1, decay_n);
+    const int n = tabs.ngram_max;
+    ws().ensure((size_t)R * V + sizeof(int) * ((size_t)R * hs + 4 * R) + sizeof(GptCtl) + (size_t)R * V + sizeof(float) * (size_t)R * decay_n + 16 * 256);
     unsigned char* d_seen = static_cast<unsigned char*>(ws().raw((size_t)R * V));
     int* finished = ws().i32(R);
     int* codes = ws().i32(R);
     int* d_hist = ws().i32((size_t)R * hs);
-    unsigned char* d_mask = static_cast<unsigned char*>(ws().raw((size_t)V));
-    float* d_decay = ws().f32(decay_n);
+    unsigned char* d_mask = static_cast<unsigned char*>(ws().raw((size_t)R * V));
+    float* d_decay = ws().f32((size_t)R * decay_n);
     GptCtl* dctl = static_cast<GptCtl*>(ws().raw(sizeof(GptCtl)));
-    c.repetition_penalty = o.repetition_penalty;
-    c.temperature = o.temperature;
-    c.top_p = o.top_p;
-    c.top_k = o.top_k;
-    c.typical_mass = o.typical_mass;
     c.suppress_eos = o.suppress_eos;
     c.max_steps = 1;
     c.forced_u = uniforms;
     c.u_stride = 1;
-    c.ngram = n;
     c.hist = n > 0 ? d_hist : nullptr;
     c.hist_stride = hs;
-    c.min_p = o.min_p;
-    c.eps_cutoff = o.epsilon_cutoff;
-    std::vector<unsigned char> mask0;
-    std::vector<float> decay0;
-    if (processors_mask_on(o)) {
-        mask0 = processor_token_mask(o, V);
+    if (!tabs.mask.empty()) {
         c.tok_mask = d_mask;
-        DTTS_CHECK_HIP(hipMemcpyAsync(d_mask, mask0.data(), mask0.size(), hipMemcpyHostToDevice, s));
+        DTTS_CHECK_HIP(hipMemcpyAsync(d_mask, tabs.mask.data(), tabs.mask.size(), hipMemcpyHostToDevice, s));
     }
-    if (o.exp_decay_factor > 0.0) {
-        decay0 = processor_decay_table(o.exp_decay_factor, decay_n);
+    if (!tabs.decay.empty()) {
         c.decay_mul = d_decay;
-        c.decay_n = decay_n;
-        DTTS_CHECK_HIP(hipMemcpyAsync(d_decay, decay0.data(), sizeof(float) * decay0.size(), hipMemcpyHostToDevice, s));
+        DTTS_CHECK_HIP(hipMemcpyAsync(d_decay, tabs.decay.data(), sizeof(float) * tabs.decay.size(), hipMemcpyHostToDevice, s));
     }
     DTTS_CHECK_HIP(hipMemcpyAsync(dctl, &c, sizeof(c), hipMemcpyHostToDevice, s));
     DTTS_CHECK_HIP(hipMemcpyAsync(d_seen, seen.data(), seen.size(), hipMemcpyHostToDevice, s));

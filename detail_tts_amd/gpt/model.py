@@ -135,12 +135,18 @@ class UnifiedVoice:
         nrs = int(num_return_sequences)
         assert nrs >= 1
         from .decode_options import validate_beam_options, validate_decode_options
+        # extension keyword sampling=[...] (gpt/sampling.py): one settings dict (or None) per prompt row; a missing key takes this
+        # call's own value.  The rows share the decode session, each under its own settings; with num_return_sequences they repeat.
+        hf_generate_kwargs = dict(hf_generate_kwargs)
+        sampling = hf_generate_kwargs.pop("sampling", None)
         # beam search (HF _beam_search, csrc/gpt_beam.hip): num_beams / length_penalty / early_stopping as the reference's
         # **hf_generate_kwargs carry them (gpt/model.py:542-544); every refusal is a ValueError before any launch
         beams, lp, es = validate_beam_options(hf_generate_kwargs.get("num_beams"), hf_generate_kwargs.get("length_penalty"),
                                               hf_generate_kwargs.get("early_stopping"), do_sample=hf_generate_kwargs.get("do_sample"),
                                               typical_sampling=typical_sampling or None, input_tokens=input_tokens,
                                               forced_uniforms=forced_uniforms, num_return_sequences=nrs)
+        if beams and sampling is not None:
+            raise ValueError("`sampling` cannot be combined with `num_beams` > 1 (a beam session is uniform)")
         return_scores = bool(hf_generate_kwargs.get("return_scores", False))
         if return_scores and not beams:
             raise ValueError("`return_scores` needs `num_beams` > 1 (sequences_scores are a beam search's)")
@@ -167,6 +173,18 @@ class UnifiedVoice:
             out = torch.from_numpy(seqs.reshape(B * nrs, G)[:, :int(lens.max())].astype(np.int64)).to(dev)
             return (out, self.last_scores) if return_scores else out
         B = (refer if cond is None else cond).shape[0]
+        rows = None
+        if sampling is not None:        # (ValueError before any launch)
+            from .sampling import repeat_rows, resolve_sampling
+            G0 = self.max_mel_tokens - 1 if max_generate_length is None else int(max_generate_length)
+            greedy = not do_sample
+            rows = resolve_sampling(sampling, B, top_k=1 if greedy else int(hf_generate_kwargs.get("top_k", 50) or 0), max_generate_length=G0,
+                                    decode_options=processors, num_beams=beams or None, always_rows=True,
+                                    base=dict(temperature=1.0 if greedy else hf_generate_kwargs.get("temperature", 1.0),
+                                              top_p=1.0 if greedy else hf_generate_kwargs.get("top_p", 1.0),
+                                              repetition_penalty=hf_generate_kwargs.get("repetition_penalty", 1.0),
+                                              typical_mass=float(typical_mass) if typical_sampling else 0.0))
+            rows = repeat_rows(rows, nrs if input_tokens is None or nrs == 1 else nrs * nrs)
         it = None
         if input_tokens is not None:
             it = torch.as_tensor(input_tokens).cpu().numpy().astype(np.int32)
@@ -212,11 +230,20 @@ class UnifiedVoice:
                         temperature=hf_generate_kwargs.get("temperature", 1.0))
         else:       # greedy search = the one largest logit after the repetition penalty: top-k 1 keeps exactly it (any draw picks it)
             samp = dict(top_k=1, top_p=1.0, temperature=1.0)
+        if rows is not None:
+            from .sampling import session_cap
+            Gs = session_cap(rows, G)
+            if Gs != G and forced_uniforms is not None:       # (its row stride is the call's max_generate_length)
+                raise ValueError(f"sampling: every row's `max_generate_length` is below the call's {G}, which `forced_uniforms` is shaped "
+                                 "for - keep one row at the call's length")
+            if forced is not None and max(len(row) for row in forced) > Gs:
+                raise ValueError(f"sampling: `input_tokens` are longer than the largest row cap {Gs}")
+            G = Gs
         codes, ncodes, lat = self.rt.gpt_generate(
             refer, cl, texts, seed, ids, max_generate_length=G, repetition_penalty=hf_generate_kwargs.get("repetition_penalty", 1.0),
             suppress_eos=suppress_eos, forced_uniforms=forced_uniforms, forced_codes=forced, forced_fill=-1,
             typical_mass=float(typical_mass) if typical_sampling else 0.0, **samp, **({} if prompt is None else dict(prompt_codes=prompt)),
-            **({"processors": processors} if processors else {}), cond=cond)
+            **({"processors": processors} if processors else {}), cond=cond, rows=rows)
         self.last_latents, self.last_ncodes = lat, ncodes
         n = int(ncodes.max())
         return torch.from_numpy(codes[:, :n].astype(np.int64)).to(dev)

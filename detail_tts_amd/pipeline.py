@@ -34,6 +34,8 @@ class Request:
     voice: object = None        # the request's speaker as a Voice (voice.py) in the place of refer: S = 1 or B until stage A expands it
     rate: dict = None           # the request's speed / durations / span_rates, checked (duration.check_request); None: no frame plan
     plan: object = None         # stage B: the FramePlan it ran under (duration.py), None on the x4 path
+    ready: object = None        # an event stage A's stream waits for before it reads the request's device tensors (None: they are complete)
+    rows: list = None           # the request's per-row sampling records (gpt/sampling.py resolve_sampling); None: the uniform session
 
 
 def normalize_request(text, text_length, refer, refer_lengths, seed=None, sample_ids=None, forced_codes=None, *, batch=True,
@@ -98,10 +100,22 @@ def merge_session(sts):
     return [v for st in sts for v in st.rl], [t for st in sts for t in st.texts], [v for st in sts for v in st.sids], seeds, forced
 
 
-def split_session(ncodes, sizes):
+def merge_rows(sts, samp):
+    """the per-row sampling records of one decode session, the requests' rows concatenated in order -> None when no request of it
+    carries any (the uniform session), else one record per row: a request without its own gets the call's settings written out.
+    samp: dict(top_k, max_generate_length, decode_options) of the call (resolve_sampling's keywords)."""
+    if all(st.rows is None for st in sts):
+        return None
+    from .gpt.sampling import resolve_sampling
+    return [r for st in sts for r in (st.rows if st.rows is not None else resolve_sampling(None, st.B, always_rows=True, **samp))]
+
+
+def split_session(ncodes, sizes, caps=None):
     """a session's code counts (stop token included) -> per request of `sizes` rows its n = ncodes - 1 (codes = codes[:, :-1],
-    vqvae/model_24k.py:795)"""
+    vqvae/model_24k.py:795).  caps: None or one cap per row (per-row max_generate_length): a row counts no code behind its own cap."""
     out, r0 = [], 0
+    if caps is not None:
+        ncodes = [min(int(c), int(k)) for c, k in zip(ncodes, caps)]
     for B in sizes:
         n = [int(c) - 1 for c in ncodes[r0:r0 + B]]
         if min(n) < 1:
@@ -195,22 +209,46 @@ def stage_c(rt, stream, home, mel, st, lens_t, noise_scale, chunk, *, wait=True,
     return wav, done, ticket
 
 
-def stream_stage_a(rt, sa, group, kw, token_wgs, trace=None, dims=None):
+def stream_stage_a(rt, sa, group, kw, token_wgs, trace=None, dims=None, samp=None):
     """infer_stream's stage A of one group on stream `sa` -> its Requests, with refer on the device and lat / n / a_done set.
 
     One request, or TWO requests of <= 8 utterances each as ONE decode session (<= 16 rows, per-row Philox seeds): the 308 MB of GPT
     weights stream once per token for both, and the chain of ~12 400 dependent launches is paid once.  A request of more than 16
-    rows is decoded session after session (gpt_generate).  `kw`: the sampling arguments; next(token_wgs): a session's token-kernel width."""
+    rows is decoded session after session (gpt_generate).  `kw`: the sampling arguments; next(token_wgs): a session's token-kernel width.
+    samp: None, or dict(default, top_k, max_generate_length, decode_options): a request's `sampling` (else the stream's default) is
+    resolved per request (gpt/sampling.py) and every row keeps its own settings, also next to another request's rows in one session."""
     dev = rt.device
     sts = [normalize_request(r["text"], r["text_length"], r.get("refer"), r.get("refer_lengths"), r.get("seed"), r.get("sample_ids"),
                              r.get("forced_codes"), speaker=r.get("speaker"), dims=dims, speed=r.get("speed"),
                              durations=r.get("durations"), span_rates=r.get("span_rates")) for r in group]
+    caps = None
+    if samp is not None:
+        from .gpt.sampling import resolve_sampling, session_cap
+        call = {k: v for k, v in samp.items() if k != "default"}
+        for st, r in zip(sts, group):
+            st.rows = resolve_sampling(samp["default"] if r.get("sampling") is None else r["sampling"], st.B, **call)
+        rows = merge_rows(sts, call)
+        if rows is not None:
+            from .gpt.sampling import check_forced_caps
+            r0 = 0
+            for st in sts:          # (ValueError before any launch: a row cap below the row's forced codes)
+                check_forced_caps(rows[r0:r0 + st.B], st.forced)
+                r0 += st.B
+            kw = dict(kw, rows=rows, max_generate_length=session_cap(rows, kw["max_generate_length"]))
+            caps = [r["max_generate_length"] for r in rows]
     tr = None
     if trace is not None:
         tr = dict(host_a0=time.perf_counter(), ev_a0=torch.cuda.Event(enable_timing=True), ev_a1=torch.cuda.Event(enable_timing=True))
     with torch.cuda.stream(sa):
         if tr:
             tr["ev_a0"].record(sa)
+        for st, r in zip(sts, group):
+            st.ready = r.get("ready")
+            if st.ready is not None:                       # the request's tensors were made on another stream: ordered before stage A
+                sa.wait_event(st.ready)
+                if st.voice is not None:
+                    for _, t in st.voice.members():
+                        t.record_stream(sa)
         for st in sts:
             if st.voice is not None:
                 st.voice = st.voice.for_batch(st.B)
@@ -237,7 +275,7 @@ def stream_stage_a(rt, sa, group, kw, token_wgs, trace=None, dims=None):
                 st.tr["host_a1"] = time.perf_counter()
         if session:
             _, ncodes, lat = drain_session(rt, kw["max_generate_length"], kw["suppress_eos"])      # waits for stream A only
-        split_latents(lat, sts, split_session(ncodes, [st.B for st in sts]))
+        split_latents(lat, sts, split_session(ncodes, [st.B for st in sts], caps))
         done = torch.cuda.Event()
         done.record(sa)
         for st in sts:

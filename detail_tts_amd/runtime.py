@@ -217,6 +217,41 @@ class Runtime:
         o.min_p, o.epsilon_cutoff = p.get("min_p", 0.0), p.get("epsilon_cutoff", 0.0)
         return keep
 
+    ROW_KEYS = ("top_k", "top_p", "temperature", "repetition_penalty", "typical_mass", "max_generate_length", "processors")
+
+    @classmethod
+    def _row_options(cls, o, rows, B, G=None, vocab=8194):
+        """rows (None, or B dicts of ROW_KEYS; a missing key is the reference's constant, a missing cap the call's) -> the
+        dtts_gpt_row_options array dtts_gpt_options.row_options points at.  Returns what has to live until the call returns."""
+        if rows is None:
+            return None
+        rows = list(rows)
+        if len(rows) != B:
+            raise ValueError(f"`rows` holds {len(rows)} records for {B} rows")
+        arr = (_lib.DttsGptRowOptions * B)()
+        keep = [arr]
+        for b, r in enumerate(rows):
+            stray = [k for k in r if k not in cls.ROW_KEYS]
+            if stray:
+                raise ValueError(f"rows[{b}]: unknown key `{stray[0]}`")
+            q = arr[b]
+            q.top_k = int(r.get("top_k", 50) or 0)
+            tp = r.get("top_p", 0.8)
+            q.top_p = float(tp if tp is not None else 1.0)
+            q.temperature, q.repetition_penalty = float(r.get("temperature", 0.8)), float(r.get("repetition_penalty", 2.0))
+            q.typical_mass = float(r.get("typical_mass") or 0.0)
+            q.max_generate_length = int(r.get("max_generate_length") or (G or 1))
+            if G is not None and not 1 <= q.max_generate_length <= G:
+                raise ValueError(f"rows[{b}]: `max_generate_length` {q.max_generate_length} outside 1 .. the call's {G}")
+            try:
+                keep.append(cls._processors(q, r.get("processors"), vocab=vocab))
+            except ValueError as e:
+                raise ValueError(f"rows[{b}]: {e}") from None
+        if G is not None and max(q.max_generate_length for q in arr) != G:
+            raise ValueError(f"`max_generate_length` ({G}) has to equal the largest cap of `rows`")
+        o.row_options = arr
+        return keep
+
     def _check_cond(self, cond):
         """a conditioning latent handed in: a contiguous float32 CUDA tensor [B, model_dim] of THIS model (ValueError / DttsError before the call)"""
         if cond is not None and cond.shape[1] != self.cfg["gpt"]["model_dim"]:
@@ -225,7 +260,7 @@ class Runtime:
 
     def gpt_generate(self, refer, refer_lens, texts, seed, sample_ids, max_generate_length=600, top_k=50, top_p=0.8,
                      temperature=0.8, repetition_penalty=2.0, suppress_eos=False, forced_uniforms=None, forced_codes=None, forced_fill=8193, typical_mass=0.0, token_wgs=0, prompt_codes=None,
-                     processors=None, cond=None):
+                     processors=None, cond=None, rows=None):
         """-> (codes int32 [B,G] incl. stop, ncodes [B], latents_cm float32 cuda [B,768,G]).  cond cuda [B,768] with refer = None: the
         conditioning encoder's output handed in (dtts_gpt_generate_cond), here and in gpt_prefill / gpt_generate_beams / gpt_latents /
         gpt_forward_losses.  prompt_codes ([B, m] or a list of B
@@ -253,6 +288,7 @@ class Runtime:
         o.typical_mass = float(typical_mass or 0.0)
         o.token_wgs = int(token_wgs or 0)       # 0: the handle's gpt_token_wgs option; 64 / 32: this session decodes on fewer workgroups (same bits)
         keep_proc = self._processors(o, processors)      # noqa: F841  (ValueError before any library call; the arrays live to the call's end)
+        keep_rows = self._row_options(o, rows, B, G)     # noqa: F841
         if prompt is not None:
             o.prompt_codes, o.prompt_lens, o.prompt_stride = prompt[0].ctypes.data_as(_lib.c_int_p), prompt[1].ctypes.data_as(_lib.c_int_p), prompt[0].shape[1]
         o.forced_uniforms = forced_uniforms.data_ptr() if forced_uniforms is not None else None
@@ -279,9 +315,12 @@ class Runtime:
     # decode session (include/detail_hip.h: dtts_gpt_prefill / _decode_step / _decode / _all_finished / _finish), <= 16 rows
     def gpt_prefill(self, refer, refer_lens, texts, seed, sample_ids, max_generate_length=600, top_k=50, top_p=0.8, temperature=0.8,
                     repetition_penalty=2.0, suppress_eos=False, forced_uniforms=None, forced_codes=None, forced_fill=8193, typical_mass=0.0, token_wgs=0, prompt_codes=None,
-                    processors=None, cond=None):
+                    processors=None, cond=None, rows=None):
         """conditioning encoder + prefill + first token; returns the latents tensor [B,768,G] the steps fill column by column.
         processors: as in gpt_generate (the session decodes under them; None / {}: off).
+        rows: None, or B dicts (top_k, top_p, temperature, repetition_penalty, typical_mass, max_generate_length, processors): every
+        row decodes under its own settings (dtts_gpt_options.row_options); the scalar keywords of the same names are then not read and
+        max_generate_length has to be the largest row cap.  A row is finished at its own cap.
 
         prompt_codes ([B, m] array or a list of B one-dimensional arrays; per-row lengths are an extension, the reference takes a
         rectangle): the acoustic prompt of UnifiedVoice.inference_speech_valle (gpt/model.py:546-579).  The prefill then covers
@@ -308,6 +347,7 @@ class Runtime:
         o.typical_mass = float(typical_mass or 0.0)
         o.token_wgs = int(token_wgs or 0)       # 0: the handle's gpt_token_wgs option; 64 / 32: this session decodes on fewer workgroups (same bits)
         keep_proc = self._processors(o, processors)      # noqa: F841  (ValueError before any library call; the arrays live to the call's end)
+        keep_rows = self._row_options(o, rows, B, G)     # noqa: F841
         if prompt is not None:
             o.prompt_codes, o.prompt_lens, o.prompt_stride = prompt[0].ctypes.data_as(_lib.c_int_p), prompt[1].ctypes.data_as(_lib.c_int_p), prompt[0].shape[1]
         o.forced_uniforms = forced_uniforms.data_ptr() if forced_uniforms is not None else None
@@ -1803,6 +1843,28 @@ class Runtime:
         out = np.zeros((R,), np.int32)
         self._rc(self.lib.dtts_op_sample_logits_opts(self.h, _ptr(logits), R, V, C.byref(o), hist.ctypes.data_as(_lib.c_int_p), hist.shape[1],
                                                      hl.ctypes.data_as(_lib.c_int_p), fl.ctypes.data_as(_lib.c_int_p),
+                                                     pl.ctypes.data_as(_lib.c_int_p), _ptr(uniforms), out.ctypes.data_as(_lib.c_int_p),
+                                                     self._stream()))
+        return out
+
+    def op_sample_logits_rows(self, logits, histories, fills, prompt_lens, uniforms, rows, suppress_eos=False):
+        """op_sample_logits_opts with one settings dict per logits row (dtts_op_sample_logits_rows): rows[r] = dict(top_k=, top_p=,
+        temperature=, repetition_penalty=, typical_mass=, processors=), missing keys the reference's constants.  -> token ids int32 [R]."""
+        _check(logits, "logits"); _check(uniforms, "uniforms")
+        R, V = logits.shape
+        hl = np.array([len(h) for h in histories], np.int32)
+        assert hl.shape == (R,) and len(fills) == R and len(prompt_lens) == R
+        hist = np.zeros((R, max(1, int(hl.max()))), np.int32)
+        for r, h in enumerate(histories):
+            hist[r, :len(h)] = np.asarray(h, np.int32)
+        fl, pl = np.ascontiguousarray(np.asarray(fills, np.int32)), np.ascontiguousarray(np.asarray(prompt_lens, np.int32))
+        o = _lib.DttsGptOptions()
+        self.lib.dtts_gpt_options_init(C.byref(o))
+        o.suppress_eos = int(bool(suppress_eos))
+        keep = self._row_options(o, rows, R, None, vocab=V)
+        out = np.zeros((R,), np.int32)
+        self._rc(self.lib.dtts_op_sample_logits_rows(self.h, _ptr(logits), R, V, C.byref(o), keep[0], hist.ctypes.data_as(_lib.c_int_p),
+                                                     hist.shape[1], hl.ctypes.data_as(_lib.c_int_p), fl.ctypes.data_as(_lib.c_int_p),
                                                      pl.ctypes.data_as(_lib.c_int_p), _ptr(uniforms), out.ctypes.data_as(_lib.c_int_p),
                                                      self._stream()))
         return out

@@ -154,6 +154,25 @@ class Voice:
         return cls(t["gpt"], t["diffusion"], t.get("vq"), rt=getattr(model, "rt", None) if model is not None else None)
 
     @staticmethod
+    def cat(voices):
+        """voices of the same members and widths joined along S, in order: the inverse of rows() (cat([v.rows(i) for i in ...]) holds
+        the bits of v's rows).  A copy per member (torch.cat), no kernel of the library."""
+        voices = list(voices)
+        if not voices:
+            raise ValueError("Voice.cat: no voices")
+        for v in voices:
+            if not isinstance(v, Voice):
+                raise ValueError(f"Voice.cat: a {type(v).__name__} among the voices")
+            if v.dims != voices[0].dims:
+                raise ValueError(f"Voice.cat: voices of different members or widths ({v.dims} against {voices[0].dims})")
+            if v.gpt.device != voices[0].gpt.device:
+                raise ValueError("Voice.cat: voices on different devices")
+        if len(voices) == 1:
+            return voices[0]
+        out = {k: torch.cat([getattr(v, k) for v in voices], 0).contiguous() for k, _ in voices[0].members()}
+        return Voice(out["gpt"], out["diffusion"], out.get("vq"), rt=voices[0].rt)
+
+    @staticmethod
     def blend(voices, weights, *, rt=None):
         """the convex combination sum_i w_i voice_i / sum_i w_i, member by member, on the pool kernel (weights >= 0, finite, sum > 0;
         they are normalised by their sum).  Voices of one S and one set of members; rt: the Runtime that launches (default: the one

@@ -18,6 +18,7 @@ import torch
 from ..config import COND_FREE_K, INFER_DIFFUSION_STEPS, MAX_GENERATE_LENGTH, MEL_MIN, NOISE_SCALE, REPETITION_PENALTY, TEMPERATURE, \
     TOP_P, TORCH_MEL_MAX, TRAINED_DIFFUSION_STEPS, load_config
 from ..gpt.decode_options import beam_request
+from ..gpt.sampling import check_forced_caps, repeat_rows, resolve_sampling, session_cap
 from ..gpt.candidates import check_choose, check_num_candidates, expand_sample_ids, rank_candidates
 from ..gpt.prompt import check_prompt_args, prompt_rows
 from ..gpt.model import UnifiedVoice
@@ -318,8 +319,18 @@ class SynthesizerTrn:
               forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False, return_lengths=False,
               stream_vocoder=False, vocoder_chunk=256, wait=True, check_range=True, diffusion_steps=None, sampler="p", eta=0.0,
               trunk_precision=None, num_candidates=1, choose=None, return_candidates=False, prompt_codes=None, decode_options=None,
-              speaker=None, return_alignment=False, align_options=None, speed=None, durations=None, span_rates=None):
+              speaker=None, return_alignment=False, align_options=None, speed=None, durations=None, span_rates=None, sampling=None):
         """vqvae/model_24k.py:774-810.  Returns wav [B,1,1024*n_max] (B=1 unless batch=True).
+
+        sampling: stage A's sampling settings, per row (gpt/sampling.py states the keys, ranges and refusals): None (today's path: the
+        reference's constants and the call's top_k), a dict (every row), or a list of B entries, each None or a dict of temperature,
+        top_p, top_k, repetition_penalty, typical_mass, max_generate_length, do_sample and decode_options' eight non-beam keys.  A
+        missing key takes the call's top_k / max_generate_length / decode_options, else the reference's constant.  The rows decode in
+        ONE session, each under its own settings and finished at its own cap (the device sampler reads the row's slot of its control
+        block); with num_candidates the settings repeat with the rows.  Not with num_beams > 1.  None, {} or a list of None: today's
+        launches and bits.  With forced_codes nothing is sampled here (the codes go straight to the teacher-forced pass), so the
+        settings are checked and otherwise not used; a row cap below the length of its forced row is a ValueError.  How any setting
+        sounds under a trained checkpoint is unmeasured.
 
         speed / durations / span_rates (at most one; duration.py): how fast the voice speaks.  The reference's
         DiffusionTts.timestep_independent expands the code embedding to any frame count (F.interpolate nearest,
@@ -392,6 +403,12 @@ class SynthesizerTrn:
                                dims=None if speaker is None else model_dims(self.cfg), speed=speed, durations=durations,
                                span_rates=span_rates)
         B, rl, texts, seed, sample_ids, forced_codes = st.B, st.rl, st.texts, st.seed, st.sids, st.forced
+        if sampling is not None and not batch and not hasattr(sampling, "items"):
+            sampling = sampling[:1]
+        samp_rows = resolve_sampling(sampling, B, top_k=top_k, max_generate_length=max_generate_length, decode_options=processors,
+                                     num_beams=(beam or {}).get("num_beams"))      # (ValueError: before any launch)
+        caps = None if samp_rows is None else [r["max_generate_length"] for r in samp_rows]
+        check_forced_caps(samp_rows, forced_codes)
         if prompt_codes is not None:       # (ValueError on a bad row count or code: before any launch)
             prompt_codes = prompt_rows(prompt_codes if batch else prompt_codes[:1], B)
         choose = check_choose(choose, B, ncand)
@@ -430,6 +447,9 @@ class SynthesizerTrn:
                 kw["prompt_codes"] = prompt_codes
             if processors:
                 kw["processors"] = processors
+            if samp_rows is not None:   # every row under its own settings; the session runs to its largest row cap
+                max_generate_length = kw["max_generate_length"] = session_cap(samp_rows, max_generate_length)
+                kw["rows"] = repeat_rows(samp_rows, ncand) if candidates and ncand > 1 else samp_rows
             a_refer, a_rl, a_texts, a_ids = refer, rl, texts, sample_ids
             if cond is not None:
                 kw["cond"] = cond if not (candidates and ncand > 1) else cond.repeat_interleave(ncand, 0).contiguous()
@@ -461,7 +481,7 @@ class SynthesizerTrn:
                 ncodes = ncodes[rows]
                 if ncand > 1:                                       # the winners' latent rows, gathered on the device
                     lat = lat.index_select(0, torch.as_tensor(rows, device=self.device))
-            n, = split_session(ncodes, [B])
+            n, = split_session(ncodes, [B], caps)
             if prompt_codes is None:
                 split_latents(lat, [st], [n])
             else:       # behind a prompt they are not: the reference's return_latent pass sees the generated codes alone (:796-799)
@@ -507,11 +527,14 @@ class SynthesizerTrn:
     # ------------------------------------------------------------------------------------------------------------
     def infer_stream(self, requests, noise_scale=NOISE_SCALE, *, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False,
                      vocoder_chunk=0, pair_stage_a=False, on_saturation="rerun_fp32", diffusion_steps=None, sampler="p", eta=0.0,
-                     trunk_precision=None, decode_options=None):
+                     trunk_precision=None, decode_options=None, sampling=None):
         """Batch server: `infer(..., batch=True)` over a sequence of request batches, software-pipelined over three HIP streams.
 
         requests: iterable of dicts with keys text [B,Lt], text_length [B], refer [B,128,Tr], refer_lengths [B] (or, in the place of those
-        two, speaker = a Voice: see infer) and optionally seed, speed / durations / span_rates (see infer: the request's speaking rate; its
+        two, speaker = a Voice: see infer) and optionally seed, sampling (per-row sampling settings as infer takes them: a dict or one
+        entry per row; `sampling=` of this call, None or a dict, serves the requests that carry none; requests paired into one decode
+        session keep their own rows' settings), ready (a torch.cuda.Event: stage A's stream waits for it before it reads the request's
+        device tensors - for a caller that made them on a stream of its own, as infer_many makes its voices), speed / durations / span_rates (see infer: the request's speaking rate; its
         yielded lengths are then 256 T_b),
         sample_ids, forced_codes (per-row code arrays fed through the KV-cache decode instead of sampling: tests / ragged benchmarks;
         <= 16 rows) (any B; up to 16 utterances share one decode session; with pair_stage_a two consecutive requests of <= 8 utterances
@@ -537,6 +560,12 @@ class SynthesizerTrn:
         (`num_beams` > 1) is refused with a ValueError before anything starts: a beam session cannot share its rows with another request."""
         assert on_saturation in ("rerun_fp32", "raise")
         processors, _ = beam_request(decode_options, stream=True)
+        # sampling: every request dict may carry `sampling` (as infer takes it: a dict, or one entry per row); `sampling=` here is the
+        # stream's default for requests without one (None or a dict).  Two requests paired into one session keep their own rows' settings.
+        if sampling is not None and not hasattr(sampling, "items"):
+            raise ValueError("infer_stream: the stream-wide `sampling` has to be None or a dict (a request dict takes the per-row list)")
+        samp = dict(default=sampling, top_k=top_k, max_generate_length=max_generate_length, decode_options=processors)
+        resolve_sampling(sampling, 1, **{k: v for k, v in samp.items() if k != "default"})      # (ValueError before anything starts)
         sched_ts, sampler_id, eta = sampling_args(diffusion_steps, sampler, eta)
         prec = SynthesizerTrn._check_trunk_precision(self, trunk_precision)
         dev = self.device
@@ -564,12 +593,15 @@ class SynthesizerTrn:
         # library supports exactly this split (include/detail_hip.h, "Threads"); ctypes releases the GIL inside the calls.
         def stage_a(group):
             torch.cuda.set_device(dev)
-            return stream_stage_a(self.rt, sa, group, kw, token_wgs, trace, dims=model_dims(self.cfg))
+            return stream_stage_a(self.rt, sa, group, kw, token_wgs, trace, dims=model_dims(self.cfg), samp=samp)
 
         def launch_bc(st):
             cur.wait_event(st.a_done)
             if st.refer is not None:
                 st.refer.record_stream(cur)
+            if st.ready is not None and st.voice is not None:        # (made on the caller's side stream, read here: see `ready`)
+                for _, t in st.voice.members():
+                    t.record_stream(cur)
             st.lat.record_stream(cur)
             if st.tr:
                 st.tr["host_b0"] = time.perf_counter()
@@ -638,7 +670,7 @@ class SynthesizerTrn:
                    space_id=None, max_len=160, min_len=0, rows_per_call=8, seed=None, pauses_ms=None, trim_db=-40.0, keep_ms=20,
                    fade_ms=5, stream=False, return_chunks=False, forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50,
                    suppress_eos=False, diffusion_steps=None, sampler="p", eta=0.0, trunk_precision=None, decode_options=None,
-                   noise_scale=NOISE_SCALE, speed=None):
+                   noise_scale=NOISE_SCALE, speed=None, sampling=None):
         """A text of any length in one voice -> one waveform [1,1,N] (longform.py; the reference has no long-form path).
 
         speed: one speaking rate in [0.25, 4] for every chunk (see infer; None or 1.0: today's path).  The join and the pauses are
@@ -680,19 +712,52 @@ class SynthesizerTrn:
         from .. import longform
         sampling_args(diffusion_steps, sampler, eta)
         SynthesizerTrn._check_trunk_precision(self, trunk_precision)
+        # sampling: None or ONE dict for every chunk (see infer), handed to the groups as it is; the per-row list is refused here
+        if sampling is not None and not hasattr(sampling, "items"):
+            raise ValueError("infer_long: `sampling` has to be None or a dict (the chunks are rows of one voice: one set of settings)")
+        resolve_sampling(sampling, 1, top_k=top_k, max_generate_length=max_generate_length, decode_options=decode_options)
         plan = longform.prepare(self, text, refer, refer_lengths, speaker=speaker, tokenizer=tokenizer, sentence_ids=sentence_ids,
                                 clause_ids=clause_ids, space_id=space_id, max_len=max_len, min_len=min_len, rows_per_call=rows_per_call,
                                 seed=seed, pauses_ms=pauses_ms, trim_db=trim_db, keep_ms=keep_ms, fade_ms=fade_ms, forced_codes=forced_codes,
                                 decode_options=decode_options, speed=speed)
         pieces = longform.run(self, plan, dict(noise_scale=noise_scale, max_generate_length=max_generate_length, top_k=top_k,
                                                suppress_eos=suppress_eos, diffusion_steps=diffusion_steps, sampler=sampler, eta=eta,
-                                               trunk_precision=trunk_precision, decode_options=decode_options),
+                                               trunk_precision=trunk_precision, decode_options=decode_options,
+                                               **({} if sampling is None else dict(sampling=sampling))),
                              pipelined=forced_codes is None)
         if stream:
             return pieces if return_chunks else (p for p, _ in pieces)
         got = list(pieces)
         wav = torch.cat([p for p, _ in got], 2)
         return (wav, [c for _, cs in got for c in cs]) if return_chunks else wav
+
+    def infer_many(self, utterances, *, rows_per_call=8, seed=None, sampling=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50,
+                   suppress_eos=False, decode_options=None, diffusion_steps=None, sampler="p", eta=0.0, trunk_precision=None,
+                   noise_scale=NOISE_SCALE, vocoder_chunk=0, on_saturation="rerun_fp32"):
+        """Single utterances in, single waveforms out, batched in between (many.py): the entry a server calls.
+
+        utterances: an iterable (a generator may be fed lazily: at most two requests are read ahead) of dicts with `text` (1-D ids);
+        exactly one of `speaker` (a Voice of S = 1) and `refer` ([128, Tr] or [1, 128, Tr], optionally `refer_length`); optionally
+        `sample_id` (default: the utterance's index), `sampling` (a dict, see infer; default: the call's `sampling`), `speed` and
+        `forced_codes` (1-D; all rows of a request or none).  Yields (wav [1,1,n], n) per utterance, in input order, each request's
+        rows as that request completes.
+
+        Consecutive utterances form requests of rows_per_call rows (1 .. 16; the last may be short).  A prompt mel becomes a Voice once
+        per distinct tensor object; each request carries speaker = Voice.cat(its rows' voices), the rows' own sampling settings - they
+        decode in one session, each under its own (gpt/sampling.py) - the call's ONE seed (None: drawn once) and the sample ids, and goes
+        through infer_stream as it is: request i + 1 decodes under request i's diffusion, and every row equals that row of the blocking
+        infer(batch=True, speaker=Voice.cat(...), sampling=[...], seed=, sample_ids=[...]) on the same group, cut at its length.  All of
+        a request's utterances are checked before it starts; the call's own arguments before anything starts.
+
+        Batch-wide by construction: the diffusion schedule, sampler, trunk precision and noise_scale.  Out of scope: reordering by
+        length, per-utterance seeds through stages B and C, cancellation."""
+        from .. import many
+        sampling_args(diffusion_steps, sampler, eta)
+        SynthesizerTrn._check_trunk_precision(self, trunk_precision)
+        return many.infer_many(self, utterances, rows_per_call=rows_per_call, seed=seed, sampling=sampling, noise_scale=noise_scale,
+                               max_generate_length=max_generate_length, top_k=top_k, suppress_eos=suppress_eos, decode_options=decode_options,
+                               diffusion_steps=diffusion_steps, sampler=sampler, eta=eta, trunk_precision=trunk_precision,
+                               vocoder_chunk=vocoder_chunk, on_saturation=on_saturation)
 
     def join_group(self, wav, lens, kinds, plan, base=0, complete=True):
         """one group of infer_long: its waveform batch cut and joined on the device (longform.join_group) -> (piece [n], chunk dicts)"""
@@ -703,7 +768,7 @@ class SynthesizerTrn:
 
     def infer_gpt(self, text, text_length, refer, refer_lengths, noise_scale=NOISE_SCALE, *, batch=False, seed=None, sample_ids=None,
                   forced_codes=None, max_generate_length=MAX_GENERATE_LENGTH, top_k=50, suppress_eos=False, prompt_codes=None,
-                  decode_options=None, speaker=None, return_alignment=False, align_options=None):
+                  decode_options=None, speaker=None, return_alignment=False, align_options=None, sampling=None):
         """vqvae/model_24k.py:811-847: GPT codes -> quantizer.decode + vq_ref_enc -> vq_dec -> infer_flowvae (no diffusion).
         return_alignment / align_options: as in infer - (wav, alignment) with one dictionary per row; a row whose stop token came first
         has no codes and an empty path.
@@ -717,9 +782,17 @@ class SynthesizerTrn:
         if speaker is not None and speaker.vq is None:
             raise ValueError("infer_gpt: this Voice has no vq member (it was made by a model without VQ weights)")
         B, rl, seed, sample_ids = st.B, st.rl, st.seed, st.sids
+        if sampling is not None and not batch and not hasattr(sampling, "items"):
+            sampling = sampling[:1]
+        rows = resolve_sampling(sampling, B, top_k=top_k, max_generate_length=max_generate_length, decode_options=processors,
+                                num_beams=(beam or {}).get("num_beams"))      # per-row sampling settings, see infer
+        check_forced_caps(rows, st.forced)
         pkw = {} if prompt_codes is None else dict(prompt_codes=prompt_rows(prompt_codes if batch else prompt_codes[:1], B))
         if processors:
             pkw["processors"] = processors
+        if rows is not None:
+            pkw["rows"] = rows
+            max_generate_length = session_cap(rows, max_generate_length)
         g_vq = None
         if st.voice is not None:
             voice = st.voice.for_batch(B)

@@ -56,7 +56,12 @@ def main():
     ap.add_argument("--max-len", type=int, default=160, help="with --text-file: the most characters of a chunk")
     ap.add_argument("--speed", type=float, help="the speaking rate, 0.25 .. 4.0 (infer(speed=) / infer_long(speed=): 0.8 is slower, 1.25 faster; "
                                                 "audio quality at other rates is unmeasured under a trained checkpoint)")
+    ap.add_argument("--temperature", type=float, help="stage A's sampling temperature (infer(sampling=dict(temperature=)); default 0.8)")
+    ap.add_argument("--top-p", type=float, help="stage A's nucleus mass in (0, 1] (default 0.8)")
+    ap.add_argument("--repetition-penalty", type=float, help="stage A's repetition penalty (default 2.0); how any of the three sounds "
+                                                             "under a trained checkpoint is unmeasured")
     a = ap.parse_args()
+    sampling = {k: v for k, v in (("temperature", a.temperature), ("top_p", a.top_p), ("repetition_penalty", a.repetition_penalty)) if v is not None}
     if a.voice and (a.wav or a.save_voice):
         ap.error("--voice stands in the place of the prompt: not with --wav or --save-voice")
     if a.text_file and a.timings:
@@ -84,6 +89,8 @@ def main():
     kw = dict(max_generate_length=a.max_generate_length, seed=a.seed, suppress_eos=a.synthetic or a.ckpt.startswith("synthetic"))
     if a.speed is not None:
         kw.update(speed=a.speed)
+    if sampling:
+        kw.update(sampling=sampling)
     if a.timings:
         space = None
         if a.vocab and not a.ids:
@@ -106,7 +113,7 @@ def main():
         return wav
     if a.text_file:
         a.long = dict(text=open(a.text_file, encoding="utf-8").read(), max_len=a.max_len, seed=a.seed, suppress_eos=kw["suppress_eos"],
-                      max_generate_length=a.max_generate_length, speed=a.speed)
+                      max_generate_length=a.max_generate_length, speed=a.speed, sampling=sampling or None)
         if a.pause_ms:
             a.long["pauses_ms"] = dict(zip(("sentence", "clause", "word", "hard"), a.pause_ms))
         if a.vocab:

@@ -91,6 +91,24 @@ int dtts_bind_weights(dtts_handle* h, const void* blob_dev, size_t nbytes, const
 
 /* ---- stage A: GPT autoregressive code decode ---------------------------------------------------------- */
 
+/* The sampling settings of ONE row of a decode session (dtts_gpt_options.row_options): rows of different requests share a session and
+ * each keeps its own.  Every field means what the dtts_gpt_options field of the same name means and passes the same checks; a record
+ * is complete - nothing is inherited from the scalar fields.  The device sampler runs one workgroup per row and reads the row's slot
+ * of its control block, so the settings stay uniform over the workgroup and a uniform session takes the very same code path. */
+typedef struct dtts_gpt_row_options {
+    float temperature, top_p, repetition_penalty, typical_mass, min_p, epsilon_cutoff;
+    int top_k;                      /* <= 0 disables */
+    int max_generate_length;        /* the row's own cap, 1 .. dtts_gpt_options.max_generate_length: the row is finished once it holds that
+                                     * many codes (dtts_gpt_finish: ncodes[b] <= cap, 8193 from there on), and a session whose other rows
+                                     * have stopped ends there and does not run on to the largest cap */
+    int no_repeat_ngram_size, min_length, min_new_tokens, exp_decay_start;
+    double exp_decay_factor;
+    const int* suppress_tokens;     /* HOST [n_suppress_tokens], or NULL */
+    int n_suppress_tokens;
+    const int* begin_suppress_tokens;      /* HOST [n_begin_suppress_tokens], or NULL */
+    int n_begin_suppress_tokens;
+} dtts_gpt_row_options;
+
 /* Sampling options of HF generate() as the reference calls it (vqvae/model_24k.py:782-792): do_sample, top_p 0.8,
  * temperature 0.8, repetition_penalty 2.0, max_generate_length 600; top_k is HF's effective default 50. */
 typedef struct dtts_gpt_options {
@@ -107,6 +125,12 @@ typedef struct dtts_gpt_options {
     const int* forced_codes;        /* HOST [B][max_generate_length] teacher-forced tokens (no sampling there; -1 = sample at this step:
                                      * a forced prefix = inference_speech_tortoise's input_tokens, gpt/model.py:533-537), or NULL */
     const unsigned long long* row_seeds;   /* HOST [B] per-row Philox seed (rows of different requests in one session), or NULL: `seed` */
+    const dtts_gpt_row_options* row_options;      /* HOST [B] one complete record per row, or NULL: the uniform session of the scalar fields.
+                                     * When set, the scalar fields of the same names (top_k, top_p, temperature, repetition_penalty,
+                                     * typical_mass and the processor block below) are NOT read, max_generate_length has to equal the
+                                     * largest row cap, and num_beams > 1 is refused (dtts_op_beam_step refuses row_options too; dtts_op_sample_logits_opts
+                                     * checks the rows as dtts_op_sample_logits_rows does).  Every row is checked on the host before any launch;
+                                     * the error names the row and the field.  dtts_gpt_generate hands each 16-row group its slice. */
     float typical_mass;             /* inference_speech_tortoise(typical_sampling=True, typical_mass): HF TypicalLogitsWarper, applied between
                                      * the repetition penalty and the temperature (gpt/model.py:539); 0 (or 1): off; values outside
                                      * [0, 1] or not finite are rejected */
@@ -1042,6 +1066,12 @@ int dtts_op_sample_logits_ex(dtts_handle* h, const float* logits, int R, int V, 
 int dtts_op_sample_logits_opts(dtts_handle* h, const float* logits, int R, int V, const dtts_gpt_options* opts, const int* history,
                                int hist_stride, const int* hist_lens, const int* fills, const int* prompt_lens, const float* uniforms,
                                int* tokens_out, void* stream);
+/* dtts_op_sample_logits_opts with one dtts_gpt_row_options per logits row (rows HOST [R]; max_generate_length of a record is not read:
+ * the entry draws one token).  opts supplies suppress_eos and struct_size only.  Row r draws exactly what a one-row
+ * dtts_op_sample_logits_opts launch under row r's settings draws. */
+int dtts_op_sample_logits_rows(dtts_handle* h, const float* logits, int R, int V, const dtts_gpt_options* opts,
+                               const dtts_gpt_row_options* rows, const int* history, int hist_stride, const int* hist_lens, const int* fills,
+                               const int* prompt_lens, const float* uniforms, int* tokens_out, void* stream);
 /* Host only (no device, no handle): the arithmetic the library applies for the processors above.
  * dtts_gpt_first_stop_step: min_length and min_new_tokens folded - the first decode step at which the stop token may be drawn by a row
  * whose input_ids hold input_len ids at step 0 (prefix columns, 8192 and an acoustic prompt's codes included), forced_prefix of whose

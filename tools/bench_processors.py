@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time the GPT decode at batch 8 with 234 codes under HF's remaining logits processors (profiles/processors_timing.txt).
 
-    python tools/bench_processors.py CHECKOUT LABEL ['{"no_repeat_ngram_size": 3}']
+    python tools/bench_processors.py CHECKOUT LABEL ['{"no_repeat_ngram_size": 3}'] [rows]
 
 CHECKOUT is the root of a built checkout of this project whose `detail_tts_amd` package is imported - this one, or for an A/B the
 parent commit's (which takes no processors).  One process prints one line: median / min / max over 10 timed repetitions (3 warm-ups)
@@ -9,7 +9,9 @@ of the 233 decode steps behind the prefill, host clock around the session's deco
 SHA-1 of the codes.  suppress_eos keeps every row at the full length, so the timings compare the same work; the stop-token options
 then change no code, and the others rarely do under the synthetic weights - identical hashes do not mean an option was not applied
 (tests/test_gpu_processors.py shows that each one bites).  For an A/B alternate the two checkouts, process by process, in one shell
-loop, and compare the difference of the means with the process-to-process spread of either side."""
+loop, and compare the difference of the means with the process-to-process spread of either side.
+A fourth argument `rows` decodes the same session under per-row settings (Runtime rows=: the eight rows at eight temperatures, the
+processors - pass null for none - on every row): the per-row path at the same size (profiles/row_sampling_timing.txt)."""
 import json
 import sys
 import time
@@ -36,6 +38,9 @@ if proc:
     if "exponential_decay_length_penalty" in proc:
         proc["exponential_decay_length_penalty"] = tuple(proc["exponential_decay_length_penalty"])
     kw["processors"] = proc
+if len(sys.argv) > 4 and sys.argv[4] == "rows":
+    kw["rows"] = [dict(top_k=50, top_p=0.8, temperature=0.6 + 0.05 * b, repetition_penalty=2.0, max_generate_length=G, processors=proc)
+                  for b in range(8)]
 ts, codes0 = [], None
 for rep in range(13):
     rt.gpt_prefill(refer, [200] * B, texts, 5, list(range(B)), **kw)
